@@ -24,7 +24,13 @@ stream is fed to several GPUs when throughput is all that matters.
 `value` counts input depth pixels per second with the frames already resident in HBM when the timed region starts
 (the contract of this bench); `from_pinned_host` is the same loop fed from pinned host memory (H2D inside the step).
 
-One JSON line is printed by rank 0:
+A plain run sets up, primes and warms up, times exactly --steps steps and prints one JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config).  --dump-outputs DIR then writes what the last timed step returned -- the fused
+points and colours (float32) and the sensors' transforms (float64) -- as DIR/<name>.npy (past 64 MB, a fixed seeded sample of
+the point rows); the frame that step ran depends on the arguments alone.  --full adds every other leg below; without it they
+are reported as null.
+
+With --full, the JSON line printed by rank 0 also holds:
   roofline          the kernel with the largest share of device time (the ICP correspondence kernel), timed ALONE on a quiet
                     device with HIP events on its launch stream: `achieved` = flops of the 16x16x4 fp64-MFMA tiles it
                     really multiplied (counted on the device) / duration; it is latency-bound, so `frac` is small by
@@ -33,6 +39,8 @@ One JSON line is printed by rank 0:
   roofline_targets  the north-star kernels measured in this process at BASELINE sizes: the dense all-pairs fp64-MFMA
                     correspondence sweep at 100k x 100k, the 33-D feature GEMM, and the HBM-bound operators on >= 0.75 GB;
   cpu_baseline      the same step through the CPU oracle (oracle/, C + OpenMP on the host cores), a bounded sample;
+  stages            the per-stage breakdown of one step;
+  from_pinned_host  the same loop fed from pinned host memory (see above);
   spread            median / min / max over repeated blocks of steps.
 """
 import argparse
@@ -687,6 +695,30 @@ def emulate_world(torch, world, ranks, S, F, steps, depth_in_flight=4, fused_fil
                     "frame); xGMI / RCCL time and the node's host are NOT measured -- this prices the partition's compute balance"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(out):
+    """(points, colours, transforms) of one step -> host arrays: points / colours float32, transforms float64"""
+    p, c, Ts = out
+    return {"points": p.detach().cpu().numpy().astype(np.float32), "colors": c.detach().cpu().numpy().astype(np.float32),
+            "transforms": np.asarray([np.asarray(T, dtype=np.float64) for T in Ts], dtype=np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays -> out_dir/<name>.npy.  Past DUMP_LIMIT_BYTES in all, the point rows (points and colours alike) are cut to a fixed,
+    seeded sample in their original order."""
+    total = sum(a.nbytes for a in arrays.values())
+    n = arrays["points"].shape[0]
+    if total > DUMP_LIMIT_BYTES and n:
+        row_bytes = arrays["points"][0].nbytes + arrays["colors"][0].nbytes
+        keep = max(1, (DUMP_LIMIT_BYTES - (total - n * row_bytes)) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = dict(arrays, points=arrays["points"][rows], colors=arrays["colors"][rows])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -717,7 +749,13 @@ def main():
                     "collective payloads replayed from a recorded W-rank in-process run; prints one JSON line of its own and exits")
     ap.add_argument("--emulate-ranks", default="0,1", help="ranks to measure with --emulate-world")
     ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval for the frame threads (0 = leave the default 5 ms)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: pinned-host feed, spread blocks, "
+                    "roofline, roofline_targets, per-stage breakdown, CPU baseline (a plain run times the --steps steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (fused points, colours, "
+                    "transforms) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.check and not args.full:
+        ap.error("--check compares against the CPU baseline leg: add --full")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))          # started bare (python bench.py --gpus N): this process only starts the ranks
@@ -812,6 +850,8 @@ def main():
     else:
         frames = NativeFrameStream(pipes if isinstance(pipe, NativeShardPipeline) else pipe, overlap)
 
+    last_out = [None]                               # what the most recent step returned (valid until the next steps run)
+
     def run_steps(first, count, d=None, c=None):
         """`count` steps, all finished on return; with --overlap > 1 up to that many frames are in flight"""
         d, c = (depth, rgb) if d is None else (d, c)
@@ -820,14 +860,14 @@ def main():
                 dk, ck = d[k % F], c[k % F]
                 if not dk.is_cuda and not native_loop:      # the native loop stages host frames itself (kpx_frame_step_host)
                     dk, ck = dk.to(dev, non_blocking=True), ck.to(dev, non_blocking=True)
-                fuse(pipe.step(dk, ck))
+                last_out[0] = fuse(pipe.step(dk, ck))
             return
         for k in range(first, first + count):
             if frames.full():
-                fuse(frames.pop())
+                last_out[0] = fuse(frames.pop())
             frames.submit(d[k % F], c[k % F])
         while frames.pending:
-            fuse(frames.pop())
+            last_out[0] = fuse(frames.pop())
 
     def timed(first, count, d=None, c=None):
         parallel.barrier()
@@ -850,17 +890,21 @@ def main():
         best_t = t_blk if best_t is None else min(best_t, t_blk)
         if blk >= 3 and flat >= 2:                  # at least 100 steps; two blocks in a row without a 3 % gain on the best so far
             break
-    run_steps(k_prime, args.warmup)
+    # the warm-up and timed steps start again at frame 0 of the cycle, so the frame of the last timed step does not depend on how
+    # many priming steps ran (--dump-outputs compares that step's outputs from run to run)
+    k_warm = -(-k_prime // F) * F
+    run_steps(k_warm, args.warmup)
     st0 = frames.stats() if hasattr(frames, "stats") else None
-    dt = timed(k_prime + args.warmup, args.steps)                        # THE timed region: exactly --steps steps, frames resident in HBM
+    dt = timed(k_warm + args.warmup, args.steps)                         # THE timed region: exactly --steps steps, frames resident in HBM
     st1 = frames.stats() if hasattr(frames, "stats") else None
-    k0 = k_prime + args.warmup + args.steps
+    dumped = host_outputs(last_out[0]) if (args.dump_outputs and rank == 0) else None
+    k0 = k_warm + args.warmup + args.steps
     # SURVEY 8(d)'s interval -- "depth frame resident in host pinned memory -> fused cloud on the GPU": the same loop, every frame
     # handed over in pinned host memory (native loop: staged through the slot's workspace on the frame's stream by
     # kpx_frame_step_host, no allocation; the copy of frame k+1 runs under frame k's kernels).  Same protocol as the headline: a
     # priming block of its own, the --warmup steps, exactly --steps timed steps; then both legs alternate through the spread blocks.
     dt_pin = None
-    if args.steps:
+    if args.full and args.steps:
         # its own adaptive priming (the copy path has a ramp of its own: a 20-step window right behind 30 host-fed steps was seen at
         # 1438 Mpoints/s on a box whose following blocks ran at 2000-2170): blocks of 25 until one is no faster than the best so far
         best_p, n_p = None, 0
@@ -875,7 +919,7 @@ def main():
         dt_pin = timed(k0 + n_p + args.warmup, args.steps, depth_pin, rgb_pin)
         k0 += n_p + args.warmup + args.steps
     blocks, blocks_pin = [], []
-    for b in range(args.spread_blocks):
+    for b in range(args.spread_blocks if args.full else 0):
         blocks.append(px_per_step * 20 / timed(k0, 20) / 1e6)
         blocks_pin.append(px_per_step * 20 / timed(k0 + 20, 20, depth_pin, rgb_pin) / 1e6)
         k0 += 40
@@ -887,33 +931,37 @@ def main():
         return
     ms_step = dt / args.steps * 1e3
     value = px_per_step * args.steps / dt / 1e6
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
 
     # ---- roofline of the dominant kernel, alone on the device
-    if sensor_mode and 1 in mine and 0 in mine:
-        pair = torch.stack([depth[0][mine.index(0)], depth[0][mine.index(1)]])
-        init01 = inits[0]
-    elif sensor_mode:
-        _, d01, _, i01, _ = synth.sensor_ring(S, 1, sensors=[0, 1])
-        pair, init01 = torch.as_tensor(d01[0]).to(dev), i01[0]
-    else:
-        pair, init01 = depth[0][:2].contiguous(), local_inits[0]
-    roof = quiet_kernel_roofline(torch, ops, pipe.xy, pair, init01, P)
+    roof = None
+    if args.full:
+        if sensor_mode and 1 in mine and 0 in mine:
+            pair = torch.stack([depth[0][mine.index(0)], depth[0][mine.index(1)]])
+            init01 = inits[0]
+        elif sensor_mode:
+            _, d01, _, i01, _ = synth.sensor_ring(S, 1, sensors=[0, 1])
+            pair, init01 = torch.as_tensor(d01[0]).to(dev), i01[0]
+        else:
+            pair, init01 = depth[0][:2].contiguous(), local_inits[0]
+        roof = quiet_kernel_roofline(torch, ops, pipe.xy, pair, init01, P)
     if roof is not None and last.get("icp"):
         its = [s[0] for s in last["icp"]]
         roof["registrations_per_step_on_rank0"] = len(its)
         roof["iterations_last_step"] = its
     targets = None
-    if world == 1 and not args.no_targets:
+    if args.full and world == 1 and not args.no_targets:
         targets = roofline_targets(torch, ops, quick=args.quick_targets)
 
     stages = None
-    if world == 1 and sensor_mode and not args.no_stages:
+    if args.full and world == 1 and sensor_mode and not args.no_stages:
         stages = stage_breakdown(torch, ops, pipe.xy, depth, rgb, inits, P)
     ref_stream = None
     if world == 1 and sensor_mode and args.workload == "reference-stream":
         ref_stream = reference_stream(torch, ops, pipe.xy, depth, rgb, inits, truth, max(20, min(args.steps, 100)), P.gate)
     cpu = None
-    if world == 1 and args.cpu_budget_s > 0:
+    if args.full and world == 1 and args.cpu_budget_s > 0:
         from oracle import oracle as O
         O.build()
         t_cpu, n_cpu, ref = 0.0, 0, None

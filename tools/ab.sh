@@ -13,7 +13,7 @@ mode=$1; shift
 tag=$(echo "$1" | tr -c 'A-Za-z0-9_\n' '_')
 out=gpurun_out/exp_${mode}_${tag}.txt
 : > $out
-B="python bench.py --no-targets --cpu-budget-s 0"
+B="python bench.py --full --no-targets --cpu-budget-s 0"
 line='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("   value", d["value"], "ms", d["ms_per_step"], "pinned", (d.get("from_pinned_host") or {}).get("value"), "spread", d.get("spread"))'
 bench4() { timeout -k 10 300 $B --steps 300 --warmup 20 "$@" 2>/dev/null | python -c "$line" >> $out || exit 1; }
 bench1() { timeout -k 10 300 $B --steps 200 --warmup 20 --overlap 1 --spread-blocks 0 "$@" 2>/dev/null | python -c "$line" >> $out || exit 1; }
