@@ -104,11 +104,21 @@ class PointCloud:
     # cloud, or the first get_*_bound / remove_floor); dropped whenever the points change
     _bounds = None
 
+    # every assignment of _pts (here, in _make, in utils/processing.py) goes through this setter and drops the cached bounds; in-place
+    # writes into the tensor (transform()) drop them themselves
+    @property
+    def _pts(self):
+        return self._pts_t
+
+    @_pts.setter
+    def _pts(self, t):
+        self._pts_t = t
+        self._bounds = None
+
     def __init__(self, points=None):
         self._pts = Vector3dVector(points).t
         self._col = None
         self._nrm = None
-        self._bounds = None
 
     # ---- attributes ---------------------------------------------------------------------------
     @property
@@ -118,7 +128,6 @@ class PointCloud:
     @points.setter
     def points(self, v):
         self._pts = Vector3dVector(v).t
-        self._bounds = None
 
     @property
     def colors(self):

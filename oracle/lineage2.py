@@ -318,6 +318,128 @@ def remove_statistical_outlier(pts, nb_neighbors, std_ratio):
     return keep.astype(np.int64), (mu, sigma, thr), avg
 
 
+# ------------------------------------------------------------------------------------------------ sampled-row references
+# The definitions above evaluate every point; these evaluate a given subset of query rows against the whole cloud, so a GPU result can
+# be checked at any size (one cKDTree over 5M points and a few thousand queries take seconds where the full oracle takes minutes).
+# Float64 on the promoted float32 values, neighbours ordered by (d^2, index) as in hybrid_neighbours.
+TOL_STATS = 1e-11       # relative: mu, sigma and the threshold of a8 (the GPU's parallel reduction reorders the sums)
+TOL_AVG = 1e-12         # relative: a per-point mean distance (the same k distances summed in another order)
+TOL_NORMAL = 1e-4       # radians: a normal against the float64 eigenvector, on rows whose eigengap is well conditioned
+
+
+def _kth_cut(tree, p, q, k, workers):
+    """the k nearest of the cloud for each query row q (k <= len(p)), ties at the cut broken by index: -> idx (m, k), d2 (m, k), and the
+    (k+1)-th d2 (inf where there is none)"""
+    n = len(p)
+    kq = min(n, k + 17)
+    _, idx = tree.query(q, k=kq, workers=workers)
+    idx = idx.reshape(len(q), kq)
+    d2 = ((q[:, None, :] - p[idx]) ** 2).sum(axis=2)
+    order = np.lexsort((idx, d2), axis=1)
+    idx, d2 = np.take_along_axis(idx, order, 1), np.take_along_axis(d2, order, 1)
+    # rows whose k-th distance is shared past the queried window (lattice data): all points at <= that distance, by ball query
+    wide = (d2[:, k - 1] == d2[:, -1]) if kq < n else np.zeros(len(q), bool)
+    nxt = d2[:, k].copy() if kq > k else np.full(len(q), np.inf)
+    for r in np.flatnonzero(wide):
+        ball = np.asarray(tree.query_ball_point(q[r], np.sqrt(d2[r, k - 1]) * (1 + 1e-9) + 1e-9), dtype=np.int64)
+        bd2 = ((q[r] - p[ball]) ** 2).sum(axis=1)
+        o = np.lexsort((ball, bd2))
+        idx[r, :k], d2[r, :k], nxt[r] = ball[o][:k], bd2[o][:k], bd2[o][k]
+    return idx[:, :k], d2[:, :k], nxt
+
+
+def sor_avg_at(pts, k, rows, workers=16, tree=None):
+    """a8's per-point mean distance at the given rows: mean of the sqrt(d^2) of the min(k, N) nearest, the point itself counted.
+    -> avg (m,), d_k and d_(k+1) (m,) -- the k-th distance and the next larger one (inf when there is none)"""
+    p = np.asarray(pts, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    rows = np.asarray(rows, dtype=np.int64)
+    kk = min(int(k), len(p))
+    tree = cKDTree(p) if tree is None else tree
+    _, d2, nxt = _kth_cut(tree, p, p[rows], kk, workers)
+    d = np.sqrt(d2)
+    return d.sum(axis=1) / kk, d[:, -1], np.sqrt(nxt)
+
+
+def hybrid_cov_at(pts, radius, max_nn, rows, workers=16, tree=None):
+    """KDTreeSearchParamHybrid neighbourhood of the given rows (the max_nn nearest by (d^2, index), of those d^2 < r^2) and its
+    covariance E[x x^T] - E[x] E[x]^T.  -> count (m,), cov (m, 3, 3)"""
+    p = np.asarray(pts, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    rows = np.asarray(rows, dtype=np.int64)
+    kk = min(int(max_nn), len(p))
+    tree = cKDTree(p) if tree is None else tree
+    idx, d2, _ = _kth_cut(tree, p, p[rows], kk, workers)
+    keep = d2 < radius * radius
+    cnt = keep.sum(axis=1).astype(np.int32)
+    w = keep.astype(np.float64)
+    q = p[idx]
+    c = np.maximum(cnt, 1)[:, None]
+    m = (q * w[:, :, None]).sum(axis=1) / c
+    cov = np.einsum("rk,rki,rkj->rij", w, q, q) / c[:, :, None] - m[:, :, None] * m[:, None, :]
+    return cnt, cov
+
+
+def normals_at(pts, radius, max_nn, rows, workers=16, tree=None):
+    """estimate_normals at the given rows: eigenvector of the smallest eigenvalue (up to sign); fewer than 3 neighbours: (0, 0, 1).
+    -> normals (m, 3), well (m,) -- rows with >= 3 neighbours whose smallest eigengap is > 1e-3 of the largest eigenvalue, count (m,)"""
+    cnt, cov = hybrid_cov_at(pts, radius, max_nn, rows, workers, tree)
+    w, v = np.linalg.eigh(cov)
+    nrm = v[:, :, 0].copy()
+    nrm[cnt < 3] = [0.0, 0.0, 1.0]
+    well = (cnt >= 3) & ((w[:, 1] - w[:, 0]) > 1e-3 * np.maximum(w[:, 2], 1e-30)) & (w[:, 2] > 1e-9)
+    return nrm, well, cnt
+
+
+def check_normals_f64(pts, radius, max_nn, normals, rows, workers=16, tree=None):
+    """asserts that `normals` (the library's, (N, 3)) agree with normals_at on the given rows: within TOL_NORMAL of the float64
+    eigenvector up to sign where the eigengap is well conditioned, (0, 0, 1) below 3 neighbours.  -> fraction of well rows"""
+    rows = np.asarray(rows, dtype=np.int64)
+    want, well, cnt = normals_at(pts, radius, max_nn, rows, workers, tree)
+    got = np.asarray(normals, dtype=np.float64).reshape(-1, 3)[rows]
+    sin = np.linalg.norm(np.cross(got / np.linalg.norm(got, axis=1, keepdims=True), want), axis=1)
+    assert np.all(sin[well] < TOL_NORMAL), ("normal off the float64 eigenvector", rows[well][np.argmax(sin[well])], sin[well].max())
+    assert np.all(got[cnt < 3] == [0.0, 0.0, 1.0]), "rows with fewer than 3 neighbours must get (0, 0, 1)"
+    return float(well.mean())
+
+
+def check_sor_f64(pts, k, ratio, keep, stats, avg, rows, workers=16, tree=None):
+    """asserts that one a8 result (keep indices, [mu, sigma, thr], the per-point means `avg`, all of the library's) is right:
+    1. avg at the sampled rows equals sor_avg_at to TOL_AVG;
+    2. mu, sigma and thr recomputed in float64 from the full avg (mu: the sum over avg > 0 divided by N; sigma: Bessel-corrected over
+       avg > 0 -- the library's statistic) equal stats to TOL_STATS;
+    3. keep == {i : 0 < avg_i < thr}, up to points within 1e-9 thr of the threshold;
+    4. at least a quarter of the sampled rows discriminate a wrong selection: taking the (k+1)-th neighbour instead of the k-th moves
+       their mean by more than 10 x TOL_AVG (dropping or adding a neighbour moves it by about d_k / k, more still), so such a slip
+       cannot hide inside the tolerance of 1.  (Rows whose k-th and (k+1)-th distances coincide, or differ by a float32 rounding
+       step at large k, cannot tell the two apart -- nor does it matter there.)
+    -> the number of sampled rows that discriminate a swapped neighbour"""
+    p = np.asarray(pts, dtype=np.float32).reshape(-1, 3)
+    n = len(p)
+    avg = np.asarray(avg, dtype=np.float64).reshape(-1)
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1)
+    keep = np.asarray(keep, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64)
+    assert avg.shape == (n,) and stats.shape == (3,)
+    want, dk, dk1 = sor_avg_at(p, k, rows, workers, tree)
+    err = np.abs(avg[rows] - want) / np.maximum(want, 1e-300)
+    assert np.all(err <= TOL_AVG), ("avg off the float64 k-NN mean", rows[np.argmax(err)], err.max())
+    pos = avg > 0
+    mu = avg[pos].sum() / n
+    sigma = np.sqrt(((avg[pos] - mu) ** 2).sum() / (n - 1)) if n > 1 else 0.0
+    thr = mu + ratio * sigma
+    ref = np.array([mu, sigma, thr])
+    assert np.all(np.abs(stats - ref) <= TOL_STATS * np.abs(ref)), ("statistics", stats, ref)
+    near = np.abs(avg - thr) <= 1e-9 * abs(thr)
+    want_keep = np.flatnonzero(pos & (avg < thr) & ~near)
+    got_keep = np.setdiff1d(keep, np.flatnonzero(near))
+    assert np.array_equal(got_keep, want_keep), ("keep list", np.setxor1d(got_keep, want_keep)[:10])
+    kk = min(int(k), n)
+    with np.errstate(invalid="ignore"):
+        moved = np.where(np.isfinite(dk1), (dk1 - dk) / kk, 0.0) / np.maximum(want, 1e-300)
+    sharp = int((moved > 10 * TOL_AVG).sum())
+    assert kk == n or sharp * 4 >= len(rows), ("too few rows discriminate a swapped neighbour", sharp, len(rows))
+    return sharp
+
+
 def fuse_voxel_down_sample(clouds, colours, transforms, voxel_size):
     """data.py:44-61: every sensor's cloud moved by its 4x4 (`pcd.transform(T)`: float64 points), the moved clouds stacked in order
     (`np.vstack`), `voxel_down_sample` of the stack.  The stack is float64 in the reference, so the voxel index and the means are taken

@@ -368,7 +368,9 @@ def test_sor_large_k_at_frame_density(ops, oracle, base_cloud, n, k, ratio):
     """the block-per-64-queries kernel (k > 128) where it works hardest: dense clouds, whose 27-cell blocks hold up to 2048 candidates and
     whose k-th neighbour lies near the distance the block covers (the selection window ends at the cover's high word); n = 0: the whole
     283k-point frame cloud at filter_outliers' defaults.  Keep list equal, per-point means to 1e-14 -- a selection that takes one candidate
-    too many moves a mean by ~1e-3 of itself"""
+    too many moves a mean by ~1e-3 of itself.  Then the float64 sampled-row check of oracle/lineage2.py on 2000 rows: a second lineage
+    (cKDTree) for the means, the statistics and the keep list"""
+    from oracle import lineage2 as L2
     rng = np.random.default_rng(n + k)
     p = base_cloud if n == 0 else base_cloud[rng.choice(len(base_cloud), n, replace=False)]
     gi, gs, ga = ops.sor(p, k, ratio, want_avg=True)
@@ -376,6 +378,8 @@ def test_sor_large_k_at_frame_density(ops, oracle, base_cloud, n, k, ratio):
     assert np.array_equal(npy(gi), ri)
     assert np.allclose(npy(ga), ra, rtol=1e-14, atol=0)
     assert np.allclose(npy(gs), rs, rtol=TOL_STATS, atol=0)
+    rows = np.sort(rng.choice(len(p), 2000, replace=False))
+    L2.check_sor_f64(p, k, ratio, npy(gi), npy(gs), npy(ga), rows, workers=16)
 
 
 def test_sor_block_kernel_fuzz_ties_duplicates_clusters(ops, oracle):
