@@ -199,6 +199,23 @@ size_t kpx_sor_finish_workspace_bytes(int64_t n);
 int kpx_sor_finish(const double *d_avg_sorted, const int32_t *d_order, int64_t n, double std_ratio, int32_t *keep_idx,
                    int32_t *d_count, double *d_stats, double *d_avg, void *ws, size_t ws_bytes, void *stream);
 
+/* labels = pcd.cluster_dbscan(eps, min_points) ([O3D] PointCloud::ClusterDBSCAN; the geometric stand-in for the person mask of
+ * preprocessing/filtering.py:28-95).  Neighbours: every point (itself included) with d2 < eps^2 (AC3, strict <).  A point is core
+ * iff it has >= min_points neighbours (0 or 1: every point); clusters are the connected components of the core points, numbered
+ * by their smallest core index; a non-core point takes the smallest id among its core neighbours, or -1 -- exactly the labels of
+ * Open3D's sequential loop, bit-identical run to run.  labels i32 [n]; d_nclusters = number of clusters (a negative kpx_status if
+ * the union pass gave up).  Rejects !(eps > 0) and min_points < 0.  n == 0: d_nclusters = 0. */
+size_t kpx_dbscan_workspace_bytes(int64_t n);
+int kpx_cluster_dbscan(const float *pts, int64_t n, double eps, int32_t min_points, int32_t *labels /* [n] */,
+                       int32_t *d_nclusters, void *ws, size_t ws_bytes, void *stream);
+
+/* cl, ind = pcd.remove_radius_outlier(nb_points, radius) ([O3D] PointCloud::RemoveRadiusOutliers): point i is kept iff it has
+ * more than nb_points neighbours with d2 < radius^2 (itself included; AC3, strict <).  keep_idx ascending, d_count = kept.
+ * Rejects nb_points < 1 or !(radius > 0) with Open3D's message. */
+size_t kpx_radius_outlier_workspace_bytes(int64_t n);
+int kpx_remove_radius_outlier(const float *pts, int64_t n, int32_t nb_points, double radius, int32_t *keep_idx,
+                              int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+
 /* estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (preprocessing/registration.py:9-13):
  * neighbours = up to max_nn nearest with d2 < radius^2; < 3 neighbours -> (0,0,1); else the
  * eigenvector of the smallest eigenvalue of the neighbourhood covariance.  max_nn <= KPX_NORMALS_MAX_NN (beyond KPX_NORMALS_LDS_NN the

@@ -50,6 +50,10 @@ SIGNATURES = {
     "kpx_sor_partial": (C.c_int, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "kpx_sor_finish_workspace_bytes": (_sz, [_i64]),
     "kpx_sor_finish": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_dbscan_workspace_bytes": (_sz, [_i64]),
+    "kpx_cluster_dbscan": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_radius_outlier_workspace_bytes": (_sz, [_i64]),
+    "kpx_remove_radius_outlier": (C.c_int, [_vp, _i64, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),
     "kpx_normals_workspace_bytes": (_sz, [_i64, _i32]),
     "kpx_estimate_normals": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _sz, _vp]),
     "kpx_segment_plane_workspace_bytes": (_sz, [_i64, _i32, _i32]),

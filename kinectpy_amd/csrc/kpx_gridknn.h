@@ -143,6 +143,34 @@ __device__ __forceinline__ void grid_knn_scan(const GridParams &g, const uint32_
     }
 }
 
+// Radius visitor (cluster_dbscan, remove_radius_outlier): every point with d2 < r2 (AC3, strict), in cell-sorted position order
+// within each (x, y) column, is handed to visit(sorted position, d2); visit returns true to stop the walk.  The block is the cell
+// range that holds [q - eps', q + eps'] on every axis: cell_coord is monotone, and eps' = eps (1 + 1e-9) plus 1e-12 of the
+// coordinates' magnitude lies beyond every rounding of q - p and of d2 < eps^2, so no point inside the radius is missed for any h.
+template <class Visit>
+__device__ __forceinline__ void grid_radius_scan(const GridParams &g, const uint32_t *__restrict__ cell_start,
+                                                 const float *__restrict__ spts, const double q[3], double eps, double r2, Visit &&visit)
+{
+    int lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double e = eps * (1.0 + 1e-9) + 1e-12 * (fabs(q[a]) + fabs(g.org[a]) + g.h);
+        lo[a] = cell_coord(q[a] - e, g.org[a], g.h, g.dim[a]);
+        hi[a] = cell_coord(q[a] + e, g.org[a], g.h, g.dim[a]);
+    }
+    for (int x = lo[0]; x <= hi[0]; ++x)
+        for (int y = lo[1]; y <= hi[1]; ++y) {
+            const int64_t col = ((int64_t)x * g.dim[1] + y) * g.dim[2];
+            const uint32_t s0 = cell_start[col + lo[2]], s1 = cell_start[col + hi[2] + 1];     // a column's cells are contiguous
+            for (uint32_t s = s0; s < s1; ++s) {
+                const float *p = spts + 3 * (int64_t)s;
+                const double dx = q[0] - (double)p[0], dy = q[1] - (double)p[1], dz = q[2] - (double)p[2];
+                const double d = fma(dz, dz, fma(dy, dy, dx * dx));
+                if (d < r2 && visit(s, d)) return;
+            }
+        }
+}
+
 // ---- wave-per-query neighbour selection (SOR, normals, FPFH neighbour lists) -------------------------------------------------------
 // The lanes gather the squared distances (AC3, fp64) of the points of the (2r+1)^3 cell block around the query into
 // LDS (every (x, y) column of the block is one contiguous run of the cell-sorted points: 64 columns at a time, lane c

@@ -231,6 +231,24 @@ class PointCloud:
         (p, c, n), bb = ops.select_by_index(self._attrs(), idx, False, trusted=True, want_bounds=True)
         return PointCloud._make(p, c, n, bb), idx.cpu().numpy()
 
+    def remove_radius_outlier(self, nb_points, radius, print_progress=False):
+        if nb_points < 1 or not radius > 0:
+            raise RuntimeError("Illegal input parameters, number of points and radius must be positive")
+        if not self.has_points():
+            return PointCloud(), np.zeros(0, dtype=np.int32)
+        idx = ops.remove_radius_outlier(self._pts, int(nb_points), float(radius))
+        (p, c, n), bb = ops.select_by_index(self._attrs(), idx, False, trusted=True, want_bounds=True)
+        return PointCloud._make(p, c, n, bb), idx.cpu().numpy()
+
+    def cluster_dbscan(self, eps, min_points, print_progress=False):
+        """labels int32 (N): -1 = noise, clusters 0.. numbered by their smallest core point's index (Open3D's order)"""
+        if not self.has_points():
+            return np.zeros(0, dtype=np.int32)
+        labels, cnt = ops.cluster_dbscan(self._pts, float(eps), int(min_points))
+        if int(cnt.cpu()[0]) < 0:
+            raise RuntimeError("cluster_dbscan: the union pass did not converge")
+        return labels.cpu().numpy()
+
     def segment_plane(self, distance_threshold, ransac_n, num_iterations, probability=0.99999999, seed=None):
         """seed: the reference's RANSAC is unseeded (floor_removal.py:70); ours draws from Philox with
         the given seed (None -> a fresh random seed, i.e. the reference's behaviour)."""

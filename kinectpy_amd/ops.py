@@ -358,6 +358,32 @@ def sor_finish(avg_sorted, order, std_ratio, want_avg=False):
     return idx[:k], stats, avg
 
 
+def cluster_dbscan(pts, eps, min_points):
+    """[O3D] ClusterDBSCAN: labels i32 (N) device tensor (-1 = noise), number of clusters i32 (1) device tensor (negative: a
+    kpx_status raised by the union pass).  No host sync."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    labels = torch.empty(n, dtype=torch.int32, device=pts.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_dbscan_workspace_bytes(n))
+    L.check(lib.kpx_cluster_dbscan(L.ptr(pts), n, float(eps), int(min_points), L.ptr(labels), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return labels, cnt
+
+
+def remove_radius_outlier(pts, nb_points, radius):
+    """[O3D] RemoveRadiusOutliers: keep_idx i32 (K) ascending device tensor (K = points with more than nb_points neighbours)."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    idx = torch.empty(max(n, 1), dtype=torch.int32, device=pts.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_radius_outlier_workspace_bytes(n))
+    L.check(lib.kpx_remove_radius_outlier(L.ptr(pts), n, int(nb_points), float(radius), L.ptr(idx), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    k = _count(cnt)[0]
+    return idx[:k]
+
+
 def estimate_normals(pts, radius, max_nn):
     lib = L.load()
     pts = _dev(pts, torch.float32).reshape(-1, 3)

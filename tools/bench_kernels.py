@@ -119,6 +119,14 @@ def main():
     ms, nrm = timed(lambda: ops.estimate_normals(vp[:100000].contiguous(), 70.0, 40), reps=3, warm=1)
     report("estimate_normals r=70 nn=40 on 100k (a11)", ms, 24 * 100000, n=100000)
 
+    # ---- radius-neighbourhood operators on the frame cloud (config 1's cloud, frame-typical radius)
+    fc = torch.as_tensor(synth.frame_cloud()).to(dev)
+    ms, (lab, nc) = timed(lambda: ops.cluster_dbscan(fc, 20.0, 10), reps=5, warm=2)
+    report("cluster_dbscan eps=20 min_points=10 on the frame cloud", ms, n=int(fc.shape[0]), clusters=int(nc.item()),
+           noise=int((lab < 0).sum().item()))
+    ms, kr = timed(lambda: ops.remove_radius_outlier(fc, 10, 20.0), reps=5, warm=2)
+    report("remove_radius_outlier nb_points=10 radius=20 on the frame cloud", ms, n=int(fc.shape[0]), kept=int(kr.shape[0]))
+
     # ---- config 3 as a whole: filter_outliers(voxel 10, k 20, ratio 2) + floor removal (floor_removal.py:61-73), host wall time
     from kinectpy_amd.geometry import PointCloud as _PC
     from kinectpy_amd.floor_removal import remove_floor
