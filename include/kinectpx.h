@@ -216,6 +216,38 @@ size_t kpx_radius_outlier_workspace_bytes(int64_t n);
 int kpx_remove_radius_outlier(const float *pts, int64_t n, int32_t nb_points, double radius, int32_t *keep_idx,
                               int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
 
+/* pcd.farthest_point_down_sample(k, start_index) ([O3D] PointCloud::FarthestPointDownSample): the fixed-size input of the PointNet
+ * regressor (datasets/kinect_dataset*.py, number_of_points) by farthest-point sampling instead of a uniform draw.  Open3D's loop:
+ *   dist[j] = +inf; far = start_index; for i < k: sel[i] = far; s = p[far]; max_dist = 0;
+ *     for j ascending: dist[j] = min(dist[j], d2(p[j], s)); if (dist[j] > max_dist) { max_dist = dist[j]; far = j; }
+ * d2 = AC3 in fp64 of the float32 coordinates (equal to Open3D's (dx^2 + dy^2) + dz^2 whenever every square is exact, e.g. integer
+ * millimetres).  So sample i + 1 is the smallest index among the points of largest dist, and when every dist is 0 (only duplicates
+ * left) the previous index repeats.  sel i32 [k] in selection order, repeats kept (Open3D's selected_indices; the down-sampled cloud
+ * is SelectByIndex(sel), mask semantics); cover f64 [k] (nullable) = max_dist of iteration i, the squared coverage radius after
+ * i + 1 samples (non-increasing).  Bit-identical run to run and across forms.  Rejects k > n ("Illegal number of samples") and, for
+ * k > 0, start_index >= n ("Illegal start index"); k == 0 writes nothing.  (Open3D returns a copy for k == n without the loop; the
+ * ABI runs it.)  Non-finite coordinates are outside the contract.
+ * Forms: one block of KPX_FPS_BLOCK_THREADS threads per cloud (block form; all such clouds of a batch in one launch, one barrier
+ * per sample; a point's running dist stays in registers for the first KPX_FPS_REG_N points, in LDS up to KPX_FPS_LDS_N, in the
+ * workspace beyond), or a chain of k + 1 launches over the whole device (each reduces the previous launch's per-block candidates,
+ * then updates its slice of dist).  Dispatch, from measurement (MI355X): the chain costs ~5.6 us per sample at any
+ * size, the block form 2.5 us at 8k points, 4.0 at 19k and ~0.33 us more per 1000 points beyond.  A cloud takes the block form
+ * when n <= KPX_FPS_BLOCK_MAX_N; in a batch with at least KPX_FPS_BATCH_MIN_CLOUDS clouds of KPX_FPS_BLOCK_MAX_N < n <=
+ * KPX_FPS_BATCH_BLOCK_MAX_N, those join the block launch too (they run side by side, while chains run one after another).
+ * Batch: h_* are host arrays of device pointers (h_cover may be NULL, or hold NULL entries); k and start_index hold for every
+ * cloud.  Workspace: kpx_fps_workspace_bytes(count, max n). */
+#define KPX_FPS_BLOCK_THREADS 1024
+#define KPX_FPS_REG_N 12288
+#define KPX_FPS_LDS_N 19456
+#define KPX_FPS_BLOCK_MAX_N 24576
+#define KPX_FPS_BATCH_BLOCK_MAX_N 65536
+#define KPX_FPS_BATCH_MIN_CLOUDS 4
+size_t kpx_fps_workspace_bytes(int32_t count, int64_t n_max);
+int kpx_farthest_point_sample(const float *pts, int64_t n, int32_t k, int32_t start_index, int32_t *sel /* [k] */,
+                              double *cover /* [k] or NULL */, void *ws, size_t ws_bytes, void *stream);
+int kpx_farthest_point_sample_batch(int32_t count, const float *const *h_pts, const int64_t *h_n, int32_t k, int32_t start_index,
+                                    int32_t *const *h_sel, double *const *h_cover, void *ws, size_t ws_bytes, void *stream);
+
 /* estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (preprocessing/registration.py:9-13):
  * neighbours = up to max_nn nearest with d2 < radius^2; < 3 neighbours -> (0,0,1); else the
  * eigenvector of the smallest eigenvalue of the neighbourhood covariance.  max_nn <= KPX_NORMALS_MAX_NN (beyond KPX_NORMALS_LDS_NN the

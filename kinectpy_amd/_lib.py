@@ -54,6 +54,9 @@ SIGNATURES = {
     "kpx_cluster_dbscan": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_radius_outlier_workspace_bytes": (_sz, [_i64]),
     "kpx_remove_radius_outlier": (C.c_int, [_vp, _i64, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_fps_workspace_bytes": (_sz, [_i32, _i64]),
+    "kpx_farthest_point_sample": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_farthest_point_sample_batch": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_normals_workspace_bytes": (_sz, [_i64, _i32]),
     "kpx_estimate_normals": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _sz, _vp]),
     "kpx_segment_plane_workspace_bytes": (_sz, [_i64, _i32, _i32]),

@@ -240,6 +240,22 @@ class PointCloud:
         (p, c, n), bb = ops.select_by_index(self._attrs(), idx, False, trusted=True, want_bounds=True)
         return PointCloud._make(p, c, n, bb), idx.cpu().numpy()
 
+    def farthest_point_down_sample(self, num_samples, start_index=0):
+        """[O3D] FarthestPointDownSample: the points picked by farthest-point sampling, in ascending original order (SelectByIndex's
+        mask semantics: a repeated pick -- only duplicates left -- appears once, so the cloud may hold fewer than num_samples)."""
+        n = len(self._pts) if self.has_points() else 0
+        if num_samples == 0:
+            return PointCloud()
+        if num_samples == n:
+            return copy.deepcopy(self)
+        if num_samples > n:
+            raise RuntimeError(f"Illegal number of samples: {num_samples}, must <= point size: {n}")
+        if not 0 <= start_index < n:
+            raise RuntimeError(f"Illegal start index: {start_index}, must <= point size: {n}")
+        sel, _ = ops.farthest_point_sample(self._pts, int(num_samples), int(start_index))
+        p, c, nrm = ops.select_by_index(self._attrs(), sel)
+        return PointCloud._make(p, c, nrm)
+
     def cluster_dbscan(self, eps, min_points, print_progress=False):
         """labels int32 (N): -1 = noise, clusters 0.. numbered by their smallest core point's index (Open3D's order)"""
         if not self.has_points():

@@ -384,6 +384,38 @@ def remove_radius_outlier(pts, nb_points, radius):
     return idx[:k]
 
 
+def farthest_point_sample(pts, k, start_index=0, want_cover=False):
+    """[O3D] FarthestPointDownSample's loop: sel i32 (k) device tensor in selection order (repeats kept: the previous index
+    repeats once every distance is 0), cover f64 (k) | None -- the largest running distance after each sample.  No host sync."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n, k = pts.shape[0], int(k)
+    sel = torch.empty(max(k, 1), dtype=torch.int32, device=pts.device)
+    cover = torch.empty(max(k, 1), dtype=torch.float64, device=pts.device) if want_cover else None
+    ws, wsz = L.workspace(lib.kpx_fps_workspace_bytes(1, n))
+    L.check(lib.kpx_farthest_point_sample(L.ptr(pts), n, k, int(start_index), L.ptr(sel), L.ptr(cover), ws, wsz, L.stream_ptr()))
+    return sel[:k], (cover[:k] if cover is not None else None)
+
+
+def farthest_point_sample_batch(clouds, k, start_index=0):
+    """farthest_point_sample of several clouds with one k and start_index (clouds up to KPX_FPS_BLOCK_MAX_N points share one
+    launch).  Returns sel i32 (count, k), cover f64 (count, k) device tensors."""
+    lib = L.load()
+    clouds = [_dev(p, torch.float32).reshape(-1, 3) for p in clouds]
+    cnt, k = len(clouds), int(k)
+    dev = clouds[0].device if cnt else L.device()
+    sel = torch.empty((cnt, max(k, 1)), dtype=torch.int32, device=dev)
+    cover = torch.empty((cnt, max(k, 1)), dtype=torch.float64, device=dev)
+    if cnt == 0:
+        return sel[:, :k], cover[:, :k]
+    n_arr = np.array([p.shape[0] for p in clouds], dtype=np.int64)
+    arr = lambda ts: C.cast((C.c_void_p * cnt)(*[t.data_ptr() for t in ts]), C.c_void_p)
+    ws, wsz = L.workspace(lib.kpx_fps_workspace_bytes(cnt, int(n_arr.max())))
+    L.check(lib.kpx_farthest_point_sample_batch(cnt, arr(clouds), n_arr.ctypes.data_as(C.c_void_p), k, int(start_index), arr(sel),
+                                                arr(cover), ws, wsz, L.stream_ptr()))
+    return sel[:, :k], cover[:, :k]
+
+
 def estimate_normals(pts, radius, max_nn):
     lib = L.load()
     pts = _dev(pts, torch.float32).reshape(-1, 3)

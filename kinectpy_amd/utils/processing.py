@@ -39,6 +39,17 @@ def select_points_randomly(pointcloud, number_of_points, seed=None):
     return pts.cpu().numpy().astype(np.float64)
 
 
+def select_points_farthest(pointcloud, number_of_points, start_index=0):
+    """The farthest-point counterpart of select_points_randomly: `number_of_points` points of the cloud picked by Open3D's
+    farthest-point loop, as a float64 (k,3) array in selection order -- exactly k rows, a repeated pick (only duplicates left)
+    kept, as a fixed-size network input needs."""
+    sel, _ = ops.farthest_point_sample(pointcloud._pts, int(number_of_points), int(start_index))
+    if sel.numel() == 0:
+        return np.zeros((0, 3), dtype=np.float64)
+    pts = ops.select_by_index([pointcloud._pts], sel, trusted=True)[0]       # KPX_SELECT_GATHER: row i = point sel[i], repeats kept
+    return pts.cpu().numpy().astype(np.float64)
+
+
 def scale_point_cloud(pcd, xs=0.001, ys=0.001, zs=0.001):
     """utils/processing.py:185-197"""
     out = copy.deepcopy(pcd)

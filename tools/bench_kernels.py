@@ -127,6 +127,22 @@ def main():
     ms, kr = timed(lambda: ops.remove_radius_outlier(fc, 10, 20.0), reps=5, warm=2)
     report("remove_radius_outlier nb_points=10 radius=20 on the frame cloud", ms, n=int(fc.shape[0]), kept=int(kr.shape[0]))
 
+    # ---- farthest-point sampling (the PointNet input): the chain on the frame cloud and on 30k points, the block form on 19456 points
+    # and on a batch of 64 x 30k (one launch)
+    for k in (1024, 4096):
+        ms, _ = timed(lambda: ops.farthest_point_sample(fc, k, 0, True), reps=20, warm=2)
+        report(f"farthest_point_sample k={k} on the frame cloud (chain)", ms, n=int(fc.shape[0]), us_per_sample=round(1e3 * ms / k, 3))
+    c30 = fc[torch.as_tensor(np.random.default_rng(0).choice(int(fc.shape[0]), 30000, replace=False)).to(dev)].contiguous()
+    ms, _ = timed(lambda: ops.farthest_point_sample(c30, 2048, 0, True), reps=20, warm=2)
+    report("farthest_point_sample k=2048 on 30k points (chain: above KPX_FPS_BLOCK_MAX_N)", ms, n=30000, us_per_sample=round(1e3 * ms / 2048, 3))
+    c19 = c30[:19456].contiguous()
+    ms, _ = timed(lambda: ops.farthest_point_sample(c19, 2048, 0, True), reps=20, warm=2)
+    report("farthest_point_sample k=2048 on 19456 points (block, every point on chip)", ms, n=19456, us_per_sample=round(1e3 * ms / 2048, 3))
+    b64 = [fc[torch.as_tensor(np.random.default_rng(s).choice(int(fc.shape[0]), 30000, replace=False)).to(dev)].contiguous() for s in range(64)]
+    ms, _ = timed(lambda: ops.farthest_point_sample_batch(b64, 2048, 0), reps=20, warm=2)
+    report("farthest_point_sample_batch 64 x 30k, k=2048 (block, one launch)", ms, n=30000, count=64,
+           us_per_sample=round(1e3 * ms / 2048, 3), us_per_cloud_sample=round(1e3 * ms / 2048 / 64, 4))
+
     # ---- config 3 as a whole: filter_outliers(voxel 10, k 20, ratio 2) + floor removal (floor_removal.py:61-73), host wall time
     from kinectpy_amd.geometry import PointCloud as _PC
     from kinectpy_amd.floor_removal import remove_floor
