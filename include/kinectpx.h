@@ -257,6 +257,11 @@ int kpx_farthest_point_sample_batch(int32_t count, const float *const *h_pts, co
 size_t kpx_normals_workspace_bytes(int64_t n, int32_t max_nn);
 int kpx_estimate_normals(const float *pts, int64_t n, double radius, int32_t max_nn, float *normals,
                          void *ws, size_t ws_bytes, void *stream);
+/* PointCloud.estimate_covariances(search_param): per point the covariance of the estimate_normals neighbourhood (same search,
+ * same ties), E[x x^T] - mu mu^T with divisor m; < 3 neighbours -> the identity.  cov f64 [n][9] (symmetric, row-major). */
+size_t kpx_covariances_workspace_bytes(int64_t n, int32_t max_nn);
+int kpx_estimate_covariances(const float *pts, int64_t n, double radius, int32_t max_nn, double *cov,
+                             void *ws, size_t ws_bytes, void *stream);
 
 /* a21: PointCloud.segment_plane(distance_threshold, ransac_n, num_iterations) (floor_removal.py:70).
  * Seeded (Philox4x32-10) so results are reproducible; the reference's is unseeded.
@@ -402,6 +407,21 @@ int kpx_colored_icp(const float *src, const float *src_colors, int64_t n_src, co
                     const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist, const double *h_init,
                     double lambda_geometric, int32_t max_iteration, double relative_fitness, double relative_rmse,
                     int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes, void *stream);
+
+/* Generalized ICP ([O3D] registration_generalized_icp with TransformationEstimationForGeneralizedICP, L2 loss).
+ * kpx_gicp_covariances = InitializePointCloudForGeneralizedICP from normals: C = R_x diag(epsilon, 1, 1) R_x^T,
+ *   R_x = GetRotationFromE1ToX(n) evaluated literally (identity when n.x < -0.99, Open3D's branch).  cov f64 [n][9].
+ * kpx_rotate_covariances: out = R C R^T (R = rotation of the row-major host 4x4 h_T), in == out allowed.
+ * kpx_generalized_icp: the kpx_icp loop (correspondences, fitness, inlier rmse, convergence; same argument checks and
+ *   d_result layout) with the plane-to-plane update: per pair M = Ct + R Cs R^T, W = M^{-1/2}, three rows (s x w_i, w_i | w_i.(s - t)).
+ *   Covariances f64 [n][9] in each cloud's own frame.  A pair with a singular M adds nothing, and a singular 6x6 system gives the
+ *   identity update (Open3D yields NaN in both cases).  idx / d2 optional as in kpx_icp. */
+int kpx_gicp_covariances(const float *normals, int64_t n, double epsilon, double *cov, void *stream);
+int kpx_rotate_covariances(const double *cov, int64_t n, const double *h_T, double *out, void *stream);
+size_t kpx_generalized_icp_workspace_bytes(int64_t n_src, int64_t n_tgt);
+int kpx_generalized_icp(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov, int64_t n_tgt,
+                        double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                        int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream);
 
 /* fuse_skeletons_gradient (utils/skeleton_fusion.py:21-74), SURVEY 8f rank 4: gradient- and centroid-weighted average of the
  * joints seen by three cameras.  skeletons f64 [cams][frames][joints][3] on the device; the first initial_frame (reference: 20)

@@ -600,19 +600,86 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
 //        2 = coloured ICP ([O3D] TransformationEstimationForColoredICP): the normal equations hold a geometric row
 //            sqrt(lambda) (s x n, n | (s - t).n) and a photometric row sqrt(1 - lambda) (s x g', g' | I_s - (I_t + g.(s' - t))),
 //            s' = s projected onto the target's tangent plane, g the target's colour gradient, g' = -(I - n n^T) g
+//        3 = generalized ICP (GicpTerms, the nn_merge_kernel<GicpTerms> instantiation only): three rows per pair, see gicp_pair_rows
+// The kernel is a template on its pair term: nn_merge_kernel<ColorTerms> serves modes -2..2, nn_merge_kernel<GicpTerms> mode 3 (the
+// 3x3 eigen-solve of a GICP pair never enters the instantiation every point-to-point / point-to-plane registration runs).
 struct ColorTerms {
+    static constexpr bool kGicp = false;
     const float *src_col, *tgt_col;
     const double *tgt_grad;
     double sqrt_lg, sqrt_lp;
 };
+struct GicpTerms {
+    static constexpr bool kGicp = true;
+    const double *src_cov, *tgt_cov;       // [n_src][9], [n_tgt][9] row-major, in the ORIGINAL source frame / the target's frame
+};
+constexpr int kModeGicp = 3;
+
+// [O3D] TransformationEstimationForGeneralizedICP, one correspondence (s = T src_i in fp64, t its target partner):
+//   Cs' = R Cs R^T (R = rotation of the current T: Open3D rotates the source's covariances with every PointCloud::Transform),
+//   M = Ct + Cs', W = M^{-1/2} = V diag(lambda^{-1/2}) V^T (sym3_eigen), d = s - t,
+//   rows i = 0..2: residual r_i = w_i . d, Jacobian J_i = (s x w_i, w_i) with w_i row i of W,
+// accumulated into the point-to-plane slots 17..43 (J^T J upper triangle, J^T r); the update is the point-to-plane solve.
+// Deviation: Open3D yields NaN when M is singular (e.g. two exactly flat neighbourhoods with aligned normals, raw covariances);
+// here a pair whose smallest eigenvalue of M is <= 0, or whose W is not finite, adds nothing to slots 17..43.
+__device__ __forceinline__ void gicp_pair_rows(const double *__restrict__ T, const double *__restrict__ Cs, const double *__restrict__ Ct,
+                                               const double s[3], const double t[3], double acc[kAcc])
+{
+    double RC[9];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) RC[3 * p + q] = T[4 * p] * Cs[q] + T[4 * p + 1] * Cs[3 + q] + T[4 * p + 2] * Cs[6 + q];
+    double M[6];
+    {
+        int e = 0;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p; q < 3; ++q)
+                M[e++] = (RC[3 * p] * T[4 * q] + RC[3 * p + 1] * T[4 * q + 1] + RC[3 * p + 2] * T[4 * q + 2]) + Ct[3 * p + q];
+    }
+    double lam[3], V[9];
+    sym3_eigen(M, lam, V);
+    if (!(lam[0] > 0.0)) return;
+    double il[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) il[c] = 1.0 / sqrt(lam[c]);
+    double W[9];
+    bool finite = true;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            W[3 * p + q] = V[3 * p] * il[0] * V[3 * q] + V[3 * p + 1] * il[1] * V[3 * q + 1] + V[3 * p + 2] * il[2] * V[3 * q + 2];
+            finite = finite && isfinite(W[3 * p + q]);
+        }
+    if (!finite) return;
+    const double d[3] = { s[0] - t[0], s[1] - t[1], s[2] - t[2] };
+#pragma unroll
+    for (int row = 0; row < 3; ++row) {
+        const double wx = W[3 * row], wy = W[3 * row + 1], wz = W[3 * row + 2];
+        const double r = wx * d[0] + wy * d[1] + wz * d[2];
+        const double J[6] = { s[1] * wz - s[2] * wy, s[2] * wx - s[0] * wz, s[0] * wy - s[1] * wx, wx, wy, wz };
+        int q = 17;
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+            for (int c = p; c < 6; ++c) acc[q++] += J[p] * J[c];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) acc[38 + p] += J[p] * r;
+    }
+}
+
 constexpr int kMergeThreads = 64;
+template <class Terms>
 __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__restrict__ src, int64_t n, const float *__restrict__ tgt,
                                                        const float *__restrict__ tn, const double *__restrict__ T,
                                                        const int32_t *__restrict__ done, const double *__restrict__ part_val,
                                                        const int32_t *__restrict__ part_idx, int splits, double max_d2, int mode,
                                                        int32_t *__restrict__ idx_out, double *__restrict__ d2_out,
                                                        double *__restrict__ val_out, double *__restrict__ part_acc,
-                                                       const int32_t *__restrict__ cand_cnt, const int32_t *__restrict__ cand, ColorTerms ct)
+                                                       const int32_t *__restrict__ cand_cnt, const int32_t *__restrict__ cand, Terms ct)
 {
     if (done && *done) return;
     __shared__ double sh[kAcc][kMergeThreads + 1];
@@ -670,7 +737,9 @@ __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
                     for (int q = 0; q < 3; ++q) acc[8 + 3 * p + q] = t[p] * s[q];
-                if (mode == 1) {
+                if constexpr (Terms::kGicp) {
+                    gicp_pair_rows(T, ct.src_cov + 9 * i, ct.tgt_cov + 9 * (int64_t)bj, s, t, acc);
+                } else if (mode == 1) {
                     const float *np_ = tn + 3 * (int64_t)bj;
                     double nx = np_[0], ny = np_[1], nz = np_[2];
                     double r = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
@@ -2261,9 +2330,10 @@ static int nn_prep(const float *tgt, const NnPlan &p, const NnBuffers &b, hipStr
 
 // One correspondence search.  have_prev: b.idx_cur holds the partners of the previous search (bound from them),
 // otherwise a seed sweep over every 64th target tile provides the bound.
+template <class Terms = ColorTerms>
 static int nn_search_launch(const float *src, const float *tgt, const float *tn, const NnPlan &p, const NnBuffers &b,
                             const double *T, const int32_t *done, bool have_prev, bool allow_screen, double max_d2, int mode, hipStream_t st,
-                            ColorTerms ct = ColorTerms{})
+                            Terms ct = Terms{})
 {
     const int64_t n = p.n_src;
     const dim3 thr(256);
@@ -2277,7 +2347,7 @@ static int nn_search_launch(const float *src, const float *tgt, const float *tn,
                                p.l_groups, b.sort_t.bbox, done, b.A64, b.K64, b.init_val, b.init_idx, b.row_of, b.part_val, b.part_idx,
                                prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr);
         }
-        hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done,
+        hipLaunchKernelGGL(nn_merge_kernel<Terms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done,
                            b.part_val, b.part_idx, 1, max_d2, mode, b.idx_cur, b.d2_cur, (double *)nullptr, b.part_acc,
                            (const int32_t *)nullptr, (const int32_t *)nullptr, ct);
         KPX_LAUNCH_CHECK();
@@ -2295,7 +2365,7 @@ static int nn_search_launch(const float *src, const float *tgt, const float *tn,
         }
         hipLaunchKernelGGL(nn_overflow_kernel, dim3(1024), thr, 0, st, src, n, tgt,
                            p.n_tgt, T, done, b.cand_cnt, b.cand, b.overflow);
-        hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.init_val, b.init_idx, 1,
+        hipLaunchKernelGGL(nn_merge_kernel<Terms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.init_val, b.init_idx, 1,
                            max_d2, mode, b.idx_cur, b.d2_cur, (double *)nullptr, b.part_acc, b.cand_cnt, b.cand, ct);
         KPX_LAUNCH_CHECK();
         return KPX_OK;
@@ -2308,7 +2378,7 @@ static int nn_search_launch(const float *src, const float *tgt, const float *tn,
     if (!have_prev) {
         hipLaunchKernelGGL(nn_mfma_kernel<false>, dim3(p.row_blocks, 1), thr, 0, st, n, b.Bseed, b.colSeed, (int32_t)p.seed_tiles_pad,
                            done, b.A64, b.K64, (const double *)nullptr, (const int32_t *)nullptr, b.part_val, b.part_idx, rperm);
-        hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx, 1,
+        hipLaunchKernelGGL(nn_merge_kernel<ColorTerms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx, 1,
                            0.0, -2, b.init_idx, (double *)nullptr, b.init_val, b.part_acc, (const int32_t *)nullptr, (const int32_t *)nullptr,
                            ColorTerms{});
     }
@@ -2323,7 +2393,7 @@ static int nn_search_launch(const float *src, const float *tgt, const float *tn,
         hipLaunchKernelGGL(nn_mfma_kernel<false>, dim3(p.row_blocks, p.splits), thr, 0, st, n, b.B, b.colB, p.tiles_per_split, done, b.A64, b.K64,
                            b.init_val, b.init_idx, b.part_val, b.part_idx, rperm);
     }
-    hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx,
+    hipLaunchKernelGGL(nn_merge_kernel<Terms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx,
                        p.splits, max_d2, mode, b.idx_cur, b.d2_cur, (double *)nullptr, b.part_acc, (const int32_t *)nullptr,
                        (const int32_t *)nullptr, ct);
     KPX_LAUNCH_CHECK();
@@ -2545,6 +2615,125 @@ KPX_EXPORT int kpx_colored_icp(const float *src, const float *src_colors, int64_
             if (h_done) break;
         }
     }
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+// ---- generalized ICP ----------------------------------------------------------------------------------------------------------
+// [O3D] registration_generalized_icp = the registration_icp loop (same correspondences, fitness, inlier rmse, convergence test and
+// iteration count) with TransformationEstimationForGeneralizedICP as the update (gicp_pair_rows; L2 loss only).  Search -> sums ->
+// solve per iteration as kpx_colored_icp (nn_merge_kernel<GicpTerms> + icp_solve_kernel in its point-to-plane mode), on whichever
+// engine kpx_nn_engine selected; the all-pairs engine screens from the third search on, as kpx_icp does.  The covariances come from
+// kpx_estimate_covariances or kpx_gicp_covariances; the source's stay in the original frame and are rotated by the current T per pair.
+// An iteration whose 6x6 system is singular takes the identity update (solve6_ldlt), as a pair with a singular M adds nothing.
+KPX_EXPORT size_t kpx_generalized_icp_workspace_bytes(int64_t n_src, int64_t n_tgt) { return kpx_icp_workspace_bytes(n_src, n_tgt); }
+KPX_EXPORT int kpx_generalized_icp(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov, int64_t n_tgt,
+                                   double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                                   int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(src_cov && tgt_cov, "kpx_generalized_icp: covariances of both clouds are required");
+    KPX_REQUIRE(max_dist > 0.0, "Invalid max_correspondence_distance.");          // [O3D]
+    KPX_REQUIRE(n_src >= 1 && n_tgt >= 1 && max_iteration >= 0, "kpx_generalized_icp: empty cloud");
+    KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_generalized_icp: cloud too large");
+    KPX_REQUIRE(src && tgt && h_init && d_result && ws, "kpx_generalized_icp: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    NnPlan p = nn_plan(n_src, n_tgt);
+    NnBuffers b;
+    nn_carve(a, n_src, n_tgt, p, &b);
+    KPX_ARENA_CHECK(a);
+    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
+    int rc = nn_prep(tgt, p, b, st);
+    if (rc) return rc;
+    rc = nn_prep_source(src, p, b, st);
+    if (rc) return rc;
+    const GicpTerms gt{ src_cov, tgt_cov };
+    const double md2 = max_dist * max_dist;
+    for (int k = 0; k <= max_iteration; ++k) {
+        rc = nn_search_launch(src, tgt, nullptr, p, b, b.state->T, &b.state->done, k > 0, k >= 2, md2, kModeGicp, st, gt);
+        if (rc) return rc;
+        hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kSolveThreads), 0, st, b.part_acc, (int)cdiv(n_src, kMergeThreads), n_src, 1, k,
+                           max_iteration, relative_fitness, relative_rmse, b.state, d_result);
+        if (poll_interval > 0 && (k + 1) % poll_interval == 0 && k < max_iteration) {
+            int32_t h_done = 0;
+            KPX_HIP(hipMemcpyAsync(&h_done, &b.state->done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            KPX_HIP(hipStreamSynchronize(st));
+            if (h_done) break;
+        }
+    }
+    if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+// [O3D] InitializePointCloudForGeneralizedICP, covariances from normals: C = R_x diag(eps, 1, 1) R_x^T with R_x = GetRotationFromE1ToX(n),
+// evaluated literally -- v = e1 x n, c = e1 . n; c < -0.99: R_x = I (Open3D's branch, kept); else R_x = I + [v]x + [v]x^2 / (1 + c).
+// One thread per point, fp64 from the float32 normal.
+__global__ __launch_bounds__(256) void gicp_covariances_kernel(const float *__restrict__ normals, int64_t n, double eps, double *__restrict__ cov)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double nx = normals[3 * i], ny = normals[3 * i + 1], nz = normals[3 * i + 2];
+    double R[9] = { 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0 };
+    const double c = nx;
+    if (!(c < -0.99)) {
+        const double v0 = 0.0, v1 = -nz, v2 = ny;                        // e1 x n
+        const double S[9] = { 0.0, -v2, v1, v2, 0.0, -v0, -v1, v0, 0.0 };
+        const double f = 1.0 / (1.0 + c);
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const double s2 = S[3 * p] * S[q] + S[3 * p + 1] * S[3 + q] + S[3 * p + 2] * S[6 + q];
+                R[3 * p + q] = (R[3 * p + q] + S[3 * p + q]) + s2 * f;
+            }
+    }
+    const double dg[3] = { eps, 1.0, 1.0 };
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            cov[9 * i + 3 * p + q] = R[3 * p] * dg[0] * R[3 * q] + R[3 * p + 1] * dg[1] * R[3 * q + 1] + R[3 * p + 2] * dg[2] * R[3 * q + 2];
+}
+struct Rot9 {
+    double r[9];
+};
+// out = R C R^T per point (PointCloud.transform with covariances); in == out allowed
+__global__ __launch_bounds__(256) void rotate_covariances_kernel(const double *__restrict__ cov, int64_t n, Rot9 R, double *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double C[9], RC[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) C[e] = cov[9 * i + e];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) RC[3 * p + q] = R.r[3 * p] * C[q] + R.r[3 * p + 1] * C[3 + q] + R.r[3 * p + 2] * C[6 + q];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) out[9 * i + 3 * p + q] = RC[3 * p] * R.r[3 * q] + RC[3 * p + 1] * R.r[3 * q + 1] + RC[3 * p + 2] * R.r[3 * q + 2];
+}
+KPX_EXPORT int kpx_gicp_covariances(const float *normals, int64_t n, double epsilon, double *cov, void *stream)
+{
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_gicp_covariances: bad size");
+    if (n == 0) return KPX_OK;
+    KPX_REQUIRE(normals && cov, "kpx_gicp_covariances: null pointer");
+    hipLaunchKernelGGL(gicp_covariances_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, normals, n, epsilon, cov);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+KPX_EXPORT int kpx_rotate_covariances(const double *cov, int64_t n, const double *h_T, double *out, void *stream)
+{
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_rotate_covariances: bad size");
+    if (n == 0) return KPX_OK;
+    KPX_REQUIRE(cov && h_T && out, "kpx_rotate_covariances: null pointer");
+    Rot9 R;
+    for (int p = 0; p < 3; ++p)
+        for (int q = 0; q < 3; ++q) R.r[3 * p + q] = h_T[4 * p + q];
+    hipLaunchKernelGGL(rotate_covariances_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, cov, n, R, out);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -1201,9 +1201,23 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
 }
 
 // ---- estimate_normals ---------------------------------------------------------------------------------
+// the symmetric 3x3 (xx, xy, xz, yy, yz, zz) as 9 row-major doubles; nullptr: the identity ([O3D] estimate_covariances, < 3 neighbours)
+__device__ __forceinline__ void store_cov9(double *o, const double *cov)
+{
+    if (!cov) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) o[e] = (e % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
+    o[0] = cov[0]; o[1] = cov[1]; o[2] = cov[2];
+    o[3] = cov[1]; o[4] = cov[3]; o[5] = cov[4];
+    o[6] = cov[2]; o[7] = cov[4]; o[8] = cov[5];
+}
+// COV: write the neighbourhood covariance (estimate_covariances) to out_cov [n][9] instead of the normal; < 3 neighbours -> identity
+template <bool COV>
 __global__ void normals_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
                                const float *__restrict__ spts, const int32_t *__restrict__ sidx, const float *__restrict__ pts,
-                               int64_t n, int k, double r2, float *__restrict__ normals, const int32_t *__restrict__ list,
+                               int64_t n, int k, double r2, float *__restrict__ normals, double *__restrict__ out_cov, const int32_t *__restrict__ list,
                                const int32_t *__restrict__ list_count, double *__restrict__ gheap, int32_t *__restrict__ gix)
 {
     // gheap / gix != NULL (max_nn beyond what LDS holds): the thread's (d^2, index) heap lives in the workspace
@@ -1233,13 +1247,18 @@ __global__ void normals_kernel(const GridParams *__restrict__ gp, const uint32_t
             for (int q = 0; q < 9; ++q) c[q] /= m;
             double cov[6] = { c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2],
                               c[6] - c[1] * c[1], c[7] - c[1] * c[2], c[8] - c[2] * c[2] };
+            if constexpr (COV) {
+                store_cov9(out_cov + 9 * me, cov);
+                continue;
+            }
             double w[3], V[9];
             sym3_eigen(cov, w, V);
             nx = V[0]; ny = V[3]; nz = V[6];                       // eigenvector of the smallest eigenvalue
             double nn = sqrt(nx * nx + ny * ny + nz * nz);
             if (nn > 0.0) { nx /= nn; ny /= nn; nz /= nn; } else { nx = 0.0; ny = 0.0; nz = 1.0; }
         }
-        normals[3 * me] = (float)nx; normals[3 * me + 1] = (float)ny; normals[3 * me + 2] = (float)nz;
+        if constexpr (COV) store_cov9(out_cov + 9 * me, nullptr);          // (< 3 neighbours)
+        else { normals[3 * me] = (float)nx; normals[3 * me + 1] = (float)ny; normals[3 * me + 2] = (float)nz; }
     }
 }
 
@@ -1292,14 +1311,29 @@ __global__ __launch_bounds__(WAVES * 64) void normals_wave_kernel(const GridPara
 }
 // sums -> covariance -> eigenvector of the smallest eigenvalue; one thread per (cell-sorted) query.  count < 0: the
 // query was handed to the heap walk, which writes its normal itself.
+template <bool COV>
 __global__ __launch_bounds__(256) void normals_eigen_kernel(const double *__restrict__ covbuf, const int32_t *__restrict__ sidx, int64_t n,
-                                                            float *__restrict__ normals)
+                                                            float *__restrict__ normals, double *__restrict__ out_cov)
 {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const double *in = covbuf + 10 * s;
     const double m = in[9];
     if (m < 0.0) return;
+    if constexpr (COV) {
+        double *o = out_cov + 9 * (int64_t)sidx[s];
+        if (m >= 3.0) {
+            double c[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) c[q] = in[q] / m;
+            const double cov[6] = { c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2],
+                                    c[6] - c[1] * c[1], c[7] - c[1] * c[2], c[8] - c[2] * c[2] };
+            store_cov9(o, cov);
+        } else {
+            store_cov9(o, nullptr);
+        }
+        return;
+    }
     double nx = 0.0, ny = 0.0, nz = 1.0;
     if (m >= 3.0) {
         double c[9];
@@ -1317,7 +1351,9 @@ __global__ __launch_bounds__(256) void normals_eigen_kernel(const double *__rest
     normals[3 * me] = (float)nx; normals[3 * me + 1] = (float)ny; normals[3 * me + 2] = (float)nz;
 }
 
-static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, float *normals, Arena &a, hipStream_t st)
+// normals != nullptr: estimate_normals; otherwise out_cov [n][9]: estimate_covariances (the same search, the covariance the normal comes from)
+static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, float *normals, Arena &a, hipStream_t st,
+                        double *out_cov = nullptr)
 {
     Grid g;
     int kk = (int64_t)max_nn < n ? max_nn : (int)(n > 0 ? n : 1);
@@ -1337,7 +1373,8 @@ static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, 
     const size_t lds = global_heap ? 0 : (size_t)kk * threads * (sizeof(double) + sizeof(int32_t));
     static bool attr_set = false;
     if (!attr_set) {
-        KPX_HIP(hipFuncSetAttribute((const void *)normals_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        KPX_HIP(hipFuncSetAttribute((const void *)normals_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        KPX_HIP(hipFuncSetAttribute((const void *)normals_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         KPX_HIP(hipFuncSetAttribute((const void *)normals_wave_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         attr_set = true;
     }
@@ -1349,10 +1386,19 @@ static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, 
         hipLaunchKernelGGL(normals_wave_kernel<4>, dim3((unsigned)(cdiv(n, 4) > 8192 ? 8192 : cdiv(n, 4))), dim3(256),
                            (size_t)4 * cap * (sizeof(double) + sizeof(uint32_t)), st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, n, kk,
                            cap, radius * radius, covbuf, fb_list, fb_count);
-        hipLaunchKernelGGL(normals_eigen_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals);
+        if (out_cov)
+            hipLaunchKernelGGL(normals_eigen_kernel<true>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals, out_cov);
+        else
+            hipLaunchKernelGGL(normals_eigen_kernel<false>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals, out_cov);
     }
-    hipLaunchKernelGGL(normals_kernel, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, pts, n, kk,
-                       radius * radius, normals, wave_pass ? fb_list : (const int32_t *)nullptr, wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
+    if (out_cov)
+        hipLaunchKernelGGL(normals_kernel<true>, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, pts,
+                           n, kk, radius * radius, normals, out_cov, wave_pass ? fb_list : (const int32_t *)nullptr,
+                           wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
+    else
+        hipLaunchKernelGGL(normals_kernel<false>, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, pts,
+                           n, kk, radius * radius, normals, out_cov, wave_pass ? fb_list : (const int32_t *)nullptr,
+                           wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -1461,4 +1507,19 @@ KPX_EXPORT int kpx_estimate_normals(const float *pts, int64_t n, double radius, 
     KPX_REQUIRE(pts && normals && ws, "kpx_estimate_normals: null pointer");
     Arena a(ws, ws_bytes);
     return normals_impl(pts, n, radius, max_nn, normals, a, (hipStream_t)stream);
+}
+
+// [O3D] PointCloud.estimate_covariances(search_param): per point the covariance of its estimate_normals neighbourhood (same search, same
+// ties), E[x x^T] - mu mu^T with divisor m; < 3 neighbours -> the identity.  cov f64 [n][9], symmetric.
+KPX_EXPORT size_t kpx_covariances_workspace_bytes(int64_t n, int32_t max_nn) { return kpx_normals_workspace_bytes(n, max_nn); }
+KPX_EXPORT int kpx_estimate_covariances(const float *pts, int64_t n, double radius, int32_t max_nn, double *cov, void *ws, size_t ws_bytes,
+                                        void *stream)
+{
+    KPX_REQUIRE(radius > 0.0 && max_nn >= 1, "estimate_covariances: radius and max_nn must be positive");
+    KPX_REQUIRE(max_nn <= KPX_NORMALS_MAX_NN, "estimate_covariances: max_nn > %d is not supported", KPX_NORMALS_MAX_NN);
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_estimate_covariances: bad size");
+    if (n == 0) return KPX_OK;
+    KPX_REQUIRE(pts && cov && ws, "kpx_estimate_covariances: null pointer");
+    Arena a(ws, ws_bytes);
+    return normals_impl(pts, n, radius, max_nn, nullptr, a, (hipStream_t)stream, cov);
 }

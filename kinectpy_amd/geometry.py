@@ -42,6 +42,33 @@ class Vector3dVector:
         return np.asarray(self)[i]
 
 
+class Matrix3dVector:
+    """o3d.utility.Matrix3dVector stand-in: wraps an (N,3,3) float64 array; np.asarray() gives float64 (N,3,3)."""
+
+    def __init__(self, data=None):
+        if isinstance(data, Matrix3dVector):
+            self.t = data.t
+        elif data is None:
+            self.t = torch.empty((0, 3, 3), dtype=torch.float64, device=L.device())
+        elif isinstance(data, torch.Tensor):
+            self.t = data.to(device=L.device(), dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+        else:
+            a = np.asarray(data)
+            if a.size and (a.ndim != 3 or a.shape[1:] != (3, 3)):
+                raise RuntimeError("Matrix3dVector: expected an (N, 3, 3) array")
+            self.t = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3, 3)).to(L.device())
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.t.cpu().numpy()
+        return a if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return int(self.t.shape[0])
+
+    def __getitem__(self, i):
+        return np.asarray(self)[i]
+
+
 class Vector2iVector:
     def __init__(self, data):
         self.a = np.ascontiguousarray(np.asarray(data), dtype=np.int32).reshape(-1, 2)
@@ -100,6 +127,10 @@ class OrientedBoundingBox:
 
 
 class PointCloud:
+    """Covariances (`covariances`, estimate_covariances, generalized ICP) are an fp64 (N,3,3) device tensor `_cov`.  transform()
+    rotates them, deepcopy / clone() and `+` carry them; every other method returns a cloud WITHOUT covariances -- unlike Open3D,
+    whose select_by_index (and the filters built on it) keeps them."""
+    _cov = None
     # _bounds: the cloud's min / max as a float64[6] DEVICE tensor once some kernel has computed them (the gather that produced the
     # cloud, or the first get_*_bound / remove_floor); dropped whenever the points change
     _bounds = None
@@ -119,6 +150,7 @@ class PointCloud:
         self._pts = Vector3dVector(points).t
         self._col = None
         self._nrm = None
+        self._cov = None
 
     # ---- attributes ---------------------------------------------------------------------------
     @property
@@ -147,6 +179,18 @@ class PointCloud:
         t = Vector3dVector(v).t
         self._nrm = t if t.shape[0] else None
 
+    @property
+    def covariances(self):
+        return Matrix3dVector(self._cov if self._cov is not None else None)
+
+    @covariances.setter
+    def covariances(self, v):
+        t = Matrix3dVector(v).t
+        self._cov = t if t.shape[0] else None
+
+    def has_covariances(self):
+        return self._cov is not None and self._cov.shape[0] == self._pts.shape[0] and self.has_points()
+
     def has_points(self):
         return self._pts.shape[0] > 0
 
@@ -172,8 +216,10 @@ class PointCloud:
         return self._bounds
 
     def __deepcopy__(self, memo):
-        return PointCloud._make(self._pts.clone(), None if self._col is None else self._col.clone(),
-                                None if self._nrm is None else self._nrm.clone())
+        pc = PointCloud._make(self._pts.clone(), None if self._col is None else self._col.clone(),
+                              None if self._nrm is None else self._nrm.clone())
+        pc._cov = None if self._cov is None else self._cov.clone()
+        return pc
 
     __copy__ = lambda self: self.__deepcopy__({})
 
@@ -201,6 +247,8 @@ class PointCloud:
             ops.transform(self._pts, T, out=self._pts)
             if self.has_normals():
                 ops.rotate(self._nrm, T, out=self._nrm)
+            if self.has_covariances():
+                ops.rotate_covariances(self._cov, T, out=self._cov)
         return self
 
     def select_by_index(self, indices, invert=False):
@@ -280,6 +328,14 @@ class PointCloud:
             self._nrm = ops.estimate_normals(self._pts, sp.radius, sp.max_nn)       # any max_nn up to KPX_NORMALS_MAX_NN (beyond 128 the fall-back heaps live in the workspace)
         return self
 
+    def estimate_covariances(self, search_param=None):
+        """[O3D] estimate_covariances: per point the covariance of its estimate_normals neighbourhood (None: KDTreeSearchParamKNN(30));
+        fewer than 3 neighbours give the identity"""
+        sp = search_param if search_param is not None else KDTreeSearchParamKNN(30)
+        if self.has_points():
+            self._cov = ops.estimate_covariances(self._pts, sp.radius, sp.max_nn)
+        return self
+
     def get_oriented_bounding_box(self, robust=False):
         """utils/normalization.py:39, 74, 105; utils/processing.py:341"""
         obb, _ = ops.obb_batch(self._pts)
@@ -288,15 +344,18 @@ class PointCloud:
     def __add__(self, other):
         both_c = self.has_colors() and other.has_colors()
         both_n = self.has_normals() and other.has_normals()
+        both_v = self.has_covariances() and other.has_covariances()
         if not self.has_points():
-            both_c, both_n = other.has_colors(), other.has_normals()
-        return PointCloud._make(torch.cat([self._pts, other._pts], 0),
-                                torch.cat([self._col, other._col], 0) if both_c and self.has_points() else (other._col if both_c else None),
-                                torch.cat([self._nrm, other._nrm], 0) if both_n and self.has_points() else (other._nrm if both_n else None))
+            both_c, both_n, both_v = other.has_colors(), other.has_normals(), other.has_covariances()
+        pc = PointCloud._make(torch.cat([self._pts, other._pts], 0),
+                              torch.cat([self._col, other._col], 0) if both_c and self.has_points() else (other._col if both_c else None),
+                              torch.cat([self._nrm, other._nrm], 0) if both_n and self.has_points() else (other._nrm if both_n else None))
+        pc._cov = torch.cat([self._cov, other._cov], 0) if both_v and self.has_points() else (other._cov if both_v else None)
+        return pc
 
     def __iadd__(self, other):
         r = self + other
-        self._pts, self._col, self._nrm, self._bounds = r._pts, r._col, r._nrm, None
+        self._pts, self._col, self._nrm, self._cov, self._bounds = r._pts, r._col, r._nrm, r._cov, None
         return self
 
     def clone(self):

@@ -8,7 +8,7 @@ import types
 import numpy as np
 
 from . import ops
-from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, OrientedBoundingBox, PointCloud, Vector2iVector,
+from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, Matrix3dVector, OrientedBoundingBox, PointCloud, Vector2iVector,
                        Vector3dVector)
 from . import pcd_io
 
@@ -83,6 +83,45 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
         tn = target._nrm
     r = ops.icp(source._pts, target._pts, float(max_correspondence_distance), init, est.mode, tn, crit.max_iteration,
                 crit.relative_fitness, crit.relative_rmse, want_corr=True)
+    idx, d2 = r["idx"].cpu().numpy(), r["d2"].cpu().numpy()
+    ok = d2 < float(max_correspondence_distance) ** 2
+    corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
+    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], corr)
+
+
+class L2Loss:
+    """o3d.pipelines.registration.L2Loss: the plain least-squares loss (weight 1 for every residual)"""
+
+
+class TransformationEstimationForGeneralizedICP:
+    """[O3D] plane-to-plane ICP (Segal et al.): the L2 loss only"""
+    mode = "gicp"
+
+    def __init__(self, epsilon=1e-3, kernel=None):
+        if kernel is not None and not isinstance(kernel, L2Loss) and type(kernel).__name__ != "L2Loss":
+            raise NotImplementedError("TransformationEstimationForGeneralizedICP: only the L2 loss is implemented (no robust kernels)")
+        self.epsilon, self.kernel = float(epsilon), kernel
+
+
+def _gicp_covariances(cloud, epsilon):
+    """[O3D] InitializePointCloudForGeneralizedICP, without touching `cloud`: its covariances as they are; else from its normals;
+    else from normals estimated with KDTreeSearchParamKNN(20)"""
+    if cloud.has_covariances():
+        return cloud._cov
+    nrm = cloud._nrm if cloud.has_normals() else ops.estimate_normals(cloud._pts, KDTreeSearchParamKNN(20).radius, 20)
+    return ops.gicp_covariances(nrm, epsilon)
+
+
+def registration_generalized_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """[O3D] registration_generalized_icp: the registration_icp loop with TransformationEstimationForGeneralizedICP as the update.
+    Source and target are left as they are (covariances are built on copies, as Open3D does)."""
+    est = estimation_method if estimation_method is not None else TransformationEstimationForGeneralizedICP()
+    crit = criteria if criteria is not None else ICPConvergenceCriteria()
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    r = ops.generalized_icp(source._pts, _gicp_covariances(source, est.epsilon), target._pts, _gicp_covariances(target, est.epsilon),
+                            float(max_correspondence_distance), init, crit.max_iteration, crit.relative_fitness, crit.relative_rmse,
+                            want_corr=True)
     idx, d2 = r["idx"].cpu().numpy(), r["d2"].cpu().numpy()
     ok = d2 < float(max_correspondence_distance) ** 2
     corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
@@ -170,7 +209,7 @@ def _off_path(name):
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN)
-utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector)
+utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
 io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
 pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     registration_icp=registration_icp,
@@ -186,6 +225,9 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     RANSACConvergenceCriteria=RANSACConvergenceCriteria,
     registration_colored_icp=registration_colored_icp,
     TransformationEstimationForColoredICP=TransformationEstimationForColoredICP,
+    registration_generalized_icp=registration_generalized_icp,
+    L2Loss=L2Loss,
+    TransformationEstimationForGeneralizedICP=TransformationEstimationForGeneralizedICP,
 ))
 visualization = types.SimpleNamespace(VisualizerWithEditing=_off_path("VisualizerWithEditing"),
                                       draw_geometries=_off_path("draw_geometries"))

@@ -861,3 +861,64 @@ def colored_icp(src, src_colors, tgt, tgt_colors, tgt_normals, max_dist, init=No
     r = res.cpu().numpy()
     return {"transformation": r[:16].reshape(4, 4).copy(), "fitness": float(r[16]), "inlier_rmse": float(r[17]),
             "iterations": int(r[18]), "count": int(r[19])}
+
+
+# ---- generalized ICP ----------------------------------------------------------------------------------------
+def estimate_covariances(pts, radius, max_nn):
+    """[O3D] estimate_covariances: the covariance of each point's estimate_normals neighbourhood (< 3 neighbours: identity),
+    (n, 3, 3) f64 on the device"""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    out = torch.empty((n, 3, 3), dtype=torch.float64, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_covariances_workspace_bytes(n, int(max_nn)))
+    L.check(lib.kpx_estimate_covariances(L.ptr(pts), n, float(radius), int(max_nn), L.ptr(out), ws, wsz, L.stream_ptr()))
+    return out
+
+
+def gicp_covariances(normals, epsilon=1e-3):
+    """[O3D] InitializePointCloudForGeneralizedICP from normals: R_x diag(epsilon, 1, 1) R_x^T, (n, 3, 3) f64 on the device"""
+    lib = L.load()
+    nrm = _dev(normals, torch.float32).reshape(-1, 3)
+    n = nrm.shape[0]
+    out = torch.empty((n, 3, 3), dtype=torch.float64, device=nrm.device)
+    L.check(lib.kpx_gicp_covariances(L.ptr(nrm), n, float(epsilon), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def rotate_covariances(cov, T, out=None):
+    """R C R^T per point (R = rotation of T); out may be cov"""
+    lib = L.load()
+    cov = _dev(cov, torch.float64).reshape(-1, 3, 3)
+    if out is None:
+        out = torch.empty_like(cov)
+    L.check(lib.kpx_rotate_covariances(L.ptr(cov), cov.shape[0], L.hptr(_T(T)), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def generalized_icp(src, src_cov, tgt, tgt_cov, max_dist, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                    want_corr=False, poll_interval=4):
+    """[O3D] registration_generalized_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count[, idx, d2])."""
+    lib = L.load()
+    src = _dev(src, torch.float32).reshape(-1, 3)
+    tgt = _dev(tgt, torch.float32).reshape(-1, 3)
+    sc = _dev(src_cov, torch.float64).reshape(-1, 3, 3)
+    tc = _dev(tgt_cov, torch.float64).reshape(-1, 3, 3)
+    n, m = src.shape[0], tgt.shape[0]
+    if sc.shape[0] != n or tc.shape[0] != m:
+        raise L.KinectPxError("generalized_icp: one covariance per point is required")
+    dev = src.device
+    res = torch.zeros(20, dtype=torch.float64, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev) if want_corr else None
+    d2 = torch.empty(n, dtype=torch.float64, device=dev) if want_corr else None
+    init = _T(np.eye(4) if init is None else init)
+    ws, wsz = L.workspace(lib.kpx_generalized_icp_workspace_bytes(n, m))
+    L.check(lib.kpx_generalized_icp(L.ptr(src), L.ptr(sc), n, L.ptr(tgt), L.ptr(tc), m, float(max_dist), L.hptr(init), int(max_iteration),
+                                    float(relative_fitness), float(relative_rmse), int(poll_interval), L.ptr(res), L.ptr(idx), L.ptr(d2),
+                                    ws, wsz, L.stream_ptr()))
+    r = res.cpu().numpy()
+    out = {"transformation": r[:16].reshape(4, 4).copy(), "fitness": float(r[16]), "inlier_rmse": float(r[17]),
+           "iterations": int(r[18]), "count": int(r[19])}
+    if want_corr:
+        out["idx"], out["d2"] = idx, d2
+    return out

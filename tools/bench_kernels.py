@@ -242,6 +242,13 @@ def main():
     report("registration_icp p2plane 100k x 100k (a14)", ms, iterations=r["iterations"], fitness=round(r["fitness"], 5),
            ms_per_iteration=round(ms / (r["iterations"] + 1), 4), dense_equivalent_flops=int(dense * (r["iterations"] + 1)),
            **sweep(ops.prof_end()))
+    # generalized ICP: covariances from the same target normals (and the source's, estimated alike), built outside the timing
+    tc, sc = ops.gicp_covariances(tn), ops.gicp_covariances(ops.estimate_normals(s, 70.0, 40))
+    ops.prof_begin(256)
+    ms, r = timed(lambda: ops.generalized_icp(s, sc, t, tc, 100.0, None, 30), reps=5, warm=1)
+    report("registration_generalized_icp 100k x 100k", ms, iterations=r["iterations"], fitness=round(r["fitness"], 5),
+           ms_per_iteration=round(ms / (r["iterations"] + 1), 4), dense_equivalent_flops=int(dense * (r["iterations"] + 1)),
+           **sweep(ops.prof_end()))
 
 
 if __name__ == "__main__":
