@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void fpfh_kernel(int64_t n, const int32_t *__r
 // conflict-free for the 16 columns a lane group reads) already scaled by -2, their norms are formed once per stage.
 typedef double fnn_d4 __attribute__((ext_vector_type(4)));
 constexpr int kFnnCols = 128, kFnnStride = 37;
-// gridDim.y column splits (stages of 64 columns dealt round-robin); split s writes (value, column) of its best to
+// gridDim.y column splits (stages of 128 columns dealt round-robin); split s writes (value, column) of its best to
 // part_val / part_idx [s][na]; feature_nn_merge_kernel takes the lexicographic minimum.
 __global__ __launch_bounds__(256) void feature_nn_kernel(const double *__restrict__ fa, int64_t na, const double *__restrict__ fb,
                                                          int64_t nb, double *__restrict__ part_val, int32_t *__restrict__ part_idx)
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void feature_nn_kernel(const double *__restric
         for (int e = threadIdx.x; e < cnt * 33; e += 256) sb[e / 33][e % 33] = -2.0 * fb[j0 * 33 + e];    // B rows: -2 b (exact)
         __syncthreads();
         if ((int)threadIdx.x < kFnnCols) {
-            double n2 = kSentinelF;                            // columns past the end can never win
+            double n2 = kSentinelF;                            // columns past the end: see feature_nn_merge_kernel
             if ((int)threadIdx.x < cnt) {
                 n2 = 0.0;
                 for (int k = 0; k < 33; ++k) { const double v = -0.5 * sb[threadIdx.x][k]; n2 = fma(v, v, n2); }
@@ -291,17 +291,38 @@ __global__ __launch_bounds__(256) void feature_nn_kernel(const double *__restric
         if (j == 0 && row < na) { part_val[(int64_t)blockIdx.y * na + row] = v; part_idx[(int64_t)blockIdx.y * na + row] = c; }
     }
 }
+// A padding column (|b|^2 = kSentinelF) wins a split only when no real column of the split has a distance below |a|^2 + 1e300:
+// huge features, NaN / inf rows.  Such a row (or one no column won: index INT_MAX) is rescanned here over every column with the
+// same fma chain, keeping the first minimum below +inf and 0 when there is none -- the oracle's rule.  The main loop stays as it is.
 __global__ __launch_bounds__(256) void feature_nn_merge_kernel(const double *__restrict__ part_val, const int32_t *__restrict__ part_idx,
-                                                               int64_t na, int splits, int32_t *__restrict__ idx)
+                                                               int64_t na, int splits, const double *__restrict__ fa,
+                                                               const double *__restrict__ fb, int64_t nb, int32_t *__restrict__ idx)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= na) return;
     double bv = part_val[i];
     int32_t bj = part_idx[i];
+    bool exact = bj >= nb;
     for (int s = 1; s < splits; ++s) {
         const double v = part_val[(int64_t)s * na + i];
         const int32_t c = part_idx[(int64_t)s * na + i];
+        exact = exact || c >= nb;
         if (v < bv || (v == bv && c < bj)) { bv = v; bj = c; }
+    }
+    if (exact) {
+        const double *a = fa + i * 33;
+        double na2 = 0.0;
+        for (int k = 0; k < 33; ++k) na2 = fma(a[k], a[k], na2);
+        bv = INFINITY;
+        bj = 0;
+        for (int64_t j = 0; j < nb; ++j) {
+            const double *b = fb + j * 33;
+            double nb2 = 0.0, d = na2;
+            for (int k = 0; k < 33; ++k) nb2 = fma(b[k], b[k], nb2);
+            for (int k = 0; k < 33; ++k) d = fma(a[k], -2.0 * b[k], d);
+            d = fma(1.0, nb2, d);
+            if (d < bv) { bv = d; bj = (int32_t)j; }
+        }
     }
     idx[i] = bj;
 }
@@ -320,8 +341,25 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// one thread per iteration `itr0 + t`: sample 3 correspondences (with replacement), edge-length check, Umeyama,
-// distance check.  pass[t] = 1 and T[t] (16 doubles) when the hypothesis survives.
+// A triple whose points are (nearly) collinear -- a correspondence drawn twice, or points on a line -- gives a rank-1 S: the
+// rotation about the line is not determined, and any construction of it is arbitrary.  Such triples are rejected like a failed
+// checker, on either side (arithmetic contract; the CPU oracle restates the test):
+//     flat  <=>  !( |e1 x e2|^2 > kTripleFlat L^4 ),   e1 = p1 - p0, e2 = p2 - p0, L^2 the longest squared edge.
+constexpr double kTripleFlat = 1e-10;
+__device__ __forceinline__ bool triple_flat(const double p[3][3])
+{
+    double e1[3], e2[3], e3[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { e1[a] = p[1][a] - p[0][a]; e2[a] = p[2][a] - p[0][a]; e3[a] = p[2][a] - p[1][a]; }
+    const double c[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+    const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
+    const double l3 = e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2];
+    const double l = fmax(l1, fmax(l2, l3));
+    return !(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] > kTripleFlat * l * l);
+}
+
+// one thread per iteration `itr0 + t`: sample 3 correspondences (with replacement), edge-length check, flat-triple rejection,
+// Umeyama, distance check.  pass[t] = 1 and T[t] (16 doubles) when the hypothesis survives.
 __global__ __launch_bounds__(256) void ransac_hyp_kernel(const float *__restrict__ src, const float *__restrict__ tgt,
                                                          const int32_t *__restrict__ corres, int64_t nc, int32_t itr0, int32_t count,
                                                          uint32_t seed_lo, uint32_t seed_hi, double edge_sim, double max_dist,
@@ -351,7 +389,7 @@ __global__ __launch_bounds__(256) void ransac_hyp_kernel(const float *__restrict
             ok = ok && !(ds < dt * edge_sim || dt < ds * edge_sim);
         }
     pass[t] = 0;
-    if (!ok) return;
+    if (!ok || triple_flat(sp) || triple_flat(tp)) return;
     double ms[3] = { 0, 0, 0 }, mt[3] = { 0, 0, 0 }, S[9], R[9];
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -687,7 +725,7 @@ KPX_EXPORT int kpx_feature_nn(const double *fa, int64_t na, const double *fb, in
     KPX_ARENA_CHECK(a);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(feature_nn_kernel, dim3((unsigned)cdiv(na, 64), splits), dim3(256), 0, st, fa, na, fb, nb, pv, pi);
-    hipLaunchKernelGGL(feature_nn_merge_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, st, pv, pi, na, splits, idx);
+    hipLaunchKernelGGL(feature_nn_merge_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, st, pv, pi, na, splits, fa, fb, nb, idx);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -718,7 +756,7 @@ KPX_EXPORT int kpx_ransac_corres(const float *src, int64_t n_src, const float *t
     KPX_ARENA_CHECK(a);
     const double r2 = max_dist * max_dist;
     double best_fit = 0.0, best_rmse = 0.0;
-    int est_k = max_iteration, validations = 0, itr_done = 0;
+    int est_k = max_iteration, validations = 0, last_cut = -1;     // last_cut: the iteration whose validation last set est_k
     // Per batch: hypotheses -> survivors compacted in iteration order -> the first kSpec survivors are validated and scored
     // speculatively (kernels guarded by the device count) -> ONE read-back (count, list, scores) -> Open3D's loop body is
     // replayed on the host in iteration order.  Batches with more than kSpec survivors validate the rest in further chunks.
@@ -765,15 +803,16 @@ KPX_EXPORT int kpx_ransac_corres(const float *src, int64_t n_src, const float *t
                     best_in_batch = (int)h_score[4 * v + 3];
                     const double ratio = h_score[4 * v + 2] / (double)n_corres;
                     const double ek = log(1.0 - confidence) / log(1.0 - pow(ratio, (double)ransac_n));
-                    if (ek < (double)est_k) est_k = (int)ceil(ek);
+                    if (ek < (double)est_k) { est_k = ek > 0.0 ? (int)ceil(ek) : 0; last_cut = itr; }
                 }
             }
         }
         if (best_in_batch >= 0)                                         // the batch's transforms are overwritten by the next one
             KPX_HIP(hipMemcpy(h_result, b.Ts + (int64_t)best_in_batch * 16, 16 * sizeof(double), hipMemcpyDeviceToHost));
-        itr_done = itr0 + count < est_k ? itr0 + count : est_k;
         if (stop) break;
     }
+    // Open3D's loop ends at the first iteration >= est_k: est_k itself, or the one after the validation that set est_k below it
+    const int itr_done = est_k > last_cut + 1 ? est_k : last_cut + 1;
     h_result[16] = best_fit; h_result[17] = best_rmse; h_result[18] = (double)itr_done; h_result[19] = (double)validations;
     return KPX_OK;
 }

@@ -991,10 +991,25 @@ static void kabsch_pairs(const double *s, const double *t, int m, double T[16])
 }
 KPO_API void kpo_kabsch_pairs(const double *s, const double *t, int m, double *T) { kabsch_pairs(s, t, m, T); }
 
+/* Flat triple (contract shared with the product's ransac_hyp_kernel): the three points are collinear to within     */
+/* |e1 x e2|^2 <= 1e-10 L^4 (e1 = p1 - p0, e2 = p2 - p0, L the longest edge), which covers a correspondence drawn twice. */
+/* S is then rank 1 and the rotation about the line is arbitrary: such a triple is rejected before Umeyama.           */
+static int triple_flat(const double *p)
+{
+    double e1[3], e2[3], e3[3];
+    for (int a = 0; a < 3; ++a) { e1[a] = p[3 + a] - p[a]; e2[a] = p[6 + a] - p[a]; e3[a] = p[6 + a] - p[3 + a]; }
+    double c0 = e1[1] * e2[2] - e1[2] * e2[1], c1 = e1[2] * e2[0] - e1[0] * e2[2], c2 = e1[0] * e2[1] - e1[1] * e2[0];
+    double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
+    double l3 = e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2];
+    double l = fmax(l1, fmax(l2, l3));
+    return !(c0 * c0 + c1 * c1 + c2 * c2 > 1e-10 * l * l);
+}
+
 /* a13: [O3D] RegistrationRANSACBasedOnCorrespondence (preprocessing/registration.py:50-57):            */
 /*   sample ransac_n correspondences (with replacement; Philox(ctr=(block,itr,1,0), key=seed), index =  */
 /*   (u*|corres|)>>32), Umeyama, checkers (edge length 0.95, distance), validation = full nearest-      */
 /*   neighbour correspondence search within max_dist (fitness, rmse), better-than test, est_k update    */
+/*   (est_k = ceil(ek), 0 when ek <= 0; the loop ends at the first iteration >= est_k)                  */
 /*   from the inlier ratio of the correspondence set.  Iterations run in order (Open3D's run in an       */
 /*   OpenMP loop in unspecified order: the reference result is not reproducible).                       */
 /* stats[0] = iterations run, [1] = validations, [2] = fitness, [3] = rmse.  Returns 0, T = identity if  */
@@ -1033,6 +1048,7 @@ KPO_API int kpo_ransac_corres(const real_t *src, int64_t n, const real_t *tgt, i
                 if (ds < dt * edge_sim || dt < ds * edge_sim) { ok = 0; break; }
             }
         if (!ok) continue;
+        if (ransac_n == 3 && (triple_flat(sp) || triple_flat(tp))) continue;      /* rank-1 S: rotation undetermined */
         double T[16];
         kabsch_pairs(sp, tp, ransac_n, T);
         for (int q = 0; q < ransac_n && ok; ++q) {           /* CorrespondenceCheckerBasedOnDistance */
@@ -1059,7 +1075,7 @@ KPO_API int kpo_ransac_corres(const real_t *src, int64_t n, const real_t *tgt, i
             }
             double ratio = (double)inl / (double)nc;
             double ek = log(1.0 - confidence) / log(1.0 - pow(ratio, (double)ransac_n));
-            if (ek < (double)est_k) est_k = (int)ceil(ek);
+            if (ek < (double)est_k) est_k = ek > 0.0 ? (int)ceil(ek) : 0;
         }
     }
     free(idx); free(d2); free(sp); free(tp);
