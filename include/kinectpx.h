@@ -282,6 +282,18 @@ size_t kpx_nn_workspace_bytes(int64_t n_src, int64_t n_tgt);
 int kpx_nn_search(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *d_T,
                   int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream);
 
+/* [O3D] evaluate_registration + get_information_matrix_from_point_clouds at one transformation, without an ICP: the
+ * correspondence search of kpx_nn_search (the engine kpx_nn_engine selects), then one deterministic fp64 reduction over the
+ * rows with d2 < max_dist^2 (the test of the ICP accumulation, strict).  d_T device f64 [16].
+ * d_result device f64 [40]: fitness = count / n_src, inlier_rmse = sqrt(sum d2 / count) (0 when count is 0), count, sum d2,
+ * then the 6x6 information matrix row-major: sum G^T G with G = [-[t]x | I3] of the matched TARGET points t (rotation block
+ * first, Open3D's order).  The block is bit-identical across the three engines and from run to run.
+ * idx i32 [n_src] / d2 f64 [n_src]: the correspondences as kpx_nn_search gives them; either may be NULL. */
+size_t kpx_registration_eval_workspace_bytes(int64_t n_src, int64_t n_tgt);
+int kpx_registration_eval(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *d_T,
+                          double max_dist, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes,
+                          void *stream);
+
 /* TransformationEstimationPointToPoint().compute_transformation(src, tgt, corr)
  * (manual_pointcloud_registration.py:90-91): Umeyama/Kabsch without scale on explicit pairs.
  * corr i32 [n_corr*2] = (source index, target index); d_T f64 [16]. */

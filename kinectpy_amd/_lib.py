@@ -63,6 +63,8 @@ SIGNATURES = {
     "kpx_segment_plane": (C.c_int, [_vp, _i64, _f64, _i32, _i32, _f64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_nn_workspace_bytes": (_sz, [_i64, _i64]),
     "kpx_nn_search": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_registration_eval_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_registration_eval": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_kabsch_workspace_bytes": (_sz, [_i64]),
     "kpx_kabsch": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "kpx_icp_workspace_bytes": (_sz, [_i64, _i64]),

@@ -2486,6 +2486,108 @@ KPX_EXPORT int kpx_nn_search(const float *src, int64_t n_src, const float *tgt, 
     return KPX_OK;
 }
 
+// ---- evaluate_registration + get_information_matrix_from_point_clouds in one pass ---------------------------------------
+// After the correspondence search: over the rows that pass the distance test of the ICP accumulation (d2 < max_dist^2, strict),
+// eleven fp64 sums -- count, sum d2, and the moments of the MATCHED TARGET points t = tgt[idx]: sum t (3), sum t t^T (6).
+// Rounding: a float32 coordinate converts to fp64 exactly and the product of two of them (<= 48 significant bits) is exact in
+// fp64, so the only rounding in the ten moment sums is that of the additions (d2 comes from the search as it is).  Order of the
+// additions: a thread's rows in grid-stride order, the 64 lanes by the wave tree (wave_sum), the block's waves in order
+// (block_sum), the blocks in order (regeval_finish_kernel) -- fixed by (n, grid), no floating-point atomics, so equal idx / d2
+// give equal bits whichever engine searched.
+// The gathers of t are n random 12-byte loads; the kernel is a few microseconds beside the search.
+constexpr int kEvalSums = 11, kEvalBlocks = 256, kEvalThreads = 256;
+__global__ __launch_bounds__(kEvalThreads) void regeval_acc_kernel(const float *__restrict__ tgt, int64_t n, int64_t m, const int32_t *__restrict__ idx,
+                                                                  const double *__restrict__ d2, double max_d2, double *__restrict__ part)
+{
+    __shared__ double sh[kEvalThreads / 64];
+    double acc[kEvalSums];
+#pragma unroll
+    for (int q = 0; q < kEvalSums; ++q) acc[q] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx[i];
+        const double d = d2[i];
+        if (j < 0 || j >= m || !(d < max_d2)) continue;
+        const float *tp = tgt + 3 * j;
+        const double x = tp[0], y = tp[1], z = tp[2];
+        acc[0] += 1.0; acc[1] += d;
+        acc[2] += x; acc[3] += y; acc[4] += z;
+        acc[5] += x * x; acc[6] += x * y; acc[7] += x * z;
+        acc[8] += y * y; acc[9] += y * z; acc[10] += z * z;
+    }
+#pragma unroll
+    for (int q = 0; q < kEvalSums; ++q) {
+        const double v = block_sum(acc[q], sh);
+        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * kEvalSums + q] = v;
+    }
+}
+// result f64 [40]: fitness, inlier_rmse, count, sum d2, then the 6x6 information matrix row-major (rotation block first).
+// Every entry is one sum, the sum of two (the diagonal of the rotation block, from sum x^2, sum y^2, sum z^2 -- never a
+// difference) or a negation.
+__global__ __launch_bounds__(64) void regeval_finish_kernel(const double *__restrict__ part, int nblocks, int64_t n, double *__restrict__ res)
+{
+    __shared__ double S[kEvalSums];
+    if (threadIdx.x < kEvalSums) {
+        double s = 0.0;
+        for (int b = 0; b < nblocks; ++b) s += part[(int64_t)b * kEvalSums + threadIdx.x];
+        S[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 40) return;
+    const double cnt = S[0], sx = S[2], sy = S[3], sz = S[4], xx = S[5], xy = S[6], xz = S[7], yy = S[8], yz = S[9], zz = S[10];
+    const double L[36] = { yy + zz, -xy, -xz, 0.0, -sz, sy,
+                           -xy, xx + zz, -yz, sz, 0.0, -sx,
+                           -xz, -yz, xx + yy, -sy, sx, 0.0,
+                           0.0, sz, -sy, cnt, 0.0, 0.0,
+                           -sz, 0.0, sx, 0.0, cnt, 0.0,
+                           sy, -sx, 0.0, 0.0, 0.0, cnt };
+    const int q = threadIdx.x;
+    double v;
+    if (q == 0) v = n > 0 ? cnt / (double)n : 0.0;
+    else if (q == 1) v = cnt > 0.0 ? sqrt(S[1] / cnt) : 0.0;
+    else if (q == 2) v = cnt;
+    else if (q == 3) v = S[1];
+    else v = L[q - 4] + 0.0;                                   // + 0.0: no negative zeros in the matrix
+    res[q] = v;
+}
+
+KPX_EXPORT size_t kpx_registration_eval_workspace_bytes(int64_t n_src, int64_t n_tgt)
+{
+    Arena a(nullptr, 0);
+    NnBuffers b;
+    nn_carve(a, n_src, n_tgt, nn_plan(n_src, n_tgt), &b);
+    a.get<double>((size_t)kEvalBlocks * kEvalSums);
+    return a.off;
+}
+KPX_EXPORT int kpx_registration_eval(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *d_T,
+                                     double max_dist, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes,
+                                     void *stream)
+{
+    KPX_REQUIRE(max_dist > 0.0, "Invalid max_correspondence_distance.");          // [O3D]
+    KPX_REQUIRE(n_src >= 1 && n_tgt >= 1, "kpx_registration_eval: empty cloud");
+    KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_registration_eval: cloud too large");
+    KPX_REQUIRE(src && tgt && d_T && d_result && ws, "kpx_registration_eval: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    NnPlan p = nn_plan(n_src, n_tgt);
+    NnBuffers b;
+    nn_carve(a, n_src, n_tgt, p, &b);
+    double *part = a.get<double>((size_t)kEvalBlocks * kEvalSums);
+    KPX_ARENA_CHECK(a);
+    int rc = nn_prep(tgt, p, b, st);
+    if (rc) return rc;
+    rc = nn_prep_source(src, p, b, st);
+    if (rc) return rc;
+    rc = nn_search_launch(src, tgt, nullptr, p, b, d_T, nullptr, false, false, 0.0, -1, st);      // as kpx_nn_search: the engine kpx_nn_engine selects
+    if (rc) return rc;
+    const int nb = (int)(cdiv(n_src, kEvalThreads) > kEvalBlocks ? kEvalBlocks : cdiv(n_src, kEvalThreads));
+    hipLaunchKernelGGL(regeval_acc_kernel, dim3(nb), dim3(kEvalThreads), 0, st, tgt, n_src, n_tgt, b.idx_cur, b.d2_cur, max_dist * max_dist, part);
+    hipLaunchKernelGGL(regeval_finish_kernel, dim3(1), dim3(64), 0, st, part, nb, n_src, d_result);
+    KPX_LAUNCH_CHECK();
+    if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return KPX_OK;
+}
+
 KPX_EXPORT size_t kpx_kabsch_workspace_bytes(int64_t n_corr)
 {
     Arena a(nullptr, 0);

@@ -11,6 +11,7 @@ from . import ops
 from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, Matrix3dVector, OrientedBoundingBox, PointCloud, Vector2iVector,
                        Vector3dVector)
 from . import pcd_io
+from . import posegraph
 
 
 class ICPConvergenceCriteria:
@@ -87,6 +88,25 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     ok = d2 < float(max_correspondence_distance) ** 2
     corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
     return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], corr)
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None):
+    """[O3D] evaluate_registration: fitness / inlier_rmse / correspondence_set of `transformation` as given (no ICP)"""
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    T = np.eye(4) if transformation is None else np.array(transformation, dtype=np.float64).reshape(4, 4)
+    r = ops.registration_eval(source._pts, target._pts, float(max_correspondence_distance), T, want_corr=True)
+    idx, d2 = r["idx"].cpu().numpy(), r["d2"].cpu().numpy()
+    ok = d2 < float(max_correspondence_distance) ** 2
+    corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
+    return RegistrationResult(T, r["fitness"], r["inlier_rmse"], corr)
+
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation):
+    """[O3D] GetInformationMatrixFromPointClouds: sum G^T G, G = [-[t]x | I3], over the matched target points -> (6, 6) float64"""
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    return ops.registration_eval(source._pts, target._pts, float(max_correspondence_distance), transformation)["information"]
 
 
 class L2Loss:
@@ -228,6 +248,16 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     registration_generalized_icp=registration_generalized_icp,
     L2Loss=L2Loss,
     TransformationEstimationForGeneralizedICP=TransformationEstimationForGeneralizedICP,
+    evaluate_registration=evaluate_registration,
+    get_information_matrix_from_point_clouds=get_information_matrix_from_point_clouds,
+    PoseGraphNode=posegraph.PoseGraphNode,
+    PoseGraphEdge=posegraph.PoseGraphEdge,
+    PoseGraph=posegraph.PoseGraph,
+    GlobalOptimizationConvergenceCriteria=posegraph.GlobalOptimizationConvergenceCriteria,
+    GlobalOptimizationOption=posegraph.GlobalOptimizationOption,
+    GlobalOptimizationLevenbergMarquardt=posegraph.GlobalOptimizationLevenbergMarquardt,
+    GlobalOptimizationGaussNewton=posegraph.GlobalOptimizationGaussNewton,
+    global_optimization=posegraph.global_optimization,
 ))
 visualization = types.SimpleNamespace(VisualizerWithEditing=_off_path("VisualizerWithEditing"),
                                       draw_geometries=_off_path("draw_geometries"))

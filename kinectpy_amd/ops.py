@@ -459,6 +459,30 @@ def nn_search(src, tgt, T=None):
     return idx, d2
 
 
+def registration_eval(src, tgt, max_dist, T=None, want_corr=False):
+    """[O3D] evaluate_registration + get_information_matrix_from_point_clouds at T (no ICP): one correspondence search, one
+    reduction.  Returns dict(fitness, inlier_rmse, count, information (6,6) float64[, idx, d2])."""
+    lib = L.load()
+    if not max_dist > 0:
+        raise L.KinectPxError("Invalid max_correspondence_distance.")
+    src = _dev(src, torch.float32).reshape(-1, 3)
+    tgt = _dev(tgt, torch.float32).reshape(-1, 3)
+    dev = src.device
+    Td = torch.as_tensor(_T(np.eye(4) if T is None else T)).to(dev)
+    n, m = src.shape[0], tgt.shape[0]
+    res = torch.empty(40, dtype=torch.float64, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev) if want_corr else None
+    d2 = torch.empty(n, dtype=torch.float64, device=dev) if want_corr else None
+    ws, wsz = L.workspace(lib.kpx_registration_eval_workspace_bytes(n, m))
+    L.check(lib.kpx_registration_eval(L.ptr(src), n, L.ptr(tgt), m, L.ptr(Td), float(max_dist), L.ptr(res), L.ptr(idx), L.ptr(d2),
+                                      ws, wsz, L.stream_ptr()))
+    r = res.cpu().numpy()
+    out = {"fitness": float(r[0]), "inlier_rmse": float(r[1]), "count": int(r[2]), "information": r[4:40].reshape(6, 6).copy()}
+    if want_corr:
+        out["idx"], out["d2"] = idx, d2
+    return out
+
+
 def kabsch(src, tgt, corr):
     lib = L.load()
     src = _dev(src, torch.float32).reshape(-1, 3)

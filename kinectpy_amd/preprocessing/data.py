@@ -21,7 +21,7 @@ from ..pcd_io import write_point_cloud
 from ..utils.io import load_color, load_depth, rgbd_to_pointcloud
 from ..utils.processing import sort_filenames_by_timestamp
 from .filtering import Filtering, filter_outliers
-from .registration import execute_global_registration, execute_point_to_plane_registration
+from .registration import execute_global_registration, execute_multiway_registration, execute_point_to_plane_registration
 
 
 def transform_filtered_image_to_pointcloud(filtered_img, depth_img) -> PointCloud:
@@ -65,15 +65,17 @@ def fuse_and_filter(filtered_pcds: Sequence[PointCloud], registration_transforma
 class DataProcessor:
     def __init__(self, output_dirs: List[str], mask_rcnn_pb_file: Optional[str] = None, mask_rcnn_pbtxt_file: Optional[str] = None, *,
                  mask_fn=None, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None,
-                 run: bool = True):
+                 run: bool = True, multiway: bool = False):
         """reference signature (data.py:15-27) + keyword-only extras: `mask_fn` (the person mask, instead of Mask R-CNN),
         `initial_transformations` (skip the global registration: data.py:156), `seed` (the reference's RANSAC is unseeded),
-        `run=False` (build the object, call find / process yourself)."""
+        `run=False` (build the object, call find / process yourself), `multiway=True` (calibrate with execute_multiway_registration:
+        every pair of devices registered, one pose graph solved -- instead of the reference's star of sub -> master ICPs)."""
         self.device_filenames_df = self._create_device_filenames_df(output_dirs)
         self.number_of_devices = len(self.device_filenames_df.columns)
         self.registration_transformations: List[np.ndarray] = []
         self.initial_transformations = initial_transformations
         self.seed = seed
+        self.multiway = multiway
         self.segmentation = None
         self._mask_args = (mask_rcnn_pb_file, mask_rcnn_pbtxt_file, mask_fn)
         if not run:
@@ -90,7 +92,8 @@ class DataProcessor:
             write_point_cloud(dst + '.pcd', registered_pcd)                       # data.py:64-69
 
     @classmethod
-    def in_memory(cls, number_of_devices: int, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None):
+    def in_memory(cls, number_of_devices: int, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None,
+                  multiway: bool = False):
         """the frame loop without the directory walk: find_registration_transforms(master, subs) / process_frame(imgs, depths)"""
         self = cls.__new__(cls)
         self.device_filenames_df = None
@@ -98,6 +101,7 @@ class DataProcessor:
         self.registration_transformations = []
         self.initial_transformations = initial_transformations
         self.seed = seed
+        self.multiway = multiway
         self.segmentation = None
         return self
 
@@ -136,6 +140,10 @@ class DataProcessor:
 
     def find_registration_transforms(self, master_pcd: PointCloud, sub_pcds: Sequence[PointCloud]):
         self.registration_transformations = []
+        if self.multiway:
+            self.registration_transformations = execute_multiway_registration([master_pcd] + list(sub_pcds), initial_transformations=self.initial_transformations,
+                                                                              seed=self.seed)
+            return self.registration_transformations
         for i, sub in enumerate(sub_pcds):
             if self.initial_transformations is None:
                 init = execute_global_registration(master_pcd, sub, seed=self.seed)            # data.py:156

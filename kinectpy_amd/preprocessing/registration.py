@@ -83,3 +83,56 @@ def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation
             o3d.pipelines.registration.TransformationEstimationForColoredICP(),
             o3d.pipelines.registration.ICPConvergenceCriteria(relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=iters))
     return result_icp.transformation
+
+
+def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transformations=None, seed=None, preference_loop_closure=None,
+                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False):
+    """[O3D] multiway registration of a rig: pcds[0] is the master.  Not in the reference, whose calibration is the star alone
+    (data.py:137-147); opt-in through DataProcessor(multiway=True).  -> the sub -> master 4x4 list in the form
+    DataProcessor.registration_transformations holds (and the optimised PoseGraph with return_pose_graph).
+
+    1. star edges (i, 0, T_i), certain: the existing chain per sub (execute_global_registration unless an initial transformation
+       is given, then the point-to-plane ICP of execute_point_to_plane_registration);
+    2. loop edges (i, j, X_ij), 1 <= i < j, uncertain: the same ICP of down-sampled cloud i onto down-sampled cloud j from
+       T_j^-1 T_i, all sources of one target in one ops.icp_batch call;
+    3. every edge's information matrix from ops.registration_eval at its transformation and the ICP's distance; an edge without
+       a single correspondence is left out;
+    4. node poses start at T_i; global_optimization with reference_node = 0.
+    preference_loop_closure=None: mu = (median correspondence count of the uncertain edges) * voxel_size^2 -- a closure goes when
+    it disagrees with the rest by more than about one voxel rms over its matched points ("Multiway registration")."""
+    from .. import ops
+    reg = o3d.pipelines.registration
+    threshold = 100                                                       # execute_point_to_plane_registration's
+    S = len(pcds)
+    downs = [preprocess_point_cloud(copy.deepcopy(p), voxel_size, 40, with_fpfh=False)[0] for p in pcds]      # prepare_dataset's normals_nn
+    star = [np.eye(4)]
+    for i in range(1, S):
+        if initial_transformations is None:
+            init = execute_global_registration(pcds[0], pcds[i], voxel_size, seed=seed)
+            if init is None:
+                raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)")
+        else:
+            init = initial_transformations[i - 1]
+        star.append(reg.registration_icp(downs[i], downs[0], threshold, init, reg.TransformationEstimationPointToPlane()).transformation)
+    edges = [(i, 0, star[i], False) for i in range(1, S)]
+    for j in range(2, S):
+        Tj_inv = np.linalg.inv(star[j])
+        res = ops.icp_batch([downs[i]._pts for i in range(1, j)], downs[j]._pts, threshold, [Tj_inv @ star[i] for i in range(1, j)],
+                            "p2plane", downs[j]._nrm)
+        edges += [(i, j, r["transformation"], True) for i, r in zip(range(1, j), res)]
+    pose_graph = reg.PoseGraph()
+    pose_graph.nodes = [reg.PoseGraphNode(T) for T in star]
+    counts = []
+    for s, t, X, uncertain in edges:
+        ev = ops.registration_eval(downs[s]._pts, downs[t]._pts, threshold, X)
+        if ev["count"] == 0:
+            continue
+        pose_graph.edges.append(reg.PoseGraphEdge(s, t, X, ev["information"], uncertain))
+        if uncertain:
+            counts.append(ev["count"])
+    if preference_loop_closure is None:
+        preference_loop_closure = (float(np.median(counts)) if counts else 1.0) * float(voxel_size) ** 2
+    reg.global_optimization(pose_graph, reg.GlobalOptimizationLevenbergMarquardt(), reg.GlobalOptimizationConvergenceCriteria(),
+                            reg.GlobalOptimizationOption(threshold, edge_prune_threshold, preference_loop_closure, 0))
+    out = [nd.pose.copy() for nd in pose_graph.nodes[1:]]
+    return (out, pose_graph) if return_pose_graph else out

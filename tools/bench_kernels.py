@@ -231,6 +231,9 @@ def main():
     ops.prof_begin(256)
     ms, _ = timed(lambda: ops.nn_search(s, t, np.eye(4)), reps=5, warm=1)
     report("nn_search 100k x 100k, cold", ms, dense_equivalent_flops=int(dense), **sweep(ops.prof_end()))
+    ms_eval, r = timed(lambda: ops.registration_eval(s, t, 100.0, np.eye(4)), reps=5, warm=1)
+    report("registration_eval 100k x 100k (evaluate_registration + information matrix: nn_search + one reduction)", ms_eval,
+           nn_search_ms=round(ms, 4), fitness=round(r["fitness"], 5), count=r["count"])
     ops.prof_begin(256)
     ms, r = timed(lambda: ops.icp(s, t, 100.0, None, "p2p", None, 30), reps=5, warm=1)
     report("registration_icp p2p 100k x 100k, 30 it (a16, config 2)", ms, iterations=r["iterations"], fitness=round(r["fitness"], 5),
