@@ -569,10 +569,8 @@ int kpx_stream_pending(const kpx_stream *stream);
 int kpx_stream_capacity(const kpx_stream *stream);    /* frames kpx_stream_submit takes before a pop: 2 x depth on one GPU (one queue, any free worker
                                                          takes the oldest frame), depth with communicators (frame j runs on slot j % depth on every rank) */
 int kpx_stream_destroy(kpx_stream *stream);
-/* h_out4: [0] frames finished by the stream's workers, [1] 1 = the frames' registrations run through the device's ICP engine (one host
- * thread and one HIP stream carry the point-to-plane / point-to-point iterations of EVERY frame in flight in one launch per tick --
- * preprocessing/registration.py:78-84 as called from data.py:144-161, for all frames at once; KPX_STREAM_ENGINE=1 -- measured slower
- * than a chain of launches per frame, the default: DESIGN.md), [2] iteration launches and [3] ticks of that engine since it started (process-wide per device). */
+/* h_out4: [0] frames finished by the stream's workers, [1..3] reserved: always 0 (they reported an all-frames ICP scheduler that
+ * was measured slower than a chain of launches per frame and removed: DESIGN.md section 5.2). */
 int kpx_stream_stats(const kpx_stream *stream, uint64_t *h_out4);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------- */

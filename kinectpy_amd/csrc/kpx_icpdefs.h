@@ -1,0 +1,184 @@
+// kpx_icpdefs.h -- what the registration's headers share: tile constants, compile-time knobs, the state of a registration, the
+// argument blocks of the iteration kernels and a few device helpers (kpx_nndense.h, kpx_icpsolve.h, kpx_nnlocal.h, kpx_icpiter.h,
+// kpx_icprows.h; the map is at the top of kpx_icp.hip).
+#pragma once
+#include <limits.h>
+
+#include "kpx_internal.h"
+
+namespace kpx {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+#ifndef KPX_ICP_WPE
+#define KPX_ICP_WPE 3                            // waves per SIMD the iteration kernels are register-budgeted for
+#endif
+
+#ifndef KPX_ICP_WAVES
+#define KPX_ICP_WAVES 4
+#endif
+constexpr int kIWaves = KPX_ICP_WAVES;       // waves (16-row tiles) per block: a block lives as long as its slowest wave
+constexpr int kIThreads = kIWaves * 64;
+constexpr int kRT = 2;                       // 16-row tiles per wave (the sweep below is written for 2)
+constexpr int kWaves = 4;
+constexpr int kRowsPerBlock = kWaves * kRT * 16;   // 128
+constexpr int kCT = 32;                      // 16-column tiles per LDS stage (16 KiB)
+#ifndef KPX_NN_CHUNK
+#define KPX_NN_CHUNK 4                       // measured 100k x 100k inside a registration: 2 -> 38.7, 4 -> 39.1, 8 -> 36.5, 16 -> 35.9 TFLOP/s
+#endif
+
+constexpr int kChunk = KPX_NN_CHUNK;         // column tiles per fast-pass chunk of the dense sweep (nn_mfma_kernel)
+constexpr int kStageDoubles = kCT * 64;
+#ifndef KPX_SEED_STRIDE
+#define KPX_SEED_STRIDE 128                 // round 4, operands in curve order, seed = every n-th POINT of the curve: whole bare search 100k x 100k at
+                                            // 8 / 16 / 32 / 64 / 128 / 256 -> 0.42 / 0.47 / 0.49 / 0.51 / 0.515 / 0.52 of the fp64 matrix peak (the
+                                            // main sweep no longer cares how loose the bound is: a row reaches only the chunks around it).
+                                            // Until round 3 (operands in the caller's order, every n-th TILE): 64 -> 2.60 ms, 16 -> 2.48, 8 -> 2.66
+#endif
+constexpr int kSeedStride = KPX_SEED_STRIDE;  // the seed sweep visits every kSeedStride-th target tile
+constexpr double kSentinel = 1e300;
+constexpr int kFRT = 4;                      // f32 screening sweep: 16-row tiles per wave
+constexpr int kFRowsPerBlock = kWaves * kFRT * 16; // 256
+constexpr int kFCT = 64;                     // f32 tiles per LDS stage (16 KiB)
+constexpr int kFStageFloats = kFCT * 64;
+constexpr int kCand = 64;                    // candidate slots per source row
+constexpr int kAcc = 44;                     // accumulator slots: count, sum d2, sum s, sum t, sum t s^T, J^T J (21), J^T r (6)
+
+struct IcpState {
+    double T[16];
+    double fitness, rmse;
+    double count;
+    int32_t iter, done;
+    double motion, reach;      // see LightSkip: accumulated bound on how far any source point has moved; reach of a row's search
+    double last_motion;        // what the latest update added to `motion` (row certificates: how calm the registration is)
+    double smax;               // largest |T p| over the source's bounding box under the CURRENT T (the next update's lever arm); < 0: not known yet
+};
+
+__device__ __forceinline__ void xform_row(const double *__restrict__ T, const float *__restrict__ p, double s[3])
+{
+    const double x = p[0], y = p[1], z = p[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = fma(T[4 * k], x, fma(T[4 * k + 1], y, fma(T[4 * k + 2], z, T[4 * k + 3])));
+}
+__device__ __forceinline__ double row_seed(const double s[3]) { return fma(s[0], s[0], fma(s[1], s[1], s[2] * s[2])) + 1.0; }
+__device__ __forceinline__ int opaque_i(int v) { asm volatile("" : "+v"(v)); return v; }
+// bits 33..39 of a progress word: the share of the registration's rows the iteration searched, in 1/127ths rounded up (0 = none)
+__host__ __device__ __forceinline__ unsigned long long progress_searched(unsigned long long searched, int64_t n)
+{
+    const unsigned long long cls = n > 0 ? (searched * 127ull + (unsigned long long)n - 1ull) / (unsigned long long)n : 0ull;
+    return (cls > 127ull ? 127ull : cls) << 33;
+}
+// the searched-row counts of a registration: eight words behind its ticket, read (device-coherent) and cleared by the block that drew the
+// last ticket; every lane < 8 of the calling wave takes one word, the total comes back in every lane of that wave's first 8-lane group
+constexpr int kSearchedWord = 8;
+__device__ __forceinline__ unsigned long long searched_take(unsigned long long *ticket, int lane_in_block)
+{
+    unsigned long long v = 0ull;
+    if (lane_in_block < 8) {
+        v = __hip_atomic_load(ticket + kSearchedWord + lane_in_block, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ticket + kSearchedWord + lane_in_block, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane_in_block < 64) {                              // (wave 0: an 8-lane butterfly; the other waves of a block do not publish)
+        unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+            const unsigned ol = (unsigned)__shfl_xor((int)lo, o, 64), oh = (unsigned)__shfl_xor((int)hi, o, 64);
+            const unsigned long long sum = (((unsigned long long)hi << 32) | lo) + (((unsigned long long)oh << 32) | ol);
+            lo = (unsigned)sum; hi = (unsigned)(sum >> 32);
+        }
+        v = ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+// balanced tree over 16 adjacent values: (((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7))) + (the same over x8..x15) -- the order in which four
+// butterfly steps (lane ^ 1, lane ^ 2, half-row mirror, row mirror) add the 16 lanes of a DPP row (row16_tree_sum, kpx_icprows.h)
+__device__ __forceinline__ double tile_tree16(const double *x)
+{
+    double a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = x[2 * i] + x[2 * i + 1];
+    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+typedef unsigned u2 __attribute__((ext_vector_type(2)));
+// high word of the IEEE pattern as a 32-bit register reference (a shift of the 64-bit pattern makes hipcc
+// compare zero-extended 64-bit values, i.e. the slow v_cmp_*_u64 this prefilter exists to avoid)
+__device__ __forceinline__ unsigned hi32(double v) { return __builtin_bit_cast(u2, v)[1]; }
+
+// centre and radius of the target for the float32 screening operands (nn_aux_kernel, kpx_nndense.h)
+struct NnAux {
+    double c[3];      // centre used for the f32 operands
+    double rt2;       // >= max_j |t_j - c|^2
+};
+
+struct Mat16 {
+    double m[16];
+};
+static Mat16 mat16_from(const double *h)
+{
+    Mat16 m;
+    for (int q = 0; q < 16; ++q) m.m[q] = h[q];
+    return m;
+}
+
+// policy and per-registration arguments of the iteration kernels (kpx_icpiter.h, kpx_icprows.h)
+struct CertPolicy {
+    float calm, factor, smin, smax;      // KPX_CERT_CALM / _FACTOR / _SKIN_MIN / _SKIN_MAX (fractions of the correspondence distance)
+};
+struct IcpFuse {
+    IcpState *pair;
+    unsigned long long *ring;
+    int max_iter;
+    double rel_fit, rel_rmse;
+    double *result;
+    unsigned long long *progress, tag;
+    unsigned long long *ticket;        // non-null (with pair == nullptr): the LAST block of the launch to deliver its sums performs the update
+    double *light_key;                 // with ticket: per block, LightSkip key (0 = sweep); nullptr: every block sweeps
+    const double *sbbox;               // with light_key: the source's bounding box
+    uint32_t *cert;                    // with light_key: per sorted row, the certificate: L as a float rounded down to 17 mantissa bits | the iteration
+                                       // of the search in the low 6 bits (0 = none); nullptr: every row is searched
+    double *thist;                     // with cert: the transforms of iterations 0 .. 63, 12 doubles each (the winner writes entry k + 1)
+    int cert_check;                    // self-check mode: certified rows are searched anyway and compared (g_cert_check)
+    CertPolicy pol;
+    double *chain_rec;                 // icp_iter_body<true> only: the registration's records (kChainRecords x kChainRec doubles)
+    unsigned long long *stamp;         // icp_iter_body<true>, KPX_ICP_CHAIN_STAMPS=1: this iteration's row of g_chain_stamp
+};
+// one registration of a batch launch (icp_iter_batch_kernel, icp_chain_kernel, icp_rows_kernel's host side)
+constexpr int kIcpBatchMax = 8;
+struct IcpProblem {
+    const float *src;
+    const int32_t *row_of;
+    float *src_sorted;
+    int32_t *idx_sorted;
+    float *ptgt_sorted;
+    int32_t *idx_cur;
+    double *d2_cur;
+    IcpState *pair;
+    unsigned long long *ring;
+    double *result;
+    unsigned long long *progress;
+    double *light_key;
+    const double *sbbox;
+    uint32_t *cert;
+    double *thist;
+    double *chain_rec;
+    int64_t n;
+    uint32_t block0, blocks;
+    // round 5: every problem carries its own target operands, iteration number and progress tag, so that one launch can hold the
+    // registrations of SEVERAL frames in flight, each at the iteration it has reached (icp_rows_kernel; icp_chain_kernel, which iterates
+    // by itself over one shared target, takes these as kernel arguments instead)
+    const float *tgt, *tn;
+    const double *Bs;
+    const int32_t *orig;
+    const float *tile_box, *group_box;
+    const double *tbbox;
+    int32_t n_groups, k;
+    unsigned long long tag;
+};
+struct IcpBatchArgs {
+    IcpProblem p[kIcpBatchMax];
+    int32_t count;
+};
+struct Mat16x8 {
+    double m[kIcpBatchMax][16];
+};
+
+}  // namespace kpx

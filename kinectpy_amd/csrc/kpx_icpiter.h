@@ -1,0 +1,781 @@
+// kpx_icpiter.h -- one iteration of the culled registration in one kernel: icp_iter_body and the kernels built on it (one
+// registration, a batch per launch, the whole chain in one launch), the update kernel of a batch and its init kernel, and the
+// profiling words these kernels write.  The __device__ globals live here, so this header belongs to ONE translation unit
+// (kpx_icp.hip: the library is built without relocatable device code).
+#pragma once
+#include "kpx_icpdefs.h"
+#include "kpx_fixed.h"
+#include "kpx_icpsolve.h"
+#include "kpx_nnlocal.h"
+
+namespace kpx {
+
+// ---- one ICP iteration in one kernel (culled engine) -----------------------------------------------------------
+// Block = 4 waves x 16 sorted rows.  Prologue: lanes 0..15 of a wave transform their row, seed it and bound it
+// with last iteration's partner (clamped to the correspondence distance); the wave sweeps (sweep_wave); lanes 0..15
+// then form the chosen pair's direct distance (AC3) and the row's contribution to the update sums, which are added
+// in a fixed order per block and added to the exact fixed-point accumulators; icp_solve_fixed_kernel performs the
+// update step (kpx_icp).  Running the update redundantly in the prologue of the next launch (IcpFuse below) puts the serial
+// 6x6 / eigen algebra (~5-8 us) in front of every block's sweep against 5.7 us + 1.9 us for the solve kernel and its
+// boundary: for one large registration (100k x 100k: five rounds of blocks per launch) it was 20 % slower, so kpx_icp
+// keeps two kernels per iteration; kpx_icp_batch, whose small problems fit one round of blocks and whose chains are
+// bound by the host's launch rate, uses the one-launch form.
+// ("Last block finishes the job" inside this launch was measured twice and lost both times: with plain stores +
+// __threadfence() the release writes back / invalidates the XCD's L2 once per block (10x slower); with write-through
+// device-scope stores, a drained vmcnt and a relaxed ticket it still adds ~13 us at 485 blocks -- the same-address
+// ticket atomics serialise at ~12 ns each and the last block reads 170 KB through sc1 loads -- against ~11 us for
+// the boundary + the 1024-thread solve kernel.)
+constexpr int kIRows = kIWaves * kLRows;
+// One launch per iteration (used by kpx_icp_batch, whose chains are bound by the host's launch rate once several
+// registrations and two frames run side by side): launch k first performs the update of iteration k-1 -- every block
+// folds the accumulator set of the previous launch and runs the (deterministic) algebra itself, block 0 publishes the
+// state, the result and the progress word -- then sweeps with the new transform.  Three accumulator sets in a ring
+// (launch k reads set k-1, adds to set k, block 0 clears set k+1) and two state slots (launch k reads slot k-1, writes
+// slot k) keep the launches free of races.  pair == nullptr: two-kernel mode, icp_solve_fixed_kernel does the update.
+constexpr int kCertHist = 64;                 // iterations whose transforms are kept for the certificates (6 bits of the word)
+// The whole chain in ONE launch (icp_chain_kernel): the blocks of a registration stay resident and iterate; the hand-off between
+// iterations is a RECORD per iteration -- the registration's state as the update of iteration k - 1 left it -- whose 23 words the
+// winner (the block that drew the last ticket) writes with device-coherent stores and wave 0 of every block polls with
+// device-coherent loads, each lane ITS word, until none of them is the "empty" pattern any more (a NaN payload no computation
+// produces): every word validates itself, so there is no flag, no release and no second round trip.
+constexpr int kChainRec = 32;                 // doubles per record (23 used)
+constexpr int kChainRecords = 64;             // records 0 .. max_iteration + 1: the chain form serves max_iteration <= 62
+constexpr int kChainWords = 24;                // = sizeof(IcpState) / 8
+constexpr unsigned long long kChainEmpty = 0xFFF8C0DEC0DEC0DEull;
+constexpr int kAccSet = kAccCopies * kAcc * kFixedWords;
+// Phase clock of the iteration kernel (while the profiler is armed): thread 0 of every block stores 100 MHz wall-clock stamps in
+// its own row of g_icp_stamp -- [0] block start, [1] after the update prologue, [2] after row preparation, [3] after the culled
+// sweep, [4] after the pair epilogue, [5] block end.  Plain stores to private slots: the clock does not disturb what it times.
+// The rows of the LAST launch are read by kpx_prof_icp_phases.
+constexpr int kStampBlocks = 4096;
+__device__ unsigned long long g_icp_stamp[kStampBlocks][8];
+// per WAVE of the last sweep launch: [0] sweep start, [1] sweep end (100 MHz), [2] the packed counters sweep_wave returns, [3] rows
+// of the wave that ended with a partner
+__device__ unsigned long long g_icp_wave[kStampBlocks * 4][4];
+// Certificate self-check (KPX_ICP_CERT_CHECK=1): certified rows are searched all the same and the search's winner is compared with the
+// partner the certificate kept.  [0] rows certified, [1] rows searched, [2] certified rows whose search disagreed, [3..7] the first
+// disagreement: iteration, sorted row, kept partner, found partner, key as float bits.  Read (and cleared) by kpx_prof_icp_cert.
+__device__ unsigned long long g_cert_check[8];
+// Clock of the one-launch chain (KPX_ICP_CHAIN_STAMPS=1, first registration of the launch; 100 MHz stamps, one row per iteration):
+// block 0: [0] record seen, [1] rows prepared, [2] sweep over, [3] sums added, [4] ticket drawn; over all blocks: [5] latest / [10]
+// earliest "record seen", [11] latest "sums added", [6] latest ticket; the winner: [7] totals read, [8] update done, [9] record published.
+__device__ unsigned long long g_chain_stamp[64][48];    // [32 ..]: the winner's update step from inside (icp_finish_wave, tick)    // [16 ..]: block 0 wave 0's sweep (sweep_wave, dbg_tick)
+__device__ __forceinline__ void chain_tick(unsigned long long *row, int slot, bool on)
+{
+    if (row && on) row[slot] = wall_clock64();
+}
+__device__ __forceinline__ void phase_tick(unsigned long long *__restrict__ armed, int slot, unsigned bid)
+{
+    if (!armed || threadIdx.x || bid >= kStampBlocks) return;
+    __builtin_nontemporal_store(wall_clock64(), &g_icp_stamp[bid][slot]);
+}
+// Certificates: rows whose partner provably cannot change are not searched again.
+// A sweep knows more than the winner: every column it multiplied gives D, every box it culled was farther than the row's culling
+// bound.  L = sqrt(min(final culling bound, smallest D - 1 among the multiplied columns OTHER than the winner)) is therefore a lower
+// bound of the distance from the row to every other target point.  The row keeps (p_c, L): its position at that search and L.  In a
+// later iteration it stands at p, every other target is still >= L - |p - p_c| away (triangle inequality, the row's OWN displacement:
+// no global bound), and if the partner's own (exactly evaluated) distance d1 is smaller than that -- d1 + |p - p_c| < L, with margins
+// for the float32 copy of p_c and the roundings -- the partner is the STRICT nearest neighbour: an exact search would return it, ties
+// and all, so the row keeps it without one.  Rows without a partner use the reach of any row's search in place of d1.  A certificate
+// is worth something only if the search looked beyond its partner: once the registration is calm (the last update moved no point by
+// more than `calm` x the correspondence distance; IcpState::last_motion, LightSkip's bookkeeping) uncertified rows are searched with a
+// skin around their partner, `factor` x that motion (between `smin` and `smax` x the correspondence distance): a few more tiles
+// multiplied once, no search at all in the iterations that follow.  Waves whose 16 rows are all certified skip the sweep, the others
+// cull with the box and bounds of their uncertified rows only.  Partners, sums and transforms are those of the full search, bit for
+// bit.  The policy is CertPolicy, above IcpFuse.  (KPX_ICP_CERT=0 switches the certificates off: test_icp_update_placements_and_light_skip_are_bit_identical; KPX_ICP_CERT_CHECK=1
+// searches the certified rows all the same and counts disagreements: test_icp_certificates_never_contradict_the_search).
+// bid / nblocks: this block's index among the blocks of ITS registration (one launch may carry several, see icp_iter_batch_kernel)
+template <bool PERSIST = false>
+__device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned nblocks, const float *__restrict__ src, int64_t n, const float *__restrict__ tgt,
+                                                       const float *__restrict__ tn, const double *__restrict__ Bs,
+                                                       const int32_t *__restrict__ orig, const float *__restrict__ tile_box,
+                                                       const float *__restrict__ group_box, int32_t n_groups,
+                                                       const double *__restrict__ tbbox, const int32_t *__restrict__ row_of,
+                                                       const float *__restrict__ src_sorted, int32_t *__restrict__ idx_sorted,
+                                                       float *__restrict__ ptgt_sorted,
+                                                       int32_t *__restrict__ idx_cur, double *__restrict__ d2_cur, double max_d2, int mode,
+                                                       int k, const IcpState *__restrict__ st, unsigned long long *acc,
+                                                       unsigned long long *__restrict__ tile_visits, IcpFuse fuse)
+{
+    // (chain form: the thread number behind an opaque move, taken anew in every iteration -- otherwise everything derived from it,
+    // LDS addresses first of all, is hoisted out of the chain's loop and held in registers this kernel does not have)
+    const unsigned tix = PERSIST ? (unsigned)opaque_i((int)threadIdx.x) : threadIdx.x;
+    __shared__ IcpState s_state;
+    __shared__ double s_sums[kAcc];
+    // PERSIST (icp_chain_kernel: this body runs once per iteration inside ONE launch, `st` is the block's LDS copy of the iteration's
+    // record): what a row carries from one iteration to the next -- its coordinates, its partner (index, coordinates, normal), its
+    // certificate, the block's LightSkip key -- stays in LDS; nothing but constants is read from memory after iteration 0.
+    __shared__ float rowk[kIWaves][16][8];           // what a row carries across the sweep (its previous partner: coordinates, normal, index),
+                                                     // parked here: a value in 16 lanes costs a whole register through the multiply loop
+    __shared__ float rowsrc[kIWaves][16][3];
+    __shared__ uint32_t rowc[kIWaves][16];
+    __shared__ int32_t rowi[kIWaves][16][2];         // partner (bound / result), original row
+    __shared__ double s_key;
+    const int wave = PERSIST ? __builtin_amdgcn_readfirstlane((int)(tix >> 6)) : (int)(tix >> 6), lane = tix & 63, q = lane >> 4, j = lane & 15;
+    const int64_t row_base = ((int64_t)bid * kIWaves + wave) * kLRows;
+    const int64_t last = n - 1;
+    const unsigned long long t_block_start = (tile_visits && tix == 0) ? wall_clock64() : 0ull;
+    const double t2max = target_t2max(tbbox);
+    // An iteration is a chain of dependent memory round trips, so everything that does not depend on this iteration's
+    // transform is requested FIRST -- the wave's rows, their previous partners (index AND coordinates, kept in sorted-row
+    // order by the previous launch: no gather through the index), the first 128 group boxes -- and arrives while the update
+    // algebra of the previous iteration runs below.
+    float my_src[3] = { 0.0f, 0.0f, 0.0f }, my_pt[3] = { 0.0f, 0.0f, 0.0f }, my_nrm[3] = { 0.0f, 0.0f, 0.0f };
+    int32_t my_row = 0, my_prev = -1;
+    uint32_t my_cert = 0u;
+    const bool certs = fuse.ticket && fuse.light_key && fuse.cert;
+    if (PERSIST && k > 0) {
+        if (lane < 16) {
+            my_row = rowi[wave][lane][1];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { my_src[a] = rowsrc[wave][lane][a]; my_pt[a] = rowk[wave][lane][a]; my_nrm[a] = rowk[wave][lane][3 + a]; }
+            my_prev = __float_as_int(rowk[wave][lane][6]);
+            if (certs) my_cert = rowc[wave][lane];
+        }
+    } else if (lane < 16) {
+        const int64_t r = row_base + lane < last ? row_base + lane : last;
+        if (idx_cur || d2_cur) my_row = row_of[r];           // only the caller-order outputs need the original row number
+#pragma unroll
+        for (int a = 0; a < 3; ++a) my_src[a] = src_sorted[3 * r + a];
+        if (PERSIST) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) rowsrc[wave][lane][a] = my_src[a];
+            rowc[wave][lane] = 0u;
+        }
+        if (k > 0) {
+            my_prev = idx_sorted[r];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) my_pt[a] = ptgt_sorted[3 * r + a];
+            if (certs) my_cert = fuse.cert[r];
+        }
+    }
+    // (certificates) the transforms of the iterations so far: a certified row's position at its search is recomputed from them, exactly
+    __shared__ double s_thist[kCertHist][12];
+    if (PERSIST) {                                        // (the earlier entries are still there; a barrier follows before the rows use them)
+        if (certs && k < kCertHist && tix < 12) s_thist[k][tix] = st->T[tix];
+    } else if (certs && k > 0)
+        for (int e = tix; e < 12 * (k < kCertHist ? k : kCertHist); e += kIThreads) (&s_thist[0][0])[e] = fuse.thist[e];
+    GroupPre gpre;
+    group_pre_load(gpre, group_box, n_groups, lane);
+    if (!PERSIST && mode == 1 && k > 0 && lane < 16) {
+        // the previous partner's normal, requested through the index as soon as that has arrived (behind everything that does not
+        // depend on anything): it is not needed before the pair epilogue, where an unchanged partner -- the rule in the late
+        // iterations -- then costs no round trip at all
+        const float *np_ = tn + 3 * (int64_t)(my_prev > 0 ? my_prev : 0);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) my_nrm[a] = np_[a];
+    }
+    const double *Tk = st->T;
+    // (ticket mode) the registration's state, copied into LDS while everything else loads: the block that draws the last ticket runs the
+    // update step on this copy -- fitness / rmse / T / motion were four dependent global round trips inside a step that every launch waits
+    // for -- and writes the new state back in one burst
+    static_assert(sizeof(IcpState) % sizeof(double) == 0, "IcpState is copied as doubles");
+    if (fuse.ticket && tix < sizeof(IcpState) / sizeof(double))
+        reinterpret_cast<double *>(&s_state)[tix] = reinterpret_cast<const double *>(st)[tix];
+    if (fuse.pair) {
+        const IcpState *in = fuse.pair + ((k + 1) & 1);
+        IcpState *out = fuse.pair + (k & 1);
+        // state and accumulators are read in ONE round trip (the sums of a converged chain are simply not used)
+        const unsigned long long *prev = fuse.ring + (int64_t)((k + 2) % 3) * kAccSet;
+        if (k > 0 && tix < kAcc) s_sums[tix] = (int)tix < (mode == 1 ? kAcc : 17) ? fixed_total(prev, tix) : 0.0;
+        if (tix == 0) s_state = *in;
+        __syncthreads();
+        if (s_state.done) {                               // converged earlier: hand the state on, nothing else to do
+            if (bid == 0 && tix == 0) *out = s_state;
+            return;
+        }
+        __shared__ FinishScratch s_fs;
+        if (k > 0 && wave == 0)
+            icp_finish_wave(s_sums, n, mode, k - 1, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, &s_state, bid == 0 ? fuse.result : (double *)nullptr,
+                            s_fs, lane);
+        __syncthreads();
+        if (bid == 0) {
+            unsigned long long *next = fuse.ring + (int64_t)((k + 1) % 3) * kAccSet;
+            for (int e = tix; e < kAccSet; e += kIThreads) next[e] = 0ull;
+            if (tix == 0) {
+                *out = s_state;
+                if (k > 0 && fuse.progress)
+                    __hip_atomic_store(fuse.progress, fuse.tag | ((unsigned long long)(s_state.done ? 1 : 0) << 32) | (unsigned long long)(unsigned)k,
+                                       __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+        if (s_state.done) return;
+        Tk = s_state.T;
+        acc = fuse.ring + (int64_t)(k % 3) * kAccSet;
+    } else if (st->done) return;
+    // LightSkip: nothing of this block can have come within reach since it was last swept -> straight to the ticket
+    bool skip = false;
+    if (fuse.ticket && fuse.light_key) {
+        const double key = PERSIST ? (k > 0 ? s_key : 0.0) : fuse.light_key[bid];
+        skip = key > 0.0 && (st->motion + st->reach) * (1.0 + 1e-6) + 1e-6 < key;
+    }
+    __shared__ double s_light[kIWaves];
+    const int nacc = mode == 1 ? kAcc : 17;
+    if (tile_visits && tix == 0 && bid < kStampBlocks) { g_icp_stamp[bid][7] = skip ? 1ull : 0ull; g_icp_stamp[bid][6] = (unsigned long long)nblocks; }
+    do {
+    if (skip) break;
+    __shared__ int32_t lists[kIWaves][kLScratch];
+    __shared__ double rowd[kIWaves][16][kRowStride]; // s_x, s_y, s_z, (the sweep's row bound), K, bound / result value
+    __shared__ float rowf[kIWaves][16][kRowFStride]; // float32 mirror of the rows for the sweep's culling tests
+    __shared__ double sh[kAcc][kIRows + 1];
+    if (tile_visits && tix == 0 && bid < kStampBlocks) {     // only launches that sweep stamp (not the converged / closing ones)
+        g_icp_stamp[bid][0] = t_block_start;
+        g_icp_stamp[bid][6] = (unsigned long long)nblocks;
+    }
+    phase_tick(tile_visits, 1, bid);
+    // s_thist was staged by all threads of the block and is read by the rows of every wave (until this barrier was added the
+    // per-launch form relied on the waves of a block running in step: a row could read an entry before another wave had written it)
+    if (certs && (k > 0 || PERSIST)) __syncthreads();
+    if (PERSIST && fuse.stamp && tix == 0) {
+        const unsigned long long t = wall_clock64();
+        if (bid == 0) fuse.stamp[0] = t;
+        atomicMax(&fuse.stamp[5], t);
+        atomicMin(&fuse.stamp[10], t);
+    }
+
+    // Row certificates (kpx_icp.hip, "Certificates" above icp_iter_body): how calm the registration is decides the skin
+    const double c_reach = certs ? st->reach : 0.0;
+    double c_skin = 0.0;
+    if (certs && k > 0) {
+        const double lm = st->last_motion, md = sqrt(max_d2);
+        if (lm <= (double)fuse.pol.calm * md) c_skin = fmin(fmax((double)fuse.pol.factor * lm, (double)fuse.pol.smin * md), (double)fuse.pol.smax * md);
+    }
+    bool my_active = true, my_certd = false;
+    if (lane < 16) {
+        const int64_t i = my_row;
+        double s[3];
+        xform_row(Tk, my_src, s);
+        const double seed = row_seed(s);
+        double bv = INFINITY;
+        int32_t bj = INT_MAX;
+        if (k > 0) {
+            const int32_t p = my_prev;
+            if (p >= 0) {
+                const double tx = my_pt[0], ty = my_pt[1], tz = my_pt[2];
+                const double t2 = fma(tx, tx, fma(ty, ty, tz * tz));
+                double d = fma(s[0], -2.0 * tx, seed);
+                d = fma(s[1], -2.0 * ty, d);
+                d = fma(s[2], -2.0 * tz, d);
+                bv = fma(1.0, t2, d);
+                bj = p;
+            }
+        }
+        const double clamp = (max_d2 + 1.0) * (1.0 + 9.31322574615478515625e-10) + ldexp(seed + t2max + 1.0, -38);
+        if (!(bv <= clamp)) { bv = clamp; bj = INT_MAX; }
+        double rb0 = bv - 1.0;
+        if (certs) {
+            // d1: an upper bound of the distance from the row to its partner (a row without one: the reach of any row's search)
+            double d1 = c_reach;
+            if (bj != INT_MAX) {
+                const double dx = s[0] - (double)my_pt[0], dy = s[1] - (double)my_pt[1], dz = s[2] - (double)my_pt[2];
+                d1 = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) * (1.0 + 1e-12);
+            }
+            // certified: every other target point was >= L away from p_c, the row has moved by |p - p_c| since (p_c is kept as float32:
+            // 2^-24 relative per coordinate, covered by the 1e-6 relative margin on the coordinates' scale), and its partner (or the
+            // reach of a row without one) is nearer than what is left of L.  A row that HAD a partner and lost it to the clamp is
+            // searched (the certificate says nothing about that partner).
+            const bool keeps = (my_prev >= 0) == (bj != INT_MAX);
+            const int kc = (int)(my_cert & 63u);
+            const float Lc = __uint_as_float(my_cert & ~63u);
+            double pc[3] = { 0.0, 0.0, 0.0 };
+            if (Lc > 0.0f) {                                     // the row's position at that search: AC1 with that iteration's transform
+                const double *Th = s_thist[kc];
+                const double x = my_src[0], y = my_src[1], z = my_src[2];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) pc[a] = fma(Th[4 * a], x, fma(Th[4 * a + 1], y, fma(Th[4 * a + 2], z, Th[4 * a + 3])));
+            }
+            const double ex = s[0] - pc[0], ey = s[1] - pc[1], ez = s[2] - pc[2];
+            const double moved = sqrt(fma(ez, ez, fma(ey, ey, ex * ex))) * (1.0 + 1e-12);
+            const bool certd = Lc > 0.0f && keeps && (d1 + moved) * (1.0 + 1e-6) + 1e-6 < (double)Lc;
+            my_active = (!certd || fuse.cert_check) && row_base + lane <= last;
+            my_certd = certd && row_base + lane <= last;
+            if (certd && !fuse.cert_check) rb0 = -1.0;
+            else if (c_skin > 0.0) { const double rr = d1 + c_skin; rb0 = fmax(rb0, rr * rr); }
+        }
+        rowd[wave][lane][0] = s[0]; rowd[wave][lane][1] = s[1]; rowd[wave][lane][2] = s[2];
+        rowd[wave][lane][3] = rb0;
+        rowd[wave][lane][4] = seed; rowd[wave][lane][5] = bv;
+        rowi[wave][lane][0] = bj; rowi[wave][lane][1] = (int32_t)i;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { rowk[wave][lane][a] = my_pt[a]; rowk[wave][lane][3 + a] = my_nrm[a]; }
+        rowk[wave][lane][6] = __int_as_float(my_prev);
+    }
+    if (PERSIST && fuse.stamp) {          // who is searched, and why (chain clock: [26] waves, [27] rows, [28] rows without partner, [29] rows without certificate)
+        const bool searched = lane < 16 && my_active && !my_certd;
+        const unsigned long long sm = __builtin_amdgcn_ballot_w64(searched);
+        const unsigned long long np = __builtin_amdgcn_ballot_w64(searched && my_prev < 0);
+        const unsigned long long nc = __builtin_amdgcn_ballot_w64(searched && (my_cert & ~63u) == 0u);
+        if (lane == 0 && sm) {
+            atomicAdd(&fuse.stamp[26], 1ull); atomicAdd(&fuse.stamp[27], (unsigned long long)__builtin_popcountll(sm));
+            atomicAdd(&fuse.stamp[28], (unsigned long long)__builtin_popcountll(np)); atomicAdd(&fuse.stamp[29], (unsigned long long)__builtin_popcountll(nc));
+        }
+    }
+    const unsigned act_mask = (unsigned)(__builtin_amdgcn_ballot_w64(lane < 16 && my_active) & 0xFFFFull);
+    const unsigned certd_mask = (unsigned)(__builtin_amdgcn_ballot_w64(lane < 16 && my_certd) & 0xFFFFull);
+    wave_lds_fence();
+    WaveRows w;
+    w.a = q < 3 ? rowd[wave][j][q] : 1.0;
+    w.rows = &rowd[wave][0][0];
+    w.rowsf = &rowf[wave][0][0];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int rr = q + 4 * r;
+        w.seed[r] = rowd[wave][rr][4];
+        w.best[r] = rowd[wave][rr][5];
+        w.bcol[r] = rowi[wave][rr][0];
+        w.rb0[r] = rowd[wave][rr][3];
+    }
+    w.skin = c_skin;
+    w.act_mask = act_mask;
+    w.light_gap2 = -1.0;
+    w.dbg = (PERSIST && fuse.stamp && bid == 0 && wave == 0) ? fuse.stamp + 16 : (unsigned long long *)nullptr;
+    phase_tick(tile_visits, 2, bid);
+    if (PERSIST) chain_tick(fuse.stamp, 1, bid == 0 && tix == 0);
+    const unsigned long long t_sweep = tile_visits ? wall_clock64() : 0ull;
+    unsigned long long swept = 0ull;
+    int lane_p = 0, wave_p = 0, q_p = 0, j_p = 0;
+    int64_t row_base_p = 0;
+    auto rederive = [&]() {
+        lane_p = opaque_i((int)(threadIdx.x & 63)); wave_p = opaque_i((int)(threadIdx.x >> 6)); q_p = lane_p >> 4; j_p = lane_p & 15;
+        row_base_p = ((int64_t)bid * kIWaves + wave_p) * kLRows;
+    };
+    if (act_mask != 0u) {                                 // (a wave whose 16 rows are all certified keeps what it came with)
+        wave_lds_fence();                                 // rowd[..][3] is the sweep's own slot from here on
+        swept = sweep_wave<true, true, PERSIST>(w, Bs, orig, tile_box, group_box, n_groups, t2max, lists[wave], &gpre);
+        rederive();
+        // new keys for the rows that were searched: L^2 = min(final culling bound, runner-up among the multiplied columns), both on d^2
+        if (certs && fuse.cert_check && j_p == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr = q_p + 4 * r;
+                if (((certd_mask >> rr) & 1u) != 0u && w.bcol[r] != rowi[wave_p][rr][0]) {
+                    if (atomicAdd(&g_cert_check[2], 1ull) == 0ull) {
+                        g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = (unsigned long long)(row_base_p + rr);
+                        g_cert_check[5] = (unsigned long long)(unsigned)rowi[wave_p][rr][0]; g_cert_check[6] = (unsigned long long)(unsigned)w.bcol[r];
+                        g_cert_check[7] = (unsigned long long)((PERSIST ? rowc[wave_p][rr] : fuse.cert[row_base_p + rr]) & ~63u);
+                    }
+                }
+            }
+        }
+        if (certs && j_p == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr = q_p + 4 * r;
+                if (((act_mask >> rr) & 1u) != 0u && ((certd_mask >> rr) & 1u) == 0u) {
+                    typedef unsigned uu2 __attribute__((ext_vector_type(2)));
+                    const uu2 pat = { 0u, w.sec[r] };
+                    const double d2nd = w.sec[r] == 0xFFFFFFFFu ? INFINITY : __builtin_bit_cast(double, pat) - 1.0 - w.eps_out;
+                    const double l2 = fmin(w.rb_out[r], d2nd);
+                    // L rounded DOWN to a float with its low six mantissa bits cleared; those bits carry the iteration (k < 64: later iterations
+                    // of a longer chain are searched every time)
+                    const uint32_t lb = l2 > 0.0 && k < kCertHist ? (__float_as_uint(f32_down(sqrt(l2) * (1.0 - 1e-7))) & ~63u) : 0u;
+                    const uint32_t cw = lb > 63u ? (lb | (uint32_t)k) : 0u;
+                    if (PERSIST) rowc[wave_p][rr] = cw; else fuse.cert[row_base_p + rr] = cw;
+                }
+            }
+        }
+    }
+    if (act_mask == 0u) rederive();
+    // how much of the registration is still searched: what the host picks the next launches' form by (icp_rows_kernel once most rows
+    // carry a certificate).  One returning add per BLOCK into one of eight words behind the ticket (kSearchedWord: same-address atomics
+    // serialise at ~12 ns each -- one word per registration cost 20 us per launch), waited for like the sums' adds.
+    __shared__ int s_cnt[kIWaves];
+    if (lane_p == 0) s_cnt[wave_p] = __builtin_popcount(act_mask & ~certd_mask);
+    const unsigned visited = (unsigned)(swept & 0xFFFFu);
+    if (certs && fuse.cert_check && lane_p == 0) {
+        if (bid == 0 && wave_p == 0 && g_cert_check[2] == 0ull) {       // no disagreement so far: [3..7] report the chain's state at its last launch
+            g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = __builtin_bit_cast(unsigned long long, st->last_motion);
+            g_cert_check[5] = __builtin_bit_cast(unsigned long long, st->motion); g_cert_check[6] = __builtin_bit_cast(unsigned long long, c_skin);
+        }
+        atomicAdd(&g_cert_check[0], (unsigned long long)__builtin_popcount(certd_mask));
+        atomicAdd(&g_cert_check[1], (unsigned long long)__builtin_popcount(act_mask & ~certd_mask));
+    }
+    // (LightSkip speaks for ALL rows of a block: a wave that left certified rows out of its box does not count as light)
+    if (lane_p == 0) s_light[wave_p] = act_mask == 0xFFFFu ? w.light_gap2 : -1.0;
+    if (tile_visits && lane_p == 0 && bid < kStampBlocks && kIWaves <= 4) {
+        unsigned long long *o = g_icp_wave[bid * 4 + wave_p];
+        int with = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) with += (w.bcol[r] >= 0 && w.bcol[r] != INT_MAX) ? 1 : 0;      // lane 0: rows 0, 4, 8, 12 (a sample)
+        o[0] = t_sweep; o[1] = wall_clock64(); o[2] = swept; o[3] = (unsigned long long)with;
+    }
+    phase_tick(tile_visits, 3, bid);
+    if (PERSIST) chain_tick(fuse.stamp, 2, bid == 0 && lane_p == 0 && wave_p == 0);
+    if (PERSIST && fuse.stamp && bid == 0 && lane_p == 0 && wave_p == 0) { fuse.stamp[13] = swept; fuse.stamp[14] = (unsigned long long)act_mask | ((unsigned long long)certd_mask << 16); }
+    if (tile_visits && lane_p == 0) atomicAdd(tile_visits + ((bid * kIWaves + wave_p) & (kVisitSlots - 1)), (unsigned long long)visited);
+    wave_lds_fence();
+    if (j_p == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rowi[wave_p][q_p + 4 * r][0] = w.bcol[r];
+    }
+    wave_lds_fence();
+
+    // the chosen pairs: direct distance, contribution to the sums (one row per lane 0..15)
+    // (lane / wave numbers re-derived behind an opaque move: the LDS addresses the epilogue needs are then computed HERE instead of being
+    // carried through the sweep -- the kernel sits on its 168-register budget and carried addresses were spilled to scratch memory,
+    // i.e. to HBM traffic)
+    const int lane_e = lane_p, wave_e = wave_p;
+    if (lane_e < 16) {
+        const int col = wave_e * 16 + lane_e;
+        for (int a = 0; a < nacc; ++a) sh[a][col] = 0.0;
+        if (row_base_p + lane_e <= last) {
+            const int32_t bj = rowi[wave_e][lane_e][0];
+            const int64_t i = rowi[wave_e][lane_e][1];
+            const bool none = bj < 0 || bj == INT_MAX;
+            // Partners in the caller's row order (idx_cur / d2_cur: scattered 4- and 8-byte stores) only where a caller asked for
+            // them (kpx_icp with idx / d2 outputs); the sorted-order copies the NEXT launch bounds its rows with only when the
+            // partner changed -- in the late iterations of a registration almost no row changes its partner.
+            const int32_t out_j = none ? -1 : bj;
+            const int32_t prev_j = __float_as_int(rowk[wave_e][lane_e][6]);
+            const bool changed = k == 0 || out_j != prev_j;
+            if (idx_cur) idx_cur[i] = out_j;
+            if (PERSIST) rowk[wave_e][lane_e][6] = __int_as_float(out_j);
+            else if (changed) idx_sorted[row_base_p + lane_e] = out_j;
+            if (none) {
+                if (d2_cur) d2_cur[i] = INFINITY;
+            } else {
+                const double s[3] = { rowd[wave_e][lane_e][0], rowd[wave_e][lane_e][1], rowd[wave_e][lane_e][2] };
+                // The partner's coordinates and its normal are gathered through the index only where the partner CHANGED: those of an
+                // unchanged partner came at the launch's start (coordinates with the row: ptgt_sorted; the normal through the previous
+                // index).  In the late iterations whole waves skip this dependent round trip; both parts of a changed partner are
+                // requested together.
+                float tf[3] = { rowk[wave_e][lane_e][0], rowk[wave_e][lane_e][1], rowk[wave_e][lane_e][2] }, nf[3] = { rowk[wave_e][lane_e][3], rowk[wave_e][lane_e][4], rowk[wave_e][lane_e][5] };
+                if (changed) {
+                    const float *tp = tgt + 3 * (int64_t)bj;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) tf[c] = tp[c];
+                    if (mode == 1) {
+                        const float *np_ = tn + 3 * (int64_t)bj;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) nf[c] = np_[c];
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {                                                   // the next iteration bounds this row with it
+                        if (PERSIST) { rowk[wave_e][lane_e][c] = tf[c]; rowk[wave_e][lane_e][3 + c] = nf[c]; }
+                        else ptgt_sorted[3 * (row_base_p + lane_e) + c] = tf[c];
+                    }
+                }
+                const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
+                const double dx = s[0] - t[0], dy = s[1] - t[1], dz = s[2] - t[2];
+                const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
+                if (d2_cur) d2_cur[i] = d2;
+                if (d2 < max_d2) {
+                    sh[0][col] = 1.0; sh[1][col] = d2;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { sh[2 + c][col] = s[c]; sh[5 + c][col] = t[c]; }
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) sh[8 + 3 * a + c][col] = t[a] * s[c];
+                    if (mode == 1) {
+                        const double nx = nf[0], ny = nf[1], nz = nf[2];
+                        const double res = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
+                        const double J[6] = { s[1] * nz - s[2] * ny, s[2] * nx - s[0] * nz, s[0] * ny - s[1] * nx, nx, ny, nz };
+                        int slot = 17;
+#pragma unroll
+                        for (int a = 0; a < 6; ++a)
+#pragma unroll
+                            for (int c = a; c < 6; ++c) sh[slot++][col] = J[a] * J[c];
+#pragma unroll
+                        for (int a = 0; a < 6; ++a) sh[38 + a][col] = J[a] * res;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    phase_tick(tile_visits, 4, bid);
+    // (the thread number re-derived behind the sweep, like the lane state of the pair epilogue: the accumulator slot's address, a 64-bit
+    // value per lane known from the kernel's first instruction, was otherwise computed there and carried -- spilled -- across the sweep;
+    // every spilled dword is 256 B of scratch per wave written back to HBM at the end of the launch: 0.5 MB per launch at 31k rows)
+    const int tix_e = wave_e * 64 + lane_e;
+    if (tix_e < nacc) {
+        // The sums' contract (round 5): per 16-row TILE a balanced tree over adjacent rows (tile_tree16: what four DPP steps give a
+        // wave that holds one row per lane, icp_rows_kernel), the tiles' partials then added EXACTLY in 128-bit fixed point -- so the
+        // totals do not depend on how tiles are dealt out to waves, blocks or launches, and every form of the iteration agrees bit for bit.
+        unsigned long long lo = 0ull, hi = 0ull;
+#pragma unroll
+        for (int t = 0; t < kIWaves; ++t) {
+            unsigned long long l, h;
+            fixed_split(tile_tree16(&sh[tix_e][16 * t]), l, h);
+            fixed_accumulate(lo, hi, l, h);
+        }
+        unsigned long long *slot = acc + (((int64_t)(bid & (kAccCopies - 1)) * kAcc + tix_e) * kFixedWords);
+        if (fuse.ticket) fixed_add_words_performed(slot, lo, hi); else fixed_add_words(slot, lo, hi);
+    } else if (!PERSIST && fuse.ticket && tix_e == nacc) {
+        int cnt = 0;
+#pragma unroll
+        for (int wv = 0; wv < kIWaves; ++wv) cnt += s_cnt[wv];
+        if (cnt) {
+            const unsigned long long back = __hip_atomic_fetch_add(fuse.ticket + kSearchedWord + (bid & 7u), (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(back));
+        }
+    }
+    if (fuse.light_key && tix == kIThreads - 1) {      // (after the barrier above: s_light is complete)
+        double g2 = INFINITY;
+        bool light = true;
+#pragma unroll
+        for (int wv = 0; wv < kIWaves; ++wv) { light = light && s_light[wv] >= 0.0; g2 = fmin(g2, s_light[wv]); }
+        const double nk = light ? st->motion + sqrt(g2) * (1.0 - 1e-9) : 0.0;
+        if (PERSIST) s_key = nk; else fuse.light_key[bid] = nk;
+    }
+    phase_tick(tile_visits, 5, bid);
+    } while (false);
+    if (PERSIST && fuse.stamp && tix == 0) {
+        const unsigned long long t = wall_clock64();
+        if (bid == 0) fuse.stamp[3] = t;
+        atomicMax(&fuse.stamp[11], t);
+    }
+    if (!fuse.ticket) return;
+    // "The last block finishes the job": every add above has RETURNED (it has been performed at the device's point of coherence),
+    // the barrier orders the block's ticket behind them, and the block that draws the last ticket of its registration reads the
+    // totals -- 8 x 44 pairs of words -- with device-coherent loads, clears them for the next launch and performs the update.
+    // Only relaxed atomics on the producers' side: no release fence, which on this part writes back the XCD's L2 (measured 10x slower,
+    // once per block).  The CONSUMER side is by the book: the winner -- one block per registration and launch -- acquires at agent
+    // scope behind its ticket (a single buffer_inv; same-box A/B against none: equal within noise, profiles/r03/exp_icp_acquire_fence.txt).
+    // This is the `sc1` form of the valid hand-offs of MI355X_MICROARCH.md ("Correctness boundaries"): the handed-off bytes are
+    // produced by atomics (performed at the memory side, never resident in a CU's L1), drained before the ticket because every
+    // add RETURNS, and read by the winner with device-coherent (sc1) loads only (fixed_total_coherent) -- no plain load of them
+    // anywhere.  It rests on gfx950 behaviour, not on the HIP memory model: KPX_ICP_SPLIT=1 (update in its own kernel, ordered by the
+    // kernel boundary) is the portable fall-back, and test_update_placements_agree_with_four_frames_in_flight compares the three
+    // placements bit for bit under four frames in flight.
+    // The state is written with plain stores: its readers are the blocks of the NEXT launch, behind the kernel boundary.
+    __shared__ unsigned s_ticket;
+    __syncthreads();
+    if (tix == 0) s_ticket = (unsigned)__hip_atomic_fetch_add(fuse.ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (PERSIST && fuse.stamp && tix == 0) {
+        const unsigned long long t = wall_clock64();
+        if (bid == 0) fuse.stamp[4] = t;
+        atomicMax(&fuse.stamp[6], t);
+    }
+    if (s_ticket != nblocks - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the winner only: one per registration and launch
+    // (the winner's thread number behind an opaque move as well: addresses derived from it are then formed here, not in front of the sweep)
+    const int tix_w = opaque_i((int)threadIdx.x);
+    if (tix_w < kAcc) s_sums[tix_w] = tix_w < nacc ? fixed_total_coherent(acc, tix_w) : 0.0;
+    const unsigned long long n_searched = PERSIST ? 0ull : searched_take(fuse.ticket, tix_w);
+    __syncthreads();
+    if (PERSIST) chain_tick(fuse.stamp, 7, tix == 0);
+    for (int e = tix_w; e < kAccSet; e += kIThreads) __hip_atomic_store(acc + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tix == 0) __hip_atomic_store(fuse.ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // PERSIST: the blocks that see the next record add to these accumulators at once, so every clearing store (and the ticket's) must
+    // have been performed before the record is published: each wave drains its stores, the block meets at a barrier (wave 0 after the
+    // update algebra, which hides the drain), then wave 0 publishes
+    if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (wave != 0) {
+        if (PERSIST) __syncthreads();
+        return;
+    }
+    __shared__ FinishScratch s_tail;
+    // (t2max again from the target's box, behind an opaque move of its address: a double every lane would otherwise carry across the sweep)
+    const double *tbbox_w = tbbox;
+    asm volatile("" : "+s"(tbbox_w));
+    const double t2max_w = target_t2max(tbbox_w);
+    IcpState *stw = const_cast<IcpState *>(st);
+    IcpState *work = &s_state;
+    if (PERSIST)
+        icp_finish_wave_call(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, work, (double *)nullptr, &s_tail, lane,
+                             fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w, fuse.stamp ? fuse.stamp + 32 : (unsigned long long *)nullptr);
+    else
+        icp_finish_wave(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, work, fuse.result, s_tail, lane,
+                        LightSkip{ fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w });
+    wave_lds_fence();
+    if (PERSIST) chain_tick(fuse.stamp, 8, lane == 0);
+    if (PERSIST) {
+        static_assert(sizeof(IcpState) == kChainWords * sizeof(double), "record layout");
+        __syncthreads();
+        if (lane < kChainWords)
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(fuse.chain_rec + (size_t)kChainRec * (k + 1)) + lane,
+                               reinterpret_cast<const unsigned long long *>(&s_state)[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the result is written ONCE, by the winner of the last iteration: the winners of a chain sit on different XCDs, and plain stores of
+        // several of them to the same words would reach memory in whatever order their L2s are written back at the end of the kernel
+        if (work->done && fuse.result) {
+            if (lane < 16) fuse.result[lane] = work->T[lane];
+            if (lane == 0) { fuse.result[16] = work->fitness; fuse.result[17] = work->rmse; fuse.result[18] = (double)k; fuse.result[19] = work->count; }
+        }
+        if (lane == 0 && fuse.progress && work->done)
+            __hip_atomic_store(fuse.progress, fuse.tag | (1ull << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        chain_tick(fuse.stamp, 9, lane == 0);
+        if (fuse.stamp && lane == 0) fuse.stamp[12] = __builtin_amdgcn_s_memtime();      // shader clock (against [9]: the clock the chip runs the chain at)
+        return;
+    }
+    if (lane < (int)(sizeof(IcpState) / sizeof(double))) reinterpret_cast<double *>(stw)[lane] = reinterpret_cast<const double *>(&s_state)[lane];
+    if (fuse.cert && fuse.thist && k + 1 < kCertHist && lane < 12) fuse.thist[12 * (k + 1) + lane] = work->T[lane];     // what iteration k + 1 transforms with
+    if (lane == 0 && fuse.progress)
+        __hip_atomic_store(fuse.progress, fuse.tag | progress_searched(n_searched, n) | ((unsigned long long)(work->done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+
+__global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_iter_kernel(const float *__restrict__ src, int64_t n, const float *__restrict__ tgt,
+                                                       const float *__restrict__ tn, const double *__restrict__ Bs,
+                                                       const int32_t *__restrict__ orig, const float *__restrict__ tile_box,
+                                                       const float *__restrict__ group_box, int32_t n_groups,
+                                                       const double *__restrict__ tbbox, const int32_t *__restrict__ row_of,
+                                                       const float *__restrict__ src_sorted, int32_t *__restrict__ idx_sorted,
+                                                       float *__restrict__ ptgt_sorted,
+                                                       int32_t *__restrict__ idx_cur, double *__restrict__ d2_cur, double max_d2, int mode,
+                                                       int k, const IcpState *__restrict__ st, unsigned long long *acc,
+                                                       unsigned long long *__restrict__ tile_visits, IcpFuse fuse)
+{
+    icp_iter_body(blockIdx.x, gridDim.x, src, n, tgt, tn, Bs, orig, tile_box, group_box, n_groups, tbbox, row_of, src_sorted, idx_sorted, ptgt_sorted,
+                  idx_cur, d2_cur, max_d2, mode, k, st, acc, tile_visits, fuse);
+}
+
+// Several registrations onto ONE shared target in one launch per iteration (kpx_icp_batch): block b belongs to the problem
+// whose block range holds it.  A frame's three or seven registrations then cost one chain of launches instead of three or
+// seven -- every kernel boundary writes back / invalidates the XCDs' L2s for everything else running on the device, so the
+// number of launches per frame, not their size, is what the frame rate of the pipeline follows.  A problem that has
+// converged keeps its blocks in the later launches: they read its state and return.
+__global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_iter_batch_kernel(IcpBatchArgs args, double max_d2, int mode, int max_iter, double rel_fit,
+                                                       double rel_rmse, unsigned long long *__restrict__ tile_visits, int split, int light,
+                                                       CertPolicy pol)
+{
+    int pi = 0;
+#pragma unroll
+    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    const IcpProblem &P = args.p[pi];
+    const unsigned bid = blockIdx.x - P.block0;
+    const float *__restrict__ tgt = P.tgt, *__restrict__ tn = P.tn, *__restrict__ tile_box = P.tile_box, *__restrict__ group_box = P.group_box;
+    const double *__restrict__ Bs = P.Bs, *__restrict__ tbbox = P.tbbox;
+    const int32_t *__restrict__ orig = P.orig;
+    const int32_t n_groups = P.n_groups;
+    const int k = P.k;
+    const unsigned long long tag = P.tag;
+    if (k > max_iter && bid != 0) return;                   // the closing launch only performs the last update (one block per problem)
+    // split: the update runs in icp_solve_batch_kernel between the sweeps (state slot 0, first accumulator set): the sweep's blocks
+    // then live 8 us instead of 12 -- under load (several frames in flight) the device's wave slots are what the sweeps compete for
+    // split == 2: no update kernel either -- the last block of every registration's sweep performs it (ticket: first word of the
+    // second accumulator set, which only the one-launch form uses)
+    const IcpFuse fuse{ split ? (IcpState *)nullptr : P.pair, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag,
+                        split == 2 ? P.ring + kAccSet : (unsigned long long *)nullptr, (light & 1) ? P.light_key : (double *)nullptr, P.sbbox,
+                        (light & 2) ? P.cert : (uint32_t *)nullptr, (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, nullptr, nullptr };
+    icp_iter_body(bid, P.blocks, P.src, P.n, tgt, tn, Bs, orig, tile_box, group_box, n_groups, tbbox, P.row_of, P.src_sorted, P.idx_sorted, P.ptgt_sorted,
+                  P.idx_cur, P.d2_cur, max_d2, mode, k, P.pair, P.ring, tile_visits, fuse);
+}
+
+// The whole chain of a group of registrations in ONE launch: block b iterates over k on the rows it owns (icp_iter_body<true>), the
+// block that draws the last ticket of iteration k performs the update and publishes record k + 1, everybody else waits for it (see
+// kChainRec).  No kernel boundary, no host poll, no re-read of the rows: an iteration costs the ticket, the update algebra and one
+// coherent round trip instead of a launch.
+// REQUIRES every block of the launch to be resident at the same time (a block that is not can never deliver its sums): the host
+// launches this form only when the grid fits the device beside every other chain kernel it has in flight (chain_reserve), and every
+// wait is bounded -- a block that has waited `limit_ticks` (100 MHz wall clock, counted from ITS start) raises *abort_word (pinned
+// host memory), poisons its registration's result and leaves; the others follow on their own clocks.  The library reports a raised
+// word at the next call (KPX_ERR_HIP); KPX_ICP_CHAIN=0 selects the launch-per-iteration form.
+__global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_chain_kernel(IcpBatchArgs args, const float *__restrict__ tgt,
+                                                       const float *__restrict__ tn, const double *__restrict__ Bs,
+                                                       const int32_t *__restrict__ orig, const float *__restrict__ tile_box,
+                                                       const float *__restrict__ group_box, int32_t n_groups,
+                                                       const double *__restrict__ tbbox, double max_d2, int mode, int max_iter, double rel_fit,
+                                                       double rel_rmse, unsigned long long tag, unsigned long long *__restrict__ tile_visits, int light,
+                                                       CertPolicy pol, unsigned long long limit_ticks, unsigned long long *abort_word)
+{
+    int pi = 0;
+#pragma unroll
+    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    const IcpProblem &P = args.p[pi];
+    const unsigned bid = blockIdx.x - P.block0;
+    __shared__ IcpState s_cur;
+    __shared__ int s_abort;
+    const unsigned long long t0 = wall_clock64();
+    if (threadIdx.x == 0) s_abort = 0;
+    __syncthreads();
+    for (int k = 0; k <= max_iter; ++k) {
+        // (the operands' addresses behind opaque moves, per iteration: their loop-invariant loads -- the first group boxes, the problem's
+        // descriptor -- would otherwise be hoisted out of the loop and live in registers across it)
+        asm volatile("" : "+s"(tgt), "+s"(tn), "+s"(Bs), "+s"(orig), "+s"(tile_box), "+s"(group_box), "+s"(tbbox));
+        asm volatile("" : "+s"(max_d2), "+s"(mode), "+s"(n_groups), "+s"(pol.calm), "+s"(pol.factor), "+s"(pol.smin), "+s"(pol.smax));
+        const IcpFuse fuse{ (IcpState *)nullptr, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag, P.ring + kAccSet,
+                            (light & 1) ? P.light_key : (double *)nullptr, P.sbbox, (light & 2) ? P.cert : (uint32_t *)nullptr,
+                            (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, P.chain_rec,
+                            ((light & 8) && pi == 0 && k < 64) ? &g_chain_stamp[k][0] : (unsigned long long *)nullptr };
+        if (threadIdx.x < kChainWords) {
+            const unsigned long long *w = reinterpret_cast<const unsigned long long *>(P.chain_rec + (size_t)kChainRec * k) + threadIdx.x;
+            unsigned long long v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned spins = 0;
+            while (v == kChainEmpty) {
+                __builtin_amdgcn_s_sleep(2);
+                if ((++spins & 255u) == 0u && wall_clock64() - t0 > limit_ticks) { s_abort = 1; break; }
+                v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            reinterpret_cast<unsigned long long *>(&s_cur)[threadIdx.x] = v;
+        }
+        __syncthreads();
+        if (s_abort) {
+            // the abort is reported PER CALL: every result word of the registration is NaN (nothing stale leaks out, and whoever reads the
+            // result -- ops.icp_batch, kpx_frame_step*, the exchange header of the sharded step -- sees it for THIS call); the pinned word is
+            // the process-wide diagnostic behind it
+            if (threadIdx.x == 0) __hip_atomic_store(abort_word, tag | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (P.result && threadIdx.x < 20) P.result[threadIdx.x] = __builtin_nan("");
+            return;
+        }
+        if (s_cur.done) break;
+        icp_iter_body<true>(bid, P.blocks, P.src, P.n, tgt, tn, Bs, orig, tile_box, group_box, n_groups, tbbox, P.row_of, P.src_sorted, P.idx_sorted, P.ptgt_sorted,
+                            P.idx_cur, P.d2_cur, max_d2, mode, k, &s_cur, P.ring, tile_visits, fuse);
+        __syncthreads();                                     // (the body's early returns meet here before s_cur is written again)
+    }
+}
+
+// The update step of every registration of a batch, one block each (split mode: see icp_iter_batch_kernel)
+__global__ __launch_bounds__(256) void icp_solve_batch_kernel(IcpBatchArgs args, int mode, int k, int max_iter, double rel_fit, double rel_rmse,
+                                                              unsigned long long tag)
+{
+    const IcpProblem &P = args.p[blockIdx.x];
+    IcpState *st = P.pair;
+    if (st->done) return;
+    __shared__ double sums[kAcc];
+    __shared__ FinishScratch fs;
+    unsigned long long *acc = P.ring;
+    const int nacc = mode == 1 ? kAcc : 17;
+    if (threadIdx.x < kAcc) sums[threadIdx.x] = (int)threadIdx.x < nacc ? fixed_total(acc, threadIdx.x) : 0.0;
+    __syncthreads();
+    for (int e = threadIdx.x; e < kAccCopies * kAcc * kFixedWords; e += 256) acc[e] = 0ull;
+    if (threadIdx.x >= 64) return;
+    icp_finish_wave(sums, P.n, mode, k, max_iter, rel_fit, rel_rmse, st, P.result, fs, (int)threadIdx.x);
+    if (threadIdx.x == 0 && P.progress)
+        __hip_atomic_store(P.progress, tag | ((unsigned long long)(st->done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Start of a batch chain in ONE launch: per problem both state slots <- the initial transform, the accumulator ring cleared,
+// the rows gathered into Morton order (what icp_init_kernel + a memset + gather_rows_kernel did per problem)
+__global__ __launch_bounds__(256) void icp_batch_init_kernel(IcpBatchArgs args, Mat16x8 T0)
+{
+    int pi = 0;
+#pragma unroll
+    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    const IcpProblem &P = args.p[pi];
+    const unsigned bid = blockIdx.x - P.block0;
+    const int c = threadIdx.x & 3;
+    for (int rr = threadIdx.x >> 2; rr < kIRows; rr += 64) {
+        const int64_t r = (int64_t)bid * kIRows + rr;
+        if (r < P.n && c < 3) P.src_sorted[3 * r + c] = P.src[3 * (int64_t)P.row_of[r] + c];
+    }
+    if (threadIdx.x < 7) {                                  // the block's LightSkip keys at every granularity: 1 x 64 rows, 2 x 32, 4 x 16
+        const int64_t n64 = (P.n + 63) / 64, n32 = (P.n + 31) / 32, n16 = (P.n + 15) / 16;
+        const int t = threadIdx.x;
+        const int64_t e = t == 0 ? (int64_t)bid : t < 3 ? n64 + 2 * (int64_t)bid + (t - 1) : n64 + n32 + 4 * (int64_t)bid + (t - 3);
+        const int64_t lim = t == 0 ? n64 : t < 3 ? n64 + n32 : n64 + n32 + n16;
+        if (e < lim) P.light_key[e] = 0.0;
+    }
+    if (bid == 0) {
+        for (int e = threadIdx.x; e < 3 * kAccSet; e += 256) P.ring[e] = 0ull;
+        if (threadIdx.x >= 64 && threadIdx.x < 76) P.thist[threadIdx.x - 64] = T0.m[pi][threadIdx.x - 64];
+        if (P.chain_rec) {                                  // the chain form: record 0 = the initial state (below), every other record empty
+            unsigned long long *rw = reinterpret_cast<unsigned long long *>(P.chain_rec);
+            for (int e = kChainRec + threadIdx.x; e < kChainRecords * kChainRec; e += 256) rw[e] = kChainEmpty;
+            IcpState *r0 = reinterpret_cast<IcpState *>(P.chain_rec);
+            if (threadIdx.x >= 128 && threadIdx.x < 144) r0->T[threadIdx.x - 128] = T0.m[pi][threadIdx.x - 128];
+            if (threadIdx.x == 144) { r0->fitness = 0.0; r0->rmse = 0.0; r0->count = 0.0; r0->iter = 0; r0->done = 0; r0->motion = 0.0; r0->reach = INFINITY; r0->last_motion = INFINITY; r0->smax = -1.0; }
+        }
+        if (threadIdx.x < 32) {
+            IcpState *st = P.pair + (threadIdx.x >> 4);
+            st->T[threadIdx.x & 15] = T0.m[pi][threadIdx.x & 15];
+            if ((threadIdx.x & 15) == 0) { st->fitness = 0.0; st->rmse = 0.0; st->count = 0.0; st->iter = 0; st->done = 0; st->motion = 0.0; st->reach = INFINITY; st->last_motion = INFINITY; st->smax = -1.0; }
+        }
+    }
+}
+
+}  // namespace kpx

@@ -1,7 +1,7 @@
 // kpx_icprows.h -- one ICP iteration of SEVERAL registrations, one wave per 64 sorted rows (included by kpx_icp.hip only; round 5).
 //
 // icp_iter_body gives every 16-row tile a wave and every 64 rows a block of four: right for the first iterations, where every tile
-// is searched, and wasteful afterwards -- from iteration ~10 on 95-99.9 % of the rows carry a certificate ("Certificates", kpx_icp.hip),
+// is searched, and wasteful afterwards -- from iteration ~10 on 95-99.9 % of the rows carry a certificate ("Certificates", kpx_icpiter.h),
 // a block then lives ~8.6 us of which the search is 0.3, and only 16 of a wave's 64 lanes do the per-row work (transform, bound,
 // certificate test, the 44 products of the update sums).  With four frames in flight the chip's wave slots x a block's life time IS the
 // frame rate, so here
@@ -13,9 +13,9 @@
 //   * the sums follow the contract stated in icp_iter_body: per tile the balanced tree of four DPP butterfly steps
 //     (row16_tree_sum == tile_tree16), the four tile partials added exactly in fixed point, one pair of returning atomics per sum;
 //   * the block that draws the registration's last ticket performs the update (icp_finish_wave), as in icp_iter_body's ticket mode;
-//   * every problem of the launch carries its OWN target operands and its OWN iteration number: the registrations of several frames in
-//     flight share one launch per tick (kpx_stream, kpx_frame.hip), each at the iteration it has reached.
+//   * every problem of the launch carries its OWN target operands and its OWN iteration number (RowsProblem).
 #pragma once
+#include "kpx_icpiter.h"
 
 namespace kpx {
 
@@ -383,9 +383,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
     if (threadIdx.x == 0) tk = (unsigned)__hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     tk = (unsigned)__builtin_amdgcn_readfirstlane((int)tk);
     if (tk != P.blocks - 1u) return;
-#if KPX_ICP_ACQ_FENCE
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
     const int lane_w = opaque_i((int)threadIdx.x);
     if (lane_w < kAcc) s_sums[lane_w] = lane_w < NACC ? fixed_total_coherent(P.ring, lane_w) : 0.0;
     const unsigned long long n_searched = searched_take(ticket, lane_w);

@@ -82,15 +82,6 @@ int icp_batch_ordered(int32_t count, const float *const *h_src, const int64_t *h
                       double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness, double relative_rmse,
                       double *d_results, void *ws, size_t ws_bytes, void *stream, bool presorted);
 
-// The device's ICP engine (kpx_icp.hip, IcpEngine): one host thread + one stream that carry the registrations of every frame in flight
-// in one launch per tick.  acquire / release: reference-counted per device (kpx_stream_create / destroy); attach: the CALLING thread's
-// icp_batch_ordered hands its groups to the engine from now on (nullptr: drives its own chain of launches).
-struct IcpEngine;
-IcpEngine *icp_engine_acquire();
-void icp_engine_release(IcpEngine *e);
-void icp_engine_attach(IcpEngine *e);
-void icp_engine_counters(IcpEngine *e, unsigned long long *launches, unsigned long long *ticks);
-
 // Column tiles (16 rows x 16 columns, 2048 flops each) the culled nearest-neighbour sweep has multiplied since the
 // last call; resets the device counter (kpx_icp.hip).
 double nn_local_take_visits();

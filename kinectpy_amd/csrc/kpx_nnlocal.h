@@ -1,4 +1,4 @@
-// kpx_nnlocal.h -- the exact nearest-neighbour sweep with spatial tile culling (included by kpx_icp.hip only).
+// kpx_nnlocal.h -- the exact nearest-neighbour sweep with spatial tile culling (included by kpx_icpiter.h, for kpx_icp.hip only).
 //
 // Same arithmetic as the dense sweep (contract AC2: v_mfma_f64_16x16x4_f64 = the k-ordered fma chain seeded with
 // K_i; argmin, ties to the lowest ORIGINAL target index), but only the 16-column tiles that can hold a column
@@ -19,6 +19,7 @@
 //     nearest group box is a valid radius for all 16 rows.
 // The result is bit-identical to the dense sweep and to the oracle wherever a partner exists within the bound.
 #pragma once
+#include "kpx_icpdefs.h"
 #include "kpx_morton.h"
 
 namespace kpx {

@@ -530,7 +530,7 @@ class NativeFrameStream:
         return out[0][:k], out[1][:k], h_T
 
     def stats(self):
-        """frames finished, whether the registrations run through the device's ICP engine, its iteration launches and ticks so far"""
+        """frames finished; the other three keys are kept for the result format and are always False / 0 (kpx_stream_stats)"""
         out = np.zeros(4, dtype=np.uint64)
         self._L.check(self._lib.kpx_stream_stats(self.handle, out.ctypes.data_as(self._C.c_void_p)))
         return {"frames": int(out[0]), "icp_engine": bool(out[1]), "engine_launches": int(out[2]), "engine_ticks": int(out[3])}
