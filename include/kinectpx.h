@@ -76,7 +76,9 @@ int kpx_rgbd_compact(const int16_t *xyz, const uint8_t *rgb, int64_t n, int32_t 
 
 /* Fused a1+a3+a4 for the streaming pipeline: u16 depth (+ xy table, + optional rgb) straight to the
  * compacted float32 cloud, never materialising the int16 XYZ image.  Same outputs as
- * kpx_rgbd_compact; the median is taken over the raw depth (== the z column). */
+ * kpx_rgbd_compact; the median is taken over the raw depth (== the z column).
+ * Both entries take at most as many frames per call as the device's grid has rows (hipDeviceAttributeMaxGridDimY: 65536 on the
+ * MI355X) and return KPX_ERR_INVALID for more. */
 size_t kpx_depth_to_cloud_workspace_bytes(int64_t n_px, int32_t frames);
 int kpx_depth_to_cloud(const uint16_t *depth, const float *xy_table, const uint8_t *rgb, int64_t n_px,
                        int32_t frames, int32_t flags, double gate, float *pts, float *col, int32_t *idx,

@@ -852,6 +852,17 @@ __global__ __launch_bounds__(kCompactThreads) void depth_onepass_vec_kernel(cons
     if (tile == tiles - 1 && threadIdx.x == 0) d_count[f] = before + tot;
 }
 
+// The frame count of a batch becomes gridDim.y of the compaction (and of the median's histogram passes): at most what the device
+// reports for that dimension (MI355X: 65536).  The entry points refuse more before any launch.
+static int32_t max_compact_frames()
+{
+    static const int32_t lim = [] {
+        int dev = 0, y = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&y, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess || y <= 0) y = 65535;
+        return (int32_t)y;
+    }();
+    return lim;
+}
 // the 8-pixel kernels (xy == NULL: int16 XYZ image input).  counts: frames * compact_ws_ints(n) ints (the 64-bit tile words)
 static int px8_compact(const uint16_t *depth, const float *xy, const uint8_t *rgb, const double *med, int64_t n, int32_t frames, int32_t flags,
                        double gate, int32_t *counts, float *pts, float *col, int32_t *idx, int32_t *d_count, hipStream_t st, bool state_is_clear = false)
@@ -916,6 +927,7 @@ KPX_EXPORT int kpx_rgbd_compact(const int16_t *xyz, const uint8_t *rgb, int64_t 
     KPX_REQUIRE(xyz && pts && d_count && ws, "kpx_rgbd_compact: null pointer");
     KPX_REQUIRE(!(flags & KPX_COMPACT_DEPTH_GATE) || d_median, "kpx_rgbd_compact: depth gate needs d_median");
     KPX_REQUIRE(n < ((int64_t)1 << 31), "kpx_rgbd_compact: frame too large");
+    KPX_REQUIRE(frames <= max_compact_frames(), "kpx_rgbd_compact: %d frames exceed the device's grid limit of %d per call", frames, max_compact_frames());
     Arena a(ws, ws_bytes);
     int32_t *counts = a.get<int32_t>((size_t)frames * compact_ws_ints(n));
     KPX_ARENA_CHECK(a);
@@ -942,6 +954,7 @@ KPX_EXPORT int kpx_depth_to_cloud(const uint16_t *depth, const float *xy, const 
     KPX_REQUIRE(n_px > 0 && frames > 0, "kpx_depth_to_cloud: bad size");
     KPX_REQUIRE(depth && xy && pts && d_count && ws, "kpx_depth_to_cloud: null pointer");
     KPX_REQUIRE(n_px < ((int64_t)1 << 31), "kpx_depth_to_cloud: frame too large");
+    KPX_REQUIRE(frames <= max_compact_frames(), "kpx_depth_to_cloud: %d frames exceed the device's grid limit of %d per call", frames, max_compact_frames());
     Arena a(ws, ws_bytes);
     return depth_to_cloud_impl(depth, xy, rgb, n_px, frames, flags, gate, pts, col, idx, d_count, a, (hipStream_t)stream);
 }
