@@ -175,11 +175,11 @@ KPX_EXPORT int kpx_frame_step(const uint16_t *depth, const uint8_t *rgb, const f
     // The sort-key width of the registration voxel grid is speculated from the last frame of this thread (the scene's extent in
     // voxels barely changes from frame to frame): its read-back inside the call is one host round trip less; a frame that needs
     // more bits is detected with the counts and done again the careful way.
-    // The registration clouds leave the voxel grid along the Z-curve of their voxel indices (one point per voxel: the order the
-    // culled search would otherwise establish with a Morton sort of its own -- 12 dispatches per frame); nothing downstream depends
-    // on their order: normals and nearest neighbours are per point, the update sums are exact.  KPX_FRAME_ZORDER=0: A/B switch.
-    static const bool zorder_on = [] { const char *e = getenv("KPX_FRAME_ZORDER"); return !(e && e[0] == '0'); }();
-    const bool zorder = zorder_on && S <= 8;         // the voxel batch's one-pass form (the only one with the Z-curve order) takes 8 clouds
+    // The registration clouds leave the voxel grid along the curve of their voxel indices (one point per voxel: the order the
+    // culled search would otherwise establish with a sort of its own -- 12 dispatches per frame).  Normals and nearest neighbours are
+    // per point; the update sums are a tree per 16-row tile, so the order does move the transforms' last bits: it is fixed by the
+    // frame's shape alone (the switch that chose it per process is gone).
+    const bool zorder = S <= 8;                      // the voxel batch's one-pass form (the only one with the curve order) takes 8 clouds
     static thread_local int spec_bits = 0;
     static const bool speculate = [] { const char *e = getenv("KPX_FRAME_SPECULATE"); return !(e && e[0] == '0'); }();      // A/B switch
     if (!speculate) spec_bits = 0;
@@ -472,8 +472,7 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     // same headers and all of them return an error behind the same collective -- as the capacity overflow does with KPX_RETRY.
     int lerr = KPX_OK;
     if (negative(h_i, S_l) || negative(h_i + 16, S_l)) lerr = fail(KPX_ERR_RANGE, "kpx_frame_step_sharded: extraction reported %d", negative(h_i, S_l) | negative(h_i + 16, S_l));
-    static const bool zorder_on = [] { const char *e = getenv("KPX_FRAME_ZORDER"); return !(e && e[0] == '0'); }();
-    const bool zorder = zorder_on && K <= 8;                   // the same decision on every rank: the master arrives in the order rank 0 gave it
+    const bool zorder = K <= 8;                                // the same decision on every rank: the master arrives in the order rank 0 gave it
     int &spec_bits = comm_spec_bits(comm);
     for (int attempt = 0; attempt < 2 && !lerr; ++attempt) {
         KPX_SUB(voxel_downsample_batch_spec(S_l, p_in.data(), nullptr, fk.data(), prm->reg_voxel, p_out.data(), nullptr, h_i + 32, L.op_ws, L.op_bytes, st,

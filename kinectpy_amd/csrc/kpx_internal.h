@@ -49,7 +49,7 @@ int lanes_join(LaneSet *l, hipStream_t caller, int used);
 // kpx_voxel_downsample_batch with a speculated sort-key width (kpx_frame_step): spec_bits > 0 skips the width's read-back (one host
 // round trip per call); *d_bits receives the width the batch needs (0 = the call did not speculate) and the caller repeats the call
 // with spec_bits = 0 when that is larger than spec_bits.  spec_bits = 0, d_bits = NULL: the exported behaviour.
-// morton: the voxels of every cloud leave in Morton (Z-curve) order of their grid indices instead of ascending (ix, iy, iz) -- same
+// morton: the voxels of every cloud leave along the Hilbert curve of their grid indices instead of ascending (ix, iy, iz) -- same
 // voxels, same means; for consumers that only need SOME spatially coherent order (the registration inside kpx_frame_step).
 int voxel_downsample_batch_spec(int32_t count, const float *const *h_pts, const float *const *h_col, const int64_t *h_n, double voxel,
                                 float *const *h_opts, float *const *h_ocol, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream,

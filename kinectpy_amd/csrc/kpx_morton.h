@@ -51,7 +51,8 @@ __device__ __forceinline__ uint32_t morton_spread10(uint32_t v)
 // 30-bit Hilbert index of three 10-bit cell coordinates (Skilling, "Programming the Hilbert curve", 2004: axes -> transpose, the
 // transposed words' bits interleaved from the top).  The culled search orders rows and target columns along this curve: its
 // consecutive cells are neighbours, the Z-curve's are not, and 16 consecutive points -- a wave's rows, a column tile -- are a third
-// more compact (kpx_voxel.hip: voxel_hcode has the numbers).  Any order gives the same results; KPX_CURVE=z restores the Z-curve.
+// more compact (kpx_voxel.hip: voxel_hcode has the numbers).  The order decides which rows share a 16-row tile of the ICP sums, so
+// another curve moves the transforms' last bits: the Z-curve form (slower, profiles/r03/exp_curve_hilbert.txt) is gone with its switch.
 __device__ __forceinline__ uint32_t hilbert30(uint32_t x, uint32_t y, uint32_t z)
 {
     uint32_t X[3] = { x & 1023u, y & 1023u, z & 1023u };
@@ -75,17 +76,12 @@ __device__ __forceinline__ uint32_t hilbert30(uint32_t x, uint32_t y, uint32_t z
     // X[0]'s bit b is the most significant of the triple: spread and interleave
     return (morton_spread10(X[0]) << 2) | (morton_spread10(X[1]) << 1) | morton_spread10(X[2]);
 }
-__device__ __forceinline__ uint32_t curve_code30(const uint32_t q[3], int curve)
+__device__ __forceinline__ uint32_t curve_code30(const uint32_t q[3])
 {
-    return curve == 1 ? (morton_spread10(q[0]) | (morton_spread10(q[1]) << 1) | (morton_spread10(q[2]) << 2)) : hilbert30(q[0], q[1], q[2]);
-}
-static inline int curve_choice()
-{
-    static const int c = [] { const char *e = getenv("KPX_CURVE"); return (e && e[0] == 'z') ? 1 : 2; }();      // 1 Z-curve, 2 Hilbert (A/B switch)
-    return c;
+    return hilbert30(q[0], q[1], q[2]);
 }
 static __global__ __launch_bounds__(256) void morton_key_kernel(const float *__restrict__ pts, int64_t n, const double *__restrict__ bbox,
-                                                         uint32_t *__restrict__ keys, int32_t *__restrict__ vals, int curve)
+                                                         uint32_t *__restrict__ keys, int32_t *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -97,7 +93,7 @@ static __global__ __launch_bounds__(256) void morton_key_kernel(const float *__r
         const double v = ((double)pts[3 * i + a] - bbox[a]) * scale;
         q[a] = v >= 0.0 ? (uint32_t)(v < 1023.0 ? v : 1023.0) : 0u;          // NaN -> cell 0
     }
-    keys[i] = curve_code30(q, curve);
+    keys[i] = curve_code30(q);
     vals[i] = (int32_t)i;
 }
 
@@ -144,7 +140,7 @@ static int morton_order(const float *pts, int64_t n, const SortScratch &s, int32
 {
     int rc = bbox_f32(pts, n, s.bbox, s.bbox_part, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(morton_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, pts, n, s.bbox, s.keys_in, s.vals_in, curve_choice());
+    hipLaunchKernelGGL(morton_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, pts, n, s.bbox, s.keys_in, s.vals_in);
     size_t bytes = s.tmp_bytes;
     KPX_HIP(sort_pairs(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, d_perm, n, 30, st));
     return KPX_OK;
@@ -224,7 +220,7 @@ static __global__ __launch_bounds__(64) void morton_batch_bbox_final_kernel(Mort
     for (int a = 0; a < 6; ++a)
         if (lane == a) b.bbox[c][a] = v[a];
 }
-static __global__ __launch_bounds__(256) void morton_batch_key_kernel(MortonBatch b, uint64_t *__restrict__ keys, int32_t *__restrict__ vals, int curve)
+static __global__ __launch_bounds__(256) void morton_batch_key_kernel(MortonBatch b, uint64_t *__restrict__ keys, int32_t *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b.off[b.count]) return;
@@ -240,7 +236,7 @@ static __global__ __launch_bounds__(256) void morton_batch_key_kernel(MortonBatc
         const double v = ((double)pts[3 * j + a] - bbox[a]) * scale;
         q[a] = v >= 0.0 ? (uint32_t)(v < 1023.0 ? v : 1023.0) : 0u;          // NaN -> cell 0
     }
-    keys[i] = ((uint64_t)c << 30) | curve_code30(q, curve);
+    keys[i] = ((uint64_t)c << 30) | curve_code30(q);
     vals[i] = (int32_t)i;
 }
 static __global__ __launch_bounds__(256) void morton_batch_split_kernel(MortonBatch b, const int32_t *__restrict__ vals)
@@ -270,7 +266,7 @@ static int morton_order_batch(const MortonBatch &b, const MortonBatchScratch &s,
         KPX_LAUNCH_CHECK();
         return KPX_OK;
     }
-    hipLaunchKernelGGL(morton_batch_key_kernel, dim3(nb), dim3(256), 0, st, b, s.keys_in, s.vals_in, curve_choice());
+    hipLaunchKernelGGL(morton_batch_key_kernel, dim3(nb), dim3(256), 0, st, b, s.keys_in, s.vals_in);
     size_t bytes = s.tmp_bytes;
     KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)total, 0, 34, st));
     hipLaunchKernelGGL(morton_batch_split_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out);

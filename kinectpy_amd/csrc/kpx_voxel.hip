@@ -140,10 +140,10 @@ struct VoxelBatch {
     float *ocol[kVoxelBatchMax];
     int64_t off[kVoxelBatchMax + 1];      // cloud c owns [off[c], off[c+1]) of the concatenated index space
     int32_t count;
-    int32_t morton;                       // keys = cloud | curve code of (ix, iy, iz) instead of cloud | (ix, iy, iz) row-major: 1 Z-curve, 2 Hilbert curve
+    int32_t morton;                       // keys = cloud | curve code of (ix, iy, iz) instead of cloud | (ix, iy, iz) row-major: 1 = along the Hilbert curve
 };
-// bits of the Z-curve code per axis: enough for the axis' largest index in the batch.  The code interleaves bit q of every axis that
-// still has a bit q (x lowest), so its width is the SUM of the three widths -- a long axis costs its own extra bits only, not
+// bits per axis: enough for the axis' largest index in the batch.  A Z-curve code (round 2; removed: slower, and another order moves the
+// ICP transforms' last bits) interleaves bit q of every axis that still has a bit q, so its width is the SUM of the three widths -- a long axis costs its own extra bits only, not
 // three times them (a frame's 26-bit cube code would be a fourth radix pass; 7 + 7 + 8 bits + 2 for the cloud stay within three)
 __device__ __forceinline__ void voxel_batch_axis_bits(const double d[3], int bits[3])
 {
@@ -155,23 +155,11 @@ __device__ __forceinline__ void voxel_batch_axis_bits(const double d[3], int bit
         bits[a] = n;
     }
 }
-__device__ __forceinline__ unsigned long long voxel_zcode(unsigned long long x, unsigned long long y, unsigned long long z, const int bits[3])
-{
-    unsigned long long k = 0ull;
-    int o = 0;
-    const int top = bits[0] > bits[1] ? (bits[0] > bits[2] ? bits[0] : bits[2]) : (bits[1] > bits[2] ? bits[1] : bits[2]);
-    for (int q = 0; q < top; ++q) {
-        if (q < bits[0]) k |= ((x >> q) & 1ull) << o++;
-        if (q < bits[1]) k |= ((y >> q) & 1ull) << o++;
-        if (q < bits[2]) k |= ((z >> q) & 1ull) << o++;
-    }
-    return k;
-}
 // Hilbert index of (x, y, z), `bits` bits per axis (Skilling, "Programming the Hilbert curve", 2004: axes -> transpose, then the bits
 // of the three transposed words interleaved from the top).  Consecutive cells of the curve are neighbours, which the Z-curve's
 // are not: 16 consecutive points of a surface cloud -- a wave's rows, a target tile of the culled ICP sweep (kpx_nnlocal.h) -- span
 // 177 instead of 246 mm (median; p99 677 instead of 1255) on the bench's 35 mm clouds, a wave multiplies 2.0 instead of 3.0 tiles
-// on average (p99 9 instead of 13).  KPX_VOXEL_CURVE=z restores the Z-curve (A/B switch).  `bits` >= 1.
+// on average (p99 9 instead of 13; profiles/r03/exp_curve_hilbert.txt).  `bits` >= 1.
 __device__ __forceinline__ unsigned long long voxel_hcode(unsigned long long x, unsigned long long y, unsigned long long z, int bits)
 {
     unsigned long long X[3] = { x, y, z };
@@ -295,7 +283,7 @@ __device__ __forceinline__ int voxel_batch_key_bits(const VoxelBatch &b, const d
         int cb = 0, ab[3];
         while ((1 << cb) < b.count) ++cb;
         voxel_batch_axis_bits(d, ab);
-        n = (b.morton == 2 ? voxel_hilbert_key_bits(ab, voxel_hilbert_cube_bits(ab, cb)) : ab[0] + ab[1] + ab[2]) + cb;
+        n = voxel_hilbert_key_bits(ab, voxel_hilbert_cube_bits(ab, cb)) + cb;
         n = n < 1 ? 1 : (n > 64 ? 64 : n);
     } else if (!overflow) {
         const unsigned long long range = (((unsigned long long)b.count * (unsigned long long)d[0]) * (unsigned long long)d[1]) * (unsigned long long)d[2];
@@ -329,7 +317,7 @@ __global__ __launch_bounds__(256) void voxel_batch_key_kernel(VoxelBatch b, cons
         axis_bits[0] = ab[0]; axis_bits[1] = ab[1]; axis_bits[2] = ab[2];
         while ((1 << cb) < b.count) ++cb;
         cube_bits = voxel_hilbert_cube_bits(ab, cb);
-        overflow = (ov || (b.morton == 1 && ab[0] + ab[1] + ab[2] + cb > 64) || (b.morton == 2 && voxel_hilbert_key_bits(ab, cube_bits) + cb > 64)) ? 1 : 0;
+        overflow = (ov || (b.morton && voxel_hilbert_key_bits(ab, cube_bits) + cb > 64)) ? 1 : 0;
     }
     __syncthreads();
     const uint64_t DX = (uint64_t)dims[0], DY = (uint64_t)dims[1], DZ = (uint64_t)dims[2];
@@ -344,13 +332,10 @@ __global__ __launch_bounds__(256) void voxel_batch_key_kernel(VoxelBatch b, cons
         double fz = floor(((double)pts[3 * j + 2] - oz) / voxel);
         const bool bad = overflow || !(fx >= 0.0) || !(fy >= 0.0) || !(fz >= 0.0) || fx >= 2097152.0 || fy >= 2097152.0 || fz >= 2097152.0;
         if (bad) { err[c] = 1; fx = fy = fz = 0.0; }
-        if (b.morton == 2) {
+        if (b.morton) {
             const int ab[3] = { axis_bits[0], axis_bits[1], axis_bits[2] };
             const int m = cube_bits;
             keys[i] = (Key)(((uint64_t)c << voxel_hilbert_key_bits(ab, m)) | voxel_hilbert_key((uint64_t)fx, (uint64_t)fy, (uint64_t)fz, ab, m));
-        } else if (b.morton) {
-            const int ab[3] = { axis_bits[0], axis_bits[1], axis_bits[2] };
-            keys[i] = (Key)(((uint64_t)c << (ab[0] + ab[1] + ab[2])) | voxel_zcode((uint64_t)fx, (uint64_t)fy, (uint64_t)fz, ab));
         }
         else keys[i] = (Key)((((uint64_t)c * DX + (uint64_t)fx) * DY + (uint64_t)fy) * DZ + (uint64_t)fz);
         vals[i] = (int32_t)i;
@@ -873,13 +858,12 @@ int kpx::voxel_downsample_batch_spec(int32_t count, const float *const *h_pts, c
     hipStream_t st = (hipStream_t)stream;
     int64_t total = 0;
     for (int i = 0; i < count; ++i) total += h_n[i];
-    // (the Z-curve order exists in the one-pass form only; the other forms keep the row-major order -- callers that asked for it only
+    // (the curve order exists in the one-pass form only; the other forms keep the row-major order -- callers that asked for it only
     // lose locality, never correctness)
     if (count <= kVoxelBatchMax && total > 0 && total < ((int64_t)1 << 31)) {         // one pass over the concatenated clouds
         VoxelBatch b;
         b.count = count;
-        static const int curve = [] { const char *e = getenv("KPX_VOXEL_CURVE"); return (e && e[0] == 'z') ? 1 : 2; }();      // A/B switch
-        b.morton = morton ? curve : 0;
+        b.morton = morton ? 1 : 0;
         b.off[0] = 0;
         for (int i = 0; i < kVoxelBatchMax; ++i) {
             const bool on = i < count;

@@ -3,7 +3,7 @@
 # under profiles/rNN/exp_*.txt:
 #
 #   tools/ab.sh env  NAME VALUE_A VALUE_B [...]     one environment switch (KPX_ICP_LIGHT_SKIP 1 0, KPX_ICP_SPLIT 2 1 0, KPX_RADIX 1 0,
-#                                                   KPX_FRAME_ZORDER 1 0, GPU_MAX_HW_QUEUES 4 8, ...): bench at 4 frames in flight and at 1
+#                                                   KPX_FRAME_SPECULATE 1 0, GPU_MAX_HW_QUEUES 4 8, ...): bench at 4 frames in flight and at 1
 #   tools/ab.sh lib  cur NAME [...]                 library variants built by tools/build_variant.sh: ICP probe + bench line
 #   tools/ab.sh flag "--overlap 2" "--overlap 4" [...]   bench.py argument sets (frames in flight, --python-step, ...)
 #   tools/ab.sh procs                               1 process x 1|2 frames against 2 and 3 processes (GIL / runtime locks vs the device)
