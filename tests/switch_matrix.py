@@ -34,10 +34,10 @@ def _settings(*specs):
 # but other last bits in the culled ICP's transforms (up to 9.7e-12, 6.8e-14 and 4.5e-13 on an MI355X) and rmse (3.4e-13): they reorder
 # the rows, and the ICP's sums are a tree per 16-row tile.  No default path reached the forms, all three had measured slower, and sums
 # free of the row order are no small change: the forms and their switches were removed from the library.
+# Nor the wave-per-16-queries pass-0 forms of kpx_sor and their switches KPX_SOR_BLOCK, KPX_SOR_BLOCK_MINK and KPX_SOR_CELL_SMALL: removed
+# as superseded by sor_block_kernel.
 FAMILIES = {
-    "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_BLOCK=0", "SOR_BLOCK=0+SOR_CELL=1",
-                      "SOR_BLOCK=0+SOR_CELL=1+SOR_CELL_SMALL=0", "SOR_CELL=1+SOR_BLOCK_MINK=8", "SOR_BLOCK_MINK=129", "SOR_OCC=0.2", "SOR_OCC=1.0",
-                      "BBOX_VEC=0"),
+    "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_OCC=0.2", "SOR_OCC=1.0", "BBOX_VEC=0"),
     "voxel": _settings("RADIX=0", "VOXEL_SINGLE=0"),
     # the launch-per-iteration chains of icp_rows_kernel: KPX_ICP_ROWS_R only shows with the rows form forced and the one-launch chain off
     "icp": _settings("ICP_FUSE=0", "ICP_BATCH_LAUNCH=0", "ICP_WINDOW=1", "ICP_WINDOW=64", "ICP_ROWS=2+ICP_ROWS_R=16+ICP_CHAIN=0",
@@ -101,7 +101,7 @@ def sor_ratio(k):
 
 
 def halo_cloud():
-    """test_boundaries_gpu.halo_cloud's recipe: a 30k sample of the rendered frame (the cell / block kernels' dense cells) plus a sparse
+    """test_boundaries_gpu.halo_cloud's recipe: a 30k sample of the rendered frame (the block kernel's dense cells) plus a sparse
     halo of 400 points around it (queries whose k-th neighbour lies many cells away: the fall-back passes)"""
     rng = np.random.default_rng(41)
     base = synth.frame_cloud()
@@ -130,19 +130,12 @@ def sor_margin(avg, thr):
 
 
 def sor_pass0(k, env):
-    """kpx_sor's pass 0 at k under `env`: None (every query starts at the wave-per-query passes), "block<S>" or "cell<L,S,W>" """
+    """kpx_sor's pass 0 at k under `env`: None (every query starts at the wave-per-query passes) or "block<S>" """
     cell = env.get("KPX_SOR_CELL")
     mode = 1 if cell is None else (0 if cell[0] == "0" else 2)
     if not ((mode == 2 or (mode == 1 and k > 32)) and k <= 1024):
         return None
-    small = int(env.get("KPX_SOR_CELL_SMALL", "1"))
-    wave_cells = env.get("KPX_SOR_BLOCK", "")[:1] == "0"
-    mink = int(env.get("KPX_SOR_BLOCK_MINK", "33"))
-    if not wave_cells and k >= mink:
-        return "block<%d>" % (4 if k <= 32 else 8 if k <= 64 else 16 if k <= 128 else 32)
-    if k <= 24 and small:
-        return "cell<16,8,4>"
-    return "cell<16,16,4>" if k <= 32 else "cell<32,16,4>" if k <= 64 else "cell<64,16,4>" if k <= 128 else "cell<64,32,1>"
+    return "block<%d>" % (4 if k <= 32 else 8 if k <= 64 else 16 if k <= 128 else 32)
 
 
 def grid_occupancy(k, env):

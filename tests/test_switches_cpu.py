@@ -25,7 +25,7 @@ def _read_names():
 
 def test_every_switch_the_sources_read_is_tested_or_exempt():
     names = _read_names()
-    assert len(names) >= 49                                            # (the library reads 49: a scan that finds fewer has lost its pattern)
+    assert len(names) >= 46                                            # (the library reads 46: a scan that finds fewer has lost its pattern)
     covered = M.matrix_names() | set(M.FLIPPED_ELSEWHERE) | set(M.EXEMPT)
     assert not sorted(set(names) - covered), "read by the library, flipped by no test and not exempt"
     assert not sorted(set(M.EXEMPT) & (M.matrix_names() | set(M.FLIPPED_ELSEWHERE)))
@@ -50,7 +50,7 @@ def test_every_switch_is_documented():
 
 
 def test_matrix_holds_every_setting_once():
-    want = {"grid": 12, "voxel": 2, "icp": 6, "dense": 5, "frame": 7, "fps": 2}
+    want = {"grid": 7, "voxel": 2, "icp": 6, "dense": 5, "frame": 7, "fps": 2}
     assert {fam: len(s) for fam, s in M.FAMILIES.items()} == want
     for fam in M.FAMILIES.values():
         for setting, env in fam.items():
@@ -68,5 +68,4 @@ def test_sor_inputs_keep_their_distance_from_the_threshold(oracle):
 
 def test_sor_settings_reach_every_pass0_kernel():
     reached = {M.sor_pass0(k, env) for env in list(M.FAMILIES["grid"].values()) + [{}] for k in M.SOR_KS}
-    assert reached == {None, "block<4>", "block<8>", "block<16>", "block<32>", "cell<16,8,4>", "cell<16,16,4>", "cell<32,16,4>", "cell<64,16,4>",
-                       "cell<64,32,1>"}
+    assert reached == {None, "block<4>", "block<8>", "block<16>", "block<32>"}

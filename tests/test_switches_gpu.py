@@ -156,10 +156,9 @@ def test_grid_sor_bounds_switches(defaults, grid_oracle, tmp_path, setting):
 
 
 def test_the_sor_settings_reach_every_pass0_kernel():
-    """between them the settings launch every sor_cell_kernel instantiation and every sor_block_kernel<S> (kpx_knn.hip)"""
+    """between them the settings launch every sor_block_kernel<S> and the wave-per-query passes alone (kpx_knn.hip)"""
     reached = {M.sor_pass0(k, env) for env in list(M.FAMILIES["grid"].values()) + [{}] for k in M.SOR_KS}
-    assert reached == {None, "block<4>", "block<8>", "block<16>", "block<32>", "cell<16,8,4>", "cell<16,16,4>", "cell<32,16,4>", "cell<64,16,4>",
-                       "cell<64,32,1>"}
+    assert reached == {None, "block<4>", "block<8>", "block<16>", "block<32>"}
     assert {M.sor_pass0(k, {}) for k in M.SOR_KS} == {None, "block<8>", "block<16>", "block<32>"}       # what the default reaches
 
 
