@@ -354,7 +354,8 @@ int kpx_ransac_corres(const float *src, int64_t n_src, const float *tgt, int64_t
  * the master cloud).  The target operand is prepared once; the problems' iterations are queued round-robin on
  * `stream` and each problem's convergence flag is polled through a side stream that waits only for that
  * problem, so the host round trip is hidden behind the other problems' sweeps (kernels never overlap).
- * h_src / h_n_src: host arrays of `count` entries; h_init: count x 16; d_results: count x 20 (as kpx_icp). */
+ * h_src / h_n_src: host arrays of `count` entries; h_init: count x 16; d_results: count x 20 (as kpx_icp).
+ * 1 <= count <= 64: kpx_icp_batch refuses any other batch, and the size query answers 0 for it. */
 size_t kpx_icp_batch_workspace_bytes(int32_t count, const int64_t *h_n_src, int64_t n_tgt);
 int kpx_icp_batch(int32_t count, const float *const *h_src, const int64_t *h_n_src, const float *tgt,
                   const float *tgt_normals, int64_t n_tgt, double max_dist, const double *h_init, int32_t mode,

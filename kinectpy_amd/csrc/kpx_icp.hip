@@ -11,8 +11,9 @@
 //   kpx_icpiter.h   one iteration of the culled registration in one kernel: per registration, per batch, the whole chain in one launch
 //   kpx_icprows.h   the same iteration with a wave per 64 rows (the calm iterations)
 //   kpx_icpchain.h  host: which one-launch chains may be resident together
-// Below: the switches (IcpSwitches), profiling read-backs, plans and workspace, the search launches, the exported entry points, and
-// the batch driver (icp_batch_ordered with drive_grouped / drive_windowed / drive_dense_polled).
+// Below: the switches (IcpSwitches), profiling read-backs, plans and workspace, the search launches, what the entry points share (NnProblem: setup
+// and the correspondences' way out; icp_search_solve_loop), the exported entry points, and the batch driver (batch_carve, icp_batch_ordered
+// with drive_grouped / drive_windowed / drive_dense_polled).
 #include <chrono>
 #include <limits.h>
 #include <string.h>
@@ -43,8 +44,6 @@ namespace kpx {
 // first use (local_engine() below, chain_form_on() in kpx_icpchain.h).
 struct IcpSwitches {
     bool nn_screen;            // KPX_NN_SCREEN=0: dense engine without its float32 screening sweep; default on (tools/nn_dense_probe.py)
-    bool nn_dense_sort;        // KPX_NN_DENSE_SORT=0: the all-pairs operands in the caller's order; default curve order
-    int nn_fast;               // KPX_NN_FAST=0|1: force the per-trip / the chunked dense fp64 sweep; default -1 = by case
     bool batch_launch;         // KPX_ICP_BATCH_LAUNCH=0: one launch chain per registration; default one per group of 8
     bool fuse;                 // KPX_ICP_FUSE=0: per-registration chains with the update in its own kernel, and no grouped chain; default on
     int split;                 // KPX_ICP_SPLIT=0|1|2: update in the next sweep's prologue / its own kernel / the sweep's last block; default 2 (test_icp_update_placements_and_light_skip_are_bit_identical)
@@ -74,9 +73,6 @@ static const IcpSwitches &icp_switches()
         auto real = [](const char *name, float dflt) { const char *e = getenv(name); return e ? (float)atof(e) : dflt; };
         IcpSwitches w;
         w.nn_screen = not0("KPX_NN_SCREEN");
-        w.nn_dense_sort = not0("KPX_NN_DENSE_SORT");
-        const char *fast = getenv("KPX_NN_FAST");
-        w.nn_fast = fast ? atoi(fast) : -1;
         w.batch_launch = not0("KPX_ICP_BATCH_LAUNCH");
         w.fuse = not0("KPX_ICP_FUSE");
         w.split = digit("KPX_ICP_SPLIT", '2', KPX_ICP_SPLIT_DEFAULT);
@@ -324,10 +320,9 @@ static __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__
     out[3 * r] = src[3 * i]; out[3 * r + 1] = src[3 * i + 1]; out[3 * r + 2] = src[3 * i + 2];
 }
 // ordered: b.row_of already holds the Morton order (morton_order_batch)
-static bool dense_sort_on() { return icp_switches().nn_dense_sort; }      // A/B switch: the all-pairs operands in curve order
 static int nn_prep_source(const float *src, const NnPlan &p, const NnBuffers &b, hipStream_t st, bool ordered = false)
 {
-    if (!local_engine()) return dense_sort_on() ? morton_order(src, p.n_src, b.sort_s, b.row_of, st) : KPX_OK;
+    if (!local_engine()) return morton_order(src, p.n_src, b.sort_s, b.row_of, st);       // the all-pairs sweep takes its rows in curve order
     KPX_HIP(hipMemsetAsync(b.acc_fixed, 0, ((size_t)3 * kAccCopies * kAcc * kFixedWords + 8) * sizeof(unsigned long long), st));
     int rc = ordered ? KPX_OK : morton_order(src, p.n_src, b.sort_s, b.row_of, st);
     if (rc) return rc;
@@ -374,18 +369,15 @@ static int nn_prep(const float *tgt, const NnPlan &p, const NnBuffers &b, hipStr
         KPX_LAUNCH_CHECK();
         return KPX_OK;
     }
-    // the all-pairs operand in the target's curve order (KPX_NN_DENSE_SORT=0: in the caller's order, as until round 3)
-    const bool dense_sort = dense_sort_on();
-    if (dense_sort) {
-        int rc = morton_order(tgt, p.n_tgt, b.sort_t, b.orig_t, st);
-        if (rc) return rc;
-    }
+    // the all-pairs operand in the target's curve order
+    int rc = morton_order(tgt, p.n_tgt, b.sort_t, b.orig_t, st);
+    if (rc) return rc;
     int64_t work = (p.tiles_pad + p.seed_tiles_pad) * 16;
     hipLaunchKernelGGL(nn_prep_kernel, dim3((unsigned)(cdiv(work, 256) > 2048 ? 2048 : cdiv(work, 256))), dim3(256), 0, st, tgt,
-                       p.n_tgt, p.tiles_pad, b.B, p.seed_tiles_pad, b.Bseed, dense_sort ? b.orig_t : (const int32_t *)nullptr, b.colB, b.colSeed);
+                       p.n_tgt, p.tiles_pad, b.B, p.seed_tiles_pad, b.Bseed, b.orig_t, b.colB, b.colSeed);
     {   // float32 screening operand: centre + radius from the target's bounding box
         double *bbox = b.tbbox + (size_t)kBboxBlocks * 6;
-        int rc = bbox_f32(tgt, p.n_tgt, bbox, b.tbbox, st);
+        rc = bbox_f32(tgt, p.n_tgt, bbox, b.tbbox, st);
         if (rc) return rc;
         hipLaunchKernelGGL(nn_aux_kernel, dim3(1), dim3(1), 0, st, bbox, b.aux);
         int64_t fw = p.f_tiles_pad * 16;
@@ -438,33 +430,93 @@ static int nn_search_launch(const float *src, const float *tgt, const float *tn,
         KPX_LAUNCH_CHECK();
         return KPX_OK;
     }
-    const int32_t *rperm = dense_sort_on() ? b.row_of : (const int32_t *)nullptr;     // (nn_prep_source ordered the rows)
     {
     // (timed as ONE unit: a bare search's seed sweep + its merge belong to the all-pairs sweep they make cheaper -- with bounds from
     // every 16th tile the main sweep alone runs at 38 TFLOP/s, from every 64th at 33, but the seed sweep costs what it saves beyond that)
     ProfScope prof(KPX_PROF_NN_MFMA, 8.0 * (double)p.n_src * (double)p.n_tgt, st);     // 4 MAC per (source, target) pair
     if (!have_prev) {
-        hipLaunchKernelGGL(nn_mfma_kernel<false>, dim3(p.row_blocks, 1), thr, 0, st, n, b.Bseed, b.colSeed, (int32_t)p.seed_tiles_pad,
-                           done, b.A64, b.K64, (const double *)nullptr, (const int32_t *)nullptr, b.part_val, b.part_idx, rperm);
+        hipLaunchKernelGGL(nn_mfma_kernel, dim3(p.row_blocks, 1), thr, 0, st, n, b.Bseed, b.colSeed, (int32_t)p.seed_tiles_pad,
+                           done, b.A64, b.K64, (const double *)nullptr, (const int32_t *)nullptr, b.part_val, b.part_idx, b.row_of);
         hipLaunchKernelGGL(nn_merge_kernel<ColorTerms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx, 1,
                            0.0, -2, b.init_idx, (double *)nullptr, b.init_val, b.part_acc, (const int32_t *)nullptr, (const int32_t *)nullptr,
                            ColorTerms{});
     }
-    const int fast_env = icp_switches().nn_fast;               // A/B switch: 0 / 1 force a form
-    // (with the operands in curve order the per-trip form wins in both cases: its prefilter rarely passes, and the chunked form's
-    // bookkeeping is then pure overhead -- 0.545 vs 0.532 of the matrix peak warm, 0.458 vs 0.453 cold)
-    const bool fast = fast_env >= 0 ? fast_env != 0 : (have_prev && !dense_sort_on());
-    if (fast)
-        hipLaunchKernelGGL(nn_mfma_kernel<true>, dim3(p.row_blocks, p.splits), thr, 0, st, n, b.B, b.colB, p.tiles_per_split, done, b.A64, b.K64,
-                           b.init_val, b.init_idx, b.part_val, b.part_idx, rperm);
-    else
-        hipLaunchKernelGGL(nn_mfma_kernel<false>, dim3(p.row_blocks, p.splits), thr, 0, st, n, b.B, b.colB, p.tiles_per_split, done, b.A64, b.K64,
-                           b.init_val, b.init_idx, b.part_val, b.part_idx, rperm);
+    // (b.row_of: nn_prep_source put the rows in the source's curve order)
+    hipLaunchKernelGGL(nn_mfma_kernel, dim3(p.row_blocks, p.splits), thr, 0, st, n, b.B, b.colB, p.tiles_per_split, done, b.A64, b.K64,
+                       b.init_val, b.init_idx, b.part_val, b.part_idx, b.row_of);
     }
     hipLaunchKernelGGL(nn_merge_kernel<Terms>, dim3((unsigned)cdiv(n, kMergeThreads)), dim3(kMergeThreads), 0, st, src, n, tgt, tn, T, done, b.part_val, b.part_idx,
                        p.splits, max_d2, mode, b.idx_cur, b.d2_cur, (double *)nullptr, b.part_acc, (const int32_t *)nullptr,
                        (const int32_t *)nullptr, ct);
     KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+// What every entry point for one pair of clouds starts with: the workspace carved (`extra` doubles behind the search's buffers), the
+// state initialised from h_init (null: a bare search has no state) and both clouds prepared for the engine in use.
+struct NnProblem {
+    NnPlan p;
+    NnBuffers b;
+    double *extra;
+    int setup(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *h_init, void *ws, size_t ws_bytes, hipStream_t st,
+              size_t extra_doubles = 0)
+    {
+        Arena a(ws, ws_bytes);
+        p = nn_plan(n_src, n_tgt);
+        nn_carve(a, n_src, n_tgt, p, &b);
+        extra = a.get<double>(extra_doubles);
+        KPX_ARENA_CHECK(a);
+        if (h_init) hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
+        const int rc = nn_prep(tgt, p, b, st);
+        return rc ? rc : nn_prep_source(src, p, b, st);
+    }
+    // the last search's correspondences, to the callers that asked for them
+    int copy_pairs(int32_t *idx, double *d2, hipStream_t st) const
+    {
+        if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)p.n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)p.n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
+        return KPX_OK;
+    }
+};
+
+// When a search of the all-pairs engine may take the float32 screening sweep (the culled engine has none): never; from the third
+// search on; or, kByPolicy, as ScreenPolicy finds the registration calm where every iteration is polled and from the third search on
+// where not.
+enum class Screen { kNever, kFromThird, kByPolicy };
+struct IcpCriteria {
+    int max_iteration;
+    double relative_fitness, relative_rmse;
+    int poll_interval;
+};
+// The registration loop of three launches and more per iteration: the search with the sums of nn_merge_kernel<Terms> (merge_mode),
+// then icp_solve_kernel (solve_mode).  Kernels queued behind a raised `done` return at once, so the flag is only read back every
+// poll_interval iterations (0 = never); kByPolicy reads the whole tail of the state, for ScreenPolicy.
+template <class Terms>
+static int icp_search_solve_loop(const float *src, const float *tgt, const float *tn, const NnProblem &q, double md2, int merge_mode, int solve_mode,
+                                 Screen screen, const IcpCriteria &c, double *d_result, hipStream_t st, Terms terms = Terms{})
+{
+    const NnBuffers &b = q.b;
+    ScreenPolicy policy;
+    for (int k = 0; k <= c.max_iteration; ++k) {
+        // (ScreenPolicy judges by the fitness and rmse of every iteration: it has them only where every iteration is polled)
+        const bool allow_screen = screen == Screen::kByPolicy && c.poll_interval == 1 ? policy.allow(k) : screen != Screen::kNever && k >= 2;
+        const int rc = nn_search_launch<Terms>(src, tgt, tn, q.p, b, b.state->T, &b.state->done, k > 0, allow_screen, md2, merge_mode, st, terms);
+        if (rc) return rc;
+        hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kSolveThreads), 0, st, b.part_acc, (int)cdiv(q.p.n_src, kMergeThreads), q.p.n_src, solve_mode,
+                           k, c.max_iteration, c.relative_fitness, c.relative_rmse, b.state, d_result);
+        if (c.poll_interval > 0 && (k + 1) % c.poll_interval == 0 && k < c.max_iteration) {
+            // One copy from the device's state into the same bytes of h_state: everything from `fitness` on where the policy observes,
+            // the word `done` alone elsewhere.  Only what was copied is read below.
+            const bool tail = screen == Screen::kByPolicy;
+            const size_t at = tail ? offsetof(IcpState, fitness) : offsetof(IcpState, done);
+            IcpState h_state = {};
+            KPX_HIP(hipMemcpyAsync((char *)&h_state + at, (const char *)b.state + at, tail ? sizeof(IcpState) - at : sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, st));
+            KPX_HIP(hipStreamSynchronize(st));
+            if (h_state.done) break;
+            if (tail) policy.observe(h_state.fitness, h_state.rmse);
+        }
+    }
     return KPX_OK;
 }
 
@@ -538,20 +590,11 @@ KPX_EXPORT int kpx_nn_search(const float *src, int64_t n_src, const float *tgt, 
     if (n_src == 0) return KPX_OK;
     KPX_REQUIRE(src && tgt && d_T && idx && d2 && ws, "kpx_nn_search: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    NnPlan p = nn_plan(n_src, n_tgt);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, p, &b);
-    KPX_ARENA_CHECK(a);
-    int rc = nn_prep(tgt, p, b, st);
+    NnProblem q;
+    int rc = q.setup(src, n_src, tgt, n_tgt, nullptr, ws, ws_bytes, st);
     if (rc) return rc;
-    rc = nn_prep_source(src, p, b, st);
-    if (rc) return rc;
-    rc = nn_search_launch(src, tgt, nullptr, p, b, d_T, nullptr, false, false, 0.0, -1, st);
-    if (rc) return rc;
-    KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return KPX_OK;
+    rc = nn_search_launch(src, tgt, nullptr, q.p, q.b, d_T, nullptr, false, false, 0.0, -1, st);
+    return rc ? rc : q.copy_pairs(idx, d2, st);
 }
 
 // ---- evaluate_registration + get_information_matrix_from_point_clouds in one pass ---------------------------------------
@@ -635,25 +678,17 @@ KPX_EXPORT int kpx_registration_eval(const float *src, int64_t n_src, const floa
     KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_registration_eval: cloud too large");
     KPX_REQUIRE(src && tgt && d_T && d_result && ws, "kpx_registration_eval: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    NnPlan p = nn_plan(n_src, n_tgt);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, p, &b);
-    double *part = a.get<double>((size_t)kEvalBlocks * kEvalSums);
-    KPX_ARENA_CHECK(a);
-    int rc = nn_prep(tgt, p, b, st);
+    NnProblem q;
+    int rc = q.setup(src, n_src, tgt, n_tgt, nullptr, ws, ws_bytes, st, (size_t)kEvalBlocks * kEvalSums);      // (the state is not used)
     if (rc) return rc;
-    rc = nn_prep_source(src, p, b, st);
+    rc = nn_search_launch(src, tgt, nullptr, q.p, q.b, d_T, nullptr, false, false, 0.0, -1, st);      // as kpx_nn_search: the engine kpx_nn_engine selects
     if (rc) return rc;
-    rc = nn_search_launch(src, tgt, nullptr, p, b, d_T, nullptr, false, false, 0.0, -1, st);      // as kpx_nn_search: the engine kpx_nn_engine selects
-    if (rc) return rc;
+    double *part = q.extra;
     const int nb = (int)(cdiv(n_src, kEvalThreads) > kEvalBlocks ? kEvalBlocks : cdiv(n_src, kEvalThreads));
-    hipLaunchKernelGGL(regeval_acc_kernel, dim3(nb), dim3(kEvalThreads), 0, st, tgt, n_src, n_tgt, b.idx_cur, b.d2_cur, max_dist * max_dist, part);
+    hipLaunchKernelGGL(regeval_acc_kernel, dim3(nb), dim3(kEvalThreads), 0, st, tgt, n_src, n_tgt, q.b.idx_cur, q.b.d2_cur, max_dist * max_dist, part);
     hipLaunchKernelGGL(regeval_finish_kernel, dim3(1), dim3(64), 0, st, part, nb, n_src, d_result);
     KPX_LAUNCH_CHECK();
-    if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return KPX_OK;
+    return q.copy_pairs(idx, d2, st);
 }
 
 KPX_EXPORT size_t kpx_kabsch_workspace_bytes(int64_t n_corr)
@@ -695,16 +730,11 @@ KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const 
     KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_icp: cloud too large");
     KPX_REQUIRE(src && tgt && h_init && d_result && ws, "kpx_icp: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    NnPlan p = nn_plan(n_src, n_tgt);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, p, &b);
-    KPX_ARENA_CHECK(a);
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
-    int rc = nn_prep(tgt, p, b, st);
+    NnProblem q;
+    int rc = q.setup(src, n_src, tgt, n_tgt, h_init, ws, ws_bytes, st);
     if (rc) return rc;
-    rc = nn_prep_source(src, p, b, st);
-    if (rc) return rc;
+    const NnPlan &p = q.p;
+    const NnBuffers &b = q.b;
     const double md2 = max_dist * max_dist;
     if (local_engine()) {
         // one launch per iteration; kernels queued behind a raised `done` return at once, so the flag is only read back
@@ -720,24 +750,12 @@ KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const 
             }
         }
     } else {
-        ScreenPolicy policy;
-        for (int k = 0; k <= max_iteration; ++k) {
-            rc = nn_search_launch(src, tgt, tgt_normals, p, b, b.state->T, &b.state->done, k > 0,
-                                  poll_interval == 1 ? policy.allow(k) : k >= 2, md2, mode, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kSolveThreads), 0, st, b.part_acc, (int)cdiv(n_src, kMergeThreads), n_src, mode, k,
-                               max_iteration, relative_fitness, relative_rmse, b.state, d_result);
-            if (poll_interval > 0 && (k + 1) % poll_interval == 0 && k < max_iteration) {
-                IcpState h_state;
-                KPX_HIP(hipMemcpyAsync(&h_state.fitness, &b.state->fitness, sizeof(IcpState) - offsetof(IcpState, fitness), hipMemcpyDeviceToHost, st));
-                KPX_HIP(hipStreamSynchronize(st));
-                if (h_state.done) break;
-                policy.observe(h_state.fitness, h_state.rmse);
-            }
-        }
+        rc = icp_search_solve_loop<ColorTerms>(src, tgt, tgt_normals, q, md2, mode, mode, Screen::kByPolicy,
+                                               IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st);
+        if (rc) return rc;
     }
-    if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
+    rc = q.copy_pairs(idx, d2, st);
+    if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -761,30 +779,13 @@ KPX_EXPORT int kpx_colored_icp(const float *src, const float *src_colors, int64_
     KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_colored_icp: cloud too large");
     KPX_REQUIRE(src && tgt && h_init && d_result && ws, "kpx_colored_icp: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    NnPlan p = nn_plan(n_src, n_tgt);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, p, &b);
-    KPX_ARENA_CHECK(a);
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
-    int rc = nn_prep(tgt, p, b, st);
-    if (rc) return rc;
-    rc = nn_prep_source(src, p, b, st);
+    NnProblem q;
+    int rc = q.setup(src, n_src, tgt, n_tgt, h_init, ws, ws_bytes, st);
     if (rc) return rc;
     const ColorTerms ct{ src_colors, tgt_colors, tgt_gradient, sqrt(lambda_geometric), sqrt(1.0 - lambda_geometric) };
-    const double md2 = max_dist * max_dist;
-    for (int k = 0; k <= max_iteration; ++k) {
-        rc = nn_search_launch(src, tgt, tgt_normals, p, b, b.state->T, &b.state->done, k > 0, false, md2, 2, st, ct);
-        if (rc) return rc;
-        hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kSolveThreads), 0, st, b.part_acc, (int)cdiv(n_src, kMergeThreads), n_src, 1, k,
-                           max_iteration, relative_fitness, relative_rmse, b.state, d_result);
-        if (poll_interval > 0 && (k + 1) % poll_interval == 0 && k < max_iteration) {
-            int32_t h_done = 0;
-            KPX_HIP(hipMemcpyAsync(&h_done, &b.state->done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            KPX_HIP(hipStreamSynchronize(st));
-            if (h_done) break;
-        }
-    }
+    rc = icp_search_solve_loop(src, tgt, tgt_normals, q, max_dist * max_dist, 2, 1, Screen::kNever,
+                               IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st, ct);
+    if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -807,32 +808,14 @@ KPX_EXPORT int kpx_generalized_icp(const float *src, const double *src_cov, int6
     KPX_REQUIRE(n_src < ((int64_t)1 << 31) && n_tgt < ((int64_t)1 << 31) - 65536, "kpx_generalized_icp: cloud too large");
     KPX_REQUIRE(src && tgt && h_init && d_result && ws, "kpx_generalized_icp: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    NnPlan p = nn_plan(n_src, n_tgt);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, p, &b);
-    KPX_ARENA_CHECK(a);
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
-    int rc = nn_prep(tgt, p, b, st);
+    NnProblem q;
+    int rc = q.setup(src, n_src, tgt, n_tgt, h_init, ws, ws_bytes, st);
     if (rc) return rc;
-    rc = nn_prep_source(src, p, b, st);
+    rc = icp_search_solve_loop(src, tgt, nullptr, q, max_dist * max_dist, kModeGicp, 1, Screen::kFromThird,
+                               IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st, GicpTerms{ src_cov, tgt_cov });
     if (rc) return rc;
-    const GicpTerms gt{ src_cov, tgt_cov };
-    const double md2 = max_dist * max_dist;
-    for (int k = 0; k <= max_iteration; ++k) {
-        rc = nn_search_launch(src, tgt, nullptr, p, b, b.state->T, &b.state->done, k > 0, k >= 2, md2, kModeGicp, st, gt);
-        if (rc) return rc;
-        hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kSolveThreads), 0, st, b.part_acc, (int)cdiv(n_src, kMergeThreads), n_src, 1, k,
-                           max_iteration, relative_fitness, relative_rmse, b.state, d_result);
-        if (poll_interval > 0 && (k + 1) % poll_interval == 0 && k < max_iteration) {
-            int32_t h_done = 0;
-            KPX_HIP(hipMemcpyAsync(&h_done, &b.state->done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            KPX_HIP(hipStreamSynchronize(st));
-            if (h_done) break;
-        }
-    }
-    if (idx) KPX_HIP(hipMemcpyAsync(idx, b.idx_cur, (size_t)n_src * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (d2) KPX_HIP(hipMemcpyAsync(d2, b.d2_cur, (size_t)n_src * sizeof(double), hipMemcpyDeviceToDevice, st));
+    rc = q.copy_pairs(idx, d2, st);
+    if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -914,24 +897,43 @@ KPX_EXPORT int kpx_rotate_covariances(const double *cov, int64_t n, const double
 // short and latency-bound: one problem alone leaves most of the chip idle), each with two chunks of iterations in
 // flight and its state copied to pinned memory after every chunk, so neither the lanes nor the host wait for a round
 // trip.  The caller's stream continues after all lanes have finished.
+namespace kpx {
+// The workspace of a batch (count <= kBatchMax), carved for the call and counted for the size query by the same lines: the target's
+// operands once, padded for the largest split plan and shared by the buffers of every problem; each problem's own; and the scratch
+// of the batch sort (ms) where that sort can take the target and the sources together.  -> whether it can
+constexpr int kBatchMax = 64;
+struct BatchLayout {
+    NnPlan plans[kBatchMax], tplan;
+    NnBuffers bufs[kBatchMax];
+    MortonBatchScratch ms;
+};
+static bool batch_carve(Arena &a, int32_t count, const int64_t *h_n_src, int64_t n_tgt, BatchLayout *L)
+{
+    L->tplan = nn_plan(h_n_src[0], n_tgt);
+    int64_t total_pts = n_tgt;
+    for (int i = 0; i < count; ++i) {
+        L->plans[i] = nn_plan(h_n_src[i], n_tgt);
+        if (L->plans[i].tiles_pad > L->tplan.tiles_pad) L->tplan.tiles_pad = L->plans[i].tiles_pad;
+        if (L->plans[i].f_tiles_pad > L->tplan.f_tiles_pad) L->tplan.f_tiles_pad = L->plans[i].f_tiles_pad;
+        total_pts += h_n_src[i];
+    }
+    NnBuffers shared = {};
+    nn_carve_target(a, L->tplan, &shared);
+    for (int i = 0; i < count; ++i) {
+        L->bufs[i] = shared;
+        nn_carve_source(a, h_n_src[i], L->plans[i], &L->bufs[i]);
+    }
+    const bool can_batch_sort = count + 1 <= kMortonBatchMax && total_pts < ((int64_t)1 << 31);
+    if (can_batch_sort) morton_batch_carve(a, total_pts, &L->ms);
+    return can_batch_sort;
+}
+}  // namespace kpx
 KPX_EXPORT size_t kpx_icp_batch_workspace_bytes(int32_t count, const int64_t *h_n_src, int64_t n_tgt)
 {
+    if (count < 1 || count > kBatchMax || !h_n_src) return 0;          // (a batch kpx_icp_batch refuses)
     Arena a(nullptr, 0);
-    NnBuffers b;
-    if (count < 1 || !h_n_src) return 0;
-    NnPlan tplan = nn_plan(h_n_src[0], n_tgt);          // the shared operand is padded for the largest split plan
-    for (int i = 1; i < count; ++i) {
-        NnPlan q = nn_plan(h_n_src[i], n_tgt);
-        if (q.tiles_pad > tplan.tiles_pad) tplan.tiles_pad = q.tiles_pad;
-        if (q.f_tiles_pad > tplan.f_tiles_pad) tplan.f_tiles_pad = q.f_tiles_pad;
-    }
-    nn_carve_target(a, tplan, &b);
-    int64_t total = n_tgt;
-    for (int i = 0; i < count; ++i) { nn_carve_source(a, h_n_src[i], nn_plan(h_n_src[i], n_tgt), &b); total += h_n_src[i]; }
-    if (count + 1 <= kMortonBatchMax && total < ((int64_t)1 << 31)) {
-        MortonBatchScratch ms;
-        morton_batch_carve(a, total, &ms);
-    }
+    BatchLayout L;
+    batch_carve(a, count, h_n_src, n_tgt, &L);
     return a.off;
 }
 KPX_EXPORT int kpx_icp_batch(int32_t count, const float *const *h_src, const int64_t *h_n_src, const float *tgt,
@@ -1320,7 +1322,7 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
                            double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness, double relative_rmse,
                            double *d_results, void *ws, size_t ws_bytes, void *stream, bool presorted)
 {
-    KPX_REQUIRE(count >= 1 && count <= 64 && h_src && h_n_src, "kpx_icp_batch: bad batch");
+    KPX_REQUIRE(count >= 1 && count <= kBatchMax && h_src && h_n_src, "kpx_icp_batch: bad batch");
     KPX_REQUIRE(mode == KPX_ICP_POINT_TO_POINT || mode == KPX_ICP_POINT_TO_PLANE, "kpx_icp: unknown estimation mode");
     KPX_REQUIRE(mode != KPX_ICP_POINT_TO_PLANE || tgt_normals,
                 "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal vectors for target PointCloud.");
@@ -1340,28 +1342,11 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
     int lrc = lanes_get(&ln);
     if (lrc) return lrc;
     Arena a(ws, ws_bytes);
-    NnPlan plans[64];
-    NnBuffers bufs[64] = {};
-    NnPlan tplan = nn_plan(h_n_src[0], n_tgt);          // the shared operand is padded for the largest split plan
-    for (int i = 0; i < count; ++i) {
-        plans[i] = nn_plan(h_n_src[i], n_tgt);
-        if (plans[i].tiles_pad > tplan.tiles_pad) tplan.tiles_pad = plans[i].tiles_pad;
-        if (plans[i].f_tiles_pad > tplan.f_tiles_pad) tplan.f_tiles_pad = plans[i].f_tiles_pad;
-    }
-    nn_carve_target(a, tplan, &bufs[0]);
-    for (int i = 0; i < count; ++i) {
-        bufs[i].B = bufs[0].B; bufs[i].Bseed = bufs[0].Bseed; bufs[i].colB = bufs[0].colB; bufs[i].colSeed = bufs[0].colSeed; bufs[i].Bf = bufs[0].Bf; bufs[i].aux = bufs[0].aux;
-        bufs[i].tbbox = bufs[0].tbbox;
-        bufs[i].Bs = bufs[0].Bs; bufs[i].orig_t = bufs[0].orig_t; bufs[i].tile_box = bufs[0].tile_box; bufs[i].group_box = bufs[0].group_box;
-        bufs[i].sort_t = bufs[0].sort_t;
-        nn_carve_source(a, h_n_src[i], plans[i], &bufs[i]);
-    }
-    int64_t total_pts = n_tgt;
-    for (int i = 0; i < count; ++i) total_pts += h_n_src[i];
-    const bool can_batch_sort = count + 1 <= kMortonBatchMax && total_pts < ((int64_t)1 << 31);
-    MortonBatchScratch ms;
-    if (can_batch_sort) morton_batch_carve(a, total_pts, &ms);
+    BatchLayout L;
+    const bool can_batch_sort = batch_carve(a, count, h_n_src, n_tgt, &L);
     KPX_ARENA_CHECK(a);
+    const NnPlan *plans = L.plans, &tplan = L.tplan;
+    const NnBuffers *bufs = L.bufs;
     // the shared target and every source are ordered along their Morton curves by ONE sort (cloud number above the code)
     const bool ordered = can_batch_sort && local_engine();
     int rc = KPX_OK;
@@ -1376,7 +1361,7 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
             mb.bbox[c] = !on ? nullptr : (c == 0 ? bufs[0].sort_t.bbox : bufs[c - 1].sort_s.bbox);
             mb.off[c + 1] = mb.off[c] + (!on ? 0 : (c == 0 ? n_tgt : h_n_src[c - 1]));
         }
-        rc = morton_order_batch(mb, ms, st, presorted);
+        rc = morton_order_batch(mb, L.ms, st, presorted);
         if (rc) return rc;
     }
     rc = nn_prep(tgt, tplan, bufs[0], st, ordered);

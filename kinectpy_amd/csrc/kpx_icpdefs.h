@@ -22,11 +22,6 @@ constexpr int kRT = 2;                       // 16-row tiles per wave (the sweep
 constexpr int kWaves = 4;
 constexpr int kRowsPerBlock = kWaves * kRT * 16;   // 128
 constexpr int kCT = 32;                      // 16-column tiles per LDS stage (16 KiB)
-#ifndef KPX_NN_CHUNK
-#define KPX_NN_CHUNK 4                       // measured 100k x 100k inside a registration: 2 -> 38.7, 4 -> 39.1, 8 -> 36.5, 16 -> 35.9 TFLOP/s
-#endif
-
-constexpr int kChunk = KPX_NN_CHUNK;         // column tiles per fast-pass chunk of the dense sweep (nn_mfma_kernel)
 constexpr int kStageDoubles = kCT * 64;
 #ifndef KPX_SEED_STRIDE
 #define KPX_SEED_STRIDE 128                 // round 4, operands in curve order, seed = every n-th POINT of the curve: whole bare search 100k x 100k at

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(const float *__restrict__ 
                                                       int32_t *__restrict__ colB, int32_t *__restrict__ colSeed)
 {
     // perm (round 4): the columns stand in the target's CURVE order (perm[slot] = the caller's index of the point in column `slot`), so
-    // that the 64 columns of a chunk are neighbours in space and a row's bound -- however loose -- reaches few chunks; colB / colSeed carry
+    // that the 32 columns of a trip are neighbours in space and a row's bound -- however loose -- reaches few trips; colB / colSeed carry
     // every column's ORIGINAL index (INT_MAX in the padding): the sweep reports, and breaks ties by, those.
     const int64_t total = (tiles_pad + seed_tiles_pad) * 16;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(const float *__restrict__ 
         double b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = kSentinel;
         int32_t oj = INT_MAX;
         if (j < m) {
-            oj = perm ? perm[j] : (int32_t)j;
+            oj = perm[j];
             double tx = tgt[3 * (int64_t)oj], ty = tgt[3 * (int64_t)oj + 1], tz = tgt[3 * (int64_t)oj + 2];
             b0 = -2.0 * tx; b1 = -2.0 * ty; b2 = -2.0 * tz;
             b3 = fma(tx, tx, fma(ty, ty, tz * tz));
@@ -285,12 +285,12 @@ __global__ __launch_bounds__(256) void nn_overflow_kernel(const float *__restric
 
 // ---- the MFMA nearest-neighbour sweep ------------------------------------------------------------------
 // colid: the ORIGINAL target index of every column of B (the full operand or the seed operand: every kSeedStride-th tile), staged in LDS beside the tiles
-// FAST: the rows arrive with TIGHT bounds (the previous partner under the new transform: every ICP iteration after the first) -- the
-// stage is swept in chunks whose hot loop is MFMAs + one v_min_u32 per result register, and a chunk is swept again the exact way
-// only when some row's smallest high word reaches its bound (measured 100k x 100k: 50.6 TFLOP/s for the hot loop alone = 0.64 of the
-// 78.6 vendor peak, the instruction's measured issue ceiling; the per-trip prefilter form runs at 31).  !FAST: loose bounds (seed
-// sweep, first search) -- nearly every chunk would be swept twice, so every trip is examined behind the prefilter as it comes.
-template <bool FAST>
+// One form: every trip is examined behind the prefilter as it comes, whether the bounds are loose (seed sweep, first search) or tight
+// (the previous partner under the new transform).  Until round 4 searches with tight bounds took a chunked form -- a hot pass of
+// MFMAs + one v_min_u32 per result register over four column tiles, swept again the exact way only when some row's smallest high word
+// reached its bound.  With the operands in curve order the prefilter rarely passes and the chunks' bookkeeping is pure overhead: per
+// trip 0.545 against chunked 0.532 of the fp64 matrix peak inside a registration, 0.458 against 0.453 in a bare search
+// (profiles/r04/nn_dense_sorted.txt), so the chunked form was removed.
 __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double *__restrict__ B, const int32_t *__restrict__ colid, int32_t tiles_per_split,
                                                          const int32_t *__restrict__ done,
                                                          const double *__restrict__ A64, const double *__restrict__ K64,
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
                                                          double *__restrict__ part_val, int32_t *__restrict__ part_idx, const int32_t *__restrict__ rperm)
 {
     // rperm (round 4): block row r is the caller's row rperm[r] -- the source's curve order, so that the 32 rows of a wave are neighbours
-    // in space and reach the SAME few chunks of the (curve-ordered) columns; operands and results stay indexed by the caller's row
+    // in space and reach the SAME few trips of the (curve-ordered) columns; operands and results stay indexed by the caller's row
     if (done && *done) return;
     __shared__ __align__(16) double lds[2][kStageDoubles];
     __shared__ __align__(16) int32_t lds_col[2][kCT * 16];           // the stage's ORIGINAL column indices (the operand stands in curve order)
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
 #pragma unroll
     for (int rt = 0; rt < kRT; ++rt) {
         const int64_t row = row_base + rt * 16 + (lane & 15);
-        a[rt] = row < n ? A64[(int64_t)(rperm ? rperm[row] : row) * 4 + (lane >> 4)] : 0.0;
+        a[rt] = row < n ? A64[(int64_t)rperm[row] * 4 + (lane >> 4)] : 0.0;
     }
     // C operands (row seeds K_i), running best and its column: D layout row = (lane>>4) + 4*reg
     d4 seed[kRT];
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
             double kk = 1.0, bv = INFINITY;
             int32_t bj = INT_MAX;
             if (row < n) {
-                const int64_t ri = rperm ? rperm[row] : row;
+                const int64_t ri = rperm[row];
                 kk = K64[ri];
                 if (init_val) { bv = init_val[ri]; bj = init_idx[ri]; }
             }
@@ -406,45 +406,10 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
         const d4 P##10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], P##b0, seed[1], 0, 0, 0);       \
         const d4 P##01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], P##b1, seed[0], 0, 0, 0);       \
         const d4 P##11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], P##b1, seed[1], 0, 0, 0);
-        if (!FAST) {
 #pragma unroll 1
         for (int ct = 0; ct < kCT; ct += 2) {
             KPX_NN_TRIP(p, ct)
             examine(p00, p10, p01, p11, ct);
-        }
-        } else {
-        // A stage is swept in chunks of kChunk column tiles.  FAST pass of a chunk: nothing but the MFMAs and one v_min_u32 per result
-        // register -- the smallest HIGH WORD any column of the chunk produced for each of the lane's rows.  Only when some row's
-        // minimum reaches the high word of its running best (hi(D) > hi(best) implies D > best, so a chunk that never does cannot
-        // change any row's (value, column) minimum) is the chunk swept again the exact way.
-#pragma unroll 1
-        for (int c0 = 0; c0 < kCT; c0 += kChunk) {
-            unsigned hmin[kRT][4];
-#pragma unroll
-            for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) hmin[rt][r] = 0xFFFFFFFFu;
-#pragma unroll
-            for (int ct = 0; ct < kChunk; ct += 2) {
-                KPX_NN_TRIP(f, c0 + ct)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    hmin[0][r] = min(hmin[0][r], min(hi32(f00[r]), hi32(f01[r])));
-                    hmin[1][r] = min(hmin[1][r], min(hi32(f10[r]), hi32(f11[r])));
-                }
-            }
-            bool pass = false;
-#pragma unroll
-            for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pass |= hmin[rt][r] <= hi32(best[rt][r]);
-            if (__builtin_amdgcn_ballot_w64(pass) == 0) continue;
-#pragma unroll 1
-            for (int ct = c0; ct < c0 + kChunk; ct += 2) {
-                KPX_NN_TRIP(p, ct)
-                examine(p00, p10, p01, p11, ct);
-            }
-        }
         }
 #undef KPX_NN_TRIP
         __syncthreads();
@@ -467,7 +432,7 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
             }
             int64_t row = row_base + rt * 16 + (lane >> 4) + 4 * r;
             if ((lane & 15) == 0 && row < n) {
-                const int64_t ri = rperm ? rperm[row] : row;
+                const int64_t ri = rperm[row];
                 part_val[(int64_t)split * n + ri] = v;
                 part_idx[(int64_t)split * n + ri] = c;
             }

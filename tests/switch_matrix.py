@@ -36,13 +36,15 @@ def _settings(*specs):
 # free of the row order are no small change: the forms and their switches were removed from the library.
 # Nor the wave-per-16-queries pass-0 forms of kpx_sor and their switches KPX_SOR_BLOCK, KPX_SOR_BLOCK_MINK and KPX_SOR_CELL_SMALL: removed
 # as superseded by sor_block_kernel.
+# Nor the all-pairs engine's chunked fp64 sweep and caller-order operands and their switches KPX_NN_FAST and KPX_NN_DENSE_SORT: removed
+# as superseded by the per-trip sweep over curve-ordered operands (profiles/r04/nn_dense_sorted.txt).
 FAMILIES = {
     "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_OCC=0.2", "SOR_OCC=1.0", "BBOX_VEC=0"),
     "voxel": _settings("RADIX=0", "VOXEL_SINGLE=0"),
     # the launch-per-iteration chains of icp_rows_kernel: KPX_ICP_ROWS_R only shows with the rows form forced and the one-launch chain off
     "icp": _settings("ICP_FUSE=0", "ICP_BATCH_LAUNCH=0", "ICP_WINDOW=1", "ICP_WINDOW=64", "ICP_ROWS=2+ICP_ROWS_R=16+ICP_CHAIN=0",
                      "ICP_ROWS=2+ICP_ROWS_R=32+ICP_CHAIN=0"),
-    "dense": _settings("NN_SCREEN=0", "NN_DENSE_SORT=0", "NN_FAST=0", "NN_FAST=1", "NN_DENSE_SORT=0+NN_FAST=0"),
+    "dense": _settings("NN_SCREEN=0"),
     # KPX_ICP_CHAIN_ALONE=0 admits one-launch chains with frames in flight (the streams below); KPX_ORDER_LOOKAHEAD: any value >= 0 is accepted and cut to slots - 1; FRAME_SLOTS = 4 slots, so 0 and 3 are its ends (default 2)
     "frame": _settings("FRAME_SPECULATE=0", "FRAME_SPIN=0", "SHARD_NORMALS=1", "SHARD_FIXED_CAP=1",
                        "ORDER_LOOKAHEAD=0", "ORDER_LOOKAHEAD=3", "ICP_CHAIN_ALONE=0"),
@@ -185,14 +187,8 @@ DENSE_ITERS = 10
 
 
 def dense_sweep(have_prev, screened, env):
-    """nn_search_launch, all-pairs engine: which kernel serves a search -> "screen" | "mfma<true>" (chunked) | "mfma<false>" (per trip),
-    and whether the rows are permuted into curve order"""
-    sort = env.get("KPX_NN_DENSE_SORT", "")[:1] != "0"
-    if have_prev and screened and env.get("KPX_NN_SCREEN", "")[:1] != "0":
-        return "screen", sort
-    fast = env.get("KPX_NN_FAST")
-    chunked = (int(fast) != 0) if fast is not None else (have_prev and not sort)
-    return ("mfma<true>" if chunked else "mfma<false>"), sort
+    """nn_search_launch, all-pairs engine: which kernel serves a search -> "screen" | "mfma" """
+    return "screen" if have_prev and screened and env.get("KPX_NN_SCREEN", "")[:1] != "0" else "mfma"
 
 
 # ---------------------------------------------------------------------------------------------------------------- FPS

@@ -615,7 +615,7 @@ def test_segment_plane_ties_thresholds_and_sequential_path(ops, oracle):
 @pytest.fixture(params=["culled", "dense", "dense_fp64"])
 def engine(request, ops):
     """the correspondence-search implementations: the culled sweep (default), the all-pairs sweeps (fp64 MFMA + float32 screening),
-    and the all-pairs engine with every search on the fp64 MFMA sweep (cold form first, chunked warm form in later iterations)"""
+    and the all-pairs engine with every search on the fp64 MFMA sweep (loose bounds from the seed sweep first, tight ones from the previous partners in later iterations)"""
     prev = ops.nn_engine(request.param)
     yield request.param
     ops.nn_engine(prev)
@@ -820,6 +820,22 @@ def test_icp_batch_more_problems_than_lanes(ops, base_cloud):
             one = ops.icp(s_, tgt, 100.0, i0, "p2p", None, 9)
             assert b["iterations"] == one["iterations"] and b["fitness"] == one["fitness"]
             assert np.array_equal(b["transformation"], one["transformation"])
+
+
+def test_icp_batch_of_eight_sources_equals_single_problems(ops, base_cloud):
+    """eight registrations onto one target: with the target one cloud more than the batch sort takes, so the batch's workspace is carved
+    without the sort's scratch and every problem runs its own chain of launches -- each equals the single-problem call bit for bit"""
+    src, tgt, _ = synth.icp_pair(4000, base_cloud)
+    tn = ops.estimate_normals(torch.as_tensor(tgt).cuda(), 70.0, 40)
+    srcs = [src[450 * i:450 * i + 200 + 57 * i] for i in range(8)]      # 200 .. 599 rows
+    assert len(srcs) == 8 and all(200 <= len(s) <= 600 for s in srcs)
+    inits = [np.eye(4)] * 8
+    for mode, nrm in (("p2p", None), ("p2plane", tn)):
+        batch = ops.icp_batch(srcs, tgt, 100.0, inits, mode, nrm, 6)
+        for s_, b in zip(srcs, batch):
+            one = ops.icp(s_, tgt, 100.0, None, mode, nrm, 6)
+            assert b["iterations"] == one["iterations"] and b["fitness"] == one["fitness"], mode
+            assert np.array_equal(b["transformation"], one["transformation"]), mode
 
 
 def test_kabsch_pairs(ops, oracle, base_cloud):

@@ -286,13 +286,11 @@ def test_dense_engine_switches(defaults, tmp_path, setting):
     assert local == 0 and mfma > 0
     plan, plan0 = _dense_plan(env), _dense_plan({})
     if "KPX_NN_SCREEN" in env:
-        assert screen == 0 and b_screen > 0 and mfma == b_mfma + b_screen and not any(kern == "screen" for kern, _ in plan)
+        assert screen == 0 and b_screen > 0 and mfma == b_mfma + b_screen and "screen" not in plan
     else:
         assert screen == b_screen and mfma == b_mfma
-    assert plan0 == {("mfma<false>", True), ("screen", True)}
-    want = {"NN_SCREEN=0": {("mfma<false>", True)}, "NN_DENSE_SORT=0": {("mfma<false>", False), ("mfma<true>", False), ("screen", False)},
-            "NN_FAST=0": plan0, "NN_FAST=1": {("mfma<true>", True), ("screen", True)},
-            "NN_DENSE_SORT=0+NN_FAST=0": {("mfma<false>", False), ("screen", False)}}[setting]
+    assert plan0 == {"mfma", "screen"}
+    want = {"NN_SCREEN=0": {"mfma"}}[setting]
     assert plan == want, (setting, plan)
 
 
