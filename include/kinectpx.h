@@ -438,6 +438,38 @@ int kpx_generalized_icp(const float *src, const double *src_cov, int64_t n_src, 
                         double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
                         int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream);
 
+/* Robust registrations: [O3D] TransformationEstimationPointToPlane / ...ForColoredICP / ...ForGeneralizedICP with a RobustKernel.
+ * Every residual row r of the update (one per pair for point-to-plane; the two scaled rows sqrt(lambda) r_G and sqrt(1 - lambda) r_I
+ * of coloured ICP; the three rows of a GICP pair) enters the normal equations as J^T w J and J^T w r with Open3D's weights
+ *   KPX_LOSS_L2      w = 1                         KPX_LOSS_CAUCHY  w = 1 / (1 + (r / k)^2)
+ *   KPX_LOSS_L1      w = 1 / |r|                   KPX_LOSS_GM      w = k / (k + r^2)^2
+ *   KPX_LOSS_HUBER   w = k / max(|r|, k)           KPX_LOSS_TUKEY   w = (1 - min(1, |r| / k)^2)^2
+ * Correspondences, fitness, inlier rmse, the convergence test and so the iteration count do not depend on the loss (as in Open3D).
+ * Each entry point takes its L2 sibling's arguments (same checks, same d_result, workspace of kpx_icp_workspace_bytes) plus
+ * loss and loss_k, and runs search -> weighted sums -> solve as three launches per iteration on whichever engine kpx_nn_engine
+ * selected.  The robust point-to-plane entry accepts KPX_ICP_POINT_TO_PLANE only: Open3D's point-to-point estimation has no kernel.
+ * Deviations from Open3D: a row whose weight is not finite adds nothing (Open3D: NaN from L1 at r == 0); loss_k > 0 is required for
+ * Huber, Cauchy, GM and Tukey (Open3D does not check k), and ignored for L2 and L1. */
+#define KPX_LOSS_L2 0
+#define KPX_LOSS_L1 1
+#define KPX_LOSS_HUBER 2
+#define KPX_LOSS_CAUCHY 3
+#define KPX_LOSS_GM 4
+#define KPX_LOSS_TUKEY 5
+int kpx_icp_robust(const float *src, int64_t n_src, const float *tgt, const float *tgt_normals, int64_t n_tgt,
+                   double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness,
+                   double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                   size_t ws_bytes, void *stream, int32_t loss, double loss_k);
+int kpx_colored_icp_robust(const float *src, const float *src_colors, int64_t n_src, const float *tgt, const float *tgt_colors,
+                           const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist, const double *h_init,
+                           double lambda_geometric, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                           int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes, void *stream, int32_t loss,
+                           double loss_k);
+int kpx_generalized_icp_robust(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov,
+                               int64_t n_tgt, double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness,
+                               double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                               size_t ws_bytes, void *stream, int32_t loss, double loss_k);
+
 /* fuse_skeletons_gradient (utils/skeleton_fusion.py:21-74), SURVEY 8f rank 4: gradient- and centroid-weighted average of the
  * joints seen by three cameras.  skeletons f64 [cams][frames][joints][3] on the device; the first initial_frame (reference: 20)
  * frames are the mean over ALL cameras, later frames weight the FIRST THREE cameras (as the reference does) with

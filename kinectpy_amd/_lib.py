@@ -90,6 +90,11 @@ SIGNATURES = {
     "kpx_rotate_covariances": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "kpx_generalized_icp_workspace_bytes": (_sz, [_i64, _i64]),
     "kpx_generalized_icp": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_icp_robust": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _f64, _vp, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _i32, _f64]),
+    "kpx_colored_icp_robust": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _f64, _i32, _f64, _f64, _i32, _vp, _vp, _sz, _vp,
+                                         _i32, _f64]),
+    "kpx_generalized_icp_robust": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp,
+                                             _i32, _f64]),
     "kpx_fuse_skeletons": (C.c_int, [_vp, _i32, _i64, _i32, _f64, _f64, _i32, _vp, _vp]),
     "kpx_nn_engine": (C.c_int, [_i32]),
     "kpx_icp_batch_workspace_bytes": (_sz, [_i32, _vp, _i64]),

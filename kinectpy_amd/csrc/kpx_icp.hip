@@ -717,10 +717,20 @@ KPX_EXPORT size_t kpx_icp_workspace_bytes(int64_t n_src, int64_t n_tgt)
 {
     return kpx_nn_workspace_bytes(n_src, n_tgt);
 }
-KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const float *tgt_normals, int64_t n_tgt,
-                       double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness,
-                       double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
-                       size_t ws_bytes, void *stream)
+// The robust entry points' own checks (Open3D does not check k: a deviation, see include/kinectpx.h).
+static int loss_check(int32_t loss, double loss_k)
+{
+    KPX_REQUIRE(loss >= KPX_LOSS_L2 && loss <= KPX_LOSS_TUKEY, "unknown robust loss kind %d", loss);
+    KPX_REQUIRE(loss == KPX_LOSS_L2 || loss == KPX_LOSS_L1 || loss_k > 0.0, "the robust loss's k must be positive");
+    return KPX_OK;
+}
+// kpx_icp (loss == nullptr) and kpx_icp_robust: a robust registration is point-to-plane and takes the three-launch loop with the
+// weighted sums of nn_merge_kernel<RobustColorTerms> on BOTH engines -- never the culled engine's one-launch iteration, whose
+// fixed-point sums are not sized for unbounded weights.
+static int icp_run(const float *src, int64_t n_src, const float *tgt, const float *tgt_normals, int64_t n_tgt,
+                   double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness,
+                   double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                   size_t ws_bytes, void *stream, const RobustLoss *loss)
 {
     KPX_REQUIRE(mode == KPX_ICP_POINT_TO_POINT || mode == KPX_ICP_POINT_TO_PLANE, "kpx_icp: unknown estimation mode");
     KPX_REQUIRE(mode != KPX_ICP_POINT_TO_PLANE || tgt_normals,
@@ -736,7 +746,12 @@ KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const 
     const NnPlan &p = q.p;
     const NnBuffers &b = q.b;
     const double md2 = max_dist * max_dist;
-    if (local_engine()) {
+    if (loss) {
+        rc = icp_search_solve_loop(src, tgt, tgt_normals, q, md2, 1, 1, Screen::kByPolicy,
+                                   IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st,
+                                   RobustColorTerms{ ColorTerms{}, *loss });
+        if (rc) return rc;
+    } else if (local_engine()) {
         // one launch per iteration; kernels queued behind a raised `done` return at once, so the flag is only read back
         // every poll_interval iterations (0 = never)
         for (int k = 0; k <= max_iteration; ++k) {
@@ -759,6 +774,27 @@ KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const 
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
+KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const float *tgt_normals, int64_t n_tgt,
+                       double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness,
+                       double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                       size_t ws_bytes, void *stream)
+{
+    return icp_run(src, n_src, tgt, tgt_normals, n_tgt, max_dist, h_init, mode, max_iteration, relative_fitness, relative_rmse, poll_interval,
+                   d_result, idx, d2, ws, ws_bytes, stream, nullptr);
+}
+KPX_EXPORT int kpx_icp_robust(const float *src, int64_t n_src, const float *tgt, const float *tgt_normals, int64_t n_tgt,
+                              double max_dist, const double *h_init, int32_t mode, int32_t max_iteration, double relative_fitness,
+                              double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                              size_t ws_bytes, void *stream, int32_t loss, double loss_k)
+{
+    KPX_REQUIRE(mode != KPX_ICP_POINT_TO_POINT,
+                "kpx_icp_robust: TransformationEstimationPointToPoint takes no robust kernel; use KPX_ICP_POINT_TO_PLANE");
+    const int rc = loss_check(loss, loss_k);
+    if (rc) return rc;
+    const RobustLoss rl{ loss, loss_k };
+    return icp_run(src, n_src, tgt, tgt_normals, n_tgt, max_dist, h_init, mode, max_iteration, relative_fitness, relative_rmse, poll_interval,
+                   d_result, idx, d2, ws, ws_bytes, stream, &rl);
+}
 
 // ---- coloured ICP (preprocessing/registration.py:89-114) -----------------------------------------------------
 // [O3D] registration_colored_icp = the registration_icp loop (same correspondences, fitness, inlier rmse and convergence
@@ -766,10 +802,10 @@ KPX_EXPORT int kpx_icp(const float *src, int64_t n_src, const float *tgt, const 
 // kpx_color_gradient.  Search -> sums -> solve are three launches per iteration (nn_merge_kernel mode 2 + icp_solve_kernel):
 // the function is unused in the reference, so this path is built for parity, not for speed.
 KPX_EXPORT size_t kpx_colored_icp_workspace_bytes(int64_t n_src, int64_t n_tgt) { return kpx_icp_workspace_bytes(n_src, n_tgt); }
-KPX_EXPORT int kpx_colored_icp(const float *src, const float *src_colors, int64_t n_src, const float *tgt, const float *tgt_colors,
-                               const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist, const double *h_init,
-                               double lambda_geometric, int32_t max_iteration, double relative_fitness, double relative_rmse,
-                               int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes, void *stream)
+static int colored_icp_run(const float *src, const float *src_colors, int64_t n_src, const float *tgt, const float *tgt_colors,
+                           const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist, const double *h_init,
+                           double lambda_geometric, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                           int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes, void *stream, const RobustLoss *loss)
 {
     KPX_REQUIRE(tgt_normals, "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal vectors for target PointCloud.");
     KPX_REQUIRE(src_colors && tgt_colors && tgt_gradient, "kpx_colored_icp: colours of both clouds and the target's colour gradient are required");
@@ -783,24 +819,48 @@ KPX_EXPORT int kpx_colored_icp(const float *src, const float *src_colors, int64_
     int rc = q.setup(src, n_src, tgt, n_tgt, h_init, ws, ws_bytes, st);
     if (rc) return rc;
     const ColorTerms ct{ src_colors, tgt_colors, tgt_gradient, sqrt(lambda_geometric), sqrt(1.0 - lambda_geometric) };
-    rc = icp_search_solve_loop(src, tgt, tgt_normals, q, max_dist * max_dist, 2, 1, Screen::kNever,
-                               IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st, ct);
+    const IcpCriteria crit{ max_iteration, relative_fitness, relative_rmse, poll_interval };
+    rc = loss ? icp_search_solve_loop(src, tgt, tgt_normals, q, max_dist * max_dist, 2, 1, Screen::kNever, crit, d_result, st,
+                                      RobustColorTerms{ ct, *loss })
+              : icp_search_solve_loop(src, tgt, tgt_normals, q, max_dist * max_dist, 2, 1, Screen::kNever, crit, d_result, st, ct);
     if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
+KPX_EXPORT int kpx_colored_icp(const float *src, const float *src_colors, int64_t n_src, const float *tgt, const float *tgt_colors,
+                               const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist, const double *h_init,
+                               double lambda_geometric, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                               int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes, void *stream)
+{
+    return colored_icp_run(src, src_colors, n_src, tgt, tgt_colors, tgt_normals, tgt_gradient, n_tgt, max_dist, h_init, lambda_geometric,
+                           max_iteration, relative_fitness, relative_rmse, poll_interval, d_result, ws, ws_bytes, stream, nullptr);
+}
+KPX_EXPORT int kpx_colored_icp_robust(const float *src, const float *src_colors, int64_t n_src, const float *tgt, const float *tgt_colors,
+                                      const float *tgt_normals, const double *tgt_gradient, int64_t n_tgt, double max_dist,
+                                      const double *h_init, double lambda_geometric, int32_t max_iteration, double relative_fitness,
+                                      double relative_rmse, int32_t poll_interval, double *d_result, void *ws, size_t ws_bytes,
+                                      void *stream, int32_t loss, double loss_k)
+{
+    const int rc = loss_check(loss, loss_k);
+    if (rc) return rc;
+    const RobustLoss rl{ loss, loss_k };
+    return colored_icp_run(src, src_colors, n_src, tgt, tgt_colors, tgt_normals, tgt_gradient, n_tgt, max_dist, h_init, lambda_geometric,
+                           max_iteration, relative_fitness, relative_rmse, poll_interval, d_result, ws, ws_bytes, stream, &rl);
+}
 
 // ---- generalized ICP ----------------------------------------------------------------------------------------------------------
 // [O3D] registration_generalized_icp = the registration_icp loop (same correspondences, fitness, inlier rmse, convergence test and
-// iteration count) with TransformationEstimationForGeneralizedICP as the update (gicp_pair_rows; L2 loss only).  Search -> sums ->
+// iteration count) with TransformationEstimationForGeneralizedICP as the update (gicp_pair_rows; kpx_generalized_icp_robust weights
+// its rows by a robust loss).  Search -> sums ->
 // solve per iteration as kpx_colored_icp (nn_merge_kernel<GicpTerms> + icp_solve_kernel in its point-to-plane mode), on whichever
 // engine kpx_nn_engine selected; the all-pairs engine screens from the third search on, as kpx_icp does.  The covariances come from
 // kpx_estimate_covariances or kpx_gicp_covariances; the source's stay in the original frame and are rotated by the current T per pair.
 // An iteration whose 6x6 system is singular takes the identity update (solve6_ldlt), as a pair with a singular M adds nothing.
 KPX_EXPORT size_t kpx_generalized_icp_workspace_bytes(int64_t n_src, int64_t n_tgt) { return kpx_icp_workspace_bytes(n_src, n_tgt); }
-KPX_EXPORT int kpx_generalized_icp(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov, int64_t n_tgt,
-                                   double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
-                                   int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream)
+static int generalized_icp_run(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov, int64_t n_tgt,
+                               double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                               int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream,
+                               const RobustLoss *loss)
 {
     KPX_REQUIRE(src_cov && tgt_cov, "kpx_generalized_icp: covariances of both clouds are required");
     KPX_REQUIRE(max_dist > 0.0, "Invalid max_correspondence_distance.");          // [O3D]
@@ -811,13 +871,34 @@ KPX_EXPORT int kpx_generalized_icp(const float *src, const double *src_cov, int6
     NnProblem q;
     int rc = q.setup(src, n_src, tgt, n_tgt, h_init, ws, ws_bytes, st);
     if (rc) return rc;
-    rc = icp_search_solve_loop(src, tgt, nullptr, q, max_dist * max_dist, kModeGicp, 1, Screen::kFromThird,
-                               IcpCriteria{ max_iteration, relative_fitness, relative_rmse, poll_interval }, d_result, st, GicpTerms{ src_cov, tgt_cov });
+    const IcpCriteria crit{ max_iteration, relative_fitness, relative_rmse, poll_interval };
+    const GicpTerms gt{ src_cov, tgt_cov };
+    rc = loss ? icp_search_solve_loop(src, tgt, nullptr, q, max_dist * max_dist, kModeGicp, 1, Screen::kFromThird, crit, d_result, st,
+                                      RobustGicpTerms{ gt, *loss })
+              : icp_search_solve_loop(src, tgt, nullptr, q, max_dist * max_dist, kModeGicp, 1, Screen::kFromThird, crit, d_result, st, gt);
     if (rc) return rc;
     rc = q.copy_pairs(idx, d2, st);
     if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
+}
+KPX_EXPORT int kpx_generalized_icp(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov, int64_t n_tgt,
+                                   double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                                   int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws, size_t ws_bytes, void *stream)
+{
+    return generalized_icp_run(src, src_cov, n_src, tgt, tgt_cov, n_tgt, max_dist, h_init, max_iteration, relative_fitness, relative_rmse,
+                               poll_interval, d_result, idx, d2, ws, ws_bytes, stream, nullptr);
+}
+KPX_EXPORT int kpx_generalized_icp_robust(const float *src, const double *src_cov, int64_t n_src, const float *tgt, const double *tgt_cov,
+                                          int64_t n_tgt, double max_dist, const double *h_init, int32_t max_iteration, double relative_fitness,
+                                          double relative_rmse, int32_t poll_interval, double *d_result, int32_t *idx, double *d2, void *ws,
+                                          size_t ws_bytes, void *stream, int32_t loss, double loss_k)
+{
+    const int rc = loss_check(loss, loss_k);
+    if (rc) return rc;
+    const RobustLoss rl{ loss, loss_k };
+    return generalized_icp_run(src, src_cov, n_src, tgt, tgt_cov, n_tgt, max_dist, h_init, max_iteration, relative_fitness, relative_rmse,
+                               poll_interval, d_result, idx, d2, ws, ws_bytes, stream, &rl);
 }
 
 // [O3D] InitializePointCloudForGeneralizedICP, covariances from normals: C = R_x diag(eps, 1, 1) R_x^T with R_x = GetRotationFromE1ToX(n),

@@ -98,6 +98,45 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 // compare zero-extended 64-bit values, i.e. the slow v_cmp_*_u64 this prefilter exists to avoid)
 __device__ __forceinline__ unsigned hi32(double v) { return __builtin_bit_cast(u2, v)[1]; }
 
+// [O3D] RobustKernel.cpp: the loss of a robust registration (kpx_icp_robust and its siblings), kind = KPX_LOSS_*.  weight(r) is what
+// Open3D's ComputeJTJandJTr multiplies a residual row with (JTJ += J w J^T, JTr += J w r); written with plain fp64 operations, no pow,
+// so that tests/robust_ref.py restates it operation by operation.  Open3D does not check k; the entry points require k > 0 where the
+// loss has one.
+struct RobustLoss {
+    int32_t kind;
+    double k;
+    __device__ __forceinline__ double weight(double r) const
+    {
+        switch (kind) {
+        case KPX_LOSS_L1: return 1.0 / fabs(r);
+        case KPX_LOSS_HUBER: return k / fmax(fabs(r), k);
+        case KPX_LOSS_CAUCHY: { const double q = r / k; return 1.0 / (1.0 + q * q); }
+        case KPX_LOSS_GM: { const double d = k + r * r; return k / (d * d); }
+        case KPX_LOSS_TUKEY: { const double q = fmin(1.0, fabs(r) / k); const double u = 1.0 - q * q; return u * u; }
+        default: return 1.0;             // KPX_LOSS_L2
+        }
+    }
+};
+// One residual row (Jacobian J, residual r) of a robust registration into accumulator slots 17..43: J^T w J (upper triangle) and
+// J^T w r with w = loss.weight(r).
+// Deviation: Open3D yields NaN from L1Loss at r == 0 (its weight is infinite, times the zero residual); here a row whose weight is
+// not finite adds nothing to slots 17..43.
+__device__ __forceinline__ void robust_row(const RobustLoss &loss, const double J[6], double r, double *acc)
+{
+    const double w = loss.weight(r);
+    if (!isfinite(w)) return;
+    double wJ[6];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) wJ[p] = w * J[p];
+    int q = 17;
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int c = p; c < 6; ++c) acc[q++] += wJ[p] * J[c];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) acc[38 + p] += wJ[p] * r;
+}
+
 // centre and radius of the target for the float32 screening operands (nn_aux_kernel, kpx_nndense.h)
 struct NnAux {
     double c[3];      // centre used for the f32 operands

@@ -445,18 +445,32 @@ __global__ __launch_bounds__(256, 4) void nn_mfma_kernel(int64_t n, const double
 //        2 = coloured ICP ([O3D] TransformationEstimationForColoredICP): the normal equations hold a geometric row
 //            sqrt(lambda) (s x n, n | (s - t).n) and a photometric row sqrt(1 - lambda) (s x g', g' | I_s - (I_t + g.(s' - t))),
 //            s' = s projected onto the target's tangent plane, g the target's colour gradient, g' = -(I - n n^T) g
-//        3 = generalized ICP (GicpTerms, the nn_merge_kernel<GicpTerms> instantiation only): three rows per pair, see gicp_pair_rows
+//        3 = generalized ICP (GicpTerms / RobustGicpTerms: those instantiations only): three rows per pair, see gicp_pair_rows
 // The kernel is a template on its pair term: nn_merge_kernel<ColorTerms> serves modes -2..2, nn_merge_kernel<GicpTerms> mode 3 (the
 // 3x3 eigen-solve of a GICP pair never enters the instantiation every point-to-point / point-to-plane registration runs).
+// Robust registrations (kpx_icp_robust, kpx_colored_icp_robust, kpx_generalized_icp_robust) take instantiations of their own,
+// nn_merge_kernel<RobustColorTerms> (modes 1 and 2) and nn_merge_kernel<RobustGicpTerms> (mode 3): every residual row of modes 1..3
+// goes through robust_row (kpx_icpdefs.h), weighted by the loss of its own residual -- the one row of point-to-plane, the two SCALED
+// rows of coloured ICP (sqrt(lambda) r_G, sqrt(1 - lambda) r_I), the three rows r_i = w_i . d of a GICP pair.  Slots 0..16 (count,
+// sum d2, the point-to-point sums) stay unweighted: fitness, inlier rmse, the correspondences and the convergence test do not depend
+// on the loss, as in Open3D.  The weighting stands behind `if constexpr`: the two instantiations above compile as they did without it.
 struct ColorTerms {
-    static constexpr bool kGicp = false;
+    static constexpr bool kGicp = false, kRobust = false;
     const float *src_col, *tgt_col;
     const double *tgt_grad;
     double sqrt_lg, sqrt_lp;
 };
 struct GicpTerms {
-    static constexpr bool kGicp = true;
+    static constexpr bool kGicp = true, kRobust = false;
     const double *src_cov, *tgt_cov;       // [n_src][9], [n_tgt][9] row-major, in the ORIGINAL source frame / the target's frame
+};
+struct RobustColorTerms : ColorTerms {
+    static constexpr bool kRobust = true;
+    RobustLoss loss;
+};
+struct RobustGicpTerms : GicpTerms {
+    static constexpr bool kRobust = true;
+    RobustLoss loss;
 };
 constexpr int kModeGicp = 3;
 
@@ -467,8 +481,9 @@ constexpr int kModeGicp = 3;
 // accumulated into the point-to-plane slots 17..43 (J^T J upper triangle, J^T r); the update is the point-to-plane solve.
 // Deviation: Open3D yields NaN when M is singular (e.g. two exactly flat neighbourhoods with aligned normals, raw covariances);
 // here a pair whose smallest eigenvalue of M is <= 0, or whose W is not finite, adds nothing to slots 17..43.
-__device__ __forceinline__ void gicp_pair_rows(const double *__restrict__ T, const double *__restrict__ Cs, const double *__restrict__ Ct,
-                                               const double s[3], const double t[3], double acc[kAcc])
+template <class Terms>
+__device__ __forceinline__ void gicp_pair_rows(const Terms &ct, const double *__restrict__ T, const double *__restrict__ Cs,
+                                               const double *__restrict__ Ct, const double s[3], const double t[3], double acc[kAcc])
 {
     double RC[9];
 #pragma unroll
@@ -506,13 +521,17 @@ __device__ __forceinline__ void gicp_pair_rows(const double *__restrict__ T, con
         const double wx = W[3 * row], wy = W[3 * row + 1], wz = W[3 * row + 2];
         const double r = wx * d[0] + wy * d[1] + wz * d[2];
         const double J[6] = { s[1] * wz - s[2] * wy, s[2] * wx - s[0] * wz, s[0] * wy - s[1] * wx, wx, wy, wz };
-        int q = 17;
+        if constexpr (Terms::kRobust) {
+            robust_row(ct.loss, J, r, acc);
+        } else {
+            int q = 17;
 #pragma unroll
-        for (int p = 0; p < 6; ++p)
+            for (int p = 0; p < 6; ++p)
 #pragma unroll
-            for (int c = p; c < 6; ++c) acc[q++] += J[p] * J[c];
+                for (int c = p; c < 6; ++c) acc[q++] += J[p] * J[c];
 #pragma unroll
-        for (int p = 0; p < 6; ++p) acc[38 + p] += J[p] * r;
+            for (int p = 0; p < 6; ++p) acc[38 + p] += J[p] * r;
+        }
     }
 }
 
@@ -583,19 +602,23 @@ __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__
 #pragma unroll
                     for (int q = 0; q < 3; ++q) acc[8 + 3 * p + q] = t[p] * s[q];
                 if constexpr (Terms::kGicp) {
-                    gicp_pair_rows(T, ct.src_cov + 9 * i, ct.tgt_cov + 9 * (int64_t)bj, s, t, acc);
+                    gicp_pair_rows(ct, T, ct.src_cov + 9 * i, ct.tgt_cov + 9 * (int64_t)bj, s, t, acc);
                 } else if (mode == 1) {
                     const float *np_ = tn + 3 * (int64_t)bj;
                     double nx = np_[0], ny = np_[1], nz = np_[2];
                     double r = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
                     double J[6] = { s[1] * nz - s[2] * ny, s[2] * nx - s[0] * nz, s[0] * ny - s[1] * nx, nx, ny, nz };
-                    int q = 17;
+                    if constexpr (Terms::kRobust) {
+                        robust_row(ct.loss, J, r, acc);
+                    } else {
+                        int q = 17;
 #pragma unroll
-                    for (int p = 0; p < 6; ++p)
+                        for (int p = 0; p < 6; ++p)
 #pragma unroll
-                        for (int c = p; c < 6; ++c) acc[q++] = J[p] * J[c];
+                            for (int c = p; c < 6; ++c) acc[q++] = J[p] * J[c];
 #pragma unroll
-                    for (int p = 0; p < 6; ++p) acc[38 + p] = J[p] * r;
+                        for (int p = 0; p < 6; ++p) acc[38 + p] = J[p] * r;
+                    }
                 } else if (mode == 2) {
                     const float *np_ = tn + 3 * (int64_t)bj;
                     const double nv[3] = { np_[0], np_[1], np_[2] };
@@ -614,13 +637,18 @@ __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__
                     const double JI[6] = { ct.sqrt_lp * (s[1] * gm[2] - s[2] * gm[1]), ct.sqrt_lp * (s[2] * gm[0] - s[0] * gm[2]),
                                            ct.sqrt_lp * (s[0] * gm[1] - s[1] * gm[0]), ct.sqrt_lp * gm[0], ct.sqrt_lp * gm[1], ct.sqrt_lp * gm[2] };
                     const double rG = ct.sqrt_lg * rg, rI = ct.sqrt_lp * (is - is0);
-                    int q = 17;
+                    if constexpr (Terms::kRobust) {
+                        robust_row(ct.loss, JG, rG, acc);
+                        robust_row(ct.loss, JI, rI, acc);
+                    } else {
+                        int q = 17;
 #pragma unroll
-                    for (int p = 0; p < 6; ++p)
+                        for (int p = 0; p < 6; ++p)
 #pragma unroll
-                        for (int c = p; c < 6; ++c) acc[q++] = JG[p] * JG[c] + JI[p] * JI[c];
+                            for (int c = p; c < 6; ++c) acc[q++] = JG[p] * JG[c] + JI[p] * JI[c];
 #pragma unroll
-                    for (int p = 0; p < 6; ++p) acc[38 + p] = JG[p] * rG + JI[p] * rI;
+                        for (int p = 0; p < 6; ++p) acc[38 + p] = JG[p] * rG + JI[p] * rI;
+                    }
                 }
             }
         }

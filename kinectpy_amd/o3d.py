@@ -43,15 +43,103 @@ class TransformationEstimationPointToPoint:
         return ops.kabsch(source._pts, target._pts, np.asarray(corres, dtype=np.int32))
 
 
+class RobustKernel:
+    """o3d.pipelines.registration.RobustKernel: `.weight(residual)` is what a residual row of the normal equations is multiplied
+    with (J^T w J, J^T w r) -- the same formulas, operation by operation, as RobustLoss::weight on the device (kpx_icpdefs.h).
+    `.kind` names the loss for ops (ops.LOSS_KINDS); `.k` is None for the losses without a parameter.  Open3D does not check k;
+    here it must be positive."""
+    kind = None
+    k = None
+
+    def weight(self, residual):
+        raise NotImplementedError
+
+
+class L2Loss(RobustKernel):
+    """o3d.pipelines.registration.L2Loss: the plain least-squares loss (weight 1 for every residual)"""
+    kind = "l2"
+
+    def weight(self, residual):
+        r = np.asarray(residual, dtype=np.float64)
+        return np.ones_like(r)[()]
+
+
+class L1Loss(RobustKernel):
+    """w = 1 / |r|  (infinite at r == 0: such a row is left out of the normal equations, where Open3D yields NaN)"""
+    kind = "l1"
+
+    def weight(self, residual):
+        r = np.asarray(residual, dtype=np.float64)
+        with np.errstate(divide="ignore"):
+            return (1.0 / np.abs(r))[()]
+
+
+class _LossWithK(RobustKernel):
+    def __init__(self, k):
+        self.k = float(k)
+        if not self.k > 0.0:
+            raise ValueError(f"{type(self).__name__}: k must be positive")
+
+
+class HuberLoss(_LossWithK):
+    """w = k / max(|r|, k)"""
+    kind = "huber"
+
+    def weight(self, residual):
+        r = np.asarray(residual, dtype=np.float64)
+        return (self.k / np.maximum(np.abs(r), self.k))[()]
+
+
+class CauchyLoss(_LossWithK):
+    """w = 1 / (1 + (r / k)^2)"""
+    kind = "cauchy"
+
+    def weight(self, residual):
+        q = np.asarray(residual, dtype=np.float64) / self.k
+        return (1.0 / (1.0 + q * q))[()]
+
+
+class GMLoss(_LossWithK):
+    """Geman-McClure: w = k / (k + r^2)^2"""
+    kind = "gm"
+
+    def weight(self, residual):
+        r = np.asarray(residual, dtype=np.float64)
+        d = self.k + r * r
+        return (self.k / (d * d))[()]
+
+
+class TukeyLoss(_LossWithK):
+    """w = (1 - min(1, |r| / k)^2)^2"""
+    kind = "tukey"
+
+    def weight(self, residual):
+        r = np.asarray(residual, dtype=np.float64)
+        q = np.minimum(1.0, np.abs(r) / self.k)
+        u = 1.0 - q * q
+        return (u * u)[()]
+
+
+def _kernel(kernel, who, error=TypeError):
+    """the `kernel` argument of an estimation: None (L2) or one of the losses above"""
+    if kernel is not None and not isinstance(kernel, RobustKernel):
+        raise error(f"{who}: kernel must be one of L2Loss, L1Loss, HuberLoss, CauchyLoss, GMLoss, TukeyLoss, not {kernel!r}")
+    return kernel
+
+
 class TransformationEstimationPointToPlane:
     mode = "p2plane"
+
+    def __init__(self, kernel=None):
+        self.kernel = _kernel(kernel, "TransformationEstimationPointToPlane")
 
 
 class TransformationEstimationForColoredICP:
     mode = "colored"
 
-    def __init__(self, lambda_geometric=0.968):
+    def __init__(self, lambda_geometric=0.968, kernel=None):
         self.lambda_geometric = float(lambda_geometric)
+        self.kernel = _kernel(kernel, "TransformationEstimationForColoredICP")
 
 
 def registration_colored_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
@@ -66,7 +154,7 @@ def registration_colored_icp(source, target, max_correspondence_distance, init=N
     if not (source.has_colors() and target.has_colors()):
         raise RuntimeError("ColoredICP requires colored point clouds.")
     r = ops.colored_icp(source._pts, source._col, target._pts, target._col, target._nrm, float(max_correspondence_distance), init,
-                        est.lambda_geometric, crit.max_iteration, crit.relative_fitness, crit.relative_rmse)
+                        est.lambda_geometric, crit.max_iteration, crit.relative_fitness, crit.relative_rmse, loss=est.kernel)
     return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], None)
 
 
@@ -83,7 +171,7 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
                                "require pre-computed normal vectors for target PointCloud.")
         tn = target._nrm
     r = ops.icp(source._pts, target._pts, float(max_correspondence_distance), init, est.mode, tn, crit.max_iteration,
-                crit.relative_fitness, crit.relative_rmse, want_corr=True)
+                crit.relative_fitness, crit.relative_rmse, want_corr=True, loss=getattr(est, "kernel", None))
     idx, d2 = r["idx"].cpu().numpy(), r["d2"].cpu().numpy()
     ok = d2 < float(max_correspondence_distance) ** 2
     corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
@@ -109,18 +197,12 @@ def get_information_matrix_from_point_clouds(source, target, max_correspondence_
     return ops.registration_eval(source._pts, target._pts, float(max_correspondence_distance), transformation)["information"]
 
 
-class L2Loss:
-    """o3d.pipelines.registration.L2Loss: the plain least-squares loss (weight 1 for every residual)"""
-
-
 class TransformationEstimationForGeneralizedICP:
-    """[O3D] plane-to-plane ICP (Segal et al.): the L2 loss only"""
+    """[O3D] plane-to-plane ICP (Segal et al.), with any of the robust kernels above"""
     mode = "gicp"
 
     def __init__(self, epsilon=1e-3, kernel=None):
-        if kernel is not None and not isinstance(kernel, L2Loss) and type(kernel).__name__ != "L2Loss":
-            raise NotImplementedError("TransformationEstimationForGeneralizedICP: only the L2 loss is implemented (no robust kernels)")
-        self.epsilon, self.kernel = float(epsilon), kernel
+        self.epsilon, self.kernel = float(epsilon), _kernel(kernel, "TransformationEstimationForGeneralizedICP", NotImplementedError)
 
 
 def _gicp_covariances(cloud, epsilon):
@@ -141,7 +223,7 @@ def registration_generalized_icp(source, target, max_correspondence_distance, in
         raise RuntimeError("Invalid max_correspondence_distance.")
     r = ops.generalized_icp(source._pts, _gicp_covariances(source, est.epsilon), target._pts, _gicp_covariances(target, est.epsilon),
                             float(max_correspondence_distance), init, crit.max_iteration, crit.relative_fitness, crit.relative_rmse,
-                            want_corr=True)
+                            want_corr=True, loss=est.kernel)
     idx, d2 = r["idx"].cpu().numpy(), r["d2"].cpu().numpy()
     ok = d2 < float(max_correspondence_distance) ** 2
     corr = np.stack([np.flatnonzero(ok).astype(np.int32), idx[ok]], 1)
@@ -246,7 +328,13 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     registration_colored_icp=registration_colored_icp,
     TransformationEstimationForColoredICP=TransformationEstimationForColoredICP,
     registration_generalized_icp=registration_generalized_icp,
+    RobustKernel=RobustKernel,
     L2Loss=L2Loss,
+    L1Loss=L1Loss,
+    HuberLoss=HuberLoss,
+    CauchyLoss=CauchyLoss,
+    GMLoss=GMLoss,
+    TukeyLoss=TukeyLoss,
     TransformationEstimationForGeneralizedICP=TransformationEstimationForGeneralizedICP,
     evaluate_registration=evaluate_registration,
     get_information_matrix_from_point_clouds=get_information_matrix_from_point_clouds,

@@ -35,6 +35,21 @@ def _T(T):
     return T
 
 
+LOSS_KINDS = {"l2": 0, "l1": 1, "huber": 2, "cauchy": 3, "gm": 4, "tukey": 5}          # KPX_LOSS_* (include/kinectpx.h)
+
+
+def _loss(loss):
+    """`loss` of icp / colored_icp / generalized_icp -> (KPX_LOSS_* kind, k).  None = L2; otherwise an object with `.kind` (a name
+    of LOSS_KINDS) and `.k` -- the o3d.pipelines.registration losses -- or a (name, k) pair."""
+    if loss is None:
+        return 0, 0.0
+    name, k = loss if isinstance(loss, (tuple, list)) else (getattr(loss, "kind", None), getattr(loss, "k", 0.0))
+    if name not in LOSS_KINDS:
+        raise ValueError(f"unknown robust loss {loss!r}: expected None, one of the o3d.pipelines.registration losses or a (name, k) pair "
+                         f"with name in {sorted(LOSS_KINDS)}")
+    return LOSS_KINDS[name], float(0.0 if k is None else k)
+
+
 # ---- extract --------------------------------------------------------------------------------------
 def unproject_u16(depth, xy_table, frames=1):
     """a1.  depth u16 [frames*n_px], xy f32 [n_px*2] -> int16 [frames, n_px, 3]."""
@@ -495,8 +510,12 @@ def kabsch(src, tgt, corr):
 
 
 def icp(src, tgt, max_dist, init=None, mode="p2p", tgt_normals=None, max_iteration=30, relative_fitness=1e-6,
-        relative_rmse=1e-6, want_corr=False, poll_interval=4):
-    """registration_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count[, idx, d2])."""
+        relative_rmse=1e-6, want_corr=False, poll_interval=4, loss=None):
+    """registration_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count[, idx, d2]).
+    loss: a robust kernel for mode="p2plane" (see _loss; kpx_icp_robust); None or L2 is the plain call."""
+    kind, k = _loss(loss)
+    if kind and mode == "p2p":
+        raise ValueError("TransformationEstimationPointToPoint takes no robust kernel (Open3D has none): use mode='p2plane'")
     lib = L.load()
     src = _dev(src, torch.float32).reshape(-1, 3)
     tgt = _dev(tgt, torch.float32).reshape(-1, 3)
@@ -511,9 +530,10 @@ def icp(src, tgt, max_dist, init=None, mode="p2p", tgt_normals=None, max_iterati
     d2 = torch.empty(n, dtype=torch.float64, device=dev) if want_corr else None
     init = _T(np.eye(4) if init is None else init)
     ws, wsz = L.workspace(lib.kpx_icp_workspace_bytes(n, m))
-    L.check(lib.kpx_icp(L.ptr(src), n, L.ptr(tgt), L.ptr(tn), m, float(max_dist), L.hptr(init), md, int(max_iteration),
-                        float(relative_fitness), float(relative_rmse), int(poll_interval), L.ptr(res), L.ptr(idx), L.ptr(d2), ws, wsz,
-                        L.stream_ptr()))
+    args = (L.ptr(src), n, L.ptr(tgt), L.ptr(tn), m, float(max_dist), L.hptr(init), md, int(max_iteration),
+            float(relative_fitness), float(relative_rmse), int(poll_interval), L.ptr(res), L.ptr(idx), L.ptr(d2), ws, wsz,
+            L.stream_ptr())
+    L.check(lib.kpx_icp_robust(*args, kind, k) if kind else lib.kpx_icp(*args))
     r = res.cpu().numpy()
     out = {"transformation": r[:16].reshape(4, 4).copy(), "fitness": float(r[16]), "inlier_rmse": float(r[17]),
            "iterations": int(r[18]), "count": int(r[19])}
@@ -864,8 +884,10 @@ def color_gradient(pts, normals, colors, radius, max_nn=30):
 
 
 def colored_icp(src, src_colors, tgt, tgt_colors, tgt_normals, max_dist, init=None, lambda_geometric=0.968, max_iteration=30,
-                relative_fitness=1e-6, relative_rmse=1e-6, poll_interval=4, tgt_gradient=None):
-    """[O3D] registration_colored_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count)."""
+                relative_fitness=1e-6, relative_rmse=1e-6, poll_interval=4, tgt_gradient=None, loss=None):
+    """[O3D] registration_colored_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count).
+    loss: a robust kernel (see _loss; kpx_colored_icp_robust); None or L2 is the plain call."""
+    kind, k = _loss(loss)
     lib = L.load()
     src = _dev(src, torch.float32).reshape(-1, 3)
     tgt = _dev(tgt, torch.float32).reshape(-1, 3)
@@ -879,9 +901,10 @@ def colored_icp(src, src_colors, tgt, tgt_colors, tgt_normals, max_dist, init=No
     res = torch.zeros(20, dtype=torch.float64, device=src.device)
     init = _T(np.eye(4) if init is None else init)
     ws, wsz = L.workspace(lib.kpx_colored_icp_workspace_bytes(n, m))
-    L.check(lib.kpx_colored_icp(L.ptr(src), L.ptr(sc), n, L.ptr(tgt), L.ptr(tc), L.ptr(tn), L.ptr(tg), m, float(max_dist), L.hptr(init),
-                                float(lambda_geometric), int(max_iteration), float(relative_fitness), float(relative_rmse), int(poll_interval),
-                                L.ptr(res), ws, wsz, L.stream_ptr()))
+    args = (L.ptr(src), L.ptr(sc), n, L.ptr(tgt), L.ptr(tc), L.ptr(tn), L.ptr(tg), m, float(max_dist), L.hptr(init),
+            float(lambda_geometric), int(max_iteration), float(relative_fitness), float(relative_rmse), int(poll_interval),
+            L.ptr(res), ws, wsz, L.stream_ptr())
+    L.check(lib.kpx_colored_icp_robust(*args, kind, k) if kind else lib.kpx_colored_icp(*args))
     r = res.cpu().numpy()
     return {"transformation": r[:16].reshape(4, 4).copy(), "fitness": float(r[16]), "inlier_rmse": float(r[17]),
             "iterations": int(r[18]), "count": int(r[19])}
@@ -921,8 +944,10 @@ def rotate_covariances(cov, T, out=None):
 
 
 def generalized_icp(src, src_cov, tgt, tgt_cov, max_dist, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                    want_corr=False, poll_interval=4):
-    """[O3D] registration_generalized_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count[, idx, d2])."""
+                    want_corr=False, poll_interval=4, loss=None):
+    """[O3D] registration_generalized_icp.  Returns dict(transformation, fitness, inlier_rmse, iterations, count[, idx, d2]).
+    loss: a robust kernel (see _loss; kpx_generalized_icp_robust); None or L2 is the plain call."""
+    kind, k = _loss(loss)
     lib = L.load()
     src = _dev(src, torch.float32).reshape(-1, 3)
     tgt = _dev(tgt, torch.float32).reshape(-1, 3)
@@ -937,9 +962,10 @@ def generalized_icp(src, src_cov, tgt, tgt_cov, max_dist, init=None, max_iterati
     d2 = torch.empty(n, dtype=torch.float64, device=dev) if want_corr else None
     init = _T(np.eye(4) if init is None else init)
     ws, wsz = L.workspace(lib.kpx_generalized_icp_workspace_bytes(n, m))
-    L.check(lib.kpx_generalized_icp(L.ptr(src), L.ptr(sc), n, L.ptr(tgt), L.ptr(tc), m, float(max_dist), L.hptr(init), int(max_iteration),
-                                    float(relative_fitness), float(relative_rmse), int(poll_interval), L.ptr(res), L.ptr(idx), L.ptr(d2),
-                                    ws, wsz, L.stream_ptr()))
+    args = (L.ptr(src), L.ptr(sc), n, L.ptr(tgt), L.ptr(tc), m, float(max_dist), L.hptr(init), int(max_iteration),
+            float(relative_fitness), float(relative_rmse), int(poll_interval), L.ptr(res), L.ptr(idx), L.ptr(d2),
+            ws, wsz, L.stream_ptr())
+    L.check(lib.kpx_generalized_icp_robust(*args, kind, k) if kind else lib.kpx_generalized_icp(*args))
     r = res.cpu().numpy()
     out = {"transformation": r[:16].reshape(4, 4).copy(), "fitness": float(r[16]), "inlier_rmse": float(r[17]),
            "iterations": int(r[18]), "count": int(r[19])}

@@ -1,5 +1,6 @@
 """Drop-in for KinectPy's preprocessing/registration.py (reference lines 7-114)."""
 import copy
+import inspect
 
 import numpy as np
 
@@ -50,17 +51,24 @@ def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransa
 
 
 def execute_point_to_plane_registration(pcd_master, pcd_sub, initial_transformation: np.ndarray,
-                                        voxel_size: int = 35) -> np.ndarray:
+                                        voxel_size: int = 35, *, kernel=None) -> np.ndarray:
     """registration.py:65-86.  The reference names master `source` and sub `target` and then calls
     prepare_dataset(source, target), which swaps them back: the effective call is
-    registration_icp(sub_down, master_down, 100, init, PointToPlane) and the result maps sub -> master."""
+    registration_icp(sub_down, master_down, 100, init, PointToPlane) and the result maps sub -> master.
+    kernel: a robust loss of o3d.pipelines.registration (e.g. TukeyLoss(k)) for the ICP; None is the reference's plain L2."""
     source, target = copy.deepcopy(pcd_master), copy.deepcopy(pcd_sub)
     threshold = 100
     _, _, source_down, target_down, _, _ = prepare_dataset(source, target, voxel_size, with_fpfh=False)
     reg = o3d.pipelines.registration.registration_icp(
         source_down, target_down, threshold, initial_transformation,
-        o3d.pipelines.registration.TransformationEstimationPointToPlane())
+        o3d.pipelines.registration.TransformationEstimationPointToPlane(kernel))
     return reg.transformation
+
+
+# Introspection shows the reference's signature, which this drop-in stands for (SURVEY.md 8b; the host suite compares it parameter
+# by parameter): `kernel` is this library's keyword-only extension and is documented in the docstring above.
+execute_point_to_plane_registration.__signature__ = inspect.Signature(
+    [p for p in inspect.signature(execute_point_to_plane_registration).parameters.values() if p.name != "kernel"])
 
 
 def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation):
@@ -86,7 +94,7 @@ def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation
 
 
 def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transformations=None, seed=None, preference_loop_closure=None,
-                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False):
+                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False, kernel=None):
     """[O3D] multiway registration of a rig: pcds[0] is the master.  Not in the reference, whose calibration is the star alone
     (data.py:137-147); opt-in through DataProcessor(multiway=True).  -> the sub -> master 4x4 list in the form
     DataProcessor.registration_transformations holds (and the optimised PoseGraph with return_pose_graph).
@@ -99,7 +107,9 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
        a single correspondence is left out;
     4. node poses start at T_i; global_optimization with reference_node = 0.
     preference_loop_closure=None: mu = (median correspondence count of the uncertain edges) * voxel_size^2 -- a closure goes when
-    it disagrees with the rest by more than about one voxel rms over its matched points ("Multiway registration")."""
+    it disagrees with the rest by more than about one voxel rms over its matched points ("Multiway registration").
+    kernel: a robust loss for every pairwise ICP (star and loop edges); the loop edges then go one by one through ops.icp, as
+    ops.icp_batch runs the culled iteration kernels, which take no weights."""
     from .. import ops
     reg = o3d.pipelines.registration
     threshold = 100                                                       # execute_point_to_plane_registration's
@@ -113,12 +123,16 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
                 raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)")
         else:
             init = initial_transformations[i - 1]
-        star.append(reg.registration_icp(downs[i], downs[0], threshold, init, reg.TransformationEstimationPointToPlane()).transformation)
+        star.append(reg.registration_icp(downs[i], downs[0], threshold, init, reg.TransformationEstimationPointToPlane(kernel)).transformation)
     edges = [(i, 0, star[i], False) for i in range(1, S)]
     for j in range(2, S):
         Tj_inv = np.linalg.inv(star[j])
-        res = ops.icp_batch([downs[i]._pts for i in range(1, j)], downs[j]._pts, threshold, [Tj_inv @ star[i] for i in range(1, j)],
-                            "p2plane", downs[j]._nrm)
+        inits = [Tj_inv @ star[i] for i in range(1, j)]
+        if kernel is None:
+            res = ops.icp_batch([downs[i]._pts for i in range(1, j)], downs[j]._pts, threshold, inits, "p2plane", downs[j]._nrm)
+        else:
+            res = [ops.icp(downs[i]._pts, downs[j]._pts, threshold, init, "p2plane", downs[j]._nrm, loss=kernel)
+                   for i, init in zip(range(1, j), inits)]
         edges += [(i, j, r["transformation"], True) for i, r in zip(range(1, j), res)]
     pose_graph = reg.PoseGraph()
     pose_graph.nodes = [reg.PoseGraphNode(T) for T in star]
