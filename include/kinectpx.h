@@ -265,6 +265,34 @@ size_t kpx_covariances_workspace_bytes(int64_t n, int32_t max_nn);
 int kpx_estimate_covariances(const float *pts, int64_t n, double radius, int32_t max_nn, double *cov,
                              void *ws, size_t ws_bytes, void *stream);
 
+/* Neighbour search between a cloud and ARBITRARY query points ([O3D] KDTreeFlann SearchKNN / SearchRadius / SearchHybrid).
+ * The index is a caller-owned device buffer of kpx_search_index_bytes(n) bytes that kpx_search_index_build fills from a float32 (n,3)
+ * cloud: grid parameters, cell starts, cell-sorted coordinates, original indices.  It does not point back into pts and the library keeps
+ * no state: it may be queried any number of times, copied, and outlives the cloud.  n == 0 and degenerate bounding boxes are fine.
+ * Queries are float32 (m,3).  d2 = AC3 in fp64 (d = q - p); every result row ascends in (d2, index) -- on equal d2 the LOWEST cloud index
+ * comes first (Open3D leaves the order of ties open).  A query with a non-finite coordinate finds nothing; results do not depend on the
+ * grid, the launch shape or the order of the queries.
+ *   kpx_search_knn: radius <= 0: the min(k, n) nearest; radius > 0: hybrid, the first min(k, count) of the radius result.  idx i32 [m][k],
+ *     d2 f64 [m][k], count i32 [m]; slots past count hold -1 / +inf.  1 <= k <= 4096.
+ *   kpx_search_radius_count: offsets i64 [m+1] = exclusive scan of the per-query number of points with d2 < radius*radius (strict, r2 in
+ *     fp64), offsets[m] = total.  The caller reads the total, allocates idx i32 [total] and d2 f64 [total], and calls
+ *   kpx_search_radius_fill with the same index, queries, radius and offsets: segment q = [offsets[q], offsets[q+1]) sorted.  A total above
+ *     2^31 - 1 is KPX_ERR_RANGE.  Both reject !(radius > 0).
+ * Every query call reads the index header back (one small copy and a synchronisation of `stream`) and rejects a buffer that is not
+ * an index or whose index_bytes is smaller than kpx_search_index_bytes of the n it records; k, radius, a null index and an
+ * index_bytes below kpx_search_index_bytes(0) are rejected before the device is touched.
+ * Workspace: kpx_search_workspace_bytes(m, k) for the three query calls (m queries); kpx_search_workspace_bytes(n, 0) for
+ * kpx_search_index_build of an n-point cloud. */
+size_t kpx_search_index_bytes(int64_t n);
+int kpx_search_index_build(const float *pts, int64_t n, void *index, size_t index_bytes, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_search_workspace_bytes(int64_t m, int32_t k);
+int kpx_search_knn(const void *index, size_t index_bytes, const float *queries, int64_t m, int32_t k, double radius, int32_t *idx /* [m][k] */,
+                   double *d2 /* [m][k] */, int32_t *count /* [m] */, void *ws, size_t ws_bytes, void *stream);
+int kpx_search_radius_count(const void *index, size_t index_bytes, const float *queries, int64_t m, double radius, int64_t *offsets /* [m+1] */,
+                            void *ws, size_t ws_bytes, void *stream);
+int kpx_search_radius_fill(const void *index, size_t index_bytes, const float *queries, int64_t m, double radius, const int64_t *offsets,
+                           int64_t total, int32_t *idx /* [total] */, double *d2 /* [total] */, void *ws, size_t ws_bytes, void *stream);
+
 /* a21: PointCloud.segment_plane(distance_threshold, ransac_n, num_iterations) (floor_removal.py:70).
  * Seeded (Philox4x32-10) so results are reproducible; the reference's is unseeded.
  * d_plane f64 [4], inlier_idx ascending, d_count = #inliers. */

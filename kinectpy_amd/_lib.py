@@ -59,6 +59,12 @@ SIGNATURES = {
     "kpx_farthest_point_sample_batch": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_normals_workspace_bytes": (_sz, [_i64, _i32]),
     "kpx_estimate_normals": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _sz, _vp]),
+    "kpx_search_index_bytes": (_sz, [_i64]),
+    "kpx_search_index_build": (C.c_int, [_vp, _i64, _vp, _sz, _vp, _sz, _vp]),
+    "kpx_search_workspace_bytes": (_sz, [_i64, _i32]),
+    "kpx_search_knn": (C.c_int, [_vp, _sz, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_search_radius_count": (C.c_int, [_vp, _sz, _vp, _i64, _f64, _vp, _vp, _sz, _vp]),
+    "kpx_search_radius_fill": (C.c_int, [_vp, _sz, _vp, _i64, _f64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "kpx_segment_plane_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "kpx_segment_plane": (C.c_int, [_vp, _i64, _f64, _i32, _i32, _f64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_nn_workspace_bytes": (_sz, [_i64, _i64]),

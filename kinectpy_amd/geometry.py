@@ -90,6 +90,11 @@ class KDTreeSearchParamKNN:
         self.radius, self.max_nn = 1e150, int(knn)
 
 
+class KDTreeSearchParamRadius:
+    def __init__(self, radius):
+        self.radius = float(radius)
+
+
 def _idx_array(indices):
     """accepts lists, (K,), (K,1) arrays (np.argwhere output, floor_removal.py:50,65-69) and tensors"""
     if isinstance(indices, torch.Tensor):
@@ -336,6 +341,24 @@ class PointCloud:
             self._cov = ops.estimate_covariances(self._pts, sp.radius, sp.max_nn)
         return self
 
+    def compute_point_cloud_distance(self, target):
+        """[O3D] ComputePointCloudDistance: float64 (N) distance of every point to its nearest point of `target`"""
+        if not self.has_points():
+            return np.zeros(0, dtype=np.float64)
+        if not target.has_points():
+            raise RuntimeError("compute_point_cloud_distance: the target cloud has no points")
+        _, d2, _ = ops.search_knn(ops.search_index(target._pts), self._pts, 1)
+        return np.sqrt(d2[:, 0].cpu().numpy())
+
+    def compute_nearest_neighbor_distance(self):
+        """[O3D] ComputeNearestNeighborDistance: float64 (N) distance of every point to its nearest OTHER point -- the second
+        entry of a 2-nearest search on the cloud itself (0 for a duplicated point); 0 where fewer than two results exist"""
+        if not self.has_points():
+            return np.zeros(0, dtype=np.float64)
+        _, d2, cnt = ops.search_knn(ops.search_index(self._pts), self._pts, 2)
+        d2, cnt = d2.cpu().numpy(), cnt.cpu().numpy()
+        return np.where(cnt >= 2, np.sqrt(np.where(cnt >= 2, d2[:, 1], 0.0)), 0.0)
+
     def get_oriented_bounding_box(self, robust=False):
         """utils/normalization.py:39, 74, 105; utils/processing.py:341"""
         obb, _ = ops.obb_batch(self._pts)
@@ -360,3 +383,76 @@ class PointCloud:
 
     def clone(self):
         return copy.deepcopy(self)
+
+
+class KDTreeFlann:
+    """o3d.geometry.KDTreeFlann over a PointCloud or an (N,3) array: the search index (ops.search_index) is built once per
+    set_geometry and never per query.  The three *_vector_3d searches take ONE query point and return Open3D's
+    (count, indices, squared distances); search_knn / search_radius / search_hybrid take (M,3) queries -- the library's
+    extension -- and return device tensors (ops.search_*).  Rows ascend in (d2, index): on equal distances the lowest index comes
+    first (Open3D leaves the order of ties open).  Coordinates are float32 storage: float64 input is rounded on entry."""
+
+    def __init__(self, geometry=None):
+        self._index = None
+        if geometry is not None:
+            self.set_geometry(geometry)
+
+    def set_geometry(self, geometry):
+        if isinstance(geometry, PointCloud):
+            pts = geometry._pts
+        elif isinstance(geometry, Vector3dVector):
+            pts = geometry.t
+        elif isinstance(geometry, torch.Tensor) or (isinstance(geometry, (np.ndarray, list, tuple)) and len(geometry) >= 0):
+            pts = geometry if isinstance(geometry, torch.Tensor) else np.asarray(geometry)
+            if pts.dtype == object or pts.ndim != 2 or pts.shape[1] != 3:
+                raise TypeError("KDTreeFlann: expected a PointCloud or an (N, 3) array of points")
+        else:
+            raise TypeError(f"KDTreeFlann: expected a PointCloud or an (N, 3) array of points, not {type(geometry).__name__}")
+        self._index = ops.search_index(pts)
+        return True
+
+    def _need_index(self):
+        if self._index is None:
+            raise RuntimeError("KDTreeFlann: no geometry set")
+        return self._index
+
+    # ---- batched (the library's extension) ---------------------------------------------------------
+    def search_knn(self, queries, knn):
+        return ops.search_knn(self._need_index(), queries, knn)
+
+    def search_radius(self, queries, radius):
+        return ops.search_radius(self._need_index(), queries, radius)
+
+    def search_hybrid(self, queries, radius, max_nn):
+        return ops.search_hybrid(self._need_index(), queries, radius, max_nn)
+
+    # ---- Open3D's single-query calls ----------------------------------------------------------------
+    @staticmethod
+    def _one(query):
+        q = np.asarray(query, dtype=np.float64).reshape(-1)
+        if q.shape[0] != 3:
+            raise RuntimeError("KDTreeFlann: a query is one 3-D point")
+        return q.reshape(1, 3)
+
+    def search_knn_vector_3d(self, query, knn):
+        idx, d2, cnt = self.search_knn(self._one(query), knn)
+        c = int(cnt[0])
+        return c, idx[0, :c].cpu().numpy(), d2[0, :c].cpu().numpy()
+
+    def search_hybrid_vector_3d(self, query, radius, max_nn):
+        idx, d2, cnt = self.search_hybrid(self._one(query), radius, max_nn)
+        c = int(cnt[0])
+        return c, idx[0, :c].cpu().numpy(), d2[0, :c].cpu().numpy()
+
+    def search_radius_vector_3d(self, query, radius):
+        off, idx, d2 = self.search_radius(self._one(query), radius)
+        return int(off[1]), idx.cpu().numpy(), d2.cpu().numpy()
+
+    def search_vector_3d(self, query, search_param):
+        if isinstance(search_param, KDTreeSearchParamKNN):
+            return self.search_knn_vector_3d(query, search_param.max_nn)
+        if isinstance(search_param, KDTreeSearchParamRadius):
+            return self.search_radius_vector_3d(query, search_param.radius)
+        if isinstance(search_param, KDTreeSearchParamHybrid):
+            return self.search_hybrid_vector_3d(query, search_param.radius, search_param.max_nn)
+        raise TypeError("KDTreeFlann.search_vector_3d: expected a KDTreeSearchParamKNN, KDTreeSearchParamRadius or KDTreeSearchParamHybrid")

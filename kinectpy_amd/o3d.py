@@ -8,8 +8,8 @@ import types
 import numpy as np
 
 from . import ops
-from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, Matrix3dVector, OrientedBoundingBox, PointCloud, Vector2iVector,
-                       Vector3dVector)
+from .geometry import (KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector, OrientedBoundingBox,
+                       PointCloud, Vector2iVector, Vector3dVector)
 from . import pcd_io
 from . import posegraph
 
@@ -310,7 +310,7 @@ def _off_path(name):
 
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
-                                 KDTreeSearchParamKNN=KDTreeSearchParamKNN)
+                                 KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
 io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
 pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(

@@ -441,6 +441,79 @@ def estimate_normals(pts, radius, max_nn):
     return out
 
 
+# ---- neighbour search between a cloud and arbitrary queries ---------------------------
+SEARCH_MAX_K = 4096
+
+
+class SearchIndex:
+    """Opaque holder of a search index: the device buffer kpx_search_index_build filled and the number of points it holds.  The
+    buffer is self-contained (it does not refer to the cloud it was built from)."""
+
+    def __init__(self, buf, n):
+        self.buf, self.n = buf, int(n)
+
+    def __len__(self):
+        return self.n
+
+
+def search_index(pts):
+    """index of a float32 (N,3) cloud for search_knn / search_hybrid / search_radius (float64 input is rounded to float32)"""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    buf = torch.empty(lib.kpx_search_index_bytes(n), dtype=torch.uint8, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_search_workspace_bytes(n, 0))
+    L.check(lib.kpx_search_index_build(L.ptr(pts), n, L.ptr(buf), buf.numel(), ws, wsz, L.stream_ptr()))
+    return SearchIndex(buf, n)
+
+
+def _search_knn(index, queries, k, radius):
+    lib = L.load()
+    q = _dev(queries, torch.float32).reshape(-1, 3)
+    m, k = q.shape[0], int(k)
+    idx = torch.empty((m, max(k, 1)), dtype=torch.int32, device=q.device)
+    d2 = torch.empty((m, max(k, 1)), dtype=torch.float64, device=q.device)
+    cnt = torch.empty(m, dtype=torch.int32, device=q.device)
+    ws, wsz = L.workspace(lib.kpx_search_workspace_bytes(m, max(k, 1)))
+    L.check(lib.kpx_search_knn(L.ptr(index.buf), index.buf.numel(), L.ptr(q), m, k, float(radius), L.ptr(idx), L.ptr(d2), L.ptr(cnt), ws, wsz,
+                               L.stream_ptr()))
+    return idx, d2, cnt
+
+
+def search_knn(index, queries, k):
+    """[O3D] KDTreeFlann.SearchKNN for M queries: idx i32 (M,k), d2 f64 (M,k), count i32 (M) device tensors; row q holds the
+    count[q] = min(k, N) nearest points ascending in (d2, index), then -1 / +inf."""
+    return _search_knn(index, queries, k, 0.0)
+
+
+def search_hybrid(index, queries, radius, max_nn):
+    """[O3D] KDTreeFlann.SearchHybrid for M queries: the first min(max_nn, count) entries of the radius result (d2 < radius^2,
+    strict); same layout as search_knn."""
+    if not float(radius) > 0.0:
+        raise L.KinectPxError("search_hybrid: radius must be positive")
+    return _search_knn(index, queries, max_nn, radius)
+
+
+def search_radius(index, queries, radius):
+    """[O3D] KDTreeFlann.SearchRadius for M queries as a CSR: offsets i64 (M+1), idx i32 (total), d2 f64 (total) device tensors;
+    segment q = [offsets[q], offsets[q+1]) holds every point with d2 < radius^2 (strict) ascending in (d2, index).  One host read
+    (the total) between the count pass and the fill pass."""
+    lib = L.load()
+    q = _dev(queries, torch.float32).reshape(-1, 3)
+    m = q.shape[0]
+    offsets = torch.empty(m + 1, dtype=torch.int64, device=q.device)
+    ws, wsz = L.workspace(lib.kpx_search_workspace_bytes(m, 1))
+    L.check(lib.kpx_search_radius_count(L.ptr(index.buf), index.buf.numel(), L.ptr(q), m, float(radius), L.ptr(offsets), ws, wsz, L.stream_ptr()))
+    total = int(offsets[m].item())
+    if total > 2**31 - 1:
+        raise L.KinectPxError(f"search_radius: {total} entries, more than 2^31 - 1")
+    idx = torch.empty(total, dtype=torch.int32, device=q.device)
+    d2 = torch.empty(total, dtype=torch.float64, device=q.device)
+    L.check(lib.kpx_search_radius_fill(L.ptr(index.buf), index.buf.numel(), L.ptr(q), m, float(radius), L.ptr(offsets), total, L.ptr(idx),
+                                       L.ptr(d2), ws, wsz, L.stream_ptr()))
+    return offsets, idx, d2
+
+
 def segment_plane(pts, distance_threshold, ransac_n, num_iterations, probability=0.99999999, seed=0):
     """a21.  Returns plane (numpy f64 (4,)), inlier idx i32 (K) device tensor."""
     lib = L.load()

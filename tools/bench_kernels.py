@@ -127,6 +127,27 @@ def main():
     ms, kr = timed(lambda: ops.remove_radius_outlier(fc, 10, 20.0), reps=5, warm=2)
     report("remove_radius_outlier nb_points=10 radius=20 on the frame cloud", ms, n=int(fc.shape[0]), kept=int(kr.shape[0]))
 
+    # ---- neighbour search (KDTreeFlann) on the frame cloud: index build, self-query knn, the hybrid search of the bench's
+    # estimate_normals setting beside estimate_normals itself (the same selection plus covariance and eigen-solve), one radius search at
+    # DBSCAN's eps, and queries far outside the cloud
+    nfc = int(fc.shape[0])
+    ms, sidx = timed(lambda: ops.search_index(fc), reps=20, warm=2)
+    report("search_index on the frame cloud", ms, n=nfc)
+    for k in (1, 8, 30):
+        ms, _ = timed(lambda: ops.search_knn(sidx, fc, k), reps=20, warm=2)
+        report(f"search_knn k={k}, self-query on the frame cloud", ms, n=nfc, m=nfc)
+    ms, _ = timed(lambda: ops.search_hybrid(sidx, fc, 70.0, 40), reps=20, warm=2)
+    report("search_hybrid r=70 max_nn=40, self-query on the frame cloud", ms, n=nfc, m=nfc)
+    ms, _ = timed(lambda: ops.estimate_normals(fc, 70.0, 40), reps=20, warm=2)
+    report("estimate_normals r=70 max_nn=40 on the frame cloud (the yardstick of search_hybrid)", ms, n=nfc)
+    ms, (soff, _, _) = timed(lambda: ops.search_radius(sidx, fc, 20.0), reps=20, warm=2)
+    report("search_radius r=20, self-query on the frame cloud (count, host read of the total, fill, segment sort)", ms, n=nfc, m=nfc,
+           entries=int(soff[-1].item()))
+    bb = ops.bounds(fc).cpu().numpy()
+    farq = bb[3:] + (bb[3:] - bb[:3]) * np.random.default_rng(0).uniform(5.0, 100.0, (32, 3))
+    ms, _ = timed(lambda: ops.search_knn(sidx, farq, 8), reps=20, warm=2)
+    report("search_knn k=8, 32 queries 5-100 box lengths outside the frame cloud", ms, n=nfc, m=32)
+
     # ---- farthest-point sampling (the PointNet input): the chain on the frame cloud and on 30k points, the block form on 19456 points
     # and on a batch of 64 x 30k (one launch)
     for k in (1024, 4096):
