@@ -218,6 +218,32 @@ size_t kpx_radius_outlier_workspace_bytes(int64_t n);
 int kpx_remove_radius_outlier(const float *pts, int64_t n, int32_t nb_points, double radius, int32_t *keep_idx,
                               int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
 
+/* keypoints = o3d.geometry.keypoint.compute_iss_keypoints(pcd, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)
+ * ([O3D] geometry::keypoint::ComputeISSKeypoints, Zhong 2009).  Neighbours of i within r: every j (i included) with d2 < r^2 (AC3,
+ * strict <).  Saliency s_i: with m = #neighbours within salient_radius, s_i = 0 if m < min_neighbors; else C = covariance of those
+ * points in Open3D's raw-moment form (nine moments / m, C_ab = E[ab] - E[a] E[b]; fp64), s_i = 0 if every |C_ab| <= 1e-12; else with
+ * the eigenvalues e3 <= e2 <= e1 of C, s_i = e3 if e2 / e1 < gamma_21 and e3 / e2 < gamma_32 (a NaN ratio fails), else 0.
+ * i is a keypoint iff s_i > 0, it has >= min_neighbors neighbours within non_max_radius and none of them has a larger saliency
+ * (equal saliencies do not suppress each other).  keep_idx ascending, d_count = keypoints.
+ *   kpx_iss_saliency  writes saliency f64 [n] (by point index);
+ *   kpx_iss_nonmax    suppresses ANY caller-supplied saliency f64 [n] (NaN, zero and negative entries are never keypoints);
+ *   kpx_iss_keypoints both on one grid: saliency [n] out, keep_idx [n], d_count.
+ * The radii are given (the defaults of Open3D's 0.0 -- 6 x and 4 x the mean nearest-neighbour distance -- are resolved by the caller,
+ * kpx_mean_nn_distance).  Rejects radii that are not positive and finite and min_neighbors < 0.  n == 0: d_count = 0. */
+size_t kpx_iss_workspace_bytes(int64_t n);
+int kpx_iss_saliency(const float *pts, int64_t n, double salient_radius, double gamma_21, double gamma_32, int32_t min_neighbors,
+                     double *saliency /* [n] */, void *ws, size_t ws_bytes, void *stream);
+int kpx_iss_nonmax(const float *pts, int64_t n, const double *saliency /* [n] */, double non_max_radius, int32_t min_neighbors,
+                   int32_t *keep_idx, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_iss_keypoints(const float *pts, int64_t n, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                      int32_t min_neighbors, double *saliency /* [n] */, int32_t *keep_idx, int32_t *d_count, void *ws, size_t ws_bytes,
+                      void *stream);
+/* Mean of [O3D] ComputeNearestNeighborDistance from a 2-nearest search of a cloud on itself (kpx_search_knn, k = 2): d_mean =
+ * (sum over rows with count >= 2 of sqrt(d2[row * stride + 1])) / m, the sum exact in 128-bit fixed point -- the same bits whatever
+ * the order of the adds.  ws: 256 bytes. */
+int kpx_mean_nn_distance(const double *d2, const int32_t *count, int64_t m, int32_t stride, double *d_mean, void *ws, size_t ws_bytes,
+                         void *stream);
+
 /* pcd.farthest_point_down_sample(k, start_index) ([O3D] PointCloud::FarthestPointDownSample): the fixed-size input of the PointNet
  * regressor (datasets/kinect_dataset*.py, number_of_points) by farthest-point sampling instead of a uniform draw.  Open3D's loop:
  *   dist[j] = +inf; far = start_index; for i < k: sel[i] = far; s = p[far]; max_dist = 0;

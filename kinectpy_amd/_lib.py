@@ -54,6 +54,11 @@ SIGNATURES = {
     "kpx_cluster_dbscan": (C.c_int, [_vp, _i64, _f64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_radius_outlier_workspace_bytes": (_sz, [_i64]),
     "kpx_remove_radius_outlier": (C.c_int, [_vp, _i64, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_iss_workspace_bytes": (_sz, [_i64]),
+    "kpx_iss_saliency": (C.c_int, [_vp, _i64, _f64, _f64, _f64, _i32, _vp, _vp, _sz, _vp]),
+    "kpx_iss_nonmax": (C.c_int, [_vp, _i64, _vp, _f64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_iss_keypoints": (C.c_int, [_vp, _i64, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mean_nn_distance": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "kpx_fps_workspace_bytes": (_sz, [_i32, _i64]),
     "kpx_farthest_point_sample": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_farthest_point_sample_batch": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),

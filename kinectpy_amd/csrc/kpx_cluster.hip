@@ -1,6 +1,7 @@
 // kpx_cluster.hip -- radius-neighbourhood operators on the exact grid of kpx_knn.hip:
 //   PointCloud.cluster_dbscan(eps, min_points)          ([O3D] PointCloud::ClusterDBSCAN)
 //   PointCloud.remove_radius_outlier(nb_points, radius) ([O3D] PointCloud::RemoveRadiusOutliers)
+//   keypoint.compute_iss_keypoints(...)                 ([O3D] geometry::keypoint::ComputeISSKeypoints; below, "ISS keypoints")
 // Neighbours of i: every j (i itself included) with d2(i, j) < eps^2, AC3 arithmetic (d2 = fma(dz,dz, fma(dy,dy, dx*dx)), fp64
 // differences of the float32 coordinates), strict <, the convention of the hybrid searches.
 //
@@ -16,7 +17,11 @@
 //   4 rank    ordered compaction of the roots (index order): rank[root] = cluster id, the count -> d_nclusters
 //   5 label   core points take rank[parent[i]]; non-core points walk once more and take the smallest id of a core neighbour
 // Nothing depends on the order in which the atomics land: the partition, its roots and the ranks are functions of the input.
+#include <float.h>
+
+#include "kpx_fixed.h"
 #include "kpx_gridknn.h"
+#include "kpx_linalg.h"
 
 namespace kpx {
 
@@ -180,6 +185,107 @@ __global__ __launch_bounds__(kClusterThreads) void dbscan_border_kernel(const Gr
     }
 }
 
+// ---- ISS keypoints ("ISS keypoints") -----------------------------------------------------------------------------------------
+//   s_i = smallest eigenvalue e3 of the covariance of the points within salient_radius of i, if there are >= min_neighbors of them,
+//         the covariance is not Eigen's isZero (some |C_ab| > 1e-12) and e2/e1 < gamma_21, e3/e2 < gamma_32 (e3 <= e2 <= e1); else 0
+//   i is a keypoint <=> s_i > 0, i has >= min_neighbors points within non_max_radius, and none of them has a larger s
+// Both passes: one thread per query in cell-sorted order on ONE grid whose cells are half the larger radius (a salient ball holds
+// ~10^2 points: cells of 8 points would make the visitor walk hundreds of columns for it).
+constexpr double kIssZero = 1e-12;          // Eigen's default precision of isZero() for double
+
+// pass 1.  The moments are those of q - p_j (exact in fp64 for float32 coordinates; the covariance does not move with the origin and
+// the sums stay small), Open3D's ComputeCovariance otherwise: nine raw moments / m, C_ab = E[ab] - E[a] E[b].
+__global__ __launch_bounds__(kClusterThreads) void iss_saliency_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
+                                                                       const float *__restrict__ spts, const int32_t *__restrict__ sidx, int64_t n,
+                                                                       double eps, double r2, double gamma_21, double gamma_32, int64_t min_nb,
+                                                                       double *__restrict__ sal_s, double *__restrict__ sal_o)
+{
+    const GridParams g = *gp;
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        double q[3];
+        load_query(spts, s, q);
+        int64_t m = 0;
+        double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+        grid_radius_scan(g, cell_start, spts, q, eps, r2, [&](uint32_t t, double) {
+            const float *p = spts + 3 * (int64_t)t;
+            const double dx = q[0] - (double)p[0], dy = q[1] - (double)p[1], dz = q[2] - (double)p[2];
+            ++m;
+            sx += dx; sy += dy; sz += dz;
+            sxx += dx * dx; sxy += dx * dy; sxz += dx * dz; syy += dy * dy; syz += dy * dz; szz += dz * dz;
+            return false;
+        });
+        double sal = 0.0;
+        if (m >= min_nb && m > 0) {
+            const double im = (double)m;
+            const double mx = sx / im, my = sy / im, mz = sz / im;
+            const double c[6] = { sxx / im - mx * mx, sxy / im - mx * my, sxz / im - mx * mz, syy / im - my * my, syz / im - my * mz, szz / im - mz * mz };
+            bool zero = true;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) zero = zero && fabs(c[k]) <= kIssZero;
+            if (!zero) {
+                double w[3], V[9];
+                sym3_eigen(c, w, V);
+                if (w[1] / w[2] < gamma_21 && w[0] / w[1] < gamma_32) sal = w[0];          // IEEE comparisons: a NaN ratio fails
+            }
+        }
+        if (sal_s) sal_s[s] = sal;
+        sal_o[sidx[s]] = sal;
+    }
+}
+
+// a caller's saliency (by original index) in cell-sorted order for pass 2
+__global__ __launch_bounds__(kClusterThreads) void iss_gather_kernel(const int32_t *__restrict__ sidx, int64_t n, const double *__restrict__ sal_o,
+                                                                     double *__restrict__ sal_s)
+{
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) sal_s[s] = sal_o[sidx[s]];
+}
+
+// pass 2: the walk stops at the first neighbour with a larger saliency (a stopped walk is no keypoint whatever its count); equal
+// saliencies do not suppress each other
+__global__ __launch_bounds__(kClusterThreads) void iss_nonmax_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
+                                                                     const float *__restrict__ spts, const int32_t *__restrict__ sidx, int64_t n,
+                                                                     double eps, double r2, int64_t min_nb, const double *__restrict__ sal_s,
+                                                                     uint8_t *__restrict__ flag_o)
+{
+    const GridParams g = *gp;
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        const double si = sal_s[s];
+        uint8_t f = 0;
+        if (si > 0.0) {
+            double q[3];
+            load_query(spts, s, q);
+            int64_t cnt = 0;
+            bool beaten = false;
+            grid_radius_scan(g, cell_start, spts, q, eps, r2, [&](uint32_t t, double) {
+                ++cnt;
+                beaten = si < sal_s[t];
+                return beaten;
+            });
+            f = (!beaten && cnt >= min_nb) ? 1 : 0;
+        }
+        flag_o[sidx[s]] = f;
+    }
+}
+
+// Mean over the m queries of the distance to the nearest OTHER point: row q of a 2-nearest search (d2 [m, stride], count [m]) adds
+// sqrt(d2[q, 1]) when it has two results.  The sum is taken in 128-bit fixed point (kpx_fixed.h): exact, whatever the order.
+__global__ __launch_bounds__(kClusterThreads) void nn_distance_sum_kernel(const double *__restrict__ d2, const int32_t *__restrict__ cnt, int64_t m,
+                                                                          int32_t stride, unsigned long long *__restrict__ acc)
+{
+    unsigned long long lo = 0ull, hi = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        if (cnt[i] >= 2) {
+            unsigned long long l, h;
+            fixed_split(sqrt(d2[i * stride + 1]), l, h);
+            fixed_accumulate(lo, hi, l, h);
+        }
+    fixed_add_words(acc, lo, hi);
+}
+__global__ void nn_distance_mean_kernel(const unsigned long long *__restrict__ acc, int64_t m, double *__restrict__ out)
+{
+    *out = fixed_value(acc[0], acc[1]) / (double)m;
+}
+
 unsigned launch_blocks(int64_t n)
 {
     const int64_t b = cdiv(n > 0 ? n : 1, kClusterThreads);
@@ -245,6 +351,35 @@ int radius_outlier_impl(const float *pts, int64_t n, int32_t nb_points, double r
     return compact(KeepPred{ r.flag_o }, KeepEmit{ keep_idx }, n, 1, r.counts, d_count, st);
 }
 
+// ISS on one grid: saliency (sal_o written) when salient_radius > 0, else sal_o is the caller's; suppression and the ordered
+// compaction when non_max_radius > 0.
+int iss_impl(const float *pts, int64_t n, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int32_t min_neighbors,
+             double *sal_o, int32_t *keep_idx, int32_t *d_count, Arena &a, hipStream_t st)
+{
+    const double rmax = salient_radius > non_max_radius ? salient_radius : non_max_radius;
+    Grid g;
+    int rc = grid_build(pts, n, 8.0, a, &g, st, 0.5 * rmax);
+    if (rc) return rc;
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    double *sal_s = a.get<double>(nn);
+    uint8_t *flag_o = a.get<uint8_t>(nn);
+    int32_t *counts = a.get<int32_t>((size_t)compact_ws_ints(n));
+    if (a.dry) return KPX_OK;
+    KPX_ARENA_CHECK(a);
+    const unsigned nb = launch_blocks(n);
+    if (salient_radius > 0.0)
+        hipLaunchKernelGGL(iss_saliency_kernel, dim3(nb), dim3(kClusterThreads), 0, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, n,
+                           salient_radius, salient_radius * salient_radius, gamma_21, gamma_32, (int64_t)min_neighbors,
+                           non_max_radius > 0.0 ? sal_s : (double *)nullptr, sal_o);
+    else
+        hipLaunchKernelGGL(iss_gather_kernel, dim3(nb), dim3(kClusterThreads), 0, st, (const int32_t *)g.sorted_idx, n, (const double *)sal_o, sal_s);
+    if (!(non_max_radius > 0.0)) { KPX_LAUNCH_CHECK(); return KPX_OK; }
+    hipLaunchKernelGGL(iss_nonmax_kernel, dim3(nb), dim3(kClusterThreads), 0, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, n, non_max_radius,
+                       non_max_radius * non_max_radius, (int64_t)min_neighbors, (const double *)sal_s, flag_o);
+    KPX_LAUNCH_CHECK();
+    return compact(KeepPred{ flag_o }, KeepEmit{ keep_idx }, n, 1, counts, d_count, st);
+}
+
 }  // namespace
 
 }  // namespace kpx
@@ -289,4 +424,69 @@ KPX_EXPORT int kpx_remove_radius_outlier(const float *pts, int64_t n, int32_t nb
     KPX_REQUIRE(pts && keep_idx, "kpx_remove_radius_outlier: null pointer");
     Arena a(ws, ws_bytes);
     return radius_outlier_impl(pts, n, nb_points, radius, keep_idx, d_count, a, st);
+}
+
+KPX_EXPORT size_t kpx_iss_workspace_bytes(int64_t n)
+{
+    Arena a(nullptr, 0);
+    iss_impl(nullptr, n, 1.0, 1.0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, a, nullptr);
+    return a.off;
+}
+#define KPX_ISS_RADIUS(r, name) KPX_REQUIRE((r) > 0.0 && (r) <= DBL_MAX, "compute_iss_keypoints: " name " must be positive and finite")
+KPX_EXPORT int kpx_iss_saliency(const float *pts, int64_t n, double salient_radius, double gamma_21, double gamma_32, int32_t min_neighbors,
+                                double *saliency, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_ISS_RADIUS(salient_radius, "salient_radius");
+    KPX_REQUIRE(min_neighbors >= 0, "compute_iss_keypoints: min_neighbors must be non-negative");
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_iss_saliency: bad size");
+    KPX_REQUIRE(ws, "kpx_iss_saliency: null pointer");
+    if (n == 0) return KPX_OK;
+    KPX_REQUIRE(pts && saliency, "kpx_iss_saliency: null pointer");
+    Arena a(ws, ws_bytes);
+    return iss_impl(pts, n, salient_radius, 0.0, gamma_21, gamma_32, min_neighbors, saliency, nullptr, nullptr, a, (hipStream_t)stream);
+}
+KPX_EXPORT int kpx_iss_nonmax(const float *pts, int64_t n, const double *saliency, double non_max_radius, int32_t min_neighbors, int32_t *keep_idx,
+                              int32_t *d_count, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_ISS_RADIUS(non_max_radius, "non_max_radius");
+    KPX_REQUIRE(min_neighbors >= 0, "compute_iss_keypoints: min_neighbors must be non-negative");
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_iss_nonmax: bad size");
+    KPX_REQUIRE(d_count && ws, "kpx_iss_nonmax: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { KPX_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st)); return KPX_OK; }
+    KPX_REQUIRE(pts && saliency && keep_idx, "kpx_iss_nonmax: null pointer");
+    Arena a(ws, ws_bytes);
+    return iss_impl(pts, n, 0.0, non_max_radius, 0.0, 0.0, min_neighbors, const_cast<double *>(saliency), keep_idx, d_count, a, st);
+}
+KPX_EXPORT int kpx_iss_keypoints(const float *pts, int64_t n, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                                 int32_t min_neighbors, double *saliency, int32_t *keep_idx, int32_t *d_count, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_ISS_RADIUS(salient_radius, "salient_radius");
+    KPX_ISS_RADIUS(non_max_radius, "non_max_radius");
+    KPX_REQUIRE(min_neighbors >= 0, "compute_iss_keypoints: min_neighbors must be non-negative");
+    KPX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "kpx_iss_keypoints: bad size");
+    KPX_REQUIRE(d_count && ws, "kpx_iss_keypoints: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { KPX_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st)); return KPX_OK; }
+    KPX_REQUIRE(pts && saliency && keep_idx, "kpx_iss_keypoints: null pointer");
+    Arena a(ws, ws_bytes);
+    return iss_impl(pts, n, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, saliency, keep_idx, d_count, a, st);
+}
+#undef KPX_ISS_RADIUS
+
+KPX_EXPORT int kpx_mean_nn_distance(const double *d2, const int32_t *count, int64_t m, int32_t stride, double *d_mean, void *ws, size_t ws_bytes,
+                                    void *stream)
+{
+    KPX_REQUIRE(m >= 1 && stride >= 2, "kpx_mean_nn_distance: needs at least one row of a 2-nearest search");
+    KPX_REQUIRE(d2 && count && d_mean && ws, "kpx_mean_nn_distance: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    unsigned long long *acc = a.get<unsigned long long>(kFixedWords);
+    KPX_ARENA_CHECK(a);
+    KPX_HIP(hipMemsetAsync(acc, 0, kFixedWords * sizeof(unsigned long long), st));
+    const int64_t b = cdiv(m, kClusterThreads);
+    hipLaunchKernelGGL(nn_distance_sum_kernel, dim3((unsigned)(b > 1024 ? 1024 : b)), dim3(kClusterThreads), 0, st, d2, count, m, stride, acc);
+    hipLaunchKernelGGL(nn_distance_mean_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long *)acc, m, d_mean);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
 }

@@ -29,8 +29,9 @@ struct Grid {
 };
 constexpr int kGridExtraWords = 4104;
 // Carves a Grid out of the arena (dry arenas only count bytes) and, when real, builds it on `st`.
-// target_per_cell: desired mean occupancy of non-empty cells.
-int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Grid *g, hipStream_t st);
+// target_per_cell: desired mean occupancy of non-empty cells.  fixed_h > 0: cells of that size instead (coarser where the grid would
+// outgrow its cell budget or hold fewer than target_per_cell points per cell); no result of any search depends on the cell size.
+int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Grid *g, hipStream_t st, double fixed_h = 0.0);
 
 // ---- library-internal lanes ------------------------------------------------------------------------
 // Batched entry points run their independent problems (chains of short, latency-bound kernels) side by side on

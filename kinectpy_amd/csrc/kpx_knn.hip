@@ -33,8 +33,10 @@ __device__ __forceinline__ void grid_dims(const double ext[3], double &h, int32_
         h *= 1.26;
     }
 }
+// fixed_h > 0: the caller's cell size instead (ISS: half its larger radius), never below the heuristic's cell of `target` points (a
+// radius under the point spacing would ask for more cells than there are points) and without the occupancy feedback.
 __device__ __forceinline__ GridParams grid_params_of(const double *__restrict__ bbox, int64_t n, double target, int32_t cell_cap,
-                                                     const unsigned long long *__restrict__ sumsq)
+                                                     const unsigned long long *__restrict__ sumsq, double fixed_h)
 {
     GridParams gp;
     double ext[3], vol = 1.0;
@@ -45,9 +47,10 @@ __device__ __forceinline__ GridParams grid_params_of(const double *__restrict__ 
     const double h2 = sqrt(area * target / nn) * 0.5;           // clouds are surfaces: size cells by area too
     double h = h3 > h2 ? h3 : h2;
     if (!(h > 0.0)) h = 1.0;
+    if (fixed_h > h) h = fixed_h;
     int dim[3];
     grid_dims(ext, h, cell_cap, dim);
-    if (sumsq) {
+    if (sumsq && !(fixed_h > 0.0)) {
         const double occ = (double)*sumsq / nn;
         double f = pow(target / (occ > 1.0 ? occ : 1.0), 1.0 / 2.3);
         f = f < 0.125 ? 0.125 : (f > 8.0 ? 8.0 : f);
@@ -74,11 +77,12 @@ __global__ __launch_bounds__(256) void grid_occupancy_kernel(const uint32_t *__r
 }
 __global__ __launch_bounds__(256) void grid_cell_kernel(const float *__restrict__ pts, int64_t n, const double *__restrict__ bbox, double target,
                                                         int32_t cell_cap, const unsigned long long *__restrict__ sumsq, GridParams *gp,
-                                                        uint32_t *__restrict__ keys, int32_t *__restrict__ vals, uint32_t *__restrict__ cell_count)
+                                                        uint32_t *__restrict__ keys, int32_t *__restrict__ vals, uint32_t *__restrict__ cell_count,
+                                                        double fixed_h)
 {
     __shared__ GridParams sg;
     if (threadIdx.x == 0) {
-        sg = grid_params_of(bbox, n, target, cell_cap, sumsq);
+        sg = grid_params_of(bbox, n, target, cell_cap, sumsq, fixed_h);
         if (blockIdx.x == 0) *gp = sg;
     }
     __syncthreads();
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(256) void grid_scan_kernel(const uint32_t *__restri
     }
 }
 
-int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Grid *g, hipStream_t st)
+int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Grid *g, hipStream_t st, double fixed_h)
 {
     const size_t nn = (size_t)(n > 0 ? n : 1);
     g->params = a.get<GridParams>(1);
@@ -198,10 +202,10 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
     int nb = (int)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256));
     // first binning from the bounding-box heuristic, one round of occupancy feedback, then the definitive binning
     hipLaunchKernelGGL(grid_cell_kernel, dim3(nb), dim3(256), 0, st, pts, n, bbox, target_per_cell, cell_cap, (const unsigned long long *)nullptr, g->params,
-                       keys_in, vals_in, count1);
+                       keys_in, vals_in, count1, fixed_h);
     hipLaunchKernelGGL(grid_occupancy_kernel, dim3(1024), dim3(256), 0, st, count1, g->params, sumsq);
     hipLaunchKernelGGL(grid_cell_kernel, dim3(nb), dim3(256), 0, st, pts, n, bbox, target_per_cell, cell_cap, (const unsigned long long *)sumsq, g->params,
-                       keys_in, vals_in, count2);
+                       keys_in, vals_in, count2, fixed_h);
     static const bool vendor_scan = [] { const char *e = getenv("KPX_GRID_SCAN"); return e && e[0] == '0'; }();      // A/B switch
     if (vendor_scan) KPX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, count2, g->cell_start, cell_cap + 1, st));
     else

@@ -359,6 +359,12 @@ class PointCloud:
         d2, cnt = d2.cpu().numpy(), cnt.cpu().numpy()
         return np.where(cnt >= 2, np.sqrt(np.where(cnt >= 2, d2[:, 1], 0.0)), 0.0)
 
+    def _iss_keypoint_indices(self, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+        """ascending int32 device tensor of the ISS keypoints' indices (o3d.geometry.keypoint.compute_iss_keypoints)"""
+        if salient_radius < 0 or non_max_radius < 0 or min_neighbors < 0:
+            raise RuntimeError("compute_iss_keypoints: radii and min_neighbors must be non-negative")
+        return ops.iss_keypoints(self._pts, float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors))
+
     def get_oriented_bounding_box(self, robust=False):
         """utils/normalization.py:39, 74, 105; utils/processing.py:341"""
         obb, _ = ops.obb_batch(self._pts)

@@ -246,6 +246,19 @@ class Feature:
     def num(self):
         return int(self._dev.shape[0])
 
+    def select_by_index(self, indices, invert=False):
+        """[O3D] Feature.select_by_index: the columns of `.data` named by `indices` (duplicates once, ascending -- Open3D selects
+        through a mask), or every other column with invert=True; an index outside [0, num) raises"""
+        import torch
+        n = self.num()
+        idx = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices).reshape(-1).astype(np.int64))
+        idx = idx.reshape(-1).to(device=self._dev.device, dtype=torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise RuntimeError(f"Feature.select_by_index: index out of range [0, {n})")
+        mask = torch.zeros(n, dtype=torch.bool, device=self._dev.device)
+        mask[idx] = True
+        return Feature(self._dev[~mask if invert else mask].contiguous())
+
 
 class CorrespondenceCheckerBasedOnEdgeLength:
     def __init__(self, similarity_threshold=0.9):
@@ -302,6 +315,16 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], corres)
 
 
+def compute_iss_keypoints(input, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """[O3D] geometry.keypoint.compute_iss_keypoints (Zhong 2009): the points whose neighbourhood covariance has three well
+    separated eigenvalues and whose smallest eigenvalue is a maximum within non_max_radius, as a PointCloud (colours and normals
+    follow) in ascending order of their index in `input` -- Open3D's order is whatever its OpenMP loop produced.  Either radius 0:
+    both are taken from the cloud's resolution (6 x and 4 x the mean nearest-neighbour distance)."""
+    if not input.has_points():
+        return PointCloud()
+    return input._select(input._iss_keypoint_indices(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors))
+
+
 def _off_path(name):
     def f(*a, **k):
         raise NotImplementedError(f"{name} is outside the round-1 hot path of kinectpy_amd (SURVEY.md 8f); "
@@ -310,7 +333,8 @@ def _off_path(name):
 
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
-                                 KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann)
+                                 KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
+                                 keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
 io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
 pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(

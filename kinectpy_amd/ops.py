@@ -399,6 +399,76 @@ def remove_radius_outlier(pts, nb_points, radius):
     return idx[:k]
 
 
+def iss_saliency(pts, salient_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """[O3D] ComputeISSKeypoints, first half: saliency f64 (N) device tensor -- the smallest eigenvalue of the covariance of the
+    points within salient_radius where both eigenvalue ratios pass, else 0 (include/kinectpx.h).  No host sync."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    sal = torch.empty(n, dtype=torch.float64, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_iss_workspace_bytes(n))
+    L.check(lib.kpx_iss_saliency(L.ptr(pts), n, float(salient_radius), float(gamma_21), float(gamma_32), int(min_neighbors), L.ptr(sal), ws, wsz,
+                                 L.stream_ptr()))
+    return sal
+
+
+def iss_nonmax(pts, saliency, non_max_radius, min_neighbors=5):
+    """[O3D] ComputeISSKeypoints, second half, for ANY saliency f64 (N): keep_idx i32 (K) ascending device tensor of the points with
+    saliency > 0, at least min_neighbors points within non_max_radius and no larger saliency among them."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    sal = _dev(saliency, torch.float64).reshape(-1)
+    if sal.numel() != n:
+        raise L.KinectPxError(f"iss_nonmax: {sal.numel()} saliencies for {n} points")
+    idx = torch.empty(max(n, 1), dtype=torch.int32, device=pts.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_iss_workspace_bytes(n))
+    L.check(lib.kpx_iss_nonmax(L.ptr(pts), n, L.ptr(sal), float(non_max_radius), int(min_neighbors), L.ptr(idx), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    k = _count(cnt)[0]
+    return idx[:k]
+
+
+def model_resolution(pts):
+    """[O3D] ComputeModelResolution: the mean over all points of the distance to the nearest OTHER point, as an f64 (1) device
+    tensor (0 for an empty cloud).  The sum is exact (128-bit fixed point), so the value is the same bits run to run.  No host sync."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    out = torch.zeros(1, dtype=torch.float64, device=pts.device)
+    if n == 0:
+        return out
+    _, d2, cnt = search_knn(search_index(pts), pts, 2)
+    ws, wsz = L.workspace(256)
+    L.check(lib.kpx_mean_nn_distance(L.ptr(d2), L.ptr(cnt), n, int(d2.shape[1]), L.ptr(out), ws, wsz, L.stream_ptr()))
+    return out
+
+
+def iss_keypoints(pts, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, want_saliency=False):
+    """[O3D] ComputeISSKeypoints: keep_idx i32 (K) ascending device tensor (and the saliency f64 (N) with want_saliency).  Either
+    radius 0: BOTH are replaced by 6 x and 4 x model_resolution(pts) -- one host read; the count is the other."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    sal = torch.empty(n, dtype=torch.float64, device=pts.device)
+    idx = torch.empty(max(n, 1), dtype=torch.int32, device=pts.device)
+    if n == 0:
+        return (idx[:0], sal) if want_saliency else idx[:0]
+    salient_radius, non_max_radius = float(salient_radius), float(non_max_radius)
+    if salient_radius == 0.0 or non_max_radius == 0.0:
+        resolution = float(model_resolution(pts).item())
+        salient_radius, non_max_radius = 6.0 * resolution, 4.0 * resolution
+        if not resolution > 0.0:                      # one point, or nothing but duplicates: no neighbourhood has a covariance
+            sal.zero_()
+            return (idx[:0], sal) if want_saliency else idx[:0]
+    cnt = torch.empty(1, dtype=torch.int32, device=pts.device)
+    ws, wsz = L.workspace(lib.kpx_iss_workspace_bytes(n))
+    L.check(lib.kpx_iss_keypoints(L.ptr(pts), n, salient_radius, non_max_radius, float(gamma_21), float(gamma_32), int(min_neighbors), L.ptr(sal),
+                                  L.ptr(idx), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    k = _count(cnt)[0]
+    return (idx[:k], sal) if want_saliency else idx[:k]
+
+
 def farthest_point_sample(pts, k, start_index=0, want_cover=False):
     """[O3D] FarthestPointDownSample's loop: sel i32 (k) device tensor in selection order (repeats kept: the previous index
     repeats once every distance is 0), cover f64 (k) | None -- the largest running distance after each sample.  No host sync."""

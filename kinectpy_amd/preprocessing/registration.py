@@ -27,16 +27,33 @@ def prepare_dataset(pcd_master, pcd_sub, voxel_size, normals_nn=40, fpfh_nn=40, 
     return source, target, source_down, target_down, source_fpfh, target_fpfh
 
 
-def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransac_n_trials: int = 15, seed=None) -> np.ndarray:
+def _cut_to_keypoints(down, fpfh, keypoints):
+    """(cloud, feature) of the ISS keypoints of a down-sampled cloud; `keypoints`: True (default radii) or a dict of
+    compute_iss_keypoints' parameters"""
+    idx = down._iss_keypoint_indices(**(keypoints if isinstance(keypoints, dict) else {}))
+    return down._select(idx), fpfh.select_by_index(idx)
+
+
+def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransac_n_trials: int = 15, seed=None, *, keypoints=None) -> np.ndarray:
     """registration.py:32-62: ransac_n_trials runs of FPFH feature-matching RANSAC (distance threshold 1.5 v,
     mutual filter, edge-length 0.95 + distance checkers, 250000 iterations, confidence 0.999); the
     transformation of the best fitness is kept (None if every fitness is 0).  The reference recomputes
     prepare_dataset in every trial with identical results; here it is computed once.  seed: base seed of the
-    trials (None -> fresh random seeds, the reference's behaviour)."""
+    trials (None -> fresh random seeds, the reference's behaviour).
+    keypoints: None (the reference: every down-sampled point is matched), True (ISS keypoints with Open3D's default radii, from
+    the down-sampled cloud's resolution) or a dict of o3d.geometry.keypoint.compute_iss_keypoints' parameters.  Normals and FPFH are
+    still computed on the full down-sampled clouds; points and feature columns are then cut to the keypoints on both sides and the
+    RANSAC matches and scores those alone.  If either side has fewer than ransac_n = 3 keypoints, the full clouds are used as if
+    keypoints were None."""
     best_fitness = 0
     ransac_transformation = None
     reg = o3d.pipelines.registration
     (source, target, source_down, target_down, source_fpfh, target_fpfh) = prepare_dataset(pcd_master, pcd_sub, voxel_size)
+    if keypoints is not None and keypoints is not False:
+        source_key, source_key_fpfh = _cut_to_keypoints(source_down, source_fpfh, keypoints)
+        target_key, target_key_fpfh = _cut_to_keypoints(target_down, target_fpfh, keypoints)
+        if min(len(source_key.points), len(target_key.points)) >= 3:
+            source_down, source_fpfh, target_down, target_fpfh = source_key, source_key_fpfh, target_key, target_key_fpfh
     distance_threshold = voxel_size * 1.5
     for trial in range(ransac_n_trials):
         result_ransac = reg.registration_ransac_based_on_feature_matching(
@@ -69,6 +86,10 @@ def execute_point_to_plane_registration(pcd_master, pcd_sub, initial_transformat
 # by parameter): `kernel` is this library's keyword-only extension and is documented in the docstring above.
 execute_point_to_plane_registration.__signature__ = inspect.Signature(
     [p for p in inspect.signature(execute_point_to_plane_registration).parameters.values() if p.name != "kernel"])
+# likewise `keypoints` of execute_global_registration
+execute_global_registration.__signature__ = inspect.Signature(
+    [p for p in inspect.signature(execute_global_registration).parameters.values() if p.name != "keypoints"],
+    return_annotation=inspect.signature(execute_global_registration).return_annotation)
 
 
 def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation):
@@ -94,7 +115,7 @@ def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation
 
 
 def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transformations=None, seed=None, preference_loop_closure=None,
-                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False, kernel=None):
+                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False, kernel=None, keypoints=None):
     """[O3D] multiway registration of a rig: pcds[0] is the master.  Not in the reference, whose calibration is the star alone
     (data.py:137-147); opt-in through DataProcessor(multiway=True).  -> the sub -> master 4x4 list in the form
     DataProcessor.registration_transformations holds (and the optimised PoseGraph with return_pose_graph).
@@ -109,7 +130,8 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
     preference_loop_closure=None: mu = (median correspondence count of the uncertain edges) * voxel_size^2 -- a closure goes when
     it disagrees with the rest by more than about one voxel rms over its matched points ("Multiway registration").
     kernel: a robust loss for every pairwise ICP (star and loop edges); the loop edges then go one by one through ops.icp, as
-    ops.icp_batch runs the culled iteration kernels, which take no weights."""
+    ops.icp_batch runs the culled iteration kernels, which take no weights.
+    keypoints: passed to every execute_global_registration (None: every down-sampled point is matched)."""
     from .. import ops
     reg = o3d.pipelines.registration
     threshold = 100                                                       # execute_point_to_plane_registration's
@@ -118,7 +140,7 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
     star = [np.eye(4)]
     for i in range(1, S):
         if initial_transformations is None:
-            init = execute_global_registration(pcds[0], pcds[i], voxel_size, seed=seed)
+            init = execute_global_registration(pcds[0], pcds[i], voxel_size, seed=seed, keypoints=keypoints)
             if init is None:
                 raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)")
         else:

@@ -126,6 +126,17 @@ def main():
            noise=int((lab < 0).sum().item()))
     ms, kr = timed(lambda: ops.remove_radius_outlier(fc, 10, 20.0), reps=5, warm=2)
     report("remove_radius_outlier nb_points=10 radius=20 on the frame cloud", ms, n=int(fc.shape[0]), kept=int(kr.shape[0]))
+    # ISS keypoints with Open3D's default radii (6 x / 4 x the cloud's resolution) on the same cloud: the passes alone, then the whole call
+    res = float(ops.model_resolution(fc).item())
+    ms, sal = timed(lambda: ops.iss_saliency(fc, 6.0 * res), reps=5, warm=2)
+    report("iss_saliency salient_radius=6 x resolution on the frame cloud", ms, n=int(fc.shape[0]), resolution=round(res, 3),
+           nonzero=int((sal != 0).sum().item()))
+    ms, kp = timed(lambda: ops.iss_nonmax(fc, sal, 4.0 * res), reps=5, warm=2)
+    report("iss_nonmax non_max_radius=4 x resolution on the frame cloud", ms, n=int(fc.shape[0]), keypoints=int(kp.shape[0]))
+    ms, _ = timed(lambda: ops.model_resolution(fc), reps=5, warm=2)
+    report("model_resolution on the frame cloud", ms, n=int(fc.shape[0]))
+    ms, kp = timed(lambda: ops.iss_keypoints(fc), reps=5, warm=2)
+    report("iss_keypoints default radii on the frame cloud (resolution + both passes on one grid)", ms, n=int(fc.shape[0]), keypoints=int(kp.shape[0]))
 
     # ---- neighbour search (KDTreeFlann) on the frame cloud: index build, self-query knn, the hybrid search of the bench's
     # estimate_normals setting beside estimate_normals itself (the same selection plus covariance and eigen-solve), one radius search at
