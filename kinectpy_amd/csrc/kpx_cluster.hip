@@ -216,9 +216,9 @@ __global__ __launch_bounds__(kClusterThreads) void iss_saliency_kernel(const Gri
         });
         double sal = 0.0;
         if (m >= min_nb && m > 0) {
-            const double im = (double)m;
-            const double mx = sx / im, my = sy / im, mz = sz / im;
-            const double c[6] = { sxx / im - mx * mx, sxy / im - mx * my, sxz / im - mx * mz, syy / im - my * my, syz / im - my * mz, szz / im - mz * mz };
+            const double sums[9] = { sx, sy, sz, sxx, sxy, sxz, syy, syz, szz };
+            double c[6];
+            cov6_from_moments(sums, (double)m, c);
             bool zero = true;
 #pragma unroll
             for (int k = 0; k < 6; ++k) zero = zero && fabs(c[k]) <= kIssZero;

@@ -2,7 +2,7 @@
 //   compute_fpfh_feature(KDTreeSearchParamHybrid)                        preprocessing/registration.py:15-20
 //   registration_ransac_based_on_feature_matching(..., mutual_filter,    preprocessing/registration.py:50-57
 //       PointToPoint(False), 3, [EdgeLength(0.95), Distance(thr)], RANSACConvergenceCriteria(250000, 0.999))
-// Kernels: hybrid neighbour lists (exact grid search, ascending (d2, idx)), SPFH histograms, FPFH weighting,
+// Kernels: hybrid neighbour lists (NbrListOp through the shared exact grid search of kpx_gridknn.h), SPFH histograms, FPFH weighting,
 // 33-D feature nearest neighbour (LDS-tiled fp64, the oracle's accumulation order), batched RANSAC hypotheses
 // (Philox sampling, 3-point Umeyama, edge-length + distance checkers), validation by an exact radius-limited
 // nearest-neighbour count on the target grid, inlier ratio of the correspondence set.  The sequential
@@ -17,32 +17,26 @@ namespace kpx {
 constexpr double kSentinelF = 1e300;
 
 // ---- neighbour lists ------------------------------------------------------------------------------------------
-// Wave per query (wave_knn_select, kpx_gridknn.h): the selected neighbours are written in candidate order, except that
-// slot 0 receives the smallest (d^2, index) -- the entry the feature kernels skip as "the point itself".  The feature
-// sums do not depend on the order of the other slots beyond rounding.
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void nbr_list_wave_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                                                                   const float *__restrict__ spts, const int32_t *__restrict__ sidx,
-                                                                   int64_t n, int k, int cap, double r2, int32_t *__restrict__ nbr,
-                                                                   double *__restrict__ d2, int32_t *__restrict__ cnt,
-                                                                   int32_t *__restrict__ fb_list, int32_t *__restrict__ fb_count)
-{
-    extern __shared__ __align__(16) double lds[];
-    __shared__ uint32_t run_s0[WAVES][64];
-    __shared__ int32_t run_off[WAVES][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t *posbase = reinterpret_cast<uint32_t *>(lds + (size_t)WAVES * cap);
-    __shared__ __align__(16) uint32_t knn_hist[WAVES][kKnnBuckets];
-    const WaveKnnScratch sc{ lds + (size_t)wave * cap, posbase + (size_t)wave * cap, run_s0[wave], run_off[wave], cap, knn_hist[wave] };
-    const GridParams g = *gp;
-    for (int64_t s = (int64_t)blockIdx.x * WAVES + wave; s < n; s += (int64_t)gridDim.x * WAVES) {
-        const double q[3] = { (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2] };
+// The hybrid neighbour lists nbr / d2 [n][k] and cnt [n], by original index, as an operator of knn_wave_kernel / knn_heap_kernel
+// (kpx_gridknn.h); unused slots hold -1 / 0.0.
+// Wave form: the selected neighbours are written in candidate order, except that slot 0 receives the smallest (d^2, index) -- the
+// entry the feature kernels skip as "the point itself".  The feature sums do not depend on the order of the other slots beyond
+// rounding.  Heap form: ascending (d^2, index), by heap-sort extraction.
+struct NbrListOp {
+    static constexpr bool kPos = true;
+    using Heap = HeapDI;
+    const int32_t *sidx;
+    int k;
+    double r2;
+    int32_t *nbr;
+    double *d2;
+    int32_t *cnt;
+    __device__ double r2max(bool) const { return r2; }
+    __device__ void defer(int64_t) const {}
+    __device__ void wave(const WaveKnnScratch &sc, const WaveKnnResult &res, int64_t s, const float *) const
+    {
+        const int lane = threadIdx.x & 63;
         const int64_t me = sidx[s];
-        WaveKnnResult res;
-        if (!wave_knn_select<true>(g, cell_start, spts, q, k, r2, sc, res)) {
-            if (lane == 0) fb_list[atomicAdd(fb_count, 1)] = (int32_t)s;
-            continue;
-        }
         const int32_t idx_thr = wave_knn_tie_threshold(sc, res, sidx);
         int base = 0;
         double bd = INFINITY;                                  // smallest (d^2, index) written by this lane, and its slot
@@ -78,26 +72,9 @@ __global__ __launch_bounds__(WAVES * 64) void nbr_list_wave_kernel(const GridPar
             }
         }
         for (int t = res.kk + lane; t < k; t += 64) { nbr[me * k + t] = -1; d2[me * k + t] = 0.0; }
-        wave_lds_fence();
     }
-}
-
-// Thread per query with a (d^2, index) heap; list != NULL: only the queries the wave kernel could not hold.
-__global__ void nbr_list_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                                const float *__restrict__ spts, const int32_t *__restrict__ sidx, int64_t n, int k, double r2,
-                                int32_t *__restrict__ nbr, double *__restrict__ d2, int32_t *__restrict__ cnt,
-                                const int32_t *__restrict__ list, const int32_t *__restrict__ list_count, double *__restrict__ gheap, int32_t *__restrict__ gix)
-{
-    // gheap / gix != NULL (max_nn beyond what LDS holds): the thread's (d^2, index) heap lives in the workspace
-    extern __shared__ __align__(16) double lds[];
-    const int64_t total = list ? (int64_t)*list_count : n;
-    const GridParams g = *gp;
-    int32_t *ilds = reinterpret_cast<int32_t *>(lds + (size_t)k * blockDim.x);
-    const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = list ? (int64_t)list[e] : e;
-        HeapDI heap{ gheap ? gheap + gt : lds + threadIdx.x, gheap ? gix + gt : ilds + threadIdx.x, gheap ? (int)(gridDim.x * blockDim.x) : (int)blockDim.x, k, 0 };
-        grid_knn_scan(g, cell_start, spts, sidx, (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2], r2, heap);
+    __device__ void heap(int64_t s, HeapDI &heap) const
+    {
         const int64_t me = sidx[s];
         const int m = heap.sz;
         cnt[me] = m;
@@ -119,7 +96,7 @@ __global__ void nbr_list_kernel(const GridParams *__restrict__ gp, const uint32_
         }
         for (int t = m; t < k; ++t) { nbr[me * k + t] = -1; d2[me * k + t] = 0.0; }
     }
-}
+};
 
 // ---- SPFH / FPFH ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int bin11(double x)
@@ -328,19 +305,6 @@ __global__ __launch_bounds__(256) void feature_nn_merge_kernel(const double *__r
 }
 
 // ---- RANSAC hypotheses -----------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // A triple whose points are (nearly) collinear -- a correspondence drawn twice, or points on a line -- gives a rank-1 S: the
 // rotation about the line is not determined, and any construction of it is arbitrary.  Such triples are rejected like a failed
 // checker, on either side (arithmetic contract; the CPU oracle restates the test):
@@ -530,32 +494,15 @@ static int knn_lists(const float *pts, int64_t n, double radius, int k, Arena &a
     *d2 = a.get<double>(nn * k);
     *cnt = a.get<int32_t>(nn);
     int32_t *fb_list = a.get<int32_t>(nn + 1);
-    const bool global_heap = k > KPX_NORMALS_LDS_NN;              // the fall-back heaps in the workspace (<= 256 MB of distances)
-    int heap_blocks = 256;
-    while (global_heap && heap_blocks > 8 && (size_t)heap_blocks * 64 * (size_t)k * sizeof(double) > ((size_t)256 << 20)) heap_blocks >>= 1;
-    double *gheap = global_heap ? a.get<double>((size_t)heap_blocks * 64 * (size_t)k) : nullptr;
-    int32_t *gix = global_heap ? a.get<int32_t>((size_t)heap_blocks * 64 * (size_t)k) : nullptr;
+    const KnnHeaps hp = knn_heaps_carve(a, k, KPX_NORMALS_LDS_NN, true, k <= 48 ? 128 : 64);
     if (a.dry) return KPX_OK;
     KPX_ARENA_CHECK(a);
-    int32_t *fb_count = fb_list + nn;
-    const int threads = global_heap ? 64 : (k <= 48 ? 128 : 64);
-    const size_t lds = global_heap ? 0 : (size_t)k * threads * (sizeof(double) + sizeof(int32_t));
-    static bool attr_set = false;
-    if (!attr_set) {
-        KPX_HIP(hipFuncSetAttribute((const void *)nbr_list_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        KPX_HIP(hipFuncSetAttribute((const void *)nbr_list_wave_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
-    KPX_HIP(hipMemsetAsync(fb_count, 0, sizeof(int32_t), st));
     // pass 1: one wave per query, 512- or 1024-candidate buffer; pass 2: the queries that did not fit, thread-per-query heap walk
-    const int cap = k <= 48 ? 512 : 1024;
-    const bool wave_pass = k <= 512;                               // (beyond, the 1024-candidate buffer cannot hold a neighbourhood: every query takes the heap walk)
-    if (wave_pass)
-        hipLaunchKernelGGL(nbr_list_wave_kernel<4>, dim3((unsigned)(cdiv(n, 4) > 8192 ? 8192 : cdiv(n, 4))), dim3(256),
-                           (size_t)4 * cap * (sizeof(double) + sizeof(uint32_t)), st, g->params, g->cell_start, g->sorted_pts, g->sorted_idx, n, k, cap,
-                           radius * radius, *nbr, *d2, *cnt, fb_list, fb_count);
-    hipLaunchKernelGGL(nbr_list_kernel, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g->params, g->cell_start, g->sorted_pts, g->sorted_idx, n, k,
-                       radius * radius, *nbr, *d2, *cnt, wave_pass ? fb_list : (const int32_t *)nullptr, wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
+    // (k > 512: the 1024-candidate buffer cannot hold a neighbourhood -- every query takes the heap walk)
+    rc = knn_cascade<NbrListOp>(*g, k, NbrListOp{ g->sorted_idx, k, radius * radius, *nbr, *d2, *cnt }, 0, n, nullptr, nullptr,
+                                { knn_wave_pass<NbrListOp, 4>(k <= 48 ? 512 : 1024, 8192, fb_list, k <= 512) }, g->spare,
+                                knn_heap_pass<NbrListOp>(), hp, st);
+    if (rc) return rc;
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -1,5 +1,9 @@
-// kpx_gridknn.h -- device-side pieces of the exact grid neighbour search shared by kpx_knn.hip and kpx_fpfh.hip.
+// kpx_gridknn.h -- the exact grid neighbour search shared by kpx_knn.hip, kpx_fpfh.hip, kpx_cluster.hip and kpx_search.hip: the
+// device primitives (heaps, ring walk, radius visitor, wave-per-query selection) and, at the end, the ONE wave-per-query kernel, the
+// ONE thread-per-query heap kernel and the host cascade that SOR, normals / covariances and the neighbour lists run them through.
 #pragma once
+#include <initializer_list>
+
 #include "kpx_internal.h"
 
 namespace kpx {
@@ -14,6 +18,7 @@ __device__ __forceinline__ int cell_coord(double v, double org, double h, int di
 // values only (SOR): slot e of this thread lives at h[e * stride]
 struct HeapD {
     double *h; int stride, k, sz;
+    static __device__ HeapD make(double *h, int32_t *, int stride, int k) { return HeapD{ h, stride, k, 0 }; }
     __device__ bool full() const { return sz == k; }
     __device__ double worst() const { return h[0]; }
     __device__ void push(double d, int)
@@ -43,6 +48,7 @@ struct HeapD {
 // (d2, idx) pairs ordered lexicographically (normals: the neighbour identities matter)
 struct HeapDI {
     double *h; int32_t *ix; int stride, k, sz;
+    static __device__ HeapDI make(double *h, int32_t *ix, int stride, int k) { return HeapDI{ h, ix, stride, k, 0 }; }
     __device__ bool full() const { return sz == k; }
     __device__ double worst() const { return h[0]; }
     static __device__ bool less(double a, int32_t ai, double b, int32_t bi) { return a < b || (a == b && ai < bi); }
@@ -171,22 +177,16 @@ __device__ __forceinline__ void grid_radius_scan(const GridParams &g, const uint
         }
 }
 
-// ---- wave-per-query neighbour selection (SOR, normals, FPFH neighbour lists) -------------------------------------------------------
+// ---- wave-per-query neighbour selection (knn_wave_kernel below: SOR, normals / covariances, the hybrid neighbour lists) ----------------
 // The lanes gather the squared distances (AC3, fp64) of the points of the (2r+1)^3 cell block around the query into
 // LDS (every (x, y) column of the block is one contiguous run of the cell-sorted points: 64 columns at a time, lane c
 // looks up run c, a wave scan places the runs, all candidates of the chunk are fetched together and the ones that pass
-// d^2 <= tau, d^2 < r2max are appended by ballot + popcount).  The k-th smallest is found by bisection on the IEEE
-// bit patterns (d^2 >= 0: the patterns order like the values; one ballot + popcount per 64 candidates and step) and
-// the search ends when that value lies inside the distance the block covers -- the termination rule of the ring walk
-// of kpx_gridknn.h.  Otherwise the k-th candidate found so far bounds the true k-th distance: the candidates are
+// d^2 <= tau, d^2 < r2max are appended by ballot + popcount).  The k-th smallest is found by counting the IEEE bit
+// patterns into buckets (d^2 >= 0: the patterns order like the values; wave_kth_pattern below) and the search ends
+// when that value lies inside the distance the block covers -- the termination rule of the ring walk above
+// (grid_knn_scan).  Otherwise the k-th candidate found so far bounds the true k-th distance: the candidates are
 // gathered again, only those within it, from the block that covers it.  When the buffer fills, gathering stops; the
 // cap candidates held are still real points, so their k-th smallest is a valid bound too.
-__device__ __forceinline__ unsigned long long wave_all_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-    return v;
-}
 __device__ __forceinline__ unsigned long long wave_all_max_u64(unsigned long long v)
 {
 #pragma unroll
@@ -418,30 +418,6 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
         const int kk = m < k ? m : k;
         // the threshold of the kk smallest patterns
         unsigned long long lo = 0ull;
-#ifdef KPX_KNN_BISECT
-        {                                                       // (until round 5: bisection between the smallest and the largest pattern)
-            unsigned long long hi = 0ull;
-            lo = ~0ull;
-            for (int t = lane; t < m; t += 64) {
-                const unsigned long long p = (unsigned long long)__double_as_longlong(sc.vals[t]);
-                lo = p < lo ? p : lo; hi = p > hi ? p : hi;
-            }
-            lo = wave_all_min_u64(lo); hi = wave_all_max_u64(hi);
-            if (m <= k) lo = hi;                                // everything gathered is selected: no search needed
-            if (m == 0) { lo = hi = 0ull; }
-            while (lo < hi) {
-                const unsigned long long mid = lo + ((hi - lo) >> 1);
-                int cnt = 0;
-                for (int t0 = 0; t0 < m; t0 += 64) {
-                    const int t = t0 + lane;
-                    const bool le = t < m && (unsigned long long)__double_as_longlong(sc.vals[t]) <= mid;
-                    cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
-                }
-                if (cnt == kk) { lo = hi = mid; break; }       // the set is determined
-                if (cnt > kk) hi = mid; else lo = mid + 1;
-            }
-        }
-#else
         if (m > k) lo = wave_kth_pattern(sc.vals, m, kk, sc.hist);             // by counting (above)
         else if (m > 0) {                                       // everything gathered is selected: the largest pattern
             for (int t = lane; t < m; t += 64) {
@@ -450,7 +426,6 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
             }
             lo = wave_all_max_u64(lo);
         }
-#endif
         double top = 0.0;
         int cnt = 0;
         for (int t0 = 0; t0 < m; t0 += 64) {
@@ -515,6 +490,133 @@ __device__ __forceinline__ bool wave_knn_is_selected(const WaveKnnScratch &sc, c
     if (p > res.thr) return false;
     if (p < topp || res.cnt == res.kk) return true;
     return p == topp && sidx[sc.pos[t]] <= idx_thr;
+}
+
+// ---- the two query kernels and their host cascade ------------------------------------------------------------------------------------
+// An operator is a small struct Op, passed by value:
+//     Op::kPos                    the wave form keeps the candidates' sorted positions (identities matter); false: values only, no `pos`
+//                                 half is carved or touched
+//     Op::Heap                    HeapD or HeapDI; with kPos the ring walk is handed op.sidx and the heap holds original indices
+//     op.r2max(heap_walk)         the hybrid search's squared radius in the convention of wave_knn_select / grid_knn_scan
+//     op.defer(s)                 lane 0, when the wave form hands query s to the next pass
+//     op.wave(sc, res, s, spts)   the whole wave, with the selected set of query s in LDS
+//     op.heap(s, heap)            one thread, with the filled heap of query s (heap_alt: a second consumer, chosen by the host)
+// Queries are cell-sorted positions: [q0, q1), or -- in_list != NULL -- in_list[0 .. *in_count), the ones an earlier pass listed.
+template <class Op, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void knn_wave_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
+                                                              const float *__restrict__ spts, int64_t q0, int64_t q1, int k, int cap, Op op,
+                                                              const int32_t *__restrict__ in_list, const int32_t *__restrict__ in_count,
+                                                              int32_t *__restrict__ fb_list, int32_t *__restrict__ fb_count)
+{
+    extern __shared__ __align__(16) double lds[];                // WAVES x cap distances, then (kPos) WAVES x cap positions
+    __shared__ uint32_t run_s0[WAVES][64];
+    __shared__ int32_t run_off[WAVES][64];
+    __shared__ __align__(16) uint32_t knn_hist[WAVES][kKnnBuckets];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t *pos = nullptr;
+    if constexpr (Op::kPos) pos = reinterpret_cast<uint32_t *>(lds + (size_t)WAVES * cap) + (size_t)wave * cap;
+    const WaveKnnScratch sc{ lds + (size_t)wave * cap, pos, run_s0[wave], run_off[wave], cap, knn_hist[wave] };
+    const GridParams g = *gp;
+    const int64_t nq = in_list ? (int64_t)*in_count : q1 - q0;
+    for (int64_t e = (int64_t)blockIdx.x * WAVES + wave; e < nq; e += (int64_t)gridDim.x * WAVES) {
+        const int64_t s = in_list ? (int64_t)in_list[e] : q0 + e;
+        const double q[3] = { (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2] };
+        WaveKnnResult res;
+        if (!wave_knn_select<Op::kPos>(g, cell_start, spts, q, k, op.r2max(false), sc, res)) {      // does not fit the buffer
+            if (lane == 0) { fb_list[atomicAdd(fb_count, 1)] = (int32_t)s; op.defer(s); }
+            continue;
+        }
+        op.wave(sc, res, s, spts);
+        wave_lds_fence();
+    }
+}
+// Exact ring walk, one thread per query (queries in cell order: neighbouring threads walk neighbouring cells) with a k-heap: in LDS
+// (layout [slot][thread]), or -- gheap != NULL, k beyond what LDS holds -- in the workspace, strided by the grid's thread count.
+template <class Op, bool ALT>
+__global__ void knn_heap_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start, const float *__restrict__ spts,
+                                int64_t q0, int64_t q1, int k, Op op, const int32_t *__restrict__ list, const int32_t *__restrict__ list_count,
+                                double *__restrict__ gheap, int32_t *__restrict__ gix)
+{
+    extern __shared__ __align__(16) double lds[];
+    const GridParams g = *gp;
+    const int64_t total = list ? (int64_t)*list_count : q1 - q0;
+    int32_t *ilds = reinterpret_cast<int32_t *>(lds + (size_t)k * blockDim.x);
+    const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = list ? (int64_t)list[t] : q0 + t;
+        typename Op::Heap heap = Op::Heap::make(gheap ? gheap + gt : lds + threadIdx.x, gheap ? gix + gt : ilds + threadIdx.x,
+                                                gheap ? (int)(gridDim.x * blockDim.x) : (int)blockDim.x, k);
+        grid_knn_scan(g, cell_start, spts, Op::kPos ? op.sidx : (const int32_t *)nullptr, (double)spts[3 * s], (double)spts[3 * s + 1],
+                      (double)spts[3 * s + 2], op.r2max(true), heap);
+        if constexpr (ALT) op.heap_alt(s, heap);
+        else op.heap(s, heap);
+    }
+}
+
+// The heap pass's launch shape and, beyond lds_k, its heaps in the workspace (fewer blocks as k grows: <= 256 MB of distances).
+struct KnnHeaps {
+    bool global;
+    int blocks, threads;
+    size_t lds;
+    double *gheap;
+    int32_t *gix;
+};
+static inline KnnHeaps knn_heaps_carve(Arena &a, int k, int lds_k, bool with_idx, int lds_threads)
+{
+    KnnHeaps hp{ k > lds_k, 256, lds_threads, 0, nullptr, nullptr };
+    if (hp.global) {
+        while (hp.blocks > 8 && (size_t)hp.blocks * 64 * (size_t)k * sizeof(double) > ((size_t)256 << 20)) hp.blocks >>= 1;
+        hp.threads = 64;
+        hp.gheap = a.get<double>((size_t)hp.blocks * 64 * (size_t)k);
+        if (with_idx) hp.gix = a.get<int32_t>((size_t)hp.blocks * 64 * (size_t)k);
+    } else {
+        hp.lds = (size_t)k * hp.threads * (sizeof(double) + (with_idx ? sizeof(int32_t) : 0));
+    }
+    return hp;
+}
+// dynamic LDS beyond 64 KB is granted per kernel: once per instantiation
+template <auto Kernel, int Bytes> int knn_lds_limit()
+{
+    static const hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Bytes);
+    if (e != hipSuccess) return fail(KPX_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+    return KPX_OK;
+}
+template <class Op> struct KnnWavePass {
+    void (*kernel)(const GridParams *, const uint32_t *, const float *, int64_t, int64_t, int, int, Op, const int32_t *, const int32_t *, int32_t *, int32_t *);
+    int rc, waves, cap, max_blocks;
+    int32_t *fb_list;                      // what this pass cannot hold, for the next one
+    bool on;
+};
+template <class Op, int WAVES> KnnWavePass<Op> knn_wave_pass(int cap, int max_blocks, int32_t *fb_list, bool on = true)
+{
+    return { knn_wave_kernel<Op, WAVES>, knn_lds_limit<knn_wave_kernel<Op, WAVES>, 96 * 1024>(), WAVES, cap, max_blocks, fb_list, on };
+}
+template <class Op> struct KnnHeapPass {
+    void (*kernel)(const GridParams *, const uint32_t *, const float *, int64_t, int64_t, int, Op, const int32_t *, const int32_t *, double *, int32_t *);
+    int rc;
+};
+template <class Op, bool ALT = false> KnnHeapPass<Op> knn_heap_pass() { return { knn_heap_kernel<Op, ALT>, knn_lds_limit<knn_heap_kernel<Op, ALT>, 160 * 1024>() }; }
+// The cascade: every enabled wave pass searches what came in (all of [q0, q1), or `list`) and lists what it cannot hold for the next
+// one; the heap pass takes whatever is left.  counters: one cleared word per wave pass (Grid::spare).
+template <class Op>
+int knn_cascade(const Grid &g, int k, const Op &op, int64_t q0, int64_t q1, const int32_t *list, const int32_t *count,
+                std::initializer_list<KnnWavePass<Op>> passes, int32_t *counters, const KnnHeapPass<Op> &heap, const KnnHeaps &hp, hipStream_t st)
+{
+    const int64_t nq = q1 - q0;
+    if (nq <= 0) return KPX_OK;
+    for (const KnnWavePass<Op> &p : passes) {
+        int32_t *fb_count = counters++;
+        if (p.rc) return p.rc;
+        if (!p.on) continue;
+        const int64_t blocks = cdiv(nq, p.waves) > p.max_blocks ? p.max_blocks : cdiv(nq, p.waves);
+        hipLaunchKernelGGL(p.kernel, dim3((unsigned)blocks), dim3(64 * p.waves), (size_t)p.waves * p.cap * (sizeof(double) + (Op::kPos ? sizeof(uint32_t) : 0)),
+                           st, g.params, g.cell_start, g.sorted_pts, q0, q1, k, p.cap, op, list, count, p.fb_list, fb_count);
+        list = p.fb_list; count = fb_count;
+    }
+    if (heap.rc) return heap.rc;
+    hipLaunchKernelGGL(heap.kernel, dim3(hp.blocks), dim3(hp.threads), hp.lds, st, g.params, g.cell_start, g.sorted_pts, q0, q1, k, op, list, count,
+                       hp.gheap, hp.gix);
+    return KPX_OK;
 }
 
 }  // namespace kpx

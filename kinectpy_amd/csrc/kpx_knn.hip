@@ -1,9 +1,11 @@
 // kpx_knn.hip -- exact neighbour searches on a uniform grid:
 //   a8  PointCloud.remove_statistical_outlier (filtering.py:24, floor_removal.py:73, utils/processing.py:309)
-//       estimate_normals(KDTreeSearchParamHybrid) (preprocessing/registration.py:9-13)
-// One thread per query walks Chebyshev rings of cells around its own cell and keeps the k smallest
-// squared distances in a per-thread max-heap held in LDS (layout [slot][thread]: bank-conflict free
-// when the threads of a wave touch the same slot).  The search is exact: a ring loop stops only once
+//       estimate_normals(KDTreeSearchParamHybrid) (preprocessing/registration.py:9-13), estimate_covariances
+// The grid build, SOR's block-per-64-queries pass 0 and statistics, and the operators SorOp and MomentsOp: what SOR and the normals do
+// with a query's k nearest.  The search itself is shared (kpx_gridknn.h): knn_wave_kernel -- a wave per query selects the k smallest
+// squared distances of the surrounding cell block in LDS -- and, for what does not fit its buffer, knn_heap_kernel -- one thread per
+// query walks Chebyshev rings of cells and keeps the k smallest in a per-thread max-heap (layout [slot][thread]: bank-conflict free
+// when the threads of a wave touch the same slot) -- run in that order by knn_cascade.  Both are exact: a search stops only once
 // the k-th best distance is below the distance to the boundary of the covered cube.
 // Squared distance (contract AC3): d2 = fma(dz,dz, fma(dy,dy, dx*dx)), differences in fp64.
 #include <hipcub/hipcub.hpp>
@@ -234,33 +236,21 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
 }
 
 // ---- a8 SOR ------------------------------------------------------------------------------------------
-// One WAVE per query; the mean needs no identities: sum of sqrt over the selected set, ties at the k-th value counted
-// k - (#smaller) times.  Queries whose candidates exceed the LDS buffer are listed for the next pass.
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void sor_wave_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                                                              const float *__restrict__ spts, const int32_t *__restrict__ sidx,
-                                                              int64_t q0, int64_t q1, int k, int cap, double *__restrict__ avg,
-                                                              const int32_t *__restrict__ in_list, const int32_t *__restrict__ in_count,
-                                                              int32_t *__restrict__ fb_list, int32_t *__restrict__ fb_count)
-{
-    // queries = the cell-sorted positions [q0, q1) (all of them: 0, n; a slab of the grid order for kpx_sor_partial).
-    // sidx != NULL: avg is indexed by the caller's point index; sidx == NULL: by sorted position relative to q0.
-    extern __shared__ __align__(16) double lds[];
-    __shared__ uint32_t run_s0[WAVES][64];
-    __shared__ int32_t run_off[WAVES][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __shared__ __align__(16) uint32_t knn_hist[WAVES][kKnnBuckets];
-    const WaveKnnScratch sc{ lds + (size_t)wave * cap, nullptr, run_s0[wave], run_off[wave], cap, knn_hist[wave] };
-    const GridParams g = *gp;
-    const int64_t nq = in_list ? (int64_t)*in_count : q1 - q0;   // in_list: the queries an earlier pass could not hold
-    for (int64_t e = (int64_t)blockIdx.x * WAVES + wave; e < nq; e += (int64_t)gridDim.x * WAVES) {
-        const int64_t s = in_list ? (int64_t)in_list[e] : q0 + e;
-        const double q[3] = { (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2] };
-        WaveKnnResult res;
-        if (!wave_knn_select<false>(g, cell_start, spts, q, k, INFINITY, sc, res)) {
-            if (lane == 0) fb_list[atomicAdd(fb_count, 1)] = (int32_t)s;
-            continue;
-        }
+// The mean distance to the k nearest, as an operator of knn_wave_kernel / knn_heap_kernel (kpx_gridknn.h).  The mean needs no
+// identities: sum of sqrt over the selected set, ties at the k-th value counted k - (#smaller) times.
+// queries = the cell-sorted positions [q0, q1) (all of them: 0, n; a slab of the grid order for kpx_sor_partial).
+// sidx != NULL: avg is indexed by the caller's point index; sidx == NULL: by sorted position relative to q0.
+struct SorOp {
+    static constexpr bool kPos = false;
+    using Heap = HeapD;
+    const int32_t *sidx;
+    int64_t q0;
+    double *avg;
+    __device__ double r2max(bool heap_walk) const { return heap_walk ? -1.0 : INFINITY; }      // plain kNN
+    __device__ void defer(int64_t) const {}
+    __device__ void wave(const WaveKnnScratch &sc, const WaveKnnResult &res, int64_t s, const float *) const
+    {
+        const int lane = threadIdx.x & 63;
         double sum = 0.0;
         for (int t = lane; t < res.m; t += 64) {
             const double d = sc.vals[t];
@@ -270,9 +260,14 @@ __global__ __launch_bounds__(WAVES * 64) void sor_wave_kernel(const GridParams *
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
         const double total = sum - (double)(res.cnt - res.kk) * sqrt(res.top);      // ties beyond the k-th slot
         if (lane == 0) avg[sidx ? (int64_t)sidx[s] : s - q0] = res.kk > 0 ? total / (double)res.kk : -1.0;
-        wave_lds_fence();
     }
-}
+    __device__ void heap(int64_t s, const HeapD &heap) const
+    {
+        double sum = 0.0;
+        for (int e = 0; e < heap.sz; ++e) sum += sqrt(heap.h[e * heap.stride]);
+        avg[sidx ? (int64_t)sidx[s] : s - q0] = heap.sz > 0 ? sum / (double)heap.sz : -1.0;
+    }
+};
 
 // ---- a8 SOR, the queries of a cell together: a BLOCK per 64 cell-sorted queries ----------------------------------------------------------
 // The wave-per-query kernel above re-gathers the 27-cell block for every query -- binary search over the cell runs, loads, 64-lane
@@ -581,28 +576,6 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
     }
 }
 
-// Exact ring walk, one thread per query (queries in cell order: neighbouring threads walk neighbouring cells).
-// list != NULL: only the queries list[0 .. *list_count) (the wave kernel's overflow list).
-__global__ void sor_knn_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                               const float *__restrict__ spts, const int32_t *__restrict__ sidx, int64_t q0, int64_t q1, int k,
-                               double *__restrict__ avg, const int32_t *__restrict__ list, const int32_t *__restrict__ list_count,
-                               double *__restrict__ gheap)
-{
-    // gheap != NULL (k beyond what LDS holds): the thread's heap lives in the workspace, strided by the grid's thread count
-    extern __shared__ __align__(16) double lds[];
-    const GridParams g = *gp;
-    const int64_t total = list ? (int64_t)*list_count : q1 - q0;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = list ? (int64_t)list[t] : q0 + t;
-        HeapD heap{ gheap ? gheap + (size_t)blockIdx.x * blockDim.x + threadIdx.x : lds + threadIdx.x, gheap ? (int)(gridDim.x * blockDim.x) : (int)blockDim.x, k, 0 };
-        grid_knn_scan(g, cell_start, spts, (const int32_t *)nullptr, (double)spts[3 * s], (double)spts[3 * s + 1],
-                      (double)spts[3 * s + 2], -1.0, heap);
-        double sum = 0.0;
-        for (int e = 0; e < heap.sz; ++e) sum += sqrt(heap.h[e * heap.stride]);
-        avg[sidx ? (int64_t)sidx[s] : s - q0] = heap.sz > 0 ? sum / (double)heap.sz : -1.0;
-    }
-}
-
 // mean / std exactly as [O3D]: mean = sum(avg>0)/n ; std = sqrt(sum_{avg>0}(avg-mean)^2/(n-1))
 __global__ __launch_bounds__(256) void sor_sum_kernel(const double *__restrict__ avg, int64_t n, const double *__restrict__ stats,
                                                       int pass, double *__restrict__ part)
@@ -758,26 +731,14 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
     int32_t *fb_list = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     int32_t *fb_list2 = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     int32_t *fb_list0 = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
-    // k beyond the LDS heaps (KPX_SOR_LDS_K): the last pass's per-thread heaps live here (fewer blocks as k grows: <= 256 MB)
-    const bool global_heap = kk > KPX_SOR_LDS_K;
-    int heap_blocks = 256;
-    while (global_heap && heap_blocks > 8 && (size_t)heap_blocks * 64 * (size_t)kk * sizeof(double) > ((size_t)256 << 20)) heap_blocks >>= 1;
-    double *gheap = global_heap ? a.get<double>((size_t)heap_blocks * 64 * (size_t)kk) : nullptr;
+    // k beyond the LDS heaps (KPX_SOR_LDS_K): the last pass's per-thread heaps live in the workspace
+    const KnnHeaps hp = knn_heaps_carve(a, kk, KPX_SOR_LDS_K, false, sor_block_threads(kk));
     if (a.dry) return KPX_OK;
     KPX_ARENA_CHECK(a);
     if (d_avg) avg = d_avg;
     const int32_t *out_idx = full ? g.sorted_idx : nullptr;
     const int64_t nq = q1 - q0;
-    int32_t *fb_count = g.spare, *fb_count2 = g.spare + 1, *fb_count0 = g.spare + 2;       // cleared by the grid build
-    const int threads = sor_block_threads(kk);
-    const size_t lds = global_heap ? 0 : (size_t)kk * threads * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        KPX_HIP(hipFuncSetAttribute((const void *)sor_knn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        KPX_HIP(hipFuncSetAttribute((const void *)sor_wave_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        KPX_HIP(hipFuncSetAttribute((const void *)sor_wave_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
+    int32_t *fb_count0 = g.spare + 2;                             // cleared by the grid build; words 0 and 1: the cascade's passes
     {
         ProfScope prof(KPX_PROF_SOR_KNN, 12.0 * (double)n + 8.0 * (double)n, st);     // read points, write mean distances
         // pass 0: the queries of a cell together (sor_block_kernel<S>: a block per 64 queries, 64 x S candidates at most); what it cannot
@@ -801,24 +762,15 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
                                g.sorted_pts, out_idx, q0, q1, kk, kbuf, avg, fb_list0, fb_count0);
             list0 = fb_list0; count0 = fb_count0;
         }
-        // pass 1: one wave per query, 1024-candidate buffer (many waves per CU)
-        // (round 5: k beyond half a buffer skips the pass whose buffer cannot hold k candidates plus their surroundings -- the queries
-        // go on to the next one through the same lists)
-        const int cap1 = kk <= 32 ? 512 : 1024;               // small k: smaller buffers, more waves per CU
-        const bool pass1 = kk <= 512, pass2 = kk <= 4096;
-        if (nq > 0 && pass1)
-            hipLaunchKernelGGL(sor_wave_kernel<4>, dim3((unsigned)(cdiv(nq, 4) > (list0 ? 2048 : 8192) ? (list0 ? 2048 : 8192) : cdiv(nq, 4))), dim3(256), (size_t)4 * cap1 * 8, st,
-                               g.params, g.cell_start, g.sorted_pts, out_idx, q0, q1, kk, cap1, avg, list0, count0, fb_list, fb_count);
+        // pass 1: one wave per query, 512- or 1024-candidate buffer (small k: smaller buffers, more waves per CU); k beyond half a
+        // buffer skips the pass whose buffer cannot hold k candidates plus their surroundings -- the queries go on through the same lists
         // pass 2: the queries whose block did not fit (isolated points next to a dense sheet), 8192-candidate buffer
-        const int32_t *list1 = pass1 ? fb_list : list0, *count1 = pass1 ? fb_count : count0;      // what pass 2 searches: pass 1's leftovers, or its input
-        if (nq > 0 && pass2)
-            hipLaunchKernelGGL(sor_wave_kernel<1>, dim3(2048), dim3(64), (size_t)8192 * 8, st, g.params, g.cell_start, g.sorted_pts,
-                               out_idx, q0, q1, kk, 8192, avg, list1, count1, fb_list2, fb_count2);
         // pass 3: whatever is left: thread-per-query ring walk with a k-heap (in LDS; in the workspace for k > KPX_SOR_LDS_K)
-        const int32_t *list2 = pass2 ? fb_list2 : list1, *count2 = pass2 ? fb_count2 : count1;
-        if (nq > 0)
-            hipLaunchKernelGGL(sor_knn_kernel, dim3(global_heap ? heap_blocks : 256), dim3(global_heap ? 64 : threads), lds, st, g.params, g.cell_start, g.sorted_pts,
-                               out_idx, q0, q1, kk, avg, list2, count2, gheap);
+        rc = knn_cascade<SorOp>(g, kk, SorOp{ out_idx, q0, avg }, q0, q1, list0, count0,
+                                { knn_wave_pass<SorOp, 4>(kk <= 32 ? 512 : 1024, list0 ? 2048 : 8192, fb_list, kk <= 512),
+                                  knn_wave_pass<SorOp, 1>(8192, 2048, fb_list2, kk <= 4096) },
+                                g.spare, knn_heap_pass<SorOp>(), hp, st);
+        if (rc) return rc;
     }
     if (!full) {
         if (d_order) KPX_HIP(hipMemcpyAsync(d_order, g.sorted_idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -843,78 +795,41 @@ __device__ __forceinline__ void store_cov9(double *o, const double *cov)
     o[3] = cov[1]; o[4] = cov[3]; o[5] = cov[4];
     o[6] = cov[2]; o[7] = cov[4]; o[8] = cov[5];
 }
-// COV: write the neighbourhood covariance (estimate_covariances) to out_cov [n][9] instead of the normal; < 3 neighbours -> identity
+// nine raw moment sums and their count -> the normal (eigenvector of the smallest eigenvalue), or -- COV: estimate_covariances -- the
+// covariance to out_cov [n][9]; < 3 neighbours: (0, 0, 1) / the identity.  me: the query's original index.
 template <bool COV>
-__global__ void normals_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                               const float *__restrict__ spts, const int32_t *__restrict__ sidx, const float *__restrict__ pts,
-                               int64_t n, int k, double r2, float *__restrict__ normals, double *__restrict__ out_cov, const int32_t *__restrict__ list,
-                               const int32_t *__restrict__ list_count, double *__restrict__ gheap, int32_t *__restrict__ gix)
+__device__ __forceinline__ void moments_finish(const double sums[9], double m, int64_t me, float *__restrict__ normals, double *__restrict__ out_cov)
 {
-    // gheap / gix != NULL (max_nn beyond what LDS holds): the thread's (d^2, index) heap lives in the workspace
-    extern __shared__ __align__(16) double lds[];
-    const int64_t total = list ? (int64_t)*list_count : n;
-    const GridParams g = *gp;
-    int32_t *ilds = reinterpret_cast<int32_t *>(lds + (size_t)k * blockDim.x);
-    const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int gstride = (int)(gridDim.x * blockDim.x);
-    // one query per thread; list != NULL: only the queries list[0 .. *list_count) (the wave kernel's leftovers)
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = list ? (int64_t)list[t] : t;
-        HeapDI heap{ gheap ? gheap + gt : lds + threadIdx.x, gheap ? gix + gt : ilds + threadIdx.x, gheap ? gstride : (int)blockDim.x, k, 0 };
-        grid_knn_scan(g, cell_start, spts, sidx, (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2], r2, heap);
-        const int64_t me = sidx[s];
-        double nx = 0.0, ny = 0.0, nz = 1.0;
-        if (heap.sz >= 3) {
-            double c[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-            for (int e = 0; e < heap.sz; ++e) {
-                int64_t j = heap.ix[e * heap.stride];
-                double x = pts[3 * j], y = pts[3 * j + 1], z = pts[3 * j + 2];
-                c[0] += x; c[1] += y; c[2] += z;
-                c[3] += x * x; c[4] += x * y; c[5] += x * z; c[6] += y * y; c[7] += y * z; c[8] += z * z;
-            }
-            const double m = (double)heap.sz;
-#pragma unroll
-            for (int q = 0; q < 9; ++q) c[q] /= m;
-            double cov[6] = { c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2],
-                              c[6] - c[1] * c[1], c[7] - c[1] * c[2], c[8] - c[2] * c[2] };
-            if constexpr (COV) {
-                store_cov9(out_cov + 9 * me, cov);
-                continue;
-            }
-            double w[3], V[9];
-            sym3_eigen(cov, w, V);
-            nx = V[0]; ny = V[3]; nz = V[6];                       // eigenvector of the smallest eigenvalue
-            double nn = sqrt(nx * nx + ny * ny + nz * nz);
-            if (nn > 0.0) { nx /= nn; ny /= nn; nz /= nn; } else { nx = 0.0; ny = 0.0; nz = 1.0; }
-        }
-        if constexpr (COV) store_cov9(out_cov + 9 * me, nullptr);          // (< 3 neighbours)
-        else { normals[3 * me] = (float)nx; normals[3 * me + 1] = (float)ny; normals[3 * me + 2] = (float)nz; }
+    double cov[6], nrm[3] = { 0.0, 0.0, 1.0 };
+    const bool enough = m >= 3.0;
+    if (enough) cov6_from_moments(sums, m, cov);
+    if constexpr (COV) {
+        if (enough) store_cov9(out_cov + 9 * me, cov);
+        else store_cov9(out_cov + 9 * me, nullptr);
+    } else {
+        if (enough) sym3_smallest_axis(cov, nrm);
+        normals[3 * me] = (float)nrm[0]; normals[3 * me + 1] = (float)nrm[1]; normals[3 * me + 2] = (float)nrm[2];
     }
 }
-
-// One wave per query: wave_knn_select with identities, then the covariance of the selected neighbours.  Ties at the
-// k-th distance are resolved like the (d^2, index) heap of normals_kernel: the lowest original indices stay.
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void normals_wave_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
-                                                                  const float *__restrict__ spts, const int32_t *__restrict__ sidx,
-                                                                  int64_t n, int k, int cap, double r2, double *__restrict__ covbuf,
-                                                                  int32_t *__restrict__ fb_list, int32_t *__restrict__ fb_count)
-{
-    extern __shared__ __align__(16) double lds[];
-    __shared__ uint32_t run_s0[WAVES][64];
-    __shared__ int32_t run_off[WAVES][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t *posbase = reinterpret_cast<uint32_t *>(lds + (size_t)WAVES * cap);
-    __shared__ __align__(16) uint32_t knn_hist[WAVES][kKnnBuckets];
-    const WaveKnnScratch sc{ lds + (size_t)wave * cap, posbase + (size_t)wave * cap, run_s0[wave], run_off[wave], cap, knn_hist[wave] };
-    const GridParams g = *gp;
-    for (int64_t s = (int64_t)blockIdx.x * WAVES + wave; s < n; s += (int64_t)gridDim.x * WAVES) {
-        const double q[3] = { (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2] };
-        WaveKnnResult res;
-        if (!wave_knn_select<true>(g, cell_start, spts, q, k, r2, sc, res)) {
-            if (lane == 0) { fb_list[atomicAdd(fb_count, 1)] = (int32_t)s; covbuf[10 * s + 9] = -1.0; }
-            continue;
-        }
+// The raw moments of the hybrid neighbourhood, as an operator of knn_wave_kernel / knn_heap_kernel (kpx_gridknn.h).  Wave form: the
+// sums of the selected neighbours go to covbuf [n][10] (nine sums, count; count < 0: the query was handed to the heap walk) -- the 3x3
+// eigen-problem is serial work and runs one thread per query in normals_eigen_kernel.  Ties at the k-th distance are resolved like the
+// (d^2, index) heap of the heap form: the lowest original indices stay.  Heap form: sums in heap-slot order, finished in place
+// (heap: normals, heap_alt: covariances).
+struct MomentsOp {
+    static constexpr bool kPos = true;
+    using Heap = HeapDI;
+    const int32_t *sidx;
+    const float *pts;
+    double r2;
+    double *covbuf;
+    float *normals;
+    double *out_cov;
+    __device__ double r2max(bool) const { return r2; }
+    __device__ void defer(int64_t s) const { covbuf[10 * s + 9] = -1.0; }
+    __device__ void wave(const WaveKnnScratch &sc, const WaveKnnResult &res, int64_t s, const float *__restrict__ spts) const
+    {
+        const int lane = threadIdx.x & 63;
         const int32_t idx_thr = wave_knn_tie_threshold(sc, res, sidx);
         double c[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
         for (int t = lane; t < res.m; t += 64) {
@@ -929,18 +844,29 @@ __global__ __launch_bounds__(WAVES * 64) void normals_wave_kernel(const GridPara
         for (int a9 = 0; a9 < 9; ++a9)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) c[a9] += __shfl_xor(c[a9], o, 64);
-        // the 3x3 eigen-problem is serial work: it runs one thread per query in normals_eigen_kernel
         if (lane == 0) {
             double *o = covbuf + 10 * s;
 #pragma unroll
             for (int a9 = 0; a9 < 9; ++a9) o[a9] = c[a9];
             o[9] = (double)res.kk;
         }
-        wave_lds_fence();
     }
-}
-// sums -> covariance -> eigenvector of the smallest eigenvalue; one thread per (cell-sorted) query.  count < 0: the
-// query was handed to the heap walk, which writes its normal itself.
+    template <bool COV> __device__ void heap_finish(int64_t s, const HeapDI &heap) const
+    {
+        double c[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+        if (heap.sz >= 3)
+            for (int e = 0; e < heap.sz; ++e) {
+                int64_t j = heap.ix[e * heap.stride];
+                double x = pts[3 * j], y = pts[3 * j + 1], z = pts[3 * j + 2];
+                c[0] += x; c[1] += y; c[2] += z;
+                c[3] += x * x; c[4] += x * y; c[5] += x * z; c[6] += y * y; c[7] += y * z; c[8] += z * z;
+            }
+        moments_finish<COV>(c, (double)heap.sz, sidx[s], normals, out_cov);
+    }
+    __device__ void heap(int64_t s, const HeapDI &h) const { heap_finish<false>(s, h); }
+    __device__ void heap_alt(int64_t s, const HeapDI &h) const { heap_finish<true>(s, h); }
+};
+// the wave form's sums -> normal / covariance; one thread per (cell-sorted) query
 template <bool COV>
 __global__ __launch_bounds__(256) void normals_eigen_kernel(const double *__restrict__ covbuf, const int32_t *__restrict__ sidx, int64_t n,
                                                             float *__restrict__ normals, double *__restrict__ out_cov)
@@ -949,36 +875,8 @@ __global__ __launch_bounds__(256) void normals_eigen_kernel(const double *__rest
     if (s >= n) return;
     const double *in = covbuf + 10 * s;
     const double m = in[9];
-    if (m < 0.0) return;
-    if constexpr (COV) {
-        double *o = out_cov + 9 * (int64_t)sidx[s];
-        if (m >= 3.0) {
-            double c[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) c[q] = in[q] / m;
-            const double cov[6] = { c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2],
-                                    c[6] - c[1] * c[1], c[7] - c[1] * c[2], c[8] - c[2] * c[2] };
-            store_cov9(o, cov);
-        } else {
-            store_cov9(o, nullptr);
-        }
-        return;
-    }
-    double nx = 0.0, ny = 0.0, nz = 1.0;
-    if (m >= 3.0) {
-        double c[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) c[q] = in[q] / m;
-        double cov[6] = { c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2],
-                          c[6] - c[1] * c[1], c[7] - c[1] * c[2], c[8] - c[2] * c[2] };
-        double w[3], V[9];
-        sym3_eigen(cov, w, V);
-        nx = V[0]; ny = V[3]; nz = V[6];
-        const double nn = sqrt(nx * nx + ny * ny + nz * nz);
-        if (nn > 0.0) { nx /= nn; ny /= nn; nz /= nn; } else { nx = 0.0; ny = 0.0; nz = 1.0; }
-    }
-    const int64_t me = sidx[s];
-    normals[3 * me] = (float)nx; normals[3 * me + 1] = (float)ny; normals[3 * me + 2] = (float)nz;
+    if (m < 0.0) return;                                         // the heap walk writes this query's result itself
+    moments_finish<COV>(in, m, sidx[s], normals, out_cov);
 }
 
 // normals != nullptr: estimate_normals; otherwise out_cov [n][9]: estimate_covariances (the same search, the covariance the normal comes from)
@@ -991,44 +889,18 @@ static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, 
     if (rc) return rc;
     int32_t *fb_list = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     double *covbuf = a.get<double>((size_t)(n > 0 ? n : 1) * 10);
-    const bool global_heap = kk > KPX_NORMALS_LDS_NN;            // the fall-back heaps in the workspace (<= 256 MB of distances)
-    int heap_blocks = 256;
-    while (global_heap && heap_blocks > 8 && (size_t)heap_blocks * 64 * (size_t)kk * sizeof(double) > ((size_t)256 << 20)) heap_blocks >>= 1;
-    double *gheap = global_heap ? a.get<double>((size_t)heap_blocks * 64 * (size_t)kk) : nullptr;
-    int32_t *gix = global_heap ? a.get<int32_t>((size_t)heap_blocks * 64 * (size_t)kk) : nullptr;
+    const KnnHeaps hp = knn_heaps_carve(a, kk, KPX_NORMALS_LDS_NN, true, kk <= 48 ? 128 : 64);
     if (a.dry) return KPX_OK;
     KPX_ARENA_CHECK(a);
-    int32_t *fb_count = g.spare;                                  // cleared by the grid build
-    const int threads = global_heap ? 64 : (kk <= 48 ? 128 : 64);
-    const size_t lds = global_heap ? 0 : (size_t)kk * threads * (sizeof(double) + sizeof(int32_t));
-    static bool attr_set = false;
-    if (!attr_set) {
-        KPX_HIP(hipFuncSetAttribute((const void *)normals_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        KPX_HIP(hipFuncSetAttribute((const void *)normals_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        KPX_HIP(hipFuncSetAttribute((const void *)normals_wave_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
     // pass 1: one wave per query, 512- or 1024-candidate buffer; pass 2: the few queries that did not fit, thread-per-query heap walk
     // (max_nn > 512: the wave kernel's 1024-candidate buffer cannot hold a neighbourhood and its surroundings -- every query takes the heap walk)
-    const int cap = kk <= 48 ? 512 : 1024;
     const bool wave_pass = kk <= 512;
-    if (wave_pass) {
-        hipLaunchKernelGGL(normals_wave_kernel<4>, dim3((unsigned)(cdiv(n, 4) > 8192 ? 8192 : cdiv(n, 4))), dim3(256),
-                           (size_t)4 * cap * (sizeof(double) + sizeof(uint32_t)), st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, n, kk,
-                           cap, radius * radius, covbuf, fb_list, fb_count);
-        if (out_cov)
-            hipLaunchKernelGGL(normals_eigen_kernel<true>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals, out_cov);
-        else
-            hipLaunchKernelGGL(normals_eigen_kernel<false>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals, out_cov);
-    }
-    if (out_cov)
-        hipLaunchKernelGGL(normals_kernel<true>, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, pts,
-                           n, kk, radius * radius, normals, out_cov, wave_pass ? fb_list : (const int32_t *)nullptr,
-                           wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
-    else
-        hipLaunchKernelGGL(normals_kernel<false>, dim3(global_heap ? heap_blocks : 256), dim3(threads), lds, st, g.params, g.cell_start, g.sorted_pts, g.sorted_idx, pts,
-                           n, kk, radius * radius, normals, out_cov, wave_pass ? fb_list : (const int32_t *)nullptr,
-                           wave_pass ? fb_count : (const int32_t *)nullptr, gheap, gix);
+    rc = knn_cascade<MomentsOp>(g, kk, MomentsOp{ g.sorted_idx, pts, radius * radius, covbuf, normals, out_cov }, 0, n, nullptr, nullptr,
+                                { knn_wave_pass<MomentsOp, 4>(kk <= 48 ? 512 : 1024, 8192, fb_list, wave_pass) }, g.spare,
+                                out_cov ? knn_heap_pass<MomentsOp, true>() : knn_heap_pass<MomentsOp, false>(), hp, st);
+    if (rc) return rc;
+    const auto eigen_kernel = out_cov ? normals_eigen_kernel<true> : normals_eigen_kernel<false>;
+    if (wave_pass) hipLaunchKernelGGL(eigen_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, covbuf, g.sorted_idx, n, normals, out_cov);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -56,6 +56,26 @@ __host__ __device__ __forceinline__ void sym3_eigen(const double a[6], double w[
     for (int k = 0; k < 3; ++k) { w[k] = e[k]; for (int r = 0; r < 3; ++r) V[3 * r + k] = Q[r][k]; }
 }
 
+// Covariance (xx,xy,xz,yy,yz,zz) of m points from their nine raw moment sums s = (x, y, z, xx, xy, xz, yy, yz, zz):
+// E[p p^T] - mu mu^T, every sum divided by m BEFORE the products.
+__host__ __device__ __forceinline__ void cov6_from_moments(const double s[9], double m, double cov[6])
+{
+    double c[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) c[q] = s[q] / m;
+    cov[0] = c[3] - c[0] * c[0]; cov[1] = c[4] - c[0] * c[1]; cov[2] = c[5] - c[0] * c[2];
+    cov[3] = c[6] - c[1] * c[1]; cov[4] = c[7] - c[1] * c[2]; cov[5] = c[8] - c[2] * c[2];
+}
+// Unit eigenvector of the smallest eigenvalue of the symmetric a = (xx,xy,xz,yy,yz,zz); (0,0,1) where it has no length.
+__host__ __device__ __forceinline__ void sym3_smallest_axis(const double a[6], double n[3])
+{
+    double w[3], V[9];
+    sym3_eigen(a, w, V);
+    n[0] = V[0]; n[1] = V[3]; n[2] = V[6];
+    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (nn > 0.0) { n[0] /= nn; n[1] /= nn; n[2] /= nn; } else { n[0] = 0.0; n[1] = 0.0; n[2] = 1.0; }
+}
+
 // Rotation of the Umeyama/Kabsch solution for covariance S (row-major 3x3, S = E[t s^T] - mu_t mu_s^T):
 // R = U diag(1,1,sign(det U det V)) V^T for S = U D V^T.  Built from the eigenvectors of S^T S
 // (V proper, descending), U columns u1,u2 = normalised S v1, S v2 (Gram-Schmidt), u3 = u1 x u2:
