@@ -4,6 +4,7 @@
 #pragma once
 #include <hipcub/hipcub.hpp>
 
+#include "kpx_cloudset.h"
 #include "kpx_internal.h"
 
 namespace kpx {
@@ -23,20 +24,6 @@ static inline hipError_t sort_pairs(void *tmp, size_t &bytes, const Key *keys_in
     if (end_bit <= 32)
         return rocprim::radix_sort_pairs<NarrowSortConfig>(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)end_bit, st);
     return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)end_bit, st);
-}
-
-// butterfly reductions: the result is valid in EVERY lane (kpx_common.h's wave_min / wave_max leave it in lane 0)
-__device__ __forceinline__ double wave_all_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_all_min(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 __device__ __forceinline__ uint32_t morton_spread10(uint32_t v)
@@ -153,12 +140,9 @@ static int morton_order(const float *pts, int64_t n, const SortScratch &s, int32
 // morton_order produces).
 constexpr int kMortonBatchMax = 8;
 constexpr int kMortonBatchBboxBlocks = 32;
-struct MortonBatch {
-    const float *pts[kMortonBatchMax];
+struct MortonBatch : CloudSet<kMortonBatchMax> {
     int32_t *perm[kMortonBatchMax];       // out: perm[c][r] = original index of the r-th point of cloud c along its curve
     double *bbox[kMortonBatchMax];        // out: (min x,y,z, max x,y,z) of cloud c
-    int64_t off[kMortonBatchMax + 1];
-    int32_t count;
 };
 struct MortonBatchScratch {
     uint64_t *keys_in, *keys_out;
@@ -178,53 +162,11 @@ static void morton_batch_carve(Arena &a, int64_t total, MortonBatchScratch *s)
     s->tmp_bytes = memo_bytes(8, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, 34, (hipStream_t) nullptr); return b; });
     s->tmp = a.get<char>(s->tmp_bytes);
 }
-__device__ __forceinline__ int morton_batch_cloud(const MortonBatch &b, int64_t i)
-{
-    int c = 0;
-#pragma unroll
-    for (int k = 1; k < kMortonBatchMax; ++k) c += (k < b.count && i >= b.off[k]) ? 1 : 0;
-    return c;
-}
-static __global__ __launch_bounds__(256) void morton_batch_bbox_partial_kernel(MortonBatch b, double *__restrict__ part)
-{
-    __shared__ float sh[6][4];
-    const int c = blockIdx.y;
-    const float *pts = b.pts[c];
-    const int64_t n = b.off[c + 1] - b.off[c];
-    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { float v = pts[3 * i + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_all_min((double)mn[a]); mx[a] = wave_all_max((double)mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        part[((int64_t)c * kMortonBatchBboxBlocks + blockIdx.x) * 6 + threadIdx.x] = (double)v;
-    }
-}
-static __global__ __launch_bounds__(64) void morton_batch_bbox_final_kernel(MortonBatch b, const double *__restrict__ part)
-{
-    const int c = blockIdx.x, lane = lane_id();
-    double v[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-        v[a] = lane < kMortonBatchBboxBlocks ? part[((int64_t)c * kMortonBatchBboxBlocks + lane) * 6 + a] : (a < 3 ? (double)INFINITY : -(double)INFINITY);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { v[a] = wave_all_min(v[a]); v[3 + a] = wave_all_max(v[3 + a]); }
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-        if (lane == a) b.bbox[c][a] = v[a];
-}
 static __global__ __launch_bounds__(256) void morton_batch_key_kernel(MortonBatch b, uint64_t *__restrict__ keys, int32_t *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b.off[b.count]) return;
-    const int c = morton_batch_cloud(b, i);
+    const int c = b.cloud_of(i);
     const float *pts = b.pts[c];
     const double *bbox = b.bbox[c];
     const int64_t j = i - b.off[c];
@@ -243,14 +185,14 @@ static __global__ __launch_bounds__(256) void morton_batch_split_kernel(MortonBa
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b.off[b.count]) return;
-    const int c = morton_batch_cloud(b, i);          // sorted position i lies in cloud c's range
+    const int c = b.cloud_of(i);          // sorted position i lies in cloud c's range
     b.perm[c][i - b.off[c]] = vals[i] - (int32_t)b.off[c];
 }
 static __global__ __launch_bounds__(256) void morton_batch_iota_kernel(MortonBatch b)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b.off[b.count]) return;
-    const int c = morton_batch_cloud(b, i);
+    const int c = b.cloud_of(i);
     b.perm[c][i - b.off[c]] = (int32_t)(i - b.off[c]);
 }
 // presorted: the caller's clouds already lie along a space-filling curve (the frame loop's voxel clouds, kpx_voxel.hip): the boxes
@@ -258,8 +200,11 @@ static __global__ __launch_bounds__(256) void morton_batch_iota_kernel(MortonBat
 static int morton_order_batch(const MortonBatch &b, const MortonBatchScratch &s, hipStream_t st, bool presorted = false)
 {
     const int64_t total = b.off[b.count];
-    hipLaunchKernelGGL(morton_batch_bbox_partial_kernel, dim3(kMortonBatchBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
-    hipLaunchKernelGGL(morton_batch_bbox_final_kernel, dim3(b.count), dim3(64), 0, st, b, s.part);
+    BoxDst dst;
+    for (int c = 0; c < kMortonBatchMax; ++c) dst.box[c] = b.bbox[c];
+    dst.err = nullptr;
+    hipLaunchKernelGGL((cloud_bbox_partial_kernel<MortonBatch, StoredPoint, float, kMortonBatchBboxBlocks>), dim3(kMortonBatchBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
+    hipLaunchKernelGGL(cloud_bbox_final_kernel<kMortonBatchBboxBlocks>, dim3(b.count), dim3(64), 0, st, (const double *)s.part, dst);
     const unsigned nb = (unsigned)cdiv(total, 256);
     if (presorted) {
         hipLaunchKernelGGL(morton_batch_iota_kernel, dim3(nb), dim3(256), 0, st, b);

@@ -4,89 +4,208 @@
 //   63-bit key (21 bits per axis), stable radix sort of (key, point id), one thread per voxel sums
 //   its points in ascending original index (fp64, sequential) -> bit-exact means.
 // Output order: ascending (ix,iy,iz).
+//
+// Three forms -- plain (voxel_impl: one cloud, normals), batch (voxel_batch_impl: up to 8 clouds in one pass) and fused
+// (fuse_voxel_impl: transform + stack + voxel grid) -- run the same steps: bounding box, cell index, key, stable sort, head
+// compaction, per-voxel mean.  Each step is written once below (and in kpx_cloudset.h); a form is its host policy -- key layout and
+// width, sort, read-back, speculation -- plus a key packer and a point loader.
 #include <hipcub/hipcub.hpp>
 
+#include "kpx_cloudset.h"
 #include "kpx_internal.h"
 #include "kpx_radix.h"
 
 namespace kpx {
 
-__global__ __launch_bounds__(256) void voxel_key_kernel(const float *__restrict__ pts, int64_t n, const double *__restrict__ bbox,
-                                                        double voxel, uint64_t *__restrict__ keys, int32_t *__restrict__ vals,
-                                                        int32_t *__restrict__ err)
+// ---- the steps every form shares ----------------------------------------------------------------------------------------
+// The contract's cell index of q in the grid of the box `bbox`: f = floor((q - (min - v/2)) / v) per axis.  Returns true when an
+// index lies outside [0, 2^21) -- the 21 bits an axis has in the 63-bit key -- or is NaN; own: the grid's own extents instead.
+constexpr double kVoxelAxisCells = 2097152.0;
+__device__ __forceinline__ bool voxel_cell(const double q[3], const double *__restrict__ bbox, double voxel, double f[3], const double *own = nullptr)
 {
-    const double ox = bbox[0] - voxel * 0.5, oy = bbox[1] - voxel * 0.5, oz = bbox[2] - voxel * 0.5;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double fx = floor(((double)pts[3 * i] - ox) / voxel);
-        double fy = floor(((double)pts[3 * i + 1] - oy) / voxel);
-        double fz = floor(((double)pts[3 * i + 2] - oz) / voxel);
-        bool bad = !(fx >= 0.0) || !(fy >= 0.0) || !(fz >= 0.0) || fx >= 2097152.0 || fy >= 2097152.0 || fz >= 2097152.0;
-        if (bad) { *err = 1; fx = fy = fz = 0.0; }
-        keys[i] = ((uint64_t)fx << 42) | ((uint64_t)fy << 21) | (uint64_t)fz;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) f[a] = floor((q[a] - (bbox[a] - voxel * 0.5)) / voxel);
+    if (!(f[0] >= 0.0) || !(f[1] >= 0.0) || !(f[2] >= 0.0)) return true;
+    if (own) return !(f[0] < own[0]) || !(f[1] < own[1]) || !(f[2] < own[2]);
+    return f[0] >= kVoxelAxisCells || f[1] >= kVoxelAxisCells || f[2] >= kVoxelAxisCells;
+}
+// (key, concatenated index) of every point.  Src: the point source; Pack: the form's key layout -- grid() prepares it once per block
+// (it may synchronise the block), put() writes the key of point i of cloud c and reports a bad index the form's way.
+template <class Set, class Src, class Pack>
+__global__ __launch_bounds__(256) void voxel_key_kernel(Set b, const double *__restrict__ bbox, double voxel, Pack pack, int32_t *__restrict__ vals)
+{
+    const typename Pack::Grid g = pack.grid(b, bbox, voxel);
+    const int64_t total = b.off[b.count];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = b.cloud_of(i);
+        double q[3];
+        Src()(b, c, i - b.off[c], q);
+        pack.put(g, bbox, voxel, i, c, q);
         vals[i] = (int32_t)i;
     }
 }
+// 63-bit fixed fields ix | iy | iz over the box bbox[0..5] (plain and fused form); a bad index sets *err
+struct FixedKeys {
+    struct Grid {};
+    uint64_t *keys;
+    int32_t *err;
+    template <class Set> __device__ __forceinline__ Grid grid(const Set &, const double *, double) const { return Grid(); }
+    __device__ __forceinline__ void put(const Grid &, const double *__restrict__ bbox, double voxel, int64_t i, int, const double q[3]) const
+    {
+        double f[3];
+        if (voxel_cell(q, bbox, voxel, f)) { *err = 1; f[0] = f[1] = f[2] = 0.0; }
+        keys[i] = ((uint64_t)f[0] << 42) | ((uint64_t)f[1] << 21) | (uint64_t)f[2];
+    }
+};
 
 template <class Key> struct HeadPredT {
     const Key *keys;
     __device__ bool operator()(int64_t s, int) const { return s == 0 || keys[s] != keys[s - 1]; }
 };
-using HeadPred = HeadPredT<uint64_t>;
 struct HeadEmit {
     int32_t *seg_start;
     __device__ void operator()(int64_t s, int, int32_t dst) const { seg_start[dst] = (int32_t)s; }
 };
 
-__global__ __launch_bounds__(256) void voxel_mean_kernel(const float *__restrict__ pts, const float *__restrict__ col,
-                                                         const float *__restrict__ nrm, int64_t n,
-                                                         const int32_t *__restrict__ vals, const int32_t *__restrict__ seg_start,
-                                                         int32_t *__restrict__ d_count, const int32_t *__restrict__ err,
-                                                         float *__restrict__ opts, float *__restrict__ ocol, float *__restrict__ onrm)
+// Sums of the points at sorted positions [s0, s1) -- one voxel -- in ascending point index (the contract: sequential fp64 adds).
+// Only the LOADS of 8 points are issued together: a dense voxel (a wall patch close to the camera holds 50+ points) was a chain
+// of 2 dependent global loads per point, and the longest voxel set the kernel's duration.
+// Load: the form's loader -- load(p, xyz, colour, normal) of the point with concatenated index p (Coord: float, or double for moved
+// points), has_col() whether colours are summed.  NRM: normals are loaded and summed too (plain form only).
+template <bool NRM, class Load>
+__device__ __forceinline__ void voxel_segment_sum(const int32_t *__restrict__ vals, int64_t s0, int64_t s1, const Load &load, double sp[3],
+                                                  double sc[3], double sn[3])
+{
+    for (int64_t s = s0; s < s1; s += 8) {
+        const int cnt = (int)(s1 - s < 8 ? s1 - s : 8);
+        int64_t p[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p[k] = k < cnt ? vals[s + k] : -1;
+        typename Load::Coord vp[8][3];
+        float vc[8][3], vn[8][3];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (p[k] < 0) continue;
+            load(p[k], vp[k], vc[k], vn[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (p[k] < 0) continue;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                sp[a] += (double)vp[k][a];
+                if (load.has_col()) sc[a] += (double)vc[k][a];
+                if (NRM) sn[a] += (double)vn[k][a];
+            }
+        }
+    }
+}
+// one row of means; ocol null: no colours
+__device__ __forceinline__ void voxel_write_row(const double sp[3], const double sc[3], double cn, float *__restrict__ opts, float *__restrict__ ocol)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        opts[a] = (float)(sp[a] / cn);
+        if (ocol) ocol[a] = (float)(sc[a] / cn);
+    }
+}
+// points of one cloud with optional colours and normals (plain form; a cloud of the batch form: base = its first concatenated index)
+struct StoredLoad {
+    using Coord = float;
+    const float *pts, *col, *nrm;
+    int64_t base;
+    __device__ __forceinline__ bool has_col() const { return col != nullptr; }
+    __device__ __forceinline__ void operator()(int64_t p, float v[3], float c[3], float n[3]) const
+    {
+        const int64_t j = p - base;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            v[a] = pts[3 * j + a];
+            if (col) c[a] = col[3 * j + a];
+            if (nrm) n[a] = nrm[3 * j + a];
+        }
+    }
+};
+
+// Scratch of a form.  VoxelCarve: what distinguishes the forms' workspaces -- the cloud slots, the blocks of a cloud's partial
+// bounding boxes, boxes / error words per cloud (with the batch form's head table) or one for all, the library's own radix sort,
+// and the call site and end bit of the vendor sort's size query.
+struct VoxelScratch {
+    uint64_t *keys_in, *keys_out;
+    int32_t *vals_in, *vals_out, *seg_start, *counts, *err, *head, *d_total;
+    double *part, *bbox;
+    char *sort_tmp;
+    size_t sort_bytes;
+    RadixScratch rx;            // the hand-written sort (keys of at most 32 bits, total <= kRadixMaxPairs)
+    char *counts_end;
+};
+struct VoxelCarve {
+    int clouds, bbox_blocks;
+    bool per_cloud, own_radix;
+    unsigned site;
+    int end_bit;
+};
+static void voxel_carve(Arena &a, int64_t total, const VoxelCarve &v, VoxelScratch *s)
+{
+    const size_t nn = (size_t)(total > 0 ? total : 1);
+    s->keys_in = a.get<uint64_t>(nn); s->keys_out = a.get<uint64_t>(nn);
+    s->vals_in = a.get<int32_t>(nn); s->vals_out = a.get<int32_t>(nn);
+    s->seg_start = a.get<int32_t>(nn);
+    s->err = a.get<int32_t>(v.per_cloud ? v.clouds : 1);
+    s->head = v.per_cloud ? a.get<int32_t>(v.clouds + 1) : nullptr;
+    s->d_total = v.per_cloud ? a.get<int32_t>(1) : nullptr;
+    s->part = a.get<double>((size_t)v.clouds * v.bbox_blocks * 6);
+    s->bbox = a.get<double>((size_t)(v.per_cloud ? v.clouds : 1) * 8);
+    const int end_bit = v.end_bit;
+    s->sort_bytes = memo_bytes(v.site, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, end_bit, (hipStream_t) nullptr); return b; });
+    s->sort_tmp = a.get<char>(s->sort_bytes);
+    s->rx = RadixScratch();
+    if (v.own_radix) radix_carve(a, total <= kRadixMaxPairs ? total : kRadixMaxPairs, &s->rx);      // unconditional: the workspace size stays monotonic in the point count
+    s->counts = a.get<int32_t>((size_t)compact_ws_ints(total));          // right behind the sort's cleared histograms: one memset for both
+    s->counts_end = reinterpret_cast<char *>(s->counts + (size_t)compact_ws_ints(total));
+}
+
+// Stable sort of the (key, index) pairs on key bits [0, end_bit), then the segment heads: seg_start[m] = first sorted position of the
+// m-th distinct key, *d_heads = their number.  Keys written as 32-bit words go to the library's own radix sort (three 8-bit passes of
+// two launches for a frame's ~24 bits, against the vendor's eight passes over 64-bit keys) whenever it serves the size;
+// KPX_RADIX=0: the vendor sort instead (A/B switch).
+template <class Key>
+static int voxel_sort_and_heads(const VoxelScratch &s, int64_t total, int end_bit, int32_t *d_heads, hipStream_t st)
+{
+    Key *k_in = reinterpret_cast<Key *>(s.keys_in), *k_out = reinterpret_cast<Key *>(s.keys_out);
+    static const bool vendor_sort = [] { const char *e = getenv("KPX_RADIX"); return e && e[0] == '0'; }();
+    bool cleared = false;
+    if constexpr (sizeof(Key) == 4) {
+        if (total <= kRadixMaxPairs && !vendor_sort) {
+            const int rc = radix_sort_pairs_u32(s.rx, k_in, k_out, s.vals_in, s.vals_out, total, end_bit, st, s.counts_end);
+            if (rc) return rc;
+            cleared = true;
+        }
+    }
+    if (!cleared) {
+        size_t bytes = s.sort_bytes;
+        KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, bytes, k_in, k_out, s.vals_in, s.vals_out, (int)total, 0, end_bit, st));
+    }
+    return compact(HeadPredT<Key>{ k_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, d_heads, st, cleared);
+}
+
+// ---- plain form: one cloud, colours and normals -----------------------------------------------------------------------------
+constexpr VoxelCarve kPlainCarve = { 1, kBboxBlocks, false, false, 4, 63 };
+template <bool NRM>
+__global__ __launch_bounds__(256) void voxel_mean_kernel(StoredLoad load, int64_t n, const int32_t *__restrict__ vals, const int32_t *__restrict__ seg_start,
+                                                         int32_t *__restrict__ d_count, const int32_t *__restrict__ err, float *__restrict__ opts,
+                                                         float *__restrict__ ocol, float *__restrict__ onrm)
 {
     const int32_t m_total = *d_count;
     // index overflow is reported through the count word (the host sees KPX_ERR_RANGE when it reads it); a block that reads
     // the count after this store sees a negative total and does nothing -- the output is invalid in that case anyway
     if (blockIdx.x == 0 && threadIdx.x == 0 && *err) *d_count = KPX_ERR_RANGE;
     for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < m_total; m += (int64_t)gridDim.x * blockDim.x) {
-        int64_t s0 = seg_start[m], s1 = (m + 1 < m_total) ? seg_start[m + 1] : n;
+        const int64_t s0 = seg_start[m], s1 = (m + 1 < m_total) ? seg_start[m + 1] : n;
         double sp[3] = { 0, 0, 0 }, sc[3] = { 0, 0, 0 }, sn[3] = { 0, 0, 0 };
-        // The sums stay sequential in ascending point index (the contract); only the LOADS of 8 points are issued
-        // together -- a dense voxel (a wall patch close to the camera holds 50+ points) was a chain of 2 dependent
-        // global loads per point, and the longest voxel set the kernel's duration.
-        for (int64_t s = s0; s < s1; s += 8) {
-            const int cnt = (int)(s1 - s < 8 ? s1 - s : 8);
-            int64_t p[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[k] = k < cnt ? vals[s + k] : -1;
-            float vp[8][3], vc[8][3], vn[8][3];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    vp[k][a] = pts[3 * p[k] + a];
-                    if (col) vc[k][a] = col[3 * p[k] + a];
-                    if (nrm) vn[k][a] = nrm[3 * p[k] + a];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    sp[a] += (double)vp[k][a];
-                    if (col) sc[a] += (double)vc[k][a];
-                    if (nrm) sn[a] += (double)vn[k][a];
-                }
-            }
-        }
-        double c = (double)(s1 - s0);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            opts[3 * m + a] = (float)(sp[a] / c);
-            if (col && ocol) ocol[3 * m + a] = (float)(sc[a] / c);
-        }
-        if (nrm && onrm) {
+        voxel_segment_sum<NRM>(vals, s0, s1, load, sp, sc, sn);
+        voxel_write_row(sp, sc, (double)(s1 - s0), opts + 3 * m, (load.col && ocol) ? ocol + 3 * m : nullptr);
+        if (NRM && onrm) {
             double nn = sqrt(fma(sn[2], sn[2], fma(sn[1], sn[1], sn[0] * sn[0])));
 #pragma unroll
             for (int a = 0; a < 3; ++a) onrm[3 * m + a] = (float)(nn > 0 ? sn[a] / nn : sn[a]);
@@ -96,28 +215,23 @@ __global__ __launch_bounds__(256) void voxel_mean_kernel(const float *__restrict
 static int voxel_impl(const float *pts, const float *col, const float *nrm, int64_t n, double voxel, float *opts,
                       float *ocol, float *onrm, int32_t *d_count, Arena &a, hipStream_t st)
 {
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    uint64_t *keys_in = a.get<uint64_t>(nn), *keys_out = a.get<uint64_t>(nn);
-    int32_t *vals_in = a.get<int32_t>(nn), *vals_out = a.get<int32_t>(nn);
-    int32_t *seg_start = a.get<int32_t>(nn);
-    int32_t *counts = a.get<int32_t>((size_t)compact_ws_ints(n));
-    double *part = a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    int32_t *err = a.get<int32_t>(1);
-    size_t sort_bytes = memo_bytes(4, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, keys_in, keys_out, vals_in, vals_out, (int)nn, 0, 63, st); return b; });
-    char *sort_tmp = a.get<char>(sort_bytes);
-    if (a.dry) return KPX_OK;
+    VoxelScratch s;
+    voxel_carve(a, n, kPlainCarve, &s);
     KPX_ARENA_CHECK(a);
-    double *bbox = part + (size_t)kBboxBlocks * 6;
-    int rc = bbox_f32(pts, n, bbox, part, st);
+    int rc = bbox_f32(pts, n, s.bbox, s.part, st);
     if (rc) return rc;
-    KPX_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), st));
+    KPX_HIP(hipMemsetAsync(s.err, 0, sizeof(int32_t), st));
     int nb = (int)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256));
-    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, st, pts, n, bbox, voxel, keys_in, vals_in, err);
-    KPX_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
-    rc = compact(HeadPred{ keys_out }, HeadEmit{ seg_start }, n, 1, counts, d_count, st);
+    CloudSet<1> one;
+    one.pts[0] = pts; one.off[0] = 0; one.off[1] = n; one.count = 1;
+    hipLaunchKernelGGL((voxel_key_kernel<CloudSet<1>, StoredPoint, FixedKeys>), dim3(nb), dim3(256), 0, st, one, (const double *)s.bbox, voxel,
+                       FixedKeys{ s.keys_in, s.err }, s.vals_in);
+    rc = voxel_sort_and_heads<uint64_t>(s, n, 63, d_count, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(voxel_mean_kernel, dim3(nb), dim3(256), 0, st, pts, col, nrm, n, vals_out, seg_start, d_count, err, opts,
-                       ocol, onrm);
+    const StoredLoad load = { pts, col, nrm, 0 };
+    const auto mean_kernel = nrm ? &voxel_mean_kernel<true> : &voxel_mean_kernel<false>;
+    hipLaunchKernelGGL(mean_kernel, dim3(nb), dim3(256), 0, st, load, n, (const int32_t *)s.vals_out,
+                       (const int32_t *)s.seg_start, d_count, (const int32_t *)s.err, opts, ocol, onrm);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -133,15 +247,31 @@ static int voxel_impl(const float *pts, const float *col, const float *nrm, int6
 // point index.
 constexpr int kVoxelBatchMax = 8;
 constexpr int kVoxelBatchBboxBlocks = 64;
-struct VoxelBatch {
-    const float *pts[kVoxelBatchMax];
+constexpr VoxelCarve kBatchCarve = { kVoxelBatchMax, kVoxelBatchBboxBlocks, true, true, 5, 64 };
+struct VoxelBatch : CloudSet<kVoxelBatchMax> {
     const float *col[kVoxelBatchMax];
     float *opts[kVoxelBatchMax];
     float *ocol[kVoxelBatchMax];
-    int64_t off[kVoxelBatchMax + 1];      // cloud c owns [off[c], off[c+1]) of the concatenated index space
-    int32_t count;
     int32_t morton;                       // keys = cloud | curve code of (ix, iy, iz) instead of cloud | (ix, iy, iz) row-major: 1 = along the Hilbert curve
 };
+// clouds [first, first + count) of the caller's arrays (h_col / h_ocol may be null: no colours)
+static VoxelBatch voxel_batch_of(const float *const *h_pts, const float *const *h_col, const int64_t *h_n, float *const *h_opts, float *const *h_ocol,
+                                 int first, int count, bool morton)
+{
+    VoxelBatch b;
+    b.count = count;
+    b.morton = morton ? 1 : 0;
+    b.off[0] = 0;
+    for (int i = 0; i < kVoxelBatchMax; ++i) {
+        const bool on = i < count;
+        b.pts[i] = on ? h_pts[first + i] : nullptr;
+        b.col[i] = (on && h_col) ? h_col[first + i] : nullptr;
+        b.opts[i] = on ? h_opts[first + i] : nullptr;
+        b.ocol[i] = (on && h_col && h_ocol) ? h_ocol[first + i] : nullptr;
+        b.off[i + 1] = b.off[i] + (on ? h_n[first + i] : 0);
+    }
+    return b;
+}
 // bits per axis: enough for the axis' largest index in the batch.  A Z-curve code (round 2; removed: slower, and another order moves the
 // ICP transforms' last bits) interleaves bit q of every axis that still has a bit q, so its width is the SUM of the three widths -- a long axis costs its own extra bits only, not
 // three times them (a frame's 26-bit cube code would be a fourth radix pass; 7 + 7 + 8 bits + 2 for the cloud stay within three)
@@ -213,53 +343,9 @@ __device__ __forceinline__ int voxel_hilbert_key_bits(const int ab[3], int m)
 __device__ __forceinline__ unsigned long long voxel_hilbert_key(unsigned long long x, unsigned long long y, unsigned long long z, const int ab[3], int m)
 {
     const unsigned long long mask = (1ull << m) - 1ull;
-    const int ex = ab[0] > m ? ab[0] - m : 0, ey = ab[1] > m ? ab[1] - m : 0, ez = ab[2] > m ? ab[2] - m : 0;
-    (void)ex;
+    const int ey = ab[1] > m ? ab[1] - m : 0, ez = ab[2] > m ? ab[2] - m : 0;
     const unsigned long long hi = (((x >> m) << ey | (y >> m)) << ez) | (z >> m);
     return (hi << (3 * m)) | voxel_hcode(x & mask, y & mask, z & mask, m);
-}
-__device__ __forceinline__ int voxel_batch_cloud(const VoxelBatch &b, int64_t i)
-{
-    int c = 0;
-#pragma unroll
-    for (int k = 1; k < kVoxelBatchMax; ++k) c += (k < b.count && i >= b.off[k]) ? 1 : 0;
-    return c;
-}
-__global__ __launch_bounds__(256) void voxel_batch_bbox_partial_kernel(VoxelBatch b, double *__restrict__ part)
-{
-    __shared__ float sh[6][4];
-    const int c = blockIdx.y;
-    const float *pts = b.pts[c];
-    const int64_t n = b.off[c + 1] - b.off[c];
-    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { float v = pts[3 * i + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        part[((int64_t)c * kVoxelBatchBboxBlocks + blockIdx.x) * 6 + threadIdx.x] = (double)v;
-    }
-}
-// one wave per cloud: folds the partial boxes, bbox[c][0..5]; zeroes the cloud's error word
-__global__ __launch_bounds__(64) void voxel_batch_bbox_final_kernel(const double *__restrict__ part, double *__restrict__ bbox, int32_t *__restrict__ err)
-{
-    const int c = blockIdx.x, lane = lane_id();
-    double v[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) v[a] = part[((int64_t)c * kVoxelBatchBboxBlocks + lane) * 6 + a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { v[a] = wave_min(v[a]); v[3 + a] = wave_max(v[3 + a]); }
-    if (lane == 0) {
-        for (int a = 0; a < 6; ++a) bbox[8 * c + a] = v[a];
-        err[c] = 0;
-    }
 }
 // largest grid extents of the batch (index < floor((max - origin) / v) + 1) and whether count x DX x DY x DZ fits 64 bits
 __device__ __forceinline__ void voxel_batch_dims(const VoxelBatch &b, const double *__restrict__ bbox, double voxel, double d[3], int *overflow)
@@ -267,9 +353,11 @@ __device__ __forceinline__ void voxel_batch_dims(const VoxelBatch &b, const doub
     d[0] = d[1] = d[2] = 1.0;
     for (int c = 0; c < b.count; ++c) {
         if (b.off[c + 1] == b.off[c]) continue;
+        double f[3];
+        (void)voxel_cell(bbox + 8 * c + 3, bbox + 8 * c, voxel, f);      // the cell of the box's far corner
         for (int a = 0; a < 3; ++a) {
-            const double e = floor((bbox[8 * c + 3 + a] - (bbox[8 * c + a] - voxel * 0.5)) / voxel) + 1.0;
-            if (e > d[a] && e < 2097152.0) d[a] = e;              // out-of-range clouds are flagged per point by the key kernel
+            const double e = f[a] + 1.0;
+            if (e > d[a] && e < kVoxelAxisCells) d[a] = e;        // out-of-range clouds are flagged per point by the key kernel
         }
     }
     *overflow = ((double)b.count * d[0]) * (d[1] * d[2]) >= 18446744073709551616.0 ? 1 : 0;
@@ -299,48 +387,45 @@ __global__ void voxel_batch_bits_kernel(VoxelBatch b, const double *__restrict__
     voxel_batch_dims(b, bbox, voxel, d, &overflow);
     *bits = voxel_batch_key_bits(b, d, overflow);
 }
-template <class Key>
-__global__ __launch_bounds__(256) void voxel_batch_key_kernel(VoxelBatch b, const double *__restrict__ bbox, double voxel,
-                                                              Key *__restrict__ keys, int32_t *__restrict__ vals, int32_t *__restrict__ err,
-                                                              int32_t *__restrict__ bits_out)
-{
-    __shared__ double dims[3];
-    __shared__ int overflow, axis_bits[3], cube_bits;
-    if (threadIdx.x == 0) {
-        double d[3];
-        int ov;
-        voxel_batch_dims(b, bbox, voxel, d, &ov);
-        if (bits_out && blockIdx.x == 0) *bits_out = voxel_batch_key_bits(b, d, ov);      // speculated width: the caller checks it afterwards
-        dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2];
-        int ab[3], cb = 0;
-        voxel_batch_axis_bits(d, ab);
-        axis_bits[0] = ab[0]; axis_bits[1] = ab[1]; axis_bits[2] = ab[2];
-        while ((1 << cb) < b.count) ++cb;
-        cube_bits = voxel_hilbert_cube_bits(ab, cb);
-        overflow = (ov || (b.morton && voxel_hilbert_key_bits(ab, cube_bits) + cb > 64)) ? 1 : 0;
-    }
-    __syncthreads();
-    const uint64_t DX = (uint64_t)dims[0], DY = (uint64_t)dims[1], DZ = (uint64_t)dims[2];
-    const int64_t total = b.off[b.count];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = voxel_batch_cloud(b, i);
-        const float *pts = b.pts[c];
-        const int64_t j = i - b.off[c];
-        const double ox = bbox[8 * c] - voxel * 0.5, oy = bbox[8 * c + 1] - voxel * 0.5, oz = bbox[8 * c + 2] - voxel * 0.5;
-        double fx = floor(((double)pts[3 * j] - ox) / voxel);
-        double fy = floor(((double)pts[3 * j + 1] - oy) / voxel);
-        double fz = floor(((double)pts[3 * j + 2] - oz) / voxel);
-        const bool bad = overflow || !(fx >= 0.0) || !(fy >= 0.0) || !(fz >= 0.0) || fx >= 2097152.0 || fy >= 2097152.0 || fz >= 2097152.0;
-        if (bad) { err[c] = 1; fx = fy = fz = 0.0; }
-        if (b.morton) {
-            const int ab[3] = { axis_bits[0], axis_bits[1], axis_bits[2] };
-            const int m = cube_bits;
-            keys[i] = (Key)(((uint64_t)c << voxel_hilbert_key_bits(ab, m)) | voxel_hilbert_key((uint64_t)fx, (uint64_t)fy, (uint64_t)fz, ab, m));
+// mixed radix ((c DX + ix) DY + iy) DZ + iz, or cloud | Hilbert key, over the boxes bbox[8 c ..]; a bad index sets err[c].  The
+// block's first thread works the layout out once; bits_out: the speculated width's check (the caller compares afterwards)
+template <class Key> struct BatchKeys {
+    struct Grid {
+        uint64_t DX, DY, DZ;
+        int overflow, morton, ab[3], m;
+    };
+    Key *keys;
+    int32_t *err, *bits_out;
+    __device__ __forceinline__ Grid grid(const VoxelBatch &b, const double *__restrict__ bbox, double voxel) const
+    {
+        __shared__ double dims[3];
+        __shared__ int overflow, axis_bits[3], cube_bits;
+        if (threadIdx.x == 0) {
+            double d[3];
+            int ov;
+            voxel_batch_dims(b, bbox, voxel, d, &ov);
+            if (bits_out && blockIdx.x == 0) *bits_out = voxel_batch_key_bits(b, d, ov);
+            dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2];
+            int ab[3], cb = 0;
+            voxel_batch_axis_bits(d, ab);
+            axis_bits[0] = ab[0]; axis_bits[1] = ab[1]; axis_bits[2] = ab[2];
+            while ((1 << cb) < b.count) ++cb;
+            cube_bits = voxel_hilbert_cube_bits(ab, cb);
+            overflow = (ov || (b.morton && voxel_hilbert_key_bits(ab, cube_bits) + cb > 64)) ? 1 : 0;
         }
-        else keys[i] = (Key)((((uint64_t)c * DX + (uint64_t)fx) * DY + (uint64_t)fy) * DZ + (uint64_t)fz);
-        vals[i] = (int32_t)i;
+        __syncthreads();
+        return Grid{ (uint64_t)dims[0], (uint64_t)dims[1], (uint64_t)dims[2], overflow, b.morton, { axis_bits[0], axis_bits[1], axis_bits[2] }, cube_bits };
     }
-}
+    __device__ __forceinline__ void put(const Grid &g, const double *__restrict__ bbox, double voxel, int64_t i, int c, const double q[3]) const
+    {
+        double f[3];
+        const bool bad = voxel_cell(q, bbox + 8 * c, voxel, f) || g.overflow;
+        if (bad) { err[c] = 1; f[0] = f[1] = f[2] = 0.0; }
+        if (g.morton)
+            keys[i] = (Key)(((uint64_t)c << voxel_hilbert_key_bits(g.ab, g.m)) | voxel_hilbert_key((uint64_t)f[0], (uint64_t)f[1], (uint64_t)f[2], g.ab, g.m));
+        else keys[i] = (Key)((((uint64_t)c * g.DX + (uint64_t)f[0]) * g.DY + (uint64_t)f[1]) * g.DZ + (uint64_t)f[2]);
+    }
+};
 // head[c] = number of voxels (segment heads) before cloud c in the sorted array; d_counts[c] = voxels of cloud c
 __global__ __launch_bounds__(64) void voxel_batch_locate_kernel(VoxelBatch b, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ d_total,
                                                                 const int32_t *__restrict__ err, int32_t *__restrict__ head, int32_t *__restrict__ d_counts)
@@ -368,72 +453,15 @@ __global__ __launch_bounds__(256) void voxel_batch_mean_kernel(VoxelBatch b, con
     const int64_t total = b.off[b.count];
     for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < m_total; m += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s0 = seg_start[m], s1 = (m + 1 < m_total) ? seg_start[m + 1] : total;
-        const int c = voxel_batch_cloud(b, s0);      // the sorted array keeps the clouds' ranges: position s0 tells the cloud
-        const float *pts = b.pts[c], *col = b.col[c];
-        const int64_t base = b.off[c];
-        double sp[3] = { 0, 0, 0 }, sc[3] = { 0, 0, 0 };
-        for (int64_t s = s0; s < s1; s += 8) {       // loads of 8 points issued together, sums sequential (as voxel_mean_kernel)
-            const int cnt = (int)(s1 - s < 8 ? s1 - s : 8);
-            int64_t p[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[k] = k < cnt ? (int64_t)vals[s + k] - base : -1;
-            float vp[8][3], vc[8][3];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    vp[k][a] = pts[3 * p[k] + a];
-                    if (col) vc[k][a] = col[3 * p[k] + a];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    sp[a] += (double)vp[k][a];
-                    if (col) sc[a] += (double)vc[k][a];
-                }
-            }
-        }
-        const double cn = (double)(s1 - s0);
+        const int c = b.cloud_of(s0);                // the sorted array keeps the clouds' ranges: position s0 tells the cloud
+        const StoredLoad load = { b.pts[c], b.col[c], nullptr, b.off[c] };
+        double sp[3] = { 0, 0, 0 }, sc[3] = { 0, 0, 0 }, sn[3];
+        voxel_segment_sum<false>(vals, s0, s1, load, sp, sc, sn);
         const int64_t o = m - head[c];
-        float *opts = b.opts[c], *ocol = b.ocol[c];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            opts[3 * o + a] = (float)(sp[a] / cn);
-            if (col && ocol) ocol[3 * o + a] = (float)(sc[a] / cn);
-        }
+        voxel_write_row(sp, sc, (double)(s1 - s0), b.opts[c] + 3 * o, (load.col && b.ocol[c]) ? b.ocol[c] + 3 * o : nullptr);
     }
 }
 
-struct VoxelBatchScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out, *seg_start, *counts, *err, *head, *d_total;
-    double *part, *bbox;
-    char *sort_tmp;
-    size_t sort_bytes;
-    RadixScratch rx;            // the hand-written sort (keys of at most 32 bits, total <= kRadixMaxPairs)
-    char *counts_end;
-};
-static void voxel_batch_carve(Arena &a, int64_t total, VoxelBatchScratch *s)
-{
-    const size_t nn = (size_t)(total > 0 ? total : 1);
-    s->keys_in = a.get<uint64_t>(nn); s->keys_out = a.get<uint64_t>(nn);
-    s->vals_in = a.get<int32_t>(nn); s->vals_out = a.get<int32_t>(nn);
-    s->seg_start = a.get<int32_t>(nn);
-    s->err = a.get<int32_t>(kVoxelBatchMax);
-    s->head = a.get<int32_t>(kVoxelBatchMax + 1);
-    s->d_total = a.get<int32_t>(1);
-    s->part = a.get<double>((size_t)kVoxelBatchMax * kVoxelBatchBboxBlocks * 6);
-    s->bbox = a.get<double>((size_t)kVoxelBatchMax * 8);
-    s->sort_bytes = memo_bytes(5, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, 64, (hipStream_t) nullptr); return b; });
-    s->sort_tmp = a.get<char>(s->sort_bytes);
-    radix_carve(a, total <= kRadixMaxPairs ? total : kRadixMaxPairs, &s->rx);      // unconditional: the workspace size stays monotonic in the point count
-    s->counts = a.get<int32_t>((size_t)compact_ws_ints(total));          // right behind the sort's cleared histograms: one memset for both
-    s->counts_end = reinterpret_cast<char *>(s->counts + (size_t)compact_ws_ints(total));
-}
 // spec_bits > 0 (frame loop): the key width is NOT read back -- the sort covers spec_bits bits and *d_bits receives the width the
 // batch really needs; the caller compares the two after its own read-back of the counts and repeats the call with spec_bits = 0
 // when the speculation was too narrow (the outputs of that call are garbage).
@@ -441,11 +469,14 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
                             int32_t *d_bits = nullptr)
 {
     const int64_t total = b.off[b.count];
-    VoxelBatchScratch s;
-    voxel_batch_carve(a, total, &s);
+    VoxelScratch s;
+    voxel_carve(a, total, kBatchCarve, &s);
     KPX_ARENA_CHECK(a);
-    hipLaunchKernelGGL(voxel_batch_bbox_partial_kernel, dim3(kVoxelBatchBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
-    hipLaunchKernelGGL(voxel_batch_bbox_final_kernel, dim3(b.count), dim3(64), 0, st, s.part, s.bbox, s.err);
+    BoxDst boxes;
+    for (int c = 0; c < kVoxelBatchMax; ++c) boxes.box[c] = s.bbox + 8 * c;
+    boxes.err = s.err;
+    hipLaunchKernelGGL((cloud_bbox_partial_kernel<VoxelBatch, StoredPoint, float, kVoxelBatchBboxBlocks>), dim3(kVoxelBatchBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
+    hipLaunchKernelGGL(cloud_bbox_final_kernel<kVoxelBatchBboxBlocks>, dim3(b.count), dim3(64), 0, st, (const double *)s.part, boxes);
     const int nb = (int)(cdiv(total, 256) > 4096 ? 4096 : cdiv(total, 256));
     int end_bit = 64;
     int32_t *bits_out = nullptr;
@@ -467,25 +498,15 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
     } else if (d_bits) {
         hipLaunchKernelGGL(voxel_batch_bits_kernel, dim3(1), dim3(1), 0, st, b, s.bbox, voxel, d_bits);      // for the caller's next speculation
     }
-    size_t bytes = s.sort_bytes;
     int rc;
     if (end_bit <= 32) {
-        uint32_t *k_in = reinterpret_cast<uint32_t *>(s.keys_in), *k_out = reinterpret_cast<uint32_t *>(s.keys_out);
-        hipLaunchKernelGGL(voxel_batch_key_kernel<uint32_t>, dim3(nb), dim3(256), 0, st, b, s.bbox, voxel, k_in, s.vals_in, s.err, bits_out);
-        static const bool vendor_sort = [] { const char *e = getenv("KPX_RADIX"); return e && e[0] == '0'; }();       // A/B switch
-        bool cleared = false;
-        if (total <= kRadixMaxPairs && !vendor_sort) {
-            rc = radix_sort_pairs_u32(s.rx, k_in, k_out, s.vals_in, s.vals_out, total, end_bit, st, s.counts_end);
-            if (rc) return rc;
-            cleared = true;
-        } else {
-            KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, bytes, k_in, k_out, s.vals_in, s.vals_out, (int)total, 0, end_bit, st));
-        }
-        rc = compact(HeadPredT<uint32_t>{ k_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, s.d_total, st, cleared);
+        hipLaunchKernelGGL((voxel_key_kernel<VoxelBatch, StoredPoint, BatchKeys<uint32_t>>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
+                           BatchKeys<uint32_t>{ reinterpret_cast<uint32_t *>(s.keys_in), s.err, bits_out }, s.vals_in);
+        rc = voxel_sort_and_heads<uint32_t>(s, total, end_bit, s.d_total, st);
     } else {
-        hipLaunchKernelGGL(voxel_batch_key_kernel<uint64_t>, dim3(nb), dim3(256), 0, st, b, s.bbox, voxel, s.keys_in, s.vals_in, s.err, bits_out);
-        KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)total, 0, end_bit, st));
-        rc = compact(HeadPred{ s.keys_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, s.d_total, st);
+        hipLaunchKernelGGL((voxel_key_kernel<VoxelBatch, StoredPoint, BatchKeys<uint64_t>>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
+                           BatchKeys<uint64_t>{ s.keys_in, s.err, bits_out }, s.vals_in);
+        rc = voxel_sort_and_heads<uint64_t>(s, total, end_bit, s.d_total, st);
     }
     if (rc) return rc;
     hipLaunchKernelGGL(voxel_batch_locate_kernel, dim3(1), dim3(64), 0, st, b, s.seg_start, s.d_total, s.err, s.head, d_counts);
@@ -499,57 +520,17 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
 // down-sampled.  The reference keeps the moved points as float64 arrays; storing them as float32 first would move points
 // that lie within 2^-24 |x| of a voxel face into the neighbouring voxel (measured: ~1e-5 of the points,
 // oracle/storage_deviation.py).  So the stack is never materialised: the bounding box, the voxel index and the per-voxel
-// sums all use the fp64 value p' = AC1(T[c], p), recomputed from the float32 sensor point wherever it is needed (9 fma).
-// That is also one pass less over HBM and three launches less per sensor than transform -> concat -> voxel.
+// sums all use the fp64 value p' = AC1(T[c], p), recomputed from the float32 sensor point wherever it is needed (9 fma:
+// MovedPoint).  That is also one pass less over HBM and three launches less per sensor than transform -> concat -> voxel.
 constexpr int kFuseMax = 16;
 constexpr int kFuseBboxBlocks = 32;
-struct FuseBatch {
-    const float *pts[kFuseMax];
+constexpr VoxelCarve kFuseCarve = { kFuseMax, kFuseBboxBlocks, false, true, 6, 63 };
+struct FuseBatch : CloudSet<kFuseMax> {
     const float *col[kFuseMax];
-    int64_t off[kFuseMax + 1];
     double T[kFuseMax][12];               // rows of [R | t]
     const double *dT[kFuseMax];           // non-null: the cloud's 4x4 (row-major, first 12 entries used) is read from device memory instead --
                                           // the frame loop hands over the registrations' results without a host round trip
-    int32_t count;
 };
-__device__ __forceinline__ int fuse_cloud(const FuseBatch &b, int64_t i)
-{
-    int c = 0;
-#pragma unroll
-    for (int k = 1; k < kFuseMax; ++k) c += (k < b.count && i >= b.off[k]) ? 1 : 0;
-    return c;
-}
-__device__ __forceinline__ void fuse_point(const FuseBatch &b, int c, int64_t j, double o[3])
-{
-    const float *p = b.pts[c] + 3 * j;
-    const double x = p[0], y = p[1], z = p[2];
-    const double *T = b.dT[c] ? b.dT[c] : b.T[c];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = fma(T[4 * k], x, fma(T[4 * k + 1], y, fma(T[4 * k + 2], z, T[4 * k + 3])));
-}
-__global__ __launch_bounds__(256) void fuse_bbox_partial_kernel(FuseBatch b, double *__restrict__ part)
-{
-    __shared__ double sh[6][4];
-    const int c = blockIdx.y;
-    const int64_t n = b.off[c + 1] - b.off[c];
-    double mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double q[3];
-        fuse_point(b, c, i, q);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fmin(mn[a], q[a]); mx[a] = fmax(mx[a], q[a]); }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fmin(v, sh[threadIdx.x][w]) : fmax(v, sh[threadIdx.x][w]);
-        part[((int64_t)c * kFuseBboxBlocks + blockIdx.x) * 6 + threadIdx.x] = v;
-    }
-}
 // folds the count x kFuseBboxBlocks partial boxes (min / max: exact, order-free) -> bbox[0..5]; zeroes the error word
 __global__ __launch_bounds__(64) void fuse_bbox_final_kernel(const double *__restrict__ part, int rows, double *__restrict__ bbox, int32_t *__restrict__ err)
 {
@@ -566,33 +547,17 @@ __global__ __launch_bounds__(64) void fuse_bbox_final_kernel(const double *__res
         *err = 0;
     }
 }
-__global__ __launch_bounds__(256) void fuse_key_kernel(FuseBatch b, const double *__restrict__ bbox, double voxel, uint64_t *__restrict__ keys,
-                                                       int32_t *__restrict__ vals, int32_t *__restrict__ err)
-{
-    const double ox = bbox[0] - voxel * 0.5, oy = bbox[1] - voxel * 0.5, oz = bbox[2] - voxel * 0.5;
-    const int64_t total = b.off[b.count];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = fuse_cloud(b, i);
-        double q[3];
-        fuse_point(b, c, i - b.off[c], q);
-        double fx = floor((q[0] - ox) / voxel), fy = floor((q[1] - oy) / voxel), fz = floor((q[2] - oz) / voxel);
-        const bool bad = !(fx >= 0.0) || !(fy >= 0.0) || !(fz >= 0.0) || fx >= 2097152.0 || fy >= 2097152.0 || fz >= 2097152.0;
-        if (bad) { *err = 1; fx = fy = fz = 0.0; }
-        keys[i] = ((uint64_t)fx << 42) | ((uint64_t)fy << 21) | (uint64_t)fz;
-        vals[i] = (int32_t)i;
-    }
-}
-// The same keys as 32-bit mixed-radix words (ix DY + iy) DZ + iz over the grid's own extent -- the SAME order (ascending ix, iy, iz)
+// The fused cloud's keys as 32-bit mixed-radix words (ix DY + iy) DZ + iz over the grid's own extent -- the SAME order (ascending ix, iy, iz)
 // in as few bits as the fused cloud needs (a person at 10 mm voxels: ~23), for the library's own radix sort: three 8-bit passes of two
 // launches each where the vendor's merge sort of the 63-bit keys took seven launches with host work between them (~150 us of a frame
-// under load, profiles/r05/overlap_timeline_native_stream.txt).  bits_out: the width this cloud needs (> 32: the keys written here
-// are useless and the caller takes the 63-bit path).
+// under load, profiles/r05/overlap_timeline_native_stream.txt).  The width this cloud needs (> 32: the keys written are useless and
+// the caller takes the 63-bit path):
 __device__ __forceinline__ int fuse_key_bits(const double *__restrict__ bbox, double voxel, double d[3], bool *sane_out)
 {
-    const double o[3] = { bbox[0] - voxel * 0.5, bbox[1] - voxel * 0.5, bbox[2] - voxel * 0.5 };
+    (void)voxel_cell(bbox + 3, bbox, voxel, d);      // the cell of the box's far corner
 #pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = floor((bbox[3 + a] - o[a]) / voxel) + 1.0;
-    const bool sane = d[0] >= 1.0 && d[1] >= 1.0 && d[2] >= 1.0 && d[0] < 2097152.0 && d[1] < 2097152.0 && d[2] < 2097152.0;      // (NaN / empty boxes: not sane)
+    for (int a = 0; a < 3; ++a) d[a] += 1.0;
+    const bool sane = d[0] >= 1.0 && d[1] >= 1.0 && d[2] >= 1.0 && d[0] < kVoxelAxisCells && d[1] < kVoxelAxisCells && d[2] < kVoxelAxisCells;      // (NaN / empty boxes: not sane)
     int bits = 64;
     if (sane && d[0] * d[1] * d[2] < 18446744073709551616.0) {
         const unsigned long long range = (unsigned long long)d[0] * (unsigned long long)d[1] * (unsigned long long)d[2];
@@ -608,27 +573,46 @@ __global__ void fuse_bits_kernel(const double *__restrict__ bbox, double voxel, 
     bool sane;
     *bits_out = fuse_key_bits(bbox, voxel, d, &sane);
 }
-__global__ __launch_bounds__(256) void fuse_key32_kernel(FuseBatch b, const double *__restrict__ bbox, double voxel, uint32_t *__restrict__ keys,
-                                                         int32_t *__restrict__ vals, int32_t *__restrict__ bits_out)
-{
-    const double ox = bbox[0] - voxel * 0.5, oy = bbox[1] - voxel * 0.5, oz = bbox[2] - voxel * 0.5;
-    double dd[3];
-    bool sane;
-    const int bits = fuse_key_bits(bbox, voxel, dd, &sane);
-    const double dx = dd[0], dy = dd[1], dz = dd[2];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *bits_out = bits;
-    const unsigned long long DY = sane ? (unsigned long long)dy : 1ull, DZ = sane ? (unsigned long long)dz : 1ull;
-    const int64_t total = b.off[b.count];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = fuse_cloud(b, i);
-        double q[3];
-        fuse_point(b, c, i - b.off[c], q);
-        double fx = floor((q[0] - ox) / voxel), fy = floor((q[1] - oy) / voxel), fz = floor((q[2] - oz) / voxel);
-        if (!(fx >= 0.0) || !(fy >= 0.0) || !(fz >= 0.0) || !(fx < dx) || !(fy < dy) || !(fz < dz)) fx = fy = fz = 0.0;      // (only with bits = 64: caller redoes)
-        keys[i] = (uint32_t)(((unsigned long long)fx * DY + (unsigned long long)fy) * DZ + (unsigned long long)fz);
-        vals[i] = (int32_t)i;
+// an index outside the grid's own extent becomes cell 0 and raises nothing: that happens only with *bits_out = 64, and the caller redoes
+struct ExtentKeys32 {
+    struct Grid {
+        double d[3];
+        unsigned long long DY, DZ;
+    };
+    uint32_t *keys;
+    int32_t *bits_out;
+    template <class Set> __device__ __forceinline__ Grid grid(const Set &, const double *__restrict__ bbox, double voxel) const
+    {
+        Grid g;
+        bool sane;
+        const int bits = fuse_key_bits(bbox, voxel, g.d, &sane);
+        if (blockIdx.x == 0 && threadIdx.x == 0) *bits_out = bits;
+        g.DY = sane ? (unsigned long long)g.d[1] : 1ull;
+        g.DZ = sane ? (unsigned long long)g.d[2] : 1ull;
+        return g;
     }
-}
+    __device__ __forceinline__ void put(const Grid &g, const double *__restrict__ bbox, double voxel, int64_t i, int, const double q[3]) const
+    {
+        double f[3];
+        if (voxel_cell(q, bbox, voxel, f, g.d)) f[0] = f[1] = f[2] = 0.0;
+        keys[i] = (uint32_t)(((unsigned long long)f[0] * g.DY + (unsigned long long)f[1]) * g.DZ + (unsigned long long)f[2]);
+    }
+};
+// the moved point with concatenated index p and its colour (0 where its cloud has none)
+struct MovedLoad {
+    using Coord = double;
+    const FuseBatch &b;
+    __device__ __forceinline__ bool has_col() const { return true; }
+    __device__ __forceinline__ void operator()(int64_t p, double v[3], float c[3], float *) const
+    {
+        const int cl = b.cloud_of(p);
+        const int64_t j = p - b.off[cl];
+        MovedPoint()(b, cl, j, v);
+        const float *col = b.col[cl];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = col ? col[3 * j + a] : 0.0f;
+    }
+};
 __global__ __launch_bounds__(256) void fuse_mean_kernel(FuseBatch b, const int32_t *__restrict__ vals, const int32_t *__restrict__ seg_start,
                                                         int32_t *__restrict__ d_count, const int32_t *__restrict__ err, float *__restrict__ opts,
                                                         float *__restrict__ ocol)
@@ -638,65 +622,10 @@ __global__ __launch_bounds__(256) void fuse_mean_kernel(FuseBatch b, const int32
     const int64_t total = b.off[b.count];
     for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < m_total; m += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s0 = seg_start[m], s1 = (m + 1 < m_total) ? seg_start[m + 1] : total;
-        double sp[3] = { 0, 0, 0 }, sc[3] = { 0, 0, 0 };
-        for (int64_t s = s0; s < s1; s += 8) {       // loads of 8 points issued together, sums sequential in ascending stacked index
-            const int cnt = (int)(s1 - s < 8 ? s1 - s : 8);
-            int64_t p[8];
-            int cl[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                p[k] = k < cnt ? (int64_t)vals[s + k] : -1;
-                cl[k] = p[k] >= 0 ? fuse_cloud(b, p[k]) : 0;
-            }
-            double vq[8][3];
-            float vc[8][3];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-                const int64_t j = p[k] - b.off[cl[k]];
-                fuse_point(b, cl[k], j, vq[k]);
-                const float *col = b.col[cl[k]];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) vc[k][a] = col ? col[3 * j + a] : 0.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (p[k] < 0) continue;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { sp[a] += vq[k][a]; sc[a] += (double)vc[k][a]; }
-            }
-        }
-        const double cn = (double)(s1 - s0);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            opts[3 * m + a] = (float)(sp[a] / cn);
-            if (ocol) ocol[3 * m + a] = (float)(sc[a] / cn);
-        }
+        double sp[3] = { 0, 0, 0 }, sc[3] = { 0, 0, 0 }, sn[3];
+        voxel_segment_sum<false>(vals, s0, s1, MovedLoad{ b }, sp, sc, sn);
+        voxel_write_row(sp, sc, (double)(s1 - s0), opts + 3 * m, ocol ? ocol + 3 * m : nullptr);
     }
-}
-struct FuseScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out, *seg_start, *counts, *err;
-    double *part, *bbox;
-    char *sort_tmp;
-    size_t sort_bytes;
-    RadixScratch rx;            // the library's own sort (32-bit keys, total <= kRadixMaxPairs): the speculative path of the frame loop
-    char *counts_end;
-};
-static void fuse_carve(Arena &a, int64_t total, FuseScratch *s)
-{
-    const size_t nn = (size_t)(total > 0 ? total : 1);
-    s->keys_in = a.get<uint64_t>(nn); s->keys_out = a.get<uint64_t>(nn);
-    s->vals_in = a.get<int32_t>(nn); s->vals_out = a.get<int32_t>(nn);
-    s->seg_start = a.get<int32_t>(nn);
-    radix_carve(a, total <= kRadixMaxPairs ? total : kRadixMaxPairs, &s->rx);
-    s->counts = a.get<int32_t>((size_t)compact_ws_ints(total));          // right behind the sort's cleared histograms: one memset for both
-    s->counts_end = reinterpret_cast<char *>(s->counts + (size_t)compact_ws_ints(total));
-    s->err = a.get<int32_t>(1);
-    s->part = a.get<double>((size_t)kFuseMax * kFuseBboxBlocks * 6);
-    s->bbox = a.get<double>(8);
-    s->sort_bytes = memo_bytes(6, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, 63, (hipStream_t) nullptr); return b; });
-    s->sort_tmp = a.get<char>(s->sort_bytes);
 }
 // spec_bits > 0 (frame loop): the fused cloud's keys are taken to fit `spec_bits` <= 32 bits -- the width its slot's previous frame
 // needed -- and sorted as 32-bit words by the library's own radix sort; *d_bits (pinned host memory, written by the key kernel) receives
@@ -706,34 +635,28 @@ static int fuse_voxel_impl(const FuseBatch &b, double voxel, float *opts, float 
                            int32_t *d_bits = nullptr)
 {
     const int64_t total = b.off[b.count];
-    FuseScratch s;
-    fuse_carve(a, total, &s);
+    VoxelScratch s;
+    voxel_carve(a, total, kFuseCarve, &s);
     KPX_ARENA_CHECK(a);
-    hipLaunchKernelGGL(fuse_bbox_partial_kernel, dim3(kFuseBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
+    hipLaunchKernelGGL((cloud_bbox_partial_kernel<FuseBatch, MovedPoint, double, kFuseBboxBlocks>), dim3(kFuseBboxBlocks, b.count), dim3(256), 0, st, b, s.part);
     hipLaunchKernelGGL(fuse_bbox_final_kernel, dim3(1), dim3(64), 0, st, s.part, b.count * kFuseBboxBlocks, s.bbox, s.err);
     const int nb = (int)(cdiv(total, 256) > 4096 ? 4096 : cdiv(total, 256));
+    int rc;
     if (spec_bits > 0 && spec_bits <= 32 && d_bits && total <= kRadixMaxPairs) {
-        uint32_t *k_in = reinterpret_cast<uint32_t *>(s.keys_in), *k_out = reinterpret_cast<uint32_t *>(s.keys_out);
-        hipLaunchKernelGGL(fuse_key32_kernel, dim3(nb), dim3(256), 0, st, b, s.bbox, voxel, k_in, s.vals_in, d_bits);
-        int rc = radix_sort_pairs_u32(s.rx, k_in, k_out, s.vals_in, s.vals_out, total, spec_bits, st, s.counts_end);
-        if (rc) return rc;
-        rc = compact(HeadPredT<uint32_t>{ k_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, d_count, st, true);
-        if (rc) return rc;
-        hipLaunchKernelGGL(fuse_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out, s.seg_start, d_count, s.err, opts, ocol);
-        KPX_LAUNCH_CHECK();
-        return KPX_OK;
+        hipLaunchKernelGGL((voxel_key_kernel<FuseBatch, MovedPoint, ExtentKeys32>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
+                           ExtentKeys32{ reinterpret_cast<uint32_t *>(s.keys_in), d_bits }, s.vals_in);
+        rc = voxel_sort_and_heads<uint32_t>(s, total, spec_bits, d_count, st);
+    } else {
+        if (d_bits) hipLaunchKernelGGL(fuse_bits_kernel, dim3(1), dim3(1), 0, st, s.bbox, voxel, d_bits);      // for the caller's next speculation
+        hipLaunchKernelGGL((voxel_key_kernel<FuseBatch, MovedPoint, FixedKeys>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
+                           FixedKeys{ s.keys_in, s.err }, s.vals_in);
+        rc = voxel_sort_and_heads<uint64_t>(s, total, 63, d_count, st);
     }
-    if (d_bits) hipLaunchKernelGGL(fuse_bits_kernel, dim3(1), dim3(1), 0, st, s.bbox, voxel, d_bits);      // for the caller's next speculation
-    hipLaunchKernelGGL(fuse_key_kernel, dim3(nb), dim3(256), 0, st, b, s.bbox, voxel, s.keys_in, s.vals_in, s.err);
-    size_t bytes = s.sort_bytes;
-    KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)total, 0, 63, st));
-    int rc = compact(HeadPred{ s.keys_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, d_count, st);
     if (rc) return rc;
     hipLaunchKernelGGL(fuse_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out, s.seg_start, d_count, s.err, opts, ocol);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
-
 }  // namespace kpx
 
 using namespace kpx;
@@ -741,8 +664,8 @@ using namespace kpx;
 KPX_EXPORT size_t kpx_fuse_voxel_workspace_bytes(int64_t total)
 {
     Arena a(nullptr, 0);
-    FuseScratch s;
-    fuse_carve(a, total, &s);
+    VoxelScratch s;
+    voxel_carve(a, total, kFuseCarve, &s);
     return a.off;
 }
 KPX_EXPORT int kpx_fuse_voxel_downsample(int32_t count, const float *const *h_pts, const float *const *h_col, const int64_t *h_n,
@@ -787,12 +710,7 @@ int kpx::fuse_voxel_downsample_dev(int32_t count, const float *const *h_pts, con
 
 KPX_EXPORT size_t kpx_voxel_workspace_bytes(int64_t n)
 {
-    Arena a(nullptr, 0);
-    voxel_impl(nullptr, nullptr, nullptr, n, 1.0, nullptr, nullptr, nullptr, nullptr, a, nullptr);
-    Arena one(nullptr, 0);
-    VoxelBatchScratch s;
-    voxel_batch_carve(one, n, &s);
-    return a.off > one.off ? a.off : one.off;
+    return kpx_voxel_batch_workspace_bytes(1, &n);
 }
 KPX_EXPORT int kpx_voxel_downsample(const float *pts, const float *col, const float *nrm, int64_t n, double voxel,
                                     float *opts, float *ocol, float *onrm, int32_t *d_count, void *ws, size_t ws_bytes,
@@ -810,18 +728,7 @@ KPX_EXPORT int kpx_voxel_downsample(const float *pts, const float *col, const fl
     // vendor-sort path below remains for clouds with normals.  KPX_VOXEL_SINGLE=0: A/B switch.
     static const bool single_batch = [] { const char *e = getenv("KPX_VOXEL_SINGLE"); return !(e && e[0] == '0'); }();
     if (!nrm && single_batch) {
-        VoxelBatch b;
-        b.count = 1;
-        b.morton = 0;
-        b.off[0] = 0;
-        for (int i = 0; i < kVoxelBatchMax; ++i) {
-            b.pts[i] = i == 0 ? pts : nullptr;
-            b.col[i] = i == 0 ? col : nullptr;
-            b.opts[i] = i == 0 ? opts : nullptr;
-            b.ocol[i] = (i == 0 && col) ? ocol : nullptr;
-            b.off[i + 1] = n;
-        }
-        return voxel_batch_impl(b, voxel, d_count, a, st);
+        return voxel_batch_impl(voxel_batch_of(&pts, &col, &n, &opts, col ? &ocol : nullptr, 0, 1, false), voxel, d_count, a, st);
     }
     return voxel_impl(pts, col, nrm, n, voxel, opts, ocol, onrm, d_count, a, st);
 }
@@ -829,15 +736,14 @@ KPX_EXPORT int kpx_voxel_downsample(const float *pts, const float *col, const fl
 KPX_EXPORT size_t kpx_voxel_batch_workspace_bytes(int32_t count, const int64_t *h_n)
 {
     if (count < 1 || !h_n) return 0;
-    Arena a(nullptr, 0);
+    Arena a(nullptr, 0), one(nullptr, 0);        // cloud by cloud on the lanes (plain form), or one pass
+    VoxelScratch s;
     int64_t total = 0;
     for (int i = 0; i < count; ++i) {
-        voxel_impl(nullptr, nullptr, nullptr, h_n[i], 1.0, nullptr, nullptr, nullptr, nullptr, a, nullptr);
+        voxel_carve(a, h_n[i], kPlainCarve, &s);
         total += h_n[i] > 0 ? h_n[i] : 0;
     }
-    Arena one(nullptr, 0);
-    VoxelBatchScratch s;
-    voxel_batch_carve(one, total, &s);
+    voxel_carve(one, total, kBatchCarve, &s);
     return a.off > one.off ? a.off : one.off;
 }
 KPX_EXPORT int kpx_voxel_downsample_batch(int32_t count, const float *const *h_pts, const float *const *h_col, const int64_t *h_n,
@@ -861,20 +767,8 @@ int kpx::voxel_downsample_batch_spec(int32_t count, const float *const *h_pts, c
     // (the curve order exists in the one-pass form only; the other forms keep the row-major order -- callers that asked for it only
     // lose locality, never correctness)
     if (count <= kVoxelBatchMax && total > 0 && total < ((int64_t)1 << 31)) {         // one pass over the concatenated clouds
-        VoxelBatch b;
-        b.count = count;
-        b.morton = morton ? 1 : 0;
-        b.off[0] = 0;
-        for (int i = 0; i < kVoxelBatchMax; ++i) {
-            const bool on = i < count;
-            b.pts[i] = on ? h_pts[i] : nullptr;
-            b.col[i] = (on && h_col) ? h_col[i] : nullptr;
-            b.opts[i] = on ? h_opts[i] : nullptr;
-            b.ocol[i] = (on && h_col && h_ocol) ? h_ocol[i] : nullptr;
-            b.off[i + 1] = b.off[i] + (on ? h_n[i] : 0);
-        }
         Arena one(ws, ws_bytes);
-        return voxel_batch_impl(b, voxel, d_counts, one, st, spec_bits, d_bits);
+        return voxel_batch_impl(voxel_batch_of(h_pts, h_col, h_n, h_opts, h_ocol, 0, count, morton), voxel, d_counts, one, st, spec_bits, d_bits);
     }
     if (d_bits) KPX_HIP(hipMemsetAsync(d_bits, 0, sizeof(int32_t), st));         // the other forms do not speculate: width 0 = "fine"
     if (count > kVoxelBatchMax && total > 0) {
@@ -899,20 +793,8 @@ int kpx::voxel_downsample_batch_spec(int32_t count, const float *const *h_pts, c
                 int64_t gt = 0;
                 for (int i = 0; i < gc; ++i) gt += h_n[g0 + i];
                 if (gt == 0) { KPX_HIP(hipMemsetAsync(d_counts + g0, 0, (size_t)gc * sizeof(int32_t), st)); continue; }
-                VoxelBatch b;
-                b.count = gc;
-                b.morton = 0;
-                b.off[0] = 0;
-                for (int i = 0; i < kVoxelBatchMax; ++i) {
-                    const bool on = i < gc;
-                    b.pts[i] = on ? h_pts[g0 + i] : nullptr;
-                    b.col[i] = (on && h_col) ? h_col[g0 + i] : nullptr;
-                    b.opts[i] = on ? h_opts[g0 + i] : nullptr;
-                    b.ocol[i] = (on && h_col && h_ocol) ? h_ocol[g0 + i] : nullptr;
-                    b.off[i + 1] = b.off[i] + (on ? h_n[g0 + i] : 0);
-                }
                 Arena one(ws, ws_bytes);
-                const int grc = voxel_batch_impl(b, voxel, d_counts + g0, one, st);
+                const int grc = voxel_batch_impl(voxel_batch_of(h_pts, h_col, h_n, h_opts, h_ocol, g0, gc, false), voxel, d_counts + g0, one, st);
                 if (grc) return grc;
             }
             return KPX_OK;

@@ -1806,6 +1806,31 @@ def test_fuse_voxel_downsample_bit_exact(ops, oracle):
         ops.fuse_voxel_downsample(clouds, None, [np.eye(4)] * 2, 0.0)
 
 
+def test_fuse_voxel_downsample_upper_cloud_slots(ops, oracle):
+    """9 and 16 clouds: slots 8 .. 15 of the 16-wide cloud set (the other fuse tests stop at 5 clouds).  Ragged sizes from
+    {0, 1, 7, 300}, an empty cloud at a middle slot and one at slot 8, a random rigid motion per cloud, colours on all or
+    none, a fine and a coarse voxel; a 17th cloud is refused"""
+    rng = np.random.default_rng(16)
+    base = synth.frame_cloud()
+    for cnt in (9, 16):
+        sizes = [int(rng.choice([0, 1, 7, 300])) for _ in range(cnt)]
+        sizes[0], sizes[cnt // 2], sizes[8] = 300, 0, 0
+        if cnt > 9:
+            sizes[9], sizes[cnt - 1] = 7, 300                            # points behind the empty slot 8 and in the last slot
+        clouds = [base[rng.choice(len(base), n, replace=False)] for n in sizes]
+        Ts = [synth.perturb(np.eye(4), deg=float(rng.uniform(0, 40)), mm=float(rng.uniform(0, 900)), seed=int(rng.integers(1 << 30)))
+              for _ in range(cnt)]
+        for cols in (None, [rng.random((n, 3)).astype(np.float32) for n in sizes]):
+            for voxel in (10.0, 400.0):
+                gp, gc = ops.fuse_voxel_downsample(clouds, cols, Ts, voxel)
+                rp, rc = oracle.fuse_voxel_downsample(clouds, cols, Ts, voxel)
+                assert 0 < len(rp) <= sum(sizes)
+                assert np.array_equal(npy(gp), rp), (cnt, sizes, voxel)
+                assert (cols is None and gc is None and rc is None) or np.array_equal(npy(gc), rc), (cnt, sizes, voxel)
+    with pytest.raises(Exception, match="1 .. 16 clouds"):
+        ops.fuse_voxel_downsample([base[:7]] * 17, None, [np.eye(4)] * 17, 10.0)
+
+
 def test_fused_voxel_membership_is_the_float64_path(ops, oracle):
     """what the fused pass is for: with float32 storage of the MOVED points a few points per 10^5 change voxel; the fused
     pass decides on the fp64 values, so its voxel count equals the oracle's float64-storage run (the reference's precision)"""
