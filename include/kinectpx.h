@@ -404,6 +404,26 @@ int kpx_ransac_corres(const float *src, int64_t n_src, const float *tgt, int64_t
                       double max_dist, int32_t ransac_n, double edge_similarity, int32_t max_iteration, double confidence,
                       uint64_t seed, double *h_result, void *ws, size_t ws_bytes, void *stream);
 
+/* Fast Global Registration (Zhou, Park, Koltun 2016; Open3D's FastGlobalRegistration.cpp; tests/fgr_ref.py is the pinned
+ * statement).  corres: i32 [n_corres][2] (source, target) on the device; an index outside its cloud is KPX_ERR_RANGE, raised
+ * before any point is read and before any output is written.  Both calls are synchronous.
+ * kpx_fgr_tuple_test: 100 n_corres trials; trial t draws three correspondences with replacement (Philox counter (0, t, 2, 0),
+ *     key = seed) and passes when l_k tuple_scale < m_k < l_k / tuple_scale for the three edge lengths l (source) and m (target).
+ *     d_pairs: i32 [3 min(maximum_tuple_count, 100 n_corres)][2], the three pairs of each of the first maximum_tuple_count
+ *     passing trials in trial order; d_count: the number of pairs written (device).
+ * kpx_fgr_optimize: both clouds normalised by their means and the largest radius (use_absolute_scale: by the means only),
+ *     iteration_number Gauss-Newton rounds under the weight (par / (|r|^2 + par))^2 in one launch, par divided by
+ *     division_factor after every fourth round while it exceeds maximum_correspondence_distance (decrease_mu).
+ *     h_result (host) f64 [20]: T source -> target in the clouds' units (16) | final par | rounds run | failed solves |
+ *     largest radius.  n_corres == 0 or iteration_number == 0: the identity. */
+size_t kpx_fgr_workspace_bytes(int64_t n_corres);
+int kpx_fgr_tuple_test(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const int32_t *corres, int64_t n_corres,
+                       double tuple_scale, int32_t maximum_tuple_count, uint64_t seed, int32_t *d_pairs, int32_t *d_count,
+                       void *ws, size_t ws_bytes, void *stream);
+int kpx_fgr_optimize(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const int32_t *corres, int64_t n_corres,
+                     double division_factor, int32_t use_absolute_scale, int32_t decrease_mu, double maximum_correspondence_distance,
+                     int32_t iteration_number, double *h_result, void *ws, size_t ws_bytes, void *stream);
+
 /* Several registrations onto ONE shared target (preprocessing/data.py:144-161 registers every sub device onto
  * the master cloud).  The target operand is prepared once; the problems' iterations are queued round-robin on
  * `stream` and each problem's convergence flag is polled through a side stream that waits only for that

@@ -86,6 +86,9 @@ SIGNATURES = {
     "kpx_feature_nn": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "kpx_ransac_workspace_bytes": (_sz, [_i64, _i64]),
     "kpx_ransac_corres": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _f64, _i32, _f64, _i32, _f64, _u64, _vp, _vp, _sz, _vp]),
+    "kpx_fgr_workspace_bytes": (_sz, [_i64]),
+    "kpx_fgr_tuple_test": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _f64, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_fgr_optimize": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _f64, _i32, _i32, _f64, _i32, _vp, _vp, _sz, _vp]),
     "kpx_sample_workspace_bytes": (_sz, [_i64]),
     "kpx_sample_points": (C.c_int, [_vp, _i64, _i64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "kpx_obb_workspace_bytes": (_sz, [_i32, _i64]),

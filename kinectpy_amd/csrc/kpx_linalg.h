@@ -120,7 +120,7 @@ __host__ __device__ __forceinline__ void kabsch_rotation(const double S[9], doub
 
 // Solve the symmetric positive (semi-)definite 6x6 system A x = b by LDL^T without pivoting
 // (Open3D: JTJ.ldlt().solve(-JTr)).  A row-major, destroyed.  Returns false if a pivot is ~0.
-__host__ __device__ __forceinline__ bool solve6_ldlt(double A[36], const double b[6], double x[6])
+template <bool kRel> __host__ __device__ __forceinline__ bool solve6_ldlt_t(double A[36], const double b[6], double x[6], double rel)
 {
     double L[36], D[6];
     for (int i = 0; i < 36; ++i) L[i] = 0.0;
@@ -129,6 +129,7 @@ __host__ __device__ __forceinline__ bool solve6_ldlt(double A[36], const double 
         for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k] * D[k];
         D[j] = d;
         if (!(fabs(d) > 1e-300)) return false;
+        if (kRel && !(fabs(d) > rel * fabs(A[6 * j + j]))) return false;
         L[6 * j + j] = 1.0;
         for (int i = j + 1; i < 6; ++i) {
             double v = A[6 * i + j];
@@ -141,6 +142,22 @@ __host__ __device__ __forceinline__ bool solve6_ldlt(double A[36], const double 
     for (int i = 0; i < 6; ++i) y[i] /= D[i];
     for (int i = 5; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < 6; ++k) v -= L[6 * k + i] * x[k]; x[i] = v; }
     return true;
+}
+__host__ __device__ __forceinline__ bool solve6_ldlt(double A[36], const double b[6], double x[6]) { return solve6_ldlt_t<false>(A, b, x, 0.0); }
+// The same with a rank test: pivot j is what column j keeps after the columns before it are taken out, so |D_j| / |A_jj| lies in
+// [0, 1] whatever the units of the unknowns; at or below `rel` the system counts as singular (a rank-deficient system leaves a
+// pivot of a few ulp there, not 0, and the plain form would divide by it).
+__host__ __device__ __forceinline__ bool solve6_ldlt_ranked(double A[36], const double b[6], double x[6], double rel) { return solve6_ldlt_t<true>(A, b, x, rel); }
+
+// U = [Rz(x2) Ry(x1) Rx(x0) | x3..5]: the first three rows, the caller sets the last (the form update_p2plane of kpx_icpsolve.h
+// builds in place; that one is left as it is so that the ICP kernels' code objects do not move)
+__device__ __forceinline__ void euler_update(const double x[6], double U[16])
+{
+    double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    // Rz(g) Ry(b) Rx(a)
+    U[0] = cg * cb; U[1] = cg * sb * sa - sg * ca; U[2] = cg * sb * ca + sg * sa; U[3] = x[3];
+    U[4] = sg * cb; U[5] = sg * sb * sa + cg * ca; U[6] = sg * sb * ca - cg * sa; U[7] = x[4];
+    U[8] = -sb;     U[9] = cb * sa;                U[10] = cb * ca;               U[11] = x[5];
 }
 
 }  // namespace kpx

@@ -287,6 +287,23 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
                                                   checkers=(), criteria=None, seed=None):
     """preprocessing/registration.py:50-57.  Open3D's RANSAC is unseeded and runs its iterations in an OpenMP
     loop; ours draws from Philox with `seed` (None -> fresh random seed) and replays the iterations in order."""
+    crit, edge, seed = _ransac_arguments(max_correspondence_distance, estimation_method, checkers, criteria, seed)
+    # the correspondences depend only on the two feature sets: execute_global_registration calls this 15 times with the
+    # same features (registration.py:46-57), so they are computed once and kept on the source Feature
+    key = (id(target_feature), bool(mutual_filter), int(ransac_n))
+    cached = getattr(source_feature, "_corr_cache", None)
+    if cached is not None and cached[0] == key and cached[2] is target_feature:
+        corres = cached[1]
+    else:
+        corres = ops.feature_correspondences(source_feature._dev, target_feature._dev, bool(mutual_filter), int(ransac_n))
+        source_feature._corr_cache = (key, corres, target_feature)
+    r = ops.ransac_corres(source._pts, target._pts, corres, float(max_correspondence_distance), int(ransac_n), edge,
+                          crit.max_iteration, crit.confidence, seed)
+    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], corres)
+
+
+def _ransac_arguments(max_correspondence_distance, estimation_method, checkers, criteria, seed):
+    """the restrictions the two RANSAC entry points share -> (criteria, edge similarity, seed)"""
     crit = criteria if criteria is not None else RANSACConvergenceCriteria()
     est = estimation_method if estimation_method is not None else TransformationEstimationPointToPoint()
     if est.mode != "p2p":
@@ -301,18 +318,66 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         raise NotImplementedError("distance checker threshold must equal max_correspondence_distance (as in KinectPy)")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    # the correspondences depend only on the two feature sets: execute_global_registration calls this 15 times with the
-    # same features (registration.py:46-57), so they are computed once and kept on the source Feature
-    key = (id(target_feature), bool(mutual_filter), int(ransac_n))
-    cached = getattr(source_feature, "_corr_cache", None)
-    if cached is not None and cached[0] == key and cached[2] is target_feature:
-        corres = cached[1]
-    else:
-        corres = ops.feature_correspondences(source_feature._dev, target_feature._dev, bool(mutual_filter), int(ransac_n))
-        source_feature._corr_cache = (key, corres, target_feature)
+    return crit, edge, seed
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, estimation_method=None, ransac_n=3,
+                                                checkers=(), criteria=None, seed=None):
+    """[O3D] registration_ransac_based_on_correspondence: the RANSAC of the feature variant over the correspondences as given
+    ((C, 2) source / target indices), with the same restrictions and the same `seed` keyword.  `correspondence_set` is, as in
+    Open3D, the evaluation's: every source point with a target point within max_correspondence_distance under the result."""
+    crit, edge, seed = _ransac_arguments(max_correspondence_distance, estimation_method, checkers, criteria, seed)
+    corres = np.ascontiguousarray(np.asarray(corres, dtype=np.int32).reshape(-1, 2))
     r = ops.ransac_corres(source._pts, target._pts, corres, float(max_correspondence_distance), int(ransac_n), edge,
                           crit.max_iteration, crit.confidence, seed)
-    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], corres)
+    if not max_correspondence_distance > 0:
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"])
+    inliers = evaluate_registration(source, target, max_correspondence_distance, r["transformation"]).correspondence_set
+    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], inliers)
+
+
+class FastGlobalRegistrationOption:
+    """[O3D] FastGlobalRegistrationOption, Open3D's defaults"""
+
+    def __init__(self, division_factor=1.4, use_absolute_scale=False, decrease_mu=True, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000, tuple_test=True):
+        self.division_factor, self.use_absolute_scale, self.decrease_mu = float(division_factor), bool(use_absolute_scale), bool(decrease_mu)
+        self.maximum_correspondence_distance, self.iteration_number = float(maximum_correspondence_distance), int(iteration_number)
+        self.tuple_scale, self.maximum_tuple_count, self.tuple_test = float(tuple_scale), int(maximum_tuple_count), bool(tuple_test)
+
+    def __repr__(self):
+        return ("FastGlobalRegistrationOption(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in (
+            "division_factor", "use_absolute_scale", "decrease_mu", "maximum_correspondence_distance", "iteration_number", "tuple_scale",
+            "maximum_tuple_count", "tuple_test")) + ")")
+
+
+def _fgr_result(source, target, corres, opt):
+    """optimise over `corres`, then Open3D's evaluation of the result at maximum_correspondence_distance"""
+    if opt.maximum_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    r = ops.fgr_optimize(source._pts, target._pts, corres, opt.division_factor, opt.use_absolute_scale, opt.decrease_mu,
+                         opt.maximum_correspondence_distance, opt.iteration_number)
+    return evaluate_registration(source, target, opt.maximum_correspondence_distance, r["transformation"])
+
+
+def registration_fgr_based_on_correspondence(source, target, corres, option=None):
+    """[O3D] registration_fgr_based_on_correspondence: Fast Global Registration over the correspondences as given ((C, 2) source /
+    target indices); no tuple test, as in Open3D."""
+    opt = option if option is not None else FastGlobalRegistrationOption()
+    return _fgr_result(source, target, np.ascontiguousarray(np.asarray(corres, dtype=np.int32).reshape(-1, 2)), opt)
+
+
+def registration_fgr_based_on_feature_matching(source, target, source_feature, target_feature, option=None, seed=None):
+    """[O3D] registration_fgr_based_on_feature_matching: mutual nearest neighbours of the features (no one-way fall-back), the tuple
+    test, then the optimisation.  Open3D draws the tuple test's triples from rand() seeded by the clock; ours draws from Philox
+    with `seed` (None -> fresh random seed)."""
+    opt = option if option is not None else FastGlobalRegistrationOption()
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+    corres = ops.feature_correspondences(source_feature._dev, target_feature._dev, True, ransac_n=0)
+    if opt.tuple_test and len(corres):
+        corres = ops.fgr_tuple_test(source._pts, target._pts, corres, opt.tuple_scale, opt.maximum_tuple_count, seed)
+    return _fgr_result(source, target, corres, opt)
 
 
 def compute_iss_keypoints(input, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
@@ -345,6 +410,10 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     TransformationEstimationPointToPlane=TransformationEstimationPointToPlane,
     compute_fpfh_feature=compute_fpfh_feature,
     registration_ransac_based_on_feature_matching=registration_ransac_based_on_feature_matching,
+    registration_ransac_based_on_correspondence=registration_ransac_based_on_correspondence,
+    FastGlobalRegistrationOption=FastGlobalRegistrationOption,
+    registration_fgr_based_on_feature_matching=registration_fgr_based_on_feature_matching,
+    registration_fgr_based_on_correspondence=registration_fgr_based_on_correspondence,
     Feature=Feature,
     CorrespondenceCheckerBasedOnEdgeLength=CorrespondenceCheckerBasedOnEdgeLength,
     CorrespondenceCheckerBasedOnDistance=CorrespondenceCheckerBasedOnDistance,

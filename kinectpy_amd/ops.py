@@ -733,6 +733,42 @@ def ransac_corres(src, tgt, corres, max_dist, ransac_n=3, edge_similarity=0.95, 
             "iterations": int(res[18]), "validations": int(res[19])}
 
 
+def fgr_tuple_test(src, tgt, corres, tuple_scale=0.95, maximum_tuple_count=1000, seed=0):
+    """[O3D] the tuple test of FastGlobalRegistration: 100 trials per correspondence of three correspondences each (Philox, `seed`);
+    a trial passes when its three edge lengths agree within tuple_scale on both sides.  Returns the three pairs of each of the
+    first maximum_tuple_count passing trials, in trial order, as an int32 (3 K, 2) device tensor (duplicates stay)."""
+    lib = L.load()
+    src = _dev(src, torch.float32).reshape(-1, 3)
+    tgt = _dev(tgt, torch.float32).reshape(-1, 3)
+    corres = _dev(corres, torch.int32).reshape(-1, 2)
+    nc = corres.shape[0]
+    cap = 3 * min(int(maximum_tuple_count), 100 * nc)
+    pairs = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=src.device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=src.device)
+    ws, wsz = L.workspace(lib.kpx_fgr_workspace_bytes(nc))
+    L.check(lib.kpx_fgr_tuple_test(L.ptr(src), src.shape[0], L.ptr(tgt), tgt.shape[0], L.ptr(corres), nc, float(tuple_scale),
+                                   int(maximum_tuple_count), C.c_uint64(int(seed)), L.ptr(pairs), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return pairs[:_count(cnt)[0]]
+
+
+def fgr_optimize(src, tgt, corres, division_factor=1.4, use_absolute_scale=False, decrease_mu=True, maximum_correspondence_distance=0.025,
+                 iteration_number=64):
+    """[O3D] the optimisation of FastGlobalRegistration over the correspondences as given (one launch).  Returns
+    dict(transformation (source -> target), par, iterations, failed_solves, scale)."""
+    lib = L.load()
+    src = _dev(src, torch.float32).reshape(-1, 3)
+    tgt = _dev(tgt, torch.float32).reshape(-1, 3)
+    corres = _dev(corres, torch.int32).reshape(-1, 2)
+    res = np.zeros(20)
+    res[:16] = np.eye(4).reshape(-1)
+    ws, wsz = L.workspace(lib.kpx_fgr_workspace_bytes(corres.shape[0]))
+    L.check(lib.kpx_fgr_optimize(L.ptr(src), src.shape[0], L.ptr(tgt), tgt.shape[0], L.ptr(corres), corres.shape[0], float(division_factor),
+                                 int(bool(use_absolute_scale)), int(bool(decrease_mu)), float(maximum_correspondence_distance),
+                                 int(iteration_number), L.hptr(res), ws, wsz, L.stream_ptr()))
+    return {"transformation": res[:16].reshape(4, 4).copy(), "par": float(res[16]), "iterations": int(res[17]),
+            "failed_solves": int(res[18]), "scale": float(res[19])}
+
+
 def icp_batch(srcs, tgt, max_dist, inits, mode="p2p", tgt_normals=None, max_iteration=30, relative_fitness=1e-6,
               relative_rmse=1e-6):
     """Several registrations onto one shared target, software-pipelined on the current stream.

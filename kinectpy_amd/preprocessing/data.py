@@ -65,13 +65,14 @@ def fuse_and_filter(filtered_pcds: Sequence[PointCloud], registration_transforma
 class DataProcessor:
     def __init__(self, output_dirs: List[str], mask_rcnn_pb_file: Optional[str] = None, mask_rcnn_pbtxt_file: Optional[str] = None, *,
                  mask_fn=None, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None,
-                 run: bool = True, multiway: bool = False, robust_kernel=None, keypoints=None):
+                 run: bool = True, multiway: bool = False, robust_kernel=None, keypoints=None, global_method: str = "ransac"):
         """reference signature (data.py:15-27) + keyword-only extras: `mask_fn` (the person mask, instead of Mask R-CNN),
         `initial_transformations` (skip the global registration: data.py:156), `seed` (the reference's RANSAC is unseeded),
         `run=False` (build the object, call find / process yourself), `multiway=True` (calibrate with execute_multiway_registration:
         every pair of devices registered, one pose graph solved -- instead of the reference's star of sub -> master ICPs),
         `robust_kernel` (a loss of o3d.pipelines.registration, e.g. TukeyLoss(k), for every pairwise ICP of the calibration),
-        `keypoints` (None, True or a dict of ISS parameters: execute_global_registration matches ISS keypoints only)."""
+        `keypoints` (None, True or a dict of ISS parameters: execute_global_registration matches ISS keypoints only),
+        `global_method` ("ransac", the reference's 15 RANSAC runs per sub device, or "fgr", one Fast Global Registration)."""
         self.device_filenames_df = self._create_device_filenames_df(output_dirs)
         self.number_of_devices = len(self.device_filenames_df.columns)
         self.registration_transformations: List[np.ndarray] = []
@@ -80,6 +81,7 @@ class DataProcessor:
         self.multiway = multiway
         self.robust_kernel = robust_kernel
         self.keypoints = keypoints
+        self.global_method = global_method
         self.segmentation = None
         self._mask_args = (mask_rcnn_pb_file, mask_rcnn_pbtxt_file, mask_fn)
         if not run:
@@ -97,7 +99,7 @@ class DataProcessor:
 
     @classmethod
     def in_memory(cls, number_of_devices: int, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None,
-                  multiway: bool = False, robust_kernel=None, keypoints=None):
+                  multiway: bool = False, robust_kernel=None, keypoints=None, global_method: str = "ransac"):
         """the frame loop without the directory walk: find_registration_transforms(master, subs) / process_frame(imgs, depths)"""
         self = cls.__new__(cls)
         self.device_filenames_df = None
@@ -108,6 +110,7 @@ class DataProcessor:
         self.multiway = multiway
         self.robust_kernel = robust_kernel
         self.keypoints = keypoints
+        self.global_method = global_method
         self.segmentation = None
         return self
 
@@ -148,13 +151,16 @@ class DataProcessor:
         self.registration_transformations = []
         if self.multiway:
             self.registration_transformations = execute_multiway_registration([master_pcd] + list(sub_pcds), initial_transformations=self.initial_transformations,
-                                                                              seed=self.seed, kernel=self.robust_kernel, keypoints=self.keypoints)
+                                                                              seed=self.seed, kernel=self.robust_kernel, keypoints=self.keypoints,
+                                                                              global_method=self.global_method)
             return self.registration_transformations
         for i, sub in enumerate(sub_pcds):
             if self.initial_transformations is None:
-                init = execute_global_registration(master_pcd, sub, seed=self.seed, keypoints=self.keypoints)            # data.py:156
+                init = execute_global_registration(master_pcd, sub, seed=self.seed, keypoints=self.keypoints,                 # data.py:156
+                                                   **({} if self.global_method == "ransac" else {"method": self.global_method}))
                 if init is None:
-                    raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)")
+                    raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)" if self.global_method == "ransac"
+                                       else "execute_global_registration found no transformation (the FGR fitness was 0)")
             else:
                 init = self.initial_transformations[i]
             self.registration_transformations.append(execute_point_to_plane_registration(master_pcd, sub, init, kernel=self.robust_kernel))   # data.py:157

@@ -34,7 +34,8 @@ def _cut_to_keypoints(down, fpfh, keypoints):
     return down._select(idx), fpfh.select_by_index(idx)
 
 
-def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransac_n_trials: int = 15, seed=None, *, keypoints=None) -> np.ndarray:
+def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransac_n_trials: int = 15, seed=None, *, keypoints=None,
+                                **extension) -> np.ndarray:
     """registration.py:32-62: ransac_n_trials runs of FPFH feature-matching RANSAC (distance threshold 1.5 v,
     mutual filter, edge-length 0.95 + distance checkers, 250000 iterations, confidence 0.999); the
     transformation of the best fitness is kept (None if every fitness is 0).  The reference recomputes
@@ -44,7 +45,16 @@ def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransa
     the down-sampled cloud's resolution) or a dict of o3d.geometry.keypoint.compute_iss_keypoints' parameters.  Normals and FPFH are
     still computed on the full down-sampled clouds; points and feature columns are then cut to the keypoints on both sides and the
     RANSAC matches and scores those alone.  If either side has fewer than ransac_n = 3 keypoints, the full clouds are used as if
-    keypoints were None."""
+    keypoints were None.
+    method: "ransac" (the reference) or "fgr": ONE Fast Global Registration (o3d...registration_fgr_based_on_feature_matching with
+    FastGlobalRegistrationOption(maximum_correspondence_distance=0.5 * voxel_size), as in Open3D's tutorial) on the same clouds and
+    features instead of the ransac_n_trials RANSAC runs; `seed` seeds its tuple test; None if its fitness is 0.  (`method` is the one
+    keyword `extension` takes: the function's keyword defaults stay those of before.)"""
+    method = extension.pop("method", "ransac")
+    if extension:
+        raise TypeError(f"execute_global_registration() got an unexpected keyword argument {next(iter(extension))!r}")
+    if method not in ("ransac", "fgr"):
+        raise ValueError(f"execute_global_registration: method must be 'ransac' or 'fgr', not {method!r}")
     best_fitness = 0
     ransac_transformation = None
     reg = o3d.pipelines.registration
@@ -54,6 +64,11 @@ def execute_global_registration(pcd_master, pcd_sub, voxel_size: int = 35, ransa
         target_key, target_key_fpfh = _cut_to_keypoints(target_down, target_fpfh, keypoints)
         if min(len(source_key.points), len(target_key.points)) >= 3:
             source_down, source_fpfh, target_down, target_fpfh = source_key, source_key_fpfh, target_key, target_key_fpfh
+    if method == "fgr":
+        result_fgr = reg.registration_fgr_based_on_feature_matching(
+            source_down, target_down, source_fpfh, target_fpfh,
+            reg.FastGlobalRegistrationOption(maximum_correspondence_distance=voxel_size * 0.5), seed=seed)
+        return result_fgr.transformation if result_fgr.fitness > 0 else None
     distance_threshold = voxel_size * 1.5
     for trial in range(ransac_n_trials):
         result_ransac = reg.registration_ransac_based_on_feature_matching(
@@ -86,9 +101,9 @@ def execute_point_to_plane_registration(pcd_master, pcd_sub, initial_transformat
 # by parameter): `kernel` is this library's keyword-only extension and is documented in the docstring above.
 execute_point_to_plane_registration.__signature__ = inspect.Signature(
     [p for p in inspect.signature(execute_point_to_plane_registration).parameters.values() if p.name != "kernel"])
-# likewise `keypoints` of execute_global_registration
+# likewise `keypoints` and `method` of execute_global_registration
 execute_global_registration.__signature__ = inspect.Signature(
-    [p for p in inspect.signature(execute_global_registration).parameters.values() if p.name != "keypoints"],
+    [p for p in inspect.signature(execute_global_registration).parameters.values() if p.name not in ("keypoints", "extension")],
     return_annotation=inspect.signature(execute_global_registration).return_annotation)
 
 
@@ -115,7 +130,8 @@ def execute_colored_ICP_registration(pcd_master, pcd_sub, initial_transformation
 
 
 def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transformations=None, seed=None, preference_loop_closure=None,
-                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False, kernel=None, keypoints=None):
+                                  edge_prune_threshold: float = 0.25, return_pose_graph: bool = False, kernel=None, keypoints=None,
+                                  global_method="ransac"):
     """[O3D] multiway registration of a rig: pcds[0] is the master.  Not in the reference, whose calibration is the star alone
     (data.py:137-147); opt-in through DataProcessor(multiway=True).  -> the sub -> master 4x4 list in the form
     DataProcessor.registration_transformations holds (and the optimised PoseGraph with return_pose_graph).
@@ -131,7 +147,8 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
     it disagrees with the rest by more than about one voxel rms over its matched points ("Multiway registration").
     kernel: a robust loss for every pairwise ICP (star and loop edges); the loop edges then go one by one through ops.icp, as
     ops.icp_batch runs the culled iteration kernels, which take no weights.
-    keypoints: passed to every execute_global_registration (None: every down-sampled point is matched)."""
+    keypoints: passed to every execute_global_registration (None: every down-sampled point is matched).
+    global_method: execute_global_registration's `method` ("ransac" or "fgr")."""
     from .. import ops
     reg = o3d.pipelines.registration
     threshold = 100                                                       # execute_point_to_plane_registration's
@@ -140,9 +157,11 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
     star = [np.eye(4)]
     for i in range(1, S):
         if initial_transformations is None:
-            init = execute_global_registration(pcds[0], pcds[i], voxel_size, seed=seed, keypoints=keypoints)
+            init = execute_global_registration(pcds[0], pcds[i], voxel_size, seed=seed, keypoints=keypoints,
+                                               **({} if global_method == "ransac" else {"method": global_method}))
             if init is None:
-                raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)")
+                raise RuntimeError("execute_global_registration found no transformation (every RANSAC fitness was 0)" if global_method == "ransac"
+                                   else "execute_global_registration found no transformation (the FGR fitness was 0)")
         else:
             init = initial_transformations[i - 1]
         star.append(reg.registration_icp(downs[i], downs[0], threshold, init, reg.TransformationEstimationPointToPlane(kernel)).transformation)

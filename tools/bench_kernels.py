@@ -209,6 +209,13 @@ def main():
     report("ransac feature matching 250k it (a13)", ms, corres=int(len(corr)), iterations=r["iterations"], validations=r["validations"],
            fitness=round(r["fitness"], 4))
 
+    # Fast Global Registration on the mutual correspondences of the same pair (HIP events, median of 20)
+    mutual = ops.feature_correspondences(f1, f0, True, ransac_n=0)
+    ms, tup = timed(lambda: ops.fgr_tuple_test(views[1], views[0], mutual, 0.95, 1000, 1), reps=20, warm=2)
+    report("fgr_tuple_test scale 0.95, 1000 tuples", ms, corres=int(len(mutual)), tuples=int(len(tup) // 3))
+    ms, r = timed(lambda: ops.fgr_optimize(views[1], views[0], tup, maximum_correspondence_distance=17.5), reps=20, warm=2)
+    report("fgr_optimize 64 rounds, one launch", ms, corres=int(len(tup)), failed_solves=r["failed_solves"], par=r["par"])
+
     from kinectpy_amd.geometry import PointCloud
     from kinectpy_amd.preprocessing.registration import execute_global_registration
     import time
@@ -225,6 +232,16 @@ def main():
         walls.append((time.perf_counter() - t0) * 1e3)
     report("execute_global_registration voxel 35, 15 trials x 250k it (registration.py:32-62, host wall time, median of 3)", float(np.median(walls)),
            n_master=int(len(pcs[0].points)), n_sub=int(len(pcs[1].points)), found=Tg is not None)
+
+    execute_global_registration(pcs[0], pcs[1], 35, seed=1, method="fgr")
+    walls = []
+    for _ in range(3):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        Tf = execute_global_registration(pcs[0], pcs[1], 35, seed=1, method="fgr")
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    report("execute_global_registration voxel 35, method='fgr' (one FGR; host wall time, median of 3)", float(np.median(walls)),
+           n_master=int(len(pcs[0].points)), n_sub=int(len(pcs[1].points)), found=Tf is not None)
 
     # ---- sampler / normaliser
     fused = torch.as_tensor(synth.filter_cloud(260_000)).to(dev)
