@@ -723,6 +723,41 @@ int kpx_prof_icp_cert(uint64_t *h_out8);
    the last chain launch (slots: kpx_icp.hip, g_chain_stamp); read and reset.  A development aid like the other kpx_prof_* entries. */
 int kpx_prof_icp_chain(uint64_t *h_out3072);
 
+/* ---- volumetric integration ([O3D] pipelines.integration.UniformTSDFVolume; arithmetic contract AC9) ------------ */
+/* The volume is caller-owned and zero-initialised by the caller (reset = clear it): volume f32 [res^3][2] = {tsdf, weight} per
+ * voxel, 16-byte aligned; color f32 [res^3][3] or NULL (no colours); voxel (x, y, z) at linear index (x res + y) res + z; its
+ * centre is h_origin + (index + 0.5) voxel_length.  1 <= resolution <= KPX_TSDF_MAX_RESOLUTION.
+ * kpx_tsdf_integrate: `count` images of width x height pixels, taken with the pinhole h_intrinsic = (fx, fy, cx, cy) from the
+ *     poses h_extrinsics f64 [count][16] (world -> camera, row-major 4x4, host), are integrated in ascending order: every voxel
+ *     whose centre projects into image s at a pixel of depth d > 0 with sdf = (d - z) sqrt(xm^2 + ym^2 + 1) > -sdf_trunc takes
+ *     tsdf = (tsdf w + min(1, sdf / sdf_trunc)) / (w + 1) (colours alike), w += 1.  The result equals `count` calls with one image
+ *     each, bit for bit; one launch holds up to KPX_TSDF_MAX_SENSORS images (one read and one write of a voxel for all of them),
+ *     larger counts run as consecutive launches.  h_depth: host array of device pointers, f32 [H W] (depth_u16 = 0; depth_scale
+ *     and depth_trunc are ignored) or u16 [H W] (depth_u16 = 1: d = (float)raw / (float)depth_scale, d > (float)depth_trunc -> 0,
+ *     what RGBDImage.create_from_color_and_depth computes).  h_rgb: host array of device pointers u8 [H W 3]; read only when
+ *     color is given (then required).  Asynchronous.
+ * kpx_tsdf_extract_count / kpx_tsdf_extract_fill: the two phases of extract_point_cloud (KPX_TSDF_SURFACE: one point per zero
+ *     crossing between a valid voxel -- w != 0, -0.98 <= tsdf < 0.98 -- and its valid +x / +y / +z neighbour, ascending in (linear
+ *     index, axis), with normals and, from a colour volume, colours) and of extract_voxel_point_cloud (KPX_TSDF_VOXELS: the centre
+ *     of every valid voxel, ascending, colour = grey (tsdf + 1) / 2).  count writes one count per KPX_TSDF_COUNT_BLOCK consecutive
+ *     voxels into ws, scans them there and leaves the total at d_count (i64, device).  The caller reads it, allocates pts / nrm /
+ *     col f32 [total][3] and calls fill with the SAME, untouched ws and an unchanged volume.  nrm and col may be NULL (not
+ *     wanted); col needs `color` in the surface mode.  fill writes nothing at or beyond `total`.  Asynchronous.
+ * ws: kpx_tsdf_workspace_bytes(resolution) bytes (0 for a resolution outside the range). */
+#define KPX_TSDF_MAX_RESOLUTION 1024
+#define KPX_TSDF_MAX_SENSORS 8
+#define KPX_TSDF_COUNT_BLOCK 512
+#define KPX_TSDF_SURFACE 0
+#define KPX_TSDF_VOXELS 1
+size_t kpx_tsdf_workspace_bytes(int32_t resolution);
+int kpx_tsdf_integrate(float *volume, float *color, int32_t resolution, double voxel_length, const double *h_origin, double sdf_trunc,
+                       int32_t count, const void *const *h_depth, int32_t depth_u16, double depth_scale, double depth_trunc,
+                       const uint8_t *const *h_rgb, int32_t width, int32_t height, const double *h_intrinsic, const double *h_extrinsics,
+                       void *stream);
+int kpx_tsdf_extract_count(const float *volume, int32_t resolution, int32_t mode, int64_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_tsdf_extract_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
+                          int32_t mode, int64_t total, float *pts, float *nrm, float *col, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,10 @@ SIGNATURES = {
     "kpx_prof_icp_cert": (C.c_int, [_vp]),
     "kpx_prof_icp_chain": (C.c_int, [_vp]),
     "kpx_prof_end": (C.c_int, [_vp, _vp, _vp]),
+    "kpx_tsdf_workspace_bytes": (_sz, [_i32]),
+    "kpx_tsdf_integrate": (C.c_int, [_vp, _vp, _i32, _f64, _vp, _f64, _i32, _vp, _i32, _f64, _f64, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "kpx_tsdf_extract_count": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_extract_fill": (C.c_int, [_vp, _vp, _i32, _f64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -302,6 +302,28 @@ static __global__ __launch_bounds__(1024) void compact_scan2_kernel(int32_t *cou
     compact_scan_body(blockIdx.x ? counts_b : counts_a, nblocks, blockIdx.x ? d_count_b : d_count_a);
 }
 
+// exclusive scan of m 64-bit counts in place, offsets[m] = total: one block, a contiguous slice per thread (the radius search's
+// per-query counts, the TSDF extraction's per-block counts)
+static __global__ __launch_bounds__(1024) void scan_i64_kernel(int64_t *__restrict__ offsets, int64_t m)
+{
+    __shared__ int64_t sh[1024];
+    const int64_t per = (m + 1023) / 1024;
+    const int64_t b = (int64_t)threadIdx.x * per < m ? (int64_t)threadIdx.x * per : m;
+    const int64_t e = b + per < m ? b + per : m;
+    int64_t s = 0;
+    for (int64_t i = b; i < e; ++i) s += offsets[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int t = 0; t < 1024; ++t) { const int64_t c = sh[t]; sh[t] = run; run += c; }
+        offsets[m] = run;
+    }
+    __syncthreads();
+    int64_t run = sh[threadIdx.x];
+    for (int64_t i = b; i < e; ++i) { const int64_t c = offsets[i]; offsets[i] = run; run += c; }
+}
+
 template <class Pred, class Emit>
 __global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(Pred pred, Emit emit, int64_t n,
                                                                             const int32_t *block_offsets)

@@ -282,26 +282,6 @@ __global__ __launch_bounds__(256) void search_radius_count_kernel(SearchView v, 
         offsets[qi] = cnt;
     }
 }
-// exclusive scan of m 64-bit counts in place, offsets[m] = total: one block, a contiguous slice per thread
-__global__ __launch_bounds__(1024) void search_scan_kernel(int64_t *__restrict__ offsets, int64_t m)
-{
-    __shared__ int64_t sh[1024];
-    const int64_t per = (m + 1023) / 1024;
-    const int64_t b = (int64_t)threadIdx.x * per < m ? (int64_t)threadIdx.x * per : m;
-    const int64_t e = b + per < m ? b + per : m;
-    int64_t s = 0;
-    for (int64_t i = b; i < e; ++i) s += offsets[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < 1024; ++t) { const int64_t c = sh[t]; sh[t] = run; run += c; }
-        offsets[m] = run;
-    }
-    __syncthreads();
-    int64_t run = sh[threadIdx.x];
-    for (int64_t i = b; i < e; ++i) { const int64_t c = offsets[i]; offsets[i] = run; run += c; }
-}
 __global__ __launch_bounds__(256) void search_radius_fill_kernel(SearchView v, const float *__restrict__ queries, int64_t m, double radius, double r2,
                                                                  const int64_t *__restrict__ offsets, int64_t total, int32_t *__restrict__ out_idx,
                                                                  double *__restrict__ out_d2)
@@ -507,7 +487,7 @@ KPX_EXPORT int kpx_search_radius_count(const void *index, size_t index_bytes, co
     if (m > 0)
         hipLaunchKernelGGL(search_radius_count_kernel, dim3((unsigned)(cdiv(m, 256) > 8192 ? 8192 : cdiv(m, 256))), dim3(256), 0, st, v, queries, m, radius,
                            radius * radius, offsets);
-    hipLaunchKernelGGL(search_scan_kernel, dim3(1), dim3(1024), 0, st, offsets, m);
+    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, offsets, m);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

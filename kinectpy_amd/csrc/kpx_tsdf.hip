@@ -1,0 +1,396 @@
+// kpx_tsdf.hip -- uniform truncated-signed-distance volume ([O3D] pipelines.integration.UniformTSDFVolume; arithmetic contract AC9,
+// DESIGN.md 3 and 5.11): integration of depth images (one read-modify-write of the volume for up to KPX_TSDF_MAX_SENSORS images)
+// and the two point-cloud extractions (count per block of consecutive voxels -> 64-bit scan -> fill).
+//
+// Layout: voxel (x, y, z) lives at linear index (x res + y) res + z (z fastest); volume = float2 {tsdf, weight} per voxel, colours
+// = float[3] per voxel in a separate array.  res <= 1024, so a linear index is below 2^30: it is carried as int64 (byte offsets of
+// the 8 GiB volume and of the colour array need it) and split into (x, y, z) with 32-bit divisions.
+#include "kpx_common.h"
+
+#include <math.h>
+
+namespace kpx {
+namespace {
+
+struct TsdfSensor {
+    double E[12];              // world -> camera, rows 0..2 of the row-major 4x4
+    const void *depth;         // f32 or u16 [H W]
+    const uint8_t *rgb;        // u8 [H W 3] or null
+};
+struct TsdfIntegrateArgs {
+    TsdfSensor s[KPX_TSDF_MAX_SENSORS];
+    double org[3], vl, trunc, fx, fy, cx, cy;
+    float scale, dtrunc;
+    int32_t W, H, res, count;
+};
+
+__device__ __forceinline__ void tsdf_split(int64_t lin, int res, int &x, int &y, int &z)
+{
+    const uint32_t l = (uint32_t)lin, r = (uint32_t)res;
+    const uint32_t t = l / r;
+    z = (int)(l - t * r);
+    x = (int)(t / r);
+    y = (int)(t - (uint32_t)x * r);
+}
+
+// AC9 for one voxel centre and one image: true = the voxel is updated with *t (and rgb[3])
+template <bool U16, bool COLOR>
+__device__ __forceinline__ bool tsdf_observe(const TsdfIntegrateArgs &a, const TsdfSensor &sn, const double c[3], float *t, float rgb[3])
+{
+    const double *E = sn.E;
+    const double pz = fma(E[8], c[0], fma(E[9], c[1], fma(E[10], c[2], E[11])));
+    if (pz <= 0.0) return false;
+    const double px = fma(E[0], c[0], fma(E[1], c[1], fma(E[2], c[2], E[3])));
+    const double py = fma(E[4], c[0], fma(E[5], c[1], fma(E[6], c[2], E[7])));
+    const double ax = px * a.fx, ay = py * a.fy;
+    // Division-free reject of what projects more than a pixel outside the image (the exact test below decides the rest): whole
+    // waves whose z-run misses every image leave here without a division, a gather or a volume access.
+    if (ax < (-a.cx - 1.5) * pz || ax > ((double)a.W - a.cx + 0.5) * pz || ay < (-a.cy - 1.5) * pz || ay > ((double)a.H - a.cy + 0.5) * pz) return false;
+    const double uf = ax / pz + a.cx + 0.5, vf = ay / pz + a.cy + 0.5;
+    if (!(uf >= 0.0001 && uf < (double)a.W - 0.0001 && vf >= 0.0001 && vf < (double)a.H - 0.0001)) return false;
+    const int u = (int)uf, v = (int)vf;
+    const int64_t pix = (int64_t)v * a.W + u;
+    float d;
+    if (U16) {
+        d = (float)((const uint16_t *)sn.depth)[pix] / a.scale;
+        if (d > a.dtrunc) d = 0.0f;
+    } else {
+        d = ((const float *)sn.depth)[pix];
+    }
+    if (d <= 0.0f) return false;
+    // sdf = dz mult with mult >= 1 (a correctly rounded sqrt of a value >= 1), and rounding is monotonic: dz <= -trunc gives
+    // sdf <= -trunc (no update) and dz >= trunc gives sdf / trunc >= 1 (t = 1) whatever mult is.  Only the band between the two --
+    // a few voxels either side of the surface -- pays for the two divisions, the square root and the quotient.
+    const double dz = (double)d - pz;
+    if (dz <= -a.trunc) return false;
+    if (dz >= a.trunc) {
+        *t = 1.0f;
+    } else {
+        const double xm = ((double)u - a.cx) / a.fx, ym = ((double)v - a.cy) / a.fy;
+        const double mult = sqrt(xm * xm + ym * ym + 1.0);
+        const double sdf = dz * mult;
+        if (!(sdf > -a.trunc)) return false;
+        *t = (float)fmin(1.0, sdf / a.trunc);
+    }
+    if (COLOR) {
+        const uint8_t *p = sn.rgb + 3 * pix;
+        rgb[0] = (float)p[0]; rgb[1] = (float)p[1]; rgb[2] = (float)p[2];
+    }
+    return true;
+}
+
+// One thread owns two consecutive voxels (one 16-byte access); the last thread of an odd volume owns one.  The volume is read at the
+// first image that updates either voxel and written once after the last: a pair no image reaches costs no volume traffic at all.
+template <bool U16, bool COLOR>
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(float2 *__restrict__ vol, float *__restrict__ col, int64_t nvox, TsdfIntegrateArgs a)
+{
+    const int64_t lin0 = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+    if (lin0 >= nvox) return;
+    const bool two = lin0 + 1 < nvox;
+    double c[2][3];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        int x, y, z;
+        tsdf_split(two || k == 0 ? lin0 + k : lin0, a.res, x, y, z);
+        c[k][0] = a.org[0] + ((double)x + 0.5) * a.vl;
+        c[k][1] = a.org[1] + ((double)y + 0.5) * a.vl;
+        c[k][2] = a.org[2] + ((double)z + 0.5) * a.vl;
+    }
+    float f[2] = { 0.0f, 0.0f }, w[2] = { 0.0f, 0.0f }, cc[2][3] = { { 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
+    bool loaded = false;
+    for (int s = 0; s < a.count; ++s) {
+        float t[2], rgb[2][3];
+        bool upd[2];
+        upd[0] = tsdf_observe<U16, COLOR>(a, a.s[s], c[0], &t[0], rgb[0]);
+        upd[1] = two && tsdf_observe<U16, COLOR>(a, a.s[s], c[1], &t[1], rgb[1]);
+        if (!(upd[0] || upd[1])) continue;
+        if (!loaded) {
+            loaded = true;
+            if (two) {
+                const float4 q = *reinterpret_cast<const float4 *>(vol + lin0);
+                f[0] = q.x; w[0] = q.y; f[1] = q.z; w[1] = q.w;
+            } else {
+                const float2 q = vol[lin0];
+                f[0] = q.x; w[0] = q.y;
+            }
+            if (COLOR) {
+                const float2 *cp = reinterpret_cast<const float2 *>(col + 3 * lin0);        // 24-byte stride: 8-byte aligned
+                const float2 q0 = cp[0];
+                cc[0][0] = q0.x; cc[0][1] = q0.y;
+                if (two) {
+                    const float2 q1 = cp[1], q2 = cp[2];
+                    cc[0][2] = q1.x; cc[1][0] = q1.y; cc[1][1] = q2.x; cc[1][2] = q2.y;
+                } else {
+                    cc[0][2] = col[3 * lin0 + 2];
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (!upd[k]) continue;
+            const float w1 = w[k] + 1.0f;
+            f[k] = (f[k] * w[k] + t[k]) / w1;
+            if (COLOR) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) cc[k][ch] = (cc[k][ch] * w[k] + rgb[k][ch]) / w1;
+            }
+            w[k] = w1;
+        }
+    }
+    if (!loaded) return;
+    if (two) {
+        *reinterpret_cast<float4 *>(vol + lin0) = make_float4(f[0], w[0], f[1], w[1]);
+    } else {
+        vol[lin0] = make_float2(f[0], w[0]);
+    }
+    if (COLOR) {
+        float2 *cp = reinterpret_cast<float2 *>(col + 3 * lin0);
+        cp[0] = make_float2(cc[0][0], cc[0][1]);
+        if (two) {
+            cp[1] = make_float2(cc[0][2], cc[1][0]);
+            cp[2] = make_float2(cc[1][1], cc[1][2]);
+        } else {
+            col[3 * lin0 + 2] = cc[0][2];
+        }
+    }
+}
+
+// ---- extraction ---------------------------------------------------------------------------------------------------------------
+constexpr int kChunk = KPX_TSDF_COUNT_BLOCK;       // consecutive voxels a wave counts and fills
+constexpr int kChunkRounds = kChunk / 64;
+constexpr int kExtractWaves = 4;
+
+__device__ __forceinline__ bool tsdf_valid(const float2 v) { return v.y != 0.0f && v.x >= -0.98f && v.x < 0.98f; }
+
+// what voxel `lin` emits: KPX_TSDF_SURFACE: bit i = a zero crossing towards +e_i; KPX_TSDF_VOXELS: bit 0 = the voxel is valid.
+// *v0 = the voxel, nb[i] = the neighbour of a set bit i.
+__device__ __forceinline__ unsigned tsdf_emits(const float2 *__restrict__ vol, int res, int64_t lin, int mode, float2 *v0, float2 nb[3])
+{
+    *v0 = vol[lin];
+    if (!tsdf_valid(*v0)) return 0u;
+    if (mode == KPX_TSDF_VOXELS) return 1u;
+    int p[3];
+    tsdf_split(lin, res, p[0], p[1], p[2]);
+    const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (p[i] + 1 >= res - 1) continue;            // Open3D's bound: the last layer of every axis is never a neighbour
+        nb[i] = vol[lin + step[i]];
+        if (tsdf_valid(nb[i]) && (double)v0->x * (double)nb[i].x < 0.0) m |= 1u << i;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(kExtractWaves * 64) void tsdf_count_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, int mode, int64_t nchunks,
+                                                                        int64_t *__restrict__ counts)
+{
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
+    if (chunk >= nchunks) return;
+    int c = 0;
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t lin = chunk * kChunk + r * 64 + lane_id();
+        float2 v0, nb[3];
+        if (lin < nvox) c += __builtin_popcount(tsdf_emits(vol, res, lin, mode, &v0, nb));
+    }
+    c = wave_sum(c);
+    if (lane_id() == 0) counts[chunk] = c;
+}
+
+// trilinear interpolation of the raw tsdf at q (volume coordinates, origin excluded); taps outside the volume are 0
+__device__ __forceinline__ double tsdf_at(const float2 *__restrict__ vol, int res, double vl, const double q[3])
+{
+    double r[3];
+    int i0[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double g = q[a] / vl - 0.5, fl = floor(g);
+        r[a] = g - fl;
+        i0[a] = (int)fl;
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int dx = t >> 2, dy = (t >> 1) & 1, dz = t & 1;
+        const double wx = dx ? r[0] : 1.0 - r[0], wy = dy ? r[1] : 1.0 - r[1], wz = dz ? r[2] : 1.0 - r[2];
+        const int x = i0[0] + dx, y = i0[1] + dy, z = i0[2] + dz;
+        float fv = 0.0f;
+        if (x >= 0 && x < res && y >= 0 && y < res && z >= 0 && z < res) fv = vol[((int64_t)x * res + y) * res + z].x;
+        acc = acc + wx * wy * wz * (double)fv;
+    }
+    return acc;
+}
+
+struct TsdfFillArgs {
+    double org[3], vl;
+    float *pts, *nrm, *ocol;
+    const float *col;
+    int64_t total;
+};
+
+__global__ __launch_bounds__(kExtractWaves * 64) void tsdf_fill_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, int mode, int64_t nchunks,
+                                                                       const int64_t *__restrict__ offsets, TsdfFillArgs a)
+{
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
+    if (chunk >= nchunks) return;
+    const int lane = lane_id();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int64_t pos = offsets[chunk];
+    if (offsets[chunk + 1] == pos) return;
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t lin = chunk * kChunk + r * 64 + lane;
+        float2 v0, nb[3];
+        const unsigned m = lin < nvox ? tsdf_emits(vol, res, lin, mode, &v0, nb) : 0u;
+        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
+        if ((b0 | b1 | b2) == 0ull) continue;
+        int64_t dst = pos + __builtin_popcountll(b0 & below) + __builtin_popcountll(b1 & below) + __builtin_popcountll(b2 & below);
+        pos += __builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2);
+        if (m == 0u) continue;
+        int ix[3];
+        tsdf_split(lin, res, ix[0], ix[1], ix[2]);
+        const double p0[3] = { ((double)ix[0] + 0.5) * a.vl, ((double)ix[1] + 0.5) * a.vl, ((double)ix[2] + 0.5) * a.vl };
+        if (mode == KPX_TSDF_VOXELS) {
+            if (dst >= a.total) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)(a.org[k] + p0[k]);
+            if (a.ocol) {
+                const float g = (float)(((double)v0.x + 1.0) * 0.5);
+                a.ocol[3 * dst] = g; a.ocol[3 * dst + 1] = g; a.ocol[3 * dst + 2] = g;
+            }
+            continue;
+        }
+        const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
+        for (int i = 0; i < 3; ++i) {
+            if (!((m >> i) & 1u)) continue;
+            if (dst >= a.total) break;
+            const double r0 = fabs((double)v0.x), r1 = fabs((double)nb[i].x);
+            double p[3] = { p0[0], p0[1], p0[2] };
+            p[i] = (p0[i] * r1 + (p0[i] + a.vl) * r0) / (r0 + r1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)(p[k] + a.org[k]);
+            if (a.ocol && a.col) {
+                const float *c0 = a.col + 3 * lin, *c1 = a.col + 3 * (lin + step[i]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) a.ocol[3 * dst + k] = (float)(((double)c0[k] * r1 + (double)c1[k] * r0) / (r0 + r1) / 255.0);
+            }
+            if (a.nrm) {
+                const double gap = 0.99 * a.vl;
+                double n[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double qp[3] = { p[0], p[1], p[2] }, qm[3] = { p[0], p[1], p[2] };
+                    qp[k] = p[k] + gap;
+                    qm[k] = p[k] - gap;
+                    n[k] = tsdf_at(vol, res, a.vl, qp) - tsdf_at(vol, res, a.vl, qm);
+                }
+                const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) a.nrm[3 * dst + k] = len == 0.0 ? 0.0f : (float)(n[k] / len);
+            }
+            ++dst;
+        }
+    }
+}
+
+inline int64_t tsdf_voxels(int32_t res) { return (int64_t)res * res * res; }
+inline int64_t tsdf_chunks(int32_t res) { return cdiv(tsdf_voxels(res), kChunk); }
+inline bool tsdf_res_ok(int32_t res) { return res >= 1 && res <= KPX_TSDF_MAX_RESOLUTION; }
+
+}  // namespace
+}  // namespace kpx
+
+using namespace kpx;
+
+KPX_EXPORT size_t kpx_tsdf_workspace_bytes(int32_t resolution)
+{
+    if (!tsdf_res_ok(resolution)) return 0;
+    Arena a(nullptr, 0);
+    a.get<int64_t>((size_t)tsdf_chunks(resolution) + 1);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_tsdf_integrate(float *volume, float *color, int32_t resolution, double voxel_length, const double *h_origin, double sdf_trunc,
+                                  int32_t count, const void *const *h_depth, int32_t depth_u16, double depth_scale, double depth_trunc,
+                                  const uint8_t *const *h_rgb, int32_t width, int32_t height, const double *h_intrinsic, const double *h_extrinsics,
+                                  void *stream)
+{
+    KPX_REQUIRE(tsdf_res_ok(resolution), "kpx_tsdf_integrate: resolution must be in [1, %d]", KPX_TSDF_MAX_RESOLUTION);
+    KPX_REQUIRE(voxel_length > 0.0 && sdf_trunc > 0.0, "kpx_tsdf_integrate: voxel_length and sdf_trunc must be positive");
+    KPX_REQUIRE(count >= 0, "kpx_tsdf_integrate: negative image count");
+    KPX_REQUIRE(width > 0 && height > 0 && (int64_t)width * height < ((int64_t)1 << 31), "kpx_tsdf_integrate: bad image size");
+    KPX_REQUIRE(volume && h_origin && h_intrinsic && (count == 0 || (h_depth && h_extrinsics)), "kpx_tsdf_integrate: null pointer");
+    KPX_REQUIRE(!color || h_rgb || count == 0, "kpx_tsdf_integrate: a colour volume needs colour images");
+    KPX_REQUIRE(((uintptr_t)volume % 16) == 0 && ((uintptr_t)color % 8) == 0, "kpx_tsdf_integrate: the volume must be 16-byte aligned");
+    KPX_REQUIRE(!depth_u16 || depth_scale > 0.0, "kpx_tsdf_integrate: depth_scale must be positive");
+    for (int32_t i = 0; i < count; ++i)
+        KPX_REQUIRE(h_depth[i] && (!color || h_rgb[i]), "kpx_tsdf_integrate: image %d is null", i);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nvox = tsdf_voxels(resolution);
+    const unsigned blocks = (unsigned)cdiv(cdiv(nvox, 2), 256);
+    for (int32_t first = 0; first < count; first += KPX_TSDF_MAX_SENSORS) {          // more images than a launch holds: chunks, in order
+        TsdfIntegrateArgs a;
+        memset(&a, 0, sizeof a);
+        a.count = count - first < KPX_TSDF_MAX_SENSORS ? count - first : KPX_TSDF_MAX_SENSORS;
+        for (int32_t i = 0; i < a.count; ++i) {
+            memcpy(a.s[i].E, h_extrinsics + 16 * (size_t)(first + i), sizeof a.s[i].E);
+            a.s[i].depth = h_depth[first + i];
+            a.s[i].rgb = color ? h_rgb[first + i] : nullptr;
+        }
+        for (int k = 0; k < 3; ++k) a.org[k] = h_origin[k];
+        a.vl = voxel_length; a.trunc = sdf_trunc;
+        a.fx = h_intrinsic[0]; a.fy = h_intrinsic[1]; a.cx = h_intrinsic[2]; a.cy = h_intrinsic[3];
+        a.scale = (float)depth_scale; a.dtrunc = (float)depth_trunc;
+        a.W = width; a.H = height; a.res = resolution;
+        float2 *vol = reinterpret_cast<float2 *>(volume);
+        if (depth_u16) {
+            if (color) hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), dim3(blocks), dim3(256), 0, st, vol, color, nvox, a);
+            else hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), dim3(blocks), dim3(256), 0, st, vol, color, nvox, a);
+        } else {
+            if (color) hipLaunchKernelGGL((tsdf_integrate_kernel<false, true>), dim3(blocks), dim3(256), 0, st, vol, color, nvox, a);
+            else hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), dim3(blocks), dim3(256), 0, st, vol, color, nvox, a);
+        }
+        KPX_LAUNCH_CHECK();
+    }
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_tsdf_extract_count(const float *volume, int32_t resolution, int32_t mode, int64_t *d_count, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(tsdf_res_ok(resolution), "kpx_tsdf_extract_count: resolution must be in [1, %d]", KPX_TSDF_MAX_RESOLUTION);
+    KPX_REQUIRE(mode == KPX_TSDF_SURFACE || mode == KPX_TSDF_VOXELS, "kpx_tsdf_extract_count: unknown mode %d", mode);
+    KPX_REQUIRE(volume && d_count && ws, "kpx_tsdf_extract_count: null pointer");
+    const int64_t nchunks = tsdf_chunks(resolution);
+    Arena a(ws, ws_bytes);
+    int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
+    KPX_ARENA_CHECK(a);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(tsdf_count_kernel, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
+                       reinterpret_cast<const float2 *>(volume), resolution, tsdf_voxels(resolution), mode, nchunks, offsets);
+    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, offsets, nchunks);
+    KPX_LAUNCH_CHECK();
+    KPX_HIP(hipMemcpyAsync(d_count, offsets + nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_tsdf_extract_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
+                                     int32_t mode, int64_t total, float *pts, float *nrm, float *col, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(tsdf_res_ok(resolution), "kpx_tsdf_extract_fill: resolution must be in [1, %d]", KPX_TSDF_MAX_RESOLUTION);
+    KPX_REQUIRE(mode == KPX_TSDF_SURFACE || mode == KPX_TSDF_VOXELS, "kpx_tsdf_extract_fill: unknown mode %d", mode);
+    KPX_REQUIRE(voxel_length > 0.0 && total >= 0, "kpx_tsdf_extract_fill: bad voxel_length or total");
+    if (total == 0) return KPX_OK;
+    KPX_REQUIRE(volume && h_origin && pts && ws, "kpx_tsdf_extract_fill: null pointer");
+    const int64_t nchunks = tsdf_chunks(resolution);
+    Arena a(ws, ws_bytes);
+    const int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
+    KPX_ARENA_CHECK(a);
+    TsdfFillArgs f;
+    for (int k = 0; k < 3; ++k) f.org[k] = h_origin[k];
+    f.vl = voxel_length;
+    f.pts = pts; f.nrm = mode == KPX_TSDF_SURFACE ? nrm : nullptr; f.ocol = col; f.col = color; f.total = total;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(tsdf_fill_kernel, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
+                       reinterpret_cast<const float2 *>(volume), resolution, tsdf_voxels(resolution), mode, nchunks, offsets, f);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}

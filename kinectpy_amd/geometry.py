@@ -462,3 +462,57 @@ class KDTreeFlann:
         if isinstance(search_param, KDTreeSearchParamHybrid):
             return self.search_hybrid_vector_3d(query, search_param.radius, search_param.max_nn)
         raise TypeError("KDTreeFlann.search_vector_3d: expected a KDTreeSearchParamKNN, KDTreeSearchParamRadius or KDTreeSearchParamHybrid")
+
+
+class Image:
+    """o3d.geometry.Image stand-in: wraps a host ndarray -- uint8 (H, W, 3) colour, uint16 or float32 (H, W) depth / intensity.
+    np.asarray(image) gives the array back."""
+
+    def __init__(self, data=None):
+        a = np.zeros((0, 0), np.uint8) if data is None else np.ascontiguousarray(data.data if isinstance(data, Image) else data)
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        if not ((a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8) or (a.ndim == 2 and a.dtype in (np.uint8, np.uint16, np.float32))):
+            raise RuntimeError(f"Image: unsupported array {a.dtype} {a.shape}: expected uint8 (H, W, 3), or uint16 / float32 (H, W)")
+        self.data = a
+
+    height = property(lambda self: self.data.shape[0])
+    width = property(lambda self: self.data.shape[1] if self.data.ndim > 1 else 0)
+    num_of_channels = property(lambda self: self.data.shape[2] if self.data.ndim == 3 else 1)
+    bytes_per_channel = property(lambda self: self.data.dtype.itemsize)
+
+    def is_empty(self):
+        return self.data.size == 0
+
+    def __array__(self, dtype=None, copy=None):
+        return self.data if dtype is None else self.data.astype(dtype)
+
+    def __repr__(self):
+        return f"Image of size {self.width}x{self.height}, with {self.num_of_channels} channels."
+
+
+class RGBDImage:
+    """o3d.geometry.RGBDImage: a colour (or intensity) image and a float32 depth image of the same size"""
+
+    def __init__(self, color=None, depth=None):
+        self.color, self.depth = Image(color), Image(depth)
+
+    @staticmethod
+    def create_from_color_and_depth(color, depth, depth_scale=1000.0, depth_trunc=3.0, convert_rgb_to_intensity=True):
+        """[O3D] RGBDImage::CreateFromColorAndDepth: depth -> float32 raw / depth_scale, values above depth_trunc -> 0 (both in
+        float32); colour -> float32 intensity (0.299 r + 0.587 g + 0.114 b) / 255 when convert_rgb_to_intensity, else unchanged."""
+        color, depth = Image(color), Image(depth)
+        if color.height != depth.height or color.width != depth.width:
+            raise RuntimeError("RGBDImage.create_from_color_and_depth: unsupported image format (colour and depth sizes differ)")
+        d = np.asarray(depth).astype(np.float32) / np.float32(depth_scale)
+        d[d > np.float32(depth_trunc)] = np.float32(0.0)
+        c = np.asarray(color)
+        if convert_rgb_to_intensity and c.ndim == 3:
+            f = c.astype(np.float32)
+            c = ((np.float32(0.2990) * f[:, :, 0] + np.float32(0.5870) * f[:, :, 1]) + np.float32(0.1140) * f[:, :, 2]) / np.float32(255.0)
+        elif convert_rgb_to_intensity and c.dtype != np.float32:
+            c = c.astype(np.float32) / np.float32(255.0 if c.dtype == np.uint8 else 1.0)
+        return RGBDImage(c, d)
+
+    def __repr__(self):
+        return f"RGBDImage of size \nColor image : {self.color.width}x{self.color.height}, with {self.color.num_of_channels} channels.\nDepth image : {self.depth.width}x{self.depth.height}, with {self.depth.num_of_channels} channels."

@@ -8,8 +8,9 @@ import types
 import numpy as np
 
 from . import ops
-from .geometry import (KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector, OrientedBoundingBox,
-                       PointCloud, Vector2iVector, Vector3dVector)
+from .geometry import (Image, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
+                       OrientedBoundingBox, PointCloud, RGBDImage, Vector2iVector, Vector3dVector)
+from . import integration as _integration
 from . import pcd_io
 from . import posegraph
 
@@ -390,6 +391,38 @@ def compute_iss_keypoints(input, salient_radius=0.0, non_max_radius=0.0, gamma_2
     return input._select(input._iss_keypoint_indices(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors))
 
 
+class PinholeCameraIntrinsic:
+    """[O3D] camera.PinholeCameraIntrinsic(width, height, fx, fy, cx, cy) (or (width, height, intrinsic_matrix))"""
+
+    def __init__(self, width=-1, height=-1, fx=None, fy=None, cx=None, cy=None):
+        self.width, self.height = int(width), int(height)
+        if fx is not None and np.ndim(fx) == 2:
+            self.intrinsic_matrix = np.array(fx, dtype=np.float64).reshape(3, 3)
+        else:
+            self.intrinsic_matrix = np.eye(3)
+            if fx is not None:
+                self.set_intrinsics(width, height, fx, fy, cx, cy)
+
+    def set_intrinsics(self, width, height, fx, fy, cx, cy):
+        self.width, self.height = int(width), int(height)
+        self.intrinsic_matrix = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+    def get_focal_length(self):
+        return float(self.intrinsic_matrix[0, 0]), float(self.intrinsic_matrix[1, 1])
+
+    def get_principal_point(self):
+        return float(self.intrinsic_matrix[0, 2]), float(self.intrinsic_matrix[1, 2])
+
+    def get_skew(self):
+        return float(self.intrinsic_matrix[0, 1])
+
+    def is_valid(self):
+        return self.width > 0 and self.height > 0
+
+    def __repr__(self):
+        return f"PinholeCameraIntrinsic with width = {self.width} and height = {self.height}.\nAccess intrinsics with intrinsic_matrix."
+
+
 def _off_path(name):
     def f(*a, **k):
         raise NotImplementedError(f"{name} is outside the round-1 hot path of kinectpy_amd (SURVEY.md 8f); "
@@ -399,10 +432,16 @@ def _off_path(name):
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
+                                 Image=Image, RGBDImage=RGBDImage,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
+camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
 io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
-pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
+pipelines = types.SimpleNamespace(integration=types.SimpleNamespace(
+    TSDFVolumeColorType=_integration.TSDFVolumeColorType,
+    UniformTSDFVolume=_integration.UniformTSDFVolume,
+    ScalableTSDFVolume=_integration.ScalableTSDFVolume,
+), registration=types.SimpleNamespace(
     registration_icp=registration_icp,
     ICPConvergenceCriteria=ICPConvergenceCriteria,
     RegistrationResult=RegistrationResult,

@@ -1151,3 +1151,55 @@ def generalized_icp(src, src_cov, tgt, tgt_cov, max_dist, init=None, max_iterati
     if want_corr:
         out["idx"], out["d2"] = idx, d2
     return out
+
+
+# ---- volumetric integration ---------------------------------------------------------------------------
+TSDF_MODES = {"surface": 0, "voxels": 1}          # KPX_TSDF_SURFACE / KPX_TSDF_VOXELS (include/kinectpx.h)
+
+
+def tsdf_reset(volume, color=None):
+    """zero a TSDF volume (f32 (res^3, 2) device tensor {tsdf, weight}) and its colour array (f32 (res^3, 3) or None) in place"""
+    volume.zero_()
+    if color is not None:
+        color.zero_()
+
+
+def tsdf_integrate(volume, color, resolution, voxel_length, origin, sdf_trunc, depths, rgbs, width, height, intrinsic, extrinsics,
+                   depth_scale=1.0, depth_trunc=0.0):
+    """[O3D] UniformTSDFVolume.integrate for len(depths) images in one pass over the volume (kpx_tsdf_integrate), in place.  depths:
+    device tensors, all float32 (H W) metres-like depth, or all uint16 (H W) raw depth with depth_scale / depth_trunc applied in the
+    kernel; rgbs: uint8 (H W 3) per image when `color` is given; intrinsic (fx, fy, cx, cy); extrinsics: (S, 4, 4) world -> camera."""
+    lib = L.load()
+    cnt = len(depths)
+    u16 = cnt > 0 and depths[0].dtype == torch.uint16
+    depths = [_dev(d, torch.uint16 if u16 else torch.float32).reshape(-1) for d in depths]
+    rgbs = [_dev(c, torch.uint8).reshape(-1) for c in rgbs] if color is not None else None
+    n_px = int(width) * int(height)
+    if any(d.numel() != n_px for d in depths) or (rgbs is not None and (len(rgbs) != cnt or any(c.numel() != 3 * n_px for c in rgbs))):
+        raise L.KinectPxError("tsdf_integrate: image size does not match width x height")
+    E = np.ascontiguousarray(np.asarray(extrinsics, dtype=np.float64).reshape(cnt, 16))
+    org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    K = np.ascontiguousarray(np.asarray(intrinsic, dtype=np.float64).reshape(4))
+    arr = lambda ts: C.cast((C.c_void_p * max(cnt, 1))(*[t.data_ptr() for t in ts]), C.c_void_p) if ts is not None else None
+    L.check(lib.kpx_tsdf_integrate(L.ptr(volume), L.ptr(color), int(resolution), float(voxel_length), L.hptr(org), float(sdf_trunc), cnt,
+                                   arr(depths), int(u16), float(depth_scale), float(depth_trunc), arr(rgbs), int(width), int(height),
+                                   L.hptr(K), L.hptr(E), L.stream_ptr()))
+
+
+def tsdf_extract(volume, color, resolution, voxel_length, origin, mode="surface", want_normals=True):
+    """[O3D] extract_point_cloud (mode "surface") / extract_voxel_point_cloud ("voxels") -> (points, normals | None, colours | None)
+    float32 (K, 3) device tensors.  One host read (the count) between the count pass and the fill pass."""
+    lib = L.load()
+    m = TSDF_MODES[mode]
+    dev = volume.device
+    ws = torch.empty(lib.kpx_tsdf_workspace_bytes(int(resolution)), dtype=torch.uint8, device=dev)      # carried from count to fill
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.kpx_tsdf_extract_count(L.ptr(volume), int(resolution), m, L.ptr(cnt), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    total = int(cnt.item())
+    pts = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((total, 3), dtype=torch.float32, device=dev) if m == 0 and want_normals else None
+    col = torch.empty((total, 3), dtype=torch.float32, device=dev) if m == 1 or color is not None else None
+    org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    L.check(lib.kpx_tsdf_extract_fill(L.ptr(volume), L.ptr(color), int(resolution), float(voxel_length), L.hptr(org), m, total, L.ptr(pts),
+                                      L.ptr(nrm), L.ptr(col), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return pts, nrm, col

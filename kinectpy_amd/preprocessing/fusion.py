@@ -1,0 +1,33 @@
+"""Volumetric fusion of one frame set: every sensor's depth image integrated into one TSDF volume in the master's frame with the
+calibrated sensor -> master transforms, then the surface cloud extracted (o3d.pipelines.integration on the rig's own arrays).  An
+alternative to DataProcessor's transform + vstack + voxel_down_sample + remove_statistical_outlier fuse; the frame step is
+unchanged."""
+import numpy as np
+
+from ..integration import TSDFVolumeColorType, UniformTSDFVolume
+from ..utils import synth
+
+
+class _Intrinsic:
+    def __init__(self, width, height, fx, fy, cx, cy):
+        self.width, self.height = int(width), int(height)
+        self.intrinsic_matrix = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+
+
+def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0):
+    """depth: uint16 (S, H W) raw frames (synth.sensor_ring's layout; host or device); rgb: uint8 (S, H W, 3) or None (no colours);
+    intrinsic: a PinholeCameraIntrinsic, or None for the Kinect's (synth.FX, FY, CX, CY at synth.W x synth.H); sensor_to_master:
+    the S - 1 transforms of the sub sensors (sensor 0 is the master, identity).  The world frame is the master's: sensor s is
+    integrated with the extrinsic inv(sensor_to_master[s]) (host float64).  sdf_trunc defaults to 4 voxels.  One integrate_frames
+    call and one extraction -> PointCloud with normals (and colours when rgb is given)."""
+    if intrinsic is None:
+        intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
+    n = int(depth.shape[0])
+    if len(sensor_to_master) != n - 1:
+        raise RuntimeError(f"fuse_depth_tsdf: {n} sensors need {n - 1} sensor -> master transforms, got {len(sensor_to_master)}")
+    extr = [np.eye(4)] + [np.linalg.inv(np.asarray(T, dtype=np.float64).reshape(4, 4)) for T in sensor_to_master]
+    if sdf_trunc is None:
+        sdf_trunc = 4.0 * float(length) / int(resolution)
+    vol = UniformTSDFVolume(length, resolution, sdf_trunc, TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor, origin)
+    vol.integrate_frames(depth, rgb, intrinsic, np.stack(extr), depth_scale, depth_trunc)
+    return vol.extract_point_cloud()

@@ -51,8 +51,11 @@ def report(name, ms, nbytes=None, flops=None, **extra):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    if a.tsdf:
+        return tsdf_rows(dev, a.quick)
     F = 64 if a.quick else 256
     xy = synth.xy_table()
     base_d, person = synth.render_depth(xy=xy, return_person=True)
@@ -301,6 +304,48 @@ def main():
     report("registration_generalized_icp 100k x 100k", ms, iterations=r["iterations"], fitness=round(r["fitness"], 5),
            ms_per_iteration=round(ms / (r["iterations"] + 1), 4), dense_equivalent_flops=int(dense * (r["iterations"] + 1)),
            **sweep(ops.prof_end()))
+    tsdf_rows(dev, a.quick)
+
+
+def tsdf_rows(dev, quick):
+    """TSDF integration of S = 4 full-size ring frames: the batch form against four calls with one image each, and
+    the extraction.  Resolution 256 (128 MiB of tsdf + weight: cache-resident) and 512 (1 GiB: past the Infinity Cache).  Algorithmic
+    traffic: 16 B per updated voxel (40 B with colours) -- counted per call, so the four single-image calls move the volume up to
+    four times -- plus the images."""
+    S = 4
+    _, depth, rgb, _, _ = synth.sensor_ring(S, 1)
+    depth_d = [torch.as_tensor(depth[0, s]).to(dev) for s in range(S)]
+    rgb_d = [torch.as_tensor(rgb[0, s]).to(dev) for s in range(S)]
+    extr = np.stack([np.linalg.inv(synth.camera_pose(g, S)) for g in range(S)])
+    K, origin, length = (synth.FX, synth.FY, synth.CX, synth.CY), (-1000.0, -1100.0, -1000.0), 2000.0
+    for res in ((256,) if quick else (256, 512)):
+        vl = length / res
+        for colour in (False, True):
+            vol = torch.zeros((res ** 3, 2), dtype=torch.float32, device=dev)
+            col = torch.zeros((res ** 3, 3), dtype=torch.float32, device=dev) if colour else None
+            batch = lambda: ops.tsdf_integrate(vol, col, res, vl, origin, 4 * vl, depth_d, rgb_d, synth.W, synth.H, K, extr, 1.0, 6000.0)
+            batch()
+            w = vol[:, 1]
+            any_upd, sum_upd = int((w > 0).sum().item()), int(w.sum().item())
+            per_voxel, images = (40 if colour else 16), S * N_PX * (5 if colour else 2)
+            tag = f"res {res}, {S} x 640x576 u16" + (", RGB8" if colour else "")
+            ms, _ = timed(batch)
+            report(f"tsdf_integrate batch ({tag})", ms, per_voxel * any_upd + images, voxels=res ** 3, updated=any_upd)
+
+            def one_by_one():
+                for s in range(S):
+                    ops.tsdf_integrate(vol, col, res, vl, origin, 4 * vl, depth_d[s:s + 1], rgb_d[s:s + 1], synth.W, synth.H, K, extr[s:s + 1], 1.0, 6000.0)
+            ms, _ = timed(one_by_one)
+            report(f"tsdf_integrate {S} calls of one image ({tag})", ms, per_voxel * sum_upd + images, voxels=res ** 3, updated=sum_upd)
+            ops.tsdf_reset(vol, col)
+            batch()
+            ms, (pts, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "surface"))
+            report(f"tsdf extract_point_cloud ({tag}; count + scan + host read + fill)", ms, 8 * res ** 3 + int(pts.shape[0]) * (36 if colour else 24),
+                   points=int(pts.shape[0]))
+            if not colour:
+                ms, (vp, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "voxels"))
+                report(f"tsdf extract_voxel_point_cloud ({tag})", ms, 8 * res ** 3 + int(vp.shape[0]) * 24, points=int(vp.shape[0]))
+            del vol, col
 
 
 if __name__ == "__main__":
