@@ -758,6 +758,47 @@ int kpx_tsdf_extract_count(const float *volume, int32_t resolution, int32_t mode
 int kpx_tsdf_extract_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
                           int32_t mode, int64_t total, float *pts, float *nrm, float *col, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- occupancy grids ([O3D] geometry.VoxelGrid; arithmetic contract AC10) ---------------------------------------- */
+/* A grid is caller-owned: keys u64 [M], strictly ascending, key = gx << 42 | gy << 21 | gz with every index in [0, 2^21), and colors
+ * f32 [M][3]; voxel g covers h_origin + g voxel .. h_origin + (g + 1) voxel.  All decisions are fp64.
+ * kpx_voxelgrid_from_cloud: the grid of a float32 cloud (create_from_point_cloud: h_origin NULL, origin = min_bound - voxel / 2;
+ *     create_from_point_cloud_within_bounds: h_origin = the caller's min_bound, host).  g = floor((p - origin) / voxel); the colour of a
+ *     voxel is (float)(sum / count) of its points' colours, summed in fp64 in ascending point index (col NULL: zeros).  keys and colors
+ *     hold up to n rows; d_origin (f64 [3], device) receives the origin, d_count (i32, device) the number of voxels, or KPX_ERR_RANGE
+ *     when an index leaves [0, 2^21) (Open3D's "voxel_size is too small").  Asynchronous.
+ * kpx_voxelgrid_dense: all nw nh nd indices, ascending (gx, gy, gz), every voxel with h_color (host f32 [3]).  Every dimension
+ *     <= KPX_VOXELGRID_AXIS_CELLS, at most 2^31 - 1 voxels.  Asynchronous.
+ * kpx_voxelgrid_carve: carve_depth_map (mode KPX_VOXELGRID_DEPTH) / carve_silhouette (KPX_VOXELGRID_SILHOUETTE) with `count` images of
+ *     width x height >= 2 x 2 pixels taken with the pinhole h_intrinsic = (fx, fy, cx, cy) from h_extrinsics f64 [count][16] (world ->
+ *     camera, row-major, host).  A voxel survives an image when one of its 8 corners keeps it -- a corner projects to (u, v, z), WITHOUT
+ *     a test of the sign of z; outside the image it keeps iff keep_voxels_outside_image; inside, with d the bilinear sample of the image
+ *     there, it keeps iff d > 0 and (silhouette, or z >= d), and with keep_unmeasured also when !(d > 0) -- and it survives the call
+ *     when it survives every image: the result equals `count` calls with one image each, in any order.  One launch holds up to
+ *     KPX_VOXELGRID_MAX_IMAGES images, larger counts run as consecutive launches.  h_images: host array of device pointers [H W] of
+ *     `format`: KPX_VOXELGRID_F32 (depth_scale, depth_trunc ignored), KPX_VOXELGRID_U16 (d = (float)raw / (float)depth_scale,
+ *     d > (float)depth_trunc -> 0, as kpx_tsdf_integrate) or KPX_VOXELGRID_U8 (a mask: nonzero = 1).  Survivors go to out_keys /
+ *     out_colors (room for m rows; they must not alias the input) in their order, their number to d_count (i32, device).  Asynchronous.
+ * kpx_voxelgrid_included: out[i] = 1 iff query i (f32 [n][3], or f64 when queries_f64) lies in a voxel of the grid: g = floor((q -
+ *     origin) / voxel), every component in [0, 2^21) (NaN: not included), key present.  Asynchronous. */
+#define KPX_VOXELGRID_AXIS_CELLS 2097152
+#define KPX_VOXELGRID_MAX_IMAGES 8
+#define KPX_VOXELGRID_DEPTH 0
+#define KPX_VOXELGRID_SILHOUETTE 1
+#define KPX_VOXELGRID_F32 0
+#define KPX_VOXELGRID_U16 1
+#define KPX_VOXELGRID_U8 2
+size_t kpx_voxelgrid_from_cloud_workspace_bytes(int64_t n);
+int kpx_voxelgrid_from_cloud(const float *pts, const float *col, int64_t n, double voxel, const double *h_origin, uint64_t *keys, float *colors,
+                             double *d_origin, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_voxelgrid_dense(int32_t nw, int32_t nh, int32_t nd, const float *h_color, uint64_t *keys, float *colors, void *stream);
+size_t kpx_voxelgrid_carve_workspace_bytes(int64_t m);
+int kpx_voxelgrid_carve(const uint64_t *keys, const float *colors, int64_t m, const double *h_origin, double voxel, int32_t mode, int32_t count,
+                        const void *const *h_images, int32_t format, double depth_scale, double depth_trunc, int32_t width, int32_t height,
+                        const double *h_intrinsic, const double *h_extrinsics, int32_t keep_voxels_outside_image, int32_t keep_unmeasured,
+                        uint64_t *out_keys, float *out_colors, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_voxelgrid_included(const void *queries, int32_t queries_f64, int64_t n, const uint64_t *keys, int64_t m, const double *h_origin, double voxel,
+                           uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

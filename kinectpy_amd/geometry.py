@@ -516,3 +516,269 @@ class RGBDImage:
 
     def __repr__(self):
         return f"RGBDImage of size \nColor image : {self.color.width}x{self.color.height}, with {self.color.num_of_channels} channels.\nDepth image : {self.depth.width}x{self.depth.height}, with {self.depth.num_of_channels} channels."
+
+
+def _off_path(name):
+    def f(*a, **k):
+        raise NotImplementedError(f"{name} is outside the round-1 hot path of kinectpy_amd (SURVEY.md 8f); "
+                                  "there is no CPU fallback")
+    return f
+
+
+class Voxel:
+    """o3d.geometry.Voxel: grid_index (3 ints) and color (3 floats)"""
+
+    def __init__(self, grid_index=(0, 0, 0), color=(0.0, 0.0, 0.0)):
+        self.grid_index = np.asarray(grid_index, dtype=np.int32).reshape(3).copy()
+        self.color = np.asarray(color, dtype=np.float64).reshape(3).copy()
+
+    def __repr__(self):
+        return f"Voxel with grid_index: ({self.grid_index[0]}, {self.grid_index[1]}, {self.grid_index[2]}), color: ({self.color[0]:g}, {self.color[1]:g}, {self.color[2]:g})"
+
+
+def _pinhole(intrinsic):
+    """PinholeCameraIntrinsic-like -> (width, height, (fx, fy, cx, cy)); AC10 has no skew and K[2, 2] = 1"""
+    K = np.asarray(intrinsic.intrinsic_matrix, dtype=np.float64).reshape(3, 3)
+    if K[0, 1] != 0.0 or K[2, 2] != 1.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0:
+        raise RuntimeError("[VoxelGrid] the intrinsic matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew)")
+    return int(intrinsic.width), int(intrinsic.height), (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+
+
+class VoxelGrid:
+    """[O3D] geometry.VoxelGrid (arithmetic contract AC10): `origin`, `voxel_size` and M voxels kept on the device as
+    `_keys` (int64 (M,), gx << 42 | gy << 21 | gz, strictly ascending -- Open3D keeps a hash map, and its get_voxels() comes in the
+    map's order) with one float32 colour triple each (`_col`).  Besides Open3D's surface: the batch forms carve_depth_maps /
+    carve_silhouettes (raw uint16 frames / uint8 masks of all sensors in one pass), the device accessors voxel_indices / voxel_colors
+    and included_mask.  get_voxel_center_coordinate / get_voxel_bounding_points are pure arithmetic: they do not look the voxel up
+    (Open3D returns zeros for an absent one).  add_voxel, remove_voxel, the octree conversions and create_from_triangle_mesh are off
+    the path and raise."""
+    AXIS_BITS = ops.VOXELGRID_AXIS_BITS
+    AXIS_CELLS = 1 << AXIS_BITS
+
+    def __init__(self, other=None):
+        self.origin = np.zeros(3)
+        self.voxel_size = 0.0
+        self._keys = self._col = None
+        if other is not None:
+            self.origin, self.voxel_size = np.array(other.origin, dtype=np.float64).reshape(3), float(other.voxel_size)
+            if other._keys is not None:
+                self._keys, self._col = other._keys.clone(), other._col.clone()
+
+    @classmethod
+    def _make(cls, keys, col, origin, voxel_size):
+        g = cls()
+        g._keys, g._col = keys, col
+        g.origin, g.voxel_size = np.asarray(origin, dtype=np.float64).reshape(3).copy(), float(voxel_size)
+        return g
+
+    def __deepcopy__(self, memo):
+        return VoxelGrid(self)
+
+    __copy__ = lambda self: self.__deepcopy__({})
+
+    def _count(self):
+        return 0 if self._keys is None else int(self._keys.shape[0])
+
+    # ---- constructors -------------------------------------------------------------------------
+    @staticmethod
+    def create_from_point_cloud(input, voxel_size):
+        """origin = min_bound - voxel_size / 2; colour of a voxel = mean colour of its points (zeros without colours)"""
+        if not voxel_size > 0:
+            raise RuntimeError("[VoxelGrid] voxel_size <= 0.")
+        if not input.has_points():
+            return VoxelGrid._make(None, None, np.zeros(3) - float(voxel_size) * 0.5, voxel_size)
+        keys, col, origin = ops.voxelgrid_from_cloud(input._pts, float(voxel_size), input._col if input.has_colors() else None)
+        return VoxelGrid._make(keys, col, origin, voxel_size)
+
+    @staticmethod
+    def create_from_point_cloud_within_bounds(input, voxel_size, min_bound, max_bound):
+        """origin = min_bound; points beyond max_bound are indexed like any other, as Open3D does"""
+        if not voxel_size > 0:
+            raise RuntimeError("[VoxelGrid] voxel_size <= 0.")
+        lo, hi = (np.asarray(b, dtype=np.float64).reshape(3) for b in (min_bound, max_bound))
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise RuntimeError("[VoxelGrid] min_bound and max_bound must be finite")
+        if float(voxel_size) * float(np.iinfo(np.int32).max) < (hi - lo).max():
+            raise RuntimeError("[VoxelGrid] voxel_size is too small.")
+        if not input.has_points():
+            return VoxelGrid._make(None, None, lo, voxel_size)
+        keys, col, origin = ops.voxelgrid_from_cloud(input._pts, float(voxel_size), input._col if input.has_colors() else None, origin=lo)
+        return VoxelGrid._make(keys, col, origin, voxel_size)
+
+    @staticmethod
+    def create_dense(origin, color, voxel_size, width, height, depth):
+        """all round(extent / voxel_size) cells per axis (half away from zero, as std::round), every voxel with `color`"""
+        if not voxel_size > 0:
+            raise RuntimeError("[VoxelGrid] voxel_size <= 0.")
+        dims = []
+        for extent in (width, height, depth):
+            q = float(extent) / float(voxel_size)
+            if not np.isfinite(q) or q < -0.5:
+                raise RuntimeError("[VoxelGrid] create_dense: width, height and depth must be finite and non-negative")
+            n = np.floor(abs(q))
+            dims.append(int(n) + (1 if abs(q) - n >= 0.5 else 0))
+        if max(dims) > VoxelGrid.AXIS_CELLS or dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+            raise RuntimeError(f"[VoxelGrid] create_dense: at most 2^{VoxelGrid.AXIS_BITS} cells per axis and 2^31 - 1 voxels ({dims[0]} x {dims[1]} x {dims[2]})")
+        org = np.asarray(origin, dtype=np.float64).reshape(3)
+        if dims[0] * dims[1] * dims[2] == 0:
+            return VoxelGrid._make(None, None, org, voxel_size)
+        keys, col = ops.voxelgrid_dense(dims, np.asarray(color, dtype=np.float64).reshape(3))
+        return VoxelGrid._make(keys, col, org, voxel_size)
+
+    create_from_triangle_mesh = staticmethod(_off_path("VoxelGrid.create_from_triangle_mesh"))
+    create_from_triangle_mesh_within_bounds = staticmethod(_off_path("VoxelGrid.create_from_triangle_mesh_within_bounds"))
+    create_from_octree = _off_path("VoxelGrid.create_from_octree")
+    to_octree = _off_path("VoxelGrid.to_octree")
+    add_voxel = _off_path("VoxelGrid.add_voxel")
+    remove_voxel = _off_path("VoxelGrid.remove_voxel")
+
+    # ---- state --------------------------------------------------------------------------------
+    def has_voxels(self):
+        return self._count() > 0
+
+    def has_colors(self):
+        return True                     # [O3D]: always (a grid built without colours holds zeros)
+
+    def is_empty(self):
+        return not self.has_voxels()
+
+    def clear(self):
+        self.origin, self.voxel_size, self._keys, self._col = np.zeros(3), 0.0, None, None
+        return self
+
+    def __repr__(self):
+        return f"VoxelGrid with {self._count()} voxels."
+
+    @property
+    def voxel_indices(self):
+        """int32 (M, 3) device tensor, ascending (gx, gy, gz)"""
+        if self._keys is None:
+            return torch.empty((0, 3), dtype=torch.int32, device=L.device())
+        mask = self.AXIS_CELLS - 1
+        k = self._keys
+        return torch.stack([k >> (2 * self.AXIS_BITS), (k >> self.AXIS_BITS) & mask, k & mask], 1).to(torch.int32)
+
+    @property
+    def voxel_colors(self):
+        """float32 (M, 3) device tensor, in the order of voxel_indices"""
+        return torch.empty((0, 3), dtype=torch.float32, device=L.device()) if self._col is None else self._col
+
+    def get_voxels(self):
+        """host list of Voxel, ascending (gx, gy, gz)"""
+        if not self.has_voxels():
+            return []
+        idx, col = self.voxel_indices.cpu().numpy(), self._col.cpu().numpy().astype(np.float64)
+        return [Voxel(i, c) for i, c in zip(idx, col)]
+
+    # ---- index arithmetic (host, fp64) --------------------------------------------------------
+    def get_voxel(self, point):
+        p = np.asarray(point, dtype=np.float64).reshape(3)
+        return np.floor((p - self.origin) / self.voxel_size).astype(np.int32)
+
+    def get_voxel_center_coordinate(self, idx):
+        g = np.asarray(idx, dtype=np.float64).reshape(3)
+        return self.origin + (g + 0.5) * self.voxel_size
+
+    def get_voxel_bounding_points(self, index):
+        c, r = self.get_voxel_center_coordinate(index), self.voxel_size * 0.5
+        return [c + np.array(s) * r for s in ((-1, -1, -1), (-1, -1, 1), (1, -1, -1), (1, -1, 1), (-1, 1, -1), (-1, 1, 1), (1, 1, -1), (1, 1, 1))]
+
+    def _index_range(self):
+        idx = self.voxel_indices
+        return idx.min(0).values.cpu().numpy().astype(np.float64), idx.max(0).values.cpu().numpy().astype(np.float64)
+
+    def get_min_bound(self):
+        if not self.has_voxels():
+            return self.origin.copy()
+        return self.origin + self._index_range()[0] * self.voxel_size
+
+    def get_max_bound(self):
+        if not self.has_voxels():
+            return self.origin.copy()
+        return self.origin + (self._index_range()[1] + 1.0) * self.voxel_size
+
+    def get_center(self):
+        return (self.get_min_bound() + self.get_max_bound()) * 0.5
+
+    # ---- inclusion ----------------------------------------------------------------------------
+    def included_mask(self, points):
+        """device bool tensor: does each point (a PointCloud, Vector3dVector, (N, 3) float32 / float64 tensor or array) lie in a voxel"""
+        if isinstance(points, PointCloud):
+            points = points._pts
+        elif isinstance(points, Vector3dVector):
+            points = points.t
+        elif not isinstance(points, torch.Tensor):
+            points = np.asarray(points)
+            points = np.ascontiguousarray(points if points.dtype == np.float32 else points.astype(np.float64)).reshape(-1, 3)
+        if not self.voxel_size > 0:
+            raise RuntimeError("[VoxelGrid] voxel_size <= 0.")
+        keys = self._keys if self._keys is not None else torch.empty(0, dtype=torch.int64, device=L.device())
+        return ops.voxelgrid_included(keys, self.origin, self.voxel_size, points).to(torch.bool)
+
+    def check_if_included(self, queries):
+        return [bool(b) for b in self.included_mask(queries).cpu().tolist()]
+
+    # ---- carving ------------------------------------------------------------------------------
+    def _carve(self, mode, images, width, height, K, extrinsics, keep_outside, keep_unmeasured=False, depth_scale=1.0, depth_trunc=0.0):
+        if self.has_voxels():
+            self._keys, self._col = ops.voxelgrid_carve(self._keys, self._col, self.origin, self.voxel_size, mode, images, width, height, K, extrinsics,
+                                                        keep_outside, keep_unmeasured, depth_scale, depth_trunc)
+        return self
+
+    def _carve_image(self, who, mode, image, camera_params, keep_outside, keep_unmeasured):
+        width, height, K = _pinhole(camera_params.intrinsic)
+        a = np.asarray(image)
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        if a.ndim != 2 or a.dtype != np.float32:
+            raise RuntimeError(f"[VoxelGrid] {who}: Unsupported image format (one channel of float32 expected).")
+        if a.shape != (height, width):
+            raise RuntimeError(f"[VoxelGrid] provided {who} dimensions are not compatible with the provided camera_parameters")
+        if width < 2 or height < 2:
+            raise RuntimeError(f"[VoxelGrid] {who}: images need width, height >= 2")
+        E = np.asarray(camera_params.extrinsic, dtype=np.float64).reshape(1, 4, 4)
+        if not self.has_voxels():
+            return self
+        return self._carve(mode, [torch.as_tensor(np.ascontiguousarray(a)).to(L.device())], width, height, K, E, keep_outside, keep_unmeasured)
+
+    def carve_depth_map(self, depth_map, camera_params, keep_voxels_outside_image=False, keep_unmeasured=False):
+        """[O3D] carve_depth_map: a voxel stays when one of its 8 corners projects into the image at a pixel with 0 < depth <= z (or
+        outside it, with keep_voxels_outside_image).  keep_unmeasured (extension): a corner on a pixel without depth keeps too."""
+        return self._carve_image("depth_map", "depth", depth_map, camera_params, keep_voxels_outside_image, keep_unmeasured)
+
+    def carve_silhouette(self, silhouette_mask, camera_params, keep_voxels_outside_image=False):
+        """[O3D] carve_silhouette: a voxel stays when one of its 8 corners projects onto the mask (sample > 0)"""
+        return self._carve_image("silhouette_mask", "silhouette", silhouette_mask, camera_params, keep_voxels_outside_image, False)
+
+    def _frames(self, who, frames, dtypes, count, width, height):
+        if isinstance(frames, torch.Tensor):
+            t = frames.view(torch.uint8) if frames.dtype == torch.bool else frames
+        else:
+            a = np.ascontiguousarray(frames)
+            t = torch.as_tensor(a.view(np.uint8) if a.dtype == np.bool_ else a)
+        if t.dtype not in dtypes or t.numel() != count * width * height:
+            raise RuntimeError(f"[VoxelGrid] {who}: Unsupported image format.")
+        if width < 2 or height < 2:
+            raise RuntimeError(f"[VoxelGrid] {who}: images need width, height >= 2")
+        return t.reshape(count, width * height)
+
+    def carve_depth_maps(self, depths, intrinsic, extrinsics, keep_voxels_outside_image=False, depth_scale=1000.0, depth_trunc=3.0,
+                         keep_unmeasured=False):
+        """The batch form: S raw uint16 depth frames ((S, H W) or (S, H, W), host or device) and S extrinsics (world -> camera) carve
+        the grid in one pass; depth_scale / depth_trunc as in RGBDImage.create_from_color_and_depth, applied in the kernel.
+        Bit-identical to S carve_depth_map() calls with the converted float32 images, in any order."""
+        width, height, K = _pinhole(intrinsic)
+        E = np.asarray(extrinsics, dtype=np.float64).reshape(-1, 4, 4)
+        t = self._frames("carve_depth_maps", depths, (torch.uint16,), len(E), width, height)
+        if not self.has_voxels():
+            return self
+        return self._carve("depth", list(t.to(L.device())), width, height, K, E, keep_voxels_outside_image, keep_unmeasured, depth_scale, depth_trunc)
+
+    def carve_silhouettes(self, masks, intrinsic, extrinsics, keep_voxels_outside_image=False):
+        """The batch form of carve_silhouette: S uint8 or bool masks (nonzero = inside), one pass"""
+        width, height, K = _pinhole(intrinsic)
+        E = np.asarray(extrinsics, dtype=np.float64).reshape(-1, 4, 4)
+        t = self._frames("carve_silhouettes", masks, (torch.uint8,), len(E), width, height)
+        if not self.has_voxels():
+            return self
+        return self._carve("silhouette", list(t.to(L.device())), width, height, K, E, keep_voxels_outside_image)

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import ops
 from .geometry import (Image, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
-                       OrientedBoundingBox, PointCloud, RGBDImage, Vector2iVector, Vector3dVector)
+                       OrientedBoundingBox, PointCloud, RGBDImage, Vector2iVector, Vector3dVector, Voxel, VoxelGrid, _off_path)
 from . import integration as _integration
 from . import pcd_io
 from . import posegraph
@@ -423,18 +423,31 @@ class PinholeCameraIntrinsic:
         return f"PinholeCameraIntrinsic with width = {self.width} and height = {self.height}.\nAccess intrinsics with intrinsic_matrix."
 
 
-def _off_path(name):
-    def f(*a, **k):
-        raise NotImplementedError(f"{name} is outside the round-1 hot path of kinectpy_amd (SURVEY.md 8f); "
-                                  "there is no CPU fallback")
-    return f
+class PinholeCameraParameters:
+    """[O3D] camera.PinholeCameraParameters: `intrinsic` (PinholeCameraIntrinsic) and `extrinsic` (4x4 float64, world -> camera)"""
+
+    def __init__(self, intrinsic=None, extrinsic=None):
+        self.intrinsic = PinholeCameraIntrinsic() if intrinsic is None else intrinsic
+        self.extrinsic = np.eye(4) if extrinsic is None else extrinsic
+
+    extrinsic = property(lambda self: self._extrinsic)
+
+    @extrinsic.setter
+    def extrinsic(self, E):
+        E = np.array(E, dtype=np.float64)
+        if E.shape != (4, 4):
+            raise RuntimeError("PinholeCameraParameters: extrinsic must be a 4x4 matrix")
+        self._extrinsic = E
+
+    def __repr__(self):
+        return "PinholeCameraParameters class.\nAccess its data via intrinsic and extrinsic."
 
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
-                                 Image=Image, RGBDImage=RGBDImage,
+                                 Image=Image, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
-camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic)
+camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic, PinholeCameraParameters=PinholeCameraParameters)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
 io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
 pipelines = types.SimpleNamespace(integration=types.SimpleNamespace(

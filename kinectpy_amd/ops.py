@@ -1203,3 +1203,96 @@ def tsdf_extract(volume, color, resolution, voxel_length, origin, mode="surface"
     L.check(lib.kpx_tsdf_extract_fill(L.ptr(volume), L.ptr(color), int(resolution), float(voxel_length), L.hptr(org), m, total, L.ptr(pts),
                                       L.ptr(nrm), L.ptr(col), L.ptr(ws), ws.numel(), L.stream_ptr()))
     return pts, nrm, col
+
+
+# ---- occupancy grids ------------------------------------------------------------------------------------
+VOXELGRID_MODES = {"depth": 0, "silhouette": 1}          # KPX_VOXELGRID_DEPTH / KPX_VOXELGRID_SILHOUETTE (include/kinectpx.h)
+VOXELGRID_FORMATS = {torch.float32: 0, torch.uint16: 1, torch.uint8: 2}          # KPX_VOXELGRID_F32 / U16 / U8
+VOXELGRID_AXIS_BITS = 21
+
+
+def _origin3(origin):
+    return np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+
+
+def voxelgrid_from_cloud(pts, voxel, col=None, origin=None):
+    """[O3D] VoxelGrid.create_from_point_cloud (origin None: min_bound - voxel / 2) / create_from_point_cloud_within_bounds (origin =
+    the caller's min_bound) -> (keys int64 (M,) ascending, gx << 42 | gy << 21 | gz; colours float32 (M, 3), zeros without `col`;
+    origin float64[3] host).  One host read (count and origin)."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    col = _dev(col, torch.float32).reshape(-1, 3) if col is not None else None
+    if col is not None and col.shape[0] != n:
+        raise L.KinectPxError("voxelgrid_from_cloud: one colour per point")
+    dev = pts.device
+    keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    oc = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
+    org = torch.empty(3, dtype=torch.float64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    h_org = _origin3(origin) if origin is not None else None
+    ws, wsz = L.workspace(lib.kpx_voxelgrid_from_cloud_workspace_bytes(n))
+    L.check(lib.kpx_voxelgrid_from_cloud(L.ptr(pts), L.ptr(col), n, float(voxel), L.hptr(h_org) if h_org is not None else None, L.ptr(keys),
+                                         L.ptr(oc), L.ptr(org), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    m = _count(cnt)[0]
+    return keys[:m], oc[:m], org.cpu().numpy()
+
+
+def voxelgrid_dense(dims, color):
+    """[O3D] VoxelGrid.create_dense's voxels: all dims[0] x dims[1] x dims[2] indices, ascending, with one colour -> (keys, colours)"""
+    lib = L.load()
+    nw, nh, nd = (int(d) for d in dims)
+    total = max(nw, 0) * max(nh, 0) * max(nd, 0)
+    if total > 2 ** 31 - 1:
+        total = 1                       # the library raises before it writes anything
+    dev = L.device()
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    oc = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    c = np.ascontiguousarray(np.asarray(color, dtype=np.float32).reshape(3))
+    L.check(lib.kpx_voxelgrid_dense(nw, nh, nd, L.hptr(c), L.ptr(keys), L.ptr(oc), L.stream_ptr()))
+    return keys, oc
+
+
+def voxelgrid_carve(keys, colors, origin, voxel, mode, images, width, height, intrinsic, extrinsics, keep_voxels_outside_image=False,
+                    keep_unmeasured=False, depth_scale=1.0, depth_trunc=0.0):
+    """[O3D] VoxelGrid.carve_depth_map (mode "depth") / carve_silhouette ("silhouette") with len(images) images in one pass over the
+    voxels (kpx_voxelgrid_carve).  images: device tensors (H W), all float32, all uint16 (raw depth; depth_scale / depth_trunc applied
+    in the kernel) or all uint8 (masks, nonzero = 1); intrinsic (fx, fy, cx, cy); extrinsics (S, 4, 4) world -> camera.
+    -> the surviving (keys, colours), in order."""
+    lib = L.load()
+    cnt = len(images)
+    dt = images[0].dtype if cnt else torch.float32
+    if dt not in VOXELGRID_FORMATS or any(i.dtype != dt for i in images):
+        raise L.KinectPxError("voxelgrid_carve: images must all be float32, all uint16 or all uint8")
+    images = [_dev(i, dt).reshape(-1) for i in images]
+    if any(i.numel() != int(width) * int(height) for i in images):
+        raise L.KinectPxError("voxelgrid_carve: image size does not match width x height")
+    m = int(keys.shape[0])
+    dev = keys.device
+    E = np.ascontiguousarray(np.asarray(extrinsics, dtype=np.float64).reshape(cnt, 16))
+    K = np.ascontiguousarray(np.asarray(intrinsic, dtype=np.float64).reshape(4))
+    org = _origin3(origin)
+    ok = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    oc = torch.empty((max(m, 1), 3), dtype=torch.float32, device=dev)
+    d_cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    arr = C.cast((C.c_void_p * max(cnt, 1))(*[t.data_ptr() for t in images]), C.c_void_p)
+    ws, wsz = L.workspace(lib.kpx_voxelgrid_carve_workspace_bytes(m))
+    L.check(lib.kpx_voxelgrid_carve(L.ptr(keys), L.ptr(colors), m, L.hptr(org), float(voxel), VOXELGRID_MODES[mode], cnt, arr, VOXELGRID_FORMATS[dt],
+                                    float(depth_scale), float(depth_trunc), int(width), int(height), L.hptr(K), L.hptr(E),
+                                    int(bool(keep_voxels_outside_image)), int(bool(keep_unmeasured)), L.ptr(ok), L.ptr(oc), L.ptr(d_cnt), ws, wsz,
+                                    L.stream_ptr()))
+    k = _count(d_cnt)[0]
+    return ok[:k], oc[:k]
+
+
+def voxelgrid_included(keys, origin, voxel, queries):
+    """[O3D] VoxelGrid.check_if_included: queries float32 or float64 (N, 3) (anything else is taken as float64) -> uint8 (N,) device
+    tensor, 1 = the query lies in a voxel of the grid"""
+    lib = L.load()
+    f64 = not (isinstance(queries, torch.Tensor) and queries.dtype == torch.float32) and not (isinstance(queries, np.ndarray) and queries.dtype == np.float32)
+    q = _dev(queries, torch.float64 if f64 else torch.float32).reshape(-1, 3)
+    n = q.shape[0]
+    out = torch.empty(n, dtype=torch.uint8, device=q.device)
+    org = _origin3(origin)
+    L.check(lib.kpx_voxelgrid_included(L.ptr(q), int(f64), n, L.ptr(keys), int(keys.shape[0]), L.hptr(org), float(voxel), L.ptr(out), L.stream_ptr()))
+    return out

@@ -1,9 +1,12 @@
 """Volumetric fusion of one frame set: every sensor's depth image integrated into one TSDF volume in the master's frame with the
 calibrated sensor -> master transforms, then the surface cloud extracted (o3d.pipelines.integration on the rig's own arrays).  An
 alternative to DataProcessor's transform + vstack + voxel_down_sample + remove_statistical_outlier fuse; the frame step is
-unchanged."""
+unchanged.  remove_free_space_points is the rig's space-carving filter: it drops the points of a fused cloud that lie where some
+sensor sees through (flying pixels), which the density filters keep."""
 import numpy as np
+import torch
 
+from ..geometry import VoxelGrid
 from ..integration import TSDFVolumeColorType, UniformTSDFVolume
 from ..utils import synth
 
@@ -31,3 +34,23 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     vol = UniformTSDFVolume(length, resolution, sdf_trunc, TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor, origin)
     vol.integrate_frames(depth, rgb, intrinsic, np.stack(extr), depth_scale, depth_trunc)
     return vol.extract_point_cloud()
+
+
+def remove_free_space_points(pcd, depth, intrinsic, sensor_to_master, voxel_size, keep_unmeasured=True, depth_scale=1.0, depth_trunc=6000.0):
+    """pcd: the fused cloud in the master's frame; depth, intrinsic, sensor_to_master, depth_scale, depth_trunc as in fuse_depth_tsdf.
+    The cloud's VoxelGrid (voxel_size) is carved by every sensor's depth map in one pass (carve_depth_maps with
+    keep_voxels_outside_image=True: a sensor that does not see a voxel says nothing about it); a point is kept when its voxel
+    survived.  keep_unmeasured=True: a pixel without depth is no evidence of free space (Open3D's rule, False, carves its whole
+    ray).  -> (PointCloud of the kept points, their indices in pcd: ascending int32 device tensor)"""
+    if intrinsic is None:
+        intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
+    n = int(depth.shape[0])
+    if len(sensor_to_master) != n - 1:
+        raise RuntimeError(f"remove_free_space_points: {n} sensors need {n - 1} sensor -> master transforms, got {len(sensor_to_master)}")
+    extr = [np.eye(4)] + [np.linalg.inv(np.asarray(T, dtype=np.float64).reshape(4, 4)) for T in sensor_to_master]
+    grid = VoxelGrid.create_from_point_cloud(pcd, voxel_size)
+    grid.carve_depth_maps(depth, intrinsic, np.stack(extr), True, depth_scale, depth_trunc, keep_unmeasured)
+    kept = torch.nonzero(grid.included_mask(pcd)).reshape(-1).to(torch.int32)
+    if not pcd.has_points() or kept.numel() == 0:
+        return type(pcd)(), kept
+    return pcd._select(kept), kept

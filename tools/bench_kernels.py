@@ -52,10 +52,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
+    ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.tsdf:
         return tsdf_rows(dev, a.quick)
+    if a.voxelgrid:
+        return voxelgrid_rows(dev, a.quick)
     F = 64 if a.quick else 256
     xy = synth.xy_table()
     base_d, person = synth.render_depth(xy=xy, return_person=True)
@@ -305,6 +308,7 @@ def main():
            ms_per_iteration=round(ms / (r["iterations"] + 1), 4), dense_equivalent_flops=int(dense * (r["iterations"] + 1)),
            **sweep(ops.prof_end()))
     tsdf_rows(dev, a.quick)
+    voxelgrid_rows(dev, a.quick)
 
 
 def tsdf_rows(dev, quick):
@@ -346,6 +350,70 @@ def tsdf_rows(dev, quick):
                 ms, (vp, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "voxels"))
                 report(f"tsdf extract_voxel_point_cloud ({tag})", ms, 8 * res ** 3 + int(vp.shape[0]) * 24, points=int(vp.shape[0]))
             del vol, col
+
+
+def voxelgrid_rows(dev, quick):
+    """Occupancy grids on S = 4 full-size ring frames: the grid of the fused cloud, carving a dense 2 m grid by the four
+    depth frames in one pass against four single-image calls, inclusion of the fused cloud, and the rig's filter end to end.
+    Algorithmic traffic of a carve: 8 B key + 12 B colour per voxel read, the same per survivor written, plus the images."""
+    from kinectpy_amd import o3d
+    from kinectpy_amd.preprocessing.fusion import remove_free_space_points
+    S = 4
+    _, depth, rgb, _, truth = synth.sensor_ring(S, 1)
+    K = (synth.FX, synth.FY, synth.CX, synth.CY)
+    to_master = [np.eye(4)] + list(truth)
+    parts, cols = [], []
+    for s in range(S):                               # the pinhole unprojection of every frame, moved into the master's frame (host)
+        pix = np.flatnonzero(depth[0, s] > 0)
+        z = depth[0, s][pix].astype(np.float64)
+        p = np.stack([((pix % synth.W) - K[2]) / K[0] * z, ((pix // synth.W) - K[3]) / K[1] * z, z, np.ones_like(z)], 1) @ to_master[s].T
+        parts.append(p[:, :3].astype(np.float32))
+        cols.append(rgb[0, s][pix].astype(np.float32) / np.float32(255.0))
+    pts, col = torch.as_tensor(np.concatenate(parts)).to(dev), torch.as_tensor(np.concatenate(cols)).to(dev)
+    n = int(pts.shape[0])
+    depth_d = [torch.as_tensor(depth[0, s]).to(dev) for s in range(S)]
+    extr = np.stack([np.linalg.inv(T) for T in to_master])
+    images = S * N_PX * 2
+
+    ms, (keys, kcol, origin) = timed(lambda: ops.voxelgrid_from_cloud(pts, 10.0, col))
+    m = int(keys.shape[0])
+    report("voxelgrid create_from_point_cloud (fused ring cloud, 10 mm; one host read)", ms, 24 * n + 20 * m, points=n, voxels=m)
+    ms, mask = timed(lambda: ops.voxelgrid_included(keys, origin, 10.0, pts))
+    report("voxelgrid included_mask (fused ring cloud in its own 10 mm grid)", ms, 13 * n, points=n, included=int(mask.sum().item()))
+
+    carve = lambda k, c, org, v, ims, E: ops.voxelgrid_carve(k, c, org, v, "depth", ims, synth.W, synth.H, K, E, False, False, 1.0, 6000.0)
+    for v in ((10.0,) if quick else (10.0, 5.0)):
+        cells = int(round(2000.0 / v))
+        org = (-1000.0, -1100.0, 1500.0)             # the master's frame: the person stands 2500 in front of it
+        dk, dc = ops.voxelgrid_dense((cells, cells, cells), (0.5, 0.5, 0.5))
+        total = cells ** 3
+        ms_batch, (k1, _) = timed(lambda: carve(dk, dc, org, v, depth_d, extr))
+        left = int(k1.shape[0])
+        tag = f"dense {cells}^3 at {v:g} mm, {S} x 640x576 u16"
+        report(f"voxelgrid carve_depth_maps one pass ({tag})", ms_batch, 20 * (total + left) + images, voxels=total, survivors=left)
+
+        def one_by_one():
+            k, c = dk, dc
+            for s in range(S):
+                k, c = carve(k, c, org, v, depth_d[s:s + 1], extr[s:s + 1])
+            return k
+
+        moved = 0
+        k, c = dk, dc
+        for s in range(S):
+            moved += 20 * int(k.shape[0])
+            k, c = carve(k, c, org, v, depth_d[s:s + 1], extr[s:s + 1])
+            moved += 20 * int(k.shape[0])
+        ms_single, k4 = timed(one_by_one)
+        assert torch.equal(k4, k1)
+        report(f"voxelgrid {S} carve calls of one image ({tag})", ms_single, moved + images, voxels=total, survivors=int(k4.shape[0]),
+               single_over_batch=round(ms_single / ms_batch, 3))
+        del dk, dc, k1, k4, k, c
+
+    pc = o3d.geometry.PointCloud._make(pts, col)
+    ms, (out, kept) = timed(lambda: remove_free_space_points(pc, depth[0], None, truth, 10.0))
+    report("remove_free_space_points (fused ring cloud, 10 mm, 4 frames; grid + carve + inclusion + select, host frames uploaded)", ms, points=n,
+           kept=int(kept.shape[0]))
 
 
 if __name__ == "__main__":
