@@ -682,6 +682,11 @@ int kpx_stream_destroy(kpx_stream *stream);
  * was measured slower than a chain of launches per frame and removed: DESIGN.md section 5.2). */
 int kpx_stream_stats(const kpx_stream *stream, uint64_t *h_out4);
 
+/* What the library's per-thread owners hold right now, summed over the host threads of the process:
+   h_out4[0] bytes of pinned host memory, [1] internal HIP streams, [2] HIP events, [3] threads holding any.
+   Host arithmetic only; all zero in a process that never touched a GPU. */
+int kpx_host_resources(uint64_t *h_out4);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------- */
 /* HIP-event timing of the hot kernels on the stream they are launched on.  kpx_prof_begin arms it
  * (capacity = max launches recorded); every launch of a tagged kernel is bracketed by an event pair;

@@ -244,7 +244,9 @@ KPX_EXPORT int kpx_copy_bytes(void *dst, const void *src, size_t bytes, void *st
     return KPX_OK;
 }
 
-// slot memory, for kpx_frame.hip
+// slot memory, for kpx_frame.hip.  It stays with the communicator and is NOT keyed by host thread: every rank must derive the same
+// message size for a slot's frame, and under pipeline.FrameStream a slot's frames run on whichever pool thread is free -- per-thread
+// capacities would let the ranks disagree and hang a collective.
 namespace kpx {
 int64_t &comm_cap_master(kpx_comm *c) { return c->cap_master; }
 int64_t &comm_cap_clouds(kpx_comm *c) { return c->cap_clouds; }

@@ -2,11 +2,19 @@
 // registration of data.py:127-161 folded in, the unit bench.py measures): host orchestration in C++ over the library's own
 // C ABI.  The Python mirror of the same loop (kinectpy_amd/pipeline.py) issues ~12 library calls per frame with interpreter
 // work, tensor allocations and the GIL in between; with several frames in flight on host threads that interpreter time is
-// serialised.  Here a frame is a single call with the GIL released throughout; everything lives in the caller's workspace.
+// serialised.  Here a frame is a single call with the GIL released throughout; everything lives in the caller's workspace,
+// except the calling thread's pinned read-back block (FrameReadback) and its memory of the previous frame (FrameState): both
+// belong to the thread's ThreadResources (kpx_internal.h) and are released when the thread ends.
 #include <chrono>
 #include <vector>
 
 #include "kpx_internal.h"
+
+#define KPX_SUB(call)                    \
+    do {                                 \
+        const int rc__ = (call);         \
+        if (rc__) return rc__;           \
+    } while (0)
 
 namespace kpx {
 
@@ -24,20 +32,49 @@ __global__ void frame_flag_kernel(unsigned long long *flag, unsigned long long s
 {
     __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-static int frame_wait(hipStream_t st)
+constexpr int kHdrDoubles = 24;        // per sensor: [0] masked points, [1] down-sampled points, [2..21] registration (T, fitness, rmse, iterations, pairs)
+
+// Everything a frame reads back, one pinned block per host thread (kPinFrame), shared by the one-GPU and the sharded step.
+// Counts that only the HOST reads next are written by the kernels straight into it (device-visible host memory): every D2H copy of
+// a few bytes is a dispatch of its own (~5 us) in front of the read-back it serves.  Counts that later kernels read (the fused
+// cloud's, the registrations' results) stay in device memory and are copied.
+struct FrameReadback {
+    double icp[16 * 20 + 1];              // registration i at [20 i, 20 i + 20); kpx_frame_step: the fused count's slot behind the last (ONE copy)
+    double master_rows;                   // (sharded) the broadcast header: rank 0's master count
+    double hdr[32 * kHdrDoubles];         // (sharded) the gathered header rows: world x k_max <= sensors + world - 1 <= 31 rows
+    int32_t full[16], masked[16], down[16];      // per sensor: valid pixels, person pixels, registration voxels
+    int32_t fused, kept;                  // the fused cloud's voxels, the filter's survivors
+    int32_t reg_bits, fuse_bits;          // sort-key widths the registration grids / the fused cloud need
+    alignas(64) unsigned long long done;  // completion word (frame_wait), on a cache line of its own
+};
+// what the stages of one frame share
+struct FrameRun {
+    hipStream_t st;
+    ThreadResources &tr;
+    FrameReadback *blk;
+    void *op_ws;                           // the frame's one scratch region: the operators run one after the other on `st`
+    size_t op_bytes;
+};
+static int frame_run_open(FrameRun &r)
+{
+    r.blk = static_cast<FrameReadback *>(r.tr.pinned(kPinFrame, sizeof(FrameReadback)));
+    return r.blk ? KPX_OK : KPX_ERR_HIP;
+}
+// KPX_FRAME_SPECULATE=0: no sort-key width is carried from one frame to the next (A/B switch)
+static bool frame_speculate() { static const bool on = [] { const char *e = getenv("KPX_FRAME_SPECULATE"); return !(e && e[0] == '0'); }(); return on; }
+static int spec_width(int need) { return need > 0 && need <= 32 ? (need + 7) / 8 * 8 : 0; }      // whole 8-bit passes; wide keys are not speculated
+static int negative(const int32_t *c, int n) { for (int i = 0; i < n; ++i) if (c[i] < 0) return c[i]; return 0; }
+
+static int frame_wait(const FrameRun &r)
 {
     static const bool spin = [] { const char *e = getenv("KPX_FRAME_SPIN"); return !(e && e[0] == '0'); }();
+    hipStream_t st = r.st;
     if (!spin) {
         KPX_HIP(hipStreamSynchronize(st));
         return KPX_OK;
     }
-    static thread_local unsigned long long *flag = nullptr;
-    static thread_local unsigned long long seq = 0;
-    if (!flag) {
-        KPX_HIP(hipHostMalloc((void **)&flag, 64, hipHostMallocDefault));
-        *flag = 0ull;
-    }
-    ++seq;
+    unsigned long long *flag = &r.blk->done;
+    const unsigned long long seq = ++r.tr.frame_seq;
     hipLaunchKernelGGL(frame_flag_kernel, dim3(1), dim3(1), 0, st, flag, seq);
     KPX_LAUNCH_CHECK();
     auto t0 = std::chrono::steady_clock::now();
@@ -58,13 +95,6 @@ static int frame_wait(hipStream_t st)
     }
 }
 
-struct FrameLayout {
-    float *full_pts, *mask_pts, *mask_col, *down_pts, *normals, *vox_pts, *vox_col;
-    int32_t *vox_cnt, *keep_idx;
-    double *icp_res, *sor_stats;
-    void *op_ws;
-    size_t op_bytes;
-};
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 static void frame_carve(Arena &a, int32_t S, int64_t n_px, FrameLayout *L)
 {
@@ -93,6 +123,55 @@ static void frame_carve(Arena &a, int32_t S, int64_t n_px, FrameLayout *L)
     L->op_ws = a.get<char>(w);
 }
 
+// ---- stages the one-GPU and the sharded step share ---------------------------------------------------------------------------
+// The registration voxel grids of `n` clouds.  The sort-key width is speculated from the previous frame (`spec_bits`: the calling
+// thread's, or the slot's under a communicator -- the scene's extent in voxels barely changes from frame to frame): its read-back
+// inside the call is one host round trip less; a frame that needs more bits is detected with the counts (FrameReadback::down,
+// reg_bits) and done again the careful way.
+static int reg_grids_speculated(const FrameRun &r, int n, const float *const *p_in, const int64_t *h_n, double voxel, float *const *p_out, bool zorder, int &spec_bits)
+{
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        KPX_SUB(voxel_downsample_batch_spec(n, p_in, nullptr, h_n, voxel, p_out, nullptr, r.blk->down, r.op_ws, r.op_bytes, r.st, attempt == 0 ? spec_bits : 0,
+                                            &r.blk->reg_bits, zorder));
+        KPX_SUB(frame_wait(r));
+        const int need = r.blk->reg_bits;
+        const bool narrow = attempt == 0 && spec_bits > 0 && need > spec_bits;
+        spec_bits = spec_width(need);
+        if (!narrow) break;
+    }
+    return KPX_OK;
+}
+// pcd.transform(T_i) + np.vstack + voxel_down_sample in one fp64 pass.  The fused cloud's sort-key width is speculated like the
+// registration grids' (<= 32 bits: the library's own radix sort); a frame that needs more is seen at the read-back and fused again
+// the careful way.  Each attempt's read-back also brings `bytes` from d_src to h_dst (the steps differ in what they fetch with it).
+static int fuse_speculated(const FrameRun &r, int S, const float *const *pts, const float *const *col, const int64_t *h_n, const double *h_T,
+                           const double *const *h_dT, double voxel, float *vox_pts, float *vox_col, int32_t *vox_cnt, int &fuse_spec, void *h_dst,
+                           const void *d_src, size_t bytes)
+{
+    if (!frame_speculate()) fuse_spec = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        r.blk->fuse_bits = 0;
+        KPX_SUB(fuse_voxel_downsample_dev(S, pts, col, h_n, h_T, h_dT, voxel, vox_pts, vox_col, vox_cnt, r.op_ws, r.op_bytes, r.st, attempt == 0 ? fuse_spec : 0,
+                                          &r.blk->fuse_bits));
+        KPX_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, r.st));
+        KPX_SUB(frame_wait(r));
+        const int need = r.blk->fuse_bits;
+        const bool narrow = attempt == 0 && fuse_spec > 0 && need > fuse_spec;
+        fuse_spec = frame_speculate() ? spec_width(need) : 0;
+        if (!narrow) break;
+    }
+    return KPX_OK;
+}
+// remove_statistical_outlier + selection of the M fused voxels in one pass (no count read-back between them)
+static int filter_select(const FrameRun &r, const float *vox_pts, const float *vox_col, int64_t M, const kpx_frame_params *prm, float *out_pts, float *out_col,
+                         int32_t *keep_idx, double *sor_stats, int32_t *h_count)
+{
+    KPX_SUB(kpx_sor_select(vox_pts, vox_col, M, prm->filt_k, prm->filt_ratio, out_pts, out_col, keep_idx, &r.blk->kept, sor_stats, r.op_ws, r.op_bytes, r.st));
+    KPX_SUB(frame_wait(r));
+    *h_count = r.blk->kept;
+    return KPX_OK;
+}
+
 }  // namespace kpx
 
 using namespace kpx;
@@ -105,12 +184,6 @@ KPX_EXPORT size_t kpx_frame_step_workspace_bytes(int32_t sensors, int64_t n_px)
     frame_carve(a, sensors, n_px, &L);
     return a.off;
 }
-
-#define KPX_SUB(call)                    \
-    do {                                 \
-        const int rc__ = (call);         \
-        if (rc__) return rc__;           \
-    } while (0)
 
 KPX_EXPORT int kpx_frame_step(const uint16_t *depth, const uint8_t *rgb, const float *xy_table, int64_t n_px, int32_t sensors,
                               const double *h_init, const kpx_frame_params *prm, float *out_pts, float *out_col, int32_t *h_count,
@@ -128,40 +201,28 @@ KPX_EXPORT int kpx_frame_step(const uint16_t *depth, const uint8_t *rgb, const f
     const int S = sensors;
     hipStream_t st = (hipStream_t)stream;
     BusyScope busy;                                        // (a frame in flight: see kpx_internal.h)
+    ThreadResources &tr = thread_resources();
+    FrameState &prev = tr.frame;                           // the previous frame of this host thread
     // (the layout is a function of (workspace, sensors, pixels): carved once per thread and slot -- the carve walks every operator's
     // workspace query, ~100 us of host time in front of a frame's first kernel)
-    static thread_local struct { void *ws; size_t bytes; int S; int64_t n_px; FrameLayout L; size_t off; } cache = { nullptr, 0, 0, 0, {}, 0 };
-    FrameLayout L;
-    if (cache.ws == ws && cache.bytes == ws_bytes && cache.S == S && cache.n_px == n_px) {
-        L = cache.L;
-    } else {
+    if (!(prev.carved.ws == ws && prev.carved.bytes == ws_bytes && prev.carved.S == S && prev.carved.n_px == n_px)) {
         Arena a(ws, ws_bytes);
-        frame_carve(a, S, n_px, &L);
+        FrameLayout carved;
+        frame_carve(a, S, n_px, &carved);
         KPX_ARENA_CHECK(a);
-        cache.ws = ws; cache.bytes = ws_bytes; cache.S = S; cache.n_px = n_px; cache.L = L; cache.off = a.off;
+        prev.carved = { ws, ws_bytes, S, n_px, carved };
     }
-    // pinned read-back area of the calling thread: counts and ICP results.  ONE allocation (the doubles first), published only when
-    // it succeeded; it lives as long as the thread's runtime context (a few KiB per host thread that ever ran a frame).
-    static thread_local double *h_d = nullptr;
-    static thread_local int32_t *h_i = nullptr;
-    if (!h_i) {
-        void *blk = nullptr;
-        KPX_HIP(hipHostMalloc(&blk, (16 * 20 + 1) * sizeof(double) + 256 * sizeof(int32_t), hipHostMallocDefault));
-        h_d = static_cast<double *>(blk);
-        h_i = reinterpret_cast<int32_t *>(h_d + (16 * 20 + 1));
-    }
-    auto negative = [&](const int32_t *c, int n) { for (int i = 0; i < n; ++i) if (c[i] < 0) return c[i]; return 0; };
-
+    const FrameLayout L = prev.carved.L;
+    FrameRun run{ st, tr, nullptr, L.op_ws, L.op_bytes };
+    KPX_SUB(frame_run_open(run));
+    FrameReadback *blk = run.blk;
     // extract: the registration input (every valid pixel) and the person clouds (mask + depth gate + colours); both are queued
     // before the first count is read
-    // Counts that only the HOST reads next are written by the kernels straight into the thread's pinned area (device-visible host
-    // memory): every D2H copy of a few bytes is a dispatch of its own (~5 us) in front of the read-back it serves.  Counts that
-    // later kernels read (the fused cloud's, the registrations' results) stay in device memory and are copied.
-    if (!fixed) KPX_SUB(kpx_depth_to_cloud(depth, xy_table, nullptr, n_px, S, 0, prm->gate, L.full_pts, nullptr, nullptr, h_i, L.op_ws, L.op_bytes, st));
-    else for (int i = 0; i < S; ++i) h_i[i] = 0;
+    if (!fixed) KPX_SUB(kpx_depth_to_cloud(depth, xy_table, nullptr, n_px, S, 0, prm->gate, L.full_pts, nullptr, nullptr, blk->full, L.op_ws, L.op_bytes, st));
+    else for (int i = 0; i < S; ++i) blk->full[i] = 0;
     // (every operator runs on `st`: stream order alone makes the shared scratch region safe)
     KPX_SUB(kpx_depth_to_cloud(depth, xy_table, rgb, n_px, S, KPX_COMPACT_COLOR_MASK | KPX_COMPACT_DEPTH_GATE, prm->gate, L.mask_pts, L.mask_col, nullptr,
-                               h_i + 16, L.op_ws, L.op_bytes, st));
+                               blk->masked, L.op_ws, L.op_bytes, st));
     static const int extra_dispatches = [] { const char *e = getenv("KPX_FRAME_EXTRA_DISPATCHES"); return e ? atoi(e) : 0; }();
     for (int e = 0; e < extra_dispatches; ++e) hipLaunchKernelGGL(frame_empty_kernel, dim3(1), dim3(64), 0, st);
     std::vector<int64_t> fk((size_t)S), mk((size_t)S), dk((size_t)S);
@@ -169,32 +230,20 @@ KPX_EXPORT int kpx_frame_step(const uint16_t *depth, const uint8_t *rgb, const f
     std::vector<const float *> p_in((size_t)S), c_in((size_t)S);
     std::vector<float *> p_out((size_t)S);
     for (int i = 0; i < S; ++i) { p_in[(size_t)i] = L.full_pts + (size_t)i * n_px * 3; p_out[(size_t)i] = L.down_pts + (size_t)i * n_px * 3; }
-    KPX_SUB(frame_wait(st));                     // read-back 1: both extractions' counts
-    for (int i = 0; i < S; ++i) { fk[(size_t)i] = h_i[i]; mk[(size_t)i] = h_i[16 + i]; }
-    if (negative(h_i, S) || negative(h_i + 16, S)) return fail(KPX_ERR_RANGE, "kpx_frame_step: extraction reported %d", negative(h_i, S) | negative(h_i + 16, S));
-    // The sort-key width of the registration voxel grid is speculated from the last frame of this thread (the scene's extent in
-    // voxels barely changes from frame to frame): its read-back inside the call is one host round trip less; a frame that needs
-    // more bits is detected with the counts and done again the careful way.
+    KPX_SUB(frame_wait(run));                      // read-back 1: both extractions' counts
+    for (int i = 0; i < S; ++i) { fk[(size_t)i] = blk->full[i]; mk[(size_t)i] = blk->masked[i]; }
+    if (negative(blk->full, S) || negative(blk->masked, S))
+        return fail(KPX_ERR_RANGE, "kpx_frame_step: extraction reported %d", negative(blk->full, S) | negative(blk->masked, S));
     // The registration clouds leave the voxel grid along the curve of their voxel indices (one point per voxel: the order the
     // culled search would otherwise establish with a sort of its own -- 12 dispatches per frame).  Normals and nearest neighbours are
     // per point; the update sums are a tree per 16-row tile, so the order does move the transforms' last bits: it is fixed by the
     // frame's shape alone (the switch that chose it per process is gone).
     const bool zorder = S <= 8;                      // the voxel batch's one-pass form (the only one with the curve order) takes 8 clouds
-    static thread_local int spec_bits = 0;
-    static const bool speculate = [] { const char *e = getenv("KPX_FRAME_SPECULATE"); return !(e && e[0] == '0'); }();      // A/B switch
-    if (!speculate) spec_bits = 0;
-    for (int i = 0; i < S; ++i) h_i[32 + i] = 0;
-    for (int attempt = 0; attempt < 2 && !fixed; ++attempt) {
-        KPX_SUB(voxel_downsample_batch_spec(S, p_in.data(), nullptr, fk.data(), prm->reg_voxel, p_out.data(), nullptr, h_i + 32, L.op_ws, L.op_bytes, st,
-                                            attempt == 0 ? spec_bits : 0, h_i + 50, zorder));
-        KPX_SUB(frame_wait(st));
-        const int need = h_i[50];
-        const bool narrow = attempt == 0 && spec_bits > 0 && need > spec_bits;
-        spec_bits = need > 0 && need <= 32 ? (need + 7) / 8 * 8 : 0;      // whole 8-bit passes; wide keys are not speculated
-        if (!narrow) break;
-    }
-    if (negative(h_i + 32, S)) return fail(KPX_ERR_RANGE, "voxel_size is too small");
-    for (int i = 0; i < S; ++i) dk[(size_t)i] = h_i[32 + i];
+    if (!frame_speculate()) prev.spec_bits = 0;
+    for (int i = 0; i < S; ++i) blk->down[i] = 0;
+    if (!fixed) KPX_SUB(reg_grids_speculated(run, S, p_in.data(), fk.data(), prm->reg_voxel, p_out.data(), zorder, prev.spec_bits));
+    if (negative(blk->down, S)) return fail(KPX_ERR_RANGE, "voxel_size is too small");
+    for (int i = 0; i < S; ++i) dk[(size_t)i] = blk->down[i];
     for (int q = 0; q < 16; ++q) h_T[q] = (q % 5 == 0) ? 1.0 : 0.0;
     if (h_info) for (int i = 0; i < S; ++i) { h_info[i] = (int32_t)dk[(size_t)i]; h_info[16 + i] = (int32_t)mk[(size_t)i]; h_info[32 + i] = 0; }
     if (fixed)
@@ -218,42 +267,29 @@ KPX_EXPORT int kpx_frame_step(const uint16_t *depth, const uint8_t *rgb, const f
         p_in[(size_t)i] = L.mask_pts + (size_t)i * n_px * 3; c_in[(size_t)i] = L.mask_col + (size_t)i * n_px * 3;
         if (i > 0 && !fixed) dT[(size_t)i] = L.icp_res + 20 * (size_t)(i - 1);
     }
-    // The fused cloud's sort-key width is speculated from this thread's previous frame, like the registration grids' above: <= 32 bits,
-    // the library's own radix sort; a frame that needs more is seen at the read-back below and fused again the careful way.
-    static thread_local int fuse_spec = 0;
-    if (!speculate) fuse_spec = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        h_i[51] = 0;
-        KPX_SUB(fuse_voxel_downsample_dev(S, p_in.data(), c_in.data(), mk.data(), h_T, dT.data(), prm->filt_voxel, L.vox_pts, L.vox_col, L.vox_cnt, L.op_ws,
-                                          L.op_bytes, st, attempt == 0 ? fuse_spec : 0, h_i + 51));
-        KPX_HIP(hipMemcpyAsync(h_d, L.icp_res, ((size_t)S * 20 + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-        KPX_SUB(frame_wait(st));
-        const int need = h_i[51];
-        const bool narrow = attempt == 0 && fuse_spec > 0 && need > fuse_spec;
-        fuse_spec = (speculate && need > 0 && need <= 32) ? (need + 7) / 8 * 8 : 0;      // whole 8-bit passes; wide keys are not speculated
-        if (!narrow) break;
-    }
-    h_i[48] = *reinterpret_cast<const int32_t *>(h_d + (size_t)S * 20);
-    for (int i = 1; i < S && !fixed; ++i)                  // (a one-launch ICP chain that lost its race for residency: its results are NaN)
-        if (h_d[20 * (i - 1) + 16] != h_d[20 * (i - 1) + 16]) {
+    // (the registrations' results and the fused count come home in ONE copy, with the fuse's read-back)
+    KPX_SUB(fuse_speculated(run, S, p_in.data(), c_in.data(), mk.data(), h_T, dT.data(), prm->filt_voxel, L.vox_pts, L.vox_col, L.vox_cnt, prev.fuse_spec, blk->icp,
+                            L.icp_res, ((size_t)S * 20 + 1) * sizeof(double)));
+    blk->fused = *reinterpret_cast<const int32_t *>(blk->icp + (size_t)S * 20);
+    for (int i = 1; i < S && !fixed; ++i) {                // (a one-launch ICP chain that lost its race for residency: its results are NaN)
+        const double *res = blk->icp + 20 * (i - 1);
+        if (res[16] != res[16]) {
             (void)icp_chain_abort_take();
             return fail(KPX_ERR_HIP, "kpx_frame_step: the one-launch ICP chain of sensor %d gave up waiting for its blocks to become resident; KPX_ICP_CHAIN=0 "
                                      "selects the launch-per-iteration form", i);
         }
-    for (int i = 1; i < S && !fixed; ++i) {
-        for (int q = 0; q < 16; ++q) h_T[16 * i + q] = h_d[20 * (i - 1) + q];
-        if (h_info) h_info[32 + i] = (int32_t)h_d[20 * (i - 1) + 18];
     }
-    if (h_i[48] < 0) return fail(KPX_ERR_RANGE, "voxel_size is too small");
-    const int64_t M = h_i[48];
+    for (int i = 1; i < S && !fixed; ++i) {
+        const double *res = blk->icp + 20 * (i - 1);
+        for (int q = 0; q < 16; ++q) h_T[16 * i + q] = res[q];
+        if (h_info) h_info[32 + i] = (int32_t)res[18];
+    }
+    if (blk->fused < 0) return fail(KPX_ERR_RANGE, "voxel_size is too small");
+    const int64_t M = blk->fused;
     if (h_info) h_info[48] = (int32_t)M;
     *h_count = 0;
     if (M == 0) return KPX_OK;
-    // filter + selection in one pass (no count read-back between them)
-    KPX_SUB(kpx_sor_select(L.vox_pts, L.vox_col, M, prm->filt_k, prm->filt_ratio, out_pts, out_col, L.keep_idx, h_i + 49, L.sor_stats, L.op_ws, L.op_bytes, st));
-    KPX_SUB(frame_wait(st));
-    *h_count = h_i[49];
-    return KPX_OK;
+    return filter_select(run, L.vox_pts, L.vox_col, M, prm, out_pts, out_col, L.keep_idx, L.sor_stats, h_count);
 }
 
 // The same frame handed over in HOST memory ("depth frame resident in host pinned memory -> fused registered cloud
@@ -303,8 +339,6 @@ int64_t &comm_cap_master(kpx_comm *c);
 int64_t &comm_cap_clouds(kpx_comm *c);
 int &comm_spec_bits(kpx_comm *c);
 int &comm_fuse_bits(kpx_comm *c);
-
-constexpr int kHdrDoubles = 24;        // per sensor: [0] masked points, [1] down-sampled points, [2..21] registration (T, fitness, rmse, iterations, pairs)
 
 static int shard_first(int n_sensors, int rank, int world)
 {
@@ -389,19 +423,6 @@ static void shard_carve(Arena &a, int S, int S_l, int world, int64_t n_px, bool 
     L->op_ws = a.get<char>(w);
 }
 
-// pinned read-back block of the calling thread (32 KiB): [0, 8K) doubles, [8K, 12K) ints, [12K, 32K) gathered headers
-static int pinned_block(char **out)
-{
-    static thread_local char *blk = nullptr;
-    if (!blk) {
-        void *p = nullptr;
-        KPX_HIP(hipHostMalloc(&p, 32768, hipHostMallocDefault));
-        blk = static_cast<char *>(p);
-    }
-    *out = blk;
-    return KPX_OK;
-}
-
 }  // namespace kpx
 
 KPX_EXPORT size_t kpx_frame_step_sharded_workspace_bytes(int32_t sensors, int32_t rank, int32_t world, int64_t n_px, int32_t host_input)
@@ -441,12 +462,9 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     shard_carve(a, S, S_l, world, n_px, host_input != 0, &L);
     KPX_ARENA_CHECK(a);
     const int K = L.k_max;
-    char *pin = nullptr;
-    KPX_SUB(pinned_block(&pin));
-    double *h_d = reinterpret_cast<double *>(pin);
-    int32_t *h_i = reinterpret_cast<int32_t *>(pin + 8192);
-    double *h_hdr = reinterpret_cast<double *>(pin + 12288);                     // world x K x kHdrDoubles doubles <= 16 x 24 x 8 B
-    auto negative = [&](const int32_t *c, int n) { for (int i = 0; i < n; ++i) if (c[i] < 0) return c[i]; return 0; };
+    FrameRun run{ st, thread_resources(), nullptr, L.op_ws, L.op_bytes };
+    KPX_SUB(frame_run_open(run));
+    FrameReadback *blk = run.blk;
     *h_count = 0;
     if (h_info) memset(h_info, 0, 64 * sizeof(int32_t));
 
@@ -457,34 +475,27 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
         rgb = L.stage_rgb;
     }
     // -- this rank's sensors: registration input (every valid pixel) and person clouds (mask + gate + colours)
-    KPX_SUB(kpx_depth_to_cloud(depth, xy_table, nullptr, n_px, S_l, 0, prm->gate, L.full_pts, nullptr, nullptr, h_i, L.op_ws, L.op_bytes, st));
+    KPX_SUB(kpx_depth_to_cloud(depth, xy_table, nullptr, n_px, S_l, 0, prm->gate, L.full_pts, nullptr, nullptr, blk->full, L.op_ws, L.op_bytes, st));
     KPX_SUB(kpx_depth_to_cloud(depth, xy_table, rgb, n_px, S_l, KPX_COMPACT_COLOR_MASK | KPX_COMPACT_DEPTH_GATE, prm->gate, L.mask_pts, L.mask_col, nullptr,
-                               h_i + 16, L.op_ws, L.op_bytes, st));
+                               blk->masked, L.op_ws, L.op_bytes, st));
     std::vector<int64_t> fk((size_t)S_l), mk((size_t)S_l), dk((size_t)S_l);
     std::vector<const float *> p_in((size_t)S_l);
     std::vector<float *> p_out((size_t)S_l);
     for (int i = 0; i < S_l; ++i) { p_in[(size_t)i] = L.full_pts + (size_t)i * n_px * 3; p_out[(size_t)i] = L.down_pts + (size_t)i * n_px * 3; }
-    KPX_SUB(frame_wait(st));
-    for (int i = 0; i < S_l; ++i) { fk[(size_t)i] = h_i[i]; mk[(size_t)i] = h_i[16 + i]; }
+    KPX_SUB(frame_wait(run));
+    for (int i = 0; i < S_l; ++i) { fk[(size_t)i] = blk->full[i]; mk[(size_t)i] = blk->masked[i]; }
     // A data-dependent failure on ONE rank (an occluded camera, a voxel size too small for its cloud) must not leave its peers
     // spinning inside a collective it never enters: the rank keeps its place in the frame's collectives with an empty payload and a
     // NEGATIVE count in the header it contributes (master header: rank 0; exchange header rows: every rank), every rank reads the
     // same headers and all of them return an error behind the same collective -- as the capacity overflow does with KPX_RETRY.
     int lerr = KPX_OK;
-    if (negative(h_i, S_l) || negative(h_i + 16, S_l)) lerr = fail(KPX_ERR_RANGE, "kpx_frame_step_sharded: extraction reported %d", negative(h_i, S_l) | negative(h_i + 16, S_l));
+    if (negative(blk->full, S_l) || negative(blk->masked, S_l))
+        lerr = fail(KPX_ERR_RANGE, "kpx_frame_step_sharded: extraction reported %d", negative(blk->full, S_l) | negative(blk->masked, S_l));
     const bool zorder = K <= 8;                                // the same decision on every rank: the master arrives in the order rank 0 gave it
-    int &spec_bits = comm_spec_bits(comm);
-    for (int attempt = 0; attempt < 2 && !lerr; ++attempt) {
-        KPX_SUB(voxel_downsample_batch_spec(S_l, p_in.data(), nullptr, fk.data(), prm->reg_voxel, p_out.data(), nullptr, h_i + 32, L.op_ws, L.op_bytes, st,
-                                            attempt == 0 ? spec_bits : 0, h_i + 50, zorder));
-        KPX_SUB(frame_wait(st));
-        const int need = h_i[50];
-        const bool narrow = attempt == 0 && spec_bits > 0 && need > spec_bits;
-        spec_bits = need > 0 && need <= 32 ? (need + 7) / 8 * 8 : 0;
-        if (!narrow) break;
-    }
-    if (!lerr && negative(h_i + 32, S_l)) lerr = fail(KPX_ERR_RANGE, "voxel_size is too small");
-    for (int i = 0; i < S_l; ++i) dk[(size_t)i] = lerr ? 0 : h_i[32 + i];
+    // (the width speculated from the SLOT's previous frame; an extraction error skips the grids, the rank keeps its place below)
+    if (!lerr) KPX_SUB(reg_grids_speculated(run, S_l, p_in.data(), fk.data(), prm->reg_voxel, p_out.data(), zorder, comm_spec_bits(comm)));
+    if (!lerr && negative(blk->down, S_l)) lerr = fail(KPX_ERR_RANGE, "voxel_size is too small");
+    for (int i = 0; i < S_l; ++i) dk[(size_t)i] = lerr ? 0 : blk->down[i];
     for (int i = 0; i < S_l && !lerr; ++i)
         if (dk[(size_t)i] < 1) lerr = fail(KPX_ERR_INVALID, "kpx_frame_step_sharded: sensor %d has no valid pixel", g0 + i);
 
@@ -518,8 +529,8 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
             KPX_HIP(hipMemcpyAsync(m_xyz, L.down_pts, rows * 12, hipMemcpyDeviceToDevice, st));
             if (ship_n) KPX_HIP(hipMemcpyAsync(m_nrm, L.normals, rows * 12, hipMemcpyDeviceToDevice, st));
         }
-        h_d[0] = lerr ? -1.0 : (double)dk[0];                   // a negative count: rank 0 cannot provide the master (every rank returns)
-        KPX_HIP(hipMemcpyAsync(m_hdr, h_d, sizeof(double), hipMemcpyHostToDevice, st));
+        blk->master_rows = lerr ? -1.0 : (double)dk[0];         // a negative count: rank 0 cannot provide the master (every rank returns)
+        KPX_HIP(hipMemcpyAsync(m_hdr, &blk->master_rows, sizeof(double), hipMemcpyHostToDevice, st));
     }
     kpx_order_turn_begin(order, frame, 0);
     int rc = kpx_comm_broadcast(comm, msg, (size_t)capm * row_b + 256, 0, st);
@@ -531,9 +542,9 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     }
     int64_t m = owns_master ? dk[0] : 0;
     if (!owns_master) {
-        KPX_HIP(hipMemcpyAsync(h_d, m_hdr, sizeof(double), hipMemcpyDeviceToHost, st));
-        KPX_SUB(frame_wait(st));
-        m = (int64_t)h_d[0];
+        KPX_HIP(hipMemcpyAsync(&blk->master_rows, m_hdr, sizeof(double), hipMemcpyDeviceToHost, st));
+        KPX_SUB(frame_wait(run));
+        m = (int64_t)blk->master_rows;
         if (!(m >= 1 && m <= n_px)) {
             kpx_order_finish(order, frame);
             return m < 0 ? fail(KPX_ERR_RANGE, "kpx_frame_step_sharded: rank 0 could not provide the master cloud (see its error)")
@@ -593,8 +604,8 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     kpx_order_turn_end(order, frame, 1);
     if (rc) return rc;
     const size_t hrow = (size_t)K * kHdrDoubles * sizeof(double);
-    KPX_HIP(hipMemcpy2DAsync(h_hdr, hrow, L.xchg_recv + (size_t)capc * 24, xbytes, hrow, (size_t)world, hipMemcpyDeviceToHost, st));
-    KPX_SUB(frame_wait(st));
+    KPX_HIP(hipMemcpy2DAsync(blk->hdr, hrow, L.xchg_recv + (size_t)capc * 24, xbytes, hrow, (size_t)world, hipMemcpyDeviceToHost, st));
+    KPX_SUB(frame_wait(run));
     std::vector<const float *> f_p((size_t)S), f_c((size_t)S);
     std::vector<int64_t> f_n((size_t)S);
     int64_t need = 0;
@@ -602,7 +613,7 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
         const int own = shard_count(S, r, world);
         int64_t off = 0;
         for (int j = 0; j < own; ++j, ++g) {
-            const double *row = h_hdr + ((size_t)r * K + j) * kHdrDoubles;
+            const double *row = blk->hdr + ((size_t)r * K + j) * kHdrDoubles;
             const int64_t n = (int64_t)row[0];
             if (!(n >= 0 && n <= n_px)) {                          // the same rows on every rank: everyone returns here
                 kpx_order_finish(order, frame);
@@ -634,25 +645,12 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
         kpx_order_skip(order, frame, 2);
         return KPX_OK;
     }
-    // -- fuse: pcd.transform(T_i) + np.vstack + voxel_down_sample in one fp64 pass (every rank that filters: identical everywhere)
-    // (the fused cloud's key width speculated from the slot's previous frame, as in kpx_frame_step: the library's own radix sort instead
-    // of the vendor's merge sort; every rank fuses the same cloud, so every rank speculates and -- rarely -- repeats alike)
-    int &fuse_spec = comm_fuse_bits(comm);
-    static const bool speculate_fuse = [] { const char *e = getenv("KPX_FRAME_SPECULATE"); return !(e && e[0] == '0'); }();
-    if (!speculate_fuse) fuse_spec = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        h_i[51] = 0;
-        KPX_SUB(fuse_voxel_downsample_dev(S, f_p.data(), f_c.data(), f_n.data(), h_T, nullptr, prm->filt_voxel, L.vox_pts, L.vox_col, L.vox_cnt, L.op_ws,
-                                          L.op_bytes, st, attempt == 0 ? fuse_spec : 0, h_i + 51));
-        KPX_HIP(hipMemcpyAsync(h_i + 48, L.vox_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        KPX_SUB(frame_wait(st));
-        const int need_bits = h_i[51];
-        const bool narrow = attempt == 0 && fuse_spec > 0 && need_bits > fuse_spec;
-        fuse_spec = (speculate_fuse && need_bits > 0 && need_bits <= 32) ? (need_bits + 7) / 8 * 8 : 0;
-        if (!narrow) break;
-    }
-    if (h_i[48] < 0) return fail(KPX_ERR_RANGE, "voxel_size is too small");
-    const int64_t M = h_i[48];
+    // -- fuse (every rank that filters: identical everywhere).  The key width is speculated from the SLOT's previous frame; every
+    // rank fuses the same cloud, so every rank speculates and -- rarely -- repeats alike.  The transforms are the host's (h_T).
+    KPX_SUB(fuse_speculated(run, S, f_p.data(), f_c.data(), f_n.data(), h_T, nullptr, prm->filt_voxel, L.vox_pts, L.vox_col, L.vox_cnt, comm_fuse_bits(comm),
+                            &blk->fused, L.vox_cnt, sizeof(int32_t)));
+    if (blk->fused < 0) return fail(KPX_ERR_RANGE, "voxel_size is too small");
+    const int64_t M = blk->fused;
     if (h_info) h_info[48] = (int32_t)M;
     if (M == 0) {
         kpx_order_skip(order, frame, 2);
@@ -660,10 +658,7 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     }
     if (fused_filter >= 1) {                                   // the owner, alone: the one-GPU filter + selection
         kpx_order_skip(order, frame, 2);
-        KPX_SUB(kpx_sor_select(L.vox_pts, L.vox_col, M, prm->filt_k, prm->filt_ratio, out_pts, out_col, L.keep_idx, h_i + 49, L.sor_stats, L.op_ws, L.op_bytes, st));
-        KPX_SUB(frame_wait(st));
-        *h_count = h_i[49];
-        return KPX_OK;
+        return filter_select(run, L.vox_pts, L.vox_col, M, prm, out_pts, out_col, L.keep_idx, L.sor_stats, h_count);
     }
     // -- sharded filter: this rank searches the neighbours of slab `rank` of the grid order; collective 2 = the slabs' mean distances
     const int64_t rows = (M + world - 1) / world;
@@ -674,15 +669,15 @@ KPX_EXPORT int kpx_frame_step_sharded(kpx_comm *comm, kpx_order *order, int64_t 
     kpx_order_turn_end(order, frame, 2);
     if (rc) return rc;
     KPX_SUB(kpx_sor_finish(L.avg_all, L.order_idx, M, prm->filt_ratio, L.keep_idx, L.keep_cnt, L.sor_stats, nullptr, L.op_ws, L.op_bytes, st));
-    KPX_HIP(hipMemcpyAsync(h_i + 49, L.keep_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KPX_SUB(frame_wait(st));
-    const int64_t kept = h_i[49];
+    KPX_HIP(hipMemcpyAsync(&blk->kept, L.keep_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    KPX_SUB(frame_wait(run));
+    const int64_t kept = blk->kept;
     if (kept > 0) {
         KPX_SUB(kpx_select_by_index(L.vox_pts, L.vox_col, nullptr, M, L.keep_idx, kept, KPX_SELECT_GATHER, out_pts, out_col, nullptr, nullptr, L.op_ws,
                                     L.op_bytes, st));
         // the rows are complete when the call returns, as kpx_frame_step's are (a kpx_stream hands them to the caller without another
         // synchronisation; until round 5 pipeline.FrameStream synchronised the slot's stream behind every step)
-        KPX_SUB(frame_wait(st));
+        KPX_SUB(frame_wait(run));
     }
     *h_count = (int32_t)kept;
     return KPX_OK;

@@ -1085,12 +1085,10 @@ struct ProgressWindow {
 
     int open(double stall_seconds)
     {
-        static thread_local unsigned long long *h_progress = nullptr;
-        static thread_local unsigned long long last_generation = 0;
-        if (!h_progress) KPX_HIP(hipHostMalloc((void **)&h_progress, 64 * sizeof(unsigned long long), hipHostMallocDefault));
-        last_generation = (last_generation + 1) & 0xFFFFFFull;
-        words = h_progress;
-        generation = last_generation;
+        ThreadResources &tr = thread_resources();
+        words = static_cast<unsigned long long *>(tr.pinned(kPinIcpProgress, 64 * sizeof(unsigned long long)));
+        if (!words) return KPX_ERR_HIP;
+        generation = tr.icp_generation = (tr.icp_generation + 1) & 0xFFFFFFull;
         stall_limit = stall_seconds;
         t_last = std::chrono::steady_clock::now();
         return KPX_OK;
@@ -1349,8 +1347,8 @@ static int drive_windowed(const BatchCtx &x)
 // -- and queues the next iteration.
 static int drive_dense_polled(const BatchCtx &x)
 {
-    static thread_local IcpState *h_states = nullptr;   // pinned: two poll slots per problem (per calling thread)
-    if (!h_states) KPX_HIP(hipHostMalloc((void **)&h_states, 64 * 2 * sizeof(IcpState), hipHostMallocDefault));
+    IcpState *h_states = static_cast<IcpState *>(thread_resources().pinned(kPinIcpStates, 64 * 2 * sizeof(IcpState)));   // two poll slots per problem
+    if (!h_states) return KPX_ERR_HIP;
     hipEvent_t ev[64][2];
     int made = 0, rc = KPX_OK;
     for (; made < 2 * x.count && !rc; ++made)
@@ -1419,9 +1417,6 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
     (void)icp_chain_abort_take();
     // the problems of a batch are independent chains of short, latency-bound kernels: they run side by side on the
     // library's internal lanes (kpx_internal.h), forked from / joined to the caller's stream by events
-    LaneSet *ln = nullptr;
-    int lrc = lanes_get(&ln);
-    if (lrc) return lrc;
     Arena a(ws, ws_bytes);
     BatchLayout L;
     const bool can_batch_sort = batch_carve(a, count, h_n_src, n_tgt, &L);
@@ -1453,8 +1448,10 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
     const int n_chain = grouped ? (int)cdiv(count, kIcpBatchMax) : count;
     const bool on_caller = grouped && n_chain == 1;
     const int used_lanes = on_caller ? 0 : (n_chain < kLaneCount ? n_chain : kLaneCount);
+    LaneSet *ln = nullptr;                          // (the thread's lanes exist only once one of its calls has forked)
+    if (used_lanes && (rc = lanes_get(&ln))) return rc;
     const BatchCtx ctx{ count, h_src, h_n_src, tgt, tgt_normals, h_init, max_dist * max_dist, mode, max_iteration, relative_fitness, relative_rmse, d_results,
-                        plans, &tplan, bufs, ordered, st, ln->s, n_chain, on_caller };
+                        plans, &tplan, bufs, ordered, st, ln ? ln->s : nullptr, n_chain, on_caller };
     if (used_lanes) rc = lanes_fork(ln, st, used_lanes);
     if (!rc) rc = grouped ? drive_grouped(ctx) : local_engine() ? drive_windowed(ctx) : drive_dense_polled(ctx);
     if (used_lanes) {

@@ -37,15 +37,57 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
 // Batched entry points run their independent problems (chains of short, latency-bound kernels) side by side on
 // kLaneCount internal streams: lanes_fork makes the lanes wait for everything queued on the caller's stream,
 // lanes_join makes the caller's stream wait for everything queued on the lanes.  One set per host thread and device,
-// created at first use.
+// created when a call first forks (lanes_get) and held by the thread's ThreadResources.
 constexpr int kLaneCount = 4;
+constexpr int kLaneDevices = 16;
 struct LaneSet {
     hipStream_t s[kLaneCount];
-    hipEvent_t fork, join[kLaneCount];
+    hipEvent_t fork, join[kLaneCount];      // (fork is created last: non-null = the set is complete)
 };
 int lanes_get(LaneSet **out);
 int lanes_fork(LaneSet *l, hipStream_t caller, int used);
 int lanes_join(LaneSet *l, hipStream_t caller, int used);
+
+// ---- what a host thread holds -----------------------------------------------------------------------
+// Every host-side HIP resource the library keeps per calling thread lives in ONE thread_local object (kpx_misc.hip): the pinned
+// read-back blocks of the sites below, the lane sets, and the plain counters and caches that go with them.  Its destructor runs when
+// the thread ends (a kpx_stream worker: before kpx_stream_destroy's join returns) and gives everything back, ignoring every error
+// code -- a runtime that has already shut down must not turn a normal exit into a failure.  kpx_host_resources sums what all
+// threads hold.
+enum PinnedSite { kPinFrame, kPinVoxelBits, kPinIcpProgress, kPinIcpStates, kPinnedSites };
+
+// kpx_frame_step's memory of "the previous frame of this host thread"
+struct FrameLayout {
+    float *full_pts, *mask_pts, *mask_col, *down_pts, *normals, *vox_pts, *vox_col;
+    int32_t *vox_cnt, *keep_idx;
+    double *icp_res, *sor_stats;
+    void *op_ws;
+    size_t op_bytes;
+};
+struct FrameState {
+    struct { void *ws; size_t bytes; int S; int64_t n_px; FrameLayout L; } carved;      // the layout is a function of these four
+    int spec_bits, fuse_spec;              // speculated sort-key widths: registration grids, fused cloud (0 = none)
+};
+
+struct ThreadResources {
+    void *pin[kPinnedSites] = {};
+    size_t pin_bytes[kPinnedSites] = {};
+    LaneSet lanes[kLaneDevices] = {};
+    unsigned long long frame_seq = 0;      // kPinFrame's completion word: the value the next wait stores
+    unsigned long long icp_generation = 0; // kPinIcpProgress: the last call's tag
+    FrameState frame = {};
+    bool counted = false;                  // this thread is in the "threads holding any" count
+
+    // the site's block, allocated (and zeroed) at first use; nullptr = the allocation failed (the thread's error is set)
+    void *pinned(PinnedSite site, size_t bytes) { return pin[site] ? pin[site] : pinned_alloc(site, bytes); }
+    ThreadResources() = default;
+    ~ThreadResources();
+    ThreadResources(const ThreadResources &) = delete;
+    ThreadResources &operator=(const ThreadResources &) = delete;
+    void *pinned_alloc(PinnedSite site, size_t bytes);
+    void hold();
+};
+ThreadResources &thread_resources();
 
 // kpx_voxel_downsample_batch with a speculated sort-key width (kpx_frame_step): spec_bits > 0 skips the width's read-back (one host
 // round trip per call); *d_bits receives the width the batch needs (0 = the call did not speculate) and the caller repeats the call

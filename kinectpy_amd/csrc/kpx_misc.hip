@@ -1,5 +1,6 @@
 // kpx_misc.hip -- container operations of the Open3D surface the path touches:
 // transform, select_by_index, half-space select, slab split, bounding box.  HBM-streaming.
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include "kpx_internal.h"
@@ -260,24 +261,67 @@ __global__ __launch_bounds__(256) void bbox_final_kernel(const double *__restric
         bbox[threadIdx.x] = r;
     }
 }
+// ---- what a host thread holds (kpx_internal.h) -------------------------------------------------------------------
+// process-wide sums over the threads' owners: [0] pinned bytes, [1] streams, [2] events, [3] threads holding any
+static std::atomic<uint64_t> g_held[4];
+ThreadResources &thread_resources()
+{
+    static thread_local ThreadResources mine;
+    return mine;
+}
+void ThreadResources::hold()
+{
+    if (!counted) g_held[3].fetch_add(1, std::memory_order_relaxed);
+    counted = true;
+}
+void *ThreadResources::pinned_alloc(PinnedSite site, size_t bytes)
+{
+    void *p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        fail(KPX_ERR_HIP, "hipHostMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    memset(p, 0, bytes);
+    pin[site] = p;
+    pin_bytes[site] = bytes;
+    g_held[0].fetch_add(bytes, std::memory_order_relaxed);
+    hold();
+    return p;
+}
+ThreadResources::~ThreadResources()
+{
+    for (int i = 0; i < kPinnedSites; ++i)
+        if (pin[i]) {
+            (void)hipHostFree(pin[i]);
+            g_held[0].fetch_sub(pin_bytes[i], std::memory_order_relaxed);
+        }
+    for (LaneSet &set : lanes) {
+        for (int l = 0; l < kLaneCount; ++l) {
+            if (set.s[l]) { (void)hipStreamDestroy(set.s[l]); g_held[1].fetch_sub(1, std::memory_order_relaxed); }
+            if (set.join[l]) { (void)hipEventDestroy(set.join[l]); g_held[2].fetch_sub(1, std::memory_order_relaxed); }
+        }
+        if (set.fork) { (void)hipEventDestroy(set.fork); g_held[2].fetch_sub(1, std::memory_order_relaxed); }
+    }
+    if (counted) g_held[3].fetch_sub(1, std::memory_order_relaxed);
+}
 int lanes_get(LaneSet **out)
 {
     // one set per host thread and device: the fork / join events belong to one call at a time, and streams belong to
     // the device that was current when they were created
-    constexpr int kMaxDevices = 16;
-    static thread_local LaneSet sets[kMaxDevices];
-    static thread_local bool ready[kMaxDevices] = {};
     int dev = 0;
     KPX_HIP(hipGetDevice(&dev));
-    KPX_REQUIRE(dev >= 0 && dev < kMaxDevices, "lanes_get: device ordinal %d out of range", dev);
-    LaneSet &set = sets[dev];
-    if (!ready[dev]) {
+    KPX_REQUIRE(dev >= 0 && dev < kLaneDevices, "lanes_get: device ordinal %d out of range", dev);
+    ThreadResources &tr = thread_resources();
+    LaneSet &set = tr.lanes[dev];
+    if (!set.fork) {                       // (what an earlier, failed attempt did create is kept and counted)
+        tr.hold();
         for (int l = 0; l < kLaneCount; ++l) {
-            KPX_HIP(hipStreamCreateWithFlags(&set.s[l], hipStreamNonBlocking));
-            KPX_HIP(hipEventCreateWithFlags(&set.join[l], hipEventDisableTiming));
+            if (!set.s[l]) { KPX_HIP(hipStreamCreateWithFlags(&set.s[l], hipStreamNonBlocking)); g_held[1].fetch_add(1, std::memory_order_relaxed); }
+            if (!set.join[l]) { KPX_HIP(hipEventCreateWithFlags(&set.join[l], hipEventDisableTiming)); g_held[2].fetch_add(1, std::memory_order_relaxed); }
         }
         KPX_HIP(hipEventCreateWithFlags(&set.fork, hipEventDisableTiming));
-        ready[dev] = true;
+        g_held[2].fetch_add(1, std::memory_order_relaxed);
     }
     *out = &set;
     return KPX_OK;
@@ -465,6 +509,13 @@ static int grid_for(int64_t work, int per_block, int cap = 4096)
 }  // namespace kpx
 
 using namespace kpx;
+
+KPX_EXPORT int kpx_host_resources(uint64_t *h_out4)
+{
+    KPX_REQUIRE(h_out4, "kpx_host_resources: null pointer");
+    for (int i = 0; i < 4; ++i) h_out4[i] = g_held[i].load(std::memory_order_relaxed);
+    return KPX_OK;
+}
 
 KPX_EXPORT int kpx_transform(const float *pts, int64_t n, const double *h_T, float *out, void *stream)
 {

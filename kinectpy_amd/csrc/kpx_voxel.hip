@@ -311,8 +311,8 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
         // (a 4-sensor frame needs ~25, a 1M-point room at 10 mm 25) be written, sorted and compared as 32-bit words by the library's
         // own radix sort -- three 8-bit passes instead of the vendor sort's eight over 64-bit keys.  Below ~128k points the vendor's
         // merge sort of a handful of launches is as fast as the round trip.
-        static thread_local int32_t *h_bits = nullptr;
-        if (!h_bits) KPX_HIP(hipHostMalloc((void **)&h_bits, sizeof(int32_t), hipHostMallocDefault));
+        int32_t *h_bits = static_cast<int32_t *>(thread_resources().pinned(kPinVoxelBits, sizeof(int32_t)));
+        if (!h_bits) return KPX_ERR_HIP;
         hipLaunchKernelGGL(voxel_batch_bits_kernel, dim3(1), dim3(1), 0, st, b, s.bbox, voxel, s.head);
         KPX_HIP(hipMemcpyAsync(h_bits, s.head, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (d_bits) KPX_HIP(hipMemcpyAsync(d_bits, s.head, sizeof(int32_t), hipMemcpyDefault, st));      // d_bits may be pinned host memory (kpx_frame_step)

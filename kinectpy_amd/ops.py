@@ -798,6 +798,14 @@ def icp_batch(srcs, tgt, max_dist, inits, mode="p2p", tgt_normals=None, max_iter
              "iterations": int(r[i, 18]), "count": int(r[i, 19])} for i in range(cnt)]
 
 
+def host_resources():
+    """kpx_host_resources: what the library's per-thread owners hold right now, summed over the host threads of the process
+    -> {"pinned_bytes", "streams", "events", "threads"}.  A thread's share is given back when the thread ends."""
+    out = np.zeros(4, dtype=np.uint64)
+    L.check(L.load().kpx_host_resources(out.ctypes.data_as(C.c_void_p)))
+    return dict(zip(("pinned_bytes", "streams", "events", "threads"), (int(v) for v in out)))
+
+
 # ---- the frame loop as one native call ---------------------------------------------------------------------
 class FrameParams(C.Structure):
     _fields_ = [("reg_voxel", C.c_double), ("icp_max_dist", C.c_double), ("filt_voxel", C.c_double), ("filt_ratio", C.c_double),

@@ -119,6 +119,21 @@ def test_comm_and_order_objects_without_a_gpu(lib):
     assert rc == -1 and b"communicator" in lib.kpx_last_error()
 
 
+def test_host_resources_export_without_a_gpu(lib):
+    """kpx_host_resources is declared, exported and bound with the header's signature; a null pointer is KPX_ERR_INVALID; in a process
+    that never touched a GPU the per-thread owners hold nothing: four zeros (ops.host_resources: the same words by name)"""
+    import torch
+    from kinectpy_amd import _lib, ops
+    assert "kpx_host_resources" in _declared() and hasattr(lib, "kpx_host_resources")
+    assert _lib.SIGNATURES["kpx_host_resources"] == (C.c_int, [C.c_void_p])
+    assert lib.kpx_host_resources(None) == -1 and b"null pointer" in lib.kpx_last_error()
+    out = (C.c_uint64 * 4)(7, 7, 7, 7)
+    assert lib.kpx_host_resources(out) == 0
+    if not torch.cuda.is_available():
+        assert list(out) == [0, 0, 0, 0]
+        assert ops.host_resources() == {"pinned_bytes": 0, "streams": 0, "events": 0, "threads": 0}
+
+
 def test_workspace_queries_are_pure_host_arithmetic(lib):
     assert lib.kpx_median_workspace_bytes(4) >= 4 * 512 * 4
     assert lib.kpx_compact_workspace_bytes(368640, 8) >= 8 * 180 * 4
