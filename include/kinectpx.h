@@ -804,6 +804,59 @@ int kpx_voxelgrid_carve(const uint64_t *keys, const float *colors, int64_t m, co
 int kpx_voxelgrid_included(const void *queries, int32_t queries_f64, int64_t n, const uint64_t *keys, int64_t m, const double *h_origin, double voxel,
                            uint8_t *out, void *stream);
 
+/* ---- image operators and RGB-D odometry ([O3D] geometry.Image filters / pyramids, pipelines.odometry; arithmetic contract AC11,
+ *      DESIGN.md 3 / 5.13) -------------------------------------------------------------------------------------------------------- */
+/* Images are f32 [count][height][width], row-major, caller-owned, on the device; h_intrinsic = (fx, fy, cx, cy), host.
+ * kpx_image_filter: the separable filters of Open3D's Image::Filter: a horizontal pass, then a vertical pass; taps outside the image
+ *     read the border pixel; every output is accumulated in fp64 over the taps in ascending order and rounded to f32 once per pass.
+ *     GAUSSIAN3 (.25 .5 .25), GAUSSIAN5 (.0625 .25 .375 .25 .0625), GAUSSIAN7 (.03125 .109375 .21875 .28125 .21875 .109375 .03125),
+ *     SOBEL3DX ((-1 0 1) along x, (1 2 1) along y), SOBEL3DY (its transpose).  dst must not alias src.  ws: kpx_image_workspace_bytes.
+ * kpx_image_downsample: dst [count][height / 2][width / 2], every pixel the f32 (((a + b) + c) + d) / 4 of its 2 x 2 block (a b the
+ *     upper row).  width, height >= 2.
+ * kpx_odometry_correspondence: AC11's correspondences of one pair of depth images (NaN = no measurement) under h_extrinsic (row-major
+ *     4x4, host): source pixel (u_s, v_s) with finite depth d: q = d (K R K^-1) (u_s, v_s, 1) + K t, z' = q_z > 0, u_t = (int)(q_x / z' +
+ *     0.5), v_t likewise (truncation), inside the target, the target depth d_t there finite, |z' - d_t| <= depth_diff_max; a target
+ *     pixel keeps the source of the smallest (float)z', equal ones the smallest v_s W + u_s.  corres: i32 [width height][4] rows
+ *     (u_s, v_s, u_t, v_t) ascending in (v_t, u_t); d_count: i32, device.
+ * kpx_rgbd_odometry: compute_rgbd_odometry for `pairs` pairs in one chain of launches (pair = grid.y), no host read-back inside.
+ *     raw = 0: depth_* / color_* are f32 [pairs][H W] (depth, intensity); raw = 1: depth_* u16 [pairs][H W], color_* u8 [pairs][H W][3],
+ *     converted as RGBDImage.create_from_color_and_depth does (d = (float)raw / (float)depth_scale, d > (float)depth_trunc -> 0,
+ *     intensity = ((0.299f r + 0.587f g) + 0.114f b) / 255f); mask_* (u8 [pairs][H W] or NULL, raw = 1 only): nonzero = depth 0.
+ *     h_init f64 [pairs][16]; jacobian KPX_ODOMETRY_COLOR / KPX_ODOMETRY_HYBRID; h_iterations i32 [levels], index 0 = the coarsest
+ *     level.  d_results f64 [pairs][KPX_ODOMETRY_RESULT_DOUBLES], device: [0] success (1 / 0), [1] correspondences behind the
+ *     information matrix, [2..17] the 4x4, [18..53] the 6x6 information matrix (both the identity on failure).
+ * kpx_odometry_iteration: ONE Gauss-Newton step of AC11 at one pyramid level, given that level's eight images (source / target
+ *     intensity and depth, the target's Sobel images) and camera.  d_out f64 [KPX_ODOMETRY_ITERATION_DOUBLES], device: [0..20] the
+ *     upper triangle of J^T J by rows, [21..26] J^T r, [27] r.r, [28] the number of correspondences, [29] 1 = solved (0 = singular or
+ *     no correspondence), [30..45] the updated 4x4 (the given one when not solved).
+ * All asynchronous; ws: kpx_odometry_workspace_bytes(pairs, width, height, levels) (1, ..., 1 for the two single-pair calls). */
+#define KPX_IMAGE_GAUSSIAN3 0
+#define KPX_IMAGE_GAUSSIAN5 1
+#define KPX_IMAGE_GAUSSIAN7 2
+#define KPX_IMAGE_SOBEL3DX 3
+#define KPX_IMAGE_SOBEL3DY 4
+#define KPX_ODOMETRY_COLOR 0
+#define KPX_ODOMETRY_HYBRID 1
+#define KPX_ODOMETRY_MAX_LEVELS 8
+#define KPX_ODOMETRY_RESULT_DOUBLES 54
+#define KPX_ODOMETRY_ITERATION_DOUBLES 46
+size_t kpx_image_workspace_bytes(int32_t count, int32_t width, int32_t height);
+int kpx_image_filter(const float *src, float *dst, int32_t count, int32_t width, int32_t height, int32_t filter_type, void *ws, size_t ws_bytes,
+                     void *stream);
+int kpx_image_downsample(const float *src, float *dst, int32_t count, int32_t width, int32_t height, void *stream);
+size_t kpx_odometry_workspace_bytes(int32_t pairs, int32_t width, int32_t height, int32_t levels);
+int kpx_odometry_correspondence(const float *depth_s, const float *depth_t, int32_t width, int32_t height, const double *h_intrinsic,
+                                const double *h_extrinsic, double depth_diff_max, int32_t *corres, int32_t *d_count, void *ws, size_t ws_bytes,
+                                void *stream);
+int kpx_rgbd_odometry(int32_t pairs, const void *depth_s, const void *color_s, const void *depth_t, const void *color_t, int32_t raw,
+                      const uint8_t *mask_s, const uint8_t *mask_t, double depth_scale, double depth_trunc, int32_t width, int32_t height,
+                      const double *h_intrinsic, const double *h_init, int32_t jacobian, int32_t levels, const int32_t *h_iterations,
+                      double depth_diff_max, double depth_min, double depth_max, double *d_results, void *ws, size_t ws_bytes, void *stream);
+int kpx_odometry_iteration(const float *color_s, const float *depth_s, const float *color_t, const float *depth_t, const float *color_dx,
+                           const float *color_dy, const float *depth_dx, const float *depth_dy, int32_t width, int32_t height,
+                           const double *h_intrinsic, const double *h_extrinsic, int32_t jacobian, double depth_diff_max, double *d_out, void *ws,
+                           size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,14 @@ SIGNATURES = {
     "kpx_voxelgrid_carve": (C.c_int, [_vp, _vp, _i64, _vp, _f64, _i32, _i32, _vp, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
                                       _vp, _sz, _vp]),
     "kpx_voxelgrid_included": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
+    "kpx_image_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "kpx_image_filter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "kpx_image_downsample": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "kpx_odometry_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "kpx_odometry_correspondence": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_rgbd_odometry": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _f64, _f64, _f64,
+                                    _vp, _vp, _sz, _vp]),
+    "kpx_odometry_iteration": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@ preprocessing/data.py:46-58 (transform in place, np.asarray(points)), preprocess
 floor_removal.py:50,61-73 (select_by_index with (K,1) arrays, segment_plane, `+`), registration.py:8-13.
 """
 import copy
+import enum
 
 import numpy as np
 import torch
@@ -464,6 +465,15 @@ class KDTreeFlann:
         raise TypeError("KDTreeFlann.search_vector_3d: expected a KDTreeSearchParamKNN, KDTreeSearchParamRadius or KDTreeSearchParamHybrid")
 
 
+class ImageFilterType(enum.Enum):
+    """[O3D] geometry.ImageFilterType; the values are the KPX_IMAGE_* codes of include/kinectpx.h"""
+    Gaussian3 = 0
+    Gaussian5 = 1
+    Gaussian7 = 2
+    Sobel3Dx = 3
+    Sobel3Dy = 4
+
+
 class Image:
     """o3d.geometry.Image stand-in: wraps a host ndarray -- uint8 (H, W, 3) colour, uint16 or float32 (H, W) depth / intensity.
     np.asarray(image) gives the array back."""
@@ -489,6 +499,33 @@ class Image:
 
     def __repr__(self):
         return f"Image of size {self.width}x{self.height}, with {self.num_of_channels} channels."
+
+    def _float_plane(self, who):
+        if self.data.ndim != 2 or self.data.dtype != np.float32 or self.data.size == 0:
+            raise RuntimeError(f"[{who}] Unsupported image format: a float32 single-channel image is needed.")
+        return self.data
+
+    def filter(self, filter_type):
+        """[O3D] Image.filter: Gaussian3 / 5 / 7 and Sobel3Dx / y of a float32 single-channel image (kpx_image_filter: separable,
+        border pixel repeated, accumulated in fp64 and rounded once per pass) -> a new host Image"""
+        return Image(ops.image_filter(self._float_plane("Filter"), ImageFilterType(filter_type).value).cpu().numpy())
+
+    def create_pyramid(self, num_of_levels, with_gaussian_filter=True):
+        """[O3D] Image.create_pyramid: level 0 is the image, level i the 2 x 2 block means of level i - 1 (floor(w / 2) x floor(h / 2)),
+        Gaussian3-filtered first when with_gaussian_filter -> list of host Images"""
+        level = ops._dev(self._float_plane("CreatePyramid"), torch.float32)
+        out = [Image(self.data.copy())]
+        for _ in range(1, int(num_of_levels)):
+            if level.shape[0] < 2 or level.shape[1] < 2:
+                raise RuntimeError("[CreatePyramid] the image is too small for that many levels.")
+            level = ops.image_downsample(ops.image_filter(level, ImageFilterType.Gaussian3.value) if with_gaussian_filter else level)
+            out.append(Image(level.cpu().numpy()))
+        return out
+
+    @staticmethod
+    def filter_pyramid(pyramid, filter_type):
+        """[O3D] Image.filter_pyramid: every level filtered -> list of host Images"""
+        return [Image(level).filter(filter_type) for level in pyramid]
 
 
 class RGBDImage:

@@ -8,9 +8,10 @@ import types
 import numpy as np
 
 from . import ops
-from .geometry import (Image, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
+from .geometry import (Image, ImageFilterType, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
                        OrientedBoundingBox, PointCloud, RGBDImage, Vector2iVector, Vector3dVector, Voxel, VoxelGrid, _off_path)
 from . import integration as _integration
+from . import odometry as _odometry
 from . import pcd_io
 from . import posegraph
 
@@ -445,7 +446,7 @@ class PinholeCameraParameters:
 
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
-                                 Image=Image, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
+                                 Image=Image, ImageFilterType=ImageFilterType, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
 camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic, PinholeCameraParameters=PinholeCameraParameters)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
@@ -454,6 +455,14 @@ pipelines = types.SimpleNamespace(integration=types.SimpleNamespace(
     TSDFVolumeColorType=_integration.TSDFVolumeColorType,
     UniformTSDFVolume=_integration.UniformTSDFVolume,
     ScalableTSDFVolume=_integration.ScalableTSDFVolume,
+), odometry=types.SimpleNamespace(
+    OdometryOption=_odometry.OdometryOption,
+    RGBDOdometryJacobian=_odometry.RGBDOdometryJacobian,
+    RGBDOdometryJacobianFromColorTerm=_odometry.RGBDOdometryJacobianFromColorTerm,
+    RGBDOdometryJacobianFromHybridTerm=_odometry.RGBDOdometryJacobianFromHybridTerm,
+    compute_rgbd_odometry=_odometry.compute_rgbd_odometry,
+    compute_rgbd_odometry_batch=_odometry.compute_rgbd_odometry_batch,
+    compute_correspondence=_odometry.compute_correspondence,
 ), registration=types.SimpleNamespace(
     registration_icp=registration_icp,
     ICPConvergenceCriteria=ICPConvergenceCriteria,

@@ -1304,3 +1304,123 @@ def voxelgrid_included(keys, origin, voxel, queries):
     org = _origin3(origin)
     L.check(lib.kpx_voxelgrid_included(L.ptr(q), int(f64), n, L.ptr(keys), int(keys.shape[0]), L.hptr(org), float(voxel), L.ptr(out), L.stream_ptr()))
     return out
+
+
+# ---- image operators and RGB-D odometry ---------------------------------------------------------------------
+IMAGE_FILTERS = {"gaussian3": 0, "gaussian5": 1, "gaussian7": 2, "sobel3dx": 3, "sobel3dy": 4}          # KPX_IMAGE_* (include/kinectpx.h)
+ODOMETRY_JACOBIANS = {"color": 0, "hybrid": 1}          # KPX_ODOMETRY_COLOR / KPX_ODOMETRY_HYBRID
+ODOMETRY_MAX_LEVELS = 8
+ODOMETRY_RESULT_DOUBLES = 54
+ODOMETRY_ITERATION_DOUBLES = 46
+
+
+def _images(img):
+    """float32 (H, W) or (count, H, W) -> device tensor (count, H, W)"""
+    t = _dev(img, torch.float32)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise L.KinectPxError("image operators take float32 (H, W) or (count, H, W) images")
+    return t.contiguous()
+
+
+def image_filter(img, filter_type):
+    """[O3D] Image.filter for one float32 (H, W) image or a (count, H, W) stack -> device tensor of the same shape (kpx_image_filter:
+    separable, border pixel repeated, fp64 accumulation, one rounding per pass).  filter_type: a name of IMAGE_FILTERS or its code."""
+    lib = L.load()
+    src = _images(img)
+    kind = IMAGE_FILTERS[filter_type] if isinstance(filter_type, str) else int(filter_type)
+    cnt, h, w = src.shape
+    dst = torch.empty_like(src)
+    ws, wsz = L.workspace(lib.kpx_image_workspace_bytes(cnt, w, h))
+    L.check(lib.kpx_image_filter(L.ptr(src), L.ptr(dst), cnt, w, h, kind, ws, wsz, L.stream_ptr()))
+    return dst if np.ndim(img) == 3 else dst[0]
+
+
+def image_downsample(img):
+    """2 x 2 block means (float32 (((a + b) + c) + d) / 4) of a float32 (H, W) image or (count, H, W) stack -> (.., H // 2, W // 2)"""
+    lib = L.load()
+    src = _images(img)
+    cnt, h, w = src.shape
+    dst = torch.empty((cnt, h // 2, w // 2), dtype=torch.float32, device=src.device)
+    L.check(lib.kpx_image_downsample(L.ptr(src), L.ptr(dst), cnt, w, h, L.stream_ptr()))
+    return dst if np.ndim(img) == 3 else dst[0]
+
+
+def _intrinsic4(intrinsic):
+    """(fx, fy, cx, cy) or a 3x3 camera matrix without skew -> float64[4]"""
+    K = np.asarray(intrinsic, dtype=np.float64)
+    if K.shape == (3, 3):
+        if K[0, 1] != 0.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0 or K[2, 2] != 1.0:
+            raise L.KinectPxError("odometry: the intrinsic matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew)")
+        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    return np.ascontiguousarray(K.reshape(4))
+
+
+def odometry_correspondence(depth_s, depth_t, intrinsic, extrinsic, depth_diff_max):
+    """AC11's correspondences of two float32 (H, W) depth images (NaN = no measurement) -> int32 (n, 4) device tensor of
+    (u_s, v_s, u_t, v_t), ascending in (v_t, u_t).  One host read (the count)."""
+    lib = L.load()
+    ds, dt = _dev(depth_s, torch.float32), _dev(depth_t, torch.float32)
+    if ds.dim() != 2 or ds.shape != dt.shape:
+        raise L.KinectPxError("odometry_correspondence: two float32 (H, W) depth images of one size")
+    h, w = ds.shape
+    out = torch.empty((h * w, 4), dtype=torch.int32, device=ds.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=ds.device)
+    K, E = _intrinsic4(intrinsic), _T(extrinsic)
+    ws, wsz = L.workspace(lib.kpx_odometry_workspace_bytes(1, w, h, 1))
+    L.check(lib.kpx_odometry_correspondence(L.ptr(ds), L.ptr(dt), w, h, L.hptr(K), L.hptr(E), float(depth_diff_max), L.ptr(out), L.ptr(cnt), ws, wsz,
+                                            L.stream_ptr()))
+    return out[:_count(cnt)[0]]
+
+
+def odometry_iteration(color_s, depth_s, color_t, depth_t, color_dx, color_dy, depth_dx, depth_dy, intrinsic, extrinsic, jacobian, depth_diff_max):
+    """ONE Gauss-Newton step of the odometry at one pyramid level from its eight float32 (H, W) images and camera ->
+    dict(JTJ (6, 6), JTr (6,), r2, count, solved, transformation (4, 4))"""
+    lib = L.load()
+    imgs = [_dev(x, torch.float32) for x in (color_s, depth_s, color_t, depth_t, color_dx, color_dy, depth_dx, depth_dy)]
+    h, w = imgs[0].shape
+    if any(x.dim() != 2 or x.shape != (h, w) for x in imgs):
+        raise L.KinectPxError("odometry_iteration: eight float32 (H, W) images of one size")
+    out = torch.empty(ODOMETRY_ITERATION_DOUBLES, dtype=torch.float64, device=imgs[0].device)
+    K, E = _intrinsic4(intrinsic), _T(extrinsic)
+    ws, wsz = L.workspace(lib.kpx_odometry_workspace_bytes(1, w, h, 1))
+    L.check(lib.kpx_odometry_iteration(*[L.ptr(x) for x in imgs], w, h, L.hptr(K), L.hptr(E), ODOMETRY_JACOBIANS[jacobian], float(depth_diff_max),
+                                       L.ptr(out), ws, wsz, L.stream_ptr()))
+    r = out.cpu().numpy()
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = r[:21]
+    A = A + np.triu(A, 1).T
+    return {"JTJ": A, "JTr": r[21:27].copy(), "r2": float(r[27]), "sums": r[:28].copy(), "count": int(r[28]), "solved": bool(r[29]),
+            "transformation": r[30:46].reshape(4, 4).copy()}
+
+
+def rgbd_odometry(depth_s, color_s, depth_t, color_t, width, height, intrinsic, inits=None, jacobian="hybrid", iterations=(20, 10, 5),
+                  depth_diff_max=0.03, depth_min=0.0, depth_max=4.0, raw=False, depth_scale=1000.0, depth_trunc=3.0, mask_s=None, mask_t=None):
+    """compute_rgbd_odometry for P pairs in one chain of launches (kpx_rgbd_odometry), one host read at the end.  raw False: float32
+    (P, H W) depth and intensity; raw True: uint16 depth and uint8 (P, H W, 3) colour, converted in the kernel as
+    RGBDImage.create_from_color_and_depth does, and optional uint8 (P, H W) masks (nonzero = the pixel's depth is dropped).
+    -> success bool (P,), transformation (P, 4, 4), information (P, 6, 6), correspondence counts int64 (P,)"""
+    lib = L.load()
+    n_px = int(width) * int(height)
+    dt_, ct_ = (torch.uint16, torch.uint8) if raw else (torch.float32, torch.float32)
+    ds, dt = _dev(depth_s, dt_).reshape(-1, n_px), _dev(depth_t, dt_).reshape(-1, n_px)
+    P = ds.shape[0]
+    cs, ct = _dev(color_s, ct_).reshape(P, -1), _dev(color_t, ct_).reshape(P, -1)
+    ch = 3 if raw else 1
+    if dt.shape[0] != P or cs.shape[1] != ch * n_px or ct.shape[1] != ch * n_px:
+        raise L.KinectPxError("rgbd_odometry: frame sizes do not match width x height")
+    ms = _dev(mask_s, torch.uint8).reshape(P, n_px) if mask_s is not None else None
+    mt = _dev(mask_t, torch.uint8).reshape(P, n_px) if mask_t is not None else None
+    if (ms is not None or mt is not None) and not raw:
+        raise L.KinectPxError("rgbd_odometry: masks go with raw frames")
+    it = np.ascontiguousarray(np.asarray(iterations, dtype=np.int32).reshape(-1))
+    T0 = np.ascontiguousarray(np.broadcast_to(np.eye(4) if inits is None else np.asarray(inits, dtype=np.float64).reshape(-1, 4, 4), (P, 4, 4)))
+    K = _intrinsic4(intrinsic)
+    res = torch.empty((P, ODOMETRY_RESULT_DOUBLES), dtype=torch.float64, device=ds.device)
+    ws, wsz = L.workspace(lib.kpx_odometry_workspace_bytes(P, int(width), int(height), len(it)))
+    L.check(lib.kpx_rgbd_odometry(P, L.ptr(ds), L.ptr(cs), L.ptr(dt), L.ptr(ct), int(raw), L.ptr(ms), L.ptr(mt), float(depth_scale), float(depth_trunc),
+                                  int(width), int(height), L.hptr(K), L.hptr(T0), ODOMETRY_JACOBIANS[jacobian], len(it), L.hptr(it),
+                                  float(depth_diff_max), float(depth_min), float(depth_max), L.ptr(res), ws, wsz, L.stream_ptr()))
+    r = res.cpu().numpy()
+    return r[:, 0] != 0.0, r[:, 2:18].reshape(P, 4, 4).copy(), r[:, 18:54].reshape(P, 6, 6).copy(), r[:, 1].astype(np.int64)

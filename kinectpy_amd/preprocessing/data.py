@@ -21,7 +21,8 @@ from ..pcd_io import write_point_cloud
 from ..utils.io import load_color, load_depth, rgbd_to_pointcloud
 from ..utils.processing import sort_filenames_by_timestamp
 from .filtering import Filtering, filter_outliers
-from .registration import execute_global_registration, execute_multiway_registration, execute_point_to_plane_registration
+from .registration import (estimate_sensor_drift, execute_global_registration, execute_multiway_registration,
+                           execute_point_to_plane_registration)
 
 
 def transform_filtered_image_to_pointcloud(filtered_img, depth_img) -> PointCloud:
@@ -65,14 +66,23 @@ def fuse_and_filter(filtered_pcds: Sequence[PointCloud], registration_transforma
 class DataProcessor:
     def __init__(self, output_dirs: List[str], mask_rcnn_pb_file: Optional[str] = None, mask_rcnn_pbtxt_file: Optional[str] = None, *,
                  mask_fn=None, initial_transformations: Optional[List[np.ndarray]] = None, seed: Optional[int] = None,
-                 run: bool = True, multiway: bool = False, robust_kernel=None, keypoints=None, global_method: str = "ransac"):
+                 run: bool = True, multiway: bool = False, robust_kernel=None, keypoints=None, global_method: str = "ransac",
+                 drift_check_every: Optional[int] = None, drift_intrinsic=None, drift_option=None):
         """reference signature (data.py:15-27) + keyword-only extras: `mask_fn` (the person mask, instead of Mask R-CNN),
         `initial_transformations` (skip the global registration: data.py:156), `seed` (the reference's RANSAC is unseeded),
         `run=False` (build the object, call find / process yourself), `multiway=True` (calibrate with execute_multiway_registration:
         every pair of devices registered, one pose graph solved -- instead of the reference's star of sub -> master ICPs),
         `robust_kernel` (a loss of o3d.pipelines.registration, e.g. TukeyLoss(k), for every pairwise ICP of the calibration),
         `keypoints` (None, True or a dict of ISS parameters: execute_global_registration matches ISS keypoints only),
-        `global_method` ("ransac", the reference's 15 RANSAC runs per sub device, or "fgr", one Fast Global Registration)."""
+        `global_method` ("ransac", the reference's 15 RANSAC runs per sub device, or "fgr", one Fast Global Registration),
+        `drift_check_every` (None: nothing; n: every n-th frame set, estimate_sensor_drift of every device against its frame 0 with
+        the pinhole `drift_intrinsic` and `drift_option`; the person mask of `mask_fn` is left out; results are logged and collected in
+        `drift_log` as (file_idx, per-device list))."""
+        if drift_check_every is not None and (int(drift_check_every) < 1 or drift_intrinsic is None):
+            raise RuntimeError("DataProcessor: drift_check_every must be a positive frame count and needs drift_intrinsic (a PinholeCameraIntrinsic)")
+        self.drift_check_every, self.drift_intrinsic, self.drift_option = drift_check_every, drift_intrinsic, drift_option
+        self.drift_log = []
+        self._drift_ref = None
         self.device_filenames_df = self._create_device_filenames_df(output_dirs)
         self.number_of_devices = len(self.device_filenames_df.columns)
         self.registration_transformations: List[np.ndarray] = []
@@ -93,6 +103,8 @@ class DataProcessor:
             if (file_idx + 1) % 50 == 0:
                 print(f'{file_idx + 1} point clouds have been saved')
             registered_pcd = fuse_and_filter(self._filter_pointclouds_and_save(file_idx), self.registration_transformations)
+            if self.drift_check_every and file_idx % int(self.drift_check_every) == 0:
+                self._drift_check(file_idx)
             dst = os.path.join(self.device_filenames_df.columns[0], 'filtered_and_registered_pointclouds',
                                self.device_filenames_df.iloc[file_idx, 0])
             write_point_cloud(dst + '.pcd', registered_pcd)                       # data.py:64-69
@@ -112,6 +124,7 @@ class DataProcessor:
         self.keypoints = keypoints
         self.global_method = global_method
         self.segmentation = None
+        self.drift_check_every, self.drift_intrinsic, self.drift_option, self.drift_log, self._drift_ref = None, None, None, [], None
         return self
 
     # ---- data.py:73-84
@@ -138,6 +151,30 @@ class DataProcessor:
             color, depth = self._device_frame(device_idx, file_idx)
             clouds.append(transform_filtered_image_to_pointcloud(self.segmentation.apply_segmentation(color), depth))
         return clouds
+
+    def _drift_frames(self, file_idx):
+        """the raw frames of every device and, with a mask_fn, the person masks (nonzero = person)"""
+        frames = [self._device_frame(d, file_idx) for d in range(self.number_of_devices)]
+        colors = np.stack([np.asarray(c, dtype=np.uint8).reshape(-1, 3) for c, _ in frames])
+        depths = np.stack([np.asarray(z).reshape(-1, 3) for _, z in frames])
+        mask_fn = self._mask_args[2]
+        masks = np.stack([np.asarray(mask_fn(c)).astype(bool).reshape(-1) for c, _ in frames]) if mask_fn is not None else None
+        return depths, colors, masks
+
+    def _drift_check(self, file_idx):
+        """estimate_sensor_drift of every device between frame set 0 and frame set file_idx"""
+        if self._drift_ref is None:
+            self._drift_ref = self._drift_frames(0)
+        if file_idx == 0:
+            return None
+        d0, c0, m0 = self._drift_ref
+        d1, c1, m1 = self._drift_frames(file_idx)
+        report = estimate_sensor_drift(d0, c0, d1, c1, self.drift_intrinsic, m0, m1, self.drift_option)
+        self.drift_log.append((file_idx, report))
+        for dev, r in enumerate(report):
+            logging.info('drift check, frame %d, device %d: %s, %.3f deg, %.1f data units', file_idx, dev,
+                         'ok' if r["success"] else 'odometry failed', r["rotation_deg"], r["translation"])
+        return report
 
     # ---- data.py:127-161
     def _find_registration_transforms(self):

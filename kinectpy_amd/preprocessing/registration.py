@@ -191,3 +191,41 @@ def execute_multiway_registration(pcds, voxel_size: int = 35, initial_transforma
                             reg.GlobalOptimizationOption(threshold, edge_prune_threshold, preference_loop_closure, 0))
     out = [nd.pose.copy() for nd in pose_graph.nodes[1:]]
     return (out, pose_graph) if return_pose_graph else out
+
+
+def estimate_sensor_drift(depths_ref, colors_ref, depths_now, colors_now, intrinsic, masks_ref=None, masks_now=None, option=None, jacobian=None,
+                          depth_scale=1.0, depth_trunc=0.0):
+    """Has a sensor moved since the rig was calibrated?  The rig is calibrated once, on its first frame set, and those transforms are
+    applied to every later frame; a bumped tripod goes unnoticed.  Most of every sensor's own image is static room, so the rigid motion
+    between a sensor's reference frame and its current frame IS the sensor's drift: RGB-D odometry of each sensor against itself, all
+    S sensors in one compute_rgbd_odometry_batch call.
+
+    depths_*: the S sensors' depth as the pipeline holds it -- uint16 (S, n_px) / (S, H, W), or the int16 XYZ triples (S, n_px, 3)
+    whose z column is taken; colors_*: uint8 (S, n_px, 3); intrinsic: a PinholeCameraIntrinsic; masks_*: (S, n_px), nonzero = leave the
+    pixel out (the person, who does move); option: an OdometryOption in the data's units (default: millimetres, (30, 0, 4000));
+    depth_trunc 0: no truncation.
+    -> one dict per sensor: success, transformation (4, 4, reference camera -> current camera), information (6, 6), rotation_deg (the
+    angle of R) and translation (the norm of t, data units); a failed sensor reports the identities and zeros."""
+    odo = o3d.pipelines.odometry
+    option = odo.OdometryOption(depth_diff_max=30.0, depth_min=0.0, depth_max=4000.0) if option is None else option
+
+    def z_of(d):
+        if hasattr(d, "cpu"):
+            d = d.cpu().numpy()
+        d = np.asarray(d)
+        if d.dtype == np.int16 and d.ndim == 3 and d.shape[2] == 3:
+            d = np.clip(d[:, :, 2], 0, None)
+        return np.ascontiguousarray(d).astype(np.uint16).reshape(d.shape[0], -1)
+
+    def mask_of(m):
+        return None if m is None else np.ascontiguousarray(np.asarray(m.cpu().numpy() if hasattr(m, "cpu") else m) != 0).astype(np.uint8)
+
+    ok, T, info = odo.compute_rgbd_odometry_batch(z_of(depths_ref), colors_ref, z_of(depths_now), colors_now, intrinsic, None, jacobian, option,
+                                                  depth_scale=depth_scale, depth_trunc=depth_trunc if depth_trunc > 0 else np.inf,
+                                                  masks_s=mask_of(masks_ref), masks_t=mask_of(masks_now))
+    out = []
+    for i in range(len(ok)):
+        c = np.clip((np.trace(T[i, :3, :3]) - 1.0) / 2.0, -1.0, 1.0)
+        out.append({"success": bool(ok[i]), "transformation": T[i], "information": info[i], "rotation_deg": float(np.degrees(np.arccos(c))),
+                    "translation": float(np.linalg.norm(T[i, :3, 3]))})
+    return out

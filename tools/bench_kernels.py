@@ -53,12 +53,15 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
+    ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.tsdf:
         return tsdf_rows(dev, a.quick)
     if a.voxelgrid:
         return voxelgrid_rows(dev, a.quick)
+    if a.odometry:
+        return odometry_rows(dev, a.quick)
     F = 64 if a.quick else 256
     xy = synth.xy_table()
     base_d, person = synth.render_depth(xy=xy, return_person=True)
@@ -309,6 +312,7 @@ def main():
            **sweep(ops.prof_end()))
     tsdf_rows(dev, a.quick)
     voxelgrid_rows(dev, a.quick)
+    odometry_rows(dev, a.quick)
 
 
 def tsdf_rows(dev, quick):
@@ -414,6 +418,88 @@ def voxelgrid_rows(dev, quick):
     ms, (out, kept) = timed(lambda: remove_free_space_points(pc, depth[0], None, truth, 10.0))
     report("remove_free_space_points (fused ring cloud, 10 mm, 4 frames; grid + carve + inclusion + select, host frames uploaded)", ms, points=n,
            kept=int(kept.shape[0]))
+
+
+def odometry_launches(iterations):
+    """dispatches of one kpx_rgbd_odometry call: 2 clears + 1 pose copy, conversion + 2 Gaussian passes, correspondence + sums + scaling
+    for the intensity normalisation, per coarser level 2 Gaussian passes + 1 block mean, per level 2 Sobel passes, 2 per iteration,
+    2 for the information matrix"""
+    levels = len(iterations)
+    return 3 + 3 + 3 + 3 * (levels - 1) + 2 * levels + 2 * int(sum(iterations)) + 2
+
+
+def odometry_rows(dev, quick):
+    """RGB-D odometry of full-size 640 x 576 frames of the empty room seen from camera 0 of a ring of four and from that
+    pose moved by 1.5 degrees / 40 mm, raw uint16 / uint8 frames resident on the device, millimetre option (30, 0, 6000), hybrid term,
+    default iteration list: one pair, and four pairs in one batch call against four single calls.  `ms` is the device time between
+    events around the call (the chain's launches and the gaps between them), wall_ms the host time of the call including its one
+    read-back; both the median of the repetitions, with their range."""
+    import time
+    iterations = (20, 10, 5)
+    xy = synth.xy_table()
+    A = synth.camera_pose(0, 4)
+    a_, ax = np.deg2rad(1.5), np.array([0.3, 1.0, 0.2]) / np.linalg.norm([0.3, 1.0, 0.2])
+    Kx = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    M = np.eye(4)
+    M[:3, :3] = np.eye(3) + np.sin(a_) * Kx + (1 - np.cos(a_)) * Kx @ Kx
+    M[:3, 3] = (25.0, -13.0, 29.0)
+    frames = []
+    for E in (A, A @ M):
+        d = synth.render_depth(E=E, xy=xy, noise=0, drop=0, person_shift=(0.0, 1e6, 0.0))
+        z = d.astype(np.float64)
+        p = np.stack([np.nan_to_num(xy[:, 0]) * z, np.nan_to_num(xy[:, 1]) * z, z], 1) @ E[:3, :3].T + E[:3, 3]
+        f = 0.5 + 0.22 * np.sin(p[:, 0] / 310.0) * np.cos(p[:, 1] / 270.0) + 0.2 * np.cos(p[:, 2] / 350.0 + p[:, 0] / 420.0)
+        rgb = np.repeat(np.clip(np.rint(255.0 * f), 0, 255).astype(np.uint8)[:, None], 3, 1)
+        rgb[d == 0] = 0
+        frames.append((torch.as_tensor(d).to(dev), torch.as_tensor(rgb).to(dev)))
+    K = (synth.FX, synth.FY, synth.CX, synth.CY)
+    truth = np.linalg.inv(A @ M) @ A
+
+    def call(P):
+        ds, cs = frames[0][0].expand(P, -1).contiguous(), frames[0][1].expand(P, -1, -1).contiguous()
+        dt, ct = frames[1][0].expand(P, -1).contiguous(), frames[1][1].expand(P, -1, -1).contiguous()
+        return lambda: ops.rgbd_odometry(ds, cs, dt, ct, synth.W, synth.H, K, None, "hybrid", iterations, 30.0, 0.0, 6000.0, raw=True,
+                                         depth_scale=1.0, depth_trunc=6000.0)
+
+    def measure(fn, reps):
+        for _ in range(3):
+            out = fn()
+        torch.cuda.synchronize()
+        ev, wall = [], []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ev.append(e0.elapsed_time(e1))
+        stat = lambda v: (float(np.median(v)), float(np.min(v)), float(np.max(v)))
+        return stat(ev), stat(wall), out
+
+    reps = 10 if quick else 30
+    n_launch = odometry_launches(iterations)
+    one, four = call(1), call(4)
+    (ms, lo, hi), (wms, wlo, whi), (ok, T, _, cnt) = measure(one, reps)
+    D = T[0] @ np.linalg.inv(truth)
+    report("compute_rgbd_odometry 640x576 hybrid [20, 10, 5] (one pair, raw frames on the device)", ms, ms_range=[round(lo, 4), round(hi, 4)],
+           wall_ms=round(wms, 4), wall_ms_range=[round(wlo, 4), round(whi, 4)], launches=n_launch, us_per_launch=round(1e3 * ms / n_launch, 3),
+           success=bool(ok[0]), information_correspondences=int(cnt[0]),
+           error_deg=round(float(np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))), 4), error_mm=round(float(np.linalg.norm(D[:3, 3])), 3))
+    (bms, blo, bhi), (bw, bwlo, bwhi), (okb, Tb, _, _) = measure(four, reps)
+
+    def singles():
+        for _ in range(4):
+            out = one()
+        return out
+    (sms, slo, shi), (sw, swlo, swhi), _ = measure(singles, reps)
+    assert np.array_equal(Tb[0], T[0]) and np.array_equal(Tb[3], T[0])
+    report("compute_rgbd_odometry_batch 4 x 640x576 hybrid [20, 10, 5] (one call)", bms, ms_range=[round(blo, 4), round(bhi, 4)], wall_ms=round(bw, 4),
+           wall_ms_range=[round(bwlo, 4), round(bwhi, 4)], launches=n_launch, us_per_launch=round(1e3 * bms / n_launch, 3))
+    report("compute_rgbd_odometry 4 calls of one pair (same session)", sms, ms_range=[round(slo, 4), round(shi, 4)], wall_ms=round(sw, 4),
+           wall_ms_range=[round(swlo, 4), round(swhi, 4)], launches=4 * n_launch, single_over_batch=round(sms / bms, 3),
+           single_over_batch_wall=round(sw / bw, 3))
 
 
 if __name__ == "__main__":
