@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from kinectpy_amd.utils import synth
+from odometry_scenes import write_device as _write_device          # shared with the drift check's directory
 
 pytestmark = pytest.mark.gpu
 KAT = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ref_kat.json")))
@@ -1846,15 +1847,6 @@ def test_fused_voxel_membership_is_the_float64_path(ops, oracle):
 
 
 # ------------------------------------------------------------------ the reference-shaped drivers (files in, files out)
-def _write_device(root, stamps, depth_xyz, rgbs):
-    from PIL import Image
-    os.makedirs(os.path.join(root, "color")); os.makedirs(os.path.join(root, "depths"))
-    os.makedirs(os.path.join(root, "filtered_and_registered_pointclouds"))
-    for ts, xyz, rgb in zip(stamps, depth_xyz, rgbs):
-        xyz.astype(np.int16).tofile(os.path.join(root, "depths", f"{ts}_depth.dat"))
-        Image.fromarray(rgb.reshape(synth.H, synth.W, 3)).save(os.path.join(root, "color", f"{ts}_rgb.png"))
-
-
 def test_data_processor_reference_constructor(tmp_path, oracle):
     """DataProcessor(output_dirs, pb, pbtxt) as the reference runs it (preprocessing/data.py:15-69): directory walk in
     timestamp order, registration on frame 0 saved as transformation_master_sub_1.npy, per frame mask + gate + transform +
