@@ -763,6 +763,38 @@ int kpx_tsdf_extract_count(const float *volume, int32_t resolution, int32_t mode
 int kpx_tsdf_extract_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
                           int32_t mode, int64_t total, float *pts, float *nrm, float *col, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- triangle meshes ([O3D] UniformTSDFVolume.extract_triangle_mesh, geometry.TriangleMesh; arithmetic contract AC12, DESIGN.md 3 /
+ *      5.11) ------------------------------------------------------------------------------------------------------------------------ */
+/* kpx_tsdf_mesh_count / kpx_tsdf_mesh_fill: the two phases of marching cubes over a volume laid out as above.  A cube (x, y, z), every
+ *     index below res - 1, is active when its eight corner weights are != 0; bit i of its code is tsdf_i < 0 (corner and edge numbering:
+ *     kinectpy_amd/csrc/kpx_mctables.h); codes 0 and 255 emit nothing; there is no +-0.98 test.  One vertex per edge (lower voxel v, axis
+ *     a) that some active cube contains and whose ends differ in sign: centre of v, moved along a by (|f_v| vl) / (|f_v| + |f_v+a|), plus
+ *     h_origin; colour (|f_v+a| (c_v / 255) + |f_v| (c_v+a / 255)) / (|f_v| + |f_v+a|) per channel; all fp64 without fma, rounded to
+ *     f32 at the store.  Vertices ascend in (linear index of v, a) -- Open3D numbers them by first encounter; positions and the triangle
+ *     list modulo that renumbering are Open3D's.  Triangles: cubes in ascending linear index, the table row in order, every triple (t0,
+ *     t1, t2) emitted as (vertex[t0], vertex[t2], vertex[t1]).  count leaves its records in ws and the two totals at d_counts (i64 [2],
+ *     device: vertices, triangles).  The caller reads them, allocates out_vertices f32 [n_vertices][3], out_colors (optional, needs
+ *     `color`) and out_triangles i32 [n_triangles][3] and calls fill with the SAME, untouched ws and an unchanged volume; fill writes
+ *     nothing at or beyond the two counts and returns KPX_ERR_RANGE when either exceeds 2^31 - 1.  Asynchronous.
+ *     ws: kpx_tsdf_mesh_workspace_bytes(resolution) bytes (0 for a resolution outside the range): 1.5 bytes per voxel.
+ * kpx_mesh_normals: triangle normal n = (v1 - v0) x (v2 - v0) in fp64 from the f32 vertices, each component a b - c d; vertex normal =
+ *     the sum from 0 of the UNNORMALISED normals of the incident triangles in ascending triangle index, once per corner occurrence.
+ *     normalized: n / sqrt((nx^2 + ny^2) + nz^2), the zero vector -> (0, 0, 1).  Stored as f32.  Either output may be NULL.  Every
+ *     triangle index must lie in [0, n_vertices): the caller checks (a triangle that violates it reads nothing and counts as n = 0).
+ *     At most 2^31 - 1 vertices and triangle corners (KPX_ERR_RANGE).  ws: kpx_mesh_normals_workspace_bytes (0 for counts out of range),
+ *     needed for vertex normals only.  Asynchronous.
+ * kpx_mesh_surface_area: d_area (f64, device) = the sum over the triangles, in ascending order, of sqrt(...) of that n times 0.5.
+ *     The additions are one chain by contract (one block; about 3 ns per triangle).  Asynchronous. */
+size_t kpx_tsdf_mesh_workspace_bytes(int32_t resolution);
+int kpx_tsdf_mesh_count(const float *volume, int32_t resolution, int64_t *d_counts, void *ws, size_t ws_bytes, void *stream);
+int kpx_tsdf_mesh_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
+                       int64_t n_vertices, int64_t n_triangles, float *out_vertices, float *out_colors, int32_t *out_triangles, void *ws,
+                       size_t ws_bytes, void *stream);
+size_t kpx_mesh_normals_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_normals(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int32_t normalized,
+                     float *out_triangle_normals, float *out_vertex_normals, void *ws, size_t ws_bytes, void *stream);
+int kpx_mesh_surface_area(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_area, void *stream);
+
 /* ---- occupancy grids ([O3D] geometry.VoxelGrid; arithmetic contract AC10) ---------------------------------------- */
 /* A grid is caller-owned: keys u64 [M], strictly ascending, key = gx << 42 | gy << 21 | gz with every index in [0, 2^21), and colors
  * f32 [M][3]; voxel g covers h_origin + g voxel .. h_origin + (g + 1) voxel.  All decisions are fp64.

@@ -303,8 +303,8 @@ static __global__ __launch_bounds__(1024) void compact_scan2_kernel(int32_t *cou
 }
 
 // exclusive scan of m 64-bit counts in place, offsets[m] = total: one block, a contiguous slice per thread (the radius search's
-// per-query counts, the TSDF extraction's per-block counts)
-static __global__ __launch_bounds__(1024) void scan_i64_kernel(int64_t *__restrict__ offsets, int64_t m)
+// per-query counts, the TSDF extractions' per-block counts)
+static __device__ __forceinline__ void scan_i64_body(int64_t *__restrict__ offsets, int64_t m)
 {
     __shared__ int64_t sh[1024];
     const int64_t per = (m + 1023) / 1024;
@@ -322,6 +322,12 @@ static __global__ __launch_bounds__(1024) void scan_i64_kernel(int64_t *__restri
     __syncthreads();
     int64_t run = sh[threadIdx.x];
     for (int64_t i = b; i < e; ++i) { const int64_t c = offsets[i]; offsets[i] = run; run += c; }
+}
+static __global__ __launch_bounds__(1024) void scan_i64_kernel(int64_t *__restrict__ offsets, int64_t m) { scan_i64_body(offsets, m); }
+// two arrays of the same length side by side: block 0 scans a, block 1 scans b (the mesh extraction's vertex and triangle counts)
+static __global__ __launch_bounds__(1024) void scan2_i64_kernel(int64_t *__restrict__ a, int64_t *__restrict__ b, int64_t m)
+{
+    scan_i64_body(blockIdx.x ? b : a, m);
 }
 
 template <class Pred, class Emit>

@@ -1,0 +1,494 @@
+// kpx_tsdfmesh.hip -- triangle meshes: marching cubes over a uniform TSDF volume ([O3D] UniformTSDFVolume.extract_triangle_mesh;
+// arithmetic contract AC12) and the normals and surface area of any triangle mesh.
+//
+// Extraction keeps the shape of the point-cloud extraction of kpx_tsdf.hip: count, one host read, fill; no atomics, every output
+// slot has one owner.  Workspace, carried from count to fill:
+//   codes   u8  [res^3]        the cube code at the cube's corner 0 (bit i = corner i negative), 0 = inactive / no cube there
+//   groups  32B [res^3 / 64]   per 64 consecutive voxels: three ballots (bit l of m[a] = edge (voxel 64 g + l, axis a) carries a
+//                              vertex) and the group's vertex and triangle offsets inside its chunk of 512 voxels
+//   voff, toff  i64 [chunks+1] exclusive scans of the chunks' vertex and triangle counts
+// The rank of edge (v, a) -- its vertex index -- is voff[chunk] + group.vrel + popcounts of the three ballots below v's lane + the
+// set bits of the lower axes at the lane: the order of extract_point_cloud, ascending (linear index, axis).
+#include "kpx_morton.h"
+#include "kpx_mctables.h"
+
+#include <math.h>
+
+namespace kpx {
+namespace {
+
+// ---- tables ----------------------------------------------------------------------------------------------------------------
+struct McTables {
+    signed char tri[256][16];
+    unsigned char ntri[256];
+    signed char shift[12][4];       // edge -> (dx, dy, dz, axis) of its lower voxel
+};
+constexpr McTables mc_make_tables()
+{
+    McTables t{};
+    for (int c = 0; c < 256; ++c) {
+        int n = 0;
+        for (int i = 0; i < 16; ++i) {
+            t.tri[c][i] = kMcTriTable[c][i];
+            if (kMcTriTable[c][i] >= 0 && n == i) ++n;
+        }
+        t.ntri[c] = (unsigned char)(n / 3);
+    }
+    constexpr signed char sh[12][4] = { { 0, 0, 0, 0 }, { 1, 0, 0, 1 }, { 0, 1, 0, 0 }, { 0, 0, 0, 1 }, { 0, 0, 1, 0 }, { 1, 0, 1, 1 },
+                                        { 0, 1, 1, 0 }, { 0, 0, 1, 1 }, { 0, 0, 0, 2 }, { 1, 0, 0, 2 }, { 1, 1, 0, 2 }, { 0, 1, 0, 2 } };
+    for (int e = 0; e < 12; ++e)
+        for (int k = 0; k < 4; ++k) t.shift[e][k] = sh[e][k];
+    return t;
+}
+__constant__ McTables c_mc = mc_make_tables();
+
+// corner number of the cube corner at (dx, dy, dz): 0..3 run round the bottom face, 4..7 round the top
+__device__ __forceinline__ constexpr int mc_corner(int dx, int dy, int dz) { return dz * 4 + (dy ? 3 - dx : dx); }
+
+struct McGroup {
+    unsigned long long m[3];
+    uint32_t vrel, trel;
+};
+static_assert(sizeof(McGroup) == 32, "one group record is 32 bytes");
+
+constexpr int kMcChunk = KPX_TSDF_COUNT_BLOCK;        // consecutive voxels a wave counts and fills
+constexpr int kMcRounds = kMcChunk / 64;
+constexpr int kMcWaves = 4;
+
+__device__ __forceinline__ void mc_split(int64_t lin, int res, int &x, int &y, int &z)
+{
+    const uint32_t l = (uint32_t)lin, r = (uint32_t)res;
+    const uint32_t t = l / r;
+    z = (int)(l - t * r);
+    x = (int)(t / r);
+    y = (int)(t - (uint32_t)x * r);
+}
+
+// ---- sweep 1: one code byte per voxel ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mc_code_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, uint8_t *__restrict__ codes)
+{
+    const int64_t lin = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (lin >= nvox) return;
+    int x, y, z;
+    mc_split(lin, res, x, y, z);
+    unsigned code = 0u;
+    if (x < res - 1 && y < res - 1 && z < res - 1) {
+        const int64_t sx = (int64_t)res * res, sy = res;
+        bool active = true;
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dz = 0; dz < 2; ++dz) {
+                    const float2 v = vol[lin + dx * sx + dy * sy + dz];
+                    active = active && v.y != 0.0f;
+                    if (v.x < 0.0f) code |= 1u << mc_corner(dx, dy, dz);
+                }
+        if (!active) code = 0u;
+    }
+    codes[lin] = (uint8_t)code;
+}
+
+// bit a: edge (voxel, axis a) carries a vertex: one of the up to four cubes round it has the edge's two corners on different sides
+// (an inactive or absent cube has code 0: no difference).  *own = the code of the cube whose corner 0 the voxel is.
+__device__ __forceinline__ unsigned mc_edge_flags(const uint8_t *__restrict__ codes, int res, int64_t lin, int x, int y, int z, unsigned *own)
+{
+    const int64_t sx = (int64_t)res * res, sy = res;
+    unsigned m = 0u;
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dz = 0; dz < 2; ++dz) {
+                if (dx + dy + dz == 3) continue;                     // that cube holds none of the voxel's three edges
+                if (x - dx < 0 || y - dy < 0 || z - dz < 0) continue;
+                const unsigned c = codes[lin - dx * sx - dy * sy - dz];
+                if (dx + dy + dz == 0) *own = c;
+                const unsigned at = (c >> mc_corner(dx, dy, dz)) & 1u;
+                if (dx == 0 && (((c >> mc_corner(1, dy, dz)) & 1u) != at)) m |= 1u;
+                if (dy == 0 && (((c >> mc_corner(dx, 1, dz)) & 1u) != at)) m |= 2u;
+                if (dz == 0 && (((c >> mc_corner(dx, dy, 1)) & 1u) != at)) m |= 4u;
+            }
+    return m;
+}
+
+// ---- sweep 2: the group records and the chunks' counts (reads the code bytes only) --------------------------------------------
+__global__ __launch_bounds__(kMcWaves * 64) void mc_count_kernel(const uint8_t *__restrict__ codes, int res, int64_t nvox, int64_t nchunks,
+                                                                 McGroup *__restrict__ groups, int64_t *__restrict__ vcount, int64_t *__restrict__ tcount)
+{
+    const int64_t chunk = (int64_t)blockIdx.x * kMcWaves + wave_id();
+    if (chunk >= nchunks) return;
+    const int lane = lane_id();
+    uint32_t vrun = 0u, trun = 0u;             // trun is lane 0's
+    for (int r = 0; r < kMcRounds; ++r) {
+        const int64_t g = chunk * kMcRounds + r, lin = g * 64 + lane;
+        if (g * 64 >= nvox) break;
+        unsigned m = 0u, own = 0u;
+        if (lin < nvox) {
+            int x, y, z;
+            mc_split(lin, res, x, y, z);
+            m = mc_edge_flags(codes, res, lin, x, y, z, &own);
+        }
+        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
+        const int nt = wave_sum((int)c_mc.ntri[own]);
+        if (lane == 0) {
+            McGroup G;
+            G.m[0] = b0; G.m[1] = b1; G.m[2] = b2;
+            G.vrel = vrun; G.trel = trun;
+            groups[g] = G;
+            trun += (uint32_t)nt;
+        }
+        vrun += (uint32_t)(__builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2));
+    }
+    if (lane == 0) {
+        vcount[chunk] = vrun;
+        tcount[chunk] = trun;
+    }
+}
+
+struct McFillArgs {
+    double org[3], vl;
+    const float *col;
+    float *overt, *ocol;
+    int32_t *otri;
+    int64_t nv, nt;
+};
+
+// vertex index of edge (voxel lin, axis a)
+__device__ __forceinline__ int64_t mc_rank(const McGroup *__restrict__ groups, const int64_t *__restrict__ voff, int64_t lin, int a)
+{
+    const int64_t g = lin >> 6;
+    const int l = (int)(lin & 63);
+    const McGroup G = groups[g];
+    const unsigned long long below = (1ull << l) - 1ull;
+    int64_t r = voff[g / kMcRounds] + G.vrel + __builtin_popcountll(G.m[0] & below) + __builtin_popcountll(G.m[1] & below) +
+                __builtin_popcountll(G.m[2] & below);
+    if (a >= 1) r += (int64_t)((G.m[0] >> l) & 1ull);
+    if (a == 2) r += (int64_t)((G.m[1] >> l) & 1ull);
+    return r;
+}
+
+// ---- sweep 3: vertices and colours by rank, triangles by the scanned triangle offsets -----------------------------------------
+__global__ __launch_bounds__(kMcWaves * 64) void mc_fill_kernel(const float2 *__restrict__ vol, const uint8_t *__restrict__ codes, int res, int64_t nvox,
+                                                                int64_t nchunks, const McGroup *__restrict__ groups, const int64_t *__restrict__ voff,
+                                                                const int64_t *__restrict__ toff, McFillArgs a)
+{
+    const int64_t chunk = (int64_t)blockIdx.x * kMcWaves + wave_id();
+    if (chunk >= nchunks) return;
+    const int lane = lane_id();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int64_t vbase = voff[chunk], tbase = toff[chunk];
+    if (voff[chunk + 1] == vbase && toff[chunk + 1] == tbase) return;
+    const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
+    for (int r = 0; r < kMcRounds; ++r) {
+        const int64_t g = chunk * kMcRounds + r, lin = g * 64 + lane;
+        if (g * 64 >= nvox) break;
+        const McGroup G = groups[g];
+        int x = 0, y = 0, z = 0;
+        if (lin < nvox) mc_split(lin, res, x, y, z);
+        // the vertices of this voxel's three edges
+        const unsigned mine = lin < nvox ? (unsigned)((G.m[0] >> lane) & 1ull) | (unsigned)((G.m[1] >> lane) & 1ull) << 1 | (unsigned)((G.m[2] >> lane) & 1ull) << 2 : 0u;
+        if (mine) {
+            int64_t dst = vbase + G.vrel + __builtin_popcountll(G.m[0] & below) + __builtin_popcountll(G.m[1] & below) + __builtin_popcountll(G.m[2] & below);
+            const int ix[3] = { x, y, z };
+            const double f0 = fabs((double)vol[lin].x);
+            const double p0[3] = { ((double)x + 0.5) * a.vl, ((double)y + 0.5) * a.vl, ((double)z + 0.5) * a.vl };
+            for (int i = 0; i < 3; ++i) {
+                if (!((mine >> i) & 1u)) continue;
+                if (dst >= a.nv || ix[i] + 1 >= res) break;           // never true for the ws the count pass left
+                const double f1 = fabs((double)vol[lin + step[i]].x);
+                double p[3] = { p0[0], p0[1], p0[2] };
+                p[i] = p[i] + (f0 * a.vl) / (f0 + f1);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) a.overt[3 * dst + k] = (float)(p[k] + a.org[k]);
+                if (a.ocol) {
+                    const float *c0 = a.col + 3 * lin, *c1 = a.col + 3 * (lin + step[i]);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) a.ocol[3 * dst + k] = (float)((f1 * ((double)c0[k] / 255.0) + f0 * ((double)c1[k] / 255.0)) / (f0 + f1));
+                }
+                ++dst;
+            }
+        }
+        // the triangles of the cube at this voxel
+        unsigned code = 0u;
+        if (lin < nvox && x < res - 1 && y < res - 1 && z < res - 1) code = codes[lin];
+        const int nt = c_mc.ntri[code];
+        const int incl = wave_incl_scan(nt);
+        int64_t tdst = tbase + G.trel + (incl - nt);
+        for (int t = 0; t < nt; ++t, ++tdst) {
+            if (tdst >= a.nt) break;
+            int32_t idx[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int e = c_mc.tri[code][3 * t + k];
+                const signed char *s = c_mc.shift[e];
+                idx[k] = (int32_t)mc_rank(groups, voff, lin + s[0] * step[0] + s[1] * step[1] + s[2], s[3]);
+            }
+            a.otri[3 * tdst] = idx[0];
+            a.otri[3 * tdst + 1] = idx[2];
+            a.otri[3 * tdst + 2] = idx[1];
+        }
+    }
+}
+
+inline int64_t mc_voxels(int32_t res) { return (int64_t)res * res * res; }
+inline bool mc_res_ok(int32_t res) { return res >= 1 && res <= KPX_TSDF_MAX_RESOLUTION; }
+
+struct McScratch {
+    uint8_t *codes;
+    McGroup *groups;
+    int64_t *voff, *toff;
+    int64_t nvox, nchunks;
+};
+void mc_carve(Arena &a, int32_t res, McScratch *s)
+{
+    s->nvox = mc_voxels(res);
+    s->nchunks = cdiv(s->nvox, kMcChunk);
+    s->codes = a.get<uint8_t>((size_t)s->nvox);
+    s->groups = a.get<McGroup>((size_t)s->nchunks * kMcRounds);
+    s->voff = a.get<int64_t>((size_t)s->nchunks + 1);
+    s->toff = a.get<int64_t>((size_t)s->nchunks + 1);
+}
+
+// ---- normals and area of a triangle mesh -----------------------------------------------------------------------------------------
+// AC12: n = (v1 - v0) x (v2 - v0) in fp64 from the float32 vertices, each component a b - c d.  A triangle with an index outside
+// [0, nv) reads nothing and has n = 0 (callers reject such meshes first).
+__device__ __forceinline__ void mesh_cross(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t t, double n[3])
+{
+    const int32_t i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+    n[0] = n[1] = n[2] = 0.0;
+    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return;
+    double e1[3], e2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double o = (double)v[3 * (int64_t)i0 + k];
+        e1[k] = (double)v[3 * (int64_t)i1 + k] - o;
+        e2[k] = (double)v[3 * (int64_t)i2 + k] - o;
+    }
+    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+}
+__device__ __forceinline__ double mesh_norm(const double n[3]) { return sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]); }
+// n / |n|, the zero vector -> (0, 0, 1) ([O3D] NormalizeNormals), rounded to float32 at the store
+__device__ __forceinline__ void mesh_store_normal(const double n[3], bool normalized, float *__restrict__ out)
+{
+    if (!normalized) {
+        out[0] = (float)n[0]; out[1] = (float)n[1]; out[2] = (float)n[2];
+        return;
+    }
+    const double len = mesh_norm(n);
+    if (len == 0.0) {
+        out[0] = 0.0f; out[1] = 0.0f; out[2] = 1.0f;
+        return;
+    }
+    out[0] = (float)(n[0] / len); out[1] = (float)(n[1] / len); out[2] = (float)(n[2] / len);
+}
+
+// n64 (fp64 [nt][3], may be null): the unnormalised normals the vertex sums read; pairs (may be null): the identity values of the
+// 3 nt (vertex, triangle corner) pairs for the sort
+__global__ __launch_bounds__(256) void mesh_triangle_normals_kernel(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t nt,
+                                                                    int normalized, float *__restrict__ out, double *__restrict__ n64, int32_t *__restrict__ pairs)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    double n[3];
+    mesh_cross(v, nv, tri, t, n);
+    if (out) mesh_store_normal(n, normalized != 0, out + 3 * t);
+    if (n64) { n64[3 * t] = n[0]; n64[3 * t + 1] = n[1]; n64[3 * t + 2] = n[2]; }
+    if (pairs) { pairs[3 * t] = (int32_t)(3 * t); pairs[3 * t + 1] = (int32_t)(3 * t + 1); pairs[3 * t + 2] = (int32_t)(3 * t + 2); }
+}
+
+// keys: the 3 nt vertex indices sorted (stable: equal vertices keep ascending pair = triangle order), vals: their pair numbers.
+// One thread per vertex walks its segment in order: the sum from 0 in ascending triangle index, whatever the segment's length.
+__global__ __launch_bounds__(256) void mesh_vertex_normals_kernel(const uint32_t *__restrict__ keys, const int32_t *__restrict__ vals, int64_t npairs,
+                                                                  const double *__restrict__ n64, int64_t nv, int normalized, float *__restrict__ out)
+{
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    int64_t lo = 0, hi = npairs;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)keys[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    double acc[3] = { 0.0, 0.0, 0.0 };
+    for (int64_t j = lo; j < npairs && (int64_t)keys[j] == v; ++j) {
+        const int64_t t = (int64_t)(vals[j] / 3);
+        acc[0] = acc[0] + n64[3 * t];
+        acc[1] = acc[1] + n64[3 * t + 1];
+        acc[2] = acc[2] + n64[3 * t + 2];
+    }
+    mesh_store_normal(acc, normalized != 0, out + 3 * v);
+}
+
+// the sum over the triangles, ascending, of |n| / 2 in fp64.  The order is the contract, so the additions are one chain; everything
+// else is kept off it: one block computes the terms of 1024 triangles at a time into LDS (the gathers of the next batch are in flight
+// while the current one is summed), and its first wave adds the current batch in order.
+constexpr int kAreaThreads = 1024;
+__global__ __launch_bounds__(kAreaThreads) void mesh_area_kernel(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t nt,
+                                                                 double *__restrict__ out)
+{
+    __shared__ double sh[2][kAreaThreads];
+    auto term = [&](int64_t t) {
+        double half = 0.0;
+        if (t < nt) {
+            double n[3];
+            mesh_cross(v, nv, tri, t, n);
+            half = mesh_norm(n) * 0.5;
+        }
+        return half;
+    };
+    sh[0][threadIdx.x] = term(threadIdx.x);
+    __syncthreads();
+    double s = 0.0;
+    int cur = 0;
+    for (int64_t b = 0; b < nt; b += kAreaThreads, cur ^= 1) {
+        const double next = term(b + kAreaThreads + threadIdx.x);
+        if (threadIdx.x < 64) {
+            const int cnt = nt - b < kAreaThreads ? (int)(nt - b) : kAreaThreads;
+#pragma unroll 16
+            for (int i = 0; i < cnt; ++i) s = s + sh[cur][i];
+        }
+        sh[cur ^ 1][threadIdx.x] = next;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = s;
+}
+
+struct MeshNormalScratch {
+    double *n64;
+    uint32_t *keys_out;
+    int32_t *vals_in, *vals_out;
+    void *tmp;
+    size_t tmp_bytes;
+};
+void mesh_normals_carve(Arena &a, int64_t nt, MeshNormalScratch *s)
+{
+    const size_t t = (size_t)(nt > 0 ? nt : 1), p = 3 * t;
+    s->n64 = a.get<double>(3 * t);
+    s->keys_out = a.get<uint32_t>(p);
+    s->vals_in = a.get<int32_t>(p);
+    s->vals_out = a.get<int32_t>(p);
+    s->tmp_bytes = memo_bytes(10, (int64_t)p, [&] { size_t b = 0; (void)sort_pairs<uint32_t>(nullptr, b, s->keys_out, s->keys_out, s->vals_in, s->vals_out, (int64_t)p, 32, (hipStream_t) nullptr); return b; });
+    s->tmp = a.get<char>(s->tmp_bytes);
+}
+
+constexpr int64_t kMeshMax = 2147483647;        // int32 indices
+
+}  // namespace
+}  // namespace kpx
+
+using namespace kpx;
+
+KPX_EXPORT size_t kpx_tsdf_mesh_workspace_bytes(int32_t resolution)
+{
+    if (!mc_res_ok(resolution)) return 0;
+    Arena a(nullptr, 0);
+    McScratch s;
+    mc_carve(a, resolution, &s);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_tsdf_mesh_count(const float *volume, int32_t resolution, int64_t *d_counts, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(mc_res_ok(resolution), "kpx_tsdf_mesh_count: resolution must be in [1, %d]", KPX_TSDF_MAX_RESOLUTION);
+    KPX_REQUIRE(volume && d_counts && ws, "kpx_tsdf_mesh_count: null pointer");
+    Arena a(ws, ws_bytes);
+    McScratch s;
+    mc_carve(a, resolution, &s);
+    KPX_ARENA_CHECK(a);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, reinterpret_cast<const float2 *>(volume), resolution, s.nvox, s.codes);
+    hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)cdiv(s.nchunks, kMcWaves)), dim3(kMcWaves * 64), 0, st, (const uint8_t *)s.codes, resolution, s.nvox,
+                       s.nchunks, s.groups, s.voff, s.toff);
+    hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, s.voff, s.toff, s.nchunks);
+    KPX_LAUNCH_CHECK();
+    KPX_HIP(hipMemcpyAsync(d_counts, s.voff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    KPX_HIP(hipMemcpyAsync(d_counts + 1, s.toff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_tsdf_mesh_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
+                                  int64_t n_vertices, int64_t n_triangles, float *out_vertices, float *out_colors, int32_t *out_triangles, void *ws,
+                                  size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(mc_res_ok(resolution), "kpx_tsdf_mesh_fill: resolution must be in [1, %d]", KPX_TSDF_MAX_RESOLUTION);
+    KPX_REQUIRE(voxel_length > 0.0 && n_vertices >= 0 && n_triangles >= 0, "kpx_tsdf_mesh_fill: bad voxel_length or counts");
+    if (n_vertices > kMeshMax || n_triangles > kMeshMax)
+        return fail(KPX_ERR_RANGE, "kpx_tsdf_mesh_fill: %lld vertices and %lld triangles: a mesh holds fewer than 2^31 of each", (long long)n_vertices,
+                    (long long)n_triangles);
+    if (n_vertices == 0 && n_triangles == 0) return KPX_OK;
+    KPX_REQUIRE(volume && h_origin && ws && (n_vertices == 0 || out_vertices) && (n_triangles == 0 || out_triangles), "kpx_tsdf_mesh_fill: null pointer");
+    KPX_REQUIRE(!out_colors || color, "kpx_tsdf_mesh_fill: colours need a colour volume");
+    Arena a(ws, ws_bytes);
+    McScratch s;
+    mc_carve(a, resolution, &s);
+    KPX_ARENA_CHECK(a);
+    McFillArgs f;
+    for (int k = 0; k < 3; ++k) f.org[k] = h_origin[k];
+    f.vl = voxel_length;
+    f.col = color; f.overt = out_vertices; f.ocol = out_colors; f.otri = out_triangles;
+    f.nv = n_vertices; f.nt = n_triangles;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kMcWaves)), dim3(kMcWaves * 64), 0, st, reinterpret_cast<const float2 *>(volume),
+                       (const uint8_t *)s.codes, resolution, s.nvox, s.nchunks, (const McGroup *)s.groups, (const int64_t *)s.voff, (const int64_t *)s.toff, f);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT size_t kpx_mesh_normals_workspace_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (n_vertices < 0 || n_triangles < 0 || n_vertices > kMeshMax || 3 * n_triangles > kMeshMax) return 0;
+    Arena a(nullptr, 0);
+    MeshNormalScratch s;
+    mesh_normals_carve(a, n_triangles, &s);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_mesh_normals(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int32_t normalized,
+                                float *out_triangle_normals, float *out_vertex_normals, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "kpx_mesh_normals: negative count");
+    if (n_vertices > kMeshMax || 3 * n_triangles > kMeshMax)
+        return fail(KPX_ERR_RANGE, "kpx_mesh_normals: %lld vertices, %lld triangles: at most 2^31 - 1 vertices and triangle corners", (long long)n_vertices,
+                    (long long)n_triangles);
+    const bool want_v = out_vertex_normals && n_vertices > 0, want_t = out_triangle_normals && n_triangles > 0;
+    if (!want_v && !want_t) return KPX_OK;
+    KPX_REQUIRE((n_triangles == 0 || (vertices && triangles)) && (!want_v || ws), "kpx_mesh_normals: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    MeshNormalScratch s{};
+    if (want_v) {
+        Arena a(ws, ws_bytes);
+        mesh_normals_carve(a, n_triangles, &s);
+        KPX_ARENA_CHECK(a);
+    }
+    const int64_t npairs = 3 * n_triangles;
+    if (n_triangles > 0) {
+        hipLaunchKernelGGL(mesh_triangle_normals_kernel, dim3((unsigned)cdiv(n_triangles, 256)), dim3(256), 0, st, vertices, n_vertices, triangles, n_triangles,
+                           (int)normalized, want_t ? out_triangle_normals : (float *)nullptr, want_v ? s.n64 : (double *)nullptr,
+                           want_v ? s.vals_in : (int32_t *)nullptr);
+        KPX_LAUNCH_CHECK();
+    }
+    if (!want_v) return KPX_OK;
+    if (n_triangles > 0) {
+        int bits = 1;
+        while (bits < 32 && ((int64_t)1 << bits) < n_vertices) ++bits;
+        size_t bytes = s.tmp_bytes;
+        KPX_HIP(sort_pairs<uint32_t>(s.tmp, bytes, reinterpret_cast<const uint32_t *>(triangles), s.keys_out, s.vals_in, s.vals_out, npairs, bits, st));
+    }
+    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)cdiv(n_vertices, 256)), dim3(256), 0, st, (const uint32_t *)s.keys_out, (const int32_t *)s.vals_out,
+                       npairs, (const double *)s.n64, n_vertices, (int)normalized, out_vertex_normals);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_mesh_surface_area(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_area, void *stream)
+{
+    KPX_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "kpx_mesh_surface_area: negative count");
+    KPX_REQUIRE(d_area && (n_triangles == 0 || (vertices && triangles)), "kpx_mesh_surface_area: null pointer");
+    hipLaunchKernelGGL(mesh_area_kernel, dim3(1), dim3(kAreaThreads), 0, (hipStream_t)stream, vertices, n_vertices, triangles, n_triangles, d_area);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}

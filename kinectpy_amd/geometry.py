@@ -819,3 +819,148 @@ class VoxelGrid:
         if not self.has_voxels():
             return self
         return self._carve("silhouette", list(t.to(L.device())), width, height, K, E, keep_voxels_outside_image)
+
+
+class Vector3iVector:
+    """o3d.utility.Vector3iVector stand-in: wraps a (T, 3) int32 array (a triangle list); np.asarray() gives int32.  Host data
+    stays on the host until a TriangleMesh takes it."""
+
+    def __init__(self, data=None):
+        if isinstance(data, Vector3iVector):
+            self.t = data.t
+        elif data is None:
+            self.t = torch.empty((0, 3), dtype=torch.int32)
+        elif isinstance(data, torch.Tensor):
+            self.t = data.to(dtype=torch.int32).reshape(-1, 3).contiguous()
+        else:
+            a = np.asarray(data)
+            if a.size and (a.ndim != 2 or a.shape[1] != 3):
+                raise RuntimeError("Vector3iVector: expected a (T, 3) array")
+            self.t = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 3))
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.t.cpu().numpy()
+        return a if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return int(self.t.shape[0])
+
+    def __getitem__(self, i):
+        return np.asarray(self)[i]
+
+
+class TriangleMesh:
+    """[O3D] geometry.TriangleMesh, the part a fused surface needs: float32 (V, 3) vertices, int32 (T, 3) triangles and the optional
+    vertex colours, vertex normals and triangle normals, all device tensors; normals and area are arithmetic contract AC12
+    (kpx_mesh_normals, kpx_mesh_surface_area).  Simplification, clean-up, sampling and the other Open3D methods are not built."""
+    _bounds = None
+
+    def __init__(self, vertices=None, triangles=None):
+        self._vert = Vector3dVector(vertices).t
+        self._tri = Vector3iVector(triangles).t.to(L.device())
+        self._vcol = self._vnrm = self._tnrm = None
+
+    @classmethod
+    def _make(cls, vert, tri, vcol=None, vnrm=None, tnrm=None):
+        m = cls.__new__(cls)
+        m._vert, m._tri, m._vcol, m._vnrm, m._tnrm = vert, tri, vcol, vnrm, tnrm
+        return m
+
+    # ---- attributes ---------------------------------------------------------------------------
+    @property
+    def vertices(self):
+        return Vector3dVector(self._vert)
+
+    @vertices.setter
+    def vertices(self, v):
+        self._vert, self._bounds = Vector3dVector(v).t, None
+
+    @property
+    def triangles(self):
+        return Vector3iVector(self._tri)
+
+    @triangles.setter
+    def triangles(self, v):
+        self._tri = Vector3iVector(v).t.to(L.device())
+
+    def _optional(name):
+        def get(self):
+            t = getattr(self, name)
+            return Vector3dVector(t if t is not None else None)
+
+        def put(self, v):
+            t = Vector3dVector(v).t
+            setattr(self, name, t if t.shape[0] else None)
+        return property(get, put)
+
+    vertex_colors, vertex_normals, triangle_normals = _optional("_vcol"), _optional("_vnrm"), _optional("_tnrm")
+    del _optional
+
+    def has_vertices(self):
+        return self._vert.shape[0] > 0
+
+    def has_triangles(self):
+        return self.has_vertices() and self._tri.shape[0] > 0
+
+    def has_vertex_colors(self):
+        return self.has_vertices() and self._vcol is not None and self._vcol.shape[0] == self._vert.shape[0]
+
+    def has_vertex_normals(self):
+        return self.has_vertices() and self._vnrm is not None and self._vnrm.shape[0] == self._vert.shape[0]
+
+    def has_triangle_normals(self):
+        return self.has_triangles() and self._tnrm is not None and self._tnrm.shape[0] == self._tri.shape[0]
+
+    def is_empty(self):
+        return not self.has_vertices()
+
+    def __repr__(self):
+        return f"TriangleMesh with {self._vert.shape[0]} points and {self._tri.shape[0]} triangles."
+
+    def __deepcopy__(self, memo):
+        c = lambda t: None if t is None else t.clone()
+        return TriangleMesh._make(self._vert.clone(), self._tri.clone(), c(self._vcol), c(self._vnrm), c(self._tnrm))
+
+    __copy__ = lambda self: self.__deepcopy__({})
+
+    # ---- Open3D methods -------------------------------------------------------------------------
+    def compute_triangle_normals(self, normalized=True):
+        self._tnrm, _ = ops.mesh_normals(self._vert, self._tri, normalized, want_vertex=False)
+        return self
+
+    def compute_vertex_normals(self, normalized=True):
+        """also fills the triangle normals, as Open3D does"""
+        self._tnrm, self._vnrm = ops.mesh_normals(self._vert, self._tri, normalized)
+        return self
+
+    def get_surface_area(self):
+        return ops.mesh_surface_area(self._vert, self._tri)
+
+    def _device_bounds(self):
+        if self._bounds is None:
+            self._bounds = ops.bounds(self._vert)
+        return self._bounds
+
+    def get_min_bound(self):
+        if not self.has_vertices():
+            return np.zeros(3)
+        return self._device_bounds()[:3].cpu().numpy()
+
+    def get_max_bound(self):
+        if not self.has_vertices():
+            return np.zeros(3)
+        return self._device_bounds()[3:].cpu().numpy()
+
+    def transform(self, T):
+        """in place, returns self: the vertices through T, vertex and triangle normals through its rotation"""
+        T = np.asarray(T, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise RuntimeError("transform: expected a 4x4 matrix")
+        if self.has_vertices():
+            self._bounds = None
+            ops.transform(self._vert, T, out=self._vert)
+            if self.has_vertex_normals():
+                ops.rotate(self._vnrm, T, out=self._vnrm)
+            if self.has_triangle_normals():
+                ops.rotate(self._tnrm, T, out=self._tnrm)
+        return self

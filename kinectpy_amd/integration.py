@@ -1,7 +1,7 @@
 """o3d.pipelines.integration over the kinectpx hot path: a uniform truncated-signed-distance volume in device memory that depth
 images are integrated into (kpx_tsdf_integrate, arithmetic contract AC9 of DESIGN.md) and surface clouds are extracted from.
 The batch form `integrate_frames` takes the rig's uint16 depth frames as they are and updates the volume for all of them in one
-pass.  Mesh extraction and the hashed ScalableTSDFVolume are off the path and raise."""
+pass; extract_triangle_mesh is marching cubes over the same volume (AC12).  The hashed ScalableTSDFVolume is off the path and raises."""
 import enum
 
 import numpy as np
@@ -9,7 +9,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .geometry import PointCloud
+from .geometry import PointCloud, TriangleMesh
 
 
 class TSDFVolumeColorType(enum.Enum):
@@ -95,9 +95,13 @@ class UniformTSDFVolume:
         pts, _, col = ops.tsdf_extract(self._vol, self._col, self.resolution, self.voxel_length, self.origin, "voxels")
         return PointCloud._make(pts, col, None)
 
-    def extract_triangle_mesh(self, *a, **k):
-        from .o3d import _off_path
-        return _off_path("UniformTSDFVolume.extract_triangle_mesh")(*a, **k)
+    def extract_triangle_mesh(self):
+        """[O3D] extract_triangle_mesh: marching cubes over the active cubes (AC12) -> TriangleMesh with vertex colours from an RGB8
+        volume and without normals; vertices ascend in (linear voxel index, axis)"""
+        if getattr(self, "_vol", None) is None:
+            raise NotImplementedError("UniformTSDFVolume.extract_triangle_mesh: needs a volume in device memory -- no CPU fallback")
+        vert, col, tri = ops.tsdf_extract_mesh(self._vol, self._col, self.resolution, self.voxel_length, self.origin)
+        return TriangleMesh._make(vert, tri, col)
 
     def __repr__(self):
         return f"UniformTSDFVolume with {self.color_type.name}, resolution {self.resolution}, voxel_length {self.voxel_length:g}."

@@ -9,9 +9,11 @@ import numpy as np
 
 from . import ops
 from .geometry import (Image, ImageFilterType, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
-                       OrientedBoundingBox, PointCloud, RGBDImage, Vector2iVector, Vector3dVector, Voxel, VoxelGrid, _off_path)
+                       OrientedBoundingBox, PointCloud, RGBDImage, TriangleMesh, Vector2iVector, Vector3dVector, Vector3iVector, Voxel,
+                       VoxelGrid, _off_path)
 from . import integration as _integration
 from . import odometry as _odometry
+from . import mesh_io
 from . import pcd_io
 from . import posegraph
 
@@ -447,10 +449,13 @@ class PinholeCameraParameters:
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
                                  Image=Image, ImageFilterType=ImageFilterType, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
+                                 TriangleMesh=TriangleMesh,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
 camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic, PinholeCameraParameters=PinholeCameraParameters)
-utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Matrix3dVector=Matrix3dVector)
-io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud)
+utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Vector3iVector=Vector3iVector,
+                                Matrix3dVector=Matrix3dVector)
+io = types.SimpleNamespace(read_point_cloud=pcd_io.read_point_cloud, write_point_cloud=pcd_io.write_point_cloud,
+                           read_triangle_mesh=mesh_io.read_triangle_mesh, write_triangle_mesh=mesh_io.write_triangle_mesh)
 pipelines = types.SimpleNamespace(integration=types.SimpleNamespace(
     TSDFVolumeColorType=_integration.TSDFVolumeColorType,
     UniformTSDFVolume=_integration.UniformTSDFVolume,

@@ -1213,6 +1213,63 @@ def tsdf_extract(volume, color, resolution, voxel_length, origin, mode="surface"
     return pts, nrm, col
 
 
+MESH_MAX = 2 ** 31 - 1          # int32 vertex and triangle indices
+
+
+def tsdf_extract_mesh(volume, color, resolution, voxel_length, origin):
+    """[O3D] extract_triangle_mesh (marching cubes, AC12) -> (vertices float32 (V, 3), colours float32 (V, 3) | None, triangles int32
+    (T, 3)) device tensors, vertices ascending in (linear voxel index, axis).  One host read (the two counts) between count and fill."""
+    lib = L.load()
+    dev = volume.device
+    ws = torch.empty(lib.kpx_tsdf_mesh_workspace_bytes(int(resolution)), dtype=torch.uint8, device=dev)      # carried from count to fill
+    cnt = torch.empty(2, dtype=torch.int64, device=dev)
+    L.check(lib.kpx_tsdf_mesh_count(L.ptr(volume), int(resolution), L.ptr(cnt), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    nv, nt = (int(c) for c in cnt.tolist())
+    if nv > MESH_MAX or nt > MESH_MAX:
+        raise L.KinectPxError(f"tsdf_extract_mesh: {nv} vertices and {nt} triangles: a mesh holds fewer than 2^31 of each")
+    vert = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    col = torch.empty((nv, 3), dtype=torch.float32, device=dev) if color is not None else None
+    tri = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    L.check(lib.kpx_tsdf_mesh_fill(L.ptr(volume), L.ptr(color), int(resolution), float(voxel_length), L.hptr(org), nv, nt, L.ptr(vert), L.ptr(col),
+                                   L.ptr(tri), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return vert, col, tri
+
+
+def _mesh_arrays(who, vertices, triangles):
+    """device float32 (V, 3) and int32 (T, 3); an index outside [0, V) raises here, before any kernel sees it (min and max are taken
+    on the device)"""
+    vert = _dev(vertices, torch.float32).reshape(-1, 3)
+    tri = _dev(triangles, torch.int32).reshape(-1, 3)
+    if tri.shape[0]:
+        lo, hi = int(tri.min()), int(tri.max())
+        if lo < 0 or hi >= vert.shape[0]:
+            raise L.KinectPxError(f"{who}: triangle index out of range [0, {vert.shape[0]})")
+    return vert, tri
+
+
+def mesh_normals(vertices, triangles, normalized=True, want_triangle=True, want_vertex=True):
+    """AC12's normals of a triangle mesh -> (triangle normals float32 (T, 3) | None, vertex normals float32 (V, 3) | None): the fp64
+    cross product per triangle; per vertex the sum of the unnormalised normals of its triangles in ascending triangle index."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_normals", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    tn = torch.empty((nt, 3), dtype=torch.float32, device=vert.device) if want_triangle else None
+    vn = torch.empty((nv, 3), dtype=torch.float32, device=vert.device) if want_vertex else None
+    ws, wsz = L.workspace(lib.kpx_mesh_normals_workspace_bytes(nv, nt)) if want_vertex else (None, 0)
+    L.check(lib.kpx_mesh_normals(L.ptr(vert), nv, L.ptr(tri), nt, int(bool(normalized)), L.ptr(tn), L.ptr(vn), ws, wsz, L.stream_ptr()))
+    return tn, vn
+
+
+def mesh_surface_area(vertices, triangles):
+    """sum of the triangles' areas, fp64, in ascending triangle order (AC12) -> float"""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_surface_area", vertices, triangles)
+    out = torch.empty(1, dtype=torch.float64, device=vert.device)
+    L.check(lib.kpx_mesh_surface_area(L.ptr(vert), vert.shape[0], L.ptr(tri), tri.shape[0], L.ptr(out), L.stream_ptr()))
+    return float(out.item())
+
+
 # ---- occupancy grids ------------------------------------------------------------------------------------
 VOXELGRID_MODES = {"depth": 0, "silhouette": 1}          # KPX_VOXELGRID_DEPTH / KPX_VOXELGRID_SILHOUETTE (include/kinectpx.h)
 VOXELGRID_FORMATS = {torch.float32: 0, torch.uint16: 1, torch.uint8: 2}          # KPX_VOXELGRID_F32 / U16 / U8

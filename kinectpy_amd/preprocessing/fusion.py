@@ -17,12 +17,13 @@ class _Intrinsic:
         self.intrinsic_matrix = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
 
 
-def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0):
+def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0, mesh=False):
     """depth: uint16 (S, H W) raw frames (synth.sensor_ring's layout; host or device); rgb: uint8 (S, H W, 3) or None (no colours);
     intrinsic: a PinholeCameraIntrinsic, or None for the Kinect's (synth.FX, FY, CX, CY at synth.W x synth.H); sensor_to_master:
     the S - 1 transforms of the sub sensors (sensor 0 is the master, identity).  The world frame is the master's: sensor s is
     integrated with the extrinsic inv(sensor_to_master[s]) (host float64).  sdf_trunc defaults to 4 voxels.  One integrate_frames
-    call and one extraction -> PointCloud with normals (and colours when rgb is given)."""
+    call and one extraction -> PointCloud with normals (and colours when rgb is given); mesh=True: the surface as a TriangleMesh
+    (extract_triangle_mesh) with vertex normals computed instead."""
     if intrinsic is None:
         intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
     n = int(depth.shape[0])
@@ -33,6 +34,8 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
         sdf_trunc = 4.0 * float(length) / int(resolution)
     vol = UniformTSDFVolume(length, resolution, sdf_trunc, TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor, origin)
     vol.integrate_frames(depth, rgb, intrinsic, np.stack(extr), depth_scale, depth_trunc)
+    if mesh:
+        return vol.extract_triangle_mesh().compute_vertex_normals()
     return vol.extract_point_cloud()
 
 

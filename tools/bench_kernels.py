@@ -350,6 +350,15 @@ def tsdf_rows(dev, quick):
             ms, (pts, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "surface"))
             report(f"tsdf extract_point_cloud ({tag}; count + scan + host read + fill)", ms, 8 * res ** 3 + int(pts.shape[0]) * (36 if colour else 24),
                    points=int(pts.shape[0]))
+            # marching cubes: the code sweep reads the volume (8 B / voxel) and writes a byte, the count sweep reads the bytes and writes
+            # the group records (0.5 B), the fill sweep reads both: 12 B / voxel, plus the mesh
+            ms, (vert, _, tri) = timed(lambda: ops.tsdf_extract_mesh(vol, col, res, vl, origin))
+            nv, nt = int(vert.shape[0]), int(tri.shape[0])
+            report(f"tsdf extract_triangle_mesh ({tag}; codes + count + scans + host read + fill)", ms, 12 * res ** 3 + nv * (24 if colour else 12) + nt * 12,
+                   vertices=nv, triangles=nt)
+            ms, _ = timed(lambda: ops.mesh_normals(vert, tri))
+            report(f"mesh compute_vertex_normals ({tag}; triangle normals + sort of 3 T pairs + vertex sums)", ms, nv * 24 + nt * 24, vertices=nv, triangles=nt)
+            del vert, tri
             if not colour:
                 ms, (vp, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "voxels"))
                 report(f"tsdf extract_voxel_point_cloud ({tag})", ms, 8 * res ** 3 + int(vp.shape[0]) * 24, points=int(vp.shape[0]))
