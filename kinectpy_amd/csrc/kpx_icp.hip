@@ -13,7 +13,9 @@
 //   kpx_icpchain.h  host: which one-launch chains may be resident together
 // Below: the switches (IcpSwitches), profiling read-backs, plans and workspace, the search launches, what the entry points share (NnProblem: setup
 // and the correspondences' way out; icp_search_solve_loop), the exported entry points, and the batch driver (batch_carve, icp_batch_ordered
-// with drive_grouped / drive_windowed / drive_dense_polled).
+// with drive_grouped / drive_windowed / drive_dense_polled).  Each culled driver has one job: drive_grouped runs up to eight registrations
+// per launch with the update in the last block of every registration's sweep; drive_windowed runs a chain per registration with the
+// update in the next sweep's prologue, or (KPX_ICP_FUSE=0, as kpx_icp does) in its own kernel behind the kernel boundary.
 #include <chrono>
 #include <limits.h>
 #include <string.h>
@@ -33,10 +35,6 @@
 
 namespace kpx {
 
-#ifndef KPX_ICP_SPLIT_DEFAULT
-#define KPX_ICP_SPLIT_DEFAULT 2
-#endif
-
 // ---- the switches of the registration ---------------------------------------------------------------------------------------------
 // Every environment variable the registration reads, read ONCE (first use).  All of them select between forms that give the same
 // results and exist for same-box A/B measurements ("Environment switches of the library").  KPX_NN_ENGINE and
@@ -46,16 +44,14 @@ struct IcpSwitches {
     bool nn_screen;            // KPX_NN_SCREEN=0: dense engine without its float32 screening sweep; default on (tools/nn_dense_probe.py)
     bool batch_launch;         // KPX_ICP_BATCH_LAUNCH=0: one launch chain per registration; default one per group of 8
     bool fuse;                 // KPX_ICP_FUSE=0: per-registration chains with the update in its own kernel, and no grouped chain; default on
-    int split;                 // KPX_ICP_SPLIT=0|1|2: update in the next sweep's prologue / its own kernel / the sweep's last block; default 2 (test_icp_update_placements_and_light_skip_are_bit_identical)
     int window;                // KPX_ICP_WINDOW=1..64: launches of a group queued ahead of the newest progress word; default (and out of range) 3 (profiles/r04/exp_icp_window.txt)
     double stall_seconds;      // KPX_ICP_STALL_SECONDS>0: watchdog of the launch windows; default 60
     bool light_skip;           // KPX_ICP_LIGHT_SKIP=0: sweep every block; default on (test_icp_update_placements_and_light_skip_are_bit_identical)
     bool cert;                 // KPX_ICP_CERT=0: search every row every iteration; default on, ignored (off) without LightSkip (same test)
     bool cert_check;           // KPX_ICP_CERT_CHECK=1: search certified rows all the same and count disagreements; default off (test_icp_certificates_never_contradict_the_search)
     CertPolicy cert_policy;    // KPX_CERT_CALM / _FACTOR / _SKIN_MIN / _SKIN_MAX: the certificates' skin policy; default 0.15 / 3 / 0.02 / 0.2
-    int rows;                  // KPX_ICP_ROWS=0|1|2: icp_rows_kernel never / by searched share / always (split 2 only); default 1 (test_icp_update_placements_and_light_skip_are_bit_identical)
+    int rows;                  // KPX_ICP_ROWS=0|1|2: icp_rows_kernel never / by searched share / always (the grouped driver); default 1 (test_icp_update_placements_and_light_skip_are_bit_identical)
     int rows_share;            // KPX_ICP_ROWS_SHARE=1..127: largest searched share (1/127ths) served by the rows form; default (and out of range) 3 (same test)
-    int rows_r;                // KPX_ICP_ROWS_R=16|32|64: rows per wave of icp_rows_kernel; default (and anything else) 64
     bool chain_alone;          // KPX_ICP_CHAIN_ALONE=0: admit one-launch chains also with other frames in flight; default only alone
     long chain_budget;         // KPX_ICP_CHAIN_BUDGET=blocks the chains in flight may hold; default -1 = (blocks per CU - 1) x CUs (test_icp_chain_that_cannot_be_resident_fails_loudly)
     bool chain_no_lock;        // KPX_ICP_CHAIN_LOCK=0: skip the one-process-per-GPU lock file; default locked (test_icp_update_placements_and_light_skip_are_bit_identical)
@@ -75,7 +71,6 @@ static const IcpSwitches &icp_switches()
         w.nn_screen = not0("KPX_NN_SCREEN");
         w.batch_launch = not0("KPX_ICP_BATCH_LAUNCH");
         w.fuse = not0("KPX_ICP_FUSE");
-        w.split = digit("KPX_ICP_SPLIT", '2', KPX_ICP_SPLIT_DEFAULT);
         const int window = atoi(text("KPX_ICP_WINDOW"));
         w.window = window >= 1 && window <= 64 ? window : 3;
         const double stall = atof(text("KPX_ICP_STALL_SECONDS"));
@@ -87,8 +82,6 @@ static const IcpSwitches &icp_switches()
         w.rows = digit("KPX_ICP_ROWS", '2', 1);
         const int share = atoi(text("KPX_ICP_ROWS_SHARE"));
         w.rows_share = share >= 1 && share <= 127 ? share : 3;
-        const int r = atoi(text("KPX_ICP_ROWS_R"));
-        w.rows_r = r == 16 || r == 32 || r == 64 ? r : 64;
         w.chain_alone = not0("KPX_ICP_CHAIN_ALONE");
         const char *budget = getenv("KPX_ICP_CHAIN_BUDGET");
         w.chain_budget = budget ? atol(budget) : -1L;
@@ -298,7 +291,7 @@ static void nn_carve_source(Arena &a, int64_t n, const NnPlan &p, NnBuffers *b)
     b->src_sorted = a.get<float>(nn * 3);
     b->ptgt_sorted = a.get<float>(nn * 3);
     b->acc_fixed = a.get<unsigned long long>((size_t)3 * kAccCopies * kAcc * kFixedWords + 8);      // ring of three sets (icp_iter_kernel, IcpFuse)
-    b->light_key = a.get<double>((size_t)(cdiv((int64_t)nn, 64) + cdiv((int64_t)nn, 32) + cdiv((int64_t)nn, 16)));   // per 64 rows (both forms), then per 32 and per 16 (icp_rows_kernel<., R>)
+    b->light_key = a.get<double>((size_t)cdiv((int64_t)nn, 64));   // per 64 rows: a block of icp_iter_body, a wave of icp_rows_kernel
     b->cert_sorted = a.get<uint32_t>(nn);
     b->thist = a.get<double>((size_t)kCertHist * 12);
     b->chain_rec = a.get<double>((size_t)kChainRecords * kChainRec);
@@ -1041,11 +1034,10 @@ int kpx::icp_chain_abort_take()
 
 namespace kpx {
 
-// icp_rows_kernel with R rows per wave (KPX_ICP_ROWS_R: 64 / 32 / 16): problems given as IcpProblems, each at its own iteration k[c]
+// icp_rows_kernel (a wave per 64 rows): problems given as IcpProblems, each at its own iteration k[c]
 static void rows_launch(const IcpProblem *const *probs, const int *ks, int cnt, double md2, int mode, int max_iter, double rel_fit, double rel_rmse,
                         unsigned long long *visits, int light, CertPolicy pol, hipStream_t st)
 {
-    const int R = icp_switches().rows_r;
     RowsArgs ra;
     ra.count = cnt;
     unsigned b0 = 0;
@@ -1053,18 +1045,15 @@ static void rows_launch(const IcpProblem *const *probs, const int *ks, int cnt, 
         const int cc = c < cnt ? c : cnt - 1;
         const IcpProblem &Q = *probs[cc];
         RowsProblem &Rp = ra.p[c];
-        const int64_t n64 = cdiv(Q.n, 64), n32 = cdiv(Q.n, 32);
         Rp.src_sorted = Q.src_sorted; Rp.idx_sorted = Q.idx_sorted; Rp.ptgt_sorted = Q.ptgt_sorted; Rp.cert = Q.cert; Rp.thist = Q.thist;
-        Rp.light_key = Q.light_key + (R == 64 ? 0 : R == 32 ? n64 : n64 + n32); Rp.sbbox = Q.sbbox; Rp.state = Q.pair; Rp.ring = Q.ring; Rp.result = Q.result;
+        Rp.light_key = Q.light_key; Rp.sbbox = Q.sbbox; Rp.state = Q.pair; Rp.ring = Q.ring; Rp.result = Q.result;
         Rp.progress = Q.progress; Rp.tag = Q.tag; Rp.tgt = Q.tgt; Rp.tn = Q.tn; Rp.Bs = Q.Bs; Rp.orig = Q.orig; Rp.tile_box = Q.tile_box; Rp.group_box = Q.group_box;
         Rp.tbbox = Q.tbbox; Rp.n = Q.n; Rp.n_groups = Q.n_groups; Rp.k = ks[cc];
-        Rp.block0 = b0; Rp.blocks = (unsigned)cdiv(Q.n, R);
+        Rp.block0 = b0; Rp.blocks = (unsigned)cdiv(Q.n, kRowsBlock);
         if (c < cnt) b0 += Rp.blocks;
     }
-#define KPX_ROWS_LAUNCH(M, RR) hipLaunchKernelGGL((icp_rows_kernel<M, RR>), dim3(b0), dim3(64), 0, st, ra, md2, max_iter, rel_fit, rel_rmse, visits, light, pol)
-    if (mode == 1) { if (R == 64) KPX_ROWS_LAUNCH(1, 64); else if (R == 32) KPX_ROWS_LAUNCH(1, 32); else KPX_ROWS_LAUNCH(1, 16); }
-    else { if (R == 64) KPX_ROWS_LAUNCH(0, 64); else if (R == 32) KPX_ROWS_LAUNCH(0, 32); else KPX_ROWS_LAUNCH(0, 16); }
-#undef KPX_ROWS_LAUNCH
+    if (mode == 1) hipLaunchKernelGGL(icp_rows_kernel<1>, dim3(b0), dim3(64), 0, st, ra, md2, max_iter, rel_fit, rel_rmse, visits, light, pol);
+    else hipLaunchKernelGGL(icp_rows_kernel<0>, dim3(b0), dim3(64), 0, st, ra, md2, max_iter, rel_fit, rel_rmse, visits, light, pol);
 }
 
 
@@ -1171,28 +1160,24 @@ static int drive_grouped(const BatchCtx &x)
     // same box, four frames in flight 2556-2600 vs 2441-2448 Mpoints/s, one frame at a time equal (a launch lasts >= 20 us, the
     // progress word reaches the host in a few; 2 starts to starve: profiles/r04/exp_icp_window.txt).  KPX_ICP_WINDOW: A/B switch.
     const int window = sw.window;
-    // split (default): the update of every registration runs in icp_solve_batch_kernel between the sweeps; KPX_ICP_SPLIT=0: in the
-    // prologue of the next sweep's blocks (one launch per iteration).  Same-run A/B with four frames in flight: 1830-1930 vs
-    // 1730-1830 Mpoints/s -- the redundant prologue holds every block's wave slots 4 us longer, and slots are what frames compete for.
-    // KPX_ICP_SPLIT=2: in the LAST block of the sweep itself (no update kernel, no redundant prologue).
-    const int split = sw.split;
-    const int last_k = split ? x.max_iteration : x.max_iteration + 1;     // the fused chain ends with an update-only launch
+    // The update runs in the LAST block of every registration's sweep.  The other placements live in the per-registration drivers: the
+    // next sweep's prologue in drive_windowed (icp_fused_launch), its own kernel in kpx_icp and under KPX_ICP_FUSE=0 (icp_iter_launch).
     const int light = icp_light_word(sw);
     const CertPolicy cert_policy = sw.cert_policy;
-    // The one-launch chain (icp_chain_kernel) when the update is the last block's (split 2), the records hold the iterations and the
+    // The one-launch chain (icp_chain_kernel) when the records hold the iterations and the
     // group's blocks fit the device beside the chains already in flight; KPX_ICP_CHAIN=0: always a launch per iteration.
-    const bool chain_ok = chain_form_on() && split == 2 && x.max_iteration <= kChainRecords - 2 && chain_abort_word() != nullptr &&
+    const bool chain_ok = chain_form_on() && x.max_iteration <= kChainRecords - 2 && chain_abort_word() != nullptr &&
                           (!sw.chain_alone || busy_threads() <= 1);
     // KPX_ICP_ROWS=0: the iterations through icp_iter_batch_kernel (a wave per 16-row tile, blocks of four) -- the A/B switch of
-    // icp_rows_kernel (a wave per 64 rows), which serves the update in the last block (split 2) with LightSkip's bookkeeping
+    // icp_rows_kernel (a wave per 64 rows)
     // (1, the default: per launch, by how much of the registrations the last reported iteration still searched -- the progress word's
     // bits 33..39: a wave per tile while most rows are searched, a wave per 64 rows once most are certified (KPX_ICP_ROWS_SHARE: the
     // largest searched share, in 1/127ths, at which the rows form is taken); 2: always the rows form.  The forms agree bit for bit,
     // so the choice -- which follows the host's timing -- never shows in a result.)
-    const int rows_mode = split == 2 ? sw.rows : 0;
+    const int rows_mode = sw.rows;
     const int rows_share = sw.rows_share;
     const NnBuffers &tb = x.bufs[0];                       // (the target's operands are shared)
-    IcpBatchArgs A[8], Ac[8];                              // count <= 64: at most 8 groups
+    IcpBatchArgs A[8];                                     // count <= 64: at most 8 groups
     int gk[8];
     bool gfin[8];
     for (int g = 0; g < x.n_chain; ++g) {
@@ -1213,12 +1198,10 @@ static int drive_grouped(const BatchCtx &x)
             P.block0 = b0; P.blocks = (unsigned)cdiv(x.h_n_src[i], kIRows);
             P.tgt = x.tgt; P.tn = x.tgt_normals; P.Bs = tb.Bs; P.orig = tb.orig_t; P.tile_box = tb.tile_box; P.group_box = tb.group_box;
             P.tbbox = tb.sort_t.bbox; P.n_groups = x.tplan->l_groups; P.k = 0; P.tag = tag;
-            Ac[g].p[c] = P;
-            Ac[g].p[c].block0 = (unsigned)c; Ac[g].p[c].blocks = 1u;
             for (int e = 0; e < 16; ++e) T0.m[c][e] = x.h_init[16 * i + e];
             if (i0 + c < i1) { b0 += P.blocks; pw.clear(i); }
         }
-        A[g].count = Ac[g].count = i1 - i0;
+        A[g].count = i1 - i0;
         gk[g] = 0; gfin[g] = false;
         hipLaunchKernelGGL(icp_batch_init_kernel, dim3(b0), dim3(256), 0, ls, A[g], T0);
         if (chain_ok) {
@@ -1242,8 +1225,8 @@ static int drive_grouped(const BatchCtx &x)
             // the launches still to be queued carry only the registrations that have not converged yet (as far as the host
             // knows: the progress words lag by up to `window` launches); a converged problem's blocks in an already queued
             // launch read its state and return
-            IcpBatchArgs act, actc;
-            act.count = actc.count = 0;
+            IcpBatchArgs act;
+            act.count = 0;
             unsigned ab = 0;
             for (int c = 0; c < A[g].count; ++c) {
                 const ProgressWindow::Word w = pw.read(g * kIcpBatchMax + c);
@@ -1254,16 +1237,13 @@ static int drive_grouped(const BatchCtx &x)
                 act.p[act.count] = A[g].p[c];
                 act.p[act.count].block0 = ab;
                 ab += A[g].p[c].blocks;
-                actc.p[actc.count] = Ac[g].p[c];
-                actc.p[actc.count].block0 = (unsigned)actc.count;
-                ++act.count; ++actc.count;
+                ++act.count;
             }
             if (all_done) { gfin[g] = true; continue; }
-            for (int c = act.count; c < kIcpBatchMax; ++c) { act.p[c] = act.p[act.count - 1]; actc.p[c] = actc.p[actc.count - 1]; }
+            for (int c = act.count; c < kIcpBatchMax; ++c) act.p[c] = act.p[act.count - 1];
             hipStream_t ls = x.lane(g);
-            while (gk[g] <= last_k && gk[g] - seen < window) {
+            while (gk[g] <= x.max_iteration && gk[g] - seen < window) {
                 advanced = true;
-                const bool closing = gk[g] > x.max_iteration;
                 ProfScope prof(KPX_PROF_NN_LOCAL, 0.0, ls);
                 if (rows_mode == 2 || (rows_mode == 1 && share <= rows_share)) {
                     // one wave per 64 rows (kpx_icprows.h): every problem with its own operands and iteration number
@@ -1275,16 +1255,12 @@ static int drive_grouped(const BatchCtx &x)
                     ++gk[g];
                     continue;
                 }
-                for (int c = 0; c < kIcpBatchMax; ++c) { act.p[c].k = gk[g]; actc.p[c].k = gk[g]; }
-                hipLaunchKernelGGL(icp_iter_batch_kernel, dim3(closing ? (unsigned)act.count : ab), dim3(kIThreads), 0, ls, closing ? actc : act, x.md2,
-                                   x.mode, x.max_iteration, x.relative_fitness, x.relative_rmse,
-                                   prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, split, split == 2 ? light : 0, cert_policy);
-                if (split == 1)
-                    hipLaunchKernelGGL(icp_solve_batch_kernel, dim3((unsigned)act.count), dim3(256), 0, ls, act, x.mode, gk[g], x.max_iteration,
-                                       x.relative_fitness, x.relative_rmse, tag);
+                for (int c = 0; c < kIcpBatchMax; ++c) act.p[c].k = gk[g];
+                hipLaunchKernelGGL(icp_iter_batch_kernel, dim3(ab), dim3(kIThreads), 0, ls, act, x.md2, x.mode, x.max_iteration, x.relative_fitness,
+                                   x.relative_rmse, prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, light, cert_policy);
                 ++gk[g];
             }
-            if (gk[g] > last_k) { gfin[g] = true; continue; }
+            if (gk[g] > x.max_iteration) { gfin[g] = true; continue; }
             pending = true;
         }
         rc = pw.pass_done(advanced, pending);

@@ -536,9 +536,9 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     // This is the `sc1` form of the valid hand-offs of MI355X_MICROARCH.md ("Correctness boundaries"): the handed-off bytes are
     // produced by atomics (performed at the memory side, never resident in a CU's L1), drained before the ticket because every
     // add RETURNS, and read by the winner with device-coherent (sc1) loads only (fixed_total_coherent) -- no plain load of them
-    // anywhere.  It rests on gfx950 behaviour, not on the HIP memory model: KPX_ICP_SPLIT=1 (update in its own kernel, ordered by the
-    // kernel boundary) is the portable fall-back, and test_update_placements_agree_with_four_frames_in_flight compares the three
-    // placements bit for bit under four frames in flight.
+    // anywhere.  It rests on gfx950 behaviour, not on the HIP memory model: KPX_ICP_BATCH_LAUNCH=0 KPX_ICP_FUSE=0 (per-registration chains,
+    // update in its own kernel, ordered by the kernel boundary) is the portable fall-back, and
+    // test_update_placements_agree_with_four_frames_in_flight compares the two bit for bit under four frames in flight.
     // The state is written with plain stores: its readers are the blocks of the NEXT launch, behind the kernel boundary.
     __shared__ unsigned s_ticket;
     __syncthreads();
@@ -629,8 +629,7 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
 // number of launches per frame, not their size, is what the frame rate of the pipeline follows.  A problem that has
 // converged keeps its blocks in the later launches: they read its state and return.
 __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_iter_batch_kernel(IcpBatchArgs args, double max_d2, int mode, int max_iter, double rel_fit,
-                                                       double rel_rmse, unsigned long long *__restrict__ tile_visits, int split, int light,
-                                                       CertPolicy pol)
+                                                       double rel_rmse, unsigned long long *__restrict__ tile_visits, int light, CertPolicy pol)
 {
     int pi = 0;
 #pragma unroll
@@ -643,14 +642,10 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
     const int32_t n_groups = P.n_groups;
     const int k = P.k;
     const unsigned long long tag = P.tag;
-    if (k > max_iter && bid != 0) return;                   // the closing launch only performs the last update (one block per problem)
-    // split: the update runs in icp_solve_batch_kernel between the sweeps (state slot 0, first accumulator set): the sweep's blocks
-    // then live 8 us instead of 12 -- under load (several frames in flight) the device's wave slots are what the sweeps compete for
-    // split == 2: no update kernel either -- the last block of every registration's sweep performs it (ticket: first word of the
-    // second accumulator set, which only the one-launch form uses)
-    const IcpFuse fuse{ split ? (IcpState *)nullptr : P.pair, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag,
-                        split == 2 ? P.ring + kAccSet : (unsigned long long *)nullptr, (light & 1) ? P.light_key : (double *)nullptr, P.sbbox,
-                        (light & 2) ? P.cert : (uint32_t *)nullptr, (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, nullptr, nullptr };
+    // the last block of every registration's sweep performs the update (ticket: first word of the second accumulator set)
+    const IcpFuse fuse{ (IcpState *)nullptr, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag, P.ring + kAccSet,
+                        (light & 1) ? P.light_key : (double *)nullptr, P.sbbox, (light & 2) ? P.cert : (uint32_t *)nullptr,
+                        (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, nullptr, nullptr };
     icp_iter_body(bid, P.blocks, P.src, P.n, tgt, tn, Bs, orig, tile_box, group_box, n_groups, tbbox, P.row_of, P.src_sorted, P.idx_sorted, P.ptgt_sorted,
                   P.idx_cur, P.d2_cur, max_d2, mode, k, P.pair, P.ring, tile_visits, fuse);
 }
@@ -718,27 +713,6 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
     }
 }
 
-// The update step of every registration of a batch, one block each (split mode: see icp_iter_batch_kernel)
-__global__ __launch_bounds__(256) void icp_solve_batch_kernel(IcpBatchArgs args, int mode, int k, int max_iter, double rel_fit, double rel_rmse,
-                                                              unsigned long long tag)
-{
-    const IcpProblem &P = args.p[blockIdx.x];
-    IcpState *st = P.pair;
-    if (st->done) return;
-    __shared__ double sums[kAcc];
-    __shared__ FinishScratch fs;
-    unsigned long long *acc = P.ring;
-    const int nacc = mode == 1 ? kAcc : 17;
-    if (threadIdx.x < kAcc) sums[threadIdx.x] = (int)threadIdx.x < nacc ? fixed_total(acc, threadIdx.x) : 0.0;
-    __syncthreads();
-    for (int e = threadIdx.x; e < kAccCopies * kAcc * kFixedWords; e += 256) acc[e] = 0ull;
-    if (threadIdx.x >= 64) return;
-    icp_finish_wave(sums, P.n, mode, k, max_iter, rel_fit, rel_rmse, st, P.result, fs, (int)threadIdx.x);
-    if (threadIdx.x == 0 && P.progress)
-        __hip_atomic_store(P.progress, tag | ((unsigned long long)(st->done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // Start of a batch chain in ONE launch: per problem both state slots <- the initial transform, the accumulator ring cleared,
 // the rows gathered into Morton order (what icp_init_kernel + a memset + gather_rows_kernel did per problem)
 __global__ __launch_bounds__(256) void icp_batch_init_kernel(IcpBatchArgs args, Mat16x8 T0)
@@ -753,13 +727,7 @@ __global__ __launch_bounds__(256) void icp_batch_init_kernel(IcpBatchArgs args, 
         const int64_t r = (int64_t)bid * kIRows + rr;
         if (r < P.n && c < 3) P.src_sorted[3 * r + c] = P.src[3 * (int64_t)P.row_of[r] + c];
     }
-    if (threadIdx.x < 7) {                                  // the block's LightSkip keys at every granularity: 1 x 64 rows, 2 x 32, 4 x 16
-        const int64_t n64 = (P.n + 63) / 64, n32 = (P.n + 31) / 32, n16 = (P.n + 15) / 16;
-        const int t = threadIdx.x;
-        const int64_t e = t == 0 ? (int64_t)bid : t < 3 ? n64 + 2 * (int64_t)bid + (t - 1) : n64 + n32 + 4 * (int64_t)bid + (t - 3);
-        const int64_t lim = t == 0 ? n64 : t < 3 ? n64 + n32 : n64 + n32 + n16;
-        if (e < lim) P.light_key[e] = 0.0;
-    }
+    if (threadIdx.x == 0) P.light_key[bid] = 0.0;           // the block's LightSkip key
     if (bid == 0) {
         for (int e = threadIdx.x; e < 3 * kAccSet; e += 256) P.ring[e] = 0ull;
         if (threadIdx.x >= 64 && threadIdx.x < 76) P.thist[threadIdx.x - 64] = T0.m[pi][threadIdx.x - 64];

@@ -38,12 +38,18 @@ def _settings(*specs):
 # as superseded by sor_block_kernel.
 # Nor the all-pairs engine's chunked fp64 sweep and caller-order operands and their switches KPX_NN_FAST and KPX_NN_DENSE_SORT: removed
 # as superseded by the per-trip sweep over curve-ordered operands (profiles/r04/nn_dense_sorted.txt).
+# Nor the grouped ICP driver's update placements 0 and 1 (next sweep's prologue, own kernel) and the 16- and 32-row widths of
+# icp_rows_kernel, with their switches KPX_ICP_SPLIT and KPX_ICP_ROWS_R: removed.  No default path had reached them since round 2, the
+# per-registration drivers keep both placements (KPX_ICP_BATCH_LAUNCH=0, with KPX_ICP_FUSE=0), and neither narrower width measured
+# ahead of 64 (profiles/r06/exp_env_KPX_ICP_ROWS_R.txt).
 FAMILIES = {
     "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_OCC=0.2", "SOR_OCC=1.0", "BBOX_VEC=0"),
     "voxel": _settings("RADIX=0", "VOXEL_SINGLE=0"),
-    # the launch-per-iteration chains of icp_rows_kernel: KPX_ICP_ROWS_R only shows with the rows form forced and the one-launch chain off
-    "icp": _settings("ICP_FUSE=0", "ICP_BATCH_LAUNCH=0", "ICP_WINDOW=1", "ICP_WINDOW=64", "ICP_ROWS=2+ICP_ROWS_R=16+ICP_CHAIN=0",
-                     "ICP_ROWS=2+ICP_ROWS_R=32+ICP_CHAIN=0"),
+    # the launch-per-iteration chains of icp_rows_kernel: the rows form forced and the one-launch chain off
+    "icp": _settings("ICP_FUSE=0", "ICP_BATCH_LAUNCH=0", "ICP_WINDOW=1", "ICP_WINDOW=64", "ICP_ROWS=2+ICP_CHAIN=0"),
+    # the grouped driver's update in the sweep's last block (one-launch chains by default) against the per-registration drivers (update
+    # in the next sweep's prologue; behind the kernel boundary) and against its own launch-per-iteration forms, at the edge sizes
+    "icp_edges": _settings("ICP_BATCH_LAUNCH=0", "ICP_BATCH_LAUNCH=0+ICP_FUSE=0", "ICP_CHAIN=0", "ICP_ROWS=0+ICP_CHAIN=0", "ICP_ROWS=2+ICP_CHAIN=0"),
     "dense": _settings("NN_SCREEN=0"),
     # KPX_ICP_CHAIN_ALONE=0 admits one-launch chains with frames in flight (the streams below); KPX_ORDER_LOOKAHEAD: any value >= 0 is accepted and cut to slots - 1; FRAME_SLOTS = 4 slots, so 0 and 3 are its ends (default 2)
     "frame": _settings("FRAME_SPECULATE=0", "FRAME_SPIN=0", "SHARD_NORMALS=1", "SHARD_FIXED_CAP=1",
@@ -53,7 +59,7 @@ FAMILIES = {
 # every culled-ICP child: this suite's own process may hold the device's chain lock (it is idle meanwhile), as
 # test_icp_update_placements_and_light_skip_are_bit_identical sets it
 # the dense children: the environment chooses the engine at the library's first use, and ops.nn_engine("dense") then reports it
-FAMILY_ENV = {"icp": {"KPX_ICP_CHAIN_LOCK": "0"}, "frame": {"KPX_ICP_CHAIN_LOCK": "0"}, "dense": {"KPX_NN_ENGINE": "dense"}}
+FAMILY_ENV = {"icp": {"KPX_ICP_CHAIN_LOCK": "0"}, "icp_edges": {"KPX_ICP_CHAIN_LOCK": "0"}, "frame": {"KPX_ICP_CHAIN_LOCK": "0"}, "dense": {"KPX_NN_ENGINE": "dense"}}
 FRAME_SLOTS = 4
 
 FLIPPED_ELSEWHERE = {
@@ -61,7 +67,6 @@ FLIPPED_ELSEWHERE = {
     "KPX_ONEPASS_BATCH": "tests.test_compaction_gpu::test_forced_forms_agree_and_match_the_oracle",
     "KPX_MEDIAN_FRAME": "tests.test_parity_gpu::test_median_exact",
     "KPX_PLANE_MFMA": "tests.test_parity_gpu::test_segment_plane_ties_thresholds_and_sequential_path",
-    "KPX_ICP_SPLIT": "tests.test_parity_gpu::test_icp_update_placements_and_light_skip_are_bit_identical",
     "KPX_ICP_LIGHT_SKIP": "tests.test_parity_gpu::test_icp_update_placements_and_light_skip_are_bit_identical",
     "KPX_ICP_CERT": "tests.test_parity_gpu::test_icp_update_placements_and_light_skip_are_bit_identical",
     "KPX_ICP_CERT_CHECK": "tests.test_parity_gpu::test_icp_certificates_never_contradict_the_search",
@@ -179,6 +184,22 @@ def voxel_attrs(clouds, rng):
 def fused_transforms():
     T = synth.t_star()
     return [np.eye(4), T]
+
+
+# ---------------------------------------------------------------------------------------------------------------- culled ICP, edge sizes
+ICP_EDGES_N = 4000                        # synth.icp_pair(4000): the target, and the cloud the sources are cut from
+ICP_EDGES_NORMALS = (70.0, 40)            # the target's normals (test_icp_chain_edge_sizes_equal_launch_per_iteration's)
+ICP_EDGES_MAX_DIST = 100.0
+ICP_GROUP_MAX = 7                         # kpx_icp.hip kpx_icp_batch: the batch sort takes the target and seven sources; from eight on the
+                                          # clouds stay in caller order and the per-registration driver (drive_windowed) serves
+
+
+def icp_edges_cases(src):
+    """(sources, max_iteration): where a ticket count or a block range can be off by one -- a single row; partial waves, a full block,
+    one row and one block beyond it; all the grouped driver takes and one more; no iteration and one"""
+    ramp = lambda count: [src[i * 300:(i + 1) * 300 + 7 * i] for i in range(count)]
+    return [([src[:1]], 5), ([src[:17], src[:64], src[:65], src[:129]], 5), (ramp(ICP_GROUP_MAX), 6), (ramp(ICP_GROUP_MAX + 1), 6),
+            ([src[:2000]], 0), ([src[:2000]], 1)]
 
 
 # ---------------------------------------------------------------------------------------------------------------- dense engine

@@ -111,6 +111,24 @@ def icp(out):
     out["engine"] = np.array([ops.NN_ENGINES.index(ops.nn_engine())])
 
 
+def icp_edges(out):
+    """switch_matrix.icp_edges_cases through ops.icp_batch, both estimators, identity initial transforms; per call the one-launch
+    chains it started (ops.icp_chain(-2))"""
+    src, tgt, _ = synth.icp_pair(M.ICP_EDGES_N)
+    tn = ops.estimate_normals(tgt, *M.ICP_EDGES_NORMALS)
+    out["tn"] = npy(tn)
+    chains = []
+    for ci, (srcs, iters) in enumerate(M.icp_edges_cases(src)):
+        for mode in ("p2p", "p2plane"):
+            before = ops.icp_chain(-2)
+            r = ops.icp_batch(srcs, tgt, M.ICP_EDGES_MAX_DIST, [np.eye(4)] * len(srcs), mode, tn if mode == "p2plane" else None, iters)
+            out["%s_%d_T" % (mode, ci)] = np.stack([x["transformation"] for x in r])
+            out["%s_%d_s" % (mode, ci)] = np.array([[x["fitness"], x["inlier_rmse"], x["iterations"], x["count"]] for x in r])
+            chains.append(ops.icp_chain(-2) - before)
+    out["chains"] = np.array(chains).reshape(-1, 2)
+    out["engine"] = np.array([ops.NN_ENGINES.index(ops.nn_engine())])
+
+
 def dense(out):
     out["engine_before"] = np.array([ops.NN_ENGINES.index(ops.nn_engine("dense"))])      # what KPX_NN_ENGINE had chosen
     src, tgt, T = synth.icp_pair(M.DENSE_N)
@@ -187,6 +205,6 @@ def fps(out):
 
 if __name__ == "__main__":
     result = {}
-    {"grid": grid, "voxel": voxel, "icp": icp, "dense": dense, "frame": frame, "fps": fps}[sys.argv[1]](result)
+    {"grid": grid, "voxel": voxel, "icp": icp, "icp_edges": icp_edges, "dense": dense, "frame": frame, "fps": fps}[sys.argv[1]](result)
     torch.cuda.synchronize()
     np.savez(sys.argv[2], **result)

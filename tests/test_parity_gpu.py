@@ -2003,8 +2003,10 @@ np.savez(sys.argv[1], **out)
 
 
 def test_icp_update_placements_and_light_skip_are_bit_identical(tmp_path):
-    """The update step in its own kernel (KPX_ICP_SPLIT=1), in the last block of the sweep (2, the default) and with the blocks
-    that provably cannot find a partner left out of the sweeps (KPX_ICP_LIGHT_SKIP, default on) and the rows whose partner provably
+    """The update step in the last block of the sweep (the grouped driver, the default), in the next sweep's prologue
+    (KPX_ICP_BATCH_LAUNCH=0: per-registration chains) and in its own kernel behind the kernel boundary (KPX_ICP_BATCH_LAUNCH=0
+    KPX_ICP_FUSE=0), and with the blocks that provably cannot find a partner left out of the sweeps (KPX_ICP_LIGHT_SKIP, default on)
+    and the rows whose partner provably
     cannot change left out of the search (KPX_ICP_CERT, default on), and the whole chain in one launch (icp_chain_kernel, the default
     where a batch's blocks fit the device: the "small" and "alone" batches) against a launch per iteration (KPX_ICP_CHAIN=0): the
     exact fixed-point sums do not depend on which blocks add to them or when, and a certified row keeps exactly the partner a search
@@ -2016,7 +2018,8 @@ def test_icp_update_placements_and_light_skip_are_bit_identical(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     got = {}
-    for name, env in (("tail+skip", {}), ("nocert", {"KPX_ICP_CERT": "0"}), ("tail", {"KPX_ICP_LIGHT_SKIP": "0"}), ("kernel", {"KPX_ICP_SPLIT": "1"}),
+    for name, env in (("tail+skip", {}), ("nocert", {"KPX_ICP_CERT": "0"}), ("tail", {"KPX_ICP_LIGHT_SKIP": "0"}),
+                      ("kernel", {"KPX_ICP_BATCH_LAUNCH": "0", "KPX_ICP_FUSE": "0"}), ("prologue", {"KPX_ICP_BATCH_LAUNCH": "0"}),
                       ("launches", {"KPX_ICP_CHAIN": "0"}), ("chain nocert", {"KPX_ICP_CERT": "0", "KPX_ICP_CHAIN": "1"}),
                       ("blocks of four", {"KPX_ICP_ROWS": "0"}), ("blocks of four nocert", {"KPX_ICP_ROWS": "0", "KPX_ICP_CERT": "0", "KPX_ICP_CHAIN": "0"}),
                       ("rows", {"KPX_ICP_ROWS": "2", "KPX_ICP_CHAIN": "0"}), ("rows nocert", {"KPX_ICP_ROWS": "2", "KPX_ICP_CERT": "0", "KPX_ICP_CHAIN": "0"}),
@@ -2026,9 +2029,10 @@ def test_icp_update_placements_and_light_skip_are_bit_identical(tmp_path):
                            env={**os.environ, "KPX_ICP_CHAIN_LOCK": "0", **env})    # (this process may hold the device's chain lock; it is idle meanwhile)
         assert r.returncode == 0, r.stderr[-2000:]
         got[name] = dict(np.load(f))
-    # the forms that were to be compared did run: four chains (two modes x two small batches) by default, none with KPX_ICP_CHAIN=0 or a split update
-    assert got["tail+skip"]["chains"][0] == 4 and got["chain nocert"]["chains"][0] == 4 and got["launches"]["chains"][0] == 0 and got["kernel"]["chains"][0] == 0
-    for name in ("nocert", "tail", "kernel", "launches", "chain nocert", "blocks of four", "blocks of four nocert", "rows", "rows nocert", "rows early"):
+    # the forms that were to be compared did run: four chains (two modes x two small batches) by default, none with KPX_ICP_CHAIN=0 or per-registration chains
+    assert got["tail+skip"]["chains"][0] == 4 and got["chain nocert"]["chains"][0] == 4 and got["launches"]["chains"][0] == 0
+    assert got["kernel"]["chains"][0] == 0 and got["prologue"]["chains"][0] == 0
+    for name in ("nocert", "tail", "kernel", "prologue", "launches", "chain nocert", "blocks of four", "blocks of four nocert", "rows", "rows nocert", "rows early"):
         for key, v in got["tail+skip"].items():
             if key != "chains":
                 assert np.array_equal(v, got[name][key]), (name, key)
@@ -2174,16 +2178,19 @@ def test_icp_certificates_never_contradict_the_search():
 def test_update_placements_agree_with_four_frames_in_flight(tmp_path):
     """The same comparison under load: 24 frames through FrameStream with FOUR frames in flight (every kernel of four ICP chains
     sharing the device), update step in the last block of the sweep (default; its hand-off rests on returning device-scope atomics,
-    a relaxed ticket and sc1 loads in the winning block -- the `sc1` form of the guide's valid hand-offs), in its own kernel, and in the
-    next sweep's prologue: every fused cloud and every transform identical to the last bit, and the repeats of a frame identical
+    a relaxed ticket and sc1 loads in the winning block -- the `sc1` form of the guide's valid hand-offs), in its own kernel behind the
+    kernel boundary (KPX_ICP_BATCH_LAUNCH=0 KPX_ICP_FUSE=0: per-registration chains), and in the next sweep's prologue
+    (KPX_ICP_BATCH_LAUNCH=0); the default again with the blocks-of-four and the rows kernel forced: every fused cloud and every
+    transform identical to the last bit, and the repeats of a frame identical
     among themselves."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     got = {}
-    for mode in ("2", "1", "0", "blocks", "rows"):
+    envs = {"2": {}, "1": {"KPX_ICP_BATCH_LAUNCH": "0", "KPX_ICP_FUSE": "0"}, "0": {"KPX_ICP_BATCH_LAUNCH": "0"},
+            "blocks": {"KPX_ICP_ROWS": "0"}, "rows": {"KPX_ICP_ROWS": "2"}}
+    for mode, env in envs.items():
         f = str(tmp_path / f"split{mode}.npz")
-        env = {"KPX_ICP_SPLIT": "2", "KPX_ICP_ROWS": "0" if mode == "blocks" else "2"} if mode in ("blocks", "rows") else {"KPX_ICP_SPLIT": mode}
         r = subprocess.run([sys.executable, os.path.join(root, "tools", "ab_frames.py"), f, "4", "3"], cwd=root, capture_output=True, text=True,
                            timeout=600, env={**os.environ, **env, "GPU_MAX_HW_QUEUES": "8"})
         assert r.returncode == 0, r.stderr[-2000:]

@@ -239,6 +239,46 @@ def test_icp_launch_form_switches(defaults, tmp_path, setting):
     assert int(z["chains"][0]) == (4 if grouped else 0), setting
 
 
+# ---------------------------------------------------------------------------------------------------------------- culled ICP, edge sizes
+def test_icp_edges_default_matches_the_oracle(defaults, oracle):
+    """the default child of the edge-size family: a one-launch chain for every call of at most seven sources, none for eight (the
+    per-registration driver), and its 2000-row registrations against the oracle.  The one- and few-row registrations are compared
+    among the forms only: their solves are singular."""
+    from kinectpy_amd.utils import synth
+    z = defaults("icp_edges")
+    src, tgt, _ = synth.icp_pair(M.ICP_EDGES_N)
+    cases = M.icp_edges_cases(src)
+    assert int(z["engine"][0]) == 0                                     # the culled engine
+    assert [[len(s) for s in srcs] for srcs, _ in cases[:2]] == [[1], [17, 64, 65, 129]]
+    assert [len(srcs) for srcs, _ in cases[2:4]] == [M.ICP_GROUP_MAX, M.ICP_GROUP_MAX + 1] and len(cases[3][0][-1]) == 300 + 7 * M.ICP_GROUP_MAX
+    assert z["chains"].tolist() == [[1, 1] if len(srcs) <= M.ICP_GROUP_MAX else [0, 0] for srcs, _ in cases]
+    checked = 0
+    for ci, (srcs, iters) in enumerate(cases):
+        if [len(s) for s in srcs] != [2000]:
+            continue
+        for mode in ("p2p", "p2plane"):
+            rT, rf, _, rit = oracle.registration_icp(srcs[0], tgt, M.ICP_EDGES_MAX_DIST, None, mode, z["tn"], iters)
+            fit, _, its, _ = z["%s_%d_s" % (mode, ci)][0]
+            err = np.abs(z["%s_%d_T" % (mode, ci)][0] - rT).max()
+            print("icp_edges", mode, "max_iteration", iters, "iterations", its, rit, "fitness", fit, rf, "transform error", err)
+            assert its == rit and fit == rf, (mode, iters)
+            assert err < TOL_T, (mode, iters)
+            checked += 1
+    assert checked == 4
+
+
+@_params("icp_edges")
+def test_icp_edge_size_switches(defaults, tmp_path, setting):
+    """every transform, fitness, rmse, iteration number and count of the edge-size cases bit for bit between the grouped driver's
+    default and the setting's form; no setting of the family starts a one-launch chain (per-registration drivers, KPX_ICP_CHAIN=0)"""
+    env = M.FAMILIES["icp_edges"][setting]
+    assert {"KPX_ICP_BATCH_LAUNCH", "KPX_ICP_CHAIN"} & set(env), setting
+    base, z = defaults("icp_edges"), run_child("icp_edges", setting, env, tmp_path)
+    _same_keys(base, z, setting)
+    _bitwise(base, z, [key for key in base if key != "chains"], setting)
+    assert z["chains"].shape == base["chains"].shape and not z["chains"].any(), setting
+
+
 # ---------------------------------------------------------------------------------------------------------------- dense engine
 def _dense_plan(env):
     """the kernels a dense-engine child's searches go through (switch_matrix.dense_sweep): first searches have no bound from a previous

@@ -2,7 +2,7 @@
 # Same-box A/B runs (boxes differ by +-15 %: only comparisons inside one call mean anything).  One script for every experiment kept
 # under profiles/rNN/exp_*.txt:
 #
-#   tools/ab.sh env  NAME VALUE_A VALUE_B [...]     one environment switch (KPX_ICP_LIGHT_SKIP 1 0, KPX_ICP_SPLIT 2 1 0, KPX_RADIX 1 0,
+#   tools/ab.sh env  NAME VALUE_A VALUE_B [...]     one environment switch (KPX_ICP_LIGHT_SKIP 1 0, KPX_ICP_ROWS 1 0 2, KPX_RADIX 1 0,
 #                                                   KPX_FRAME_SPECULATE 1 0, GPU_MAX_HW_QUEUES 4 8, ...): bench at 4 frames in flight and at 1
 #   tools/ab.sh lib  cur NAME [...]                 library variants built by tools/build_variant.sh: ICP probe + bench line
 #   tools/ab.sh flag "--overlap 2" "--overlap 4" [...]   bench.py argument sets (frames in flight, --python-step, ...)
