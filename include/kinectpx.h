@@ -795,6 +795,75 @@ int kpx_mesh_normals(const float *vertices, int64_t n_vertices, const int32_t *t
                      float *out_triangle_normals, float *out_vertex_normals, void *ws, size_t ws_bytes, void *stream);
 int kpx_mesh_surface_area(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_area, void *stream);
 
+/* ---- mesh clean-up ([O3D] geometry.TriangleMesh; arithmetic contract AC13) ------------------------------------------
+ * Every operator takes float32 vertices / colours / normals [n][3] and int32 triangles [n_triangles][3] in device memory, works on
+ * `stream` and returns without waiting.  Every triangle index must lie in [0, n_vertices): the caller checks; a triangle that violates
+ * it reads nothing, makes no pair and no edge, has area 0 and is a cluster of its own.  At most 2^31 - 1 vertices and 6 n_triangles
+ * (KPX_ERR_RANGE); the workspace queries return 0 for counts outside that.  All floating-point work is fp64, every multiply and add
+ * separate; values round to float32 only where stated.
+ * kpx_mesh_adjacency: N(v) = the ascending distinct vertices that share a corner pair of some triangle with v (a triangle (a, a, b)
+ *     puts a into its own list), as CSR: out_offsets i32 [n_vertices + 1], out_neighbours i32 with room for 6 n_triangles entries of
+ *     which offsets[n_vertices] = *d_count (i32, device) are written.
+ * kpx_mesh_non_manifold_edges: the undirected edges {t0,t1}, {t1,t2}, {t2,t0} of every triangle, keyed min << 32 | max; out_edges i32
+ *     [3 n_triangles][2] receives, ascending, the (min, max) of the keys that occur more than 2 times (allow_boundary_edges != 0) or a
+ *     number of times other than 2 (== 0); *d_count (i32, device) = how many.
+ * kpx_mesh_cluster_triangles: triangles that share an edge key are adjacent; out_clusters i32 [n_triangles] = the id of each triangle's
+ *     connected component, components numbered by their smallest triangle index; out_n_triangles i32 and out_area f64, each with room
+ *     for n_triangles entries of which *d_count (i32, device) are written: the component's triangle count and the sum from 0, in
+ *     ascending triangle index, of its triangles' sqrt((nx^2 + ny^2) + nz^2) * 0.5 (n as kpx_mesh_normals').  *d_count = KPX_ERR_RANGE
+ *     when a union-find hook gave up.
+ * kpx_mesh_flags: out_flags u8 [n_flags].  KPX_MESH_FLAG_REFERENCED: n_flags = n_vertices, 1 where some triangle names the vertex.
+ *     KPX_MESH_FLAG_DEGENERATE: n_flags = n_triangles, 1 where two of the triangle's indices are equal.  KPX_MESH_FLAG_INDICES: 1 at
+ *     every indices[j] (i64 [n_indices], device) inside [0, n_flags), values outside are ignored.
+ * kpx_mesh_select_triangles: the triangles (and their normals when out_triangle_normals is given) with (flags[t] != 0) != (invert != 0),
+ *     in order; outputs have room for n_triangles rows, *d_count (i32, device) are written.
+ * kpx_mesh_select_vertices: the vertices with (flags[v] != 0) != (invert != 0), in order, with their colours and normals (optional);
+ *     the triangles whose three corners stay, in order, renumbered by the rank of their corners, with their normals (optional).
+ *     d_counts i32 [2] (device): vertices, triangles written.  ws: kpx_mesh_select_workspace_bytes(n_vertices, n_triangles), for
+ *     kpx_mesh_select_triangles (0, n_triangles).
+ * kpx_mesh_smooth: `iterations` steps (KPX_MESH_SMOOTH_TAUBIN: pairs of steps, lambda_filter then mu) over the CSR adjacency, on fp64
+ *     copies of the arrays whose output is given (out_vertices, out_normals, out_colors; any may be NULL = not filtered), rounded to
+ *     float32 once at the end.  x = the vertices at the start of the step (the input's when they are not filtered), y = any filtered
+ *     array, u over N(v) ascending.  SIMPLE: y'[v] = (y[v] + sum y[u]) / (1 + |N(v)|).  LAPLACIAN step(l): w = 1 / (sqrt((d0 d0 + d1 d1)
+ *     + d2 d2) + 1e-12), d = x[v] - x[u]; y'[v] = y[v] + l (sum w y[u] / sum w - y[v]); |N(v)| = 0 keeps y[v].  One launch per step.
+ * kpx_mesh_sample_points: n_points points, ordered by triangle.  prefix_t = the sum from 0 of the areas up to t (as
+ *     kpx_mesh_surface_area); upto_t = llround(prefix_t / total * n_points), the last n_points; point p lies in triangle #{upto_t <= p}.
+ *     Philox-4x32-10, counter (p lo, p hi, 0x4D534D50, 0), key = seed: r1 = ((w1 << 32 | w0) >> 11) 2^-53, r2 from w3:w2; q = sqrt(r1),
+ *     a = 1 - q, b = q (1 - r2), c = q r2; out = (a v0 + b v1) + c v2 as float32, colours (optional) alike, normals (optional) alike
+ *     from vertex_normals, else the row of triangle_normals.  *d_total (f64, device) = total; nothing is written unless total > 0. */
+#define KPX_MESH_FLAG_REFERENCED 0
+#define KPX_MESH_FLAG_DEGENERATE 1
+#define KPX_MESH_FLAG_INDICES 2
+#define KPX_MESH_SMOOTH_SIMPLE 0
+#define KPX_MESH_SMOOTH_LAPLACIAN 1
+#define KPX_MESH_SMOOTH_TAUBIN 2
+size_t kpx_mesh_adjacency_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_adjacency(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t *out_offsets, int32_t *out_neighbours,
+                       int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_mesh_edges_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_non_manifold_edges(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t allow_boundary_edges,
+                                int32_t *out_edges, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_mesh_cluster_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_cluster_triangles(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int32_t *out_clusters,
+                               int32_t *out_n_triangles, double *out_area, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_mesh_flags(int32_t kind, const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, const int64_t *indices, int64_t n_indices,
+                   uint8_t *out_flags, int64_t n_flags, void *stream);
+size_t kpx_mesh_select_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_select_triangles(const int32_t *triangles, const float *triangle_normals, int64_t n_triangles, const uint8_t *flags, int32_t invert,
+                              int32_t *out_triangles, float *out_triangle_normals, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_mesh_select_vertices(const float *vertices, const float *colors, const float *normals, int64_t n_vertices, const int32_t *triangles,
+                             const float *triangle_normals, int64_t n_triangles, const uint8_t *flags, int32_t invert, float *out_vertices,
+                             float *out_colors, float *out_normals, int32_t *out_triangles, float *out_triangle_normals, int32_t *d_counts, void *ws,
+                             size_t ws_bytes, void *stream);
+size_t kpx_mesh_smooth_workspace_bytes(int64_t n_vertices);
+int kpx_mesh_smooth(const float *vertices, const float *normals, const float *colors, int64_t n_vertices, const int32_t *offsets,
+                    const int32_t *neighbours, int64_t n_neighbours, int32_t method, int32_t iterations, double lambda_filter, double mu,
+                    float *out_vertices, float *out_normals, float *out_colors, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_mesh_sample_workspace_bytes(int64_t n_triangles);
+int kpx_mesh_sample_points(const float *vertices, const float *colors, const float *vertex_normals, const float *triangle_normals,
+                           int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int64_t n_points, uint64_t seed, float *out_points,
+                           float *out_colors, float *out_normals, double *d_total, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- occupancy grids ([O3D] geometry.VoxelGrid; arithmetic contract AC10) ---------------------------------------- */
 /* A grid is caller-owned: keys u64 [M], strictly ascending, key = gx << 42 | gy << 21 | gz with every index in [0, 2^21), and colors
  * f32 [M][3]; voxel g covers h_origin + g voxel .. h_origin + (g + 1) voxel.  All decisions are fp64.

@@ -169,6 +169,20 @@ SIGNATURES = {
     "kpx_mesh_normals_workspace_bytes": (_sz, [_i64, _i64]),
     "kpx_mesh_normals": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_mesh_surface_area": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "kpx_mesh_adjacency_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_adjacency": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_edges_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_non_manifold_edges": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_cluster_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_cluster_triangles": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_flags": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "kpx_mesh_select_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_select_triangles": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_select_vertices": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_smooth_workspace_bytes": (_sz, [_i64]),
+    "kpx_mesh_smooth": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_sample_workspace_bytes": (_sz, [_i64]),
+    "kpx_mesh_sample_points": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_voxelgrid_from_cloud_workspace_bytes": (_sz, [_i64]),
     "kpx_voxelgrid_from_cloud": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_voxelgrid_dense": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),

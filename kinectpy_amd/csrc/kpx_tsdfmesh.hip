@@ -1,5 +1,5 @@
-// kpx_tsdfmesh.hip -- triangle meshes: marching cubes over a uniform TSDF volume ([O3D] UniformTSDFVolume.extract_triangle_mesh;
-// arithmetic contract AC12) and the normals and surface area of any triangle mesh.
+// kpx_tsdfmesh.hip -- marching cubes over a uniform TSDF volume ([O3D] UniformTSDFVolume.extract_triangle_mesh; arithmetic contract
+// AC12).  The operators on the extracted mesh are kpx_mesh.hip's.
 //
 // Extraction keeps the shape of the point-cloud extraction of kpx_tsdf.hip: count, one host read, fill; no atomics, every output
 // slot has one owner.  Workspace, carried from count to fill:
@@ -252,129 +252,6 @@ void mc_carve(Arena &a, int32_t res, McScratch *s)
     s->toff = a.get<int64_t>((size_t)s->nchunks + 1);
 }
 
-// ---- normals and area of a triangle mesh -----------------------------------------------------------------------------------------
-// AC12: n = (v1 - v0) x (v2 - v0) in fp64 from the float32 vertices, each component a b - c d.  A triangle with an index outside
-// [0, nv) reads nothing and has n = 0 (callers reject such meshes first).
-__device__ __forceinline__ void mesh_cross(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t t, double n[3])
-{
-    const int32_t i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-    n[0] = n[1] = n[2] = 0.0;
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return;
-    double e1[3], e2[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double o = (double)v[3 * (int64_t)i0 + k];
-        e1[k] = (double)v[3 * (int64_t)i1 + k] - o;
-        e2[k] = (double)v[3 * (int64_t)i2 + k] - o;
-    }
-    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-}
-__device__ __forceinline__ double mesh_norm(const double n[3]) { return sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]); }
-// n / |n|, the zero vector -> (0, 0, 1) ([O3D] NormalizeNormals), rounded to float32 at the store
-__device__ __forceinline__ void mesh_store_normal(const double n[3], bool normalized, float *__restrict__ out)
-{
-    if (!normalized) {
-        out[0] = (float)n[0]; out[1] = (float)n[1]; out[2] = (float)n[2];
-        return;
-    }
-    const double len = mesh_norm(n);
-    if (len == 0.0) {
-        out[0] = 0.0f; out[1] = 0.0f; out[2] = 1.0f;
-        return;
-    }
-    out[0] = (float)(n[0] / len); out[1] = (float)(n[1] / len); out[2] = (float)(n[2] / len);
-}
-
-// n64 (fp64 [nt][3], may be null): the unnormalised normals the vertex sums read; pairs (may be null): the identity values of the
-// 3 nt (vertex, triangle corner) pairs for the sort
-__global__ __launch_bounds__(256) void mesh_triangle_normals_kernel(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t nt,
-                                                                    int normalized, float *__restrict__ out, double *__restrict__ n64, int32_t *__restrict__ pairs)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nt) return;
-    double n[3];
-    mesh_cross(v, nv, tri, t, n);
-    if (out) mesh_store_normal(n, normalized != 0, out + 3 * t);
-    if (n64) { n64[3 * t] = n[0]; n64[3 * t + 1] = n[1]; n64[3 * t + 2] = n[2]; }
-    if (pairs) { pairs[3 * t] = (int32_t)(3 * t); pairs[3 * t + 1] = (int32_t)(3 * t + 1); pairs[3 * t + 2] = (int32_t)(3 * t + 2); }
-}
-
-// keys: the 3 nt vertex indices sorted (stable: equal vertices keep ascending pair = triangle order), vals: their pair numbers.
-// One thread per vertex walks its segment in order: the sum from 0 in ascending triangle index, whatever the segment's length.
-__global__ __launch_bounds__(256) void mesh_vertex_normals_kernel(const uint32_t *__restrict__ keys, const int32_t *__restrict__ vals, int64_t npairs,
-                                                                  const double *__restrict__ n64, int64_t nv, int normalized, float *__restrict__ out)
-{
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv) return;
-    int64_t lo = 0, hi = npairs;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    double acc[3] = { 0.0, 0.0, 0.0 };
-    for (int64_t j = lo; j < npairs && (int64_t)keys[j] == v; ++j) {
-        const int64_t t = (int64_t)(vals[j] / 3);
-        acc[0] = acc[0] + n64[3 * t];
-        acc[1] = acc[1] + n64[3 * t + 1];
-        acc[2] = acc[2] + n64[3 * t + 2];
-    }
-    mesh_store_normal(acc, normalized != 0, out + 3 * v);
-}
-
-// the sum over the triangles, ascending, of |n| / 2 in fp64.  The order is the contract, so the additions are one chain; everything
-// else is kept off it: one block computes the terms of 1024 triangles at a time into LDS (the gathers of the next batch are in flight
-// while the current one is summed), and its first wave adds the current batch in order.
-constexpr int kAreaThreads = 1024;
-__global__ __launch_bounds__(kAreaThreads) void mesh_area_kernel(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t nt,
-                                                                 double *__restrict__ out)
-{
-    __shared__ double sh[2][kAreaThreads];
-    auto term = [&](int64_t t) {
-        double half = 0.0;
-        if (t < nt) {
-            double n[3];
-            mesh_cross(v, nv, tri, t, n);
-            half = mesh_norm(n) * 0.5;
-        }
-        return half;
-    };
-    sh[0][threadIdx.x] = term(threadIdx.x);
-    __syncthreads();
-    double s = 0.0;
-    int cur = 0;
-    for (int64_t b = 0; b < nt; b += kAreaThreads, cur ^= 1) {
-        const double next = term(b + kAreaThreads + threadIdx.x);
-        if (threadIdx.x < 64) {
-            const int cnt = nt - b < kAreaThreads ? (int)(nt - b) : kAreaThreads;
-#pragma unroll 16
-            for (int i = 0; i < cnt; ++i) s = s + sh[cur][i];
-        }
-        sh[cur ^ 1][threadIdx.x] = next;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = s;
-}
-
-struct MeshNormalScratch {
-    double *n64;
-    uint32_t *keys_out;
-    int32_t *vals_in, *vals_out;
-    void *tmp;
-    size_t tmp_bytes;
-};
-void mesh_normals_carve(Arena &a, int64_t nt, MeshNormalScratch *s)
-{
-    const size_t t = (size_t)(nt > 0 ? nt : 1), p = 3 * t;
-    s->n64 = a.get<double>(3 * t);
-    s->keys_out = a.get<uint32_t>(p);
-    s->vals_in = a.get<int32_t>(p);
-    s->vals_out = a.get<int32_t>(p);
-    s->tmp_bytes = memo_bytes(10, (int64_t)p, [&] { size_t b = 0; (void)sort_pairs<uint32_t>(nullptr, b, s->keys_out, s->keys_out, s->vals_in, s->vals_out, (int64_t)p, 32, (hipStream_t) nullptr); return b; });
-    s->tmp = a.get<char>(s->tmp_bytes);
-}
-
 constexpr int64_t kMeshMax = 2147483647;        // int32 indices
 
 }  // namespace
@@ -434,61 +311,6 @@ KPX_EXPORT int kpx_tsdf_mesh_fill(const float *volume, const float *color, int32
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kMcWaves)), dim3(kMcWaves * 64), 0, st, reinterpret_cast<const float2 *>(volume),
                        (const uint8_t *)s.codes, resolution, s.nvox, s.nchunks, (const McGroup *)s.groups, (const int64_t *)s.voff, (const int64_t *)s.toff, f);
-    KPX_LAUNCH_CHECK();
-    return KPX_OK;
-}
-
-KPX_EXPORT size_t kpx_mesh_normals_workspace_bytes(int64_t n_vertices, int64_t n_triangles)
-{
-    if (n_vertices < 0 || n_triangles < 0 || n_vertices > kMeshMax || 3 * n_triangles > kMeshMax) return 0;
-    Arena a(nullptr, 0);
-    MeshNormalScratch s;
-    mesh_normals_carve(a, n_triangles, &s);
-    return a.off;
-}
-
-KPX_EXPORT int kpx_mesh_normals(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int32_t normalized,
-                                float *out_triangle_normals, float *out_vertex_normals, void *ws, size_t ws_bytes, void *stream)
-{
-    KPX_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "kpx_mesh_normals: negative count");
-    if (n_vertices > kMeshMax || 3 * n_triangles > kMeshMax)
-        return fail(KPX_ERR_RANGE, "kpx_mesh_normals: %lld vertices, %lld triangles: at most 2^31 - 1 vertices and triangle corners", (long long)n_vertices,
-                    (long long)n_triangles);
-    const bool want_v = out_vertex_normals && n_vertices > 0, want_t = out_triangle_normals && n_triangles > 0;
-    if (!want_v && !want_t) return KPX_OK;
-    KPX_REQUIRE((n_triangles == 0 || (vertices && triangles)) && (!want_v || ws), "kpx_mesh_normals: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    MeshNormalScratch s{};
-    if (want_v) {
-        Arena a(ws, ws_bytes);
-        mesh_normals_carve(a, n_triangles, &s);
-        KPX_ARENA_CHECK(a);
-    }
-    const int64_t npairs = 3 * n_triangles;
-    if (n_triangles > 0) {
-        hipLaunchKernelGGL(mesh_triangle_normals_kernel, dim3((unsigned)cdiv(n_triangles, 256)), dim3(256), 0, st, vertices, n_vertices, triangles, n_triangles,
-                           (int)normalized, want_t ? out_triangle_normals : (float *)nullptr, want_v ? s.n64 : (double *)nullptr,
-                           want_v ? s.vals_in : (int32_t *)nullptr);
-        KPX_LAUNCH_CHECK();
-    }
-    if (!want_v) return KPX_OK;
-    if (n_triangles > 0) {
-        int bits = 1;
-        while (bits < 32 && ((int64_t)1 << bits) < n_vertices) ++bits;
-        size_t bytes = s.tmp_bytes;
-        KPX_HIP(sort_pairs<uint32_t>(s.tmp, bytes, reinterpret_cast<const uint32_t *>(triangles), s.keys_out, s.vals_in, s.vals_out, npairs, bits, st));
-    }
-    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)cdiv(n_vertices, 256)), dim3(256), 0, st, (const uint32_t *)s.keys_out, (const int32_t *)s.vals_out,
-                       npairs, (const double *)s.n64, n_vertices, (int)normalized, out_vertex_normals);
-    KPX_LAUNCH_CHECK();
-    return KPX_OK;
-}
-
-KPX_EXPORT int kpx_mesh_surface_area(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_area, void *stream)
-{
-    KPX_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "kpx_mesh_surface_area: negative count");
-    KPX_REQUIRE(d_area && (n_triangles == 0 || (vertices && triangles)), "kpx_mesh_surface_area: null pointer");
-    hipLaunchKernelGGL(mesh_area_kernel, dim3(1), dim3(kAreaThreads), 0, (hipStream_t)stream, vertices, n_vertices, triangles, n_triangles, d_area);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -849,11 +849,26 @@ class Vector3iVector:
         return np.asarray(self)[i]
 
 
+class FilterScope(enum.Enum):
+    """[O3D] geometry.FilterScope: the arrays a TriangleMesh.filter_smooth_* call filters"""
+    All = 0
+    Color = 1
+    Normal = 2
+    Vertex = 3
+
+
 class TriangleMesh:
     """[O3D] geometry.TriangleMesh, the part a fused surface needs: float32 (V, 3) vertices, int32 (T, 3) triangles and the optional
     vertex colours, vertex normals and triangle normals, all device tensors; normals and area are arithmetic contract AC12
-    (kpx_mesh_normals, kpx_mesh_surface_area).  Simplification, clean-up, sampling and the other Open3D methods are not built."""
+    (kpx_mesh_normals, kpx_mesh_surface_area).  The clean-up path is arithmetic contract AC13, all on the device:
+    adjacency (compute_adjacency_list), edges (get_non_manifold_edges, is_edge_manifold), cluster_connected_triangles, ordered removal
+    (remove_triangles_by_mask / _by_index, remove_vertices_by_mask / _by_index, remove_unreferenced_vertices,
+    remove_degenerate_triangles, select_by_index), smoothing (filter_smooth_simple / _laplacian / _taubin) and sample_points_uniformly.
+    Not built: remove_duplicated_vertices, remove_duplicated_triangles, the simplification methods, is_watertight,
+    sample_points_poisson_disk, crop."""
     _bounds = None
+    _adj = None               # (offsets, neighbours) device tensors: compute_adjacency_list's CSR
+    _adj_sets = None          # the same as Python sets, built on first use of adjacency_list
 
     def __init__(self, vertices=None, triangles=None):
         self._vert = Vector3dVector(vertices).t
@@ -882,6 +897,7 @@ class TriangleMesh:
     @triangles.setter
     def triangles(self, v):
         self._tri = Vector3iVector(v).t.to(L.device())
+        self._adj = self._adj_sets = None
 
     def _optional(name):
         def get(self):
@@ -964,3 +980,109 @@ class TriangleMesh:
             if self.has_triangle_normals():
                 ops.rotate(self._tnrm, T, out=self._tnrm)
         return self
+
+    # ---- clean-up (AC13) ------------------------------------------------------------------------
+    def compute_adjacency_list(self):
+        """[O3D] ComputeAdjacencyList: N(v) as CSR on the device (ops.mesh_adjacency); adjacency_list turns it into sets on the host"""
+        self._adj, self._adj_sets = ops.mesh_adjacency(self._vert, self._tri), None
+        return self
+
+    def has_adjacency_list(self):
+        return self.has_vertices() and self._adj is not None and self._adj[0].shape[0] == self._vert.shape[0] + 1
+
+    @property
+    def adjacency_list(self):
+        """a list of V Python sets, as in Open3D; empty before compute_adjacency_list()"""
+        if not self.has_adjacency_list():
+            return []
+        if self._adj_sets is None:
+            off, nb = (t.cpu().numpy() for t in self._adj)
+            self._adj_sets = [set(nb[off[v]:off[v + 1]].tolist()) for v in range(len(off) - 1)]
+        return self._adj_sets
+
+    def get_non_manifold_edges(self, allow_boundary_edges=True):
+        """-> Vector2iVector of ascending (min, max) vertex pairs"""
+        return Vector2iVector(ops.mesh_non_manifold_edges(self._vert, self._tri, allow_boundary_edges).cpu().numpy())
+
+    def is_edge_manifold(self, allow_boundary_edges=True):
+        return ops.mesh_non_manifold_edges(self._vert, self._tri, allow_boundary_edges).shape[0] == 0
+
+    def cluster_connected_triangles(self):
+        """-> (triangle_clusters int32 (T,), cluster_n_triangles int32 (C,), cluster_area float64 (C,)) device tensors; clusters are
+        numbered by their smallest triangle, as Open3D's search from ascending seeds numbers them"""
+        return ops.mesh_cluster_triangles(self._vert, self._tri)
+
+    def _set_triangles(self, tri, tnrm):
+        self._tri, self._tnrm, self._adj, self._adj_sets = tri, tnrm, None, None
+        return self
+
+    def _remove_triangles(self, flags):
+        tn = self._tnrm if self.has_triangle_normals() else None
+        return self._set_triangles(*ops.mesh_select_triangles(self._tri, flags, True, tn))
+
+    def remove_triangles_by_mask(self, triangle_mask):
+        """True removes the triangle; the triangle normals follow.  In place, returns self."""
+        return self._remove_triangles(ops._mesh_flag_bytes("remove_triangles_by_mask", triangle_mask, self._tri.shape[0]))
+
+    def remove_triangles_by_index(self, triangle_indices):
+        return self._remove_triangles(ops.mesh_flags("indices", None, 0, triangle_indices, self._tri.shape[0]))
+
+    def remove_degenerate_triangles(self):
+        return self._remove_triangles(ops.mesh_flags("degenerate", self._tri, self._vert.shape[0]))
+
+    def _select_vertices(self, flags, invert, into=None):
+        m = self if into is None else into
+        col = self._vcol if self.has_vertex_colors() else None
+        nrm = self._vnrm if self.has_vertex_normals() else None
+        tn = self._tnrm if self.has_triangle_normals() else None
+        m._vert, m._vcol, m._vnrm, tri, tn = ops.mesh_select_vertices(self._vert, self._tri, flags, invert, col, nrm, tn)
+        m._bounds = None
+        return m._set_triangles(tri, tn)
+
+    def remove_vertices_by_mask(self, vertex_mask):
+        """True removes the vertex and every triangle that names it; the kept vertices keep their order and are renumbered by rank,
+        colours, vertex normals and triangle normals follow.  In place, returns self."""
+        return self._select_vertices(ops._mesh_flag_bytes("remove_vertices_by_mask", vertex_mask, self._vert.shape[0]), True)
+
+    def remove_vertices_by_index(self, vertex_indices):
+        return self._select_vertices(ops.mesh_flags("indices", None, 0, vertex_indices, self._vert.shape[0]), True)
+
+    def remove_unreferenced_vertices(self):
+        return self._select_vertices(ops.mesh_flags("referenced", self._tri, self._vert.shape[0]), False)
+
+    def select_by_index(self, indices, cleanup=True):
+        """a new mesh of the named vertices, IN VERTEX ORDER (duplicates count once; Open3D keeps the list's order), with the triangles
+        whose three corners are named; cleanup drops the vertices those triangles leave unreferenced"""
+        m = self._select_vertices(ops.mesh_flags("indices", None, 0, indices, self._vert.shape[0]), False, TriangleMesh.__new__(TriangleMesh))
+        return m.remove_unreferenced_vertices() if cleanup else m
+
+    def _smooth(self, method, number_of_iterations, lambda_filter, mu, filter_scope):
+        scope = FilterScope(filter_scope)
+        on = (scope in (FilterScope.All, FilterScope.Vertex), scope in (FilterScope.All, FilterScope.Normal), scope in (FilterScope.All, FilterScope.Color))
+        nrm = self._vnrm if self.has_vertex_normals() else None
+        col = self._vcol if self.has_vertex_colors() else None
+        v, n, c = ops.mesh_smooth(self._vert, self._tri, method, number_of_iterations, lambda_filter, mu, nrm, col, on)
+        return TriangleMesh._make(v, self._tri.clone(), c, n)              # mesh_smooth's outputs share no storage with its inputs
+
+    def filter_smooth_simple(self, number_of_iterations=1, filter_scope=FilterScope.All):
+        """a new mesh (same triangles, no triangle normals): every vertex value becomes the mean of itself and its neighbours'"""
+        return self._smooth("simple", number_of_iterations, 0.0, 0.0, filter_scope)
+
+    def filter_smooth_laplacian(self, number_of_iterations=1, lambda_filter=0.5, filter_scope=FilterScope.All):
+        return self._smooth("laplacian", number_of_iterations, lambda_filter, 0.0, filter_scope)
+
+    def filter_smooth_taubin(self, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, filter_scope=FilterScope.All):
+        """each iteration is a Laplacian step with lambda_filter, then one with mu (negative: it undoes the shrinkage)"""
+        return self._smooth("taubin", number_of_iterations, lambda_filter, mu, filter_scope)
+
+    def sample_points_uniformly(self, number_of_points=100, use_triangle_normal=False, seed=0):
+        """-> PointCloud of number_of_points points, ordered by triangle, each triangle's share by its area; colours are interpolated
+        when the mesh has them; normals are interpolated vertex normals, or with use_triangle_normal the triangle's own (computed
+        first if absent, as Open3D does).  Seeded by Philox, not mt19937: the points inside a triangle differ from Open3D's."""
+        if use_triangle_normal and self.has_triangles() and not self.has_triangle_normals():
+            self.compute_triangle_normals(True)
+        vn = self._vnrm if self.has_vertex_normals() and not use_triangle_normal else None
+        tn = self._tnrm if use_triangle_normal and self.has_triangle_normals() else None
+        col = self._vcol if self.has_vertex_colors() else None
+        pts, c, n = ops.mesh_sample_points(self._vert, self._tri, number_of_points, seed, col, vn, tn)
+        return PointCloud._make(pts, c, n)

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import ops
 from .geometry import (Image, ImageFilterType, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
-                       OrientedBoundingBox, PointCloud, RGBDImage, TriangleMesh, Vector2iVector, Vector3dVector, Vector3iVector, Voxel,
+                       OrientedBoundingBox, PointCloud, RGBDImage, TriangleMesh, FilterScope, Vector2iVector, Vector3dVector, Vector3iVector, Voxel,
                        VoxelGrid, _off_path)
 from . import integration as _integration
 from . import odometry as _odometry
@@ -449,7 +449,7 @@ class PinholeCameraParameters:
 geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=OrientedBoundingBox, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid,
                                  KDTreeSearchParamKNN=KDTreeSearchParamKNN, KDTreeSearchParamRadius=KDTreeSearchParamRadius, KDTreeFlann=KDTreeFlann,
                                  Image=Image, ImageFilterType=ImageFilterType, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
-                                 TriangleMesh=TriangleMesh,
+                                 TriangleMesh=TriangleMesh, FilterScope=FilterScope,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
 camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic, PinholeCameraParameters=PinholeCameraParameters)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Vector3iVector=Vector3iVector,

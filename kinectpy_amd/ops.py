@@ -1237,15 +1237,19 @@ def tsdf_extract_mesh(volume, color, resolution, voxel_length, origin):
 
 
 def _mesh_arrays(who, vertices, triangles):
-    """device float32 (V, 3) and int32 (T, 3); an index outside [0, V) raises here, before any kernel sees it (min and max are taken
-    on the device)"""
+    """device float32 (V, 3) and int32 (T, 3); an index outside [0, V) raises here, before any kernel sees it"""
     vert = _dev(vertices, torch.float32).reshape(-1, 3)
     tri = _dev(triangles, torch.int32).reshape(-1, 3)
+    _mesh_index_check(who, tri, vert.shape[0])
+    return vert, tri
+
+
+def _mesh_index_check(who, tri, nv):
+    """min and max are taken on the device: two host reads"""
     if tri.shape[0]:
         lo, hi = int(tri.min()), int(tri.max())
-        if lo < 0 or hi >= vert.shape[0]:
-            raise L.KinectPxError(f"{who}: triangle index out of range [0, {vert.shape[0]})")
-    return vert, tri
+        if lo < 0 or hi >= nv:
+            raise L.KinectPxError(f"{who}: triangle index out of range [0, {nv})")
 
 
 def mesh_normals(vertices, triangles, normalized=True, want_triangle=True, want_vertex=True):
@@ -1268,6 +1272,180 @@ def mesh_surface_area(vertices, triangles):
     out = torch.empty(1, dtype=torch.float64, device=vert.device)
     L.check(lib.kpx_mesh_surface_area(L.ptr(vert), vert.shape[0], L.ptr(tri), tri.shape[0], L.ptr(out), L.stream_ptr()))
     return float(out.item())
+
+
+# ---- mesh clean-up (AC13) -------------------------------------------------------------------------------
+MESH_FLAGS = {"referenced": 0, "degenerate": 1, "indices": 2}          # KPX_MESH_FLAG_* (include/kinectpx.h)
+MESH_SMOOTH = {"simple": 0, "laplacian": 1, "taubin": 2}               # KPX_MESH_SMOOTH_*
+
+
+def _mesh_rows(who, t, n, name):
+    """an optional per-vertex or per-triangle float32 (n, 3) array on the device, or None"""
+    if t is None:
+        return None
+    t = _dev(t, torch.float32).reshape(-1, 3)
+    if t.shape[0] != n:
+        raise L.KinectPxError(f"{who}: {t.shape[0]} {name} for {n} rows")
+    return t
+
+
+def _mesh_count(who, cnt):
+    """the one host read of a counted operator; a negative count is a kpx_status the kernels left there"""
+    c = [int(x) for x in cnt.tolist()]
+    if min(c) < 0:
+        raise L.KinectPxError(f"{who}: the union-find pass gave up (kpx_status {min(c)})")
+    return c
+
+
+def mesh_adjacency(vertices, triangles):
+    """AC13's vertex adjacency as CSR -> (offsets int32 (V + 1,), neighbours int32 (offsets[V],)): row v holds, ascending, the distinct
+    vertices that share a corner pair of some triangle with v.  One host read (the length of `neighbours`)."""
+    off, nb, cnt = _mesh_adjacency(*_mesh_arrays("mesh_adjacency", vertices, triangles))
+    return off, nb[:_mesh_count("mesh_adjacency", cnt)[0]]
+
+
+def _mesh_adjacency(vert, tri):
+    """-> (offsets, neighbours with room for 6 T entries, their number int32 (1,) on the device): no host read"""
+    lib = L.load()
+    nv, nt = vert.shape[0], tri.shape[0]
+    off = torch.empty(nv + 1, dtype=torch.int32, device=vert.device)
+    nb = torch.empty(6 * nt, dtype=torch.int32, device=vert.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_adjacency_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_adjacency(L.ptr(tri), nv, nt, L.ptr(off), L.ptr(nb), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return off, nb, cnt
+
+
+def mesh_non_manifold_edges(vertices, triangles, allow_boundary_edges=True):
+    """[O3D] get_non_manifold_edges -> int32 (E, 2) ascending (min, max): the edges that more than two triangles share, with
+    allow_boundary_edges=False also those that only one has.  One host read."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_non_manifold_edges", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    out = torch.empty((3 * nt, 2), dtype=torch.int32, device=vert.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_edges_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_non_manifold_edges(L.ptr(tri), nv, nt, int(bool(allow_boundary_edges)), L.ptr(out), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return out[:_mesh_count("mesh_non_manifold_edges", cnt)[0]]
+
+
+def mesh_cluster_triangles(vertices, triangles):
+    """[O3D] cluster_connected_triangles -> (cluster of each triangle int32 (T,), triangles per cluster int32 (C,), area per cluster
+    float64 (C,)) device tensors; clusters are numbered by their smallest triangle index.  One host read (C)."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_cluster_triangles", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    lab = torch.empty(nt, dtype=torch.int32, device=vert.device)
+    num = torch.empty(nt, dtype=torch.int32, device=vert.device)
+    area = torch.empty(nt, dtype=torch.float64, device=vert.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_cluster_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_cluster_triangles(L.ptr(vert), nv, L.ptr(tri), nt, L.ptr(lab), L.ptr(num), L.ptr(area), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    c = _mesh_count("mesh_cluster_triangles", cnt)[0]
+    return lab, num[:c], area[:c]
+
+
+def mesh_flags(kind, triangles, n_vertices, indices=None, n=None):
+    """uint8 flags on the device: "referenced" (V,) the vertices some triangle names; "degenerate" (T,) the triangles with two equal
+    indices; "indices" (n,) the positions an index list names (values outside [0, n) are ignored).  "referenced" is indexed by the
+    triangles' corners and so holds them to [0, V) first, as _mesh_arrays does; the other two read no vertex."""
+    lib = L.load()
+    tri = _dev(triangles, torch.int32).reshape(-1, 3) if triangles is not None else None
+    if kind == "referenced" and tri is not None:
+        _mesh_index_check("mesh_flags", tri, int(n_vertices))
+    idx = _dev(indices, torch.int64).reshape(-1) if indices is not None else None
+    nt = 0 if tri is None else tri.shape[0]
+    size = {"referenced": int(n_vertices), "degenerate": nt, "indices": 0 if n is None else int(n)}[kind]
+    out = torch.empty(size, dtype=torch.uint8, device=L.device())
+    L.check(lib.kpx_mesh_flags(MESH_FLAGS[kind], L.ptr(tri), int(n_vertices), nt, L.ptr(idx), 0 if idx is None else idx.numel(), L.ptr(out), size,
+                               L.stream_ptr()))
+    return out
+
+
+def _mesh_flag_bytes(who, flags, n):
+    f = flags if isinstance(flags, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(flags).astype(bool)))
+    f = f.reshape(-1)
+    if f.shape[0] != n:
+        raise L.KinectPxError(f"{who}: a mask of {f.shape[0]} entries for {n} rows")
+    return _dev(f, torch.uint8)
+
+
+def mesh_select_triangles(triangles, flags, invert=False, triangle_normals=None):
+    """the triangles whose flag is set (invert: not set), in order, with their normals -> (triangles, normals | None).  One host read."""
+    lib = L.load()
+    tri = _dev(triangles, torch.int32).reshape(-1, 3)
+    nt = tri.shape[0]
+    f = _mesh_flag_bytes("mesh_select_triangles", flags, nt)
+    tn = _mesh_rows("mesh_select_triangles", triangle_normals, nt, "triangle normals")
+    otri, otn = torch.empty_like(tri), None if tn is None else torch.empty_like(tn)
+    cnt = torch.empty(1, dtype=torch.int32, device=tri.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_select_workspace_bytes(0, nt))
+    L.check(lib.kpx_mesh_select_triangles(L.ptr(tri), L.ptr(tn), nt, L.ptr(f), int(bool(invert)), L.ptr(otri), L.ptr(otn), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    c = _mesh_count("mesh_select_triangles", cnt)[0]
+    return otri[:c], None if otn is None else otn[:c]
+
+
+def mesh_select_vertices(vertices, triangles, flags, invert=False, colors=None, normals=None, triangle_normals=None):
+    """the vertices whose flag is set (invert: not set), in order, renumbered by rank, with their colours and normals; the triangles
+    whose three corners stay, in order, with their normals -> (vertices, colours | None, normals | None, triangles, triangle normals |
+    None).  One host read (both counts)."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_select_vertices", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    f = _mesh_flag_bytes("mesh_select_vertices", flags, nv)
+    col, nrm = _mesh_rows("mesh_select_vertices", colors, nv, "colours"), _mesh_rows("mesh_select_vertices", normals, nv, "normals")
+    tn = _mesh_rows("mesh_select_vertices", triangle_normals, nt, "triangle normals")
+    like = lambda t: None if t is None else torch.empty_like(t)
+    overt, ocol, onrm, otri, otn = like(vert), like(col), like(nrm), like(tri), like(tn)
+    cnt = torch.empty(2, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_select_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_select_vertices(L.ptr(vert), L.ptr(col), L.ptr(nrm), nv, L.ptr(tri), L.ptr(tn), nt, L.ptr(f), int(bool(invert)), L.ptr(overt),
+                                         L.ptr(ocol), L.ptr(onrm), L.ptr(otri), L.ptr(otn), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    cv, ct = _mesh_count("mesh_select_vertices", cnt)
+    cut = lambda t, c: None if t is None else t[:c]
+    return cut(overt, cv), cut(ocol, cv), cut(onrm, cv), cut(otri, ct), cut(otn, ct)
+
+
+def mesh_smooth(vertices, triangles, method, iterations, lambda_filter=0.5, mu=-0.53, normals=None, colors=None, scope=(True, True, True)):
+    """AC13's smoothing: method "simple" | "laplacian" | "taubin"; scope = (vertices, normals, colours): which of the arrays are
+    filtered -> (vertices, normals | None, colours | None) float32, every one a new tensor with storage of its own: the filtered
+    arrays, and copies of the others.  No host read beyond the index check's: the adjacency stays on the device."""
+    lib = L.load()
+    if int(iterations) < 0:
+        raise L.KinectPxError("filter_smooth: number_of_iterations must be non-negative")
+    vert, tri = _mesh_arrays("mesh_smooth", vertices, triangles)
+    nv = vert.shape[0]
+    nrm, col = _mesh_rows("mesh_smooth", normals, nv, "normals"), _mesh_rows("mesh_smooth", colors, nv, "colours")
+    off, nb, _ = _mesh_adjacency(vert, tri)
+    out = [torch.empty_like(t) if t is not None and on else None for t, on in zip((vert, nrm, col), scope)]
+    ws, wsz = L.workspace(lib.kpx_mesh_smooth_workspace_bytes(nv))
+    L.check(lib.kpx_mesh_smooth(L.ptr(vert), L.ptr(nrm), L.ptr(col), nv, L.ptr(off), L.ptr(nb), nb.numel(), MESH_SMOOTH[method], int(iterations),
+                                float(lambda_filter), float(mu), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), ws, wsz, L.stream_ptr()))
+    return tuple(o if o is not None else (None if t is None else t.clone()) for o, t in zip(out, (vert, nrm, col)))
+
+
+def mesh_sample_points(vertices, triangles, number_of_points, seed=0, colors=None, vertex_normals=None, triangle_normals=None):
+    """AC13's sample_points_uniformly -> (points, colours | None, normals | None) float32 (N, 3), ordered by triangle; normals are
+    interpolated from vertex_normals or copied from triangle_normals (give one of them).  One host read (the total area)."""
+    lib = L.load()
+    n = int(number_of_points)
+    if n <= 0:
+        raise L.KinectPxError("sample_points_uniformly: number_of_points must be positive")
+    vert, tri = _mesh_arrays("mesh_sample_points", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    if nv == 0 or nt == 0:
+        raise L.KinectPxError("sample_points_uniformly: the mesh has no triangles")
+    col, vn = _mesh_rows("mesh_sample_points", colors, nv, "colours"), _mesh_rows("mesh_sample_points", vertex_normals, nv, "normals")
+    tn = _mesh_rows("mesh_sample_points", triangle_normals, nt, "triangle normals") if vn is None else None
+    new = lambda on: torch.empty((n, 3), dtype=torch.float32, device=vert.device) if on else None
+    pts, ocol, onrm = new(True), new(col is not None), new(vn is not None or tn is not None)
+    total = torch.empty(1, dtype=torch.float64, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_sample_workspace_bytes(nt))
+    L.check(lib.kpx_mesh_sample_points(L.ptr(vert), L.ptr(col), L.ptr(vn), L.ptr(tn), nv, L.ptr(tri), nt, n, int(seed) & (2 ** 64 - 1), L.ptr(pts), L.ptr(ocol),
+                                       L.ptr(onrm), L.ptr(total), ws, wsz, L.stream_ptr()))
+    if not float(total.item()) > 0.0:
+        raise L.KinectPxError("sample_points_uniformly: the mesh has no surface area")
+    return pts, ocol, onrm
 
 
 # ---- occupancy grids ------------------------------------------------------------------------------------

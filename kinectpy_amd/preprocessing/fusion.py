@@ -17,13 +17,16 @@ class _Intrinsic:
         self.intrinsic_matrix = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
 
 
-def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0, mesh=False):
+def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0, mesh=False,
+                    min_cluster_triangles=0, taubin_iterations=0):
     """depth: uint16 (S, H W) raw frames (synth.sensor_ring's layout; host or device); rgb: uint8 (S, H W, 3) or None (no colours);
     intrinsic: a PinholeCameraIntrinsic, or None for the Kinect's (synth.FX, FY, CX, CY at synth.W x synth.H); sensor_to_master:
     the S - 1 transforms of the sub sensors (sensor 0 is the master, identity).  The world frame is the master's: sensor s is
     integrated with the extrinsic inv(sensor_to_master[s]) (host float64).  sdf_trunc defaults to 4 voxels.  One integrate_frames
     call and one extraction -> PointCloud with normals (and colours when rgb is given); mesh=True: the surface as a TriangleMesh
-    (extract_triangle_mesh) with vertex normals computed instead."""
+    (extract_triangle_mesh) with vertex normals computed instead.  The mesh's clean-up, both off by default: min_cluster_triangles > 0
+    drops every connected component of fewer triangles (the specks flying pixels leave) and then the vertices nothing names;
+    taubin_iterations > 0 smooths with filter_smooth_taubin's defaults before the normals are computed."""
     if intrinsic is None:
         intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
     n = int(depth.shape[0])
@@ -35,7 +38,13 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     vol = UniformTSDFVolume(length, resolution, sdf_trunc, TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor, origin)
     vol.integrate_frames(depth, rgb, intrinsic, np.stack(extr), depth_scale, depth_trunc)
     if mesh:
-        return vol.extract_triangle_mesh().compute_vertex_normals()
+        m = vol.extract_triangle_mesh()
+        if min_cluster_triangles > 0 and m.has_triangles():
+            cluster, n_triangles, _ = m.cluster_connected_triangles()
+            m.remove_triangles_by_mask(n_triangles[cluster.long()] < int(min_cluster_triangles)).remove_unreferenced_vertices()
+        if taubin_iterations > 0:
+            m = m.filter_smooth_taubin(int(taubin_iterations))
+        return m.compute_vertex_normals()
     return vol.extract_point_cloud()
 
 

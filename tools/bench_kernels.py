@@ -52,12 +52,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
+    ap.add_argument("--mesh", action="store_true", help="only the mesh clean-up rows")
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.tsdf:
         return tsdf_rows(dev, a.quick)
+    if a.mesh:
+        return mesh_rows(dev, a.quick)
     if a.voxelgrid:
         return voxelgrid_rows(dev, a.quick)
     if a.odometry:
@@ -311,6 +314,7 @@ def main():
            ms_per_iteration=round(ms / (r["iterations"] + 1), 4), dense_equivalent_flops=int(dense * (r["iterations"] + 1)),
            **sweep(ops.prof_end()))
     tsdf_rows(dev, a.quick)
+    mesh_rows(dev, a.quick)
     voxelgrid_rows(dev, a.quick)
     odometry_rows(dev, a.quick)
 
@@ -363,6 +367,42 @@ def tsdf_rows(dev, quick):
                 ms, (vp, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "voxels"))
                 report(f"tsdf extract_voxel_point_cloud ({tag})", ms, 8 * res ** 3 + int(vp.shape[0]) * 24, points=int(vp.shape[0]))
             del vol, col
+
+
+def mesh_rows(dev, quick):
+    """The clean-up path on the mesh of the fused ring volume (resolution 512, 256 with --quick), each operator
+    whole: launches, sorts and its host read.  Algorithmic traffic, V vertices, T triangles, E adjacency entries:
+      adjacency   12 T read, 4 (V + 1) + 4 E written
+      clusters    12 T + 12 V read (indices, then the vertices for the areas), 4 T + 12 C written
+      Taubin x10  20 steps, each 24 V read and 24 V written in fp64 plus the 4 E + 4 V of the CSR; 12 V in and out at the ends
+      sampling    12 T + 12 V read for the areas, 12 N written (the corner gathers of N points hit cache)"""
+    S = 4
+    _, depth, _, _, _ = synth.sensor_ring(S, 1)
+    depth_d = [torch.as_tensor(depth[0, s]).to(dev) for s in range(S)]
+    extr = np.stack([np.linalg.inv(synth.camera_pose(g, S)) for g in range(S)])
+    K, origin, length = (synth.FX, synth.FY, synth.CX, synth.CY), (-1000.0, -1100.0, -1000.0), 2000.0
+    res = 256 if quick else 512
+    vl = length / res
+    vol = torch.zeros((res ** 3, 2), dtype=torch.float32, device=dev)
+    ops.tsdf_integrate(vol, None, res, vl, origin, 4 * vl, depth_d, None, synth.W, synth.H, K, extr, 1.0, 6000.0)
+    vert, _, tri = ops.tsdf_extract_mesh(vol, None, res, vl, origin)
+    del vol
+    nv, nt = int(vert.shape[0]), int(tri.shape[0])
+    tag = f"ring mesh of res {res}"
+    ms, (_, nb) = timed(lambda: ops.mesh_adjacency(vert, tri))
+    ne = int(nb.shape[0])
+    report(f"mesh compute_adjacency_list ({tag}; keys + sort of 6 T pairs + unique + offsets + host read)", ms, 12 * nt + 4 * (nv + 1) + 4 * ne, vertices=nv,
+           triangles=nt, entries=ne)
+    ms, (_, num, _) = timed(lambda: ops.mesh_cluster_triangles(vert, tri))
+    nc = int(num.shape[0])
+    report(f"mesh cluster_connected_triangles ({tag}; sort of 3 T edges + union-find + rank + sort by cluster + area chain + host read)", ms,
+           12 * nt + 12 * nv + 4 * nt + 12 * nc, vertices=nv, triangles=nt, clusters=nc)
+    ms, _ = timed(lambda: ops.mesh_smooth(vert, tri, "taubin", 10))
+    report(f"mesh filter_smooth_taubin x10 ({tag}; adjacency + 20 steps)", ms, 12 * nt + 4 * (nv + 1) + 4 * ne + 20 * (48 * nv + 4 * ne + 4 * nv) + 24 * nv,
+           vertices=nv, triangles=nt)
+    ms, _ = timed(lambda: ops.mesh_sample_points(vert, tri, 100000))
+    report(f"mesh sample_points_uniformly 100k ({tag}; area chain + split + points + host read)", ms, 12 * nt + 12 * nv + 12 * 100000, vertices=nv,
+           triangles=nt)
 
 
 def voxelgrid_rows(dev, quick):
