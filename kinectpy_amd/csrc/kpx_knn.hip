@@ -12,7 +12,6 @@
 
 #include "kpx_gridknn.h"
 #include "kpx_morton.h"
-#include "kpx_radix.h"
 #include "kpx_linalg.h"
 
 namespace kpx {
@@ -172,19 +171,19 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
     g->cell_start = a.get<uint32_t>((size_t)kGridMaxCells + 1);
     g->sorted_pts = a.get<float>(nn * 3);
     g->sorted_idx = a.get<int32_t>(nn);
-    uint32_t *keys_in = a.get<uint32_t>(nn), *keys_out = a.get<uint32_t>(nn);
-    g->sorted_keys = keys_out;
-    int32_t *vals_in = a.get<int32_t>(nn);
     double *part = a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    size_t sort_bytes = 0, scan_bytes = 0;
-    sort_bytes = memo_bytes(2, (int64_t)nn, [&] { size_t b = 0; (void)sort_pairs(nullptr, b, keys_in, keys_out, vals_in, g->sorted_idx, (int64_t)nn, 22, st); return b; });
-    scan_bytes = memo_bytes(3, 0, [&] { size_t b = 0; (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, zero, g->cell_start, kGridMaxCells + 1, st); return b; });
-    char *tmp = a.get<char>(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
-    RadixScratch rx{};
-    const bool own_sort = (int64_t)nn > 65536 && (int64_t)nn <= kRadixMaxPairs;     // the sort build's sizes that kpx_radix.h serves
-    // carved for every size (capped at the sort's limit): the workspace a caller sized for a worst-case count then also holds any
-    // smaller cloud's build -- bytes(n) is monotonic (kpx_frame_step sizes one scratch region from the worst case)
-    radix_carve(a, (int64_t)nn <= kRadixMaxPairs ? (int64_t)nn : kRadixMaxPairs, &rx);
+    // the sort build's (cell, point) pairs; the vendor scan of KPX_GRID_SCAN=0 runs in the sort's temporary buffer.  The own radix
+    // sort's scratch is carved for every size (capped at the sort's limit): the workspace a caller sized for a worst-case count then
+    // also holds any smaller cloud's build -- bytes(n) is monotonic (kpx_frame_step sizes one scratch region from the worst case)
+    size_t scan_bytes = memo_bytes(kMemoGridScan, kGridMaxCells + 1, [&] { size_t b = 0; (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, zero, g->cell_start, kGridMaxCells + 1, st); return b; });
+    DeviceSort<uint32_t> sort;
+    SortOptions o;
+    o.vals_out = false;
+    o.radix = kRadixAndVendor;
+    o.tmp_floor = scan_bytes;
+    dsort_carve(a, n, 22, o, &sort);
+    sort.vals_out = g->sorted_idx;
+    g->sorted_keys = sort.keys_out;
     if (a.dry) return KPX_OK;
     KPX_ARENA_CHECK(a);
     double *bbox = part + (size_t)kBboxBlocks * 6;
@@ -204,12 +203,12 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
     int nb = (int)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256));
     // first binning from the bounding-box heuristic, one round of occupancy feedback, then the definitive binning
     hipLaunchKernelGGL(grid_cell_kernel, dim3(nb), dim3(256), 0, st, pts, n, bbox, target_per_cell, cell_cap, (const unsigned long long *)nullptr, g->params,
-                       keys_in, vals_in, count1, fixed_h);
+                       sort.keys_in, sort.vals_in, count1, fixed_h);
     hipLaunchKernelGGL(grid_occupancy_kernel, dim3(1024), dim3(256), 0, st, count1, g->params, sumsq);
     hipLaunchKernelGGL(grid_cell_kernel, dim3(nb), dim3(256), 0, st, pts, n, bbox, target_per_cell, cell_cap, (const unsigned long long *)sumsq, g->params,
-                       keys_in, vals_in, count2, fixed_h);
+                       sort.keys_in, sort.vals_in, count2, fixed_h);
     static const bool vendor_scan = [] { const char *e = getenv("KPX_GRID_SCAN"); return e && e[0] == '0'; }();      // A/B switch
-    if (vendor_scan) KPX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, count2, g->cell_start, cell_cap + 1, st));
+    if (vendor_scan) KPX_HIP(hipcub::DeviceScan::ExclusiveSum(sort.tmp, scan_bytes, count2, g->cell_start, cell_cap + 1, st));
     else
         hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)cdiv((int64_t)cell_cap + 1, kGridScanTile)), dim3(256), 0, st, count2, (int64_t)cell_cap + 1, g->cell_start,
                            scan_states);
@@ -220,16 +219,12 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
     static const bool force_sort = [] { const char *e = getenv("KPX_GRID_SORT"); return e && e[0] == '1'; }();
     const bool by_sort = force_sort || n > 65536;
     if (by_sort) {
-        if (own_sort) {
-            rc = radix_sort_pairs_u32(rx, keys_in, keys_out, vals_in, g->sorted_idx, n, 22, st);
-            if (rc) return rc;
-        } else {
-            KPX_HIP(sort_pairs(tmp, sort_bytes, keys_in, keys_out, vals_in, g->sorted_idx, n, 22, st));
-        }
+        rc = dsort_run(sort, n, 22, st);
+        if (rc) return rc;
         hipLaunchKernelGGL(grid_gather_kernel, dim3(nb), dim3(256), 0, st, pts, n, g->sorted_idx, g->sorted_pts);
     } else {
-        hipLaunchKernelGGL(grid_place_kernel, dim3(nb), dim3(256), 0, st, keys_in, n, g->cell_start, cursor, vals_in);
-        hipLaunchKernelGGL(grid_rank_kernel, dim3(nb), dim3(256), 0, st, pts, n, keys_in, g->cell_start, vals_in, g->sorted_idx, g->sorted_pts);
+        hipLaunchKernelGGL(grid_place_kernel, dim3(nb), dim3(256), 0, st, sort.keys_in, n, g->cell_start, cursor, sort.vals_in);
+        hipLaunchKernelGGL(grid_rank_kernel, dim3(nb), dim3(256), 0, st, pts, n, sort.keys_in, g->cell_start, sort.vals_in, g->sorted_idx, g->sorted_pts);
     }
     KPX_LAUNCH_CHECK();
     return KPX_OK;

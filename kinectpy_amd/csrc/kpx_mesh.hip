@@ -6,7 +6,7 @@
 // then a pass over the sorted keys in which every entry looks only at its predecessor.  Every fp64 sum whose order the contract fixes
 // is taken by one owner in that order (a thread over its CSR row, one block's chain over the triangles); the only atomics are the
 // union-find's hooks and integer counts, whose results do not depend on the order in which they land.
-#include "kpx_morton.h"
+#include "kpx_sort.h"
 #include "kpx_unionfind.h"
 
 #include <math.h>
@@ -121,20 +121,15 @@ __global__ __launch_bounds__(kAreaThreads) void mesh_area_kernel(const float *__
 
 struct MeshNormalScratch {
     double *n64;
-    uint32_t *keys_out;
-    int32_t *vals_in, *vals_out;
-    void *tmp;
-    size_t tmp_bytes;
+    DeviceSort<uint32_t> sort;          // (vertex, corner) pairs; keys_in: the caller's triangle array
 };
 void mesh_normals_carve(Arena &a, int64_t nt, MeshNormalScratch *s)
 {
-    const size_t t = (size_t)(nt > 0 ? nt : 1), p = 3 * t;
-    s->n64 = a.get<double>(3 * t);
-    s->keys_out = a.get<uint32_t>(p);
-    s->vals_in = a.get<int32_t>(p);
-    s->vals_out = a.get<int32_t>(p);
-    s->tmp_bytes = memo_bytes(10, (int64_t)p, [&] { size_t b = 0; (void)sort_pairs<uint32_t>(nullptr, b, s->keys_out, s->keys_out, s->vals_in, s->vals_out, (int64_t)p, 32, (hipStream_t) nullptr); return b; });
-    s->tmp = a.get<char>(s->tmp_bytes);
+    const int64_t t = nt > 0 ? nt : 1;
+    s->n64 = a.get<double>(3 * (size_t)t);
+    SortOptions o;
+    o.keys_in = false;
+    dsort_carve(a, 3 * t, 32, o, &s->sort);
 }
 
 constexpr int64_t kMeshMax = 2147483647;        // int32 indices
@@ -185,40 +180,14 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_pair_keys_kernel(const int3
     if (parent) parent[t] = (int32_t)t;
 }
 
-struct PairScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out;
-    void *tmp;
-    size_t tmp_bytes;
-};
-// with_vals: the sort carries each key's number along (vals_in / vals_out); without, it sorts the keys alone and both stay null.
-// A site is carved one way only: the memo of the sort's temporary bytes is per site.
-void pair_carve(Arena &a, int64_t npairs, unsigned site, bool with_vals, PairScratch *s)
-{
-    const size_t p = (size_t)(npairs > 0 ? npairs : 1);
-    s->keys_in = a.get<uint64_t>(p);
-    s->keys_out = a.get<uint64_t>(p);
-    s->vals_in = with_vals ? a.get<int32_t>(p) : nullptr;
-    s->vals_out = with_vals ? a.get<int32_t>(p) : nullptr;
-    s->tmp_bytes = memo_bytes(site, (int64_t)p, [&] {
-        size_t b = 0;
-        if (with_vals) (void)sort_pairs<uint64_t>(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int64_t)p, 64, (hipStream_t) nullptr);
-        else (void)rocprim::radix_sort_keys(nullptr, b, s->keys_in, s->keys_out, p, 0u, 64u, (hipStream_t) nullptr);
-        return b;
-    });
-    s->tmp = a.get<char>(s->tmp_bytes);
-}
-// keys_out (and vals_out, where carved): the pairs of every triangle in ascending key order
-int pair_sort(const int32_t *tri, int64_t nt, int64_t nv, bool directed, const PairScratch &s, int32_t *parent, hipStream_t st)
+// the pairs of every triangle in ascending key order -> keys_out (and vals_out: each key's number, where the sort carries values);
+// carved for (directed ? 6 : 3) * nt pairs
+template <bool kVals>
+int pair_sort(const int32_t *tri, int64_t nt, int64_t nv, bool directed, const DeviceSort<uint64_t, kVals> &s, int32_t *parent, hipStream_t st)
 {
     hipLaunchKernelGGL(mesh_pair_keys_kernel, dim3(mesh_blocks(nt)), dim3(kMeshThreads), 0, st, tri, nt, nv, directed ? 1 : 0, s.keys_in, s.vals_in, parent);
     KPX_LAUNCH_CHECK();
-    size_t bytes = s.tmp_bytes;
-    const int64_t n = (directed ? 6 : 3) * nt;
-    const int end_bit = 32 + bits_for(nv);
-    if (s.vals_in) KPX_HIP(sort_pairs<uint64_t>(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, n, end_bit, st));
-    else KPX_HIP(rocprim::radix_sort_keys(s.tmp, bytes, s.keys_in, s.keys_out, (size_t)n, 0u, (unsigned)end_bit, st));
-    return KPX_OK;
+    return dsort_run(s, (directed ? 6 : 3) * nt, 32 + bits_for(nv), st);
 }
 
 // ---- adjacency: the distinct sorted pairs are the CSR rows ---------------------------------------------------------------------------
@@ -245,12 +214,12 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_offsets_kernel(const int32_
 }
 
 struct AdjacencyScratch {
-    PairScratch p;
+    DeviceSort<uint64_t, false> p;
     int32_t *owner, *counts;
 };
 void adjacency_carve(Arena &a, int64_t nt, AdjacencyScratch *s)
 {
-    pair_carve(a, 6 * nt, 11, false, &s->p);
+    dsort_carve(a, 6 * nt, 64, SortOptions(), &s->p);
     s->owner = a.get<int32_t>((size_t)(nt > 0 ? 6 * nt : 1));
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(6 * nt));
 }
@@ -273,12 +242,12 @@ struct EdgeEmit {
     __device__ void operator()(int64_t i, int, int32_t dst) const { out[2 * (int64_t)dst] = (int32_t)(k[i] >> 32); out[2 * (int64_t)dst + 1] = (int32_t)(uint32_t)k[i]; }
 };
 struct EdgeScratch {
-    PairScratch p;
+    DeviceSort<uint64_t, false> p;
     int32_t *counts;
 };
 void edge_carve(Arena &a, int64_t nt, EdgeScratch *s)
 {
-    pair_carve(a, 3 * nt, 12, false, &s->p);
+    dsort_carve(a, 3 * nt, 64, SortOptions(), &s->p);
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(3 * nt));
 }
 
@@ -426,27 +395,19 @@ __global__ __launch_bounds__(kAreaThreads) void mesh_chain_kernel(const float *_
 }
 
 struct ClusterScratch {
-    PairScratch p;
+    DeviceSort<uint64_t> p;          // the edges, each with its number
     int32_t *parent, *rank, *err, *counts;
-    uint32_t *ckeys_in, *ckeys_out;
-    int32_t *cvals_in, *cvals_out;
-    void *ctmp;
-    size_t ctmp_bytes;
+    DeviceSort<uint32_t> c;          // (cluster, triangle) pairs
 };
 void cluster_carve(Arena &a, int64_t nt, ClusterScratch *s)
 {
     const size_t t = (size_t)(nt > 0 ? nt : 1);
-    pair_carve(a, 3 * nt, 14, true, &s->p);
+    dsort_carve(a, 3 * nt, 64, SortOptions(), &s->p);
     s->parent = a.get<int32_t>(t);
     s->rank = a.get<int32_t>(t);
     s->err = a.get<int32_t>(1);
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(nt));
-    s->ckeys_in = a.get<uint32_t>(t);
-    s->ckeys_out = a.get<uint32_t>(t);
-    s->cvals_in = a.get<int32_t>(t);
-    s->cvals_out = a.get<int32_t>(t);
-    s->ctmp_bytes = memo_bytes(13, (int64_t)t, [&] { size_t b = 0; (void)sort_pairs<uint32_t>(nullptr, b, s->ckeys_in, s->ckeys_out, s->cvals_in, s->cvals_out, (int64_t)t, 32, (hipStream_t) nullptr); return b; });
-    s->ctmp = a.get<char>(s->ctmp_bytes);
+    dsort_carve(a, nt, 32, SortOptions(), &s->c);
 }
 
 // ---- removal: ordered compactions of the rows ---------------------------------------------------------------------------------------
@@ -696,22 +657,23 @@ KPX_EXPORT int kpx_mesh_normals(const float *vertices, int64_t n_vertices, const
         Arena a(ws, ws_bytes);
         mesh_normals_carve(a, n_triangles, &s);
         KPX_ARENA_CHECK(a);
+        s.sort.keys_in = reinterpret_cast<uint32_t *>(const_cast<int32_t *>(triangles));          // a sort only reads its inputs
     }
     const int64_t npairs = 3 * n_triangles;
     if (n_triangles > 0) {
         hipLaunchKernelGGL(mesh_triangle_normals_kernel, dim3((unsigned)cdiv(n_triangles, 256)), dim3(256), 0, st, vertices, n_vertices, triangles, n_triangles,
                            (int)normalized, want_t ? out_triangle_normals : (float *)nullptr, want_v ? s.n64 : (double *)nullptr,
-                           want_v ? s.vals_in : (int32_t *)nullptr);
+                           want_v ? s.sort.vals_in : (int32_t *)nullptr);
         KPX_LAUNCH_CHECK();
     }
     if (!want_v) return KPX_OK;
     if (n_triangles > 0) {
         int bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < n_vertices) ++bits;
-        size_t bytes = s.tmp_bytes;
-        KPX_HIP(sort_pairs<uint32_t>(s.tmp, bytes, reinterpret_cast<const uint32_t *>(triangles), s.keys_out, s.vals_in, s.vals_out, npairs, bits, st));
+        const int rc = dsort_run(s.sort, npairs, bits, st);
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)cdiv(n_vertices, 256)), dim3(256), 0, st, (const uint32_t *)s.keys_out, (const int32_t *)s.vals_out,
+    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)cdiv(n_vertices, 256)), dim3(256), 0, st, (const uint32_t *)s.sort.keys_out, (const int32_t *)s.sort.vals_out,
                        npairs, (const double *)s.n64, n_vertices, (int)normalized, out_vertex_normals);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
@@ -821,12 +783,12 @@ KPX_EXPORT int kpx_mesh_cluster_triangles(const float *vertices, int64_t n_verti
     rc = compact(TriRootPred{ s.parent }, TriRankEmit{ s.rank }, n_triangles, 1, s.counts, d_count, st);
     if (rc) return rc;
     hipLaunchKernelGGL(mesh_label_kernel, dim3(nb), dim3(kMeshThreads), 0, st, n_triangles, (const int32_t *)s.parent, (const int32_t *)s.rank, out_clusters,
-                       out_n_triangles, s.ckeys_in, s.cvals_in, (const int32_t *)s.err, d_count);
+                       out_n_triangles, s.c.keys_in, s.c.vals_in, (const int32_t *)s.err, d_count);
     KPX_LAUNCH_CHECK();
-    size_t bytes = s.ctmp_bytes;
-    KPX_HIP(sort_pairs<uint32_t>(s.ctmp, bytes, s.ckeys_in, s.ckeys_out, s.cvals_in, s.cvals_out, n_triangles, bits_for(n_triangles), st));
-    hipLaunchKernelGGL(mesh_chain_kernel<true>, dim3(1), dim3(kAreaThreads), 0, st, vertices, n_vertices, triangles, n_triangles, (const int32_t *)s.cvals_out,
-                       (const uint32_t *)s.ckeys_out, out_area);
+    rc = dsort_run(s.c, n_triangles, bits_for(n_triangles), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mesh_chain_kernel<true>, dim3(1), dim3(kAreaThreads), 0, st, vertices, n_vertices, triangles, n_triangles, (const int32_t *)s.c.vals_out,
+                       (const uint32_t *)s.c.keys_out, out_area);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

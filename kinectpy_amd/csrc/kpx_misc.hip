@@ -4,8 +4,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "kpx_internal.h"
-#include "kpx_morton.h"
-#include "kpx_radix.h"
+#include "kpx_sort.h"
 
 namespace kpx {
 
@@ -13,22 +12,23 @@ namespace {
 std::mutex g_memo_mu;
 std::unordered_map<unsigned long long, size_t> g_memo;
 }
-bool memo_bytes_lookup(unsigned site, int64_t n, size_t *bytes)
+size_t memo_bytes(unsigned what, int64_t n, const std::function<size_t()> &query)
 {
-    const unsigned long long key = ((unsigned long long)site << 48) ^ (unsigned long long)n;
+    const unsigned long long key = ((unsigned long long)what << 48) ^ (unsigned long long)n;
+    {
+        std::lock_guard<std::mutex> lock(g_memo_mu);
+        auto it = g_memo.find(key);
+        if (it != g_memo.end()) return it->second;
+    }
+    const size_t bytes = query();
     std::lock_guard<std::mutex> lock(g_memo_mu);
-    auto it = g_memo.find(key);
-    if (it == g_memo.end()) return false;
-    *bytes = it->second;
-    return true;
+    return g_memo[key] = bytes;
 }
-void memo_bytes_store(unsigned site, int64_t n, size_t bytes)
+bool sort_radix_off()
 {
-    const unsigned long long key = ((unsigned long long)site << 48) ^ (unsigned long long)n;
-    std::lock_guard<std::mutex> lock(g_memo_mu);
-    g_memo[key] = bytes;
+    static const bool off = [] { const char *e = getenv("KPX_RADIX"); return e && e[0] == '0'; }();
+    return off;
 }
-
 
 struct Affine { double m[12]; };   // rows of [R | t]
 
@@ -577,19 +577,18 @@ KPX_EXPORT int kpx_fuse_skeletons(const double *skeletons, int32_t cams, int64_t
 
 // ---- stable sort of (uint32 key, int32 value) pairs on the low end_bit key bits: the library's own radix sort up to
 // kRadixMaxPairs pairs, rocPRIM above (exported for tests and for callers that order their own index lists)
-static void sort_u32_carve(Arena &a, int64_t n, RadixScratch *rx, char **tmp, size_t *tmp_bytes)
+static void sort_u32_carve(Arena &a, int64_t n, DeviceSort<uint32_t> *s)
 {
-    if (n <= kRadixMaxPairs) { radix_carve(a, n, rx); return; }
-    *tmp_bytes = memo_bytes(1, n, [&] { size_t b = 0; (void)sort_pairs<uint32_t>(nullptr, b, nullptr, nullptr, nullptr, nullptr, n, 32, (hipStream_t) nullptr); return b; });
-    *tmp = a.get<char>(*tmp_bytes);
+    SortOptions o;
+    o.keys_in = o.keys_out = o.vals_in = o.vals_out = false;          // the caller's four arrays
+    o.radix = kRadixOrVendor;
+    dsort_carve(a, n, 32, o, s);
 }
 KPX_EXPORT size_t kpx_sort_pairs_u32_workspace_bytes(int64_t n)
 {
     Arena a(nullptr, 0);
-    RadixScratch rx;
-    char *tmp = nullptr;
-    size_t tb = 0;
-    sort_u32_carve(a, n, &rx, &tmp, &tb);
+    DeviceSort<uint32_t> s;
+    sort_u32_carve(a, n, &s);
     return a.off;
 }
 KPX_EXPORT int kpx_sort_pairs_u32(const uint32_t *keys_in, const int32_t *vals_in, int64_t n, int32_t end_bit, uint32_t *keys_out,
@@ -600,14 +599,12 @@ KPX_EXPORT int kpx_sort_pairs_u32(const uint32_t *keys_in, const int32_t *vals_i
     KPX_REQUIRE(keys_in && vals_in && keys_out && vals_out && ws, "kpx_sort_pairs_u32: null pointer");
     KPX_REQUIRE(keys_in != keys_out && vals_in != vals_out, "kpx_sort_pairs_u32: outputs may not alias the inputs");
     Arena a(ws, ws_bytes);
-    RadixScratch rx;
-    char *tmp = nullptr;
-    size_t tb = 0;
-    sort_u32_carve(a, n, &rx, &tmp, &tb);
+    DeviceSort<uint32_t> s;
+    sort_u32_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
-    if (n <= kRadixMaxPairs) return radix_sort_pairs_u32(rx, keys_in, keys_out, vals_in, vals_out, n, end_bit, (hipStream_t)stream);
-    KPX_HIP(sort_pairs<uint32_t>(tmp, tb, keys_in, keys_out, vals_in, vals_out, n, end_bit, (hipStream_t)stream));
-    return KPX_OK;
+    s.keys_in = const_cast<uint32_t *>(keys_in); s.vals_in = const_cast<int32_t *>(vals_in);          // a sort only reads its inputs
+    s.keys_out = keys_out; s.vals_out = vals_out;
+    return dsort_run(s, n, end_bit, (hipStream_t)stream);
 }
 
 KPX_EXPORT size_t kpx_select_workspace_bytes(int64_t n)

@@ -2,29 +2,13 @@
 // nearest-neighbour sweep (kpx_nnlocal.h) and the box-hierarchy k-NN of kpx_knn.hip.  Kernels are `static`: the
 // header is included by more than one translation unit.
 #pragma once
-#include <hipcub/hipcub.hpp>
-
 #include "kpx_cloudset.h"
 #include "kpx_internal.h"
+#include "kpx_sort.h"
 
 namespace kpx {
 
 constexpr float kBoxBig = 3.0e38f;
-
-// Stable LSD radix sort of (key, int32 value) pairs on bits [0, end_bit).  Below 1M keys rocPRIM's default is a merge sort:
-// one block sort plus two launches per doubling (13 launches for 30k keys).  In this library's dependent chains the NUMBER of
-// launches is what costs (every boundary also writes back / invalidates the L2s under everything else on the device), so
-// keys of at most 32 significant bits go through Onesweep instead: histogram + scan + one pass per 8 bits (5 launches for
-// the 22-bit cell ids of a grid build).  Same result (both are stable).
-using NarrowSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 4096>;
-template <class Key>
-static inline hipError_t sort_pairs(void *tmp, size_t &bytes, const Key *keys_in, Key *keys_out, const int32_t *vals_in, int32_t *vals_out,
-                                    int64_t n, int end_bit, hipStream_t st)
-{
-    if (end_bit <= 32)
-        return rocprim::radix_sort_pairs<NarrowSortConfig>(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)end_bit, st);
-    return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)end_bit, st);
-}
 
 __device__ __forceinline__ uint32_t morton_spread10(uint32_t v)
 {
@@ -67,20 +51,25 @@ __device__ __forceinline__ uint32_t curve_code30(const uint32_t q[3])
 {
     return hilbert30(q[0], q[1], q[2]);
 }
-static __global__ __launch_bounds__(256) void morton_key_kernel(const float *__restrict__ pts, int64_t n, const double *__restrict__ bbox,
-                                                         uint32_t *__restrict__ keys, int32_t *__restrict__ vals)
+// 30-bit curve code of p in the grid of 1024^3 cells over the box bbox (cubic cells sized by the longest side; NaN -> cell 0)
+__device__ __forceinline__ uint32_t curve_code_of(const float *__restrict__ p, const double *__restrict__ bbox)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
     const double ext = fmax(bbox[3] - bbox[0], fmax(bbox[4] - bbox[1], bbox[5] - bbox[2]));
     const double scale = ext > 0.0 ? 1023.0 / ext : 0.0;
     uint32_t q[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double v = ((double)pts[3 * i + a] - bbox[a]) * scale;
+        const double v = ((double)p[a] - bbox[a]) * scale;
         q[a] = v >= 0.0 ? (uint32_t)(v < 1023.0 ? v : 1023.0) : 0u;          // NaN -> cell 0
     }
-    keys[i] = curve_code30(q);
+    return curve_code30(q);
+}
+static __global__ __launch_bounds__(256) void morton_key_kernel(const float *__restrict__ pts, int64_t n, const double *__restrict__ bbox,
+                                                         uint32_t *__restrict__ keys, int32_t *__restrict__ vals)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = curve_code_of(pts + 3 * i, bbox);
     vals[i] = (int32_t)i;
 }
 
@@ -106,20 +95,14 @@ __device__ __forceinline__ void load_box(const float *__restrict__ bx, double lo
 }
 // Morton order of a cloud: d_perm[r] = original index of the r-th point along the curve.
 struct SortScratch {
-    uint32_t *keys_in, *keys_out;
-    int32_t *vals_in;
-    void *tmp;
-    size_t tmp_bytes;
+    DeviceSort<uint32_t> sort;          // vals_out: the caller's d_perm
     double *bbox_part, *bbox;
 };
 static void sort_carve(Arena &a, int64_t n, SortScratch *s)
 {
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    s->keys_in = a.get<uint32_t>(nn);
-    s->keys_out = a.get<uint32_t>(nn);
-    s->vals_in = a.get<int32_t>(nn);
-    s->tmp_bytes = memo_bytes(7, (int64_t)nn, [&] { size_t b = 0; (void)sort_pairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_in, (int64_t)nn, 30, (hipStream_t) nullptr); return b; });
-    s->tmp = a.get<char>(s->tmp_bytes);
+    SortOptions o;
+    o.vals_out = false;
+    dsort_carve(a, n, 30, o, &s->sort);
     s->bbox_part = a.get<double>((size_t)kBboxBlocks * 6);
     s->bbox = a.get<double>(8);
 }
@@ -127,10 +110,10 @@ static int morton_order(const float *pts, int64_t n, const SortScratch &s, int32
 {
     int rc = bbox_f32(pts, n, s.bbox, s.bbox_part, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(morton_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, pts, n, s.bbox, s.keys_in, s.vals_in);
-    size_t bytes = s.tmp_bytes;
-    KPX_HIP(sort_pairs(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, d_perm, n, 30, st));
-    return KPX_OK;
+    DeviceSort<uint32_t> sort = s.sort;
+    sort.vals_out = d_perm;
+    hipLaunchKernelGGL(morton_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, pts, n, s.bbox, sort.keys_in, sort.vals_in);
+    return dsort_run(sort, n, 30, st);
 }
 
 // ---- Morton order of several clouds with ONE sort -----------------------------------------------------------------
@@ -145,40 +128,20 @@ struct MortonBatch : CloudSet<kMortonBatchMax> {
     double *bbox[kMortonBatchMax];        // out: (min x,y,z, max x,y,z) of cloud c
 };
 struct MortonBatchScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out;
+    DeviceSort<uint64_t, true, kSortDefault32> sort;
     double *part;
-    void *tmp;
-    size_t tmp_bytes;
 };
 static void morton_batch_carve(Arena &a, int64_t total, MortonBatchScratch *s)
 {
-    const size_t nn = (size_t)(total > 0 ? total : 1);
-    s->keys_in = a.get<uint64_t>(nn);
-    s->keys_out = a.get<uint64_t>(nn);
-    s->vals_in = a.get<int32_t>(nn);
-    s->vals_out = a.get<int32_t>(nn);
+    dsort_carve(a, total, 34, SortOptions(), &s->sort);
     s->part = a.get<double>((size_t)kMortonBatchMax * kMortonBatchBboxBlocks * 6);
-    s->tmp_bytes = memo_bytes(8, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, 34, (hipStream_t) nullptr); return b; });
-    s->tmp = a.get<char>(s->tmp_bytes);
 }
 static __global__ __launch_bounds__(256) void morton_batch_key_kernel(MortonBatch b, uint64_t *__restrict__ keys, int32_t *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b.off[b.count]) return;
     const int c = b.cloud_of(i);
-    const float *pts = b.pts[c];
-    const double *bbox = b.bbox[c];
-    const int64_t j = i - b.off[c];
-    const double ext = fmax(bbox[3] - bbox[0], fmax(bbox[4] - bbox[1], bbox[5] - bbox[2]));
-    const double scale = ext > 0.0 ? 1023.0 / ext : 0.0;
-    uint32_t q[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double v = ((double)pts[3 * j + a] - bbox[a]) * scale;
-        q[a] = v >= 0.0 ? (uint32_t)(v < 1023.0 ? v : 1023.0) : 0u;          // NaN -> cell 0
-    }
-    keys[i] = ((uint64_t)c << 30) | curve_code30(q);
+    keys[i] = ((uint64_t)c << 30) | curve_code_of(b.pts[c] + 3 * (i - b.off[c]), b.bbox[c]);
     vals[i] = (int32_t)i;
 }
 static __global__ __launch_bounds__(256) void morton_batch_split_kernel(MortonBatch b, const int32_t *__restrict__ vals)
@@ -211,10 +174,10 @@ static int morton_order_batch(const MortonBatch &b, const MortonBatchScratch &s,
         KPX_LAUNCH_CHECK();
         return KPX_OK;
     }
-    hipLaunchKernelGGL(morton_batch_key_kernel, dim3(nb), dim3(256), 0, st, b, s.keys_in, s.vals_in);
-    size_t bytes = s.tmp_bytes;
-    KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)total, 0, 34, st));
-    hipLaunchKernelGGL(morton_batch_split_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out);
+    hipLaunchKernelGGL(morton_batch_key_kernel, dim3(nb), dim3(256), 0, st, b, s.sort.keys_in, s.sort.vals_in);
+    const int rc = dsort_run(s.sort, total, 34, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(morton_batch_split_kernel, dim3(nb), dim3(256), 0, st, b, s.sort.vals_out);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

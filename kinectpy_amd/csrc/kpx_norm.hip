@@ -19,10 +19,9 @@
 //   key3 = e.d;  the winner maximises (key1, key2, key3), lowest index on full ties -- it is the next extreme point
 //   also when several hull points are coplanar (key2 / key3 walk the facet polygon).  New facet (b, a, c).
 // The start is the lexicographically smallest point and the virtual half plane {x = x0, y <= y0} through it.
-#include <hipcub/hipcub.hpp>
-
 #include "kpx_internal.h"
 #include "kpx_linalg.h"
+#include "kpx_sort.h"
 
 namespace kpx {
 
@@ -50,22 +49,7 @@ __global__ __launch_bounds__(256) void sample_gather_kernel(const float *__restr
         }
     }
 }
-struct SampleScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out;
-    void *tmp;
-    size_t tmp_bytes;
-};
-static void sample_carve(Arena &a, int64_t n, SampleScratch *s)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    s->keys_in = a.get<uint64_t>(nn);
-    s->keys_out = a.get<uint64_t>(nn);
-    s->vals_in = a.get<int32_t>(nn);
-    s->vals_out = a.get<int32_t>(nn);
-    s->tmp_bytes = memo_bytes(9, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, 64, (hipStream_t) nullptr); return b; });
-    s->tmp = a.get<char>(s->tmp_bytes);
-}
+using SampleSort = DeviceSort<uint64_t, true, kSortDefault32>;
 
 // ---- gift wrapping (AC5) ------------------------------------------------------------------------------
 struct WrapKey {
@@ -533,8 +517,8 @@ using namespace kpx;
 KPX_EXPORT size_t kpx_sample_workspace_bytes(int64_t n)
 {
     Arena a(nullptr, 0);
-    SampleScratch s;
-    sample_carve(a, n, &s);
+    SampleSort s;
+    dsort_carve(a, n, 64, SortOptions(), &s);
     return a.off;
 }
 KPX_EXPORT int kpx_sample_points(const float *pts, int64_t n, int64_t k, uint64_t seed, float *out_pts, int32_t *out_idx, void *ws,
@@ -548,13 +532,13 @@ KPX_EXPORT int kpx_sample_points(const float *pts, int64_t n, int64_t k, uint64_
     KPX_REQUIRE(ws && (out_idx || (out_pts && pts)), "kpx_sample_points: null pointer");
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    SampleScratch s;
-    sample_carve(a, n, &s);
+    SampleSort s;
+    dsort_carve(a, n, 64, SortOptions(), &s);
     KPX_ARENA_CHECK(a);
     hipLaunchKernelGGL(sample_key_kernel, dim3((unsigned)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256))), dim3(256), 0, st, n, (uint32_t)seed,
                        (uint32_t)(seed >> 32), s.keys_in, s.vals_in);
-    size_t bytes = s.tmp_bytes;
-    KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)n, 0, 64, st));
+    const int rc = dsort_run(s, n, 64, st);
+    if (rc) return rc;
     hipLaunchKernelGGL(sample_gather_kernel, dim3((unsigned)(cdiv(k, 256) > 4096 ? 4096 : cdiv(k, 256))), dim3(256), 0, st, pts, s.vals_out, k,
                        out_pts, out_idx);
     KPX_LAUNCH_CHECK();

@@ -12,7 +12,7 @@
 //     ballot-match per key (wave w owns 512 consecutive pairs, slot by slot, so the tile order is the memory order), staged in
 //     LDS in sorted order and written out as consecutive runs per digit.
 // Two launches per 8-bit pass, one clear per sort: 7 dispatches for the 24-bit keys of a 4-sensor frame.
-// Above kRadixMaxPairs the group rows would no longer be a handful per thread; those sorts stay with rocPRIM (kpx_morton.h).
+// Above kRadixMaxPairs the group rows would no longer be a handful per thread.  Which sorts come here is decided in kpx_sort.h.
 #pragma once
 #include "kpx_common.h"
 

@@ -48,12 +48,12 @@ static int voxel_impl(const float *pts, const float *col, const float *nrm, int6
     CloudSet<1> one;
     one.pts[0] = pts; one.off[0] = 0; one.off[1] = n; one.count = 1;
     hipLaunchKernelGGL((voxel_key_kernel<CloudSet<1>, StoredPoint, FixedKeys>), dim3(nb), dim3(256), 0, st, one, (const double *)s.bbox, voxel,
-                       FixedKeys{ s.keys_in, s.err }, s.vals_in);
+                       FixedKeys{ s.sort.keys_in, s.err }, s.sort.vals_in);
     rc = voxel_sort_and_heads<uint64_t>(s, n, 63, d_count, st);
     if (rc) return rc;
     const StoredLoad load = { pts, col, nrm, 0 };
     const auto mean_kernel = nrm ? &voxel_mean_kernel<true> : &voxel_mean_kernel<false>;
-    hipLaunchKernelGGL(mean_kernel, dim3(nb), dim3(256), 0, st, load, n, (const int32_t *)s.vals_out,
+    hipLaunchKernelGGL(mean_kernel, dim3(nb), dim3(256), 0, st, load, n, (const int32_t *)s.sort.vals_out,
                        (const int32_t *)s.seg_start, d_count, (const int32_t *)s.err, opts, ocol, onrm);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
@@ -70,7 +70,7 @@ static int voxel_impl(const float *pts, const float *col, const float *nrm, int6
 // point index.
 constexpr int kVoxelBatchMax = 8;
 constexpr int kVoxelBatchBboxBlocks = 64;
-constexpr VoxelCarve kBatchCarve = { kVoxelBatchMax, kVoxelBatchBboxBlocks, true, true, 5, 64 };
+constexpr VoxelCarve kBatchCarve = { kVoxelBatchMax, kVoxelBatchBboxBlocks, true, true, 64 };
 struct VoxelBatch : CloudSet<kVoxelBatchMax> {
     const float *col[kVoxelBatchMax];
     float *opts[kVoxelBatchMax];
@@ -324,16 +324,16 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
     int rc;
     if (end_bit <= 32) {
         hipLaunchKernelGGL((voxel_key_kernel<VoxelBatch, StoredPoint, BatchKeys<uint32_t>>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
-                           BatchKeys<uint32_t>{ reinterpret_cast<uint32_t *>(s.keys_in), s.err, bits_out }, s.vals_in);
+                           BatchKeys<uint32_t>{ reinterpret_cast<uint32_t *>(s.sort.keys_in), s.err, bits_out }, s.sort.vals_in);
         rc = voxel_sort_and_heads<uint32_t>(s, total, end_bit, s.d_total, st);
     } else {
         hipLaunchKernelGGL((voxel_key_kernel<VoxelBatch, StoredPoint, BatchKeys<uint64_t>>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
-                           BatchKeys<uint64_t>{ s.keys_in, s.err, bits_out }, s.vals_in);
+                           BatchKeys<uint64_t>{ s.sort.keys_in, s.err, bits_out }, s.sort.vals_in);
         rc = voxel_sort_and_heads<uint64_t>(s, total, end_bit, s.d_total, st);
     }
     if (rc) return rc;
     hipLaunchKernelGGL(voxel_batch_locate_kernel, dim3(1), dim3(64), 0, st, b, s.seg_start, s.d_total, s.err, s.head, d_counts);
-    hipLaunchKernelGGL(voxel_batch_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out, s.seg_start, s.d_total, s.head);
+    hipLaunchKernelGGL(voxel_batch_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.sort.vals_out, s.seg_start, s.d_total, s.head);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -347,7 +347,7 @@ static int voxel_batch_impl(const VoxelBatch &b, double voxel, int32_t *d_counts
 // MovedPoint).  That is also one pass less over HBM and three launches less per sensor than transform -> concat -> voxel.
 constexpr int kFuseMax = 16;
 constexpr int kFuseBboxBlocks = 32;
-constexpr VoxelCarve kFuseCarve = { kFuseMax, kFuseBboxBlocks, false, true, 6, 63 };
+constexpr VoxelCarve kFuseCarve = { kFuseMax, kFuseBboxBlocks, false, true, 63 };
 struct FuseBatch : CloudSet<kFuseMax> {
     const float *col[kFuseMax];
     double T[kFuseMax][12];               // rows of [R | t]
@@ -467,16 +467,16 @@ static int fuse_voxel_impl(const FuseBatch &b, double voxel, float *opts, float 
     int rc;
     if (spec_bits > 0 && spec_bits <= 32 && d_bits && total <= kRadixMaxPairs) {
         hipLaunchKernelGGL((voxel_key_kernel<FuseBatch, MovedPoint, ExtentKeys32>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
-                           ExtentKeys32{ reinterpret_cast<uint32_t *>(s.keys_in), d_bits }, s.vals_in);
+                           ExtentKeys32{ reinterpret_cast<uint32_t *>(s.sort.keys_in), d_bits }, s.sort.vals_in);
         rc = voxel_sort_and_heads<uint32_t>(s, total, spec_bits, d_count, st);
     } else {
         if (d_bits) hipLaunchKernelGGL(fuse_bits_kernel, dim3(1), dim3(1), 0, st, s.bbox, voxel, d_bits);      // for the caller's next speculation
         hipLaunchKernelGGL((voxel_key_kernel<FuseBatch, MovedPoint, FixedKeys>), dim3(nb), dim3(256), 0, st, b, (const double *)s.bbox, voxel,
-                           FixedKeys{ s.keys_in, s.err }, s.vals_in);
+                           FixedKeys{ s.sort.keys_in, s.err }, s.sort.vals_in);
         rc = voxel_sort_and_heads<uint64_t>(s, total, 63, d_count, st);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(fuse_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.vals_out, s.seg_start, d_count, s.err, opts, ocol);
+    hipLaunchKernelGGL(fuse_mean_kernel, dim3(nb), dim3(256), 0, st, b, s.sort.vals_out, s.seg_start, d_count, s.err, opts, ocol);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

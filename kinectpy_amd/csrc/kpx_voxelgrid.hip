@@ -249,10 +249,10 @@ KPX_EXPORT int kpx_voxelgrid_from_cloud(const float *pts, const float *col, int6
     CloudSet<1> one;
     one.pts[0] = pts; one.off[0] = 0; one.off[1] = n; one.count = 1;
     hipLaunchKernelGGL((voxel_key_kernel<CloudSet<1>, StoredPoint, OriginKeys>), dim3(nb), dim3(256), 0, st, one, (const double *)d_origin, voxel,
-                       OriginKeys{ s.keys_in, s.err }, s.vals_in);
+                       OriginKeys{ s.sort.keys_in, s.err }, s.sort.vals_in);
     const int rc = voxel_sort_and_heads<uint64_t>(s, n, 63, d_count, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(grid_colour_kernel, dim3(nb), dim3(256), 0, st, col, n, (const uint64_t *)s.keys_out, (const int32_t *)s.vals_out,
+    hipLaunchKernelGGL(grid_colour_kernel, dim3(nb), dim3(256), 0, st, col, n, (const uint64_t *)s.sort.keys_out, (const int32_t *)s.sort.vals_out,
                        (const int32_t *)s.seg_start, d_count, (const int32_t *)s.err, keys, colors);
     KPX_LAUNCH_CHECK();
     return KPX_OK;

@@ -2,11 +2,9 @@
 // stable sort of (key, point id), head compaction and the per-voxel sequential fp64 sums.  kpx_voxel.hip (voxel_down_sample in its
 // plain, batch and fused forms) and kpx_voxelgrid.hip (VoxelGrid.create_from_point_cloud) are host policies over them.
 #pragma once
-#include <hipcub/hipcub.hpp>
-
 #include "kpx_cloudset.h"
 #include "kpx_internal.h"
-#include "kpx_radix.h"
+#include "kpx_sort.h"
 
 namespace kpx {
 
@@ -127,68 +125,52 @@ struct StoredLoad {
 };
 
 // Scratch of a form.  VoxelCarve: what distinguishes the forms' workspaces -- the cloud slots, the blocks of a cloud's partial
-// bounding boxes, boxes / error words per cloud (with the batch form's head table) or one for all, the library's own radix sort,
-// and the call site and end bit of the vendor sort's size query.
+// bounding boxes, boxes / error words per cloud (with the batch form's head table) or one for all, whether the form also writes keys
+// of at most 32 bits as 32-bit words (sorted through dsort_view32, by the library's own radix sort where that serves), and the
+// widest key the form sorts.
+using VoxelSort = DeviceSort<uint64_t, true, kSortDefault32>;
 struct VoxelScratch {
-    uint64_t *keys_in, *keys_out;
-    int32_t *vals_in, *vals_out, *seg_start, *counts, *err, *head, *d_total;
+    int32_t *seg_start, *counts, *err, *head, *d_total;
     double *part, *bbox;
-    char *sort_tmp;
-    size_t sort_bytes;
-    RadixScratch rx;            // the hand-written sort (keys of at most 32 bits, total <= kRadixMaxPairs)
+    VoxelSort sort;
     char *counts_end;
 };
 struct VoxelCarve {
     int clouds, bbox_blocks;
-    bool per_cloud, own_radix;
-    unsigned site;
+    bool per_cloud, keys32;
     int end_bit;
 };
 static void voxel_carve(Arena &a, int64_t total, const VoxelCarve &v, VoxelScratch *s)
 {
     const size_t nn = (size_t)(total > 0 ? total : 1);
-    s->keys_in = a.get<uint64_t>(nn); s->keys_out = a.get<uint64_t>(nn);
-    s->vals_in = a.get<int32_t>(nn); s->vals_out = a.get<int32_t>(nn);
     s->seg_start = a.get<int32_t>(nn);
     s->err = a.get<int32_t>(v.per_cloud ? v.clouds : 1);
     s->head = v.per_cloud ? a.get<int32_t>(v.clouds + 1) : nullptr;
     s->d_total = v.per_cloud ? a.get<int32_t>(1) : nullptr;
     s->part = a.get<double>((size_t)v.clouds * v.bbox_blocks * 6);
     s->bbox = a.get<double>((size_t)(v.per_cloud ? v.clouds : 1) * 8);
-    const int end_bit = v.end_bit;
-    s->sort_bytes = memo_bytes(v.site, (int64_t)nn, [&] { size_t b = 0; (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)nn, 0, end_bit, (hipStream_t) nullptr); return b; });
-    s->sort_tmp = a.get<char>(s->sort_bytes);
-    s->rx = RadixScratch();
-    if (v.own_radix) radix_carve(a, total <= kRadixMaxPairs ? total : kRadixMaxPairs, &s->rx);      // unconditional: the workspace size stays monotonic in the point count
+    SortOptions o;
+    if (v.keys32) { o.radix = kRadixAndVendor; o.tmp_floor = dsort_view32_bytes(total); }
+    dsort_carve(a, total, v.end_bit, o, &s->sort);
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(total));          // right behind the sort's cleared histograms: one memset for both
     s->counts_end = reinterpret_cast<char *>(s->counts + (size_t)compact_ws_ints(total));
 }
 
 // Stable sort of the (key, index) pairs on key bits [0, end_bit), then the segment heads: seg_start[m] = first sorted position of the
-// m-th distinct key, *d_heads = their number.  Keys written as 32-bit words go to the library's own radix sort (three 8-bit passes of
-// two launches for a frame's ~24 bits, against the vendor's eight passes over 64-bit keys) whenever it serves the size;
-// KPX_RADIX=0: the vendor sort instead (A/B switch).
+// m-th distinct key, *d_heads = their number.  Key: how the form wrote its keys -- 64-bit words, or 32-bit ones (three 8-bit passes of
+// the own radix sort for a frame's ~24 bits, against the vendor's eight passes over 64-bit keys).
 template <class Key>
 static int voxel_sort_and_heads(const VoxelScratch &s, int64_t total, int end_bit, int32_t *d_heads, hipStream_t st)
 {
-    Key *k_in = reinterpret_cast<Key *>(s.keys_in), *k_out = reinterpret_cast<Key *>(s.keys_out);
-    static const bool vendor_sort = [] { const char *e = getenv("KPX_RADIX"); return e && e[0] == '0'; }();
-    bool cleared = false;
-    if constexpr (sizeof(Key) == 4) {
-        if (total <= kRadixMaxPairs && !vendor_sort) {
-            const int rc = radix_sort_pairs_u32(s.rx, k_in, k_out, s.vals_in, s.vals_out, total, end_bit, st, s.counts_end);
-            if (rc) return rc;
-            cleared = true;
-        }
-    }
-    if (!cleared) {
-        size_t bytes = s.sort_bytes;
-        KPX_HIP(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, bytes, k_in, k_out, s.vals_in, s.vals_out, (int)total, 0, end_bit, st));
-    }
-    return compact(HeadPredT<Key>{ k_out }, HeadEmit{ s.seg_start }, total, 1, s.counts, d_heads, st, cleared);
+    const bool narrow = sizeof(Key) == 4;
+    const DeviceSortView32 v = dsort_view32(s.sort);
+    const bool cleared = narrow && dsort_by_radix(v, total);
+    const int rc = narrow ? dsort_run(v, total, end_bit, st, s.counts_end) : dsort_run(s.sort, total, end_bit, st);
+    if (rc) return rc;
+    return compact(HeadPredT<Key>{ reinterpret_cast<const Key *>(s.sort.keys_out) }, HeadEmit{ s.seg_start }, total, 1, s.counts, d_heads, st, cleared);
 }
 
 // the plain form's scratch: one cloud, 63-bit keys, the vendor sort
-constexpr VoxelCarve kPlainCarve = { 1, kBboxBlocks, false, false, 4, 63 };
+constexpr VoxelCarve kPlainCarve = { 1, kBboxBlocks, false, false, 63 };
 
 }  // namespace kpx

@@ -43,7 +43,8 @@ def _settings(*specs):
 # per-registration drivers keep both placements (KPX_ICP_BATCH_LAUNCH=0, with KPX_ICP_FUSE=0), and neither narrower width measured
 # ahead of 64 (profiles/r06/exp_env_KPX_ICP_ROWS_R.txt).
 FAMILIES = {
-    "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_OCC=0.2", "SOR_OCC=1.0", "BBOX_VEC=0"),
+    # RADIX=0: the grid build above GRID_SORT_MIN points sorts with the vendor sort (kpx_sort.h reads the switch for every site)
+    "grid": _settings("GRID_SCAN=0", "GRID_SORT=1", "SOR_CELL=0", "SOR_CELL=1", "SOR_OCC=0.2", "SOR_OCC=1.0", "BBOX_VEC=0", "RADIX=0"),
     "voxel": _settings("RADIX=0", "VOXEL_SINGLE=0"),
     # the launch-per-iteration chains of icp_rows_kernel: the rows form forced and the one-launch chain off
     "icp": _settings("ICP_FUSE=0", "ICP_BATCH_LAUNCH=0", "ICP_WINDOW=1", "ICP_WINDOW=64", "ICP_ROWS=2+ICP_CHAIN=0"),

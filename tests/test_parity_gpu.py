@@ -2204,12 +2204,19 @@ def test_update_placements_agree_with_four_frames_in_flight(tmp_path):
 
 
 @pytest.mark.parametrize("n,end_bit", [(1, 32), (63, 8), (2048, 9), (2049, 24), (100_003, 27), (1_130_000, 24), (1_130_000, 32), (300_000, 1),
-                                       (4_194_304, 17), (4_200_000, 22)])
+                                       (4_194_304, 17), (4_200_000, 22), (65536, 22), (65537, 22), (4_194_305, 9), (1000, 33)])
 def test_radix_sort_pairs_is_the_stable_sort(ops, n, end_bit):
     """kpx_sort_pairs_u32 (the library's own LSD radix sort up to 4M pairs, rocPRIM above) against numpy's stable argsort of the
     masked keys: keys AND values identical, i.e. equal keys keep their input order; few distinct keys, full-range keys, a
-    partial last tile, all keys equal."""
+    partial last tile, all keys equal.  65536 / 65537: the own sort's first group-row boundary and the grid build's switch;
+    4_194_305 at 9 bits: the vendor sort one pair past the own sort's limit, run below the 32 bits its temporary size was asked for;
+    33 bits: more than the key has, refused."""
+    from kinectpy_amd._lib import KinectPxError
     rng = np.random.default_rng(n + end_bit)
+    if end_bit > 32:
+        with pytest.raises(KinectPxError):
+            ops.sort_pairs_u32(torch.zeros(n, dtype=torch.int32).cuda().view(torch.uint32), torch.arange(n, dtype=torch.int32).cuda(), end_bit)
+        return
     mask = np.uint32((1 << end_bit) - 1) if end_bit < 32 else np.uint32(0xFFFFFFFF)
     for kind in ("random", "few", "equal"):
         if kind == "random":

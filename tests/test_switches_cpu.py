@@ -50,7 +50,7 @@ def test_every_switch_is_documented():
 
 
 def test_matrix_holds_every_setting_once():
-    want = {"grid": 7, "voxel": 2, "icp": 5, "icp_edges": 5, "dense": 1, "frame": 7, "fps": 2}
+    want = {"grid": 8, "voxel": 2, "icp": 5, "icp_edges": 5, "dense": 1, "frame": 7, "fps": 2}
     assert {fam: len(s) for fam, s in M.FAMILIES.items()} == want
     for fam in M.FAMILIES.values():
         for setting, env in fam.items():

@@ -137,6 +137,8 @@ def test_grid_sor_bounds_switches(defaults, grid_oracle, tmp_path, setting):
     if "KPX_GRID_SORT" in env:
         assert M.grid_build_form(len(inp["halo"]), {}) == "count" and M.grid_build_form(len(inp["halo"]), env) == "sort"
         assert M.grid_build_form(len(inp["c70k"]), {}) == "sort"
+    if "KPX_RADIX" in env:
+        assert M.grid_build_form(len(inp["c70k"]), {}) == "sort"         # the build that sorts: by the own radix sort unless switched off
     if "KPX_BBOX_VEC" in env:
         assert M.bbox_form(len(inp["c70k"]), True, {}) == "vec" and M.bbox_form(len(inp["c70k"]), True, env) == "scalar"
     if any(name.startswith("KPX_SOR_") and name != "KPX_SOR_OCC" for name in env):
