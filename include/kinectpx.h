@@ -864,6 +864,46 @@ int kpx_mesh_sample_points(const float *vertices, const float *colors, const flo
                            int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, int64_t n_points, uint64_t seed, float *out_points,
                            float *out_colors, float *out_normals, double *d_total, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- ray casts and closest points on triangle meshes ([O3D] t.geometry.RaycastingScene; arithmetic contract AC14) --
+ * A scene is a caller-owned device buffer of kpx_rayscene_bytes(n_triangles) bytes that kpx_rayscene_build fills from float32 vertices
+ * [n_vertices][3] and int32 triangles [n_triangles][3] (the geometries of a scene concatenated, indices into the concatenated vertices;
+ * every index must lie in [0, n_vertices) and every coordinate must be finite: the caller checks): header, the boxes of an implicit
+ * complete tree (leaves of KPX_RAYSCENE_LEAF triangles consecutive along a space-filling curve, KPX_RAYSCENE_FANOUT children per node),
+ * the corners and ids of the triangles.  triangle_ids (i32 [n_triangles][2], optional): the geometry id and primitive id reported for
+ * each triangle; NULL: geometry 0, primitive = the triangle's index.  The scene does not point back into the mesh and the library keeps
+ * no state.  At most 2^28 triangles (the size queries return 0 beyond).  ws: kpx_rayscene_workspace_bytes(n_triangles).  Asynchronous.
+ * kpx_rayscene_rays: rays f32 [m][6] = origin, direction (not normalised: t is in units of |d|).  All arithmetic fp64, every multiply
+ *     and add separate.  Triangle (v0, v1, v2): e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1.p (0: miss), inv = 1 / det, s = o - v0,
+ *     u = (s.p) inv, q = s x e1, v = (d.q) inv, t = (e2.q) inv; a hit needs u >= 0, v >= 0, u + v <= 1, the ray to meet the triangle's box
+ *     (corner min / max widened by 2^-20 of the largest coordinate magnitude; slab test from tn = 0, tf = +inf) and tn <= t <= tf.  A ray
+ *     with a non-finite component or a zero direction hits nothing.
+ *     KPX_RAY_CAST: the hit of the smallest t, ties to the lowest triangle index: out_t f64 [m] (+inf: miss), out_t_hit f32 [m],
+ *         out_uvs f32 [m][2], out_normals f32 [m][3] (kpx_mesh_normals' normalised normal; a miss: zeros), the two ids i32 [m] (-1: miss).
+ *     KPX_RAY_OCCLUDED: out_count i32 [m] = 1 when some hit has tnear <= t <= tfar, else 0.
+ *     KPX_RAY_COUNT: out_count = the number of triangles hit (a ray through a shared edge counts both).
+ *     Outputs a mode does not write may be NULL.
+ * kpx_rayscene_closest: queries f32 [m][3].  Per triangle Ericson's closest point (regions A, B, AB, C, AC, BC, interior) and
+ *     D = max(d2(q, closest) as AC3, gap2 of the triangle's box); the smallest D wins, ties to the lowest triangle index, a NaN D never
+ *     wins.  out_d2 f64 [m] = D, out_points f32 [m][3], out_distance f32 [m] = (float)sqrt(D), ids i32 [m].  A query with a non-finite
+ *     coordinate gets NaN and -1.  A scene without triangles is KPX_ERR_INVALID.
+ * brute != 0: every triangle is tested in ascending index instead of walking the tree; results are the same bits (second witness and
+ * yardstick).  Every query call reads the scene header back (one small copy and a synchronisation of `stream`) and rejects a buffer
+ * that is not a scene or is smaller than the scene it claims to be. */
+#define KPX_RAYSCENE_LEAF 4
+#define KPX_RAYSCENE_FANOUT 4
+#define KPX_RAY_CAST 0
+#define KPX_RAY_OCCLUDED 1
+#define KPX_RAY_COUNT 2
+size_t kpx_rayscene_bytes(int64_t n_triangles);
+size_t kpx_rayscene_workspace_bytes(int64_t n_triangles);
+int kpx_rayscene_build(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, const int32_t *triangle_ids,
+                       void *scene, size_t scene_bytes, void *ws, size_t ws_bytes, void *stream);
+int kpx_rayscene_rays(const void *scene, size_t scene_bytes, const float *rays, int64_t m, int32_t mode, double tnear, double tfar, int32_t brute,
+                      double *out_t, float *out_t_hit, float *out_uvs, float *out_normals, int32_t *out_geometry_ids, int32_t *out_primitive_ids,
+                      int32_t *out_count, void *stream);
+int kpx_rayscene_closest(const void *scene, size_t scene_bytes, const float *queries, int64_t m, int32_t brute, double *out_d2, float *out_points,
+                         float *out_distance, int32_t *out_geometry_ids, int32_t *out_primitive_ids, void *stream);
+
 /* ---- occupancy grids ([O3D] geometry.VoxelGrid; arithmetic contract AC10) ---------------------------------------- */
 /* A grid is caller-owned: keys u64 [M], strictly ascending, key = gx << 42 | gy << 21 | gz with every index in [0, 2^21), and colors
  * f32 [M][3]; voxel g covers h_origin + g voxel .. h_origin + (g + 1) voxel.  All decisions are fp64.

@@ -1086,3 +1086,214 @@ class TriangleMesh:
         col = self._vcol if self.has_vertex_colors() else None
         pts, c, n = ops.mesh_sample_points(self._vert, self._tri, number_of_points, seed, col, vn, tn)
         return PointCloud._make(pts, c, n)
+
+
+class RaycastingScene:
+    """[O3D] t.geometry.RaycastingScene on the device: ray casts, occlusion tests, intersection counts and closest points on the
+    triangle meshes added to the scene (arithmetic contract AC14; kpx_rayscene_*).  Queries take arrays whose last
+    dimension is 6 (rays: origin, direction; directions are not normalised, t_hit is in units of |d|) or 3 (points); leading
+    dimensions are preserved.  Results are NumPy arrays in Open3D's dtypes -- the uint32 ids are the device's int32 viewed, so -1 reads
+    as INVALID_ID -- or, with device=True, the device tensors of ops.rayscene_*.  The index is built on the first query and rebuilt
+    after a later add_triangles.  Shape and dtype errors raise before the device is touched.
+    Deviations: compute_occupancy / compute_signed_distance cast ONE ray per point (nsamples = 1 only) in the fixed direction
+    (1, 0.375, 0.3125) -- marching-cubes meshes are full of axis-aligned edges, which a ray along +x would graze; a ray through an edge
+    shared by two triangles counts both.  Not built: list_intersections, nsamples > 1, line sets, t.geometry tensors."""
+    INVALID_ID = 0xFFFFFFFF
+    OCCUPANCY_DIRECTION = (1.0, 0.375, 0.3125)
+
+    def __init__(self):
+        self._geoms = []              # (vertices, triangles): host arrays, or a TriangleMesh's device tensors
+        self._scene = None
+
+    # ---- geometries ---------------------------------------------------------------------------
+    def add_triangles(self, vertex_positions, triangle_indices=None):
+        """(vertex_positions float (V, 3), triangle_indices integer (T, 3)), or one TriangleMesh -> the geometry id"""
+        if isinstance(vertex_positions, TriangleMesh):
+            if triangle_indices is not None:
+                raise RuntimeError("RaycastingScene.add_triangles: a TriangleMesh brings its own triangles")
+            pair = (vertex_positions._vert, vertex_positions._tri)
+        else:
+            v, t = vertex_positions, triangle_indices
+            if t is None:
+                raise RuntimeError("RaycastingScene.add_triangles: triangle_indices is missing")
+            if not (isinstance(v, torch.Tensor) and isinstance(t, torch.Tensor)):
+                v, t = np.asarray(v), np.asarray(t)
+                if v.dtype not in (np.float32, np.float64):
+                    raise RuntimeError(f"RaycastingScene.add_triangles: vertex_positions must be float32 or float64, got {v.dtype}")
+                if t.dtype.kind not in "iu":
+                    raise RuntimeError(f"RaycastingScene.add_triangles: triangle_indices must be integers, got {t.dtype}")
+            elif not v.dtype.is_floating_point or t.dtype.is_floating_point:
+                raise RuntimeError("RaycastingScene.add_triangles: vertex_positions must be floating point, triangle_indices integers")
+            if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+                raise RuntimeError(f"RaycastingScene.add_triangles: expected (V, 3) vertices and (T, 3) triangles, got {tuple(v.shape)} and {tuple(t.shape)}")
+            if isinstance(v, np.ndarray):
+                if t.size and (int(t.min()) < 0 or int(t.max()) >= v.shape[0]):
+                    raise RuntimeError(f"RaycastingScene.add_triangles: triangle index out of range [0, {v.shape[0]})")
+                with np.errstate(over="ignore"):
+                    v = v.astype(np.float32)
+                if not np.isfinite(v).all():
+                    raise RuntimeError("RaycastingScene.add_triangles: a vertex coordinate is not finite (after rounding to float32)")
+                t = t.astype(np.int32)
+            pair = (v, t)
+        self._geoms.append(pair)
+        self._scene = None
+        return len(self._geoms) - 1
+
+    def _built(self):
+        if self._scene is None:
+            dev = L.device()
+            verts, tris, ids, base = [], [], [], 0
+            for g, (v, t) in enumerate(self._geoms):
+                v = ops._dev(v, torch.float32).reshape(-1, 3)
+                t = ops._dev(t, torch.int32).reshape(-1, 3)
+                ops._mesh_index_check("RaycastingScene", t, v.shape[0])
+                verts.append(v)
+                tris.append(t + base)
+                ids.append(torch.stack([torch.full((t.shape[0],), g, dtype=torch.int32, device=dev),
+                                        torch.arange(t.shape[0], dtype=torch.int32, device=dev)], 1))
+                base += v.shape[0]
+            if not verts:
+                verts, tris, ids = [torch.zeros((0, 3), dtype=torch.float32, device=dev)], [torch.zeros((0, 3), dtype=torch.int32, device=dev)], \
+                    [torch.zeros((0, 2), dtype=torch.int32, device=dev)]
+            self._scene = ops.rayscene_build(torch.cat(verts), torch.cat(tris), torch.cat(ids))
+        return self._scene
+
+    def _n_triangles(self):
+        return sum(int(t.shape[0]) for _, t in self._geoms)
+
+    # ---- arguments ----------------------------------------------------------------------------
+    @staticmethod
+    def _query(who, a, width):
+        """-> (array or tensor whose last dimension is `width`, its leading shape); raises on any other shape or a non-float dtype"""
+        if isinstance(a, torch.Tensor):
+            ok = a.dtype in (torch.float32, torch.float64)
+        else:
+            a = np.asarray(a)
+            ok = a.dtype in (np.float32, np.float64)
+        if not ok:
+            raise RuntimeError(f"RaycastingScene.{who}: expected float32 or float64, got {a.dtype}")
+        if a.ndim < 1 or a.shape[-1] != width:
+            raise RuntimeError(f"RaycastingScene.{who}: the last dimension must be {width}, got shape {tuple(a.shape)}")
+        if isinstance(a, np.ndarray):
+            with np.errstate(over="ignore"):
+                a = np.ascontiguousarray(a, dtype=np.float32)
+        return a, tuple(a.shape[:-1])
+
+    @staticmethod
+    def _nsamples(who, nsamples):
+        if int(nsamples) != 1:
+            raise NotImplementedError(f"RaycastingScene.{who}: only nsamples = 1 is built")
+
+    @staticmethod
+    def _shaped(t, lead):
+        return t.reshape(lead + tuple(t.shape[1:]))
+
+    # ---- queries ------------------------------------------------------------------------------
+    def cast_rays(self, rays, nthreads=0, device=False):
+        """-> dict: t_hit float32 (+inf: miss), geometry_ids and primitive_ids uint32 (INVALID_ID: miss), primitive_uvs float32 (..., 2),
+        primitive_normals float32 (..., 3) (zeros on a miss)"""
+        rays, lead = self._query("cast_rays", rays, 6)
+        out = ops.rayscene_cast(self._built(), rays)
+        out = {k: self._shaped(v, lead) for k, v in out.items()}
+        if device:
+            return out
+        res = {k: out[k].cpu().numpy() for k in ("t_hit", "geometry_ids", "primitive_ids", "primitive_uvs", "primitive_normals")}
+        res["geometry_ids"], res["primitive_ids"] = res["geometry_ids"].view(np.uint32), res["primitive_ids"].view(np.uint32)
+        return res
+
+    def test_occlusions(self, rays, tnear=0.0, tfar=float("inf"), nthreads=0, device=False):
+        """-> bool (...): some hit has tnear <= t <= tfar"""
+        rays, lead = self._query("test_occlusions", rays, 6)
+        if float(tnear) != float(tnear) or float(tfar) != float(tfar):
+            raise RuntimeError("RaycastingScene.test_occlusions: tnear / tfar is not a number")
+        out = self._shaped(ops.rayscene_occluded(self._built(), rays, tnear, tfar), lead)
+        return out if device else out.cpu().numpy() != 0
+
+    def count_intersections(self, rays, nthreads=0, device=False):
+        """-> int32 (...): the number of triangles the ray hits; a ray through an edge that two triangles share counts both"""
+        rays, lead = self._query("count_intersections", rays, 6)
+        out = self._shaped(ops.rayscene_count(self._built(), rays), lead)
+        return out if device else out.cpu().numpy()
+
+    def _closest(self, who, query_points):
+        q, lead = self._query(who, query_points, 3)
+        if self._n_triangles() == 0:
+            raise RuntimeError(f"RaycastingScene.{who}: the scene holds no triangle")
+        return {k: self._shaped(v, lead) for k, v in ops.rayscene_closest(self._built(), q).items()}, q, lead
+
+    def compute_closest_points(self, query_points, nthreads=0, device=False):
+        """-> dict: points float32 (..., 3), geometry_ids and primitive_ids uint32"""
+        out, _, _ = self._closest("compute_closest_points", query_points)
+        if device:
+            return out
+        return {"points": out["points"].cpu().numpy(), "geometry_ids": out["geometry_ids"].cpu().numpy().view(np.uint32),
+                "primitive_ids": out["primitive_ids"].cpu().numpy().view(np.uint32)}
+
+    def compute_distance(self, query_points, nthreads=0, device=False):
+        """-> float32 (...): the distance to the closest point of the scene"""
+        out, _, _ = self._closest("compute_distance", query_points)
+        return out["distance"] if device else out["distance"].cpu().numpy()
+
+    def _occupied(self, q, lead):
+        """int32 device tensor (...): 1 where the ray from q in OCCUPANCY_DIRECTION hits an odd number of triangles"""
+        q = ops._dev(q, torch.float32).reshape(-1, 3)
+        d = torch.tensor(self.OCCUPANCY_DIRECTION, dtype=torch.float32, device=q.device).expand(q.shape[0], 3)
+        return self._shaped(ops.rayscene_count(self._built(), torch.cat([q, d], 1)) & 1, lead)
+
+    def compute_occupancy(self, query_points, nthreads=0, nsamples=1, device=False):
+        """-> float32 (...): 1 inside a closed surface, 0 outside (one ray per point, see the class's deviations)"""
+        self._nsamples("compute_occupancy", nsamples)
+        q, lead = self._query("compute_occupancy", query_points, 3)
+        out = self._occupied(q, lead).to(torch.float32)
+        return out if device else out.cpu().numpy()
+
+    def compute_signed_distance(self, query_points, nthreads=0, nsamples=1, device=False):
+        """-> float32 (...): compute_distance, negative where compute_occupancy is 1"""
+        self._nsamples("compute_signed_distance", nsamples)
+        out, q, lead = self._closest("compute_signed_distance", query_points)
+        d = out["distance"]
+        d = torch.where(self._occupied(q, lead) != 0, -d, d)
+        return d if device else d.cpu().numpy()
+
+    # ---- rays of a camera (host, fp64) ---------------------------------------------------------
+    @staticmethod
+    def create_rays_pinhole(*args, pixel_center=0.5, **kwargs):
+        """(intrinsic_matrix 3x3, extrinsic_matrix 4x4 world -> camera, width_px, height_px), or (fov_deg, center, eye, up, width_px,
+        height_px) -> float32 (H, W, 6).  Pixel (y, x): origin -(R^T t), direction R^T ((x + c - cx) / fx, (y + c - cy) / fy, 1) with
+        c = pixel_center.  The default 0.5 is Open3D's; with 0.0 the ray goes through the centre of pixel (x, y) of this library's depth
+        images (pixel u covers [u - 0.5, u + 0.5)), and because its camera-frame z is 1, t_hit is the depth."""
+        fov = "fov_deg" in kwargs or (len(args) > 0 and np.ndim(args[0]) == 0)
+        names = ("fov_deg", "center", "eye", "up", "width_px", "height_px") if fov else ("intrinsic_matrix", "extrinsic_matrix", "width_px", "height_px")
+        if len(args) > len(names) or any(k not in names[len(args):] for k in kwargs) or len(args) + len(kwargs) != len(names):
+            raise RuntimeError(f"RaycastingScene.create_rays_pinhole: expected {names}")
+        a = dict(zip(names, args), **kwargs)
+        W, H = int(a["width_px"]), int(a["height_px"])
+        if W < 0 or H < 0:
+            raise RuntimeError("RaycastingScene.create_rays_pinhole: negative image size")
+        if fov:
+            fov_deg = float(a["fov_deg"])
+            if not 0.0 < fov_deg < 180.0:
+                raise RuntimeError("RaycastingScene.create_rays_pinhole: fov_deg must lie in (0, 180)")
+            center, eye, up = (np.asarray(a[k], dtype=np.float64).reshape(3) for k in ("center", "eye", "up"))
+            fx = fy = 0.5 * W / np.tan(0.5 * np.deg2rad(fov_deg))
+            cx, cy = 0.5 * W, 0.5 * H
+            norm = lambda v: v / np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+            z = norm(center - eye)
+            x = norm(np.cross(z, up))
+            R = np.stack([x, np.cross(z, x), z])
+            t = -(R @ eye)
+        else:
+            K = np.asarray(a["intrinsic_matrix"], dtype=np.float64)
+            E = np.asarray(a["extrinsic_matrix"], dtype=np.float64)
+            if K.shape != (3, 3) or E.shape != (4, 4):
+                raise RuntimeError("RaycastingScene.create_rays_pinhole: expected a 3x3 intrinsic and a 4x4 extrinsic matrix")
+            fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+            R, t = E[:3, :3], E[:3, 3]
+        c = float(pixel_center)
+        a_ = ((np.arange(W, dtype=np.float64) + c) - cx) / fx                     # (W,)
+        b_ = ((np.arange(H, dtype=np.float64) + c) - cy) / fy                     # (H,)
+        rays = np.empty((H, W, 6), dtype=np.float64)
+        for k in range(3):
+            rays[:, :, k] = -((R[0, k] * t[0] + R[1, k] * t[1]) + R[2, k] * t[2])
+            rays[:, :, 3 + k] = (R[0, k] * a_[None, :] + R[1, k] * b_[:, None]) + R[2, k]
+        return rays.astype(np.float32)

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import ops
 from .geometry import (Image, ImageFilterType, KDTreeFlann, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, Matrix3dVector,
-                       OrientedBoundingBox, PointCloud, RGBDImage, TriangleMesh, FilterScope, Vector2iVector, Vector3dVector, Vector3iVector, Voxel,
+                       OrientedBoundingBox, PointCloud, RaycastingScene, RGBDImage, TriangleMesh, FilterScope, Vector2iVector, Vector3dVector, Vector3iVector, Voxel,
                        VoxelGrid, _off_path)
 from . import integration as _integration
 from . import odometry as _odometry
@@ -451,6 +451,8 @@ geometry = types.SimpleNamespace(PointCloud=PointCloud, OrientedBoundingBox=Orie
                                  Image=Image, ImageFilterType=ImageFilterType, RGBDImage=RGBDImage, Voxel=Voxel, VoxelGrid=VoxelGrid,
                                  TriangleMesh=TriangleMesh, FilterScope=FilterScope,
                                  keypoint=types.SimpleNamespace(compute_iss_keypoints=compute_iss_keypoints))
+# [O3D] o3d.t.geometry: only the mesh-query class; it takes NumPy arrays (or a legacy TriangleMesh), not t.geometry tensors
+t = types.SimpleNamespace(geometry=types.SimpleNamespace(RaycastingScene=RaycastingScene))
 camera = types.SimpleNamespace(PinholeCameraIntrinsic=PinholeCameraIntrinsic, PinholeCameraParameters=PinholeCameraParameters)
 utility = types.SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, Vector3iVector=Vector3iVector,
                                 Matrix3dVector=Matrix3dVector)

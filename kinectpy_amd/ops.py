@@ -1659,3 +1659,102 @@ def rgbd_odometry(depth_s, color_s, depth_t, color_t, width, height, intrinsic, 
                                   float(depth_diff_max), float(depth_min), float(depth_max), L.ptr(res), ws, wsz, L.stream_ptr()))
     r = res.cpu().numpy()
     return r[:, 0] != 0.0, r[:, 2:18].reshape(P, 4, 4).copy(), r[:, 18:54].reshape(P, 6, 6).copy(), r[:, 1].astype(np.int64)
+
+
+# ---- ray casts and closest points on triangle meshes (AC14) -----------------------------
+RAY_MODES = {"cast": 0, "occluded": 1, "count": 2}          # KPX_RAY_* (include/kinectpx.h)
+
+
+class RayScene:
+    """device buffer of a scene of T triangles (kpx_rayscene_build): self-contained, it does not refer to the meshes it was built from"""
+
+    def __init__(self, buf, n):
+        self.buf, self.n = buf, int(n)
+
+    def __len__(self):
+        return self.n
+
+
+def rayscene_build(vertices, triangles, triangle_ids=None):
+    """scene of float32 (V, 3) vertices and int32 (T, 3) triangles (several geometries: concatenated, indices into the concatenated
+    vertices); triangle_ids int32 (T, 2): the (geometry id, primitive id) reported for each triangle, None: (0, index).  Indices
+    outside [0, V) and non-finite vertices raise here (three host reads)."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("rayscene_build", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    if nt and not bool(torch.isfinite(vert).all()):
+        raise L.KinectPxError("rayscene_build: a vertex coordinate is not finite")
+    ids = None
+    if triangle_ids is not None:
+        ids = _dev(triangle_ids, torch.int32).reshape(-1, 2)
+        if ids.shape[0] != nt:
+            raise L.KinectPxError(f"rayscene_build: {ids.shape[0]} id rows for {nt} triangles")
+    size = lib.kpx_rayscene_bytes(nt)
+    if size == 0:
+        raise L.KinectPxError(f"rayscene_build: {nt} triangles: a scene holds at most 2^28")
+    buf = torch.empty(size, dtype=torch.uint8, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_rayscene_workspace_bytes(nt))
+    L.check(lib.kpx_rayscene_build(L.ptr(vert), nv, L.ptr(tri), nt, L.ptr(ids), L.ptr(buf), buf.numel(), ws, wsz, L.stream_ptr()))
+    return RayScene(buf, nt)
+
+
+def _rays(rays):
+    return _dev(rays, torch.float32).reshape(-1, 6)
+
+
+def rayscene_cast(scene, rays, brute=False):
+    """[O3D] RaycastingScene.cast_rays for M rays (origin, direction) -> dict of device tensors: t_hit float32 (M,) (+inf: miss),
+    primitive_uvs float32 (M, 2), primitive_normals float32 (M, 3), geometry_ids and primitive_ids int32 (M,) (-1: miss), and
+    `t` float64 (M,), the hit parameter before its rounding.  brute: every triangle is tested (same bits)."""
+    lib = L.load()
+    r = _rays(rays)
+    m, dev = r.shape[0], r.device
+    out = {"t": torch.empty(m, dtype=torch.float64, device=dev), "t_hit": torch.empty(m, dtype=torch.float32, device=dev),
+           "primitive_uvs": torch.empty((m, 2), dtype=torch.float32, device=dev),
+           "primitive_normals": torch.empty((m, 3), dtype=torch.float32, device=dev),
+           "geometry_ids": torch.empty(m, dtype=torch.int32, device=dev), "primitive_ids": torch.empty(m, dtype=torch.int32, device=dev)}
+    L.check(lib.kpx_rayscene_rays(L.ptr(scene.buf), scene.buf.numel(), L.ptr(r), m, RAY_MODES["cast"], 0.0, float("inf"), int(bool(brute)),
+                                  L.ptr(out["t"]), L.ptr(out["t_hit"]), L.ptr(out["primitive_uvs"]), L.ptr(out["primitive_normals"]),
+                                  L.ptr(out["geometry_ids"]), L.ptr(out["primitive_ids"]), None, L.stream_ptr()))
+    return out
+
+
+def _rayscene_counts(scene, rays, mode, tnear, tfar, brute):
+    lib = L.load()
+    tnear, tfar = float(tnear), float(tfar)
+    if tnear != tnear or tfar != tfar:
+        raise L.KinectPxError("rayscene: tnear / tfar is not a number")
+    r = _rays(rays)
+    m = r.shape[0]
+    cnt = torch.empty(m, dtype=torch.int32, device=r.device)
+    L.check(lib.kpx_rayscene_rays(L.ptr(scene.buf), scene.buf.numel(), L.ptr(r), m, RAY_MODES[mode], tnear, tfar, int(bool(brute)), None, None, None,
+                                  None, None, None, L.ptr(cnt), L.stream_ptr()))
+    return cnt
+
+
+def rayscene_occluded(scene, rays, tnear=0.0, tfar=float("inf"), brute=False):
+    """[O3D] RaycastingScene.test_occlusions -> int32 (M,) device tensor: 1 where some hit has tnear <= t <= tfar"""
+    return _rayscene_counts(scene, rays, "occluded", tnear, tfar, brute)
+
+
+def rayscene_count(scene, rays, brute=False):
+    """[O3D] RaycastingScene.count_intersections -> int32 (M,) device tensor: the triangles each ray hits (a ray through a shared
+    edge counts both of its triangles)"""
+    return _rayscene_counts(scene, rays, "count", 0.0, float("inf"), brute)
+
+
+def rayscene_closest(scene, queries, brute=False):
+    """[O3D] RaycastingScene.compute_closest_points for M points -> dict of device tensors: points float32 (M, 3), distance float32
+    (M,), d2 float64 (M,) (the squared distance before the root), geometry_ids and primitive_ids int32 (M,).  A query with a
+    non-finite coordinate gets NaN and -1; a scene without triangles raises."""
+    lib = L.load()
+    if scene.n == 0:
+        raise L.KinectPxError("rayscene_closest: the scene holds no triangle")
+    q = _dev(queries, torch.float32).reshape(-1, 3)
+    m, dev = q.shape[0], q.device
+    out = {"points": torch.empty((m, 3), dtype=torch.float32, device=dev), "distance": torch.empty(m, dtype=torch.float32, device=dev),
+           "d2": torch.empty(m, dtype=torch.float64, device=dev), "geometry_ids": torch.empty(m, dtype=torch.int32, device=dev),
+           "primitive_ids": torch.empty(m, dtype=torch.int32, device=dev)}
+    L.check(lib.kpx_rayscene_closest(L.ptr(scene.buf), scene.buf.numel(), L.ptr(q), m, int(bool(brute)), L.ptr(out["d2"]), L.ptr(out["points"]),
+                                     L.ptr(out["distance"]), L.ptr(out["geometry_ids"]), L.ptr(out["primitive_ids"]), L.stream_ptr()))
+    return out

@@ -6,7 +6,7 @@ sensor sees through (flying pixels), which the density filters keep."""
 import numpy as np
 import torch
 
-from ..geometry import VoxelGrid
+from ..geometry import RaycastingScene, VoxelGrid
 from ..integration import TSDFVolumeColorType, UniformTSDFVolume
 from ..utils import synth
 
@@ -66,3 +66,23 @@ def remove_free_space_points(pcd, depth, intrinsic, sensor_to_master, voxel_size
     if not pcd.has_points() or kept.numel() == 0:
         return type(pcd)(), kept
     return pcd._select(kept), kept
+
+
+def render_mesh_depth(mesh, intrinsic, sensor_to_master, width=None, height=None):
+    """the depth images the sensors of fuse_depth_tsdf would take of `mesh` (a TriangleMesh in the master's frame): intrinsic and
+    sensor_to_master as there (sensor 0 is the master), width x height default to the intrinsic's.  All sensors' rays go through one
+    RaycastingScene.cast_rays: pixel (y, x) of sensor s casts the ray through its centre (create_rays_pinhole with pixel_center=0.0
+    and the extrinsic inv(sensor_to_master[s])), whose camera-frame z is 1, so t_hit is the depth along the optical axis -- in the
+    mesh's unit, not divided by a depth scale.  -> float32 (S, H, W) host array, 0 where the ray misses, as in a depth image."""
+    if intrinsic is None:
+        intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
+    W = int(intrinsic.width if width is None else width)
+    H = int(intrinsic.height if height is None else height)
+    if W <= 0 or H <= 0:
+        raise RuntimeError(f"render_mesh_depth: bad image size {W} x {H}")
+    extr = [np.eye(4)] + [np.linalg.inv(np.asarray(T, dtype=np.float64).reshape(4, 4)) for T in sensor_to_master]
+    rays = np.stack([RaycastingScene.create_rays_pinhole(intrinsic.intrinsic_matrix, E, W, H, pixel_center=0.0) for E in extr])
+    scene = RaycastingScene()
+    scene.add_triangles(mesh)
+    t = scene.cast_rays(rays)["t_hit"]
+    return np.where(np.isfinite(t), t, np.float32(0.0)).astype(np.float32)

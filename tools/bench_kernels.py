@@ -53,6 +53,7 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
     ap.add_argument("--mesh", action="store_true", help="only the mesh clean-up rows")
+    ap.add_argument("--raycast", action="store_true", help="only the mesh query rows (RaycastingScene)")
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     a = ap.parse_args()
@@ -61,6 +62,8 @@ def main():
         return tsdf_rows(dev, a.quick)
     if a.mesh:
         return mesh_rows(dev, a.quick)
+    if a.raycast:
+        return raycast_rows(dev, a.quick)
     if a.voxelgrid:
         return voxelgrid_rows(dev, a.quick)
     if a.odometry:
@@ -315,6 +318,7 @@ def main():
            **sweep(ops.prof_end()))
     tsdf_rows(dev, a.quick)
     mesh_rows(dev, a.quick)
+    raycast_rows(dev, a.quick)
     voxelgrid_rows(dev, a.quick)
     odometry_rows(dev, a.quick)
 
@@ -403,6 +407,65 @@ def mesh_rows(dev, quick):
     ms, _ = timed(lambda: ops.mesh_sample_points(vert, tri, 100000))
     report(f"mesh sample_points_uniformly 100k ({tag}; area chain + split + points + host read)", ms, 12 * nt + 12 * nv + 12 * 100000, vertices=nv,
            triangles=nt)
+
+
+def raycast_rows(dev, quick):
+    """Mesh queries on the mesh of the fused ring volume (resolution 512, 256 with --quick), moved into the master's
+    frame: the scene build, the depth images of the four 640x576 ring sensors (the cast alone on rays that are already on the device,
+    and render_mesh_depth whole: host rays, upload, cast, download), 100 000 closest-point queries taken evenly from the volume's
+    surface cloud, and the brute form of both on every 360th ray and every 25th query."""
+    import time
+    from kinectpy_amd.geometry import RaycastingScene, TriangleMesh
+    from kinectpy_amd.preprocessing import fusion
+    S = 4
+    _, depth, _, _, truth = synth.sensor_ring(S, 1)
+    depth_d = [torch.as_tensor(depth[0, s]).to(dev) for s in range(S)]
+    extr = np.stack([np.linalg.inv(synth.camera_pose(g, S)) for g in range(S)])
+    K, origin, length = (synth.FX, synth.FY, synth.CX, synth.CY), (-1000.0, -1100.0, -1000.0), 2000.0
+    res = 256 if quick else 512
+    vl = length / res
+    vol = torch.zeros((res ** 3, 2), dtype=torch.float32, device=dev)
+    ops.tsdf_integrate(vol, None, res, vl, origin, 4 * vl, depth_d, None, synth.W, synth.H, K, extr, 1.0, 6000.0)
+    vert, _, tri = ops.tsdf_extract_mesh(vol, None, res, vl, origin)
+    cloud, _, _ = ops.tsdf_extract(vol, None, res, vl, origin, "surface", want_normals=False)
+    del vol
+    vert, cloud = ops.transform(vert, extr[0]), ops.transform(cloud, extr[0])          # world -> the master's frame
+    nv, nt = int(vert.shape[0]), int(tri.shape[0])
+    tag = f"ring mesh of res {res}"
+    ms, scene = timed(lambda: ops.rayscene_build(vert, tri))
+    report(f"rayscene build ({tag}; centroids + curve sort + leaves + levels; 3 host reads of the index check)", ms, 12 * nt + 12 * nv + int(scene.buf.numel()),
+           vertices=nv, triangles=nt, scene_bytes=int(scene.buf.numel()))
+    intr = fusion._Intrinsic(synth.W, synth.H, *K)
+    s2m = [np.eye(4)] + [np.asarray(T, dtype=np.float64) for T in truth]
+    rays = np.stack([RaycastingScene.create_rays_pinhole(intr.intrinsic_matrix, np.linalg.inv(T), synth.W, synth.H, pixel_center=0.0) for T in s2m])
+    rays_d = torch.as_tensor(rays.reshape(-1, 6)).to(dev)
+    nr = int(rays_d.shape[0])
+    ms, out = timed(lambda: ops.rayscene_cast(scene, rays_d))
+    hits = int(torch.isfinite(out["t_hit"]).sum().item())
+    report(f"rayscene cast, {S} x {synth.W}x{synth.H} pinhole rays ({tag}; device rays, one launch + header read)", ms, rays=nr, hits=hits,
+           Mrays_per_s=round(nr / ms / 1e3, 1))
+    mesh = TriangleMesh._make(vert, tri)
+    walls = []
+    for _ in range(7):
+        t0 = time.perf_counter()
+        img = fusion.render_mesh_depth(mesh, intr, truth)
+        walls.append((time.perf_counter() - t0) * 1e3)
+    report(f"render_mesh_depth {S} x {synth.W}x{synth.H} ({tag}; host wall time, median of 5 after 2: host rays + scene build + cast + download)",
+           float(np.median(walls[2:])), rays=nr, hits=int((img > 0).sum()))
+    sub = rays_d[::360].contiguous()
+    ms, _ = timed(lambda: ops.rayscene_cast(scene, sub))
+    ms_b, _ = timed(lambda: ops.rayscene_cast(scene, sub, brute=True))
+    report(f"rayscene cast, every 360th ray ({tag}): hierarchy", ms, rays=int(sub.shape[0]))
+    report(f"rayscene cast, every 360th ray ({tag}): brute", ms_b, rays=int(sub.shape[0]), brute_over_hierarchy=round(ms_b / ms, 1))
+    nq = 100000
+    q = cloud[:: max(1, int(cloud.shape[0]) // nq)][:nq].contiguous()
+    ms, _ = timed(lambda: ops.rayscene_closest(scene, q))
+    report(f"rayscene closest points, {int(q.shape[0])} surface points ({tag})", ms, queries=int(q.shape[0]), Mqueries_per_s=round(int(q.shape[0]) / ms / 1e3, 1))
+    subq = q[::25].contiguous()
+    ms, _ = timed(lambda: ops.rayscene_closest(scene, subq))
+    ms_b, _ = timed(lambda: ops.rayscene_closest(scene, subq, brute=True))
+    report(f"rayscene closest points, every 25th query ({tag}): hierarchy", ms, queries=int(subq.shape[0]))
+    report(f"rayscene closest points, every 25th query ({tag}): brute", ms_b, queries=int(subq.shape[0]), brute_over_hierarchy=round(ms_b / ms, 1))
 
 
 def voxelgrid_rows(dev, quick):
