@@ -8,14 +8,17 @@
 //                   contract of the correspondence search is stated at its top
 //   kpx_icpsolve.h  the update step: Kabsch / point-to-plane solve, convergence, LightSkip's bookkeeping, the solve kernels
 //   kpx_nnlocal.h   the culled search (sweep_wave) and a bare search's kernels
-//   kpx_icpiter.h   one iteration of the culled registration in one kernel: per registration, per batch, the whole chain in one launch
-//   kpx_icprows.h   the same iteration with a wave per 64 rows (the calm iterations)
+//   kpx_icpiter.h   one iteration of the culled registration in one kernel: per registration, per batch, the whole chain in one launch;
+//                   above icp_iter_body the pieces every form of the iteration shares (certificate skin / test / word, the self-check's
+//                   bookkeeping, the winner's step); the row bound and the pair terms, which the searches use too, are in kpx_icpdefs.h
+//   kpx_icprows.h   the same iteration with a wave per 64 rows (the calm iterations), same argument block and shared pieces
 //   kpx_icpchain.h  host: which one-launch chains may be resident together
 // Below: the switches (IcpSwitches), profiling read-backs, plans and workspace, the search launches, what the entry points share (NnProblem: setup
 // and the correspondences' way out; icp_search_solve_loop), the exported entry points, and the batch driver (batch_carve, icp_batch_ordered
-// with drive_grouped / drive_windowed / drive_dense_polled).  Each culled driver has one job: drive_grouped runs up to eight registrations
-// per launch with the update in the last block of every registration's sweep; drive_windowed runs a chain per registration with the
-// update in the next sweep's prologue, or (KPX_ICP_FUSE=0, as kpx_icp does) in its own kernel behind the kernel boundary.
+// with drive_grouped / drive_windowed / drive_dense_polled).  Each culled driver has one job: drive_grouped runs the registrations of a
+// batch the sort ordered (at most seven) in one launch per iteration on the caller's stream, with the update in the last block of every
+// registration's sweep; drive_windowed runs a chain per registration on the lanes with the update in the next sweep's prologue, or
+// (KPX_ICP_FUSE=0, as kpx_icp does) in its own kernel behind the kernel boundary.
 #include <chrono>
 #include <limits.h>
 #include <string.h>
@@ -42,7 +45,7 @@ namespace kpx {
 // first use (local_engine() below, chain_form_on() in kpx_icpchain.h).
 struct IcpSwitches {
     bool nn_screen;            // KPX_NN_SCREEN=0: dense engine without its float32 screening sweep; default on (tools/nn_dense_probe.py)
-    bool batch_launch;         // KPX_ICP_BATCH_LAUNCH=0: one launch chain per registration; default one per group of 8
+    bool batch_launch;         // KPX_ICP_BATCH_LAUNCH=0: one launch chain per registration; default one for the batch where one sort orders it, up to 7
     bool fuse;                 // KPX_ICP_FUSE=0: per-registration chains with the update in its own kernel, and no grouped chain; default on
     int window;                // KPX_ICP_WINDOW=1..64: launches of a group queued ahead of the newest progress word; default (and out of range) 3 (profiles/r04/exp_icp_window.txt)
     double stall_seconds;      // KPX_ICP_STALL_SECONDS>0: watchdog of the launch windows; default 60
@@ -1034,29 +1037,6 @@ int kpx::icp_chain_abort_take()
 
 namespace kpx {
 
-// icp_rows_kernel (a wave per 64 rows): problems given as IcpProblems, each at its own iteration k[c]
-static void rows_launch(const IcpProblem *const *probs, const int *ks, int cnt, double md2, int mode, int max_iter, double rel_fit, double rel_rmse,
-                        unsigned long long *visits, int light, CertPolicy pol, hipStream_t st)
-{
-    RowsArgs ra;
-    ra.count = cnt;
-    unsigned b0 = 0;
-    for (int c = 0; c < kRowsBatchMax; ++c) {
-        const int cc = c < cnt ? c : cnt - 1;
-        const IcpProblem &Q = *probs[cc];
-        RowsProblem &Rp = ra.p[c];
-        Rp.src_sorted = Q.src_sorted; Rp.idx_sorted = Q.idx_sorted; Rp.ptgt_sorted = Q.ptgt_sorted; Rp.cert = Q.cert; Rp.thist = Q.thist;
-        Rp.light_key = Q.light_key; Rp.sbbox = Q.sbbox; Rp.state = Q.pair; Rp.ring = Q.ring; Rp.result = Q.result;
-        Rp.progress = Q.progress; Rp.tag = Q.tag; Rp.tgt = Q.tgt; Rp.tn = Q.tn; Rp.Bs = Q.Bs; Rp.orig = Q.orig; Rp.tile_box = Q.tile_box; Rp.group_box = Q.group_box;
-        Rp.tbbox = Q.tbbox; Rp.n = Q.n; Rp.n_groups = Q.n_groups; Rp.k = ks[cc];
-        Rp.block0 = b0; Rp.blocks = (unsigned)cdiv(Q.n, kRowsBlock);
-        if (c < cnt) b0 += Rp.blocks;
-    }
-    if (mode == 1) hipLaunchKernelGGL(icp_rows_kernel<1>, dim3(b0), dim3(64), 0, st, ra, md2, max_iter, rel_fit, rel_rmse, visits, light, pol);
-    else hipLaunchKernelGGL(icp_rows_kernel<0>, dim3(b0), dim3(64), 0, st, ra, md2, max_iter, rel_fit, rel_rmse, visits, light, pol);
-}
-
-
 // ---- the batch driver ---------------------------------------------------------------------------------------------------------------
 // Host side of a launch window (both culled drivers).  Every update step publishes a word in pinned host memory:
 //     generation (24 bits) << 40 | searched share in 1/127ths (7 bits) << 33 | converged << 32 | iterations finished (32 bits)
@@ -1120,11 +1100,9 @@ struct BatchCtx {
     const NnPlan *plans, *tplan;
     const NnBuffers *bufs;
     bool ordered;              // clouds and target already lie in curve order (the batch sort)
-    hipStream_t st;            // the caller's stream
-    hipStream_t *lanes;
-    int n_chain;               // chains of launches: groups (drive_grouped) or problems
-    bool on_caller;            // a single group runs on the caller's stream itself (no fork / join events)
-    hipStream_t lane(int chain) const { return on_caller ? st : lanes[chain % kLaneCount]; }
+    hipStream_t st;            // the caller's stream (drive_grouped runs on it: no fork / join events)
+    hipStream_t *lanes;        // the per-problem drivers: problem i runs on lane(i)
+    hipStream_t lane(int problem) const { return lanes[problem % kLaneCount]; }
 };
 
 // development aid (KPX_ICP_CHAIN_DUMP=1): the records of every registration of a one-launch chain, per iteration
@@ -1145,10 +1123,13 @@ static void chain_dump_records(const IcpBatchArgs &A, hipStream_t ls)
     }
 }
 
-// Culled engine, clouds ordered by the batch sort: ONE chain of launches for up to kIcpBatchMax problems (icp_iter_batch_kernel /
-// icp_rows_kernel), or the whole chain in one launch (icp_chain_kernel) where it may be resident.
+// Culled engine, clouds ordered by the batch sort: ONE chain of launches for all problems of the batch (icp_iter_batch_kernel /
+// icp_rows_kernel), or the whole chain in one launch (icp_chain_kernel) where it may be resident; on the caller's stream.
+// The batch sort orders the target and the sources together, so what it takes always fits one launch:
+static_assert(kMortonBatchMax - 1 <= kIcpBatchMax, "a batch ordered by one sort is one group of launches");
 static int drive_grouped(const BatchCtx &x)
 {
+    KPX_REQUIRE(x.count <= kIcpBatchMax, "kpx_icp_batch: %d registrations in one group of launches", x.count);
     const IcpSwitches &sw = icp_switches();
     ProgressWindow pw;
     int rc = pw.open(sw.stall_seconds);
@@ -1177,92 +1158,76 @@ static int drive_grouped(const BatchCtx &x)
     const int rows_mode = sw.rows;
     const int rows_share = sw.rows_share;
     const NnBuffers &tb = x.bufs[0];                       // (the target's operands are shared)
-    IcpBatchArgs A[8];                                     // count <= 64: at most 8 groups
-    int gk[8];
-    bool gfin[8];
-    for (int g = 0; g < x.n_chain; ++g) {
-        hipStream_t ls = x.lane(g);
-        const int i0 = g * kIcpBatchMax, i1 = i0 + kIcpBatchMax < x.count ? i0 + kIcpBatchMax : x.count;
-        Mat16x8 T0;
-        unsigned b0 = 0;
-        for (int c = 0; c < kIcpBatchMax; ++c) {
-            const int i = i0 + c < i1 ? i0 + c : i1 - 1;      // unused slots repeat the last problem (never addressed: count bounds the search)
-            const NnBuffers &b = x.bufs[i];
-            IcpProblem &P = A[g].p[c];
-            P.src = x.h_src[i]; P.row_of = b.row_of; P.src_sorted = b.src_sorted; P.idx_sorted = b.idx_sorted;
-            P.ptgt_sorted = b.ptgt_sorted; P.pair = b.state;
-            P.idx_cur = nullptr; P.d2_cur = nullptr;          // a batch reports transforms, not correspondence lists
-            P.ring = b.acc_fixed; P.result = x.d_results + 20 * i; P.progress = &pw.words[i]; P.n = x.h_n_src[i];
-            P.light_key = b.light_key; P.sbbox = b.sort_s.bbox; P.cert = b.cert_sorted; P.thist = b.thist;
-            P.chain_rec = chain_ok ? b.chain_rec : nullptr;
-            P.block0 = b0; P.blocks = (unsigned)cdiv(x.h_n_src[i], kIRows);
-            P.tgt = x.tgt; P.tn = x.tgt_normals; P.Bs = tb.Bs; P.orig = tb.orig_t; P.tile_box = tb.tile_box; P.group_box = tb.group_box;
-            P.tbbox = tb.sort_t.bbox; P.n_groups = x.tplan->l_groups; P.k = 0; P.tag = tag;
-            for (int e = 0; e < 16; ++e) T0.m[c][e] = x.h_init[16 * i + e];
-            if (i0 + c < i1) { b0 += P.blocks; pw.clear(i); }
-        }
-        A[g].count = i1 - i0;
-        gk[g] = 0; gfin[g] = false;
-        hipLaunchKernelGGL(icp_batch_init_kernel, dim3(b0), dim3(256), 0, ls, A[g], T0);
-        if (chain_ok) {
-            const bool launched = chain_launch_if_fits(b0, ls, sw.chain_budget, sw.chain_no_lock, [&] {
-                ProfScope prof(KPX_PROF_NN_LOCAL, 0.0, ls);
-                hipLaunchKernelGGL(icp_chain_kernel, dim3(b0), dim3(kIThreads), 0, ls, A[g], x.tgt, x.tgt_normals, tb.Bs, tb.orig_t, tb.tile_box,
-                                   tb.group_box, x.tplan->l_groups, tb.sort_t.bbox, x.md2, x.mode, x.max_iteration, x.relative_fitness, x.relative_rmse, tag,
-                                   prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, light, cert_policy, sw.chain_wait_ticks, chain_abort_word());
-            });
-            if (launched) gfin[g] = true;
-            if (launched && sw.chain_dump) chain_dump_records(A[g], ls);
-        }
+    hipStream_t ls = x.st;
+    IcpBatchArgs A;
+    Mat16x8 T0;
+    unsigned b0 = 0;
+    for (int c = 0; c < kIcpBatchMax; ++c) {
+        const int i = c < x.count ? c : x.count - 1;          // unused slots repeat the last problem (never addressed: count bounds the search)
+        const NnBuffers &b = x.bufs[i];
+        IcpProblem &P = A.p[c];
+        P.src = x.h_src[i]; P.row_of = b.row_of; P.src_sorted = b.src_sorted; P.idx_sorted = b.idx_sorted;
+        P.ptgt_sorted = b.ptgt_sorted; P.pair = b.state;
+        P.idx_cur = nullptr; P.d2_cur = nullptr;              // a batch reports transforms, not correspondence lists
+        P.ring = b.acc_fixed; P.result = x.d_results + 20 * i; P.progress = &pw.words[i]; P.n = x.h_n_src[i];
+        P.light_key = b.light_key; P.sbbox = b.sort_s.bbox; P.cert = b.cert_sorted; P.thist = b.thist;
+        P.chain_rec = chain_ok ? b.chain_rec : nullptr;
+        P.block0 = b0; P.blocks = (unsigned)cdiv(x.h_n_src[i], kIRows);
+        P.tgt = x.tgt; P.tn = x.tgt_normals; P.Bs = tb.Bs; P.orig = tb.orig_t; P.tile_box = tb.tile_box; P.group_box = tb.group_box;
+        P.tbbox = tb.sort_t.bbox; P.n_groups = x.tplan->l_groups; P.k = 0; P.tag = tag;
+        for (int e = 0; e < 16; ++e) T0.m[c][e] = x.h_init[16 * i + e];
+        if (c < x.count) { b0 += P.blocks; pw.clear(i); }
     }
-    for (bool pending = true; pending && !rc;) {
-        pending = false;
-        bool advanced = false;
-        for (int g = 0; g < x.n_chain; ++g) {
-            if (gfin[g]) continue;
-            int seen = INT_MAX, share = 0;
-            bool all_done = true;
-            // the launches still to be queued carry only the registrations that have not converged yet (as far as the host
-            // knows: the progress words lag by up to `window` launches); a converged problem's blocks in an already queued
-            // launch read its state and return
-            IcpBatchArgs act;
-            act.count = 0;
-            unsigned ab = 0;
-            for (int c = 0; c < A[g].count; ++c) {
-                const ProgressWindow::Word w = pw.read(g * kIcpBatchMax + c);
-                if (w.converged) continue;
-                all_done = false;
-                seen = w.seen < seen ? w.seen : seen;
-                share = w.share > share ? w.share : share;
-                act.p[act.count] = A[g].p[c];
-                act.p[act.count].block0 = ab;
-                ab += A[g].p[c].blocks;
-                ++act.count;
-            }
-            if (all_done) { gfin[g] = true; continue; }
-            for (int c = act.count; c < kIcpBatchMax; ++c) act.p[c] = act.p[act.count - 1];
-            hipStream_t ls = x.lane(g);
-            while (gk[g] <= x.max_iteration && gk[g] - seen < window) {
-                advanced = true;
-                ProfScope prof(KPX_PROF_NN_LOCAL, 0.0, ls);
-                if (rows_mode == 2 || (rows_mode == 1 && share <= rows_share)) {
-                    // one wave per 64 rows (kpx_icprows.h): every problem with its own operands and iteration number
-                    const IcpProblem *pp[kRowsBatchMax];
-                    int ks[kRowsBatchMax];
-                    for (int c = 0; c < act.count; ++c) { pp[c] = &act.p[c]; ks[c] = gk[g]; }
-                    rows_launch(pp, ks, act.count, x.md2, x.mode, x.max_iteration, x.relative_fitness, x.relative_rmse,
-                                prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, light, cert_policy, ls);
-                    ++gk[g];
-                    continue;
-                }
-                for (int c = 0; c < kIcpBatchMax; ++c) act.p[c].k = gk[g];
-                hipLaunchKernelGGL(icp_iter_batch_kernel, dim3(ab), dim3(kIThreads), 0, ls, act, x.md2, x.mode, x.max_iteration, x.relative_fitness,
-                                   x.relative_rmse, prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, light, cert_policy);
-                ++gk[g];
-            }
-            if (gk[g] > x.max_iteration) { gfin[g] = true; continue; }
-            pending = true;
+    A.count = x.count;
+    hipLaunchKernelGGL(icp_batch_init_kernel, dim3(b0), dim3(256), 0, ls, A, T0);
+    bool chained = false;
+    if (chain_ok) {
+        chained = chain_launch_if_fits(b0, ls, sw.chain_budget, sw.chain_no_lock, [&] {
+            ProfScope prof(KPX_PROF_NN_LOCAL, 0.0, ls);
+            hipLaunchKernelGGL(icp_chain_kernel, dim3(b0), dim3(kIThreads), 0, ls, A, x.tgt, x.tgt_normals, tb.Bs, tb.orig_t, tb.tile_box,
+                               tb.group_box, x.tplan->l_groups, tb.sort_t.bbox, x.md2, x.mode, x.max_iteration, x.relative_fitness, x.relative_rmse, tag,
+                               prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr, light, cert_policy, sw.chain_wait_ticks, chain_abort_word());
+        });
+        if (chained && sw.chain_dump) chain_dump_records(A, ls);
+    }
+    int k = 0;                                                 // the next iteration to queue
+    for (bool pending = !chained; pending && !rc;) {
+        int seen = INT_MAX, share = 0;
+        // the launches still to be queued carry only the registrations that have not converged yet (as far as the host
+        // knows: the progress words lag by up to `window` launches); a converged problem's blocks in an already queued
+        // launch read its state and return
+        IcpBatchArgs act;
+        act.count = 0;
+        unsigned ab = 0;
+        for (int c = 0; c < A.count; ++c) {
+            const ProgressWindow::Word w = pw.read(c);
+            if (w.converged) continue;
+            seen = w.seen < seen ? w.seen : seen;
+            share = w.share > share ? w.share : share;
+            act.p[act.count] = A.p[c];
+            act.p[act.count].block0 = ab;
+            ab += A.p[c].blocks;
+            ++act.count;
         }
+        if (act.count == 0) break;                             // every registration has converged
+        for (int c = act.count; c < kIcpBatchMax; ++c) act.p[c] = act.p[act.count - 1];
+        bool advanced = false;
+        for (; k <= x.max_iteration && k - seen < window; ++k) {
+            advanced = true;
+            ProfScope prof(KPX_PROF_NN_LOCAL, 0.0, ls);
+            unsigned long long *visits = prof_armed() ? nn_visits_ptr() : (unsigned long long *)nullptr;
+            for (int c = 0; c < kIcpBatchMax; ++c) act.p[c].k = k;
+            if (!(rows_mode == 2 || (rows_mode == 1 && share <= rows_share)))
+                hipLaunchKernelGGL(icp_iter_batch_kernel, dim3(ab), dim3(kIThreads), 0, ls, act, x.md2, x.mode, x.max_iteration, x.relative_fitness,
+                                   x.relative_rmse, visits, light, cert_policy);
+            else if (x.mode == 1)                              // one wave per 64 rows (kpx_icprows.h)
+                hipLaunchKernelGGL(icp_rows_kernel<1>, dim3(ab), dim3(kRowsBlock), 0, ls, act, x.md2, x.max_iteration, x.relative_fitness, x.relative_rmse,
+                                   visits, light, cert_policy);
+            else
+                hipLaunchKernelGGL(icp_rows_kernel<0>, dim3(ab), dim3(kRowsBlock), 0, ls, act, x.md2, x.max_iteration, x.relative_fitness, x.relative_rmse,
+                                   visits, light, cert_policy);
+        }
+        pending = k <= x.max_iteration;                        // (else everything is queued)
         rc = pw.pass_done(advanced, pending);
     }
     if (hipGetLastError() != hipSuccess && !rc) rc = fail(KPX_ERR_HIP, "kpx_icp_batch: launch failed");
@@ -1418,16 +1383,15 @@ int kpx::icp_batch_ordered(int32_t count, const float *const *h_src, const int64
     }
     rc = nn_prep(tgt, tplan, bufs[0], st, ordered);
     if (rc) return rc;
-    // One chain of launches for up to kIcpBatchMax problems (drive_grouped) when the clouds were ordered by the batch sort; a single
-    // group runs on the caller's stream itself (no fork / join events).  KPX_ICP_BATCH_LAUNCH=0 / KPX_ICP_FUSE=0: one chain per problem.
+    // One chain of launches for the whole batch (drive_grouped) when the clouds were ordered by the batch sort: it runs on the caller's
+    // stream itself (no fork / join events).  KPX_ICP_BATCH_LAUNCH=0 / KPX_ICP_FUSE=0, or a batch too large for one sort: one chain per
+    // problem, on the lanes.
     const bool grouped = local_engine() && ordered && icp_switches().batch_launch && icp_switches().fuse;
-    const int n_chain = grouped ? (int)cdiv(count, kIcpBatchMax) : count;
-    const bool on_caller = grouped && n_chain == 1;
-    const int used_lanes = on_caller ? 0 : (n_chain < kLaneCount ? n_chain : kLaneCount);
+    const int used_lanes = grouped ? 0 : (count < kLaneCount ? count : kLaneCount);
     LaneSet *ln = nullptr;                          // (the thread's lanes exist only once one of its calls has forked)
     if (used_lanes && (rc = lanes_get(&ln))) return rc;
     const BatchCtx ctx{ count, h_src, h_n_src, tgt, tgt_normals, h_init, max_dist * max_dist, mode, max_iteration, relative_fitness, relative_rmse, d_results,
-                        plans, &tplan, bufs, ordered, st, ln ? ln->s : nullptr, n_chain, on_caller };
+                        plans, &tplan, bufs, ordered, st, ln ? ln->s : nullptr };
     if (used_lanes) rc = lanes_fork(ln, st, used_lanes);
     if (!rc) rc = grouped ? drive_grouped(ctx) : local_engine() ? drive_windowed(ctx) : drive_dense_polled(ctx);
     if (used_lanes) {

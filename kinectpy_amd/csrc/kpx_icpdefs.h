@@ -47,6 +47,12 @@ struct IcpState {
     double last_motion;        // what the latest update added to `motion` (row certificates: how calm the registration is)
     double smax;               // largest |T p| over the source's bounding box under the CURRENT T (the next update's lever arm); < 0: not known yet
 };
+// a registration that has not iterated yet: everything but T
+__device__ __forceinline__ void state_fresh(IcpState *st)
+{
+    st->fitness = 0.0; st->rmse = 0.0; st->count = 0.0; st->iter = 0; st->done = 0;
+    st->motion = 0.0; st->reach = INFINITY; st->last_motion = INFINITY; st->smax = -1.0;
+}
 
 __device__ __forceinline__ void xform_row(const double *__restrict__ T, const float *__restrict__ p, double s[3])
 {
@@ -56,6 +62,64 @@ __device__ __forceinline__ void xform_row(const double *__restrict__ T, const fl
 }
 __device__ __forceinline__ double row_seed(const double s[3]) { return fma(s[0], s[0], fma(s[1], s[1], s[2] * s[2])) + 1.0; }
 __device__ __forceinline__ int opaque_i(int v) { asm volatile("" : "+v"(v)); return v; }
+// What a row (s, seed) is searched with.  Where it has a previous partner: that partner's AC2 value, by the sweep's own fma chain (the
+// bound is then a value the sweep would form itself) ...
+__device__ __forceinline__ double partner_bound(const double s[3], double seed, const float *tp)
+{
+    const double tx = tp[0], ty = tp[1], tz = tp[2];
+    const double t2 = fma(tx, tx, fma(ty, ty, tz * tz));
+    double d = fma(s[0], -2.0 * tx, seed);
+    d = fma(s[1], -2.0 * ty, d);
+    d = fma(s[2], -2.0 * tz, d);
+    return fma(1.0, t2, d);
+}
+// ... clamped to the correspondence distance: nothing farther than max_d2 can become a partner; the margins cover the expanded
+// metric's rounding at the scale of the row and of the target (t2max = target_t2max, kpx_nnlocal.h).  A row without a bound, or whose
+// partner lies beyond the clamp, goes in with bj = INT_MAX.
+__device__ __forceinline__ void bound_clamp(double seed, double max_d2, double t2max, double &bv, int32_t &bj)
+{
+    const double clamp = (max_d2 + 1.0) * (1.0 + 9.31322574615478515625e-10) + ldexp(seed + t2max + 1.0, -38);
+    if (!(bv <= clamp)) { bv = clamp; bj = INT_MAX; }
+}
+// AC3: the direct squared distance of a chosen pair
+__device__ __forceinline__ double pair_d2(const double s[3], const double t[3])
+{
+    const double dx = s[0] - t[0], dy = s[1] - t[1], dz = s[2] - t[2];
+    return fma(dz, dz, fma(dy, dy, dx * dx));
+}
+// the point-to-plane row of a pair with the partner's normal at nrm: J = (s x n, n), returns the residual (s - t) . n
+__device__ __forceinline__ double plane_row(const double s[3], const double t[3], const float *nrm, double J[6])
+{
+    const double nx = nrm[0], ny = nrm[1], nz = nrm[2];
+    J[0] = s[1] * nz - s[2] * ny; J[1] = s[2] * nx - s[0] * nz; J[2] = s[0] * ny - s[1] * nx;
+    J[3] = nx; J[4] = ny; J[5] = nz;
+    return (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
+}
+// What a pair within the correspondence distance adds to the update sums, handed to put(slot, value): the 17 point-to-point terms
+// (count, d2, s, t, t s^T) and, with `plane`, the 27 point-to-plane terms (J^T J upper triangle, J^T r).  Every form of the iteration
+// gets its terms here, which is what keeps them equal to the last bit.
+template <class Put>
+__device__ __forceinline__ void pair_terms(const double s[3], const double t[3], double d2, bool plane, const float *nrm, Put put)
+{
+    put(0, 1.0); put(1, d2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { put(2 + c, s[c]); put(5 + c, t[c]); }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) put(8 + 3 * a + c, t[a] * s[c]);
+    if (plane) {
+        double J[6];
+        const double res = plane_row(s, t, nrm, J);
+        int slot = 17;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) put(slot++, J[a] * J[c]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) put(38 + a, J[a] * res);
+    }
+}
 // bits 33..39 of a progress word: the share of the registration's rows the iteration searched, in 1/127ths rounded up (0 = none)
 __host__ __device__ __forceinline__ unsigned long long progress_searched(unsigned long long searched, int64_t n)
 {
@@ -196,9 +260,9 @@ struct IcpProblem {
     double *chain_rec;
     int64_t n;
     uint32_t block0, blocks;
-    // round 5: every problem carries its own target operands, iteration number and progress tag, so that one launch can hold the
-    // registrations of SEVERAL frames in flight, each at the iteration it has reached (icp_rows_kernel; icp_chain_kernel, which iterates
-    // by itself over one shared target, takes these as kernel arguments instead)
+    // the target operands, the iteration number and the progress tag of the launch: the same for every problem of a launch (one frame's
+    // registrations onto one shared target, all at the same iteration; drive_grouped fills them in).  icp_iter_batch_kernel and
+    // icp_rows_kernel read them here; icp_chain_kernel, which iterates by itself, takes them as kernel arguments instead
     const float *tgt, *tn;
     const double *Bs;
     const int32_t *orig;
@@ -211,6 +275,14 @@ struct IcpBatchArgs {
     IcpProblem p[kIcpBatchMax];
     int32_t count;
 };
+// the problem whose block range holds this block (block = blockIdx.x - p[..].block0 within it)
+__device__ __forceinline__ int batch_problem(const IcpBatchArgs &args)
+{
+    int pi = 0;
+#pragma unroll
+    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    return pi;
+}
 struct Mat16x8 {
     double m[kIcpBatchMax][16];
 };

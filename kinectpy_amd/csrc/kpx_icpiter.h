@@ -84,6 +84,118 @@ __device__ __forceinline__ void phase_tick(unsigned long long *__restrict__ arme
 // cull with the box and bounds of their uncertified rows only.  Partners, sums and transforms are those of the full search, bit for
 // bit.  The policy is CertPolicy, above IcpFuse.  (KPX_ICP_CERT=0 switches the certificates off: test_icp_update_placements_and_light_skip_are_bit_identical; KPX_ICP_CERT_CHECK=1
 // searches the certified rows all the same and counts disagreements: test_icp_certificates_never_contradict_the_search).
+//
+// The pieces every form of the iteration shares (icp_iter_body below, icp_rows_kernel in kpx_icprows.h), one definition each:
+// how calm the registration is decides the skin uncertified rows are searched with (0: none)
+__device__ __forceinline__ double cert_skin(bool certs, int k, const IcpState *st, double max_d2, const CertPolicy &pol)
+{
+    double c_skin = 0.0;
+    if (certs && k > 0) {
+        const double lm = st->last_motion, md = sqrt(max_d2);
+        if (lm <= (double)pol.calm * md) c_skin = fmin(fmax((double)pol.factor * lm, (double)pol.smin * md), (double)pol.smax * md);
+    }
+    return c_skin;
+}
+// The certificate test of a row: s its position now, src its coordinates, (prev, pt) the partner it came with, bj what row_bound left
+// of that partner, cert its certificate word, Th the 12 doubles of the transform of the iteration the word names (read only where the
+// word holds an L), c_reach the reach of any row's search.  Returns whether the row is certified, and sets the bound rb0 it is searched
+// with: none (-1) for a certified row outside the self-check, else widened by the skin.
+__device__ __forceinline__ bool cert_test(const double s[3], const float src[3], int32_t prev, const float pt[3], int32_t bj, uint32_t cert, const double *Th,
+                                          double c_reach, double c_skin, int cert_check, double &rb0)
+{
+    // d1: an upper bound of the distance from the row to its partner (a row without one: the reach of any row's search)
+    double d1 = c_reach;
+    if (bj != INT_MAX) {
+        const double dx = s[0] - (double)pt[0], dy = s[1] - (double)pt[1], dz = s[2] - (double)pt[2];
+        d1 = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) * (1.0 + 1e-12);
+    }
+    // certified: every other target point was >= L away from p_c, the row has moved by |p - p_c| since (p_c is kept as float32:
+    // 2^-24 relative per coordinate, covered by the 1e-6 relative margin on the coordinates' scale), and its partner (or the
+    // reach of a row without one) is nearer than what is left of L.  A row that HAD a partner and lost it to the clamp is
+    // searched (the certificate says nothing about that partner).
+    const bool keeps = (prev >= 0) == (bj != INT_MAX);
+    const float Lc = __uint_as_float(cert & ~63u);
+    double pc[3] = { 0.0, 0.0, 0.0 };
+    if (Lc > 0.0f) {                                     // the row's position at that search: AC1 with that iteration's transform
+        const double x = src[0], y = src[1], z = src[2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) pc[a] = fma(Th[4 * a], x, fma(Th[4 * a + 1], y, fma(Th[4 * a + 2], z, Th[4 * a + 3])));
+    }
+    const double ex = s[0] - pc[0], ey = s[1] - pc[1], ez = s[2] - pc[2];
+    const double moved = sqrt(fma(ez, ez, fma(ey, ey, ex * ex))) * (1.0 + 1e-12);
+    const bool certd = Lc > 0.0f && keeps && (d1 + moved) * (1.0 + 1e-6) + 1e-6 < (double)Lc;
+    if (certd && !cert_check) rb0 = -1.0;
+    else if (c_skin > 0.0) { const double rr = d1 + c_skin; rb0 = fmax(rb0, rr * rr); }
+    return certd;
+}
+// The new certificate word of a row that was searched in iteration k, from what the sweep left in WaveRows (sec, eps_out, rb_out):
+// L^2 = min(final culling bound, runner-up among the multiplied columns), both on d^2; L rounded DOWN to a float with its low six
+// mantissa bits cleared; those bits carry the iteration (k < 64: later iterations of a longer chain are searched every time)
+__device__ __forceinline__ uint32_t cert_word(unsigned sec, double eps_out, double rb_out, int k)
+{
+    typedef unsigned uu2 __attribute__((ext_vector_type(2)));
+    const uu2 pat = { 0u, sec };
+    const double d2nd = sec == 0xFFFFFFFFu ? INFINITY : __builtin_bit_cast(double, pat) - 1.0 - eps_out;
+    const double l2 = fmin(rb_out, d2nd);
+    const uint32_t lb = l2 > 0.0 && k < kCertHist ? (__float_as_uint(f32_down(sqrt(l2) * (1.0 - 1e-7))) & ~63u) : 0u;
+    return lb > 63u ? (lb | (uint32_t)k) : 0u;
+}
+// Self-check bookkeeping (g_cert_check): the search of a certified row disagreed with the partner its certificate kept -- the first
+// such row is recorded
+__device__ __forceinline__ void cert_check_disagreement(int k, int64_t row, int32_t kept, int32_t found, uint32_t word)
+{
+    if (atomicAdd(&g_cert_check[2], 1ull) == 0ull) {
+        g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = (unsigned long long)row;
+        g_cert_check[5] = (unsigned long long)(unsigned)kept; g_cert_check[6] = (unsigned long long)(unsigned)found;
+        g_cert_check[7] = (unsigned long long)(word & ~63u);
+    }
+}
+// ... and per wave of rows the counters (one lane calls); `first`: the registration's first wave, which reports the chain's state
+// at its last launch in [3..7] as long as there is no disagreement
+__device__ __forceinline__ void cert_check_count(bool first, int k, const IcpState *st, double c_skin, int certified, int searched)
+{
+    if (first && g_cert_check[2] == 0ull) {
+        g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = __builtin_bit_cast(unsigned long long, st->last_motion);
+        g_cert_check[5] = __builtin_bit_cast(unsigned long long, st->motion); g_cert_check[6] = __builtin_bit_cast(unsigned long long, c_skin);
+    }
+    atomicAdd(&g_cert_check[0], (unsigned long long)certified);
+    atomicAdd(&g_cert_check[1], (unsigned long long)searched);
+}
+// IcpFuse of the ticket mode for a problem of a batch: the last block of the registration's sweep performs the update (ticket: first
+// word of the second accumulator set).  light: the switch word (icp_light_word, kpx_icp.hip)
+__device__ __forceinline__ IcpFuse ticket_fuse(const IcpProblem &P, int max_iter, double rel_fit, double rel_rmse, unsigned long long tag, int light,
+                                               CertPolicy pol, double *chain_rec, unsigned long long *stamp)
+{
+    return IcpFuse{ (IcpState *)nullptr, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag, P.ring + kAccSet,
+                    (light & 1) ? P.light_key : (double *)nullptr, P.sbbox, (light & 2) ? P.cert : (uint32_t *)nullptr,
+                    (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, chain_rec, stamp };
+}
+// The winner's step (the block that drew its registration's last ticket, THREADS threads, tix_w the caller's thread number behind an
+// opaque move), first part: the coherent totals into s_sums, the searched-row count (SEARCHED; returned), then -- the block's
+// s_sums complete -- the accumulators cleared and the ticket reset for the next launch.
+template <int THREADS, bool SEARCHED>
+__device__ __forceinline__ unsigned long long winner_take(unsigned long long *acc, unsigned long long *ticket, int nacc, double *s_sums, int tix_w)
+{
+    if (tix_w < kAcc) s_sums[tix_w] = tix_w < nacc ? fixed_total_coherent(acc, tix_w) : 0.0;
+    const unsigned long long n_searched = SEARCHED ? searched_take(ticket, tix_w) : 0ull;
+    if (THREADS > 64) __syncthreads(); else wave_lds_fence();
+    for (int e = tix_w; e < kAccSet; e += THREADS) __hip_atomic_store(acc + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tix_w == 0) __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return n_searched;
+}
+// ... last part, by the first 24 lanes of the wave that ran the update on `work` (every form but the one-launch chain, which
+// publishes a record instead): the state written back, entry k + 1 of the transforms' history (thist, or nullptr without
+// certificates), the progress word.  Plain stores: the readers are the blocks of the NEXT launch, behind the kernel boundary.
+__device__ __forceinline__ void winner_publish(IcpState *st, const IcpState *work, double *thist, int k, unsigned long long *progress, unsigned long long tag,
+                                               unsigned long long n_searched, int64_t n, int lane)
+{
+    if (lane < (int)(sizeof(IcpState) / sizeof(double))) reinterpret_cast<double *>(st)[lane] = reinterpret_cast<const double *>(work)[lane];
+    if (thist && k + 1 < kCertHist && lane < 12) thist[12 * (k + 1) + lane] = work->T[lane];     // what iteration k + 1 transforms with
+    if (lane == 0 && progress)
+        __hip_atomic_store(progress, tag | progress_searched(n_searched, n) | ((unsigned long long)(work->done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // bid / nblocks: this block's index among the blocks of ITS registration (one launch may carry several, see icp_iter_batch_kernel)
 template <bool PERSIST = false>
 __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned nblocks, const float *__restrict__ src, int64_t n, const float *__restrict__ tgt,
@@ -235,11 +347,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
 
     // Row certificates (kpx_icp.hip, "Certificates" above icp_iter_body): how calm the registration is decides the skin
     const double c_reach = certs ? st->reach : 0.0;
-    double c_skin = 0.0;
-    if (certs && k > 0) {
-        const double lm = st->last_motion, md = sqrt(max_d2);
-        if (lm <= (double)fuse.pol.calm * md) c_skin = fmin(fmax((double)fuse.pol.factor * lm, (double)fuse.pol.smin * md), (double)fuse.pol.smax * md);
-    }
+    const double c_skin = cert_skin(certs, k, st, max_d2, fuse.pol);
     bool my_active = true, my_certd = false;
     if (lane < 16) {
         const int64_t i = my_row;
@@ -248,49 +356,13 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
         const double seed = row_seed(s);
         double bv = INFINITY;
         int32_t bj = INT_MAX;
-        if (k > 0) {
-            const int32_t p = my_prev;
-            if (p >= 0) {
-                const double tx = my_pt[0], ty = my_pt[1], tz = my_pt[2];
-                const double t2 = fma(tx, tx, fma(ty, ty, tz * tz));
-                double d = fma(s[0], -2.0 * tx, seed);
-                d = fma(s[1], -2.0 * ty, d);
-                d = fma(s[2], -2.0 * tz, d);
-                bv = fma(1.0, t2, d);
-                bj = p;
-            }
-        }
-        const double clamp = (max_d2 + 1.0) * (1.0 + 9.31322574615478515625e-10) + ldexp(seed + t2max + 1.0, -38);
-        if (!(bv <= clamp)) { bv = clamp; bj = INT_MAX; }
+        if (k > 0 && my_prev >= 0) { bv = partner_bound(s, seed, my_pt); bj = my_prev; }
+        bound_clamp(seed, max_d2, t2max, bv, bj);
         double rb0 = bv - 1.0;
         if (certs) {
-            // d1: an upper bound of the distance from the row to its partner (a row without one: the reach of any row's search)
-            double d1 = c_reach;
-            if (bj != INT_MAX) {
-                const double dx = s[0] - (double)my_pt[0], dy = s[1] - (double)my_pt[1], dz = s[2] - (double)my_pt[2];
-                d1 = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) * (1.0 + 1e-12);
-            }
-            // certified: every other target point was >= L away from p_c, the row has moved by |p - p_c| since (p_c is kept as float32:
-            // 2^-24 relative per coordinate, covered by the 1e-6 relative margin on the coordinates' scale), and its partner (or the
-            // reach of a row without one) is nearer than what is left of L.  A row that HAD a partner and lost it to the clamp is
-            // searched (the certificate says nothing about that partner).
-            const bool keeps = (my_prev >= 0) == (bj != INT_MAX);
-            const int kc = (int)(my_cert & 63u);
-            const float Lc = __uint_as_float(my_cert & ~63u);
-            double pc[3] = { 0.0, 0.0, 0.0 };
-            if (Lc > 0.0f) {                                     // the row's position at that search: AC1 with that iteration's transform
-                const double *Th = s_thist[kc];
-                const double x = my_src[0], y = my_src[1], z = my_src[2];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) pc[a] = fma(Th[4 * a], x, fma(Th[4 * a + 1], y, fma(Th[4 * a + 2], z, Th[4 * a + 3])));
-            }
-            const double ex = s[0] - pc[0], ey = s[1] - pc[1], ez = s[2] - pc[2];
-            const double moved = sqrt(fma(ez, ez, fma(ey, ey, ex * ex))) * (1.0 + 1e-12);
-            const bool certd = Lc > 0.0f && keeps && (d1 + moved) * (1.0 + 1e-6) + 1e-6 < (double)Lc;
+            const bool certd = cert_test(s, my_src, my_prev, my_pt, bj, my_cert, s_thist[my_cert & 63u], c_reach, c_skin, fuse.cert_check, rb0);
             my_active = (!certd || fuse.cert_check) && row_base + lane <= last;
             my_certd = certd && row_base + lane <= last;
-            if (certd && !fuse.cert_check) rb0 = -1.0;
-            else if (c_skin > 0.0) { const double rr = d1 + c_skin; rb0 = fmax(rb0, rr * rr); }
         }
         rowd[wave][lane][0] = s[0]; rowd[wave][lane][1] = s[1]; rowd[wave][lane][2] = s[2];
         rowd[wave][lane][3] = rb0;
@@ -348,13 +420,8 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int rr = q_p + 4 * r;
-                if (((certd_mask >> rr) & 1u) != 0u && w.bcol[r] != rowi[wave_p][rr][0]) {
-                    if (atomicAdd(&g_cert_check[2], 1ull) == 0ull) {
-                        g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = (unsigned long long)(row_base_p + rr);
-                        g_cert_check[5] = (unsigned long long)(unsigned)rowi[wave_p][rr][0]; g_cert_check[6] = (unsigned long long)(unsigned)w.bcol[r];
-                        g_cert_check[7] = (unsigned long long)((PERSIST ? rowc[wave_p][rr] : fuse.cert[row_base_p + rr]) & ~63u);
-                    }
-                }
+                if (((certd_mask >> rr) & 1u) != 0u && w.bcol[r] != rowi[wave_p][rr][0])
+                    cert_check_disagreement(k, row_base_p + rr, rowi[wave_p][rr][0], w.bcol[r], PERSIST ? rowc[wave_p][rr] : fuse.cert[row_base_p + rr]);
             }
         }
         if (certs && j_p == 0) {
@@ -362,14 +429,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
             for (int r = 0; r < 4; ++r) {
                 const int rr = q_p + 4 * r;
                 if (((act_mask >> rr) & 1u) != 0u && ((certd_mask >> rr) & 1u) == 0u) {
-                    typedef unsigned uu2 __attribute__((ext_vector_type(2)));
-                    const uu2 pat = { 0u, w.sec[r] };
-                    const double d2nd = w.sec[r] == 0xFFFFFFFFu ? INFINITY : __builtin_bit_cast(double, pat) - 1.0 - w.eps_out;
-                    const double l2 = fmin(w.rb_out[r], d2nd);
-                    // L rounded DOWN to a float with its low six mantissa bits cleared; those bits carry the iteration (k < 64: later iterations
-                    // of a longer chain are searched every time)
-                    const uint32_t lb = l2 > 0.0 && k < kCertHist ? (__float_as_uint(f32_down(sqrt(l2) * (1.0 - 1e-7))) & ~63u) : 0u;
-                    const uint32_t cw = lb > 63u ? (lb | (uint32_t)k) : 0u;
+                    const uint32_t cw = cert_word(w.sec[r], w.eps_out, w.rb_out[r], k);
                     if (PERSIST) rowc[wave_p][rr] = cw; else fuse.cert[row_base_p + rr] = cw;
                 }
             }
@@ -382,14 +442,8 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     __shared__ int s_cnt[kIWaves];
     if (lane_p == 0) s_cnt[wave_p] = __builtin_popcount(act_mask & ~certd_mask);
     const unsigned visited = (unsigned)(swept & 0xFFFFu);
-    if (certs && fuse.cert_check && lane_p == 0) {
-        if (bid == 0 && wave_p == 0 && g_cert_check[2] == 0ull) {       // no disagreement so far: [3..7] report the chain's state at its last launch
-            g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = __builtin_bit_cast(unsigned long long, st->last_motion);
-            g_cert_check[5] = __builtin_bit_cast(unsigned long long, st->motion); g_cert_check[6] = __builtin_bit_cast(unsigned long long, c_skin);
-        }
-        atomicAdd(&g_cert_check[0], (unsigned long long)__builtin_popcount(certd_mask));
-        atomicAdd(&g_cert_check[1], (unsigned long long)__builtin_popcount(act_mask & ~certd_mask));
-    }
+    if (certs && fuse.cert_check && lane_p == 0)
+        cert_check_count(bid == 0 && wave_p == 0, k, st, c_skin, __builtin_popcount(certd_mask), __builtin_popcount(act_mask & ~certd_mask));
     // (LightSkip speaks for ALL rows of a block: a wave that left certified rows out of its box does not count as light)
     if (lane_p == 0) s_light[wave_p] = act_mask == 0xFFFFu ? w.light_gap2 : -1.0;
     if (tile_visits && lane_p == 0 && bid < kStampBlocks && kIWaves <= 4) {
@@ -456,30 +510,9 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
                     }
                 }
                 const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
-                const double dx = s[0] - t[0], dy = s[1] - t[1], dz = s[2] - t[2];
-                const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
+                const double d2 = pair_d2(s, t);
                 if (d2_cur) d2_cur[i] = d2;
-                if (d2 < max_d2) {
-                    sh[0][col] = 1.0; sh[1][col] = d2;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) { sh[2 + c][col] = s[c]; sh[5 + c][col] = t[c]; }
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) sh[8 + 3 * a + c][col] = t[a] * s[c];
-                    if (mode == 1) {
-                        const double nx = nf[0], ny = nf[1], nz = nf[2];
-                        const double res = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
-                        const double J[6] = { s[1] * nz - s[2] * ny, s[2] * nx - s[0] * nz, s[0] * ny - s[1] * nx, nx, ny, nz };
-                        int slot = 17;
-#pragma unroll
-                        for (int a = 0; a < 6; ++a)
-#pragma unroll
-                            for (int c = a; c < 6; ++c) sh[slot++][col] = J[a] * J[c];
-#pragma unroll
-                        for (int a = 0; a < 6; ++a) sh[38 + a][col] = J[a] * res;
-                    }
-                }
+                if (d2 < max_d2) pair_terms(s, t, d2, mode == 1, nf, [&](int slot, double v) { sh[slot][col] = v; });
             }
         }
     }
@@ -553,12 +586,8 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the winner only: one per registration and launch
     // (the winner's thread number behind an opaque move as well: addresses derived from it are then formed here, not in front of the sweep)
     const int tix_w = opaque_i((int)threadIdx.x);
-    if (tix_w < kAcc) s_sums[tix_w] = tix_w < nacc ? fixed_total_coherent(acc, tix_w) : 0.0;
-    const unsigned long long n_searched = PERSIST ? 0ull : searched_take(fuse.ticket, tix_w);
-    __syncthreads();
-    if (PERSIST) chain_tick(fuse.stamp, 7, tix == 0);
-    for (int e = tix_w; e < kAccSet; e += kIThreads) __hip_atomic_store(acc + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tix == 0) __hip_atomic_store(fuse.ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long n_searched = winner_take<kIThreads, !PERSIST>(acc, fuse.ticket, nacc, s_sums, tix_w);
+    if (PERSIST) chain_tick(fuse.stamp, 7, tix == 0);         // (the clearing stores are issued, not waited for)
     // PERSIST: the blocks that see the next record add to these accumulators at once, so every clearing store (and the ticket's) must
     // have been performed before the record is published: each wave drains its stores, the block meets at a barrier (wave 0 after the
     // update algebra, which hides the drain), then wave 0 publishes
@@ -600,11 +629,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
         if (fuse.stamp && lane == 0) fuse.stamp[12] = __builtin_amdgcn_s_memtime();      // shader clock (against [9]: the clock the chip runs the chain at)
         return;
     }
-    if (lane < (int)(sizeof(IcpState) / sizeof(double))) reinterpret_cast<double *>(stw)[lane] = reinterpret_cast<const double *>(&s_state)[lane];
-    if (fuse.cert && fuse.thist && k + 1 < kCertHist && lane < 12) fuse.thist[12 * (k + 1) + lane] = work->T[lane];     // what iteration k + 1 transforms with
-    if (lane == 0 && fuse.progress)
-        __hip_atomic_store(fuse.progress, fuse.tag | progress_searched(n_searched, n) | ((unsigned long long)(work->done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    winner_publish(stw, work, fuse.cert ? fuse.thist : (double *)nullptr, k, fuse.progress, fuse.tag, n_searched, n, lane);
 }
 
 
@@ -631,21 +656,14 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
 __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_iter_batch_kernel(IcpBatchArgs args, double max_d2, int mode, int max_iter, double rel_fit,
                                                        double rel_rmse, unsigned long long *__restrict__ tile_visits, int light, CertPolicy pol)
 {
-    int pi = 0;
-#pragma unroll
-    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
-    const IcpProblem &P = args.p[pi];
+    const IcpProblem &P = args.p[batch_problem(args)];
     const unsigned bid = blockIdx.x - P.block0;
     const float *__restrict__ tgt = P.tgt, *__restrict__ tn = P.tn, *__restrict__ tile_box = P.tile_box, *__restrict__ group_box = P.group_box;
     const double *__restrict__ Bs = P.Bs, *__restrict__ tbbox = P.tbbox;
     const int32_t *__restrict__ orig = P.orig;
     const int32_t n_groups = P.n_groups;
     const int k = P.k;
-    const unsigned long long tag = P.tag;
-    // the last block of every registration's sweep performs the update (ticket: first word of the second accumulator set)
-    const IcpFuse fuse{ (IcpState *)nullptr, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag, P.ring + kAccSet,
-                        (light & 1) ? P.light_key : (double *)nullptr, P.sbbox, (light & 2) ? P.cert : (uint32_t *)nullptr,
-                        (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, nullptr, nullptr };
+    const IcpFuse fuse = ticket_fuse(P, max_iter, rel_fit, rel_rmse, P.tag, light, pol, nullptr, nullptr);
     icp_iter_body(bid, P.blocks, P.src, P.n, tgt, tn, Bs, orig, tile_box, group_box, n_groups, tbbox, P.row_of, P.src_sorted, P.idx_sorted, P.ptgt_sorted,
                   P.idx_cur, P.d2_cur, max_d2, mode, k, P.pair, P.ring, tile_visits, fuse);
 }
@@ -667,9 +685,7 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
                                                        double rel_rmse, unsigned long long tag, unsigned long long *__restrict__ tile_visits, int light,
                                                        CertPolicy pol, unsigned long long limit_ticks, unsigned long long *abort_word)
 {
-    int pi = 0;
-#pragma unroll
-    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    const int pi = batch_problem(args);
     const IcpProblem &P = args.p[pi];
     const unsigned bid = blockIdx.x - P.block0;
     __shared__ IcpState s_cur;
@@ -682,10 +698,8 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
         // descriptor -- would otherwise be hoisted out of the loop and live in registers across it)
         asm volatile("" : "+s"(tgt), "+s"(tn), "+s"(Bs), "+s"(orig), "+s"(tile_box), "+s"(group_box), "+s"(tbbox));
         asm volatile("" : "+s"(max_d2), "+s"(mode), "+s"(n_groups), "+s"(pol.calm), "+s"(pol.factor), "+s"(pol.smin), "+s"(pol.smax));
-        const IcpFuse fuse{ (IcpState *)nullptr, P.ring, max_iter, rel_fit, rel_rmse, P.result, P.progress, tag, P.ring + kAccSet,
-                            (light & 1) ? P.light_key : (double *)nullptr, P.sbbox, (light & 2) ? P.cert : (uint32_t *)nullptr,
-                            (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, P.chain_rec,
-                            ((light & 8) && pi == 0 && k < 64) ? &g_chain_stamp[k][0] : (unsigned long long *)nullptr };
+        const IcpFuse fuse = ticket_fuse(P, max_iter, rel_fit, rel_rmse, tag, light, pol, P.chain_rec,
+                                         ((light & 8) && pi == 0 && k < 64) ? &g_chain_stamp[k][0] : (unsigned long long *)nullptr);
         if (threadIdx.x < kChainWords) {
             const unsigned long long *w = reinterpret_cast<const unsigned long long *>(P.chain_rec + (size_t)kChainRec * k) + threadIdx.x;
             unsigned long long v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -717,9 +731,7 @@ __global__ __launch_bounds__(kIThreads) __attribute__((amdgpu_waves_per_eu(KPX_I
 // the rows gathered into Morton order (what icp_init_kernel + a memset + gather_rows_kernel did per problem)
 __global__ __launch_bounds__(256) void icp_batch_init_kernel(IcpBatchArgs args, Mat16x8 T0)
 {
-    int pi = 0;
-#pragma unroll
-    for (int c = 1; c < kIcpBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
+    const int pi = batch_problem(args);
     const IcpProblem &P = args.p[pi];
     const unsigned bid = blockIdx.x - P.block0;
     const int c = threadIdx.x & 3;
@@ -736,12 +748,12 @@ __global__ __launch_bounds__(256) void icp_batch_init_kernel(IcpBatchArgs args, 
             for (int e = kChainRec + threadIdx.x; e < kChainRecords * kChainRec; e += 256) rw[e] = kChainEmpty;
             IcpState *r0 = reinterpret_cast<IcpState *>(P.chain_rec);
             if (threadIdx.x >= 128 && threadIdx.x < 144) r0->T[threadIdx.x - 128] = T0.m[pi][threadIdx.x - 128];
-            if (threadIdx.x == 144) { r0->fitness = 0.0; r0->rmse = 0.0; r0->count = 0.0; r0->iter = 0; r0->done = 0; r0->motion = 0.0; r0->reach = INFINITY; r0->last_motion = INFINITY; r0->smax = -1.0; }
+            if (threadIdx.x == 144) state_fresh(r0);
         }
         if (threadIdx.x < 32) {
             IcpState *st = P.pair + (threadIdx.x >> 4);
             st->T[threadIdx.x & 15] = T0.m[pi][threadIdx.x & 15];
-            if ((threadIdx.x & 15) == 0) { st->fitness = 0.0; st->rmse = 0.0; st->count = 0.0; st->iter = 0; st->done = 0; st->motion = 0.0; st->reach = INFINITY; st->last_motion = INFINITY; st->smax = -1.0; }
+            if ((threadIdx.x & 15) == 0) state_fresh(st);
         }
     }
 }

@@ -13,42 +13,15 @@
 //   * the sums follow the contract stated in icp_iter_body: per tile the balanced tree of four DPP butterfly steps
 //     (row16_tree_sum == tile_tree16), the four tile partials added exactly in fixed point, one pair of returning atomics per sum;
 //   * the block that draws the registration's last ticket performs the update (icp_finish_wave), as in icp_iter_body's ticket mode;
-//   * every problem of the launch carries its OWN target operands and its OWN iteration number (RowsProblem).
+//   * the launch takes the argument block of icp_iter_batch_kernel (IcpBatchArgs: one frame's registrations onto their shared target,
+//     all at iteration p[..].k), and the row prologue, the pair terms and the winner's step are the functions icp_iter_body calls.
 #pragma once
 #include "kpx_icpiter.h"
 
 namespace kpx {
 
-constexpr int kRowsBatchMax = 16;                  // registrations per launch (kernel arguments: 16 x 176 B)
 constexpr int kRowsBlock = 64;
-struct RowsProblem {
-    // source side (sorted-row order; written by icp_batch_init_kernel and by the iterations themselves)
-    const float *src_sorted;
-    int32_t *idx_sorted;
-    float *ptgt_sorted;
-    uint32_t *cert;
-    double *thist;
-    double *light_key;
-    const double *sbbox;
-    IcpState *state;
-    unsigned long long *ring;
-    double *result;
-    unsigned long long *progress;
-    unsigned long long tag;
-    // target side (nn_local_prep_kernel)
-    const float *tgt, *tn;
-    const double *Bs;
-    const int32_t *orig;
-    const float *tile_box, *group_box;
-    const double *tbbox;
-    int64_t n;
-    int32_t n_groups, k;
-    uint32_t block0, blocks;
-};
-struct RowsArgs {
-    RowsProblem p[kRowsBatchMax];
-    int32_t count;
-};
+static_assert(kRowsBlock == kIRows, "IcpProblem::block0 / blocks count 64-row blocks for icp_iter_batch_kernel and icp_rows_kernel alike");
 
 constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
 // sum over the 16 lanes of a DPP row, the same value (bit for bit: addition commutes) in all of them: tile_tree16's order
@@ -62,18 +35,17 @@ __device__ __forceinline__ double row16_tree_sum(double v)
 }
 
 template <int MODE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_rows_kernel(RowsArgs args, double max_d2, int max_iter, double rel_fit,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE, KPX_ICP_WPE))) void icp_rows_kernel(IcpBatchArgs args, double max_d2, int max_iter, double rel_fit,
                                                                                                                      double rel_rmse, unsigned long long *__restrict__ tile_visits,
                                                                                                                      int light, CertPolicy pol)
 {
     constexpr int NACC = MODE == 1 ? kAcc : 17;
-    int pi = 0;
-#pragma unroll
-    for (int c = 1; c < kRowsBatchMax; ++c) pi += (c < args.count && blockIdx.x >= args.p[c].block0) ? 1 : 0;
-    const RowsProblem &P = args.p[pi];
+    // (the descriptor by VALUE: read through a reference into the argument block, field by field where it is used, the kernel came out
+    // with 22 / 4 spilled vector registers (MODE 1 / 0) instead of 18 / 2 -- one more double carried through the sweep in scratch memory)
+    const IcpProblem P = args.p[batch_problem(args)];
     const unsigned bid = blockIdx.x - P.block0;
     const int k = P.k;
-    IcpState *const st = P.state;
+    IcpState *const st = P.pair;
     if (st->done) return;
 
     // LDS: 10.3 KB per wave (12 waves per CU).  The sweep's records are COMPACT: slot = the row's rank among the block's rows that are
@@ -140,11 +112,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
     unsigned visited_total = 0u;
     if (!skip) {
         const double c_reach = certs ? st->reach : 0.0;
-        double c_skin = 0.0;
-        if (certs && k > 0) {
-            const double lm = st->last_motion, md = sqrt(max_d2);
-            if (lm <= (double)pol.calm * md) c_skin = fmin(fmax((double)pol.factor * lm, (double)pol.smin * md), (double)pol.smax * md);
-        }
+        const double c_skin = cert_skin(certs, k, st, max_d2, pol);
         bool my_active = valid, my_certd = false;
         unsigned long long act64, certd64;
         int n_act;
@@ -154,38 +122,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
             const double seed = row_seed(s);
             double bv = INFINITY;
             int32_t bj = INT_MAX;
-            if (k > 0 && my_prev >= 0) {
-                const double tx = my_pt[0], ty = my_pt[1], tz = my_pt[2];
-                const double t2 = fma(tx, tx, fma(ty, ty, tz * tz));
-                double d = fma(s[0], -2.0 * tx, seed);
-                d = fma(s[1], -2.0 * ty, d);
-                d = fma(s[2], -2.0 * tz, d);
-                bv = fma(1.0, t2, d);
-                bj = my_prev;
-            }
-            const double clamp = (max_d2 + 1.0) * (1.0 + 9.31322574615478515625e-10) + ldexp(seed + t2max + 1.0, -38);
-            if (!(bv <= clamp)) { bv = clamp; bj = INT_MAX; }
+            if (k > 0 && my_prev >= 0) { bv = partner_bound(s, seed, my_pt); bj = my_prev; }
+            bound_clamp(seed, max_d2, t2max, bv, bj);
             double rb0 = bv - 1.0;
             if (certs) {
-                double d1 = c_reach;
-                if (bj != INT_MAX) {
-                    const double dx = s[0] - (double)my_pt[0], dy = s[1] - (double)my_pt[1], dz = s[2] - (double)my_pt[2];
-                    d1 = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) * (1.0 + 1e-12);
-                }
-                const bool keeps = (my_prev >= 0) == (bj != INT_MAX);
-                double pc[3] = { 0.0, 0.0, 0.0 };
-                if (Lc > 0.0f) {
-                    const double x = my_src[0], y = my_src[1], z = my_src[2];
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) pc[a] = fma(Th[4 * a], x, fma(Th[4 * a + 1], y, fma(Th[4 * a + 2], z, Th[4 * a + 3])));
-                }
-                const double ex = s[0] - pc[0], ey = s[1] - pc[1], ez = s[2] - pc[2];
-                const double moved = sqrt(fma(ez, ez, fma(ey, ey, ex * ex))) * (1.0 + 1e-12);
-                const bool certd = Lc > 0.0f && keeps && (d1 + moved) * (1.0 + 1e-6) + 1e-6 < (double)Lc;
+                const bool certd = cert_test(s, my_src, my_prev, my_pt, bj, my_cert, Th, c_reach, c_skin, cert_check ? 1 : 0, rb0);
                 my_active = (!certd || cert_check) && valid;
                 my_certd = certd && valid;
-                if (certd && !cert_check) rb0 = -1.0;
-                else if (c_skin > 0.0) { const double rr = d1 + c_skin; rb0 = fmax(rb0, rr * rr); }
             }
             act64 = __builtin_amdgcn_ballot_w64(my_active);
             certd64 = __builtin_amdgcn_ballot_w64(my_certd);
@@ -245,13 +188,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
 #pragma unroll
                 for (int rr4 = 0; rr4 < 4; ++rr4) {
                     const int rr = q_p + 4 * rr4;
-                    if (((act_mask >> rr) & 1u) != 0u && rowm[v0 + rr] != 0 && w.bcol[rr4] != rowi[v0 + rr]) {
-                        if (atomicAdd(&g_cert_check[2], 1ull) == 0ull) {
-                            g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = (unsigned long long)((int64_t)bid * kRowsBlock + v0 + rr);
-                            g_cert_check[5] = (unsigned long long)(unsigned)rowi[v0 + rr]; g_cert_check[6] = (unsigned long long)(unsigned)w.bcol[rr4];
-                            g_cert_check[7] = (unsigned long long)(rowc[v0 + rr] & ~63u);
-                        }
-                    }
+                    if (((act_mask >> rr) & 1u) != 0u && rowm[v0 + rr] != 0 && w.bcol[rr4] != rowi[v0 + rr])
+                        cert_check_disagreement(k, (int64_t)bid * kRowsBlock + v0 + rr, rowi[v0 + rr], w.bcol[rr4], rowc[v0 + rr]);
                 }
             }
             wave_lds_fence();
@@ -260,15 +198,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
                 for (int rr4 = 0; rr4 < 4; ++rr4) {
                     const int rr = q_p + 4 * rr4;
                     rowi[v0 + rr] = w.bcol[rr4];
-                    // new keys for the rows that were searched: L^2 = min(final culling bound, runner-up among the multiplied columns), both on d^2
-                    if (certs && ((act_mask >> rr) & 1u) != 0u && rowm[v0 + rr] == 0) {
-                        typedef unsigned uu2 __attribute__((ext_vector_type(2)));
-                        const uu2 pat = { 0u, w.sec[rr4] };
-                        const double d2nd = w.sec[rr4] == 0xFFFFFFFFu ? INFINITY : __builtin_bit_cast(double, pat) - 1.0 - w.eps_out;
-                        const double l2 = fmin(w.rb_out[rr4], d2nd);
-                        const uint32_t lb = l2 > 0.0 && k < kCertHist ? (__float_as_uint(f32_down(sqrt(l2) * (1.0 - 1e-7))) & ~63u) : 0u;
-                        rowc[v0 + rr] = lb > 63u ? (lb | (uint32_t)k) : 0u;
-                    }
+                    // new keys for the rows that were searched
+                    if (certs && ((act_mask >> rr) & 1u) != 0u && rowm[v0 + rr] == 0) rowc[v0 + rr] = cert_word(w.sec[rr4], w.eps_out, w.rb_out[rr4], k);
                 }
             }
             if (w.light_gap2 >= 0.0) gap2_blk = fmin(gap2_blk, w.light_gap2);
@@ -277,14 +208,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
         }
         const int lane_e = opaque_i((int)threadIdx.x);
         const unsigned long long lt_e = (1ull << lane_e) - 1ull;
-        if (certs && cert_check && lane_e == 0) {
-            if (bid == 0 && g_cert_check[2] == 0ull) {
-                g_cert_check[3] = (unsigned long long)k; g_cert_check[4] = __builtin_bit_cast(unsigned long long, st->last_motion);
-                g_cert_check[5] = __builtin_bit_cast(unsigned long long, st->motion); g_cert_check[6] = __builtin_bit_cast(unsigned long long, c_skin);
-            }
-            atomicAdd(&g_cert_check[0], (unsigned long long)__builtin_popcountll(certd64));
-            atomicAdd(&g_cert_check[1], (unsigned long long)__builtin_popcountll(act64 & ~certd64));
-        }
+        if (certs && cert_check && lane_e == 0) cert_check_count(bid == 0, k, st, c_skin, __builtin_popcountll(certd64), __builtin_popcountll(act64 & ~certd64));
         if (tile_visits && lane_e == 0 && visited_total) atomicAdd(tile_visits + (blockIdx.x & (kVisitSlots - 1)), (unsigned long long)visited_total);
 
         // the chosen pairs: direct distance (AC3), contribution to the sums -- one row per lane
@@ -322,29 +246,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
                     for (int e = 0; e < 3; ++e) P.ptgt_sorted[3 * row_e + e] = tf[e];
                 }
                 const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
-                const double dx = s[0] - t[0], dy = s[1] - t[1], dz = s[2] - t[2];
-                const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
-                if (d2 < max_d2) {
-                    c[0] = 1.0; c[1] = d2;
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) { c[2 + e] = s[e]; c[5 + e] = t[e]; }
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) c[8 + 3 * a + e] = t[a] * s[e];
-                    if (MODE == 1) {
-                        const double nx = nf[0], ny = nf[1], nz = nf[2];
-                        const double res = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
-                        const double J[6] = { s[1] * nz - s[2] * ny, s[2] * nx - s[0] * nz, s[0] * ny - s[1] * nx, nx, ny, nz };
-                        int slot = 17;
-#pragma unroll
-                        for (int a = 0; a < 6; ++a)
-#pragma unroll
-                            for (int e = a; e < 6; ++e) c[slot++] = J[a] * J[e];
-#pragma unroll
-                        for (int a = 0; a < 6; ++a) c[38 + a] = J[a] * res;
-                    }
-                }
+                const double d2 = pair_d2(s, t);
+                if (d2 < max_d2) pair_terms(s, t, d2, MODE == 1, nf, [&](int slot, double v) { c[slot] = v; });
             }
         }
         // per tile the balanced tree (every lane of the tile's DPP row ends with the tile's partial), then the four partials exactly
@@ -384,22 +287,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
     if (tk != P.blocks - 1u) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int lane_w = opaque_i((int)threadIdx.x);
-    if (lane_w < kAcc) s_sums[lane_w] = lane_w < NACC ? fixed_total_coherent(P.ring, lane_w) : 0.0;
-    const unsigned long long n_searched = searched_take(ticket, lane_w);
-    for (int e = lane_w; e < kAccSet; e += 64) __hip_atomic_store(P.ring + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane_w == 0) __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    wave_lds_fence();
+    const unsigned long long n_searched = winner_take<kRowsBlock, true>(P.ring, ticket, NACC, s_sums, lane_w);
     const double *tbbox_w = P.tbbox;
     asm volatile("" : "+s"(tbbox_w));
     const double t2max_w = target_t2max(tbbox_w);
     icp_finish_wave(s_sums, P.n, MODE, k, max_iter, rel_fit, rel_rmse, &s_state, P.result, s_tail, lane_w,
                     LightSkip{ use_light ? P.sbbox : (const double *)nullptr, max_d2, t2max_w });
     wave_lds_fence();
-    if (lane_w < (int)(sizeof(IcpState) / sizeof(double))) reinterpret_cast<double *>(st)[lane_w] = reinterpret_cast<const double *>(&s_state)[lane_w];
-    if (certs && k + 1 < kCertHist && lane_w < 12) P.thist[12 * (k + 1) + lane_w] = s_state.T[lane_w];     // what iteration k + 1 transforms with
-    if (lane_w == 0 && P.progress)
-        __hip_atomic_store(P.progress, P.tag | progress_searched(n_searched, P.n) | ((unsigned long long)(s_state.done ? 1 : 0) << 32) | (unsigned long long)(unsigned)(k + 1),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    winner_publish(st, &s_state, certs ? P.thist : (double *)nullptr, k, P.progress, P.tag, n_searched, P.n, lane_w);
 }
 
 }  // namespace kpx

@@ -290,8 +290,7 @@ __global__ void icp_init_kernel(IcpState *st, Mat16 T0)
     if (threadIdx.x || blockIdx.x) return;
     for (int slot = 0; slot < 2; ++slot) {               // both slots (see IcpFuse)
         for (int q = 0; q < 16; ++q) st[slot].T[q] = T0.m[q];
-        st[slot].fitness = 0.0; st[slot].rmse = 0.0; st[slot].count = 0.0; st[slot].iter = 0; st[slot].done = 0;
-        st[slot].motion = 0.0; st[slot].reach = INFINITY; st[slot].last_motion = INFINITY; st[slot].smax = -1.0;
+        state_fresh(&st[slot]);
     }
 }
 

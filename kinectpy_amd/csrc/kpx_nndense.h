@@ -589,35 +589,20 @@ __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__
             double s[3];
             xform_row(T, src + 3 * i, s);
             const float *tp = tgt + 3 * (int64_t)bj;
-            double t[3] = { (double)tp[0], (double)tp[1], (double)tp[2] };
-            double dx = s[0] - t[0], dy = s[1] - t[1], dz = s[2] - t[2];
-            double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
+            const double t[3] = { (double)tp[0], (double)tp[1], (double)tp[2] };
+            const double d2 = pair_d2(s, t);
             if (d2_out) d2_out[i] = d2;
             if (mode >= 0 && d2 < max_d2) {
-                acc[0] = 1.0; acc[1] = d2;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { acc[2 + k] = s[k]; acc[5 + k] = t[k]; }
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) acc[8 + 3 * p + q] = t[p] * s[q];
+                // (the plain point-to-plane terms come with the point-to-point ones; GICP, the robust losses and the coloured mode form theirs below)
+                const bool plane = !Terms::kGicp && !Terms::kRobust && mode == 1;
+                pair_terms(s, t, d2, plane, plane ? tn + 3 * (int64_t)bj : (const float *)nullptr, [&](int q, double v) { acc[q] = v; });
                 if constexpr (Terms::kGicp) {
                     gicp_pair_rows(ct, T, ct.src_cov + 9 * i, ct.tgt_cov + 9 * (int64_t)bj, s, t, acc);
                 } else if (mode == 1) {
-                    const float *np_ = tn + 3 * (int64_t)bj;
-                    double nx = np_[0], ny = np_[1], nz = np_[2];
-                    double r = (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
-                    double J[6] = { s[1] * nz - s[2] * ny, s[2] * nx - s[0] * nz, s[0] * ny - s[1] * nx, nx, ny, nz };
                     if constexpr (Terms::kRobust) {
+                        double J[6];
+                        const double r = plane_row(s, t, tn + 3 * (int64_t)bj, J);
                         robust_row(ct.loss, J, r, acc);
-                    } else {
-                        int q = 17;
-#pragma unroll
-                        for (int p = 0; p < 6; ++p)
-#pragma unroll
-                            for (int c = p; c < 6; ++c) acc[q++] = J[p] * J[c];
-#pragma unroll
-                        for (int p = 0; p < 6; ++p) acc[38 + p] = J[p] * r;
                     }
                 } else if (mode == 2) {
                     const float *np_ = tn + 3 * (int64_t)bj;

@@ -71,6 +71,15 @@ __global__ __launch_bounds__(256) void nn_local_prep_kernel(const float *__restr
     }
 }
 
+// largest |t|^2 a target point can have (from the target's bounding box): scales the rounding margin of the expanded metric
+__device__ __forceinline__ double target_t2max(const double *__restrict__ tbbox)
+{
+    double t2max = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t2max += fmax(tbbox[a] * tbbox[a], tbbox[3 + a] * tbbox[3 + a]);
+    return t2max;
+}
+
 // Per-row operands in sorted row order.  prev (indexed by ORIGINAL row) = partners of the last search or NULL;
 // max_d2 > 0 clamps the bound to the correspondence distance.
 __global__ __launch_bounds__(256) void nn_local_rowprep_kernel(const float *__restrict__ src, int64_t n, const float *__restrict__ tgt,
@@ -94,24 +103,9 @@ __global__ __launch_bounds__(256) void nn_local_rowprep_kernel(const float *__re
     int32_t bj = INT_MAX;
     if (prev) {
         const int32_t j = prev[i];
-        if (j >= 0 && j != INT_MAX) {
-            const float *tp = tgt + 3 * (int64_t)j;
-            const double tx = tp[0], ty = tp[1], tz = tp[2];
-            const double t2 = fma(tx, tx, fma(ty, ty, tz * tz));
-            double d = fma(s[0], -2.0 * tx, seed);
-            d = fma(s[1], -2.0 * ty, d);
-            d = fma(s[2], -2.0 * tz, d);
-            bv = fma(1.0, t2, d);
-            bj = j;
-        }
+        if (j >= 0 && j != INT_MAX) { bv = partner_bound(s, seed, tgt + 3 * (int64_t)j); bj = j; }
     }
-    if (max_d2 > 0.0) {
-        double t2max = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) t2max += fmax(tbbox[a] * tbbox[a], tbbox[3 + a] * tbbox[3 + a]);
-        const double clamp = (max_d2 + 1.0) * (1.0 + 9.31322574615478515625e-10) + ldexp(seed + t2max + 1.0, -38);
-        if (!(bv <= clamp)) { bv = clamp; bj = INT_MAX; }
-    }
+    if (max_d2 > 0.0) bound_clamp(seed, max_d2, target_t2max(tbbox), bv, bj);
     init_val[r] = bv;
     init_idx[r] = bj;
 }
@@ -247,14 +241,6 @@ __device__ __forceinline__ void group_pre_load(GroupPre &g, const float *__restr
 {
 #pragma unroll
     for (int t = 0; t < kGroupPre; ++t) group_box_load(g.b[t], group_box, n_groups, 64 * t + lane);
-}
-// largest |t|^2 a target point can have (from the target's bounding box): scales the rounding margin of the expanded metric
-__device__ __forceinline__ double target_t2max(const double *__restrict__ tbbox)
-{
-    double t2max = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t2max += fmax(tbbox[a] * tbbox[a], tbbox[3 + a] * tbbox[3 + a]);
-    return t2max;
 }
 __device__ __forceinline__ double box_gap2v(const double slo[3], const double shi[3], const float bx[6])
 {
