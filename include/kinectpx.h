@@ -904,6 +904,49 @@ int kpx_rayscene_rays(const void *scene, size_t scene_bytes, const float *rays, 
 int kpx_rayscene_closest(const void *scene, size_t scene_bytes, const float *queries, int64_t m, int32_t brute, double *out_d2, float *out_points,
                          float *out_distance, int32_t *out_geometry_ids, int32_t *out_primitive_ids, void *stream);
 
+/* ---- mesh checks ([O3D] geometry.TriangleMesh; arithmetic contract AC15) ---------------------------------------------
+ * Arrays, index rule, limits and fp64 arithmetic as in the clean-up section above; tests/mesh_checks_ref.py is the pinned statement.
+ * kpx_mesh_non_manifold_vertices: the link of v has one edge {u, w} per triangle in which v occurs exactly once (u, w: its other two
+ *     corners); out_vertices i32 (room for n_vertices) receives, ascending, the vertices whose link has more than one connected
+ *     component, *d_count (i32, device) = how many, or KPX_ERR_RANGE when a union-find hook gave up.  A vertex without a link edge is not
+ *     reported.  ws: kpx_mesh_links_workspace_bytes.
+ * kpx_mesh_orientation: triangles with a repeated index take no part.  Two others are neighbours when they share an edge key (every pair
+ *     of a run of equal keys) and agree on it when they run it in opposite directions.  *d_orientable (i32, device) = 1 when some flip
+ *     assignment makes all neighbours agree on all shared edges, 0 when none does, KPX_ERR_RANGE when a hook gave up.  When orientable:
+ *     in every connected component the smallest triangle keeps its winding and decides the rest; out_flip u8 [n_triangles] (optional) =
+ *     1 for the triangles to flip, apply_triangles (optional, may be `triangles` itself) gets (t0, t1, t2) -> (t0, t2, t1) for them and
+ *     apply_triangle_normals (optional) their rows negated.  When not orientable out_flip is 0 and nothing else is written.
+ * kpx_mesh_volume: *d_volume (f64, device) = |S| / 6.0, S the sum from 0, in ascending triangle index, of v0 . (v1 x v2) (cross
+ *     components a b - c d, dot (x x' + y y') + z z').  Whether the mesh encloses a volume is the caller's question.
+ * kpx_mesh_edge_count: *d_count (i32, device) = the number of distinct edge keys.  ws: kpx_mesh_edges_workspace_bytes.
+ * kpx_rayscene_triangle_pairs_*: one query triangle per row of `triangles` (indices into `vertices`) against the triangles of a scene.
+ *     A query i and a scene triangle g intersect when their exact boxes (corner min / max as doubles, no padding; closed comparison)
+ *     overlap and Moeller's division-free interval test with the coplanar fallback, tri_tri(i, g) of the pinned statement, says so
+ *     (plane distances below the absolute 1e-6 count as 0).  self != 0: the queries are the very triangles the scene was built from
+ *     (m = its triangle count, else KPX_ERR_INVALID); only g > i is examined and a pair that shares a vertex index is skipped.
+ *     _count, any == 0: out_offsets i64 [m + 1] = the exclusive prefix sums of the queries' partner counts, [m] the total.
+ *     _count, any != 0: *d_flag (i32, device) = 1 when some query has a partner, else 0; lanes stop at their first.
+ *     _fill: out_pairs i32 [n_pairs][2] = the pairs (i, g) ascending in (i, g); offsets and n_pairs as _count left them (the caller reads
+ *         offsets[m]); more than 2^31 - 1 pairs is KPX_ERR_RANGE.  ws: kpx_rayscene_triangle_pairs_workspace_bytes(n_pairs).
+ *     brute != 0: every scene triangle in ascending index instead of the tree walk; same pairs.  The tree prunes a node only when its
+ *     box does not overlap the query's exact box.  Scene checks and the header read-back as for the ray queries. */
+size_t kpx_mesh_links_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_non_manifold_vertices(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t *out_vertices, int32_t *d_count, void *ws,
+                                   size_t ws_bytes, void *stream);
+size_t kpx_mesh_orientation_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int kpx_mesh_orientation(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, uint8_t *out_flip, int32_t *apply_triangles,
+                         float *apply_triangle_normals, int32_t *d_orientable, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_mesh_volume_workspace_bytes(int64_t n_triangles);
+int kpx_mesh_volume(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_volume, void *ws,
+                    size_t ws_bytes, void *stream);
+int kpx_mesh_edge_count(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_rayscene_triangle_pairs_count(const void *scene, size_t scene_bytes, const float *vertices, int64_t n_vertices, const int32_t *triangles,
+                                      int64_t m, int32_t self, int32_t any, int32_t brute, int64_t *out_offsets, int32_t *d_flag, void *stream);
+size_t kpx_rayscene_triangle_pairs_workspace_bytes(int64_t n_pairs);
+int kpx_rayscene_triangle_pairs_fill(const void *scene, size_t scene_bytes, const float *vertices, int64_t n_vertices, const int32_t *triangles,
+                                     int64_t m, int32_t self, int32_t brute, const int64_t *offsets, int64_t n_pairs, int32_t *out_pairs, void *ws,
+                                     size_t ws_bytes, void *stream);
+
 /* ---- occupancy grids ([O3D] geometry.VoxelGrid; arithmetic contract AC10) ---------------------------------------- */
 /* A grid is caller-owned: keys u64 [M], strictly ascending, key = gx << 42 | gy << 21 | gz with every index in [0, 2^21), and colors
  * f32 [M][3]; voxel g covers h_origin + g voxel .. h_origin + (g + 1) voxel.  All decisions are fp64.

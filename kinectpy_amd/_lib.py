@@ -188,6 +188,16 @@ SIGNATURES = {
     "kpx_rayscene_build": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     "kpx_rayscene_rays": (C.c_int, [_vp, _sz, _vp, _i64, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kpx_rayscene_closest": (C.c_int, [_vp, _sz, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kpx_mesh_links_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_non_manifold_vertices": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_orientation_workspace_bytes": (_sz, [_i64, _i64]),
+    "kpx_mesh_orientation": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_volume_workspace_bytes": (_sz, [_i64]),
+    "kpx_mesh_volume": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "kpx_mesh_edge_count": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "kpx_rayscene_triangle_pairs_count": (C.c_int, [_vp, _sz, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "kpx_rayscene_triangle_pairs_workspace_bytes": (_sz, [_i64]),
+    "kpx_rayscene_triangle_pairs_fill": (C.c_int, [_vp, _sz, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "kpx_voxelgrid_from_cloud_workspace_bytes": (_sz, [_i64]),
     "kpx_voxelgrid_from_cloud": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_voxelgrid_dense": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),

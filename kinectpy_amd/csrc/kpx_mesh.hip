@@ -1,6 +1,8 @@
 // kpx_mesh.hip -- operators on a triangle mesh (float32 vertices, int32 triangles): normals and surface area (arithmetic contract
 // AC12) and the clean-up path of AC13: vertex adjacency, non-manifold edges, connected triangles,
 // ordered removal, Laplacian / Taubin smoothing and uniform sampling ([O3D] geometry.TriangleMesh).
+// The checks of AC15 reuse those pieces: vertex links as a union-find over the adjacency's entries, orientation as a
+// union-find over the double cover of the triangles, the volume as the ordered chain with another term, the edge count.
 //
 // The shape shared by adjacency, edges and clusters: one 64-bit key per (vertex, vertex) pair of every triangle, one stable radix sort,
 // then a pass over the sorted keys in which every entry looks only at its predecessor.  Every fp64 sum whose order the contract fixes
@@ -154,14 +156,17 @@ __device__ __forceinline__ bool mesh_corners(const int32_t *__restrict__ tri, in
 // ---- pair keys (AC13) -------------------------------------------------------------------------------------------------------------
 // directed: the six ordered corner pairs of a triangle, key = v << 32 | u (adjacency); else its three undirected edges, key =
 // min << 32 | max.  A triangle with a corner out of range gets the key nv << 32, above every real one.  vals: the key's number, for
-// the caller that needs the triangle behind a sorted key (the clusters); null otherwise.
+// the caller that needs the triangle behind a sorted key (the clusters); null otherwise.  skip_repeated: a triangle with two equal
+// indices gets that key too (AC15's orientation: it takes no part).
 __global__ __launch_bounds__(kMeshThreads) void mesh_pair_keys_kernel(const int32_t *__restrict__ tri, int64_t nt, int64_t nv, int directed,
-                                                                      uint64_t *__restrict__ keys, int32_t *__restrict__ vals, int32_t *__restrict__ parent)
+                                                                      uint64_t *__restrict__ keys, int32_t *__restrict__ vals, int32_t *__restrict__ parent,
+                                                                      int skip_repeated)
 {
     const int64_t t = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
     if (t >= nt) return;
     int32_t c[3];
-    const bool ok = mesh_corners(tri, t, nv, c);
+    bool ok = mesh_corners(tri, t, nv, c);
+    if (skip_repeated && (c[0] == c[1] || c[1] == c[2] || c[0] == c[2])) ok = false;
     const uint64_t bad = (uint64_t)nv << 32;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -183,9 +188,11 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_pair_keys_kernel(const int3
 // the pairs of every triangle in ascending key order -> keys_out (and vals_out: each key's number, where the sort carries values);
 // carved for (directed ? 6 : 3) * nt pairs
 template <bool kVals>
-int pair_sort(const int32_t *tri, int64_t nt, int64_t nv, bool directed, const DeviceSort<uint64_t, kVals> &s, int32_t *parent, hipStream_t st)
+int pair_sort(const int32_t *tri, int64_t nt, int64_t nv, bool directed, const DeviceSort<uint64_t, kVals> &s, int32_t *parent, hipStream_t st,
+              bool skip_repeated = false)
 {
-    hipLaunchKernelGGL(mesh_pair_keys_kernel, dim3(mesh_blocks(nt)), dim3(kMeshThreads), 0, st, tri, nt, nv, directed ? 1 : 0, s.keys_in, s.vals_in, parent);
+    hipLaunchKernelGGL(mesh_pair_keys_kernel, dim3(mesh_blocks(nt)), dim3(kMeshThreads), 0, st, tri, nt, nv, directed ? 1 : 0, s.keys_in, s.vals_in, parent,
+                       skip_repeated ? 1 : 0);
     KPX_LAUNCH_CHECK();
     return dsort_run(s, (directed ? 6 : 3) * nt, 32 + bits_for(nv), st);
 }
@@ -222,6 +229,21 @@ void adjacency_carve(Arena &a, int64_t nt, AdjacencyScratch *s)
     dsort_carve(a, 6 * nt, 64, SortOptions(), &s->p);
     s->owner = a.get<int32_t>((size_t)(nt > 0 ? 6 * nt : 1));
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(6 * nt));
+}
+
+// the CSR of n_triangles > 0 triangles -> out_offsets [nv + 1], out_neighbours [6 nt], *d_count entries
+int adjacency_run(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, const AdjacencyScratch &s, int32_t *out_offsets, int32_t *out_neighbours,
+                  int32_t *d_count, hipStream_t st)
+{
+    int rc = pair_sort(triangles, n_triangles, n_vertices, true, s.p, nullptr, st);
+    if (rc) return rc;
+    const uint64_t bad = (uint64_t)n_vertices << 32;
+    rc = compact(UniquePairPred{ s.p.keys_out, bad }, NeighbourEmit{ s.p.keys_out, out_neighbours, s.owner }, 6 * n_triangles, 1, s.counts, d_count, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mesh_offsets_kernel, dim3(mesh_blocks(n_vertices + 1)), dim3(kMeshThreads), 0, st, (const int32_t *)s.owner, (const int32_t *)d_count,
+                       n_vertices, out_offsets);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
 }
 
 // ---- edges --------------------------------------------------------------------------------------------------------------------------
@@ -318,11 +340,29 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_label_kernel(int64_t nt, co
 //   SEG = false: out[i] = the sum of the terms 0 .. i (the sampler's cumulative areas)
 //   SEG = true:  seg[i] (ascending) is the item's segment; the accumulator restarts from 0 at each new segment and out[seg] = the sum
 //                at the segment's last item (the clusters' areas)
+//   TERM = kTermTriple: the term is AC15's v0 . (v1 x v2) instead (the volume); a sum of signed terms that starts from +0.0 is
+//                never -0.0 either (x + -x rounds to +0.0)
+enum { kTermArea, kTermTriple };
+__device__ __forceinline__ double mesh_triple(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t t)
+{
+    int32_t c[3];
+    c[0] = tri[3 * t]; c[1] = tri[3 * t + 1]; c[2] = tri[3 * t + 2];
+    if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= nv || c[1] >= nv || c[2] >= nv) return 0.0;
+    double a[3], b[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a[k] = (double)v[3 * (int64_t)c[0] + k];
+        b[k] = (double)v[3 * (int64_t)c[1] + k];
+        d[k] = (double)v[3 * (int64_t)c[2] + k];
+    }
+    const double cx = b[1] * d[2] - b[2] * d[1], cy = b[2] * d[0] - b[0] * d[2], cz = b[0] * d[1] - b[1] * d[0];
+    return (a[0] * cx + a[1] * cy) + a[2] * cz;
+}
 constexpr int kChainGroup = 16;
 constexpr int kChainWorkers = kAreaThreads - 64;
 constexpr int kChainBatch = 2 * kChainWorkers;
 static_assert(kChainBatch % kChainGroup == 0, "the adder takes whole groups");
-template <bool SEG>
+template <bool SEG, int TERM = kTermArea>
 __global__ __launch_bounds__(kAreaThreads) void mesh_chain_kernel(const float *__restrict__ v, int64_t nv, const int32_t *__restrict__ tri, int64_t nt,
                                                                   const int32_t *__restrict__ order, const uint32_t *__restrict__ seg, double *__restrict__ out)
 {
@@ -334,9 +374,13 @@ __global__ __launch_bounds__(kAreaThreads) void mesh_chain_kernel(const float *_
         if (i < nt) {
             const int64_t t = order ? (int64_t)order[i] : i;
             if (t >= 0 && t < nt) {
-                double n[3];
-                mesh_cross(v, nv, tri, t, n);
-                half = mesh_norm(n) * 0.5;
+                if (TERM == kTermTriple) {
+                    half = mesh_triple(v, nv, tri, t);
+                } else {
+                    double n[3];
+                    mesh_cross(v, nv, tri, t, n);
+                    half = mesh_norm(n) * 0.5;
+                }
             }
         }
         return half;
@@ -618,6 +662,162 @@ void sample_carve(Arena &a, int64_t nt, SampleScratch *s)
     s->upto = a.get<int64_t>(t);
 }
 
+// ---- checks (AC15) ----------------------------------------------------------------------------------------------------------------------
+// parent[i] = i, mark[i] = 0 (mark may be null)
+__global__ __launch_bounds__(kMeshThreads) void mesh_iota_kernel(int64_t n, int32_t *__restrict__ parent, uint8_t *__restrict__ mark)
+{
+    const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = (int32_t)i;
+    if (mark) mark[i] = 0;
+}
+// where row v of the CSR names u, or -1
+__device__ __forceinline__ int32_t link_entry(const int32_t *__restrict__ off, const int32_t *__restrict__ nb, int64_t n_nb, int32_t v, int32_t u)
+{
+    int64_t lo = off[v], hi = off[v + 1];
+    if (lo < 0 || hi > n_nb || hi < lo) return -1;
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (nb[mid] < u) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && nb[lo] == u ? (int32_t)lo : -1;
+}
+// Vertex links on the CSR: the entries (v, u) are union-find nodes; a triangle in which v occurs once, beside u and w, marks (v, u)
+// and (v, w) as link nodes and unites them.  Marks are the same byte from every writer; the hooks are order-free.
+__global__ __launch_bounds__(kMeshThreads) void mesh_link_union_kernel(const int32_t *__restrict__ tri, int64_t nt, int64_t nv, const int32_t *__restrict__ off,
+                                                                       const int32_t *__restrict__ nb, int64_t n_nb, int32_t *parent, uint8_t *__restrict__ mark,
+                                                                       int32_t *__restrict__ err)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
+    if (t >= nt) return;
+    int32_t c[3];
+    if (!mesh_corners(tri, t, nv, c)) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int32_t v = c[k], u = c[(k + 1) % 3], w = c[(k + 2) % 3];
+        if (v == u || v == w) continue;
+        const int32_t eu = link_entry(off, nb, n_nb, v, u), ew = link_entry(off, nb, n_nb, v, w);
+        if (eu < 0 || ew < 0) continue;                        // (cannot happen: the row was built from these very pairs)
+        mark[eu] = 1;
+        mark[ew] = 1;
+        int32_t r = eu;
+        if (eu != ew && !uf_unite(parent, r, ew)) atomicExch(err, 1);
+    }
+}
+// flag[v] = 1 when the link nodes of row v (parent compressed) have more than one root
+__global__ __launch_bounds__(kMeshThreads) void mesh_link_flag_kernel(int64_t nv, const int32_t *__restrict__ off, int64_t n_nb, const int32_t *__restrict__ parent,
+                                                                      const uint8_t *__restrict__ mark, uint8_t *__restrict__ flag)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
+    if (v >= nv) return;
+    int64_t lo = off[v], hi = off[v + 1];
+    if (lo < 0 || hi > n_nb || hi < lo) lo = hi = 0;
+    int32_t first = -1;
+    uint8_t split = 0;
+    for (int64_t e = lo; e < hi; ++e) {
+        if (!mark[e]) continue;
+        const int32_t r = parent[e];
+        if (first < 0) first = r;
+        else if (r != first) split = 1;
+    }
+    flag[v] = split;
+}
+struct IndexEmit {
+    int32_t *out;
+    __device__ void operator()(int64_t i, int, int32_t dst) const { out[dst] = (int32_t)i; }
+};
+struct NoEmit {
+    __device__ void operator()(int64_t, int, int32_t) const {}
+};
+// a hook that gave up turns the count into KPX_ERR_RANGE
+__global__ void mesh_status_kernel(const int32_t *__restrict__ err, int32_t *__restrict__ d_count)
+{
+    if (*err) *d_count = KPX_ERR_RANGE;
+}
+struct LinkScratch {
+    AdjacencyScratch adj;
+    int32_t *off, *nb, *n_nb, *parent, *err, *counts;
+    uint8_t *mark, *flag;
+};
+void link_carve(Arena &a, int64_t nv, int64_t nt, LinkScratch *s)
+{
+    const size_t e = (size_t)(nt > 0 ? 6 * nt : 1), v = (size_t)(nv > 0 ? nv : 1);
+    adjacency_carve(a, nt, &s->adj);
+    s->off = a.get<int32_t>(v + 1);
+    s->nb = a.get<int32_t>(e);
+    s->n_nb = a.get<int32_t>(1);
+    s->parent = a.get<int32_t>(e);
+    s->err = a.get<int32_t>(1);
+    s->counts = a.get<int32_t>((size_t)compact_ws_ints(nv));
+    s->mark = a.get<uint8_t>(e);
+    s->flag = a.get<uint8_t>(v);
+}
+
+// Orientation on the double cover: node 2 t is triangle t as it is, 2 t + 1 flipped.  Consecutive entries of a run of equal edge keys
+// are neighbours: they agree when they run the edge in opposite directions (the direction is read back from the triangle through the
+// key's number 3 t + k).  A run of three or more cannot be satisfied by any assignment (of three directions two are equal, and every
+// pair of the run must differ), so it is flagged outright and the remaining pairs of the run need no hook.
+__global__ __launch_bounds__(kMeshThreads) void mesh_orient_union_kernel(const uint64_t *__restrict__ keys, const int32_t *__restrict__ vals, int64_t n, uint64_t bad,
+                                                                         const int32_t *__restrict__ tri, int32_t *parent, int32_t *__restrict__ err,
+                                                                         int32_t *__restrict__ one_sided)
+{
+    const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x + 1;
+    if (i >= n) return;
+    const uint64_t x = keys[i];
+    if (x >= bad || keys[i - 1] != x) return;
+    if (i >= 2 && keys[i - 2] == x) atomicExch(one_sided, 1);
+    const int32_t ja = vals[i], jb = vals[i - 1];
+    const int32_t ta = ja / 3, ka = ja % 3, tb = jb / 3, kb = jb % 3;
+    const bool da = tri[3 * (int64_t)ta + ka] < tri[3 * (int64_t)ta + (ka + 1) % 3], db = tri[3 * (int64_t)tb + kb] < tri[3 * (int64_t)tb + (kb + 1) % 3];
+    const int32_t a = 2 * ta, b = 2 * tb + (da == db ? 1 : 0);
+    int32_t r = a;
+    if (!uf_unite(parent, r, b)) atomicExch(err, 1);
+    r = a ^ 1;
+    if (!uf_unite(parent, r, b ^ 1)) atomicExch(err, 1);
+}
+__global__ __launch_bounds__(kMeshThreads) void mesh_orient_check_kernel(int64_t nt, const int32_t *__restrict__ parent, int32_t *__restrict__ one_sided)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
+    if (t < nt && parent[2 * t] == parent[2 * t + 1]) atomicExch(one_sided, 1);
+}
+// A root is its set's smallest member, so the set of a component's smallest triangle t0 as it is has the root 2 t0 and the mirror
+// set 2 t0 + 1: t is flipped exactly when the root of 2 t is odd.  Nothing is written to the mesh unless it is orientable.
+__global__ __launch_bounds__(kMeshThreads) void mesh_orient_apply_kernel(int64_t nt, const int32_t *__restrict__ parent, const int32_t *__restrict__ one_sided,
+                                                                         const int32_t *__restrict__ err, uint8_t *__restrict__ out_flip, int32_t *tri, float *tnrm,
+                                                                         int32_t *__restrict__ d_orientable)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
+    const bool ok = !*one_sided && !*err;
+    if (t == 0) *d_orientable = *err ? KPX_ERR_RANGE : (ok ? 1 : 0);
+    if (t >= nt) return;
+    const bool flip = ok && (parent[2 * t] & 1);
+    if (out_flip) out_flip[t] = flip ? 1 : 0;
+    if (!flip) return;
+    if (tri) {
+        const int32_t c1 = tri[3 * t + 1], c2 = tri[3 * t + 2];
+        tri[3 * t + 1] = c2;
+        tri[3 * t + 2] = c1;
+    }
+    if (tnrm) { tnrm[3 * t] = -tnrm[3 * t]; tnrm[3 * t + 1] = -tnrm[3 * t + 1]; tnrm[3 * t + 2] = -tnrm[3 * t + 2]; }
+}
+struct OrientScratch {
+    DeviceSort<uint64_t> p;
+    int32_t *parent, *err, *one_sided;
+};
+void orient_carve(Arena &a, int64_t nt, OrientScratch *s)
+{
+    dsort_carve(a, 3 * nt, 64, SortOptions(), &s->p);
+    s->parent = a.get<int32_t>((size_t)(nt > 0 ? 2 * nt : 1));
+    s->err = a.get<int32_t>(1);
+    s->one_sided = a.get<int32_t>(1);
+}
+// *out = |prefix[nt - 1]| / 6.0: one division, after the sum (AC15)
+__global__ void mesh_volume_kernel(const double *__restrict__ prefix, int64_t nt, double *__restrict__ out)
+{
+    *out = nt > 0 ? fabs(prefix[nt - 1]) / 6.0 : 0.0;
+}
+
 inline bool mesh_counts_ok(int64_t nv, int64_t nt) { return nv >= 0 && nt >= 0 && nv <= kMeshMax && 6 * nt <= kMeshMax; }
 #define KPX_MESH_COUNTS(who, nv, nt)                                                                                                       \
     do {                                                                                                                                   \
@@ -712,15 +912,7 @@ KPX_EXPORT int kpx_mesh_adjacency(const int32_t *triangles, int64_t n_vertices, 
     AdjacencyScratch s;
     adjacency_carve(a, n_triangles, &s);
     KPX_ARENA_CHECK(a);
-    int rc = pair_sort(triangles, n_triangles, n_vertices, true, s.p, nullptr, st);
-    if (rc) return rc;
-    const uint64_t bad = (uint64_t)n_vertices << 32;
-    rc = compact(UniquePairPred{ s.p.keys_out, bad }, NeighbourEmit{ s.p.keys_out, out_neighbours, s.owner }, 6 * n_triangles, 1, s.counts, d_count, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(mesh_offsets_kernel, dim3(mesh_blocks(n_vertices + 1)), dim3(kMeshThreads), 0, st, (const int32_t *)s.owner, (const int32_t *)d_count,
-                       n_vertices, out_offsets);
-    KPX_LAUNCH_CHECK();
-    return KPX_OK;
+    return adjacency_run(triangles, n_vertices, n_triangles, s, out_offsets, out_neighbours, d_count, st);
 }
 
 KPX_EXPORT size_t kpx_mesh_edges_workspace_bytes(int64_t n_vertices, int64_t n_triangles)
@@ -949,4 +1141,126 @@ KPX_EXPORT int kpx_mesh_sample_points(const float *vertices, const float *colors
     hipLaunchKernelGGL(mesh_sample_kernel, dim3(mesh_blocks(n_points)), dim3(kMeshThreads), 0, st, (const int64_t *)s.upto, (const double *)d_total, S);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
+}
+
+KPX_EXPORT size_t kpx_mesh_links_workspace_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (!mesh_counts_ok(n_vertices, n_triangles)) return 0;
+    Arena a(nullptr, 0);
+    LinkScratch s;
+    link_carve(a, n_vertices, n_triangles, &s);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_mesh_non_manifold_vertices(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t *out_vertices, int32_t *d_count, void *ws,
+                                              size_t ws_bytes, void *stream)
+{
+    KPX_MESH_COUNTS("kpx_mesh_non_manifold_vertices", n_vertices, n_triangles);
+    KPX_REQUIRE(d_count && ws, "kpx_mesh_non_manifold_vertices: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_triangles == 0 || n_vertices == 0) { KPX_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st)); return KPX_OK; }
+    KPX_REQUIRE(triangles && out_vertices, "kpx_mesh_non_manifold_vertices: null pointer");
+    Arena a(ws, ws_bytes);
+    LinkScratch s;
+    link_carve(a, n_vertices, n_triangles, &s);
+    KPX_ARENA_CHECK(a);
+    const int64_t n_nb = 6 * n_triangles;
+    KPX_HIP(hipMemsetAsync(s.err, 0, sizeof(int32_t), st));
+    int rc = adjacency_run(triangles, n_vertices, n_triangles, s.adj, s.off, s.nb, s.n_nb, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mesh_iota_kernel, dim3(mesh_blocks(n_nb)), dim3(kMeshThreads), 0, st, n_nb, s.parent, s.mark);
+    hipLaunchKernelGGL(mesh_link_union_kernel, dim3(mesh_blocks(n_triangles)), dim3(kMeshThreads), 0, st, triangles, n_triangles, n_vertices, (const int32_t *)s.off,
+                       (const int32_t *)s.nb, n_nb, s.parent, s.mark, s.err);
+    hipLaunchKernelGGL(mesh_compress_kernel, dim3(mesh_blocks(n_nb)), dim3(kMeshThreads), 0, st, n_nb, s.parent);
+    hipLaunchKernelGGL(mesh_link_flag_kernel, dim3(mesh_blocks(n_vertices)), dim3(kMeshThreads), 0, st, n_vertices, (const int32_t *)s.off, n_nb,
+                       (const int32_t *)s.parent, (const uint8_t *)s.mark, s.flag);
+    KPX_LAUNCH_CHECK();
+    rc = compact(FlagPred{ s.flag, 0 }, IndexEmit{ out_vertices }, n_vertices, 1, s.counts, d_count, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mesh_status_kernel, dim3(1), dim3(1), 0, st, (const int32_t *)s.err, d_count);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT size_t kpx_mesh_orientation_workspace_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (!mesh_counts_ok(n_vertices, n_triangles)) return 0;
+    Arena a(nullptr, 0);
+    OrientScratch s;
+    orient_carve(a, n_triangles, &s);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_mesh_orientation(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, uint8_t *out_flip, int32_t *apply_triangles,
+                                    float *apply_triangle_normals, int32_t *d_orientable, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_MESH_COUNTS("kpx_mesh_orientation", n_vertices, n_triangles);          // (6 T < 2^31: the 2 T nodes fit an int32 with room)
+    KPX_REQUIRE(d_orientable && ws, "kpx_mesh_orientation: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_triangles == 0) {
+        const int32_t one = 1;
+        KPX_HIP(hipMemcpyAsync(d_orientable, &one, sizeof(one), hipMemcpyHostToDevice, st));
+        KPX_HIP(hipStreamSynchronize(st));
+        return KPX_OK;
+    }
+    KPX_REQUIRE(triangles, "kpx_mesh_orientation: null pointer");
+    Arena a(ws, ws_bytes);
+    OrientScratch s;
+    orient_carve(a, n_triangles, &s);
+    KPX_ARENA_CHECK(a);
+    KPX_HIP(hipMemsetAsync(s.err, 0, sizeof(int32_t), st));
+    KPX_HIP(hipMemsetAsync(s.one_sided, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(mesh_iota_kernel, dim3(mesh_blocks(2 * n_triangles)), dim3(kMeshThreads), 0, st, 2 * n_triangles, s.parent, (uint8_t *)nullptr);
+    const int rc = pair_sort(triangles, n_triangles, n_vertices, false, s.p, nullptr, st, true);
+    if (rc) return rc;
+    const unsigned nb = mesh_blocks(n_triangles);
+    hipLaunchKernelGGL(mesh_orient_union_kernel, dim3(mesh_blocks(3 * n_triangles)), dim3(kMeshThreads), 0, st, (const uint64_t *)s.p.keys_out,
+                       (const int32_t *)s.p.vals_out, 3 * n_triangles, (uint64_t)n_vertices << 32, triangles, s.parent, s.err, s.one_sided);
+    hipLaunchKernelGGL(mesh_compress_kernel, dim3(mesh_blocks(2 * n_triangles)), dim3(kMeshThreads), 0, st, 2 * n_triangles, s.parent);
+    hipLaunchKernelGGL(mesh_orient_check_kernel, dim3(nb), dim3(kMeshThreads), 0, st, n_triangles, (const int32_t *)s.parent, s.one_sided);
+    hipLaunchKernelGGL(mesh_orient_apply_kernel, dim3(nb), dim3(kMeshThreads), 0, st, n_triangles, (const int32_t *)s.parent, (const int32_t *)s.one_sided,
+                       (const int32_t *)s.err, out_flip, apply_triangles, apply_triangle_normals, d_orientable);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT size_t kpx_mesh_volume_workspace_bytes(int64_t n_triangles)
+{
+    if (n_triangles < 0 || n_triangles > kMeshMax) return 0;
+    Arena a(nullptr, 0);
+    a.get<double>((size_t)(n_triangles > 0 ? n_triangles : 1));
+    return a.off;
+}
+
+KPX_EXPORT int kpx_mesh_volume(const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double *d_volume, void *ws,
+                               size_t ws_bytes, void *stream)
+{
+    KPX_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "kpx_mesh_volume: negative count");
+    if (n_vertices > kMeshMax || n_triangles > kMeshMax) return fail(KPX_ERR_RANGE, "kpx_mesh_volume: at most 2^31 - 1 vertices and triangles");
+    KPX_REQUIRE(d_volume && ws && (n_triangles == 0 || (vertices && triangles)), "kpx_mesh_volume: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    double *prefix = a.get<double>((size_t)(n_triangles > 0 ? n_triangles : 1));
+    KPX_ARENA_CHECK(a);
+    if (n_triangles > 0)
+        hipLaunchKernelGGL((mesh_chain_kernel<false, kTermTriple>), dim3(1), dim3(kAreaThreads), 0, st, vertices, n_vertices, triangles, n_triangles,
+                           (const int32_t *)nullptr, (const uint32_t *)nullptr, prefix);
+    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(1), 0, st, (const double *)prefix, n_triangles, d_volume);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_mesh_edge_count(const int32_t *triangles, int64_t n_vertices, int64_t n_triangles, int32_t *d_count, void *ws, size_t ws_bytes, void *stream)
+{
+    KPX_MESH_COUNTS("kpx_mesh_edge_count", n_vertices, n_triangles);
+    KPX_REQUIRE(d_count && ws && (n_triangles == 0 || triangles), "kpx_mesh_edge_count: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_triangles == 0) { KPX_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st)); return KPX_OK; }
+    Arena a(ws, ws_bytes);
+    EdgeScratch s;
+    edge_carve(a, n_triangles, &s);
+    KPX_ARENA_CHECK(a);
+    const int rc = pair_sort(triangles, n_triangles, n_vertices, false, s.p, nullptr, st);
+    if (rc) return rc;
+    return compact(UniquePairPred{ s.p.keys_out, (uint64_t)n_vertices << 32 }, NoEmit{}, 3 * n_triangles, 1, s.counts, d_count, st);
 }

@@ -12,6 +12,8 @@
 //            `brute` form (every triangle in ascending global index) call the same two functions, so the hierarchy can only decide
 //            WHICH triangles are tested.  A node is skipped only when the contract's pruning clauses allow it.  The closest-point
 //            kernel first descends once by the nearest child to have a bound before the walk starts (it decides no result).
+//   pairs  = AC15: one lane per query triangle walks the same tree with the visit "boxes overlap" and runs tri_tri in
+//            the leaves; count, scan, emit, one sort.
 #include "kpx_morton.h"
 
 #include <math.h>
@@ -449,6 +451,209 @@ void ray_launch(bool brute, unsigned nb, hipStream_t st, const RaySceneView &v, 
     else hipLaunchKernelGGL((ray_kernel<MODE, false>), dim3(nb), dim3(kRayThreads), 0, st, v, rays, m, tnear, tfar, t64, t, uv, nrm, geom, prim, count);
 }
 
+// ---- AC15: triangle against triangle ------------------------------------------------------------------------------------------------------
+// Moeller's interval-overlap test, division-free, with the coplanar fallback; tests/mesh_checks_ref.py is the pinned statement and
+// this follows it operation for operation.  Everything per lane is a scalar or a statically indexed array (the projection axes are
+// selects), so nothing lives in scratch memory.
+constexpr double kTriTriEpsilon = 1e-6;          // absolute: plane distances below it count as 0, whatever the mesh's scale
+
+__device__ __forceinline__ double pick3(int k, double x, double y, double z) { return k == 0 ? x : (k == 1 ? y : z); }
+// -> false: the triangle lies in the other's plane
+__device__ __forceinline__ bool tri_intervals(double vv0, double vv1, double vv2, double d0, double d1, double d2, double d0d1, double d0d2, double *A, double *B,
+                                              double *C, double *X0, double *X1)
+{
+    if (d0d1 > 0.0) { *A = vv2; *B = (vv0 - vv2) * d2; *C = (vv1 - vv2) * d2; *X0 = d2 - d0; *X1 = d2 - d1; }
+    else if (d0d2 > 0.0) { *A = vv1; *B = (vv0 - vv1) * d1; *C = (vv2 - vv1) * d1; *X0 = d1 - d0; *X1 = d1 - d2; }
+    else if (d1 * d2 > 0.0 || d0 != 0.0) { *A = vv0; *B = (vv1 - vv0) * d0; *C = (vv2 - vv0) * d0; *X0 = d0 - d1; *X1 = d0 - d2; }
+    else if (d1 != 0.0) { *A = vv1; *B = (vv0 - vv1) * d1; *C = (vv2 - vv1) * d1; *X0 = d1 - d0; *X1 = d1 - d2; }
+    else if (d2 != 0.0) { *A = vv2; *B = (vv0 - vv2) * d2; *C = (vv1 - vv2) * d2; *X0 = d2 - d0; *X1 = d2 - d1; }
+    else return false;
+    return true;
+}
+// closed test of the 2D edge from (vx, vy) along (ax, ay) against the edge u0 u1; parallel edges report nothing
+__device__ __forceinline__ bool edge_edge(double ax, double ay, double vx, double vy, double u0x, double u0y, double u1x, double u1y)
+{
+    const double bx = u0x - u1x, by = u0y - u1y, cx = vx - u0x, cy = vy - u0y;
+    const double f = ay * bx - ax * by, d = by * cx - bx * cy;
+    if ((f > 0.0 && d >= 0.0 && d <= f) || (f < 0.0 && d <= 0.0 && d >= f)) {
+        const double e = ax * cy - ay * cx;
+        return f > 0.0 ? (e >= 0.0 && e <= f) : (e <= 0.0 && e >= f);
+    }
+    return false;
+}
+// (px, py) strictly inside the 2D triangle u
+__device__ __forceinline__ bool point_in_tri(double px, double py, const double ux[3], const double uy[3])
+{
+    double a = uy[1] - uy[0], b = -(ux[1] - ux[0]), c = -a * ux[0] - b * uy[0];
+    const double d0 = (a * px + b * py) + c;
+    a = uy[2] - uy[1]; b = -(ux[2] - ux[1]); c = -a * ux[1] - b * uy[1];
+    const double d1 = (a * px + b * py) + c;
+    a = uy[0] - uy[2]; b = -(ux[0] - ux[2]); c = -a * ux[2] - b * uy[2];
+    const double d2 = (a * px + b * py) + c;
+    return d0 * d1 > 0.0 && d0 * d2 > 0.0;
+}
+__device__ __forceinline__ bool tri_coplanar(const double n[3], const double v[3][3], const double u[3][3])
+{
+    const double a0 = fabs(n[0]), a1 = fabs(n[1]), a2 = fabs(n[2]);
+    // the axes kept: (1, 2) when x is dropped, (0, 1) when z is, else (0, 2)
+    const bool drop_x = a0 > a1 && a0 > a2, drop_z = a0 > a1 ? !(a0 > a2) : a2 > a1;
+    double px[3], py[3], qx[3], qy[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        px[k] = drop_x ? v[k][1] : v[k][0]; py[k] = drop_z ? v[k][1] : v[k][2];
+        qx[k] = drop_x ? u[k][1] : u[k][0]; qy[k] = drop_z ? u[k][1] : u[k][2];
+    }
+    bool hit = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int e = (k + 1) % 3;
+        const double ax = px[e] - px[k], ay = py[e] - py[k];
+        hit = hit || edge_edge(ax, ay, px[k], py[k], qx[0], qy[0], qx[1], qy[1]) || edge_edge(ax, ay, px[k], py[k], qx[1], qy[1], qx[2], qy[2]) ||
+              edge_edge(ax, ay, px[k], py[k], qx[2], qy[2], qx[0], qy[0]);
+    }
+    return hit || point_in_tri(px[0], py[0], qx, qy) || point_in_tri(qx[0], qy[0], px, py);
+}
+// whether triangle v (the query; in a self search the lower index) meets triangle u; nine corner coordinates each
+__device__ __forceinline__ bool tri_tri(const float *__restrict__ cv, const float *__restrict__ cu)
+{
+    double v[3][3], u[3][3], e1[3], e2[3], n1[3], n2[3], dd[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        v[0][k] = (double)cv[k]; v[1][k] = (double)cv[3 + k]; v[2][k] = (double)cv[6 + k];
+        u[0][k] = (double)cu[k]; u[1][k] = (double)cu[3 + k]; u[2][k] = (double)cu[6 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { e1[k] = v[1][k] - v[0][k]; e2[k] = v[2][k] - v[0][k]; }
+    cross3(e1, e2, n1);
+    const double d1 = -dot3(n1, v[0]);
+    double du0 = dot3(n1, u[0]) + d1, du1 = dot3(n1, u[1]) + d1, du2 = dot3(n1, u[2]) + d1;
+    du0 = fabs(du0) < kTriTriEpsilon ? 0.0 : du0;
+    du1 = fabs(du1) < kTriTriEpsilon ? 0.0 : du1;
+    du2 = fabs(du2) < kTriTriEpsilon ? 0.0 : du2;
+    const double du0du1 = du0 * du1, du0du2 = du0 * du2;
+    if (du0du1 > 0.0 && du0du2 > 0.0) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { e1[k] = u[1][k] - u[0][k]; e2[k] = u[2][k] - u[0][k]; }
+    cross3(e1, e2, n2);
+    const double d2 = -dot3(n2, u[0]);
+    double dv0 = dot3(n2, v[0]) + d2, dv1 = dot3(n2, v[1]) + d2, dv2 = dot3(n2, v[2]) + d2;
+    dv0 = fabs(dv0) < kTriTriEpsilon ? 0.0 : dv0;
+    dv1 = fabs(dv1) < kTriTriEpsilon ? 0.0 : dv1;
+    dv2 = fabs(dv2) < kTriTriEpsilon ? 0.0 : dv2;
+    const double dv0dv1 = dv0 * dv1, dv0dv2 = dv0 * dv2;
+    if (dv0dv1 > 0.0 && dv0dv2 > 0.0) return false;
+    cross3(n1, n2, dd);
+    int index = 0;
+    double big = fabs(dd[0]);
+    if (fabs(dd[1]) > big) { index = 1; big = fabs(dd[1]); }
+    if (fabs(dd[2]) > big) index = 2;
+    double a, b, c, x0, x1, d, e, f, y0, y1;
+    if (!tri_intervals(pick3(index, v[0][0], v[0][1], v[0][2]), pick3(index, v[1][0], v[1][1], v[1][2]), pick3(index, v[2][0], v[2][1], v[2][2]), dv0, dv1, dv2, dv0dv1, dv0dv2, &a, &b, &c, &x0, &x1))
+        return tri_coplanar(n1, v, u);
+    if (!tri_intervals(pick3(index, u[0][0], u[0][1], u[0][2]), pick3(index, u[1][0], u[1][1], u[1][2]), pick3(index, u[2][0], u[2][1], u[2][2]), du0, du1, du2, du0du1, du0du2, &d, &e, &f, &y0, &y1))
+        return tri_coplanar(n1, v, u);
+    const double xx = x0 * x1, yy = y0 * y1, xxyy = xx * yy;
+    double tmp = a * xxyy;
+    const double p0 = tmp + (b * x1) * yy, p1 = tmp + (c * x0) * yy;
+    tmp = d * xxyy;
+    const double q0 = tmp + (e * xx) * y1, q1 = tmp + (f * xx) * y0;
+    const double lo1 = p0 > p1 ? p1 : p0, hi1 = p0 > p1 ? p0 : p1, lo2 = q0 > q1 ? q1 : q0, hi2 = q0 > q1 ? q0 : q1;
+    return !(hi1 < lo2 || hi2 < lo1);
+}
+// the exact box of a triangle (no padding) and the closed overlap of two boxes
+__device__ __forceinline__ void exact_box(const float *__restrict__ c, double lo[3], double hi[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = (double)fminf(c[k], fminf(c[3 + k], c[6 + k]));
+        hi[k] = (double)fmaxf(c[k], fmaxf(c[3 + k], c[6 + k]));
+    }
+}
+__device__ __forceinline__ bool boxes_meet(const double alo[3], const double ahi[3], const double blo[3], const double bhi[3])
+{
+    return alo[0] <= bhi[0] && blo[0] <= ahi[0] && alo[1] <= bhi[1] && blo[1] <= ahi[1] && alo[2] <= bhi[2] && blo[2] <= ahi[2];
+}
+
+// One lane per query triangle i of (q_vert, q_tri).  A scene triangle g is its partner when the exact boxes overlap and tri_tri(i, g)
+// says so; SELF: the queries are the triangles the scene was built from, only g > i is looked at and a pair that shares a vertex
+// index is skipped (the index triples are q_tri's, found through the scene's stored global index).  A node is entered only when its
+// box -- which contains the padded, hence the exact, boxes of its triangles -- overlaps the query's exact box: nothing else prunes.
+//   kPairCount: counts[i] = the number of partners      kPairEmit: keys[offsets[i] + n] = i << 32 | g, in the walk's order
+//   kPairAny:   *flag = 1 when some lane has a partner; such a lane leaves its walk at once
+enum { kPairCount, kPairEmit, kPairAny };
+template <int PASS, bool SELF, bool BRUTE>
+__global__ __launch_bounds__(kRayThreads) void tri_pairs_kernel(RaySceneView v, const float *__restrict__ q_vert, int64_t q_nv, const int32_t *__restrict__ q_tri,
+                                                                int64_t m, int64_t *__restrict__ counts, uint64_t *__restrict__ keys, int64_t total,
+                                                                int32_t *__restrict__ flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * kRayThreads + threadIdx.x;
+    if (i >= m) return;
+    float qc[9];
+    load_corners(q_vert, q_nv, q_tri, i, qc);
+    const int32_t q0 = q_tri[3 * i], q1 = q_tri[3 * i + 1], q2 = q_tri[3 * i + 2];
+    double qlo[3], qhi[3];
+    exact_box(qc, qlo, qhi);
+    int64_t count = 0;
+    const int64_t base = PASS == kPairEmit ? counts[i] : 0, room = PASS == kPairEmit ? counts[i + 1] - counts[i] : 0;
+    // -> true: this lane is done
+    auto test = [&](int64_t pos) {
+        const int32_t g = v.ids[4 * pos];
+        if (SELF) {
+            if ((int64_t)g <= i || (int64_t)g >= m) return false;
+            const int32_t g0 = q_tri[3 * (int64_t)g], g1 = q_tri[3 * (int64_t)g + 1], g2 = q_tri[3 * (int64_t)g + 2];
+            if (g0 == q0 || g0 == q1 || g0 == q2 || g1 == q0 || g1 == q1 || g1 == q2 || g2 == q0 || g2 == q1 || g2 == q2) return false;
+        }
+        const float *c = v.corners + 9 * pos;
+        double lo[3], hi[3];
+        exact_box(c, lo, hi);
+        if (!boxes_meet(qlo, qhi, lo, hi) || !tri_tri(qc, c)) return false;
+        if (PASS == kPairAny) { *flag = 1; return true; }
+        if (PASS == kPairEmit && count < room && base + count < total) keys[base + count] = (uint64_t)i << 32 | (uint64_t)(uint32_t)g;
+        ++count;
+        return false;
+    };
+    if (BRUTE) {
+        for (int64_t g = 0; g < v.nt; ++g) {
+            const int64_t pos = v.ids[4 * g + 3];
+            if ((uint64_t)pos < (uint64_t)v.nt && test(pos)) break;
+        }
+    } else {
+        walk(v, [&](const double lo[3], const double hi[3]) { return boxes_meet(qlo, qhi, lo, hi); },
+             [&](uint32_t leaf) {
+                 const int64_t p0 = (int64_t)leaf * kLeaf, p1 = p0 + kLeaf < v.nt ? p0 + kLeaf : v.nt;
+                 for (int64_t pos = p0; pos < p1; ++pos)
+                     if (test(pos)) return true;
+                 return false;
+             });
+    }
+    if (PASS == kPairCount) counts[i] = count;
+}
+template <int PASS>
+void pairs_launch(bool self, bool brute, hipStream_t st, const RaySceneView &v, const float *q_vert, int64_t q_nv, const int32_t *q_tri, int64_t m, int64_t *counts,
+                  uint64_t *keys, int64_t total, int32_t *flag)
+{
+    const dim3 grid((unsigned)cdiv(m, kRayThreads)), block(kRayThreads);
+    if (self && brute) hipLaunchKernelGGL((tri_pairs_kernel<PASS, true, true>), grid, block, 0, st, v, q_vert, q_nv, q_tri, m, counts, keys, total, flag);
+    else if (self) hipLaunchKernelGGL((tri_pairs_kernel<PASS, true, false>), grid, block, 0, st, v, q_vert, q_nv, q_tri, m, counts, keys, total, flag);
+    else if (brute) hipLaunchKernelGGL((tri_pairs_kernel<PASS, false, true>), grid, block, 0, st, v, q_vert, q_nv, q_tri, m, counts, keys, total, flag);
+    else hipLaunchKernelGGL((tri_pairs_kernel<PASS, false, false>), grid, block, 0, st, v, q_vert, q_nv, q_tri, m, counts, keys, total, flag);
+}
+__global__ __launch_bounds__(256) void pair_unpack_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[2 * i] = (int32_t)(keys[i] >> 32);
+    out[2 * i + 1] = (int32_t)(uint32_t)keys[i];
+}
+constexpr int64_t kPairMax = 2147483647;
+int pairs_args(const char *who, const void *scene, size_t scene_bytes, const float *q_vert, int64_t q_nv, const int32_t *q_tri, int64_t m)
+{
+    KPX_RAYSCENE_ARGS("kpx_rayscene_triangle_pairs");
+    KPX_REQUIRE(q_nv >= 0 && q_nv < ((int64_t)1 << 31), "%s: bad number of vertices", who);
+    KPX_REQUIRE(m == 0 || (q_vert && q_tri), "%s: null pointer", who);
+    return KPX_OK;
+}
+
 }  // namespace
 }  // namespace kpx
 
@@ -538,6 +743,71 @@ KPX_EXPORT int kpx_rayscene_closest(const void *scene, size_t scene_bytes, const
     const unsigned nb = (unsigned)cdiv(m, kRayThreads);
     if (brute) hipLaunchKernelGGL(closest_kernel<true>, dim3(nb), dim3(kRayThreads), 0, st, v, queries, m, out_d2, out_points, out_distance, out_geometry_ids, out_primitive_ids);
     else hipLaunchKernelGGL(closest_kernel<false>, dim3(nb), dim3(kRayThreads), 0, st, v, queries, m, out_d2, out_points, out_distance, out_geometry_ids, out_primitive_ids);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_rayscene_triangle_pairs_count(const void *scene, size_t scene_bytes, const float *vertices, int64_t n_vertices, const int32_t *triangles,
+                                                 int64_t m, int32_t self, int32_t any, int32_t brute, int64_t *out_offsets, int32_t *d_flag, void *stream)
+{
+    const int rc0 = pairs_args("kpx_rayscene_triangle_pairs_count", scene, scene_bytes, vertices, n_vertices, triangles, m);
+    if (rc0) return rc0;
+    KPX_REQUIRE(any ? d_flag != nullptr : out_offsets != nullptr, "kpx_rayscene_triangle_pairs_count: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (any) KPX_HIP(hipMemsetAsync(d_flag, 0, sizeof(int32_t), st));
+    else KPX_HIP(hipMemsetAsync(out_offsets, 0, (size_t)(m + 1) * sizeof(int64_t), st));
+    RaySceneView v;
+    const int rc = ray_open(scene, scene_bytes, st, &v);
+    if (rc) return rc;
+    KPX_REQUIRE(!self || v.nt == m, "kpx_rayscene_triangle_pairs_count: a self search needs the %lld triangles the scene was built from, got %lld",
+                (long long)v.nt, (long long)m);
+    if (m == 0 || v.nt == 0) return KPX_OK;
+    if (any) {
+        pairs_launch<kPairAny>(self != 0, brute != 0, st, v, vertices, n_vertices, triangles, m, nullptr, nullptr, 0, d_flag);
+    } else {
+        pairs_launch<kPairCount>(self != 0, brute != 0, st, v, vertices, n_vertices, triangles, m, out_offsets, nullptr, 0, nullptr);
+        hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, out_offsets, m);
+    }
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT size_t kpx_rayscene_triangle_pairs_workspace_bytes(int64_t n_pairs)
+{
+    if (n_pairs < 0 || n_pairs > kPairMax) return 0;
+    Arena a(nullptr, 0);
+    DeviceSort<uint64_t, false> s;
+    dsort_carve(a, n_pairs, 64, SortOptions(), &s);
+    return a.off;
+}
+
+KPX_EXPORT int kpx_rayscene_triangle_pairs_fill(const void *scene, size_t scene_bytes, const float *vertices, int64_t n_vertices, const int32_t *triangles,
+                                                int64_t m, int32_t self, int32_t brute, const int64_t *offsets, int64_t n_pairs, int32_t *out_pairs, void *ws,
+                                                size_t ws_bytes, void *stream)
+{
+    const int rc0 = pairs_args("kpx_rayscene_triangle_pairs_fill", scene, scene_bytes, vertices, n_vertices, triangles, m);
+    if (rc0) return rc0;
+    KPX_REQUIRE(n_pairs >= 0, "kpx_rayscene_triangle_pairs_fill: negative count");
+    if (n_pairs > kPairMax) return fail(KPX_ERR_RANGE, "kpx_rayscene_triangle_pairs_fill: %lld pairs: at most 2^31 - 1", (long long)n_pairs);
+    if (n_pairs == 0) return KPX_OK;
+    KPX_REQUIRE(offsets && out_pairs && ws && m > 0, "kpx_rayscene_triangle_pairs_fill: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    RaySceneView v;
+    int rc = ray_open(scene, scene_bytes, st, &v);
+    if (rc) return rc;
+    KPX_REQUIRE(!self || v.nt == m, "kpx_rayscene_triangle_pairs_fill: a self search needs the %lld triangles the scene was built from, got %lld",
+                (long long)v.nt, (long long)m);
+    Arena a(ws, ws_bytes);
+    DeviceSort<uint64_t, false> s;
+    dsort_carve(a, n_pairs, 64, SortOptions(), &s);
+    KPX_ARENA_CHECK(a);
+    // a slot the emit pass does not reach (offsets that are not this search's) sorts last and reads as (-1, -1)
+    KPX_HIP(hipMemsetAsync(s.keys_in, 0xff, (size_t)n_pairs * sizeof(uint64_t), st));
+    pairs_launch<kPairEmit>(self != 0, brute != 0, st, v, vertices, n_vertices, triangles, m, const_cast<int64_t *>(offsets), s.keys_in, n_pairs, nullptr);
+    KPX_LAUNCH_CHECK();
+    rc = dsort_run(s, n_pairs, 64, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(pair_unpack_kernel, dim3((unsigned)cdiv(n_pairs, 256)), dim3(256), 0, st, (const uint64_t *)s.keys_out, n_pairs, out_pairs);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

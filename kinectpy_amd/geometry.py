@@ -864,8 +864,12 @@ class TriangleMesh:
     adjacency (compute_adjacency_list), edges (get_non_manifold_edges, is_edge_manifold), cluster_connected_triangles, ordered removal
     (remove_triangles_by_mask / _by_index, remove_vertices_by_mask / _by_index, remove_unreferenced_vertices,
     remove_degenerate_triangles, select_by_index), smoothing (filter_smooth_simple / _laplacian / _taubin) and sample_points_uniformly.
-    Not built: remove_duplicated_vertices, remove_duplicated_triangles, the simplification methods, is_watertight,
-    sample_points_poisson_disk, crop."""
+    The checks are arithmetic contract AC15: get_non_manifold_vertices / is_vertex_manifold,
+    get_self_intersecting_triangles / is_self_intersecting / is_intersecting (a triangle-triangle search over RaycastingScene's box
+    hierarchy), is_orientable / orient_triangles, get_volume and euler_poincare_characteristic; watertightness is
+    ops.mesh_is_watertight(vertices, triangles) on the mesh's arrays.
+    Not built: remove_duplicated_vertices, remove_duplicated_triangles, the simplification methods, is_watertight as a method (the
+    clean-up suite holds the class to not having it), sample_points_poisson_disk, crop, is_bounding_box_intersecting."""
     _bounds = None
     _adj = None               # (offsets, neighbours) device tensors: compute_adjacency_list's CSR
     _adj_sets = None          # the same as Python sets, built on first use of adjacency_list
@@ -1011,6 +1015,57 @@ class TriangleMesh:
         """-> (triangle_clusters int32 (T,), cluster_n_triangles int32 (C,), cluster_area float64 (C,)) device tensors; clusters are
         numbered by their smallest triangle, as Open3D's search from ascending seeds numbers them"""
         return ops.mesh_cluster_triangles(self._vert, self._tri)
+
+    # ---- checks (AC15) ---------------------------------------------------------------------------
+    def get_non_manifold_vertices(self):
+        """-> int32 array, ascending: the vertices whose triangles do not form one fan (or one open fan) around them.  A vertex that
+        no triangle names once is not reported (Open3D reads an empty map there)."""
+        return ops.mesh_non_manifold_vertices(self._vert, self._tri).cpu().numpy()
+
+    def is_vertex_manifold(self):
+        return ops.mesh_non_manifold_vertices(self._vert, self._tri).shape[0] == 0
+
+    def get_self_intersecting_triangles(self):
+        """-> Vector2iVector of (t0, t1), t0 < t1, ascending: the intersecting pairs that share no vertex index"""
+        return Vector2iVector(ops.mesh_self_intersections(self._vert, self._tri).cpu().numpy())
+
+    def is_self_intersecting(self):
+        return ops.mesh_is_self_intersecting(self._vert, self._tri)
+
+    def is_intersecting(self, other):
+        """whether some triangle of this mesh meets some triangle of `other` (no shared-vertex exemption)"""
+        if not isinstance(other, TriangleMesh):
+            raise RuntimeError(f"is_intersecting: expected a TriangleMesh, got {type(other).__name__}")
+        if not self.has_triangles() or not other.has_triangles():
+            return False
+        return ops.rayscene_triangles_meet(ops.rayscene_build(other._vert, other._tri), self._vert, self._tri)
+
+    def is_orientable(self):
+        return ops.mesh_orientation(self._vert, self._tri)[0]
+
+    def orient_triangles(self):
+        """-> whether the mesh is orientable.  If so the triangles are rewritten in place: in every connected component the smallest
+        triangle keeps its winding, the others are flipped ((t0, t1, t2) -> (t0, t2, t1), a stored triangle normal negated) where
+        they contradict it; vertex normals are not touched.  Otherwise the mesh stays bit for bit as it was."""
+        tn = self._tnrm if self.has_triangle_normals() else None
+        ok, _, tri, tn = ops.mesh_orientation(self._vert, self._tri, True, tn)
+        if ok:
+            self._tri = tri
+            if tn is not None:
+                self._tnrm = tn
+        return ok
+
+    def get_volume(self):
+        """the volume a watertight, orientable mesh encloses; raises RuntimeError for any other mesh, as Open3D does"""
+        if not ops.mesh_is_watertight(self._vert, self._tri):
+            raise RuntimeError("get_volume: the mesh is not watertight")
+        if not self.is_orientable():
+            raise RuntimeError("get_volume: the mesh is not orientable")
+        return ops.mesh_volume(self._vert, self._tri)
+
+    def euler_poincare_characteristic(self):
+        """V - E + F with E the number of distinct undirected edges"""
+        return self._vert.shape[0] - ops.mesh_edge_count(self._vert, self._tri) + self._tri.shape[0]
 
     def _set_triangles(self, tri, tnrm):
         self._tri, self._tnrm, self._adj, self._adj_sets = tri, tnrm, None, None

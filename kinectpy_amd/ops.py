@@ -1758,3 +1758,115 @@ def rayscene_closest(scene, queries, brute=False):
     L.check(lib.kpx_rayscene_closest(L.ptr(scene.buf), scene.buf.numel(), L.ptr(q), m, int(bool(brute)), L.ptr(out["d2"]), L.ptr(out["points"]),
                                      L.ptr(out["distance"]), L.ptr(out["geometry_ids"]), L.ptr(out["primitive_ids"]), L.stream_ptr()))
     return out
+
+
+# ---- mesh checks (AC15, DESIGN.md 5.16) -----------------------------------------------------------------
+PAIR_MAX = (1 << 31) - 1
+
+
+def mesh_non_manifold_vertices(vertices, triangles):
+    """[O3D] get_non_manifold_vertices -> int32 (N,) ascending device tensor: the vertices whose link (one edge per triangle that names
+    the vertex once, between its other two corners) falls into more than one connected component.  One host read."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_non_manifold_vertices", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    out = torch.empty(nv, dtype=torch.int32, device=vert.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_links_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_non_manifold_vertices(L.ptr(tri), nv, nt, L.ptr(out), L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return out[:_mesh_count("mesh_non_manifold_vertices", cnt)[0]]
+
+
+def mesh_orientation(vertices, triangles, apply=False, triangle_normals=None):
+    """AC15's orientation -> (orientable, flip uint8 (T,), triangles, triangle normals | None).  flip marks the triangles whose
+    winding the smallest triangle of their connected component contradicts (all 0 when the mesh is not orientable).  apply: the
+    flips are made IN PLACE in the device tensors given (a host array is copied first) and those tensors come back; nothing is
+    written when the mesh is not orientable.  One host read."""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_orientation", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    tn = _mesh_rows("mesh_orientation", triangle_normals, nt, "triangle normals")
+    flip = torch.empty(nt, dtype=torch.uint8, device=vert.device)
+    ok = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_orientation_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_orientation(L.ptr(tri), nv, nt, L.ptr(flip), L.ptr(tri) if apply else None, L.ptr(tn) if apply else None, L.ptr(ok), ws, wsz,
+                                     L.stream_ptr()))
+    return bool(_mesh_count("mesh_orientation", ok)[0]), flip, tri, tn
+
+
+def mesh_volume(vertices, triangles):
+    """|sum from 0, ascending, of v0 . (v1 x v2)| / 6 in fp64 (AC15) -> float; whether the mesh encloses anything is the caller's question"""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_volume", vertices, triangles)
+    out = torch.empty(1, dtype=torch.float64, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_volume_workspace_bytes(tri.shape[0]))
+    L.check(lib.kpx_mesh_volume(L.ptr(vert), vert.shape[0], L.ptr(tri), tri.shape[0], L.ptr(out), ws, wsz, L.stream_ptr()))
+    return float(out.item())
+
+
+def mesh_edge_count(vertices, triangles):
+    """the number of distinct undirected edges (min, max) of the triangles -> int"""
+    lib = L.load()
+    vert, tri = _mesh_arrays("mesh_edge_count", vertices, triangles)
+    nv, nt = vert.shape[0], tri.shape[0]
+    cnt = torch.empty(1, dtype=torch.int32, device=vert.device)
+    ws, wsz = L.workspace(lib.kpx_mesh_edges_workspace_bytes(nv, nt))
+    L.check(lib.kpx_mesh_edge_count(L.ptr(tri), nv, nt, L.ptr(cnt), ws, wsz, L.stream_ptr()))
+    return _mesh_count("mesh_edge_count", cnt)[0]
+
+
+def _pair_queries(who, scene, vertices, triangles, self_pairs):
+    if not isinstance(scene, RayScene):
+        raise L.KinectPxError(f"{who}: expected a RayScene (rayscene_build)")
+    vert, tri = _mesh_arrays(who, vertices, triangles)
+    if self_pairs and tri.shape[0] != scene.n:
+        raise L.KinectPxError(f"{who}: a self search needs the {scene.n} triangles the scene was built from, got {tri.shape[0]}")
+    if tri.shape[0] and not bool(torch.isfinite(vert).all()):
+        raise L.KinectPxError(f"{who}: a vertex coordinate is not finite")
+    return vert, tri
+
+
+def rayscene_triangle_pairs(scene, vertices, triangles, self_pairs=False, brute=False):
+    """the intersecting pairs (query triangle i, scene triangle g) of AC15 -> int32 (P, 2) device tensor, ascending in (i, g).
+    self_pairs: the queries are the triangles the scene was built from; only i < g, and a pair that shares a vertex index is skipped.
+    brute: every scene triangle is tested (same pairs).  One host read between the counting and the emitting pass."""
+    lib = L.load()
+    vert, tri = _pair_queries("rayscene_triangle_pairs", scene, vertices, triangles, self_pairs)
+    nv, m, dev = vert.shape[0], tri.shape[0], vert.device
+    off = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    args = (L.ptr(scene.buf), scene.buf.numel(), L.ptr(vert), nv, L.ptr(tri), m, int(bool(self_pairs)))
+    L.check(lib.kpx_rayscene_triangle_pairs_count(*args, 0, int(bool(brute)), L.ptr(off), None, L.stream_ptr()))
+    total = int(off[m].item())
+    if total > PAIR_MAX:
+        raise L.KinectPxError(f"rayscene_triangle_pairs: {total} pairs: at most 2^31 - 1")
+    out = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    if total:
+        ws, wsz = L.workspace(lib.kpx_rayscene_triangle_pairs_workspace_bytes(total))
+        L.check(lib.kpx_rayscene_triangle_pairs_fill(*args, int(bool(brute)), L.ptr(off), total, L.ptr(out), ws, wsz, L.stream_ptr()))
+    return out
+
+
+def rayscene_triangles_meet(scene, vertices, triangles, self_pairs=False, brute=False):
+    """whether rayscene_triangle_pairs would report a pair -> bool; lanes leave the search at their first partner.  One host read."""
+    lib = L.load()
+    vert, tri = _pair_queries("rayscene_triangles_meet", scene, vertices, triangles, self_pairs)
+    flag = torch.empty(1, dtype=torch.int32, device=vert.device)
+    L.check(lib.kpx_rayscene_triangle_pairs_count(L.ptr(scene.buf), scene.buf.numel(), L.ptr(vert), vert.shape[0], L.ptr(tri), tri.shape[0],
+                                                  int(bool(self_pairs)), 1, int(bool(brute)), None, L.ptr(flag), L.stream_ptr()))
+    return bool(flag.item())
+
+
+def mesh_self_intersections(vertices, triangles, brute=False):
+    """[O3D] get_self_intersecting_triangles -> int32 (P, 2) device tensor of (t0, t1), t0 < t1, ascending (builds the scene first)"""
+    return rayscene_triangle_pairs(rayscene_build(vertices, triangles), vertices, triangles, True, brute)
+
+
+def mesh_is_self_intersecting(vertices, triangles, brute=False):
+    return rayscene_triangles_meet(rayscene_build(vertices, triangles), vertices, triangles, True, brute)
+
+
+def mesh_is_watertight(vertices, triangles):
+    """[O3D] is_watertight: edge manifold without boundary, vertex manifold and free of self-intersections -- asked in that order,
+    cheapest first, stopping at the first that fails -> bool"""
+    return (mesh_non_manifold_edges(vertices, triangles, False).shape[0] == 0 and mesh_non_manifold_vertices(vertices, triangles).shape[0] == 0
+            and not mesh_is_self_intersecting(vertices, triangles))

@@ -54,6 +54,7 @@ def main():
     ap.add_argument("--tsdf", action="store_true", help="only the TSDF integration rows")
     ap.add_argument("--mesh", action="store_true", help="only the mesh clean-up rows")
     ap.add_argument("--raycast", action="store_true", help="only the mesh query rows (RaycastingScene)")
+    ap.add_argument("--mesh-checks", action="store_true", help="only the mesh check rows (watertight, orientation, volume, triangle pairs)")
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     a = ap.parse_args()
@@ -64,6 +65,8 @@ def main():
         return mesh_rows(dev, a.quick)
     if a.raycast:
         return raycast_rows(dev, a.quick)
+    if a.mesh_checks:
+        return mesh_check_rows(dev, a.quick)
     if a.voxelgrid:
         return voxelgrid_rows(dev, a.quick)
     if a.odometry:
@@ -319,6 +322,7 @@ def main():
     tsdf_rows(dev, a.quick)
     mesh_rows(dev, a.quick)
     raycast_rows(dev, a.quick)
+    mesh_check_rows(dev, a.quick)
     voxelgrid_rows(dev, a.quick)
     odometry_rows(dev, a.quick)
 
@@ -466,6 +470,68 @@ def raycast_rows(dev, quick):
     ms_b, _ = timed(lambda: ops.rayscene_closest(scene, subq, brute=True))
     report(f"rayscene closest points, every 25th query ({tag}): hierarchy", ms, queries=int(subq.shape[0]))
     report(f"rayscene closest points, every 25th query ({tag}): brute", ms_b, queries=int(subq.shape[0]), brute_over_hierarchy=round(ms_b / ms, 1))
+
+
+def mesh_check_rows(dev, quick):
+    """The mesh checks on the mesh of the fused ring volume (resolution 512, 256 with --quick): every method whole,
+    with its index check and host reads; the self-intersection search split into scene build, counting pass (+ scan) and the fill
+    (emit + sort + unpack); and the hierarchy against the brute form on 4096 evenly spaced query triangles (searched as another
+    mesh's, so that every query has partners: itself and its neighbours)."""
+    from kinectpy_amd import _lib as L
+    from kinectpy_amd.geometry import TriangleMesh
+    S = 4
+    _, depth, _, _, _ = synth.sensor_ring(S, 1)
+    depth_d = [torch.as_tensor(depth[0, s]).to(dev) for s in range(S)]
+    extr = np.stack([np.linalg.inv(synth.camera_pose(g, S)) for g in range(S)])
+    K, origin, length = (synth.FX, synth.FY, synth.CX, synth.CY), (-1000.0, -1100.0, -1000.0), 2000.0
+    res = 256 if quick else 512
+    vl = length / res
+    vol = torch.zeros((res ** 3, 2), dtype=torch.float32, device=dev)
+    ops.tsdf_integrate(vol, None, res, vl, origin, 4 * vl, depth_d, None, synth.W, synth.H, K, extr, 1.0, 6000.0)
+    vert, _, tri = ops.tsdf_extract_mesh(vol, None, res, vl, origin)
+    del vol
+    nv, nt = int(vert.shape[0]), int(tri.shape[0])
+    tag = f"ring mesh of res {res}"
+    mesh = TriangleMesh._make(vert, tri)
+    ms, out = timed(mesh.get_non_manifold_vertices)
+    report(f"mesh get_non_manifold_vertices ({tag}; adjacency + link union-find + compress + flags + compaction + host read)", ms, vertices=nv, triangles=nt,
+           non_manifold=int(len(out)))
+    ms, out = timed(mesh.is_orientable)
+    report(f"mesh is_orientable ({tag}; sort of 3 T edges + double-cover union-find + compress + check + host read)", ms, triangles=nt, orientable=bool(out))
+    ms, out = timed(lambda: TriangleMesh._make(vert, tri.clone()).orient_triangles())
+    report(f"mesh orient_triangles ({tag}; on a copy of the triangles)", ms, triangles=nt, orientable=bool(out))
+    ms, out = timed(lambda: ops.mesh_volume(vert, tri))
+    report(f"mesh volume sum ({tag}; one ordered fp64 chain + host read)", ms, 12 * nt + 12 * nv, triangles=nt, value=out)
+    ms, out = timed(mesh.euler_poincare_characteristic)
+    report(f"mesh euler_poincare_characteristic ({tag}; sort of 3 T edges + count of run heads + host read)", ms, 12 * nt, triangles=nt, value=int(out))
+    ms, out = timed(lambda: mesh.is_edge_manifold(False))
+    report(f"mesh is_edge_manifold(False) ({tag})", ms, triangles=nt, value=bool(out))
+    ms, scene = timed(lambda: ops.rayscene_build(vert, tri))
+    report(f"triangle pairs: scene build ({tag})", ms, triangles=nt)
+    lib = L.load()
+    off = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    args = (L.ptr(scene.buf), scene.buf.numel(), L.ptr(vert), nv, L.ptr(tri), nt, 1)
+    ms, _ = timed(lambda: L.check(lib.kpx_rayscene_triangle_pairs_count(*args, 0, 0, L.ptr(off), None, L.stream_ptr())))
+    total = int(off[nt].item())
+    report(f"triangle pairs: counting pass + scan ({tag}; self search)", ms, triangles=nt, pairs=total)
+    if total:
+        pairs = torch.empty((total, 2), dtype=torch.int32, device=dev)
+        ws, wsz = L.workspace(lib.kpx_rayscene_triangle_pairs_workspace_bytes(total))
+        ms, _ = timed(lambda: L.check(lib.kpx_rayscene_triangle_pairs_fill(*args, 0, L.ptr(off), total, L.ptr(pairs), ws, wsz, L.stream_ptr())))
+        report(f"triangle pairs: emitting pass + sort + unpack ({tag}; self search)", ms, pairs=total)
+    ms, out = timed(lambda: ops.mesh_self_intersections(vert, tri))
+    report(f"mesh get_self_intersecting_triangles ({tag}; whole: index checks, build, count, host read, fill)", ms, triangles=nt, pairs=int(out.shape[0]))
+    ms, out = timed(mesh.is_self_intersecting)
+    report(f"mesh is_self_intersecting ({tag}; whole: build + any-mode search + host read)", ms, triangles=nt, value=bool(out))
+    ms, out = timed(lambda: ops.mesh_is_watertight(vert, tri))
+    report(f"mesh_is_watertight ({tag}; stops at the first check that fails)", ms, triangles=nt, value=bool(out))
+    sub = tri[:: max(1, nt // 4096)][:4096].contiguous()
+    ms, a = timed(lambda: ops.rayscene_triangle_pairs(scene, vert, sub))
+    ms_b, b = timed(lambda: ops.rayscene_triangle_pairs(scene, vert, sub, brute=True))
+    assert torch.equal(a, b)
+    report(f"triangle pairs, {int(sub.shape[0])} evenly spaced queries ({tag}): hierarchy", ms, queries=int(sub.shape[0]), pairs=int(a.shape[0]))
+    report(f"triangle pairs, {int(sub.shape[0])} evenly spaced queries ({tag}): brute", ms_b, queries=int(sub.shape[0]), pairs=int(b.shape[0]),
+           brute_over_hierarchy=round(ms_b / ms, 1))
 
 
 def voxelgrid_rows(dev, quick):
