@@ -763,6 +763,53 @@ int kpx_tsdf_extract_count(const float *volume, int32_t resolution, int32_t mode
 int kpx_tsdf_extract_fill(const float *volume, const float *color, int32_t resolution, double voxel_length, const double *h_origin,
                           int32_t mode, int64_t total, float *pts, float *nrm, float *col, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- block-sparse integration ([O3D] pipelines.integration.ScalableTSDFVolume; arithmetic contract AC16) ------- */
+/* Blocks of R^3 voxels (R = unit_resolution in [1, KPX_TSDF_BLOCKS_MAX_RESOLUTION]) on the world lattice: block (bx, by, bz) spans
+ * [b ul, (b + 1) ul) per axis, ul = voxel_length R, voxel (x, y, z) of it at local index (x R + y) R + z, centre b ul + (index + 0.5)
+ * voxel_length.  All storage is the caller's: pool f32 [capacity][R^3][2] = {tsdf, weight}, color_pool f32 [capacity][R^3][3] or
+ * null, and the index: index_keys i64 [n_blocks] ascending, key = (bx + 2^20) << 42 | (by + 2^20) << 21 | (bz + 2^20), index_slots
+ * i32 [n_blocks] the pool slot of each.  Every call is asynchronous on `stream`.
+ * kpx_tsdf_blocks_touch: the blocks `count` (1..KPX_TSDF_MAX_SENSORS) images touch: of every stride-th pixel of every stride-th row
+ *     with depth > 0 (f32 images, or u16 with depth_scale / depth_trunc as kpx_tsdf_integrate) the world point h_poses[s] (x, y, z, 1)
+ *     (camera -> world, f64 row-major 4x4 each; fma chain as in AC1) and every block of the box floor((p -+ sdf_trunc) / ul).
+ *     0 < sdf_trunc <= unit_length.  d_counts i64 [3] = {touched blocks, touched blocks that are not in the index, 1 when a block index
+ *     left [-2^20, 2^20) -- KPX_ERR_RANGE for the caller to raise -- else 0}.  The workspace keeps the touched keys ascending, their
+ *     image masks and pool slots (a new block: n_blocks + its rank among the new ones) for the two calls below, which take the same
+ *     count / width / height / stride / unit_length / sdf_trunc.  ws: kpx_tsdf_blocks_touch_workspace_bytes (0 for a bad shape).
+ * kpx_tsdf_blocks_insert: out_keys / out_slots [n_blocks + n_new] = the index merged with the touch's n_new new keys (slots n_blocks,
+ *     n_blocks + 1, ... in ascending key order); zeroes those pool slots.  capacity >= n_blocks + n_new.
+ * kpx_tsdf_blocks_integrate: AC9's update of every voxel of the touch's n_touched blocks by the images of each block's mask, ascending;
+ *     h_extrinsics world -> camera as kpx_tsdf_integrate.  A block is read and written at most once.
+ * kpx_tsdf_blocks_extract_count / _fill, kpx_tsdf_blocks_mesh_count / _fill: as the uniform volume's four, over the voxels of the
+ *     existing blocks in ascending (key, local index); neighbours, interpolation taps and cube corners are taken by global voxel index
+ *     and may lie in adjacent blocks; an absent block gives no crossing, taps of 0 and inactive cubes.  There is no origin and no last-
+ *     layer exclusion.  ws: kpx_tsdf_blocks_extract_workspace_bytes(n_blocks, R, mesh), carried from count to fill. */
+#define KPX_TSDF_BLOCKS_MAX_RESOLUTION 32
+size_t kpx_tsdf_blocks_touch_workspace_bytes(int32_t count, int32_t width, int32_t height, int32_t stride, double unit_length, double sdf_trunc);
+int kpx_tsdf_blocks_touch(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, int32_t count, const void *const *h_depth,
+                          int32_t depth_u16, double depth_scale, double depth_trunc, int32_t width, int32_t height, const double *h_intrinsic,
+                          const double *h_poses, int32_t stride, double unit_length, double sdf_trunc, int64_t *d_counts, void *ws,
+                          size_t ws_bytes, void *stream);
+int kpx_tsdf_blocks_insert(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, int64_t n_new, int64_t *out_keys,
+                           int32_t *out_slots, float *pool, float *color_pool, int64_t capacity, int32_t unit_resolution, int32_t count,
+                           int32_t width, int32_t height, int32_t stride, double unit_length, double sdf_trunc, const void *ws, size_t ws_bytes,
+                           void *stream);
+int kpx_tsdf_blocks_integrate(float *pool, float *color_pool, int64_t capacity, int32_t unit_resolution, double voxel_length, double sdf_trunc,
+                              int64_t n_touched, int32_t count, const void *const *h_depth, int32_t depth_u16, double depth_scale,
+                              double depth_trunc, const uint8_t *const *h_rgb, int32_t width, int32_t height, const double *h_intrinsic,
+                              const double *h_extrinsics, int32_t stride, const void *ws, size_t ws_bytes, void *stream);
+size_t kpx_tsdf_blocks_extract_workspace_bytes(int64_t n_blocks, int32_t unit_resolution, int32_t mesh);
+int kpx_tsdf_blocks_extract_count(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, const float *pool,
+                                  int32_t unit_resolution, int32_t mode, int64_t *d_count, void *ws, size_t ws_bytes, void *stream);
+int kpx_tsdf_blocks_extract_fill(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, const float *pool,
+                                 const float *color_pool, int32_t unit_resolution, double voxel_length, int32_t mode, int64_t total, float *pts,
+                                 float *nrm, float *col, void *ws, size_t ws_bytes, void *stream);
+int kpx_tsdf_blocks_mesh_count(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, const float *pool,
+                               int32_t unit_resolution, int64_t *d_counts, void *ws, size_t ws_bytes, void *stream);
+int kpx_tsdf_blocks_mesh_fill(const int64_t *index_keys, const int32_t *index_slots, int64_t n_blocks, const float *pool,
+                              const float *color_pool, int32_t unit_resolution, double voxel_length, int64_t n_vertices, int64_t n_triangles,
+                              float *out_vertices, float *out_colors, int32_t *out_triangles, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- triangle meshes ([O3D] UniformTSDFVolume.extract_triangle_mesh, geometry.TriangleMesh; arithmetic contract AC12, DESIGN.md 3 /
  *      5.11) ------------------------------------------------------------------------------------------------------------------------ */
 /* kpx_tsdf_mesh_count / kpx_tsdf_mesh_fill: the two phases of marching cubes over a volume laid out as above.  A cube (x, y, z), every

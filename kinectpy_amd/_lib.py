@@ -166,6 +166,16 @@ SIGNATURES = {
     "kpx_tsdf_mesh_workspace_bytes": (_sz, [_i32]),
     "kpx_tsdf_mesh_count": (C.c_int, [_vp, _i32, _vp, _vp, _sz, _vp]),
     "kpx_tsdf_mesh_fill": (C.c_int, [_vp, _vp, _i32, _f64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_touch_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _f64, _f64]),
+    "kpx_tsdf_blocks_touch": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_insert": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_integrate": (C.c_int, [_vp, _vp, _i64, _i32, _f64, _f64, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _sz,
+                                            _vp]),
+    "kpx_tsdf_blocks_extract_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "kpx_tsdf_blocks_extract_count": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_extract_fill": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _f64, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_mesh_count": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "kpx_tsdf_blocks_mesh_fill": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _f64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_mesh_normals_workspace_bytes": (_sz, [_i64, _i64]),
     "kpx_mesh_normals": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_mesh_surface_area": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),

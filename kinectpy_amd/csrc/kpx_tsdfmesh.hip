@@ -10,46 +10,12 @@
 // The rank of edge (v, a) -- its vertex index -- is voff[chunk] + group.vrel + popcounts of the three ballots below v's lane + the
 // set bits of the lower axes at the lane: the order of extract_point_cloud, ascending (linear index, axis).
 #include "kpx_morton.h"
-#include "kpx_mctables.h"
+#include "kpx_mccore.h"
 
 #include <math.h>
 
 namespace kpx {
 namespace {
-
-// ---- tables ----------------------------------------------------------------------------------------------------------------
-struct McTables {
-    signed char tri[256][16];
-    unsigned char ntri[256];
-    signed char shift[12][4];       // edge -> (dx, dy, dz, axis) of its lower voxel
-};
-constexpr McTables mc_make_tables()
-{
-    McTables t{};
-    for (int c = 0; c < 256; ++c) {
-        int n = 0;
-        for (int i = 0; i < 16; ++i) {
-            t.tri[c][i] = kMcTriTable[c][i];
-            if (kMcTriTable[c][i] >= 0 && n == i) ++n;
-        }
-        t.ntri[c] = (unsigned char)(n / 3);
-    }
-    constexpr signed char sh[12][4] = { { 0, 0, 0, 0 }, { 1, 0, 0, 1 }, { 0, 1, 0, 0 }, { 0, 0, 0, 1 }, { 0, 0, 1, 0 }, { 1, 0, 1, 1 },
-                                        { 0, 1, 1, 0 }, { 0, 0, 1, 1 }, { 0, 0, 0, 2 }, { 1, 0, 0, 2 }, { 1, 1, 0, 2 }, { 0, 1, 0, 2 } };
-    for (int e = 0; e < 12; ++e)
-        for (int k = 0; k < 4; ++k) t.shift[e][k] = sh[e][k];
-    return t;
-}
-__constant__ McTables c_mc = mc_make_tables();
-
-// corner number of the cube corner at (dx, dy, dz): 0..3 run round the bottom face, 4..7 round the top
-__device__ __forceinline__ constexpr int mc_corner(int dx, int dy, int dz) { return dz * 4 + (dy ? 3 - dx : dx); }
-
-struct McGroup {
-    unsigned long long m[3];
-    uint32_t vrel, trel;
-};
-static_assert(sizeof(McGroup) == 32, "one group record is 32 bytes");
 
 constexpr int kMcChunk = KPX_TSDF_COUNT_BLOCK;        // consecutive voxels a wave counts and fills
 constexpr int kMcRounds = kMcChunk / 64;

@@ -1236,6 +1236,108 @@ def tsdf_extract_mesh(volume, color, resolution, voxel_length, origin):
     return vert, col, tri
 
 
+# ---- block-sparse volumetric integration (ScalableTSDFVolume, AC16) --------------------------------------
+def _ptr_array(ts, cnt):
+    return C.cast((C.c_void_p * max(cnt, 1))(*[t.data_ptr() for t in ts]), C.c_void_p) if ts is not None else None
+
+
+def tsdf_blocks_touch(index_keys, index_slots, depths, width, height, intrinsic, poses, stride, unit_length, sdf_trunc, depth_scale=1.0,
+                      depth_trunc=0.0):
+    """The blocks that len(depths) <= 8 images touch (kpx_tsdf_blocks_touch): depths as tsdf_integrate's, poses (S, 4, 4) camera ->
+    world.  -> (touched, new, ws): the two counts (the one host read of an integration) and the workspace that tsdf_blocks_insert
+    and tsdf_blocks_integrate continue from.  A block index outside [-2^20, 2^20) raises."""
+    lib = L.load()
+    cnt = len(depths)
+    dev = L.device()
+    size = lib.kpx_tsdf_blocks_touch_workspace_bytes(cnt, int(width), int(height), int(stride), float(unit_length), float(sdf_trunc))
+    if size == 0:
+        raise L.KinectPxError("tsdf_blocks_touch: 1 to 8 images of a positive size, stride >= 1 and 0 < sdf_trunc <= unit length")
+    if any(d.numel() != int(width) * int(height) for d in depths):
+        raise L.KinectPxError("tsdf_blocks_touch: image size does not match width x height")
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(cnt, 16))
+    K = np.ascontiguousarray(np.asarray(intrinsic, dtype=np.float64).reshape(4))
+    u16 = depths[0].dtype == torch.uint16
+    L.check(lib.kpx_tsdf_blocks_touch(L.ptr(index_keys), L.ptr(index_slots), 0 if index_keys is None else index_keys.numel(), cnt,
+                                      _ptr_array(depths, cnt), int(u16), float(depth_scale), float(depth_trunc), int(width), int(height), L.hptr(K),
+                                      L.hptr(P), int(stride), float(unit_length), float(sdf_trunc), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    touched, new, err = (int(c) for c in counts.tolist())
+    if err:
+        raise L.KinectPxError("tsdf_blocks_touch: a block index outside [-2^20, 2^20) (KPX_ERR_RANGE): the scene is too far from the origin for this unit length")
+    return touched, new, ws
+
+
+def tsdf_blocks_insert(index_keys, index_slots, n_new, pool, color_pool, unit_resolution, shape, ws):
+    """the index merged with the n_new new keys a touch left in ws -> (keys int64 (B + n_new,), slots int32); the new pool slots (B,
+    B + 1, ... in ascending key order) are zeroed.  shape = the touch's (count, width, height, stride, unit_length, sdf_trunc)."""
+    lib = L.load()
+    nb = 0 if index_keys is None else index_keys.numel()
+    keys = torch.empty(nb + n_new, dtype=torch.int64, device=pool.device)
+    slots = torch.empty(nb + n_new, dtype=torch.int32, device=pool.device)
+    cnt, width, height, stride, ul, trunc = shape
+    L.check(lib.kpx_tsdf_blocks_insert(L.ptr(index_keys), L.ptr(index_slots), nb, int(n_new), L.ptr(keys), L.ptr(slots), L.ptr(pool), L.ptr(color_pool),
+                                       pool.shape[0], int(unit_resolution), int(cnt), int(width), int(height), int(stride), float(ul), float(trunc),
+                                       L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return keys, slots
+
+
+def tsdf_blocks_integrate(pool, color_pool, unit_resolution, voxel_length, sdf_trunc, n_touched, depths, rgbs, width, height, intrinsic, extrinsics,
+                          stride, ws, depth_scale=1.0, depth_trunc=0.0):
+    """AC9's update of the n_touched blocks a touch left in ws, each by the images that touch it (kpx_tsdf_blocks_integrate), in place"""
+    lib = L.load()
+    cnt = len(depths)
+    u16 = depths[0].dtype == torch.uint16
+    if color_pool is not None and (rgbs is None or len(rgbs) != cnt or any(c.numel() != 3 * int(width) * int(height) for c in rgbs)):
+        raise L.KinectPxError("tsdf_blocks_integrate: a colour volume needs one width x height x 3 colour image per depth image")
+    E = np.ascontiguousarray(np.asarray(extrinsics, dtype=np.float64).reshape(cnt, 16))
+    K = np.ascontiguousarray(np.asarray(intrinsic, dtype=np.float64).reshape(4))
+    L.check(lib.kpx_tsdf_blocks_integrate(L.ptr(pool), L.ptr(color_pool), pool.shape[0], int(unit_resolution), float(voxel_length), float(sdf_trunc),
+                                          int(n_touched), cnt, _ptr_array(depths, cnt), int(u16), float(depth_scale), float(depth_trunc),
+                                          _ptr_array(rgbs if color_pool is not None else None, cnt), int(width), int(height), L.hptr(K), L.hptr(E),
+                                          int(stride), L.ptr(ws), ws.numel(), L.stream_ptr()))
+
+
+def tsdf_blocks_extract(index_keys, index_slots, pool, color_pool, unit_resolution, voxel_length, mode="surface"):
+    """extract_point_cloud / extract_voxel_point_cloud over the blocks of the index -> (points, normals | None, colours | None), ascending
+    in (block key, local voxel index, axis).  One host read between count and fill."""
+    lib = L.load()
+    m = TSDF_MODES[mode]
+    dev = pool.device
+    nb = 0 if index_keys is None else index_keys.numel()
+    ws = torch.empty(lib.kpx_tsdf_blocks_extract_workspace_bytes(nb, int(unit_resolution), 0), dtype=torch.uint8, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.kpx_tsdf_blocks_extract_count(L.ptr(index_keys), L.ptr(index_slots), nb, L.ptr(pool), int(unit_resolution), m, L.ptr(cnt), L.ptr(ws),
+                                              ws.numel(), L.stream_ptr()))
+    total = int(cnt.item())
+    pts = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((total, 3), dtype=torch.float32, device=dev) if m == 0 else None
+    col = torch.empty((total, 3), dtype=torch.float32, device=dev) if m == 1 or color_pool is not None else None
+    L.check(lib.kpx_tsdf_blocks_extract_fill(L.ptr(index_keys), L.ptr(index_slots), nb, L.ptr(pool), L.ptr(color_pool), int(unit_resolution),
+                                             float(voxel_length), m, total, L.ptr(pts), L.ptr(nrm), L.ptr(col), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return pts, nrm, col
+
+
+def tsdf_blocks_extract_mesh(index_keys, index_slots, pool, color_pool, unit_resolution, voxel_length):
+    """extract_triangle_mesh (AC12 by global voxel index, AC16) over the blocks of the index -> (vertices, colours | None, triangles)"""
+    lib = L.load()
+    dev = pool.device
+    nb = 0 if index_keys is None else index_keys.numel()
+    ws = torch.empty(lib.kpx_tsdf_blocks_extract_workspace_bytes(nb, int(unit_resolution), 1), dtype=torch.uint8, device=dev)
+    cnt = torch.empty(2, dtype=torch.int64, device=dev)
+    L.check(lib.kpx_tsdf_blocks_mesh_count(L.ptr(index_keys), L.ptr(index_slots), nb, L.ptr(pool), int(unit_resolution), L.ptr(cnt), L.ptr(ws),
+                                           ws.numel(), L.stream_ptr()))
+    nv, nt = (int(c) for c in cnt.tolist())
+    if nv > MESH_MAX or nt > MESH_MAX:
+        raise L.KinectPxError(f"tsdf_blocks_extract_mesh: {nv} vertices and {nt} triangles: a mesh holds fewer than 2^31 of each")
+    vert = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    col = torch.empty((nv, 3), dtype=torch.float32, device=dev) if color_pool is not None else None
+    tri = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    L.check(lib.kpx_tsdf_blocks_mesh_fill(L.ptr(index_keys), L.ptr(index_slots), nb, L.ptr(pool), L.ptr(color_pool), int(unit_resolution),
+                                          float(voxel_length), nv, nt, L.ptr(vert), L.ptr(col), L.ptr(tri), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return vert, col, tri
+
+
 def _mesh_arrays(who, vertices, triangles):
     """device float32 (V, 3) and int32 (T, 3); an index outside [0, V) raises here, before any kernel sees it"""
     vert = _dev(vertices, torch.float32).reshape(-1, 3)

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from ..geometry import RaycastingScene, VoxelGrid
-from ..integration import TSDFVolumeColorType, UniformTSDFVolume
+from ..integration import ScalableTSDFVolume, TSDFVolumeColorType, UniformTSDFVolume
 from ..utils import synth
 
 
@@ -18,7 +18,7 @@ class _Intrinsic:
 
 
 def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0, mesh=False,
-                    min_cluster_triangles=0, taubin_iterations=0):
+                    min_cluster_triangles=0, taubin_iterations=0, scalable=False, volume_unit_resolution=16, depth_sampling_stride=4):
     """depth: uint16 (S, H W) raw frames (synth.sensor_ring's layout; host or device); rgb: uint8 (S, H W, 3) or None (no colours);
     intrinsic: a PinholeCameraIntrinsic, or None for the Kinect's (synth.FX, FY, CX, CY at synth.W x synth.H); sensor_to_master:
     the S - 1 transforms of the sub sensors (sensor 0 is the master, identity).  The world frame is the master's: sensor s is
@@ -26,7 +26,9 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     call and one extraction -> PointCloud with normals (and colours when rgb is given); mesh=True: the surface as a TriangleMesh
     (extract_triangle_mesh) with vertex normals computed instead.  The mesh's clean-up, both off by default: min_cluster_triangles > 0
     drops every connected component of fewer triangles (the specks flying pixels leave) and then the vertices nothing names;
-    taubin_iterations > 0 smooths with filter_smooth_taubin's defaults before the normals are computed."""
+    taubin_iterations > 0 smooths with filter_smooth_taubin's defaults before the normals are computed.  scalable=True: a
+    ScalableTSDFVolume of voxel length `length / resolution` with volume_unit_resolution and depth_sampling_stride instead of the
+    uniform volume; `origin` is not used (the blocks sit on the world lattice); everything after the volume is the same."""
     if intrinsic is None:
         intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
     n = int(depth.shape[0])
@@ -35,7 +37,11 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     extr = [np.eye(4)] + [np.linalg.inv(np.asarray(T, dtype=np.float64).reshape(4, 4)) for T in sensor_to_master]
     if sdf_trunc is None:
         sdf_trunc = 4.0 * float(length) / int(resolution)
-    vol = UniformTSDFVolume(length, resolution, sdf_trunc, TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor, origin)
+    color_type = TSDFVolumeColorType.RGB8 if rgb is not None else TSDFVolumeColorType.NoColor
+    if scalable:
+        vol = ScalableTSDFVolume(float(length) / int(resolution), sdf_trunc, color_type, volume_unit_resolution, depth_sampling_stride)
+    else:
+        vol = UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin)
     vol.integrate_frames(depth, rgb, intrinsic, np.stack(extr), depth_scale, depth_trunc)
     if mesh:
         m = vol.extract_triangle_mesh()

@@ -375,6 +375,58 @@ def tsdf_rows(dev, quick):
                 ms, (vp, _, _) = timed(lambda: ops.tsdf_extract(vol, col, res, vl, origin, "voxels"))
                 report(f"tsdf extract_voxel_point_cloud ({tag})", ms, 8 * res ** 3 + int(vp.shape[0]) * 24, points=int(vp.shape[0]))
             del vol, col
+    tsdf_blocks_rows(dev, quick, depth[0], rgb[0], extr, K)
+
+
+def tsdf_blocks_rows(dev, quick, depth, rgb, extr, K):
+    """ScalableTSDFVolume on the same four frames next to the uniform rows above: R = 16, stride 4, the voxel length
+    of the uniform row of that resolution.  depth_trunc 2600 keeps the subject (what the uniform 2 m box holds), 6000 the whole room
+    (blocks over the walls too: where the block form loses its advantage).  "res 64" is the small case where the touch's sort and the
+    host read-backs cost more than a pass over the whole uniform volume.  Bytes: 8 (20 with colours) per voxel of the blocks held for an
+    integration (one read, one write), 8 per voxel for the clouds, 12 for the mesh -- of the blocks, not of a box."""
+    from kinectpy_amd.integration import ScalableTSDFVolume, TSDFVolumeColorType, UniformTSDFVolume
+    intr = type("Intrinsic", (), {"width": synth.W, "height": synth.H, "intrinsic_matrix": np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1.0]])})()
+    depths, colors = torch.as_tensor(np.ascontiguousarray(depth)).to(dev), torch.as_tensor(np.ascontiguousarray(rgb)).to(dev)
+    for res, trunc in ((64, 2600.0), (256, 2600.0)) + (() if quick else ((512, 2600.0), (512, 6000.0))):
+        vl = 2000.0 / res
+        for colour in (False, True):
+            ct = TSDFVolumeColorType.RGB8 if colour else TSDFVolumeColorType.NoColor
+            vol = ScalableTSDFVolume(vl, 4 * vl, ct, 16, 4)
+            run = lambda: vol.integrate_frames(depths, colors if colour else None, intr, extr, 1.0, trunc)
+            run()
+            blocks = vol.volume_unit_count()
+            nvox = blocks * 16 ** 3
+            held = nvox * (20 if colour else 8)
+            tag = f"vl 2000/{res}, R 16, stride 4, trunc {trunc:g}" + (", RGB8" if colour else "")
+
+            def fresh():
+                vol.reset()
+                run()
+            ms, _ = timed(fresh)
+            report(f"scalable integrate_frames into an empty volume ({tag}; touch + host read + insert + integrate)", ms, 2 * held, blocks=blocks, bytes_held=held)
+            ms, _ = timed(run)
+            report(f"scalable integrate_frames into existing blocks ({tag}; touch + host read + integrate)", ms, 2 * held, blocks=blocks, bytes_held=held)
+            vol.reset()
+            run()
+            ms, pc = timed(vol.extract_point_cloud)
+            report(f"scalable extract_point_cloud ({tag})", ms, 8 * nvox, points=int(pc._pts.shape[0]), blocks=blocks)
+            ms, m = timed(vol.extract_triangle_mesh)
+            report(f"scalable extract_triangle_mesh ({tag})", ms, 12 * nvox, vertices=int(m._vert.shape[0]), triangles=int(m._tri.shape[0]), blocks=blocks)
+            if not colour:
+                ms, vc = timed(vol.extract_voxel_point_cloud)
+                report(f"scalable extract_voxel_point_cloud ({tag})", ms, 8 * nvox, points=int(vc._pts.shape[0]), blocks=blocks)
+            del vol
+            if res == 64:                                   # the uniform volume of the same voxel length, which the rows above do not hold
+                uni = UniformTSDFVolume(2000.0, res, 4 * vl, ct, (-1000.0, -1100.0, -1000.0))
+                urun = lambda: uni.integrate_frames(depths, colors if colour else None, intr, extr, 1.0, 6000.0)
+                urun()
+                ms, _ = timed(urun)
+                report(f"uniform integrate_frames (res {res}" + (", RGB8)" if colour else ")"), ms, res ** 3 * (40 if colour else 16), voxels=res ** 3)
+                ms, pc = timed(uni.extract_point_cloud)
+                report(f"uniform extract_point_cloud (res {res}" + (", RGB8)" if colour else ")"), ms, 8 * res ** 3, points=int(pc._pts.shape[0]))
+                ms, m = timed(uni.extract_triangle_mesh)
+                report(f"uniform extract_triangle_mesh (res {res}" + (", RGB8)" if colour else ")"), ms, 12 * res ** 3, vertices=int(m._vert.shape[0]))
+                del uni
 
 
 def mesh_rows(dev, quick):
