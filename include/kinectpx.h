@@ -1088,6 +1088,40 @@ int kpx_odometry_iteration(const float *color_s, const float *depth_s, const flo
                            const double *h_intrinsic, const double *h_extrinsic, int32_t jacobian, double depth_diff_max, double *d_out, void *ws,
                            size_t ws_bytes, void *stream);
 
+/* ---- normal orientation (arithmetic contract AC17) ------------------------------------------------------------------
+ * pts, normals: f32 [n][3] on the device; the normals are rewritten in place.  All decision arithmetic is fp64 on the f32 values,
+ * every multiply and add rounded separately: dot(a, b) = (ax bx + ay by) + az bz, len = sqrt(dot(n, n)); a flip negates the three
+ * components.  n >= 2^31 is KPX_ERR_RANGE; null pointers, an unknown mode and k outside [0, KPX_ORIENT_MAX_K] are rejected before the
+ * device is touched; n = 0 does nothing.
+ * kpx_orient_normals (one streaming kernel, asynchronous), h_ref f64 [3] on the host:
+ *     KPX_ORIENT_NORMALIZE: len > 0: every component becomes (float)(c / len).  pts and h_ref are not read (may be NULL).
+ *     KPX_ORIENT_DIRECTION: len == 0: the normal becomes (float)h_ref; else flipped when dot(n, h_ref) < 0.  pts is not read.
+ *     KPX_ORIENT_CAMERA: r = h_ref - p; len == 0: the normal becomes (float)(r / |r|), (0, 0, 1) when |r| == 0; else flipped when
+ *         dot(n, r) < 0.
+ * kpx_emst: the Euclidean minimum spanning tree of the cloud: the unique minimum spanning tree of the complete graph whose pairs
+ *     {a < b} are ordered by (d2(a, b), a, b), d2 the squared distance of kpx_search_knn.  edges: i32 [n - 1][2], rows (a < b) ascending
+ *     in (a, b).  k is the width of the neighbour lists the Boruvka rounds work from: it changes the time, never the result.
+ * kpx_orient_normals_tangent: [O3D] OrientNormalsConsistentTangentPlane(k) with its ties pinned.  Graph: the tree of kpx_emst plus
+ *     {v, u} for every u != v among the first min(k, n) entries of v's kpx_search_knn row of the cloud queried with itself; weights
+ *     w(a, b) = 1 - |dot(n_a, n_b)| on the input normals; T = the unique minimum spanning tree under (w, a, b).  Root r = the lowest
+ *     index among the points of maximal z, flipped when n_r.z < 0; along every edge of T from parent a to child b, c = dot(n_a, n_b)
+ *     of the input normals: c == 0 leaves b as it came in, otherwise b is flipped when (a is flipped) != (c < 0).  flips (u8 [n], 1 =
+ *     negated) and tree (i32 [n - 1][2], T's rows (a < b) ascending in (a, b)) are optional (NULL).  Its EMST works from rows of
+ *     max(k, 30) entries whatever k is (the tree does not depend on that width, the time does); the graph takes the first min(k, n).
+ * h_stats (i64 [8] on the host, or NULL): [0] rounds of the EMST, [1] points that took the bounded exact search (summed over the
+ *     rounds), [2] the unbounded one, [3] rounds of T, [4] edges of T with c == 0 (more than none: the signs are walked on the host).
+ * kpx_emst and kpx_orient_normals_tangent read one word back per round: they return with the stream drained. */
+#define KPX_ORIENT_NORMALIZE 0
+#define KPX_ORIENT_DIRECTION 1
+#define KPX_ORIENT_CAMERA 2
+#define KPX_ORIENT_MAX_K 4096
+int kpx_orient_normals(const float *pts, float *normals, int64_t n, int32_t mode, const double *h_ref, void *stream);
+size_t kpx_emst_workspace_bytes(int64_t n, int32_t k);
+int kpx_emst(const float *pts, int64_t n, int32_t k, int32_t *edges, int64_t *h_stats, void *ws, size_t ws_bytes, void *stream);
+size_t kpx_orient_normals_tangent_workspace_bytes(int64_t n, int32_t k);
+int kpx_orient_normals_tangent(const float *pts, float *normals, int64_t n, int32_t k, uint8_t *flips, int32_t *tree, int64_t *h_stats, void *ws,
+                               size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,11 @@ SIGNATURES = {
     "kpx_rgbd_odometry": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _f64, _f64, _f64,
                                     _vp, _vp, _sz, _vp]),
     "kpx_odometry_iteration": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _sz, _vp]),
+    "kpx_orient_normals": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "kpx_emst_workspace_bytes": (_sz, [_i64, _i32]),
+    "kpx_emst": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_orient_normals_tangent_workspace_bytes": (_sz, [_i64, _i32]),
+    "kpx_orient_normals_tangent": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -9,44 +9,9 @@
 //   radius: count pass (grid_radius_scan, no cap), the library's own 64-bit scan, fill pass, then every segment sorted by
 //            (d2, index): a wave per segment in LDS up to kSegLds entries, one block per longer segment in place in global memory.
 // Squared distance (contract AC3): d2 = fma(dz,dz, fma(dy,dy, dx*dx)), d = q - p in fp64.  Rows ascend in (d2, index).
-#include "kpx_gridknn.h"
+#include "kpx_searchview.h"
 
 namespace kpx {
-
-constexpr unsigned long long kSearchMagic = 0x314843525358504bull;      // "KPXSRCH1"
-struct SearchHeader {
-    unsigned long long magic;
-    int64_t n;
-    unsigned long long bytes;      // kpx_search_index_bytes(n)
-    int32_t cell_cap, pad;
-    GridParams gp;
-};
-struct SearchLayout { size_t cell_start, pts, idx, bytes; };
-// the ceiling grid_build puts on the number of cells of an n-point cloud
-static inline int32_t search_cell_cap(int64_t n)
-{
-    int32_t cell_cap = 65536;
-    while (cell_cap < kGridMaxCells && (int64_t)cell_cap < 16 * n) cell_cap <<= 1;
-    return cell_cap;
-}
-static inline SearchLayout search_layout(int64_t n)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    SearchLayout l;
-    l.cell_start = up(sizeof(SearchHeader));
-    l.pts = l.cell_start + up(((size_t)search_cell_cap(n) + 1) * sizeof(uint32_t));
-    l.idx = l.pts + up(nn * 3 * sizeof(float));
-    l.bytes = l.idx + up(nn * sizeof(int32_t));
-    return l;
-}
-struct SearchView {
-    GridParams g;
-    const uint32_t *cell_start;
-    const float *spts;
-    const int32_t *sidx;
-    int64_t n;
-};
 
 // gp == NULL: the index of an empty cloud (one cell, no points)
 __global__ __launch_bounds__(256) void search_pack_kernel(char *__restrict__ index, SearchLayout l, int64_t n, int32_t cell_cap,
@@ -365,28 +330,6 @@ __global__ __launch_bounds__(1024) void search_sort_long_kernel(const int64_t *_
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-// The header comes back to the host (one small copy and a stream synchronisation per call): a buffer that is not an index, or is
-// shorter than the index it claims to be, must not reach a kernel that would walk it.
-static int search_open(const void *index, size_t index_bytes, hipStream_t st, SearchView *v)
-{
-    SearchHeader h;
-    KPX_HIP(hipMemcpyAsync(&h, index, sizeof(h), hipMemcpyDeviceToHost, st));
-    KPX_HIP(hipStreamSynchronize(st));
-    KPX_REQUIRE(h.magic == kSearchMagic && h.n >= 0 && h.n < ((int64_t)1 << 31), "kpx_search: the buffer holds no index (kpx_search_index_build)");
-    const SearchLayout l = search_layout(h.n);
-    KPX_REQUIRE(h.bytes == l.bytes && h.cell_cap == search_cell_cap(h.n) && h.gp.dim[0] >= 1 && h.gp.dim[1] >= 1 && h.gp.dim[2] >= 1 &&
-                    (int64_t)h.gp.dim[0] * h.gp.dim[1] * h.gp.dim[2] == (int64_t)h.gp.ncell && h.gp.ncell <= h.cell_cap && h.gp.h > 0.0,
-                "kpx_search: the buffer holds no index (kpx_search_index_build)");
-    KPX_REQUIRE(index_bytes >= l.bytes, "kpx_search: index_bytes %zu is smaller than the %zu bytes of an index of %lld points", index_bytes, l.bytes,
-                (long long)h.n);
-    const char *base = (const char *)index;
-    v->g = h.gp;
-    v->cell_start = reinterpret_cast<const uint32_t *>(base + l.cell_start);
-    v->spts = reinterpret_cast<const float *>(base + l.pts);
-    v->sidx = reinterpret_cast<const int32_t *>(base + l.idx);
-    v->n = h.n;
-    return KPX_OK;
-}
 #define KPX_SEARCH_INDEX_ARGS(who)                                                                                                          \
     KPX_REQUIRE(index, who ": null index");                                                                                                 \
     KPX_REQUIRE(index_bytes >= search_layout(0).bytes, who ": index_bytes %zu is smaller than the %zu bytes of an index of 0 points",       \

@@ -334,6 +334,45 @@ class PointCloud:
             self._nrm = ops.estimate_normals(self._pts, sp.radius, sp.max_nn)       # any max_nn up to KPX_NORMALS_MAX_NN (beyond 128 the fall-back heaps live in the workspace)
         return self
 
+    def _need_normals(self, who):
+        if not self.has_normals():
+            raise RuntimeError(f"{who}: the cloud has no normals (estimate_normals)")
+
+    def normalize_normals(self):
+        """[O3D] normalize_normals, in place -> self: every normal of positive length divided by it (AC17); a zero normal stays"""
+        if self.has_points():
+            self._need_normals("normalize_normals")
+            self._nrm = ops.orient_normals(self._nrm, "normalize")
+        return self
+
+    def orient_normals_to_align_with_direction(self, orientation_reference=(0.0, 0.0, 1.0)):
+        """[O3D] orient_normals_to_align_with_direction, in place -> self: a normal is flipped when its dot product with the reference
+        is negative; a zero normal becomes the reference (AC17)"""
+        if self.has_points():
+            self._need_normals("orient_normals_to_align_with_direction")
+            self._nrm = ops.orient_normals(self._nrm, "direction", orientation_reference)
+        return self
+
+    def orient_normals_towards_camera_location(self, camera_location=(0.0, 0.0, 0.0)):
+        """[O3D] orient_normals_towards_camera_location, in place -> self: a normal is flipped when it points away from the camera; a
+        zero normal becomes the unit vector towards it, (0, 0, 1) for a point at the camera (AC17)"""
+        if self.has_points():
+            self._need_normals("orient_normals_towards_camera_location")
+            self._nrm = ops.orient_normals(self._nrm, "camera", camera_location, self._pts)
+        return self
+
+    def orient_normals_consistent_tangent_plane(self, k, lambda_penalty=0.0, cos_alpha_tol=1.0):
+        """[O3D] orient_normals_consistent_tangent_plane(k), in place -> self: the signs are propagated from the topmost point along
+        the minimum spanning tree, under 1 - |n_a . n_b|, of the Riemannian graph (Euclidean minimum spanning tree plus the k nearest
+        neighbours), all on the device with every tie pinned (AC17).  Open3D's lambda_penalty / cos_alpha_tol
+        variant is not built: anything but their defaults raises NotImplementedError."""
+        if float(lambda_penalty) != 0.0 or float(cos_alpha_tol) != 1.0:
+            raise NotImplementedError("orient_normals_consistent_tangent_plane: lambda_penalty and cos_alpha_tol are not built (only their defaults)")
+        if self.has_points():
+            self._need_normals("orient_normals_consistent_tangent_plane")
+            self._nrm = ops.orient_normals_tangent(self._pts, self._nrm, k)[0]
+        return self
+
     def estimate_covariances(self, search_param=None):
         """[O3D] estimate_covariances: per point the covariance of its estimate_normals neighbourhood (None: KDTreeSearchParamKNN(30));
         fewer than 3 neighbours give the identity"""

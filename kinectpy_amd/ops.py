@@ -1972,3 +1972,77 @@ def mesh_is_watertight(vertices, triangles):
     cheapest first, stopping at the first that fails -> bool"""
     return (mesh_non_manifold_edges(vertices, triangles, False).shape[0] == 0 and mesh_non_manifold_vertices(vertices, triangles).shape[0] == 0
             and not mesh_is_self_intersecting(vertices, triangles))
+
+
+# ---- normal orientation and the Euclidean minimum spanning tree (arithmetic contract AC17, DESIGN.md 5.18) ----------------
+ORIENT_MODES = {"normalize": 0, "direction": 1, "camera": 2}          # KPX_ORIENT_* (include/kinectpx.h)
+ORIENT_MAX_K = 4096
+ORIENT_STATS = ("emst_rounds", "bounded_searches", "unbounded_searches", "tree_rounds", "zero_edges")
+
+
+def _orient_k(who, k):
+    k = int(k)
+    if not 0 <= k <= ORIENT_MAX_K:
+        raise L.KinectPxError(f"{who}: k must lie in [0, {ORIENT_MAX_K}]")
+    return k
+
+
+def _orient_stats(stats):
+    return {name: int(stats[i]) for i, name in enumerate(ORIENT_STATS)}
+
+
+def orient_normals(normals, mode, ref=None, pts=None):
+    """[O3D] normalize_normals / orient_normals_to_align_with_direction / orient_normals_towards_camera_location on a float32 (N,3)
+    device tensor, IN PLACE (a tensor of another dtype or device is converted first and the converted one is returned).  mode: a name
+    of ORIENT_MODES; ref: the direction or the camera location (3 floats, host); pts: the points, for "camera" only."""
+    lib = L.load()
+    if mode not in ORIENT_MODES:
+        raise ValueError(f"orient_normals: unknown mode {mode!r}: expected one of {sorted(ORIENT_MODES)}")
+    nrm = _dev(normals, torch.float32).reshape(-1, 3)
+    n = nrm.shape[0]
+    h_ref = None if ref is None else np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(3))
+    if mode != "normalize" and h_ref is None:
+        raise L.KinectPxError(f"orient_normals: mode {mode!r} needs a reference")
+    p = None
+    if mode == "camera":
+        if pts is None:
+            raise L.KinectPxError("orient_normals: mode 'camera' needs the points")
+        p = _dev(pts, torch.float32).reshape(-1, 3)
+        if p.shape[0] != n:
+            raise L.KinectPxError(f"orient_normals: {p.shape[0]} points for {n} normals")
+    L.check(lib.kpx_orient_normals(L.ptr(p), L.ptr(nrm), n, ORIENT_MODES[mode], None if h_ref is None else L.hptr(h_ref), L.stream_ptr()))
+    return nrm
+
+
+def emst(pts, k=30, want_stats=False):
+    """Exact Euclidean minimum spanning tree of a float32 (N,3) cloud: int32 (N-1, 2) device tensor of rows (a < b) ascending in
+    (a, b) -- the unique minimum spanning tree of the complete graph under (d2, a, b), d2 as search_knn's.  k: the width of the
+    neighbour lists the rounds work from; it changes the time, never the result (narrow lists, and components that
+    lie far apart, fall back on an exact search that scans all points).  want_stats: also a dict of ORIENT_STATS."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    n, k = pts.shape[0], _orient_k("emst", k)
+    edges = torch.empty((max(n - 1, 0), 2), dtype=torch.int32, device=pts.device)
+    stats = np.zeros(8, dtype=np.int64)
+    ws, wsz = L.workspace(lib.kpx_emst_workspace_bytes(n, k))
+    L.check(lib.kpx_emst(L.ptr(pts), n, k, L.ptr(edges), L.hptr(stats), ws, wsz, L.stream_ptr()))
+    return (edges, _orient_stats(stats)) if want_stats else edges
+
+
+def orient_normals_tangent(pts, normals, k, want_flips=False, want_tree=False, want_stats=False):
+    """[O3D] orient_normals_consistent_tangent_plane(k) with its ties pinned (AC17): flips the float32 (N,3) device tensor `normals`
+    IN PLACE (converted first when it is something else) -> (normals, flips uint8 (N) or None, tree int32 (N-1, 2) or None[, stats]):
+    flips[v] = 1 where the normal was negated; tree = the orientation tree's rows (a < b) ascending in (a, b)."""
+    lib = L.load()
+    pts = _dev(pts, torch.float32).reshape(-1, 3)
+    nrm = _dev(normals, torch.float32).reshape(-1, 3)
+    n, k = pts.shape[0], _orient_k("orient_normals_tangent", k)
+    if nrm.shape[0] != n:
+        raise L.KinectPxError(f"orient_normals_tangent: {n} points for {nrm.shape[0]} normals")
+    flips = torch.empty(n, dtype=torch.uint8, device=pts.device) if want_flips else None
+    tree = torch.empty((max(n - 1, 0), 2), dtype=torch.int32, device=pts.device) if want_tree else None
+    stats = np.zeros(8, dtype=np.int64)
+    ws, wsz = L.workspace(lib.kpx_orient_normals_tangent_workspace_bytes(n, k))
+    L.check(lib.kpx_orient_normals_tangent(L.ptr(pts), L.ptr(nrm), n, k, L.ptr(flips), L.ptr(tree), L.hptr(stats), ws, wsz, L.stream_ptr()))
+    out = (nrm, flips, tree)
+    return out + (_orient_stats(stats),) if want_stats else out

@@ -92,3 +92,19 @@ def render_mesh_depth(mesh, intrinsic, sensor_to_master, width=None, height=None
     scene.add_triangles(mesh)
     t = scene.cast_rays(rays)["t_hit"]
     return np.where(np.isfinite(t), t, np.float32(0.0)).astype(np.float32)
+
+
+def orient_normals_to_sensors(pcds, sensor_to_master):
+    """pcds: one PointCloud with normals per sensor, each already in the master's frame (sensor 0 is the master); sensor_to_master
+    as in fuse_depth_tsdf (the S - 1 transforms of the sub sensors; S transforms, the master's first, are accepted too).  Every
+    cloud's normals are oriented, in place, towards its own sensor's centre T[:3, 3] (orient_normals_towards_camera_location) --
+    before the clouds are fused and the sensor of origin is lost.  -> pcds"""
+    n = len(pcds)
+    Ts = [np.asarray(T, dtype=np.float64).reshape(4, 4) for T in sensor_to_master]
+    if len(Ts) == n - 1:
+        Ts = [np.eye(4)] + Ts
+    if len(Ts) != n:
+        raise RuntimeError(f"orient_normals_to_sensors: {n} sensors need {n - 1} sensor -> master transforms, got {len(sensor_to_master)}")
+    for pcd, T in zip(pcds, Ts):
+        pcd.orient_normals_towards_camera_location(T[:3, 3])
+    return pcds

@@ -57,6 +57,7 @@ def main():
     ap.add_argument("--mesh-checks", action="store_true", help="only the mesh check rows (watertight, orientation, volume, triangle pairs)")
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
+    ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.tsdf:
@@ -71,6 +72,8 @@ def main():
         return voxelgrid_rows(dev, a.quick)
     if a.odometry:
         return odometry_rows(dev, a.quick)
+    if a.orient:
+        return orient_rows(dev, a.quick)
     F = 64 if a.quick else 256
     xy = synth.xy_table()
     base_d, person = synth.render_depth(xy=xy, return_person=True)
@@ -648,6 +651,30 @@ def voxelgrid_rows(dev, quick):
     ms, (out, kept) = timed(lambda: remove_free_space_points(pc, depth[0], None, truth, 10.0))
     report("remove_free_space_points (fused ring cloud, 10 mm, 4 frames; grid + carve + inclusion + select, host frames uploaded)", ms, points=n,
            kept=int(kept.shape[0]))
+
+
+def orient_rows(dev, quick):
+    """orient_normals_consistent_tangent_plane and the EMST on the voxel-filtered frame cloud and on the same cloud beside a copy of
+    itself shifted well clear of it (components closed under their neighbour lists: the unbounded exact search), each beside
+    search_index + search_knn at the same n and k -- the like-for-like yardstick -- and the three streaming kernels"""
+    fc = ops.voxel_downsample(torch.as_tensor(synth.frame_cloud()).to(dev), 10.0)[0].contiguous()
+    bb = ops.bounds(fc).cpu().numpy()
+    shift = torch.tensor([3.0 * float(bb[3] - bb[0]), 0.0, 0.0], dtype=torch.float32, device=dev)
+    reps = 3 if quick else 10
+    for what, pts in (("the voxel-filtered (10 mm) frame cloud", fc),
+                      ("the voxel-filtered frame cloud + a copy shifted 3 box lengths", torch.cat([fc, fc + shift]).contiguous())):
+        n = int(pts.shape[0])
+        nrm = ops.estimate_normals(pts, 70.0, 40)
+        for k in (8, 30):
+            knn_ms, _ = timed(lambda: ops.search_knn(ops.search_index(pts), pts, k), reps=reps, warm=2)
+            report(f"search_index + search_knn k={k}, self-query on {what} (the yardstick)", knn_ms, n=n)
+            ms, (_, st) = timed(lambda: ops.emst(pts, k, want_stats=True), reps=reps, warm=2)
+            report(f"emst k={k} on {what}", ms, n=n, x_knn=round(ms / knn_ms, 2), **st)
+            ms, out = timed(lambda: ops.orient_normals_tangent(pts, nrm, k, want_stats=True), reps=reps, warm=2)
+            report(f"orient_normals_tangent k={k} on {what}", ms, n=n, x_knn=round(ms / knn_ms, 2), **out[3])
+        for mode in ("normalize", "direction", "camera"):
+            ms, _ = timed(lambda: ops.orient_normals(nrm, mode, (0.0, 0.0, 1.0), pts), reps=20, warm=2)
+            report(f"orient_normals {mode} on {what}", ms, n * (36 if mode == "camera" else 24), n=n)
 
 
 def odometry_launches(iterations):
