@@ -1122,6 +1122,37 @@ size_t kpx_orient_normals_tangent_workspace_bytes(int64_t n, int32_t k);
 int kpx_orient_normals_tangent(const float *pts, float *normals, int64_t n, int32_t k, uint8_t *flips, int32_t *tree, int64_t *h_stats, void *ws,
                                size_t ws_bytes, void *stream);
 
+/* ---- PointNet joint regression, inference (arithmetic contract AC18) ---------------------------------------------------
+ * models/pointnet.py create_pointnet(number_of_points, number_of_joints) with batch normalisation on its moving statistics (folded
+ * into the layer in front of it) and dropout as the identity; evaluate.py's metrics.
+ * The model is 20 layers (W f32 [c_in][c_out] row-major, b f32 [c_out]), y = x W + b, ReLU after every layer except the three marked *:
+ *    0..5   tnet(3):   3 -> 32, 32 -> 64, 64 -> 512, max over the points, 512 -> 256, 256 -> 128, 128 -> 9 *
+ *    6..7              3 -> 32, 32 -> 32                                        (applied to x T3,  T3[k][j] = t[3 k + j])
+ *    8..13  tnet(32):  32 -> 32, 32 -> 64, 64 -> 512, max, 512 -> 256, 256 -> 128, 128 -> 1024 *
+ *    14..19            32 -> 32, 32 -> 64, 64 -> 512, max, 512 -> 256, 256 -> 128, 128 -> 3 joints *      (applied to f T32)
+ * weights: the packed buffer, f32, 16-byte aligned: for layer 0, 1, ... its W then its b, each array starting at a multiple of 64
+ *     floats (gaps are not read).  W is stored [c_in][c_out] row-major, except for the three 64 -> 512 layers (2, 10, 16), which are
+ *     stored in the operand order of v_mfma_f32_32x32x2_f32: element ((c 8 + q) 64 + l) 4 + e = W[2 (4 q + e) + (l >> 5)][32 c + (l & 31)],
+ *     c < 16, q < 8, l < 64, e < 4.  weights_floats: the length of the buffer, checked against the layout for `joints`.
+ * pts: f32 [batch][n][3]; out: f32 [batch][3 joints].  Optional stage outputs (NULL = not wanted): T3 f32 [batch][9], T32 f32
+ *     [batch][1024], g1 / g2 / g3 f32 [batch][512] (the three maxima over the points).
+ * Arithmetic: f32 products and sums, fused multiply-adds, in an order that is fixed for a cloud whatever the batch around it; the maxima
+ *     are exact (integer atomicMax on the bit patterns of values >= +0), so a result does not depend on scheduling.  relu(x) = x > 0 ? x
+ *     : +0.  Non-finite coordinates give an unspecified result.
+ * joints >= 1 and 3 joints <= KPX_POINTNET_MAX_OUT; n = 0 is rejected; batch n >= 2^31 is KPX_ERR_RANGE; batch = 0 does nothing.  All
+ *     arguments are checked before the device is touched.  Six launches and the clears of the maxima, asynchronous, no host read-back.
+ * kpx_joint_metrics: over the n = batch 3 joints values of y_true, y_pred (f32): d_counts[t] (i64, device) = the number of
+ *     |(float)(pred - true)| <= (float)h_thresholds[t] (metrics/metric.py's float32 comparison; h_thresholds f64 on the host,
+ *     n_thresholds <= KPX_METRICS_MAX_THRESHOLDS), d_sum_sq (f64, device) = the sum of the squared f32 differences, each squared and
+ *     added in fp64 in a fixed order.  Asynchronous. */
+#define KPX_POINTNET_MAX_OUT 1024
+#define KPX_METRICS_MAX_THRESHOLDS 64
+size_t kpx_pointnet_workspace_bytes(int32_t batch, int64_t n, int32_t joints);
+int kpx_pointnet_forward(const float *weights, int64_t weights_floats, const float *pts, int32_t batch, int64_t n, int32_t joints, float *out,
+                         float *T3, float *T32, float *g1, float *g2, float *g3, void *ws, size_t ws_bytes, void *stream);
+int kpx_joint_metrics(const float *y_true, const float *y_pred, int64_t n, const double *h_thresholds, int32_t n_thresholds, int64_t *d_counts,
+                      double *d_sum_sq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

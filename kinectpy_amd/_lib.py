@@ -228,6 +228,9 @@ SIGNATURES = {
     "kpx_emst": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "kpx_orient_normals_tangent_workspace_bytes": (_sz, [_i64, _i32]),
     "kpx_orient_normals_tangent": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_pointnet_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "kpx_pointnet_forward": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kpx_joint_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2046,3 +2046,123 @@ def orient_normals_tangent(pts, normals, k, want_flips=False, want_tree=False, w
     L.check(lib.kpx_orient_normals_tangent(L.ptr(pts), L.ptr(nrm), n, k, L.ptr(flips), L.ptr(tree), L.hptr(stats), ws, wsz, L.stream_ptr()))
     out = (nrm, flips, tree)
     return out + (_orient_stats(stats),) if want_stats else out
+
+
+# ---- PointNet joint regression, inference (AC18) -----------------------------------------------------------------------------
+POINTNET_MAX_OUT = 1024                  # KPX_POINTNET_MAX_OUT (include/kinectpx.h)
+METRICS_MAX_THRESHOLDS = 64              # KPX_METRICS_MAX_THRESHOLDS
+POINTNET_WEIGHT_ARRAYS = 108             # Keras model.get_weights() of create_pointnet
+# (c_in, c_out, has batch normalisation) of the 20 layers in network order; c_out None = 3 joints
+_PN_TNET = lambda f: [(f, 32, True), (32, 64, True), (64, 512, True), (512, 256, True), (256, 128, True), (128, f * f, False)]
+POINTNET_LAYERS = _PN_TNET(3) + [(3, 32, True), (32, 32, True)] + _PN_TNET(32) + [(32, 32, True), (32, 64, True), (64, 512, True), (512, 256, True),
+                                                                                   (256, 128, True), (128, None, False)]
+_PN_MFMA_LAYERS = (2, 10, 16)            # the 64 -> 512 layers, packed in the matrix instruction's operand order
+_PN_PAD = 64
+BN_EPSILON = 1e-3                        # Keras' BatchNormalization default
+
+
+def pointnet_layer_shapes(joints):
+    """(c_in, c_out, has_bn) of the 20 layers for `joints` joints"""
+    return [(ci, 3 * int(joints) if co is None else co, bn) for ci, co, bn in POINTNET_LAYERS]
+
+
+def pointnet_fold(weights):
+    """Keras model.get_weights() of create_pointnet (108 arrays: kernel, bias, gamma, beta, moving_mean, moving_variance per conv_bn /
+    dense_bn, kernel, bias per plain Dense) -> the model: 20 (W f32 (c_in, c_out), b f32 (c_out)) pairs with the batch normalisation
+    folded in float64: s = gamma / sqrt(var + 1e-3), W' = fl32(K s), b' = fl32((b - mean) s + beta)."""
+    weights = list(weights)
+    if len(weights) != POINTNET_WEIGHT_ARRAYS:
+        raise ValueError(f"pointnet_fold: expected {POINTNET_WEIGHT_ARRAYS} weight arrays, got {len(weights)}")
+    last = np.asarray(weights[-1])
+    if last.ndim != 1 or last.size % 3 or not 1 <= last.size // 3 or last.size > POINTNET_MAX_OUT:
+        raise ValueError(f"pointnet_fold: array {POINTNET_WEIGHT_ARRAYS - 1} (the output bias) has shape {last.shape}: expected (3 joints,) with 3 joints <= "
+                         f"{POINTNET_MAX_OUT}")
+    folded, i = [], 0
+    for ci, co, bn in pointnet_layer_shapes(last.size // 3):
+        k = np.asarray(weights[i], dtype=np.float64)
+        if k.shape not in ((ci, co), (1, ci, co)):
+            raise ValueError(f"pointnet_fold: array {i} (a kernel) has shape {k.shape}: expected {(ci, co)} or {(1, ci, co)}")
+        k = k.reshape(ci, co)
+        vecs = []
+        for q in range(1, 6 if bn else 2):
+            v = np.asarray(weights[i + q], dtype=np.float64)
+            if v.shape != (co,):
+                raise ValueError(f"pointnet_fold: array {i + q} has shape {v.shape}: expected {(co,)}")
+            vecs.append(v)
+        if bn:
+            b, gamma, beta, mean, var = vecs
+            s = gamma / np.sqrt(var + BN_EPSILON)
+            folded.append(((k * s).astype(np.float32), ((b - mean) * s + beta).astype(np.float32)))
+            i += 6
+        else:
+            folded.append((k.astype(np.float32), vecs[0].astype(np.float32)))
+            i += 2
+    return folded
+
+
+def _pn_joints_of(floats):
+    """joints from the length of a packed buffer (the layout is strictly increasing in joints)"""
+    pad = lambda v: -(-v // _PN_PAD) * _PN_PAD
+    base = sum(pad(ci * co) + pad(co) for ci, co, _ in POINTNET_LAYERS[:-1])
+    for j in range(1, POINTNET_MAX_OUT // 3 + 1):
+        if base + pad(128 * 3 * j) + pad(3 * j) == floats:
+            return j
+    raise ValueError(f"a buffer of {floats} floats is not a packed PointNet")
+
+
+def pointnet_pack(folded):
+    """the model of pointnet_fold -> the packed f32 device buffer kpx_pointnet_forward reads (layout: include/kinectpx.h)"""
+    folded = list(folded)
+    if len(folded) != len(POINTNET_LAYERS):
+        raise ValueError(f"pointnet_pack: expected {len(POINTNET_LAYERS)} (W, b) pairs, got {len(folded)}")
+    joints = np.asarray(folded[-1][1]).size // 3
+    parts = []
+    for l, ((ci, co, _), (W, b)) in enumerate(zip(pointnet_layer_shapes(joints), folded)):
+        W, b = np.asarray(W), np.asarray(b)
+        if W.shape != (ci, co) or b.shape != (co,) or W.dtype != np.float32 or b.dtype != np.float32:
+            raise ValueError(f"pointnet_pack: layer {l}: expected float32 W {(ci, co)} and b {(co,)}, got {W.dtype} {W.shape} and {b.dtype} {b.shape}")
+        if l in _PN_MFMA_LAYERS:
+            # [c][q][l][e] = W[2 (4 q + e) + (l >> 5)][32 c + (l & 31)]: W[k][j] -> axes (q, e, half, c, lane31)
+            W = W.reshape(8, 4, 2, 16, 32).transpose(3, 0, 2, 4, 1)
+        for a in (W, b):
+            flat = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            parts.append(np.concatenate([flat, np.zeros(-flat.size % _PN_PAD, np.float32)]))
+    return _dev(np.concatenate(parts), torch.float32)
+
+
+def pointnet_forward(packed, x, want_stages=False):
+    """create_pointnet's forward on x f32 (B, N, 3) with the packed model -> joints f32 (B, 3 J) on the device; want_stages: also a dict of
+    the stage outputs T3 (B, 3, 3), T32 (B, 32, 32), g1, g2, g3 (B, 512).  Six launches, asynchronous, no host read-back."""
+    lib = L.load()
+    if not (isinstance(packed, torch.Tensor) and packed.dtype == torch.float32):
+        raise ValueError("pointnet_forward: packed must be the float32 buffer of pointnet_pack")
+    joints = _pn_joints_of(int(packed.numel()))
+    x = _dev(x, torch.float32)
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError(f"pointnet_forward: x must be (B, N, 3), got {tuple(x.shape)}")
+    B, N = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((B, 3 * joints), dtype=torch.float32, device=x.device)
+    st = None
+    if want_stages:
+        new = lambda *s: torch.empty((B,) + s, dtype=torch.float32, device=x.device)
+        st = {"T3": new(3, 3), "T32": new(32, 32), "g1": new(512), "g2": new(512), "g3": new(512)}
+    ws, wsz = L.workspace(lib.kpx_pointnet_workspace_bytes(B, N, joints)) if B else (None, 0)
+    sp = [L.ptr(st[k]) if st else None for k in ("T3", "T32", "g1", "g2", "g3")]
+    L.check(lib.kpx_pointnet_forward(L.ptr(packed), int(packed.numel()), L.ptr(x), B, N, joints, L.ptr(out), *sp, ws, wsz, L.stream_ptr()))
+    return (out, st) if want_stages else out
+
+
+def joint_metrics(y_true, y_pred, thresholds):
+    """-> (counts i64 (T) device tensor: |fl32(pred - true)| <= fl32(thr) per threshold, sum of squared f32 differences f64 (1) device
+    tensor, number of values).  Asynchronous."""
+    lib = L.load()
+    yt, yp = _dev(y_true, torch.float32).reshape(-1), _dev(y_pred, torch.float32).reshape(-1)
+    if yt.numel() != yp.numel():
+        raise ValueError(f"joint_metrics: {yt.numel()} true values against {yp.numel()} predicted")
+    thr = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.float64).reshape(-1))
+    if thr.size > METRICS_MAX_THRESHOLDS:
+        raise ValueError(f"joint_metrics: at most {METRICS_MAX_THRESHOLDS} thresholds per call")
+    counts = torch.zeros(max(thr.size, 1), dtype=torch.int64, device=yt.device)
+    total = torch.zeros(1, dtype=torch.float64, device=yt.device)
+    L.check(lib.kpx_joint_metrics(L.ptr(yt), L.ptr(yp), int(yt.numel()), L.hptr(thr), int(thr.size), L.ptr(counts), L.ptr(total), L.stream_ptr()))
+    return counts[:thr.size], total, int(yt.numel())

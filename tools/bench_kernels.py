@@ -58,8 +58,11 @@ def main():
     ap.add_argument("--voxelgrid", action="store_true", help="only the occupancy grid rows")
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
+    ap.add_argument("--pointnet", action="store_true", help="only the PointNet forward rows (fused against eval-mode torch modules)")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    if a.pointnet:
+        return pointnet_rows(dev, a.quick)
     if a.tsdf:
         return tsdf_rows(dev, a.quick)
     if a.mesh:
@@ -757,6 +760,96 @@ def odometry_rows(dev, quick):
     report("compute_rgbd_odometry 4 calls of one pair (same session)", sms, ms_range=[round(slo, 4), round(shi, 4)], wall_ms=round(sw, 4),
            wall_ms_range=[round(swlo, 4), round(swhi, 4)], launches=4 * n_launch, single_over_batch=round(sms / bms, 3),
            single_over_batch_wall=round(sw / bw, 3))
+
+
+POINTNET_FLOP_PER_POINT = 219.7e3       # 2 x the multiply-adds of the three trunks as the fused kernels run them (the front recomputed twice)
+FP32_PEAK = 157.3                       # TFLOP/s, vector and matrix alike on gfx950
+
+
+def torch_pointnet(weights, dev):
+    """the same 108 arrays as eval-mode torch-ROCm modules: Conv1d(kernel 1) / Linear + BatchNorm1d(eps 1e-3) + ReLU, bmm for the T-nets"""
+    nn = torch.nn
+    it = iter(weights)
+
+    def block(conv, bn=True):
+        k = np.asarray(next(it))
+        k = k.reshape(k.shape[-2], k.shape[-1])
+        lin = nn.Conv1d(k.shape[0], k.shape[1], 1) if conv else nn.Linear(k.shape[0], k.shape[1])
+        lin.weight.data = torch.as_tensor(k.T.copy()).reshape(lin.weight.shape)
+        lin.bias.data = torch.as_tensor(np.asarray(next(it)))
+        if not bn:
+            return lin
+        norm = nn.BatchNorm1d(k.shape[1], eps=1e-3)
+        norm.weight.data, norm.bias.data = torch.as_tensor(np.asarray(next(it))), torch.as_tensor(np.asarray(next(it)))
+        norm.running_mean.data, norm.running_var.data = torch.as_tensor(np.asarray(next(it))), torch.as_tensor(np.asarray(next(it)))
+        return nn.Sequential(lin, norm, nn.ReLU())
+
+    class TNet(nn.Module):
+        def __init__(self, f):
+            super().__init__()
+            self.f = f
+            self.convs = nn.Sequential(block(True), block(True), block(True))
+            self.head = nn.Sequential(block(False), block(False), block(False, bn=False))
+
+        def forward(self, h):                                # h (B, f, N)
+            T = self.head(self.convs(h).amax(dim=2)).reshape(-1, self.f, self.f)
+            return torch.bmm(h.transpose(1, 2), T).transpose(1, 2)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.t3 = TNet(3)
+            self.front = nn.Sequential(block(True), block(True))
+            self.t32 = TNet(32)
+            self.trunk = nn.Sequential(block(True), block(True), block(True))
+            self.head = nn.Sequential(block(False), block(False), block(False, bn=False))
+
+        def forward(self, x):                                # x (B, N, 3)
+            h = self.t32(self.front(self.t3(x.transpose(1, 2))))
+            return self.head(self.trunk(h).amax(dim=2))
+
+    net = Net().to(dev).eval()
+    assert next(it, None) is None
+    return net
+
+
+def pointnet_rows(dev, quick):
+    """PointNet forward: the fused path against the same weights as eval-mode torch modules, same device, same process,
+    windows of `calls` forwards between two events, the two alternating window by window; median and range over the windows."""
+    from kinectpy_amd.models.pointnet import create_pointnet
+    from tests import pointnet_ref
+    windows, calls = (5, 20) if quick else (15, 50)
+    for B, N, J in ((16, 1024, 32), (32, 4096, 32)):
+        w = pointnet_ref.make_weights(J, 7)
+        m = create_pointnet(N, J)
+        m.set_weights(w)
+        net = torch_pointnet(w, dev)
+        x = torch.as_tensor(pointnet_ref.make_clouds(B, N, pointnet_ref.UNIT, 1)).to(dev)
+        packed = m.packed()
+        with torch.no_grad():
+            forms = {"fused": lambda: ops.pointnet_forward(packed, x), "torch": lambda: net(x)}
+            for fn in forms.values():
+                for _ in range(5):
+                    y = fn()
+            torch.cuda.synchronize()
+            ya, yb = forms["fused"](), forms["torch"]()
+            dev_rel = float((ya - yb).abs().max() / yb.abs().max())
+            ts = {k: [] for k in forms}
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(windows):
+                for name, fn in forms.items():
+                    e0.record()
+                    for _ in range(calls):
+                        y = fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts[name].append(e0.elapsed_time(e1) / calls)
+        floor = B * N * POINTNET_FLOP_PER_POINT / (FP32_PEAK * 1e12) * 1e3
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        for name in forms:
+            report(f"pointnet forward {name} (B, N, J) = ({B}, {N}, {J})", med[name], ms_range=[round(min(ts[name]), 4), round(max(ts[name]), 4)],
+                   windows=windows, calls_per_window=calls, fp32_floor_ms=round(floor, 4), TFLOPs_fp32=round(B * N * POINTNET_FLOP_PER_POINT / med[name] / 1e9, 2),
+                   torch_over_fused=round(med["torch"] / med["fused"], 3), fused_vs_torch_max_rel=dev_rel)
 
 
 if __name__ == "__main__":
