@@ -1,23 +1,14 @@
 // kpx_tsdf.hip -- uniform truncated-signed-distance volume ([O3D] pipelines.integration.UniformTSDFVolume; arithmetic contract AC9,
 // DESIGN.md 3 and 5.11): integration of depth images (one read-modify-write of the volume for up to KPX_TSDF_MAX_SENSORS images)
-// and the two point-cloud extractions (count per block of consecutive voxels -> 64-bit scan -> fill).
+// and the two point-cloud extractions (count per block of consecutive voxels -> 64-bit scan -> fill).  The extraction kernels are
+// kpx_tsdfcore.h's, over its UniformView; here are the integration kernel and the host side.
 //
 // Layout: voxel (x, y, z) lives at linear index (x res + y) res + z (z fastest); volume = float2 {tsdf, weight} per voxel, colours
-// = float[3] per voxel in a separate array.  res <= 1024, so a linear index is below 2^30: it is carried as int64 (byte offsets of
-// the 8 GiB volume and of the colour array need it) and split into (x, y, z) with 32-bit divisions.
+// = float[3] per voxel in a separate array.
 #include "kpx_tsdfcore.h"
 
 namespace kpx {
 namespace {
-
-__device__ __forceinline__ void tsdf_split(int64_t lin, int res, int &x, int &y, int &z)
-{
-    const uint32_t l = (uint32_t)lin, r = (uint32_t)res;
-    const uint32_t t = l / r;
-    z = (int)(l - t * r);
-    x = (int)(t / r);
-    y = (int)(t - (uint32_t)x * r);
-}
 
 // One thread owns two consecutive voxels (one 16-byte access); the last thread of an odd volume owns one.  The volume is read at the
 // first image that updates either voxel and written once after the last: a pair no image reaches costs no volume traffic at all.
@@ -31,7 +22,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float2 *__restrict_
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         int x, y, z;
-        tsdf_split(two || k == 0 ? lin0 + k : lin0, a.res, x, y, z);
+        tsdf_split((uint32_t)(two || k == 0 ? lin0 + k : lin0), (uint32_t)a.res, x, y, z);
         c[k][0] = a.org[0] + ((double)x + 0.5) * a.vl;
         c[k][1] = a.org[1] + ((double)y + 0.5) * a.vl;
         c[k][2] = a.org[2] + ((double)z + 0.5) * a.vl;
@@ -91,141 +82,6 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float2 *__restrict_
             cp[2] = make_float2(cc[1][1], cc[1][2]);
         } else {
             col[3 * lin0 + 2] = cc[0][2];
-        }
-    }
-}
-
-// ---- extraction ---------------------------------------------------------------------------------------------------------------
-constexpr int kChunk = KPX_TSDF_COUNT_BLOCK;       // consecutive voxels a wave counts and fills
-constexpr int kChunkRounds = kChunk / 64;
-constexpr int kExtractWaves = 4;
-
-// what voxel `lin` emits: KPX_TSDF_SURFACE: bit i = a zero crossing towards +e_i; KPX_TSDF_VOXELS: bit 0 = the voxel is valid.
-// *v0 = the voxel, nb[i] = the neighbour of a set bit i.
-__device__ __forceinline__ unsigned tsdf_emits(const float2 *__restrict__ vol, int res, int64_t lin, int mode, float2 *v0, float2 nb[3])
-{
-    *v0 = vol[lin];
-    if (!tsdf_valid(*v0)) return 0u;
-    if (mode == KPX_TSDF_VOXELS) return 1u;
-    int p[3];
-    tsdf_split(lin, res, p[0], p[1], p[2]);
-    const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
-    unsigned m = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        if (p[i] + 1 >= res - 1) continue;            // Open3D's bound: the last layer of every axis is never a neighbour
-        nb[i] = vol[lin + step[i]];
-        if (tsdf_valid(nb[i]) && (double)v0->x * (double)nb[i].x < 0.0) m |= 1u << i;
-    }
-    return m;
-}
-
-__global__ __launch_bounds__(kExtractWaves * 64) void tsdf_count_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, int mode, int64_t nchunks,
-                                                                        int64_t *__restrict__ counts)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
-    if (chunk >= nchunks) return;
-    int c = 0;
-    for (int r = 0; r < kChunkRounds; ++r) {
-        const int64_t lin = chunk * kChunk + r * 64 + lane_id();
-        float2 v0, nb[3];
-        if (lin < nvox) c += __builtin_popcount(tsdf_emits(vol, res, lin, mode, &v0, nb));
-    }
-    c = wave_sum(c);
-    if (lane_id() == 0) counts[chunk] = c;
-}
-
-// trilinear interpolation of the raw tsdf at q (volume coordinates, origin excluded); taps outside the volume are 0
-__device__ __forceinline__ double tsdf_at(const float2 *__restrict__ vol, int res, double vl, const double q[3])
-{
-    double r[3];
-    int i0[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double g = q[a] / vl - 0.5, fl = floor(g);
-        r[a] = g - fl;
-        i0[a] = (int)fl;
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int dx = t >> 2, dy = (t >> 1) & 1, dz = t & 1;
-        const double wx = dx ? r[0] : 1.0 - r[0], wy = dy ? r[1] : 1.0 - r[1], wz = dz ? r[2] : 1.0 - r[2];
-        const int x = i0[0] + dx, y = i0[1] + dy, z = i0[2] + dz;
-        float fv = 0.0f;
-        if (x >= 0 && x < res && y >= 0 && y < res && z >= 0 && z < res) fv = vol[((int64_t)x * res + y) * res + z].x;
-        acc = acc + wx * wy * wz * (double)fv;
-    }
-    return acc;
-}
-
-struct TsdfFillArgs {
-    double org[3], vl;
-    float *pts, *nrm, *ocol;
-    const float *col;
-    int64_t total;
-};
-
-__global__ __launch_bounds__(kExtractWaves * 64) void tsdf_fill_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, int mode, int64_t nchunks,
-                                                                       const int64_t *__restrict__ offsets, TsdfFillArgs a)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
-    if (chunk >= nchunks) return;
-    const int lane = lane_id();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int64_t pos = offsets[chunk];
-    if (offsets[chunk + 1] == pos) return;
-    for (int r = 0; r < kChunkRounds; ++r) {
-        const int64_t lin = chunk * kChunk + r * 64 + lane;
-        float2 v0, nb[3];
-        const unsigned m = lin < nvox ? tsdf_emits(vol, res, lin, mode, &v0, nb) : 0u;
-        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
-        if ((b0 | b1 | b2) == 0ull) continue;
-        int64_t dst = pos + __builtin_popcountll(b0 & below) + __builtin_popcountll(b1 & below) + __builtin_popcountll(b2 & below);
-        pos += __builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2);
-        if (m == 0u) continue;
-        int ix[3];
-        tsdf_split(lin, res, ix[0], ix[1], ix[2]);
-        const double p0[3] = { ((double)ix[0] + 0.5) * a.vl, ((double)ix[1] + 0.5) * a.vl, ((double)ix[2] + 0.5) * a.vl };
-        if (mode == KPX_TSDF_VOXELS) {
-            if (dst >= a.total) continue;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)(a.org[k] + p0[k]);
-            if (a.ocol) {
-                const float g = (float)(((double)v0.x + 1.0) * 0.5);
-                a.ocol[3 * dst] = g; a.ocol[3 * dst + 1] = g; a.ocol[3 * dst + 2] = g;
-            }
-            continue;
-        }
-        const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
-        for (int i = 0; i < 3; ++i) {
-            if (!((m >> i) & 1u)) continue;
-            if (dst >= a.total) break;
-            const double r0 = fabs((double)v0.x), r1 = fabs((double)nb[i].x);
-            double p[3] = { p0[0], p0[1], p0[2] };
-            p[i] = (p0[i] * r1 + (p0[i] + a.vl) * r0) / (r0 + r1);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)(p[k] + a.org[k]);
-            if (a.ocol && a.col) {
-                const float *c0 = a.col + 3 * lin, *c1 = a.col + 3 * (lin + step[i]);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) a.ocol[3 * dst + k] = (float)(((double)c0[k] * r1 + (double)c1[k] * r0) / (r0 + r1) / 255.0);
-            }
-            if (a.nrm) {
-                const double gap = 0.99 * a.vl;
-                double n[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double qp[3] = { p[0], p[1], p[2] }, qm[3] = { p[0], p[1], p[2] };
-                    qp[k] = p[k] + gap;
-                    qm[k] = p[k] - gap;
-                    n[k] = tsdf_at(vol, res, a.vl, qp) - tsdf_at(vol, res, a.vl, qm);
-                }
-                const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) a.nrm[3 * dst + k] = len == 0.0 ? 0.0f : (float)(n[k] / len);
-            }
-            ++dst;
         }
     }
 }
@@ -302,8 +158,8 @@ KPX_EXPORT int kpx_tsdf_extract_count(const float *volume, int32_t resolution, i
     int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
     KPX_ARENA_CHECK(a);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tsdf_count_kernel, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
-                       reinterpret_cast<const float2 *>(volume), resolution, tsdf_voxels(resolution), mode, nchunks, offsets);
+    hipLaunchKernelGGL(tsdf_count_kernel<UniformView>, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
+                       uniform_view(volume, nullptr, resolution, 0.0, nullptr), mode, nchunks, offsets);
     hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, offsets, nchunks);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_count, offsets + nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -322,13 +178,10 @@ KPX_EXPORT int kpx_tsdf_extract_fill(const float *volume, const float *color, in
     Arena a(ws, ws_bytes);
     const int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
     KPX_ARENA_CHECK(a);
-    TsdfFillArgs f;
-    for (int k = 0; k < 3; ++k) f.org[k] = h_origin[k];
-    f.vl = voxel_length;
-    f.pts = pts; f.nrm = mode == KPX_TSDF_SURFACE ? nrm : nullptr; f.ocol = col; f.col = color; f.total = total;
+    const TsdfFillArgs f = { pts, mode == KPX_TSDF_SURFACE ? nrm : nullptr, col, total };
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tsdf_fill_kernel, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
-                       reinterpret_cast<const float2 *>(volume), resolution, tsdf_voxels(resolution), mode, nchunks, offsets, f);
+    hipLaunchKernelGGL(tsdf_fill_kernel<UniformView>, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
+                       uniform_view(volume, color, resolution, voxel_length, h_origin), mode, nchunks, offsets, f);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -23,9 +23,6 @@ namespace {
 
 constexpr int kBias = 1 << 20;
 constexpr uint64_t kNoKey = ~0ull;                  // bit 63 set: sorts behind every key
-constexpr int kBlkChunk = KPX_TSDF_COUNT_BLOCK;     // consecutive keys / virtual voxels a wave counts and fills
-constexpr int kBlkRounds = kBlkChunk / 64;
-constexpr int kBlkWaves = 4;
 
 __device__ __forceinline__ uint64_t blk_pack(int bx, int by, int bz)
 {
@@ -119,15 +116,15 @@ __global__ __launch_bounds__(256) void blk_emit_kernel(TouchArgs a, int64_t np, 
             }
 }
 
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_heads_count_kernel(const uint64_t *__restrict__ sorted, int64_t n, int64_t nchunks,
-                                                                         const uint64_t *__restrict__ index, int32_t nblocks,
-                                                                         int64_t *__restrict__ hcount, int64_t *__restrict__ ncount)
+__global__ __launch_bounds__(kExtractWaves * 64) void blk_heads_count_kernel(const uint64_t *__restrict__ sorted, int64_t n, int64_t nchunks,
+                                                                             const uint64_t *__restrict__ index, int32_t nblocks,
+                                                                             int64_t *__restrict__ hcount, int64_t *__restrict__ ncount)
 {
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
     if (chunk >= nchunks) return;
     int h = 0, nw = 0;
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t i = chunk * kBlkChunk + r * 64 + lane_id();
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t i = chunk * kChunk + r * 64 + lane_id();
         if (i >= n) continue;
         const uint64_t key = sorted[i];
         if (key == kNoKey || (i > 0 && sorted[i - 1] == key)) continue;
@@ -143,20 +140,20 @@ __global__ __launch_bounds__(kBlkWaves * 64) void blk_heads_count_kernel(const u
 }
 
 // ukeys / tslot may be the sort's input arrays: nothing reads those after the sort.  tmask is cleared before the launch.
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_heads_fill_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ svals, int64_t n,
-                                                                        int64_t nchunks, const uint64_t *__restrict__ index,
-                                                                        const int32_t *__restrict__ islots, int32_t nblocks,
-                                                                        const int64_t *__restrict__ hoff, const int64_t *__restrict__ noff,
-                                                                        uint64_t *__restrict__ ukeys, int32_t *__restrict__ tslot,
-                                                                        uint32_t *__restrict__ tmask, uint64_t *__restrict__ newkeys)
+__global__ __launch_bounds__(kExtractWaves * 64) void blk_heads_fill_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ svals, int64_t n,
+                                                                            int64_t nchunks, const uint64_t *__restrict__ index,
+                                                                            const int32_t *__restrict__ islots, int32_t nblocks,
+                                                                            const int64_t *__restrict__ hoff, const int64_t *__restrict__ noff,
+                                                                            uint64_t *__restrict__ ukeys, int32_t *__restrict__ tslot,
+                                                                            uint32_t *__restrict__ tmask, uint64_t *__restrict__ newkeys)
 {
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
     if (chunk >= nchunks) return;
     const int lane = lane_id();
     const unsigned long long upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull, below = (1ull << lane) - 1ull;
     int64_t hpos = hoff[chunk], npos = noff[chunk];
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t i = chunk * kBlkChunk + r * 64 + lane;
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t i = chunk * kChunk + r * 64 + lane;
         uint64_t key = kNoKey;
         int32_t val = 0, found = -1;
         bool head = false, sub = false;
@@ -230,7 +227,7 @@ void touch_carve(Arena &a, const TouchShape &s, TouchScratch *t)
     t->nax = touch_nax(s);
     t->np = (int64_t)s.count * t->nw * t->nh;
     t->n = t->np * t->nax * t->nax * t->nax;
-    t->nchunks = cdiv(t->n, kBlkChunk);
+    t->nchunks = cdiv(t->n, kChunk);
     dsort_carve(a, t->n, 64, SortOptions(), &t->sort);
     t->hoff = a.get<int64_t>((size_t)t->nchunks + 1);
     t->noff = a.get<int64_t>((size_t)t->nchunks + 1);
@@ -354,14 +351,61 @@ __global__ __launch_bounds__(256) void blk_integrate_kernel(float2 *__restrict__
     }
 }
 
-// ---- the view of the blocks the extractions share --------------------------------------------------------------------------------
+// ---- the view of the blocks (kpx_tsdfcore.h) ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int blk_floordiv(int x, int r) { return x >= 0 ? x / r : -((-x + r - 1) / r); }
+
+// The sweeps run over the virtual linear index rank(block) R^3 + local.  Interpolation works in world coordinates; there is no
+// neighbour that the surface leaves out: a voxel in an absent block closes no crossing.
 struct BlkView {
     const uint64_t *keys;          // [B] ascending
     const int32_t *slots;          // [B] pool slot
     const int32_t *nbr;            // [B][27] rank of the block at (dx, dy, dz) in {-1, 0, 1}^3, -1 = absent
-    const float2 *pool;
-    const float *cpool;
+    const float2 *vol;             // the pool
+    const float *col;
+    double vl, ul;                 // the fills'
     int32_t B, R, R3;
+    struct Cell {
+        int32_t rank;
+        int l, p[3];               // the voxel in its block: l = (p[0] R + p[1]) R + p[2]
+        int b[3];                  // the block's index, once anchored
+    };
+    __device__ __forceinline__ int64_t size() const { return (int64_t)B * R3; }
+    __device__ __forceinline__ Cell split(int64_t vlin) const
+    {
+        Cell c;
+        c.rank = (int32_t)(vlin / R3);
+        c.l = (int)(vlin - (int64_t)c.rank * R3);
+        c.p[2] = c.l % R;                    // signed, as at()'s: the compiler then takes 1 / R once for all of them
+        c.p[0] = (c.l / R) / R;
+        c.p[1] = (c.l / R) % R;
+        return c;
+    }
+    // from l, not from p[]: the voxel's load then waits for the rank alone and not for the divisions by R
+    __device__ __forceinline__ int64_t self(const Cell &c) const { return (int64_t)slots[c.rank] * R3 + c.l; }
+    __device__ __forceinline__ int64_t at(const Cell &c, int ox, int oy, int oz, int64_t *virt) const
+    {
+        const int x = c.p[0] + ox, y = c.p[1] + oy, z = c.p[2] + oz;
+        const int dx = blk_floordiv(x, R), dy = blk_floordiv(y, R), dz = blk_floordiv(z, R);
+        int32_t nr = c.rank;
+        if (dx | dy | dz) {
+            if (dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1 && dz >= -1 && dz <= 1) {
+                nr = nbr[(int64_t)c.rank * 27 + (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)];
+            } else {                                  // R = 1: a normal's tap two blocks away
+                int b[3];
+                blk_unpack(keys[c.rank], b);
+                nr = blk_in_range(b[0] + dx, b[1] + dy, b[2] + dz) ? blk_find(keys, B, blk_pack(b[0] + dx, b[1] + dy, b[2] + dz)) : -1;
+            }
+            if (nr < 0) return -1;
+        }
+        const int local = ((x - dx * R) * R + (y - dy * R)) * R + (z - dz * R);
+        *virt = (int64_t)nr * R3 + local;
+        return (int64_t)slots[nr] * R3 + local;
+    }
+    __device__ __forceinline__ bool surface_neighbour(const Cell &, int) const { return true; }
+    __device__ __forceinline__ void anchor(Cell &c) const { blk_unpack(keys[c.rank], c.b); }
+    __device__ __forceinline__ double centre(const Cell &c, int k) const { return (double)c.b[k] * ul + ((double)c.p[k] + 0.5) * vl; }
+    __device__ __forceinline__ double world(double p, int) const { return p; }
+    __device__ __forceinline__ int tap0(const Cell &c, double fl, int k) const { return (int)(fl - (double)c.b[k] * (double)R); }
 };
 
 __global__ __launch_bounds__(256) void blk_neighbours_kernel(const uint64_t *__restrict__ keys, int32_t nblocks, int32_t *__restrict__ nbr)
@@ -376,185 +420,13 @@ __global__ __launch_bounds__(256) void blk_neighbours_kernel(const uint64_t *__r
     nbr[t] = k == 13 ? rank : blk_in_range(bx, by, bz) ? blk_find(keys, nblocks, blk_pack(bx, by, bz)) : -1;
 }
 
-__device__ __forceinline__ int blk_floordiv(int x, int r) { return x >= 0 ? x / r : -((-x + r - 1) / r); }
-
-// The voxel at (x, y, z) counted from block `rank`'s first voxel (any of them may leave [0, R)): its pool index, -1 when its block is
-// absent; *virt = its virtual linear index rank' R^3 + local.
-__device__ __forceinline__ int64_t blk_voxel(const BlkView &v, int32_t rank, int x, int y, int z, int64_t *virt)
-{
-    const int dx = blk_floordiv(x, v.R), dy = blk_floordiv(y, v.R), dz = blk_floordiv(z, v.R);
-    int32_t nr = rank;
-    if (dx | dy | dz) {
-        if (dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1 && dz >= -1 && dz <= 1) {
-            nr = v.nbr[(int64_t)rank * 27 + (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)];
-        } else {                                  // R = 1: a normal's tap two blocks away
-            int b[3];
-            blk_unpack(v.keys[rank], b);
-            nr = blk_in_range(b[0] + dx, b[1] + dy, b[2] + dz) ? blk_find(v.keys, v.B, blk_pack(b[0] + dx, b[1] + dy, b[2] + dz)) : -1;
-        }
-        if (nr < 0) return -1;
-    }
-    const int local = ((x - dx * v.R) * v.R + (y - dy * v.R)) * v.R + (z - dz * v.R);
-    *virt = (int64_t)nr * v.R3 + local;
-    return (int64_t)v.slots[nr] * v.R3 + local;
-}
-
-__device__ __forceinline__ void blk_split(const BlkView &v, int64_t vlin, int32_t &rank, int &x, int &y, int &z)
-{
-    rank = (int32_t)(vlin / v.R3);
-    const int l = (int)(vlin - (int64_t)rank * v.R3);
-    z = l % v.R;
-    x = (l / v.R) / v.R;
-    y = (l / v.R) % v.R;
-}
-
-// ---- point-cloud extraction ------------------------------------------------------------------------------------------------------
-// what virtual voxel `vlin` emits (as tsdf_emits of the uniform volume, the neighbour by global index); *self = its pool index,
-// nbi[i] = the pool index of the neighbour of a set bit i
-__device__ __forceinline__ unsigned blk_emits(const BlkView &v, int64_t vlin, int mode, int64_t *self, float2 *v0, float2 nb[3], int64_t nbi[3])
-{
-    int32_t rank;
-    int p[3];
-    blk_split(v, vlin, rank, p[0], p[1], p[2]);
-    *self = (int64_t)v.slots[rank] * v.R3 + (vlin - (int64_t)rank * v.R3);
-    *v0 = v.pool[*self];
-    if (!tsdf_valid(*v0)) return 0u;
-    if (mode == KPX_TSDF_VOXELS) return 1u;
-    unsigned m = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        int64_t virt;
-        nbi[i] = blk_voxel(v, rank, p[0] + (i == 0), p[1] + (i == 1), p[2] + (i == 2), &virt);
-        if (nbi[i] < 0) continue;
-        nb[i] = v.pool[nbi[i]];
-        if (tsdf_valid(nb[i]) && (double)v0->x * (double)nb[i].x < 0.0) m |= 1u << i;
-    }
-    return m;
-}
-
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_count_kernel(BlkView v, int64_t nvox, int mode, int64_t nchunks, int64_t *__restrict__ counts)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
-    if (chunk >= nchunks) return;
-    int c = 0;
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t vlin = chunk * kBlkChunk + r * 64 + lane_id();
-        int64_t self, nbi[3];
-        float2 v0, nb[3];
-        if (vlin < nvox) c += __builtin_popcount(blk_emits(v, vlin, mode, &self, &v0, nb, nbi));
-    }
-    c = wave_sum(c);
-    if (lane_id() == 0) counts[chunk] = c;
-}
-
-// trilinear interpolation of the stored tsdf at the world point q; taps by global voxel index, a tap in an absent block is 0.
-// (rank, b) = the block the taps are counted from
-__device__ __forceinline__ double blk_tsdf_at(const BlkView &v, int32_t rank, const int b[3], double vl, const double q[3])
-{
-    double r[3];
-    int i0[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double g = q[a] / vl - 0.5, fl = floor(g);
-        r[a] = g - fl;
-        i0[a] = (int)(fl - (double)b[a] * (double)v.R);
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int dx = t >> 2, dy = (t >> 1) & 1, dz = t & 1;
-        const double wx = dx ? r[0] : 1.0 - r[0], wy = dy ? r[1] : 1.0 - r[1], wz = dz ? r[2] : 1.0 - r[2];
-        int64_t virt;
-        const int64_t at = blk_voxel(v, rank, i0[0] + dx, i0[1] + dy, i0[2] + dz, &virt);
-        const float fv = at >= 0 ? v.pool[at].x : 0.0f;
-        acc = acc + wx * wy * wz * (double)fv;
-    }
-    return acc;
-}
-
-struct BlkFillArgs {
-    double vl, ul;
-    float *pts, *nrm, *ocol;
-    int64_t total;
-};
-
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_fill_kernel(BlkView v, int64_t nvox, int mode, int64_t nchunks, const int64_t *__restrict__ offsets,
-                                                                  BlkFillArgs a)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
-    if (chunk >= nchunks) return;
-    const int lane = lane_id();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int64_t pos = offsets[chunk];
-    if (offsets[chunk + 1] == pos) return;
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t vlin = chunk * kBlkChunk + r * 64 + lane;
-        int64_t self = 0, nbi[3] = { -1, -1, -1 };
-        float2 v0, nb[3];
-        const unsigned m = vlin < nvox ? blk_emits(v, vlin, mode, &self, &v0, nb, nbi) : 0u;
-        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
-        if ((b0 | b1 | b2) == 0ull) continue;
-        int64_t dst = pos + __builtin_popcountll(b0 & below) + __builtin_popcountll(b1 & below) + __builtin_popcountll(b2 & below);
-        pos += __builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2);
-        if (m == 0u) continue;
-        int32_t rank;
-        int ix[3], b[3];
-        blk_split(v, vlin, rank, ix[0], ix[1], ix[2]);
-        blk_unpack(v.keys[rank], b);
-        double p0[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p0[k] = (double)b[k] * a.ul + ((double)ix[k] + 0.5) * a.vl;
-        if (mode == KPX_TSDF_VOXELS) {
-            if (dst >= a.total) continue;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)p0[k];
-            if (a.ocol) {
-                const float g = (float)(((double)v0.x + 1.0) * 0.5);
-                a.ocol[3 * dst] = g; a.ocol[3 * dst + 1] = g; a.ocol[3 * dst + 2] = g;
-            }
-            continue;
-        }
-        for (int i = 0; i < 3; ++i) {
-            if (!((m >> i) & 1u)) continue;
-            if (dst >= a.total) break;
-            const double r0 = fabs((double)v0.x), r1 = fabs((double)nb[i].x);
-            double p[3] = { p0[0], p0[1], p0[2] };
-            p[i] = (p0[i] * r1 + (p0[i] + a.vl) * r0) / (r0 + r1);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.pts[3 * dst + k] = (float)p[k];
-            if (a.ocol && v.cpool) {
-                const float *c0 = v.cpool + 3 * self, *c1 = v.cpool + 3 * nbi[i];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) a.ocol[3 * dst + k] = (float)(((double)c0[k] * r1 + (double)c1[k] * r0) / (r0 + r1) / 255.0);
-            }
-            if (a.nrm) {
-                const double gap = 0.99 * a.vl;
-                double n[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double qp[3] = { p[0], p[1], p[2] }, qm[3] = { p[0], p[1], p[2] };
-                    qp[k] = p[k] + gap;
-                    qm[k] = p[k] - gap;
-                    n[k] = blk_tsdf_at(v, rank, b, a.vl, qp) - blk_tsdf_at(v, rank, b, a.vl, qm);
-                }
-                const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) a.nrm[3 * dst + k] = len == 0.0 ? 0.0f : (float)(n[k] / len);
-            }
-            ++dst;
-        }
-    }
-}
-
-// ---- marching cubes ----------------------------------------------------------------------------------------------------------------
-// sweep 1: the code of the cube whose corner 0 the virtual voxel is; a corner in an absent block or of weight 0 makes it inactive (0)
-__global__ __launch_bounds__(256) void blk_mc_code_kernel(BlkView v, int64_t nvox, uint8_t *__restrict__ codes)
+// marching cubes, sweep 1: a corner in an absent block makes the cube inactive.  Eight loads and little else; it keeps its own form
+// because the uniform one (kpx_tsdfmesh.hip) pairs its loads along z, which at() does not let the compiler see.
+__global__ __launch_bounds__(256) void blk_mc_code_kernel(BlkView v, uint8_t *__restrict__ codes)
 {
     const int64_t vlin = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (vlin >= nvox) return;
-    int32_t rank;
-    int x, y, z;
-    blk_split(v, vlin, rank, x, y, z);
+    if (vlin >= v.size()) return;
+    const BlkView::Cell c = v.split(vlin);
     unsigned code = 0u;
     bool active = true;
 #pragma unroll
@@ -564,71 +436,13 @@ __global__ __launch_bounds__(256) void blk_mc_code_kernel(BlkView v, int64_t nvo
 #pragma unroll
             for (int dz = 0; dz < 2; ++dz) {
                 int64_t virt;
-                const int64_t at = blk_voxel(v, rank, x + dx, y + dy, z + dz, &virt);
+                const int64_t at = v.at(c, dx, dy, dz, &virt);
                 if (at < 0) { active = false; continue; }
-                const float2 q = v.pool[at];
+                const float2 q = v.vol[at];
                 active = active && q.y != 0.0f;
                 if (q.x < 0.0f) code |= 1u << mc_corner(dx, dy, dz);
             }
     codes[vlin] = (uint8_t)(active ? code : 0u);
-}
-
-// bit a: edge (voxel, axis a) carries a vertex (as mc_edge_flags of the uniform volume; the cubes behind the voxel may sit in the
-// backward neighbour blocks, an absent block has no cubes)
-__device__ __forceinline__ unsigned blk_mc_edge_flags(const BlkView &v, const uint8_t *__restrict__ codes, int32_t rank, int x, int y, int z, unsigned *own)
-{
-    unsigned m = 0u;
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dz = 0; dz < 2; ++dz) {
-                if (dx + dy + dz == 3) continue;                     // that cube holds none of the voxel's three edges
-                int64_t virt = 0;
-                if (blk_voxel(v, rank, x - dx, y - dy, z - dz, &virt) < 0) continue;
-                const unsigned c = codes[virt];
-                if (dx + dy + dz == 0) *own = c;
-                const unsigned at = (c >> mc_corner(dx, dy, dz)) & 1u;
-                if (dx == 0 && (((c >> mc_corner(1, dy, dz)) & 1u) != at)) m |= 1u;
-                if (dy == 0 && (((c >> mc_corner(dx, 1, dz)) & 1u) != at)) m |= 2u;
-                if (dz == 0 && (((c >> mc_corner(dx, dy, 1)) & 1u) != at)) m |= 4u;
-            }
-    return m;
-}
-
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_mc_count_kernel(BlkView v, const uint8_t *__restrict__ codes, int64_t nvox, int64_t nchunks,
-                                                                      McGroup *__restrict__ groups, int64_t *__restrict__ vcount, int64_t *__restrict__ tcount)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
-    if (chunk >= nchunks) return;
-    const int lane = lane_id();
-    uint32_t vrun = 0u, trun = 0u;             // trun is lane 0's
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t g = chunk * kBlkRounds + r, vlin = g * 64 + lane;
-        if (g * 64 >= nvox) break;
-        unsigned m = 0u, own = 0u;
-        if (vlin < nvox) {
-            int32_t rank;
-            int x, y, z;
-            blk_split(v, vlin, rank, x, y, z);
-            m = blk_mc_edge_flags(v, codes, rank, x, y, z, &own);
-        }
-        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
-        const int nt = wave_sum((int)c_mc.ntri[own]);
-        if (lane == 0) {
-            McGroup G;
-            G.m[0] = b0; G.m[1] = b1; G.m[2] = b2;
-            G.vrel = vrun; G.trel = trun;
-            groups[g] = G;
-            trun += (uint32_t)nt;
-        }
-        vrun += (uint32_t)(__builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2));
-    }
-    if (lane == 0) {
-        vcount[chunk] = vrun;
-        tcount[chunk] = trun;
-    }
 }
 
 struct BlkMcFillArgs {
@@ -638,60 +452,47 @@ struct BlkMcFillArgs {
     int64_t nv, nt;
 };
 
-// vertex index of edge (virtual voxel vlin, axis a)
-__device__ __forceinline__ int64_t blk_mc_rank(const McGroup *__restrict__ groups, const int64_t *__restrict__ voff, int64_t vlin, int a)
+// marching cubes, sweep 3, the blocks' own form like the uniform volume's (kpx_tsdfmesh.hip): vertices and colours by rank,
+// triangles by the scanned triangle offsets
+__global__ __launch_bounds__(kExtractWaves * 64) void blk_mc_fill_kernel(BlkView v, const uint8_t *__restrict__ codes, int64_t nvox, int64_t nchunks,
+                                                                         const McGroup *__restrict__ groups, const int64_t *__restrict__ voff,
+                                                                         const int64_t *__restrict__ toff, BlkMcFillArgs a)
 {
-    const int64_t g = vlin >> 6;
-    const int l = (int)(vlin & 63);
-    const McGroup G = groups[g];
-    const unsigned long long below = (1ull << l) - 1ull;
-    int64_t r = voff[g / kBlkRounds] + G.vrel + __builtin_popcountll(G.m[0] & below) + __builtin_popcountll(G.m[1] & below) +
-                __builtin_popcountll(G.m[2] & below);
-    if (a >= 1) r += (int64_t)((G.m[0] >> l) & 1ull);
-    if (a == 2) r += (int64_t)((G.m[1] >> l) & 1ull);
-    return r;
-}
-
-__global__ __launch_bounds__(kBlkWaves * 64) void blk_mc_fill_kernel(BlkView v, const uint8_t *__restrict__ codes, int64_t nvox, int64_t nchunks,
-                                                                     const McGroup *__restrict__ groups, const int64_t *__restrict__ voff,
-                                                                     const int64_t *__restrict__ toff, BlkMcFillArgs a)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kBlkWaves + wave_id();
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
     if (chunk >= nchunks) return;
     const int lane = lane_id();
     const unsigned long long below = (1ull << lane) - 1ull;
     const int64_t vbase = voff[chunk], tbase = toff[chunk];
     if (voff[chunk + 1] == vbase && toff[chunk + 1] == tbase) return;
-    for (int r = 0; r < kBlkRounds; ++r) {
-        const int64_t g = chunk * kBlkRounds + r, vlin = g * 64 + lane;
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t g = chunk * kChunkRounds + r, vlin = g * 64 + lane;
         if (g * 64 >= nvox) break;
         const McGroup G = groups[g];
-        int32_t rank = 0;
-        int ix[3] = { 0, 0, 0 };
-        if (vlin < nvox) blk_split(v, vlin, rank, ix[0], ix[1], ix[2]);
+        BlkView::Cell c{};
+        if (vlin < nvox) c = v.split(vlin);
         // the vertices of this voxel's three edges
         const unsigned mine = vlin < nvox ? (unsigned)((G.m[0] >> lane) & 1ull) | (unsigned)((G.m[1] >> lane) & 1ull) << 1 | (unsigned)((G.m[2] >> lane) & 1ull) << 2 : 0u;
         if (mine) {
             int64_t dst = vbase + G.vrel + __builtin_popcountll(G.m[0] & below) + __builtin_popcountll(G.m[1] & below) + __builtin_popcountll(G.m[2] & below);
             int b[3];
-            blk_unpack(v.keys[rank], b);
-            const int64_t self = (int64_t)v.slots[rank] * v.R3 + (vlin - (int64_t)rank * v.R3);
-            const double f0 = fabs((double)v.pool[self].x);
+            blk_unpack(v.keys[c.rank], b);
+            const int64_t self = v.self(c);
+            const double f0 = fabs((double)v.vol[self].x);
             double p0[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p0[k] = (double)b[k] * a.ul + ((double)ix[k] + 0.5) * a.vl;
+            for (int k = 0; k < 3; ++k) p0[k] = (double)b[k] * a.ul + ((double)c.p[k] + 0.5) * a.vl;
             for (int i = 0; i < 3; ++i) {
                 if (!((mine >> i) & 1u)) continue;
                 int64_t virt;
-                const int64_t at = blk_voxel(v, rank, ix[0] + (i == 0), ix[1] + (i == 1), ix[2] + (i == 2), &virt);
+                const int64_t at = v.at(c, i == 0, i == 1, i == 2, &virt);
                 if (dst >= a.nv || at < 0) break;                      // never true for the ws the count pass left
-                const double f1 = fabs((double)v.pool[at].x);
+                const double f1 = fabs((double)v.vol[at].x);
                 double p[3] = { p0[0], p0[1], p0[2] };
                 p[i] = p[i] + (f0 * a.vl) / (f0 + f1);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) a.overt[3 * dst + k] = (float)p[k];
                 if (a.ocol) {
-                    const float *c0 = v.cpool + 3 * self, *c1 = v.cpool + 3 * at;
+                    const float *c0 = v.col + 3 * self, *c1 = v.col + 3 * at;
 #pragma unroll
                     for (int k = 0; k < 3; ++k) a.ocol[3 * dst + k] = (float)((f1 * ((double)c0[k] / 255.0) + f0 * ((double)c1[k] / 255.0)) / (f0 + f1));
                 }
@@ -711,7 +512,7 @@ __global__ __launch_bounds__(kBlkWaves * 64) void blk_mc_fill_kernel(BlkView v, 
                 const int e = c_mc.tri[code][3 * t + k];
                 const signed char *s = c_mc.shift[e];
                 int64_t virt = 0;
-                if (blk_voxel(v, rank, ix[0] + s[0], ix[1] + s[1], ix[2] + s[2], &virt) >= 0) idx[k] = (int32_t)blk_mc_rank(groups, voff, virt, s[3]);
+                if (v.at(c, s[0], s[1], s[2], &virt) >= 0) idx[k] = (int32_t)mc_rank(groups, voff, virt, s[3]);
             }
             a.otri[3 * tdst] = idx[0];
             a.otri[3 * tdst + 1] = idx[2];
@@ -735,7 +536,7 @@ struct ExtractScratch {
 void extract_carve(Arena &a, int64_t nblocks, int32_t r, bool mesh, ExtractScratch *s)
 {
     s->nvox = nblocks * blk_r3(r);
-    s->nchunks = cdiv(s->nvox, kBlkChunk);
+    s->nchunks = cdiv(s->nvox, kChunk);
     s->nbr = a.get<int32_t>((size_t)(nblocks > 0 ? nblocks : 1) * 27);
     s->offsets = nullptr; s->codes = nullptr; s->groups = nullptr; s->voff = nullptr; s->toff = nullptr;
     if (!mesh) {
@@ -743,19 +544,20 @@ void extract_carve(Arena &a, int64_t nblocks, int32_t r, bool mesh, ExtractScrat
         return;
     }
     s->codes = a.get<uint8_t>((size_t)(s->nvox > 0 ? s->nvox : 1));
-    s->groups = a.get<McGroup>((size_t)(s->nchunks > 0 ? s->nchunks : 1) * kBlkRounds);
+    s->groups = a.get<McGroup>((size_t)(s->nchunks > 0 ? s->nchunks : 1) * kChunkRounds);
     s->voff = a.get<int64_t>((size_t)s->nchunks + 1);
     s->toff = a.get<int64_t>((size_t)s->nchunks + 1);
 }
-inline BlkView blk_view(const int64_t *keys, const int32_t *slots, int64_t nblocks, const float *pool, const float *cpool, int32_t r, const int32_t *nbr)
+inline BlkView blk_view(const int64_t *keys, const int32_t *slots, int64_t nblocks, const float *pool, const float *cpool, int32_t r, double vl,
+                        const int32_t *nbr)
 {
     BlkView v;
     v.keys = reinterpret_cast<const uint64_t *>(keys); v.slots = slots; v.nbr = nbr;
-    v.pool = reinterpret_cast<const float2 *>(pool); v.cpool = cpool;
+    v.vol = reinterpret_cast<const float2 *>(pool); v.col = cpool;
+    v.vl = vl; v.ul = vl * (double)r;
     v.B = (int32_t)nblocks; v.R = r; v.R3 = (int32_t)blk_r3(r);
     return v;
 }
-constexpr int64_t kBlkMeshMax = 2147483647;        // int32 indices
 constexpr int64_t kBlkMaxBlocks = 1 << 22;          // 2^37 voxels at R = 32: every grid and 27 B stay below 2^31
 
 }  // namespace
@@ -806,11 +608,11 @@ KPX_EXPORT int kpx_tsdf_blocks_touch(const int64_t *index_keys, const int32_t *i
     const int rc = dsort_run(t.sort, t.n, 64, st);
     if (rc != KPX_OK) return rc;
     const uint64_t *index = reinterpret_cast<const uint64_t *>(index_keys);
-    const unsigned grid = (unsigned)cdiv(t.nchunks, kBlkWaves);
-    hipLaunchKernelGGL(blk_heads_count_kernel, dim3(grid), dim3(kBlkWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, t.n, t.nchunks, index,
+    const unsigned grid = (unsigned)cdiv(t.nchunks, kExtractWaves);
+    hipLaunchKernelGGL(blk_heads_count_kernel, dim3(grid), dim3(kExtractWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, t.n, t.nchunks, index,
                        (int32_t)n_blocks, t.hoff, t.noff);
     hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, t.hoff, t.noff, t.nchunks);
-    hipLaunchKernelGGL(blk_heads_fill_kernel, dim3(grid), dim3(kBlkWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, (const int32_t *)t.sort.vals_out, t.n,
+    hipLaunchKernelGGL(blk_heads_fill_kernel, dim3(grid), dim3(kExtractWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, (const int32_t *)t.sort.vals_out, t.n,
                        t.nchunks, index, index_slots, (int32_t)n_blocks, (const int64_t *)t.hoff, (const int64_t *)t.noff, t.ukeys, t.tslot, t.tmask, t.newkeys);
     hipLaunchKernelGGL(blk_touch_done_kernel, dim3(1), dim3(64), 0, st, (const int64_t *)t.hoff, (const int64_t *)t.noff, t.nchunks, (const int32_t *)t.err, d_counts);
     KPX_LAUNCH_CHECK();
@@ -925,9 +727,9 @@ KPX_EXPORT int kpx_tsdf_blocks_extract_count(const int64_t *index_keys, const in
         KPX_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
         return KPX_OK;
     }
-    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, nullptr, unit_resolution, s.nbr);
+    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, nullptr, unit_resolution, 0.0, s.nbr);
     hipLaunchKernelGGL(blk_neighbours_kernel, dim3((unsigned)cdiv(n_blocks * 27, 256)), dim3(256), 0, st, v.keys, v.B, s.nbr);
-    hipLaunchKernelGGL(blk_count_kernel, dim3((unsigned)cdiv(s.nchunks, kBlkWaves)), dim3(kBlkWaves * 64), 0, st, v, s.nvox, mode, s.nchunks, s.offsets);
+    hipLaunchKernelGGL(tsdf_count_kernel<BlkView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, mode, s.nchunks, s.offsets);
     hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, s.offsets, s.nchunks);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_count, s.offsets + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -947,12 +749,10 @@ KPX_EXPORT int kpx_tsdf_blocks_extract_fill(const int64_t *index_keys, const int
     ExtractScratch s;
     extract_carve(a, n_blocks, unit_resolution, false, &s);
     KPX_ARENA_CHECK(a);
-    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, color_pool, unit_resolution, s.nbr);
-    BlkFillArgs f;
-    f.vl = voxel_length; f.ul = voxel_length * (double)unit_resolution;
-    f.pts = pts; f.nrm = mode == KPX_TSDF_SURFACE ? nrm : nullptr; f.ocol = col; f.total = total;
+    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, color_pool, unit_resolution, voxel_length, s.nbr);
+    const TsdfFillArgs f = { pts, mode == KPX_TSDF_SURFACE ? nrm : nullptr, col, total };
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(blk_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kBlkWaves)), dim3(kBlkWaves * 64), 0, st, v, s.nvox, mode, s.nchunks,
+    hipLaunchKernelGGL(tsdf_fill_kernel<BlkView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, mode, s.nchunks,
                        (const int64_t *)s.offsets, f);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
@@ -972,10 +772,10 @@ KPX_EXPORT int kpx_tsdf_blocks_mesh_count(const int64_t *index_keys, const int32
         KPX_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
         return KPX_OK;
     }
-    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, nullptr, unit_resolution, s.nbr);
+    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, nullptr, unit_resolution, 0.0, s.nbr);
     hipLaunchKernelGGL(blk_neighbours_kernel, dim3((unsigned)cdiv(n_blocks * 27, 256)), dim3(256), 0, st, v.keys, v.B, s.nbr);
-    hipLaunchKernelGGL(blk_mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, v, s.nvox, s.codes);
-    hipLaunchKernelGGL(blk_mc_count_kernel, dim3((unsigned)cdiv(s.nchunks, kBlkWaves)), dim3(kBlkWaves * 64), 0, st, v, (const uint8_t *)s.codes, s.nvox, s.nchunks,
+    hipLaunchKernelGGL(blk_mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, v, s.codes);
+    hipLaunchKernelGGL(mc_count_kernel<BlkView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, (const uint8_t *)s.codes, s.nchunks,
                        s.groups, s.voff, s.toff);
     hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, s.voff, s.toff, s.nchunks);
     KPX_LAUNCH_CHECK();
@@ -990,7 +790,7 @@ KPX_EXPORT int kpx_tsdf_blocks_mesh_fill(const int64_t *index_keys, const int32_
 {
     KPX_BLK_COMMON("kpx_tsdf_blocks_mesh_fill");
     KPX_REQUIRE(voxel_length > 0.0 && n_vertices >= 0 && n_triangles >= 0, "kpx_tsdf_blocks_mesh_fill: bad voxel_length or counts");
-    if (n_vertices > kBlkMeshMax || n_triangles > kBlkMeshMax)
+    if (n_vertices > kMeshMax || n_triangles > kMeshMax)
         return fail(KPX_ERR_RANGE, "kpx_tsdf_blocks_mesh_fill: %lld vertices and %lld triangles: a mesh holds fewer than 2^31 of each", (long long)n_vertices,
                     (long long)n_triangles);
     if ((n_vertices == 0 && n_triangles == 0) || n_blocks == 0) return KPX_OK;
@@ -1001,13 +801,10 @@ KPX_EXPORT int kpx_tsdf_blocks_mesh_fill(const int64_t *index_keys, const int32_
     ExtractScratch s;
     extract_carve(a, n_blocks, unit_resolution, true, &s);
     KPX_ARENA_CHECK(a);
-    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, color_pool, unit_resolution, s.nbr);
-    BlkMcFillArgs f;
-    f.vl = voxel_length; f.ul = voxel_length * (double)unit_resolution;
-    f.overt = out_vertices; f.ocol = out_colors; f.otri = out_triangles;
-    f.nv = n_vertices; f.nt = n_triangles;
+    const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, color_pool, unit_resolution, voxel_length, s.nbr);
+    const BlkMcFillArgs f = { v.vl, v.ul, out_vertices, out_colors, out_triangles, n_vertices, n_triangles };
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(blk_mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kBlkWaves)), dim3(kBlkWaves * 64), 0, st, v, (const uint8_t *)s.codes, s.nvox, s.nchunks,
+    hipLaunchKernelGGL(blk_mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, (const uint8_t *)s.codes, s.nvox, s.nchunks,
                        (const McGroup *)s.groups, (const int64_t *)s.voff, (const int64_t *)s.toff, f);
     KPX_LAUNCH_CHECK();
     return KPX_OK;

@@ -1,5 +1,6 @@
 // kpx_tsdfmesh.hip -- marching cubes over a uniform TSDF volume ([O3D] UniformTSDFVolume.extract_triangle_mesh; arithmetic contract
-// AC12).  The operators on the extracted mesh are kpx_mesh.hip's.
+// AC12): the code and fill sweeps of the uniform volume and the host side; the count sweep is kpx_mccore.h's
+// over the UniformView.  The operators on the extracted mesh are kpx_mesh.hip's.
 //
 // Extraction keeps the shape of the point-cloud extraction of kpx_tsdf.hip: count, one host read, fill; no atomics, every output
 // slot has one owner.  Workspace, carried from count to fill:
@@ -9,34 +10,18 @@
 //   voff, toff  i64 [chunks+1] exclusive scans of the chunks' vertex and triangle counts
 // The rank of edge (v, a) -- its vertex index -- is voff[chunk] + group.vrel + popcounts of the three ballots below v's lane + the
 // set bits of the lower axes at the lane: the order of extract_point_cloud, ascending (linear index, axis).
-#include "kpx_morton.h"
 #include "kpx_mccore.h"
-
-#include <math.h>
 
 namespace kpx {
 namespace {
 
-constexpr int kMcChunk = KPX_TSDF_COUNT_BLOCK;        // consecutive voxels a wave counts and fills
-constexpr int kMcRounds = kMcChunk / 64;
-constexpr int kMcWaves = 4;
-
-__device__ __forceinline__ void mc_split(int64_t lin, int res, int &x, int &y, int &z)
-{
-    const uint32_t l = (uint32_t)lin, r = (uint32_t)res;
-    const uint32_t t = l / r;
-    z = (int)(l - t * r);
-    x = (int)(t / r);
-    y = (int)(t - (uint32_t)x * r);
-}
-
-// ---- sweep 1: one code byte per voxel ------------------------------------------------------------------------------------------
+// sweep 1, not over the view: one test for the whole cube, then eight loads at fixed strides that the compiler pairs along z
 __global__ __launch_bounds__(256) void mc_code_kernel(const float2 *__restrict__ vol, int res, int64_t nvox, uint8_t *__restrict__ codes)
 {
     const int64_t lin = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (lin >= nvox) return;
     int x, y, z;
-    mc_split(lin, res, x, y, z);
+    tsdf_split((uint32_t)lin, (uint32_t)res, x, y, z);
     unsigned code = 0u;
     if (x < res - 1 && y < res - 1 && z < res - 1) {
         const int64_t sx = (int64_t)res * res, sy = res;
@@ -56,64 +41,6 @@ __global__ __launch_bounds__(256) void mc_code_kernel(const float2 *__restrict__
     codes[lin] = (uint8_t)code;
 }
 
-// bit a: edge (voxel, axis a) carries a vertex: one of the up to four cubes round it has the edge's two corners on different sides
-// (an inactive or absent cube has code 0: no difference).  *own = the code of the cube whose corner 0 the voxel is.
-__device__ __forceinline__ unsigned mc_edge_flags(const uint8_t *__restrict__ codes, int res, int64_t lin, int x, int y, int z, unsigned *own)
-{
-    const int64_t sx = (int64_t)res * res, sy = res;
-    unsigned m = 0u;
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dz = 0; dz < 2; ++dz) {
-                if (dx + dy + dz == 3) continue;                     // that cube holds none of the voxel's three edges
-                if (x - dx < 0 || y - dy < 0 || z - dz < 0) continue;
-                const unsigned c = codes[lin - dx * sx - dy * sy - dz];
-                if (dx + dy + dz == 0) *own = c;
-                const unsigned at = (c >> mc_corner(dx, dy, dz)) & 1u;
-                if (dx == 0 && (((c >> mc_corner(1, dy, dz)) & 1u) != at)) m |= 1u;
-                if (dy == 0 && (((c >> mc_corner(dx, 1, dz)) & 1u) != at)) m |= 2u;
-                if (dz == 0 && (((c >> mc_corner(dx, dy, 1)) & 1u) != at)) m |= 4u;
-            }
-    return m;
-}
-
-// ---- sweep 2: the group records and the chunks' counts (reads the code bytes only) --------------------------------------------
-__global__ __launch_bounds__(kMcWaves * 64) void mc_count_kernel(const uint8_t *__restrict__ codes, int res, int64_t nvox, int64_t nchunks,
-                                                                 McGroup *__restrict__ groups, int64_t *__restrict__ vcount, int64_t *__restrict__ tcount)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kMcWaves + wave_id();
-    if (chunk >= nchunks) return;
-    const int lane = lane_id();
-    uint32_t vrun = 0u, trun = 0u;             // trun is lane 0's
-    for (int r = 0; r < kMcRounds; ++r) {
-        const int64_t g = chunk * kMcRounds + r, lin = g * 64 + lane;
-        if (g * 64 >= nvox) break;
-        unsigned m = 0u, own = 0u;
-        if (lin < nvox) {
-            int x, y, z;
-            mc_split(lin, res, x, y, z);
-            m = mc_edge_flags(codes, res, lin, x, y, z, &own);
-        }
-        const unsigned long long b0 = __ballot((m & 1u) != 0), b1 = __ballot((m & 2u) != 0), b2 = __ballot((m & 4u) != 0);
-        const int nt = wave_sum((int)c_mc.ntri[own]);
-        if (lane == 0) {
-            McGroup G;
-            G.m[0] = b0; G.m[1] = b1; G.m[2] = b2;
-            G.vrel = vrun; G.trel = trun;
-            groups[g] = G;
-            trun += (uint32_t)nt;
-        }
-        vrun += (uint32_t)(__builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2));
-    }
-    if (lane == 0) {
-        vcount[chunk] = vrun;
-        tcount[chunk] = trun;
-    }
-}
-
 struct McFillArgs {
     double org[3], vl;
     const float *col;
@@ -122,38 +49,24 @@ struct McFillArgs {
     int64_t nv, nt;
 };
 
-// vertex index of edge (voxel lin, axis a)
-__device__ __forceinline__ int64_t mc_rank(const McGroup *__restrict__ groups, const int64_t *__restrict__ voff, int64_t lin, int a)
+// sweep 3, not over the view (it measured slower there): vertices and colours by rank, triangles by the scanned triangle offsets
+__global__ __launch_bounds__(kExtractWaves * 64) void mc_fill_kernel(const float2 *__restrict__ vol, const uint8_t *__restrict__ codes, int res, int64_t nvox,
+                                                                     int64_t nchunks, const McGroup *__restrict__ groups, const int64_t *__restrict__ voff,
+                                                                     const int64_t *__restrict__ toff, McFillArgs a)
 {
-    const int64_t g = lin >> 6;
-    const int l = (int)(lin & 63);
-    const McGroup G = groups[g];
-    const unsigned long long below = (1ull << l) - 1ull;
-    int64_t r = voff[g / kMcRounds] + G.vrel + __builtin_popcountll(G.m[0] & below) + __builtin_popcountll(G.m[1] & below) +
-                __builtin_popcountll(G.m[2] & below);
-    if (a >= 1) r += (int64_t)((G.m[0] >> l) & 1ull);
-    if (a == 2) r += (int64_t)((G.m[1] >> l) & 1ull);
-    return r;
-}
-
-// ---- sweep 3: vertices and colours by rank, triangles by the scanned triangle offsets -----------------------------------------
-__global__ __launch_bounds__(kMcWaves * 64) void mc_fill_kernel(const float2 *__restrict__ vol, const uint8_t *__restrict__ codes, int res, int64_t nvox,
-                                                                int64_t nchunks, const McGroup *__restrict__ groups, const int64_t *__restrict__ voff,
-                                                                const int64_t *__restrict__ toff, McFillArgs a)
-{
-    const int64_t chunk = (int64_t)blockIdx.x * kMcWaves + wave_id();
+    const int64_t chunk = (int64_t)blockIdx.x * kExtractWaves + wave_id();
     if (chunk >= nchunks) return;
     const int lane = lane_id();
     const unsigned long long below = (1ull << lane) - 1ull;
     const int64_t vbase = voff[chunk], tbase = toff[chunk];
     if (voff[chunk + 1] == vbase && toff[chunk + 1] == tbase) return;
     const int64_t step[3] = { (int64_t)res * res, (int64_t)res, 1 };
-    for (int r = 0; r < kMcRounds; ++r) {
-        const int64_t g = chunk * kMcRounds + r, lin = g * 64 + lane;
+    for (int r = 0; r < kChunkRounds; ++r) {
+        const int64_t g = chunk * kChunkRounds + r, lin = g * 64 + lane;
         if (g * 64 >= nvox) break;
         const McGroup G = groups[g];
         int x = 0, y = 0, z = 0;
-        if (lin < nvox) mc_split(lin, res, x, y, z);
+        if (lin < nvox) tsdf_split((uint32_t)lin, (uint32_t)res, x, y, z);
         // the vertices of this voxel's three edges
         const unsigned mine = lin < nvox ? (unsigned)((G.m[0] >> lane) & 1ull) | (unsigned)((G.m[1] >> lane) & 1ull) << 1 | (unsigned)((G.m[2] >> lane) & 1ull) << 2 : 0u;
         if (mine) {
@@ -199,7 +112,6 @@ __global__ __launch_bounds__(kMcWaves * 64) void mc_fill_kernel(const float2 *__
     }
 }
 
-inline int64_t mc_voxels(int32_t res) { return (int64_t)res * res * res; }
 inline bool mc_res_ok(int32_t res) { return res >= 1 && res <= KPX_TSDF_MAX_RESOLUTION; }
 
 struct McScratch {
@@ -210,15 +122,13 @@ struct McScratch {
 };
 void mc_carve(Arena &a, int32_t res, McScratch *s)
 {
-    s->nvox = mc_voxels(res);
-    s->nchunks = cdiv(s->nvox, kMcChunk);
+    s->nvox = (int64_t)res * res * res;
+    s->nchunks = cdiv(s->nvox, kChunk);
     s->codes = a.get<uint8_t>((size_t)s->nvox);
-    s->groups = a.get<McGroup>((size_t)s->nchunks * kMcRounds);
+    s->groups = a.get<McGroup>((size_t)s->nchunks * kChunkRounds);
     s->voff = a.get<int64_t>((size_t)s->nchunks + 1);
     s->toff = a.get<int64_t>((size_t)s->nchunks + 1);
 }
-
-constexpr int64_t kMeshMax = 2147483647;        // int32 indices
 
 }  // namespace
 }  // namespace kpx
@@ -242,9 +152,10 @@ KPX_EXPORT int kpx_tsdf_mesh_count(const float *volume, int32_t resolution, int6
     McScratch s;
     mc_carve(a, resolution, &s);
     KPX_ARENA_CHECK(a);
+    const UniformView v = uniform_view(volume, nullptr, resolution, 0.0, nullptr);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, reinterpret_cast<const float2 *>(volume), resolution, s.nvox, s.codes);
-    hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)cdiv(s.nchunks, kMcWaves)), dim3(kMcWaves * 64), 0, st, (const uint8_t *)s.codes, resolution, s.nvox,
+    hipLaunchKernelGGL(mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, v.vol, resolution, s.nvox, s.codes);
+    hipLaunchKernelGGL(mc_count_kernel<UniformView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, (const uint8_t *)s.codes,
                        s.nchunks, s.groups, s.voff, s.toff);
     hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, s.voff, s.toff, s.nchunks);
     KPX_LAUNCH_CHECK();
@@ -269,13 +180,9 @@ KPX_EXPORT int kpx_tsdf_mesh_fill(const float *volume, const float *color, int32
     McScratch s;
     mc_carve(a, resolution, &s);
     KPX_ARENA_CHECK(a);
-    McFillArgs f;
-    for (int k = 0; k < 3; ++k) f.org[k] = h_origin[k];
-    f.vl = voxel_length;
-    f.col = color; f.overt = out_vertices; f.ocol = out_colors; f.otri = out_triangles;
-    f.nv = n_vertices; f.nt = n_triangles;
+    const McFillArgs f = { { h_origin[0], h_origin[1], h_origin[2] }, voxel_length, color, out_vertices, out_colors, out_triangles, n_vertices, n_triangles };
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kMcWaves)), dim3(kMcWaves * 64), 0, st, reinterpret_cast<const float2 *>(volume),
+    hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, reinterpret_cast<const float2 *>(volume),
                        (const uint8_t *)s.codes, resolution, s.nvox, s.nchunks, (const McGroup *)s.groups, (const int64_t *)s.voff, (const int64_t *)s.toff, f);
     KPX_LAUNCH_CHECK();
     return KPX_OK;

@@ -335,6 +335,33 @@ def test_sphere_blocks_uploaded_in_shuffled_order():
             assert same(p, q)
 
 
+@functools.lru_cache(None)
+def small_sphere(unit_resolution, removed=None):
+    """a sphere of radius 2.1 voxels in 6^3 voxels cut into blocks of 1^3 (216, from (-3, -3, -3)) or 2^3 (27, from (-1, -1, -1)): the
+    unit resolutions below the ring's.  At R = 1 every neighbour is another block, and a normal's tap reaches two blocks away: the only
+    input on which the view looks a block up by its key and not in the 27-neighbour table."""
+    f, w = M.sphere_volume(6, 2.1, (3.29, 2.92, 3.04))
+    col = (np.arange(6 ** 3 * 3, dtype=np.float32).reshape(-1, 3) * np.float32(0.37)) % np.float32(255.0)
+    first = {1: (-3, -3, -3), 2: (-1, -1, -1)}[unit_resolution]
+    return B.from_dense(f, w, col, 6, SPHERE_VL, unit_resolution, first, None if removed is None else (lambda b: b != removed))
+
+
+# The removed block is one the surface passes through: at R = 1 voxel (3, 2, 4) of the 6^3, inside the sphere with its +z neighbour
+# outside; at R = 2 the corner block of voxels 4..5 on every axis.  (The block round the centre, (0, 0, 0) at R = 2, holds no voxel of
+# the band: without it the restatement loses triangles and no point.)  The counts are the restatement's.
+@pytest.mark.parametrize("unit_resolution,gone,left", [(1, (0, -1, 1), (81, 81, 148)), (2, (1, 1, 1), (80, 80, 149))], ids=["R1", "R2"])
+def test_small_sphere_at_unit_resolutions_one_and_two(unit_resolution, gone, left):
+    whole = small_sphere(unit_resolution)
+    assert len(whole.units) == (6 // unit_resolution) ** 3
+    vol = upload(whole)
+    assert_units(vol, whole)
+    assert assert_extractions(vol, whole) == (82, 116, 82, 160)
+    holed = small_sphere(unit_resolution, gone)
+    assert len(holed.units) == len(whole.units) - 1
+    n_pts, _, n_vert, n_tri = assert_extractions(upload(holed), holed)
+    assert (n_pts, n_vert, n_tri) == left and 0 < n_pts < 82
+
+
 # ---- fuse_depth_tsdf ---------------------------------------------------------------------------------------------------------------
 def test_fuse_depth_tsdf_scalable_and_default():
     from kinectpy_amd import o3d
