@@ -101,7 +101,8 @@ int kpx_joints_affine_f64(const double *x, int64_t rows, const double *h_A, cons
  * KPX_SELECT_GATHER (0): out[k] = in[idx[k]] for k < n_idx -- equal to Open3D for ascending duplicate-free lists (the
  *                        keep lists / inlier lists this library produces, np.argwhere results), one gather, no count;
  * KPX_SELECT_INVERT (1): ascending complement of idx; d_count receives its length;
- * KPX_SELECT_MASK   (2): the mask semantics for arbitrary lists (unsorted, repeated); d_count receives the length. */
+ * KPX_SELECT_MASK   (2): the mask semantics for arbitrary lists (unsorted, repeated); d_count receives the length.
+ * Modes 1 and 2 need a workspace of kpx_select_workspace_bytes(n); mode 0 needs none (ws may be NULL). */
 #define KPX_SELECT_GATHER 0
 #define KPX_SELECT_INVERT 1
 #define KPX_SELECT_MASK 2

@@ -2,7 +2,7 @@
 // forms) and the batched Morton order of kpx_morton.h.  Holds what those forms share below their host policy: the cloud set with
 // its index lookup, the two point sources and the per-cloud bounding boxes.
 #pragma once
-#include "kpx_common.h"
+#include "kpx_box.h"
 
 namespace kpx {
 
@@ -50,7 +50,6 @@ struct MovedPoint {
 template <class Set, class Src, class Acc, int BLOCKS>
 __global__ __launch_bounds__(256) void cloud_bbox_partial_kernel(Set b, double *__restrict__ part)
 {
-    __shared__ Acc sh[6][4];
     const int c = blockIdx.y;
     const int64_t n = b.off[c + 1] - b.off[c];
     Acc mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
@@ -60,16 +59,7 @@ __global__ __launch_bounds__(256) void cloud_bbox_partial_kernel(Set b, double *
 #pragma unroll
         for (int a = 0; a < 3; ++a) { const Acc v = (Acc)q[a]; mn[a] = fmin(mn[a], v); mx[a] = fmax(mx[a], v); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        Acc v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fmin(v, sh[threadIdx.x][w]) : fmax(v, sh[threadIdx.x][w]);
-        part[((int64_t)c * BLOCKS + blockIdx.x) * 6 + threadIdx.x] = (double)v;
-    }
+    box_block_fold<4>(mn, mx, part + ((int64_t)c * BLOCKS + blockIdx.x) * 6);
 }
 // where the box of cloud c goes; err non-null: the cloud's error word, zeroed with it
 struct BoxDst {
@@ -85,8 +75,7 @@ __global__ __launch_bounds__(64) void cloud_bbox_final_kernel(const double *__re
     double v[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) v[a] = lane < BLOCKS ? part[((int64_t)c * BLOCKS + lane) * 6 + a] : (a < 3 ? (double)INFINITY : -(double)INFINITY);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { v[a] = wave_min(v[a]); v[3 + a] = wave_max(v[3 + a]); }
+    box_wave_fold(v, v + 3);
     if (lane == 0) {
         for (int a = 0; a < 6; ++a) dst.box[c][a] = v[a];
         if (dst.err) dst.err[c] = 0;

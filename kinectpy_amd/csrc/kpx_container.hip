@@ -1,43 +1,22 @@
-// kpx_misc.hip -- container operations of the Open3D surface the path touches:
-// transform, select_by_index, half-space select, slab split, bounding box.  HBM-streaming.
-#include <atomic>
-#include <mutex>
-#include <unordered_map>
+// kpx_container.hip -- container operations of the Open3D surface the path touches: transform / rotate / joints
+// affine, skeleton fusion, bounding box, select_by_index, half-space select, slab split, and the sort of the caller's own pairs.
+// HBM-streaming.
 #include "kpx_internal.h"
+#include "kpx_box.h"
 #include "kpx_sort.h"
 
 namespace kpx {
 
-namespace {
-std::mutex g_memo_mu;
-std::unordered_map<unsigned long long, size_t> g_memo;
-}
-size_t memo_bytes(unsigned what, int64_t n, const std::function<size_t()> &query)
-{
-    const unsigned long long key = ((unsigned long long)what << 48) ^ (unsigned long long)n;
-    {
-        std::lock_guard<std::mutex> lock(g_memo_mu);
-        auto it = g_memo.find(key);
-        if (it != g_memo.end()) return it->second;
-    }
-    const size_t bytes = query();
-    std::lock_guard<std::mutex> lock(g_memo_mu);
-    return g_memo[key] = bytes;
-}
-bool sort_radix_off()
-{
-    static const bool off = [] { const char *e = getenv("KPX_RADIX"); return e && e[0] == '0'; }();
-    return off;
-}
-
 struct Affine { double m[12]; };   // rows of [R | t]
 
-// AC1: p'_k = fma(R_k0, x, fma(R_k1, y, fma(R_k2, z, t_k)))
-__device__ __forceinline__ void xform3(const Affine &A, double x, double y, double z, double o[3])
+// AC1, row k: p'_k = fma(R_k0, x, fma(R_k1, y, fma(R_k2, z, t_k))); ROT_ONLY drops t and seeds the chain with R_k2 * z
+template <bool ROT_ONLY> __device__ __forceinline__ double xform_row(const Affine &A, int k, double x, double y, double z)
 {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, fma(A.m[4 * k + 2], z, A.m[4 * k + 3])));
+    return ROT_ONLY ? fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, A.m[4 * k + 2] * z))
+                    : fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, fma(A.m[4 * k + 2], z, A.m[4 * k + 3])));
 }
+// one row of three floats
+__device__ __forceinline__ void copy3(float *o, const float *s) { o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; }
 
 // 4 points (48 B) per lane with every global access a contiguous KiB per wave: the three 16-byte pieces a lane owns are
 // 48 bytes apart, so loads and stores go through LDS (round r, lane l <-> piece 64 r + l of the wave's 3 KiB).  Covers
@@ -60,11 +39,7 @@ __global__ __launch_bounds__(256) void transform_lds_kernel(const float *__restr
         for (int p = 0; p < 4; ++p) {
             const double x = v[3 * p], y = v[3 * p + 1], z = v[3 * p + 2];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double o = ROT_ONLY ? fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, A.m[4 * k + 2] * z))
-                                          : fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, fma(A.m[4 * k + 2], z, A.m[4 * k + 3])));
-                r12[3 * p + k] = (float)o;
-            }
+            for (int k = 0; k < 3; ++k) r12[3 * p + k] = (float)xform_row<ROT_ONLY>(A, k, x, y, z);
         }
         wave_lds_fence();
         stage[wave][3 * lane] = make_float4(r12[0], r12[1], r12[2], r12[3]);
@@ -94,11 +69,7 @@ __global__ __launch_bounds__(256) void transform_kernel(const float *__restrict_
             for (int p = 0; p < 4; ++p) {
                 double x = v[3 * p], y = v[3 * p + 1], z = v[3 * p + 2];
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double o = ROT_ONLY ? fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, A.m[4 * k + 2] * z))
-                                        : fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, fma(A.m[4 * k + 2], z, A.m[4 * k + 3])));
-                    r[3 * p + k] = (float)o;
-                }
+                for (int k = 0; k < 3; ++k) r[3 * p + k] = (float)xform_row<ROT_ONLY>(A, k, x, y, z);
             }
             float4 *dst = reinterpret_cast<float4 *>(out + g * 12);
             dst[0] = make_float4(r[0], r[1], r[2], r[3]);
@@ -110,11 +81,7 @@ __global__ __launch_bounds__(256) void transform_kernel(const float *__restrict_
     for (int64_t i = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         double x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            double o = ROT_ONLY ? fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, A.m[4 * k + 2] * z))
-                                : fma(A.m[4 * k], x, fma(A.m[4 * k + 1], y, fma(A.m[4 * k + 2], z, A.m[4 * k + 3])));
-            out[3 * i + k] = (float)o;
-        }
+        for (int k = 0; k < 3; ++k) out[3 * i + k] = (float)xform_row<ROT_ONLY>(A, k, x, y, z);
     }
 }
 
@@ -172,22 +139,12 @@ __global__ __launch_bounds__(64) void fuse_skeletons_kernel(const double *__rest
 // ---- bounding box --------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restrict__ pts, int64_t n, double *__restrict__ part)
 {
-    __shared__ float sh[6][4];
     float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { float v = pts[3 * i + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        part[(int64_t)blockIdx.x * 6 + threadIdx.x] = (double)v;
-    }
+    box_block_fold<4>(mn, mx, part + (int64_t)blockIdx.x * 6);
 }
 // The same partial boxes from lane-contiguous 16-byte loads (pts 16-byte aligned): a wave reads 3 KiB = 256 points per chunk as three
 // loads of one contiguous KiB each, two chunks in flight.  Float e of the cloud belongs to axis e mod 3, and float 4 (192 c + 64 r + lane) + j
@@ -195,7 +152,6 @@ __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restri
 // lane mod 3 once at the end.  (The one-point-per-trip kernel above read 64M points at 2.9 TB/s.)
 __global__ __launch_bounds__(256) void bbox_partial_vec_kernel(const float *__restrict__ pts, int64_t n, double *__restrict__ part)
 {
-    __shared__ float sh[6][4];
     const int lane = lane_id(), wave = wave_id();
     float smn[3] = { INFINITY, INFINITY, INFINITY }, smx[3] = { -INFINITY, -INFINITY, -INFINITY };
     const int64_t chunks = n / 256, wstride = (int64_t)gridDim.x * 4;
@@ -230,122 +186,22 @@ __global__ __launch_bounds__(256) void bbox_partial_vec_kernel(const float *__re
             for (int a = 0; a < 3; ++a) { const float v = pts[3 * i + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave] = mn[a]; sh[3 + a][wave] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        part[(int64_t)blockIdx.x * 6 + threadIdx.x] = (double)v;
-    }
+    box_block_fold<4>(mn, mx, part + (int64_t)blockIdx.x * 6);
 }
+// min / max are exact and order-independent: thread t folds the partial rows t, t+256, ..., then waves, then LDS
 __global__ __launch_bounds__(256) void bbox_final_kernel(const double *__restrict__ part, int nb, double *__restrict__ bbox)
 {
-    // min / max are exact and order-independent: thread t folds the partial rows t, t+256, ..., then waves, then LDS
-    __shared__ double sh[6][4];
     double v[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
     for (int b = threadIdx.x; b < nb; b += 256) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { v[a] = fmin(v[a], part[(int64_t)b * 6 + a]); v[3 + a] = fmax(v[3 + a], part[(int64_t)b * 6 + 3 + a]); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { v[a] = wave_min(v[a]); v[3 + a] = wave_max(v[3 + a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 6; ++a) sh[a][wave_id()] = v[a];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double r = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) r = threadIdx.x < 3 ? fmin(r, sh[threadIdx.x][w]) : fmax(r, sh[threadIdx.x][w]);
-        bbox[threadIdx.x] = r;
-    }
+    box_block_fold<4>(v, v + 3, bbox);
 }
-// ---- what a host thread holds (kpx_internal.h) -------------------------------------------------------------------
-// process-wide sums over the threads' owners: [0] pinned bytes, [1] streams, [2] events, [3] threads holding any
-static std::atomic<uint64_t> g_held[4];
-ThreadResources &thread_resources()
-{
-    static thread_local ThreadResources mine;
-    return mine;
-}
-void ThreadResources::hold()
-{
-    if (!counted) g_held[3].fetch_add(1, std::memory_order_relaxed);
-    counted = true;
-}
-void *ThreadResources::pinned_alloc(PinnedSite site, size_t bytes)
-{
-    void *p = nullptr;
-    const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        fail(KPX_ERR_HIP, "hipHostMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return nullptr;
-    }
-    memset(p, 0, bytes);
-    pin[site] = p;
-    pin_bytes[site] = bytes;
-    g_held[0].fetch_add(bytes, std::memory_order_relaxed);
-    hold();
-    return p;
-}
-ThreadResources::~ThreadResources()
-{
-    for (int i = 0; i < kPinnedSites; ++i)
-        if (pin[i]) {
-            (void)hipHostFree(pin[i]);
-            g_held[0].fetch_sub(pin_bytes[i], std::memory_order_relaxed);
-        }
-    for (LaneSet &set : lanes) {
-        for (int l = 0; l < kLaneCount; ++l) {
-            if (set.s[l]) { (void)hipStreamDestroy(set.s[l]); g_held[1].fetch_sub(1, std::memory_order_relaxed); }
-            if (set.join[l]) { (void)hipEventDestroy(set.join[l]); g_held[2].fetch_sub(1, std::memory_order_relaxed); }
-        }
-        if (set.fork) { (void)hipEventDestroy(set.fork); g_held[2].fetch_sub(1, std::memory_order_relaxed); }
-    }
-    if (counted) g_held[3].fetch_sub(1, std::memory_order_relaxed);
-}
-int lanes_get(LaneSet **out)
-{
-    // one set per host thread and device: the fork / join events belong to one call at a time, and streams belong to
-    // the device that was current when they were created
-    int dev = 0;
-    KPX_HIP(hipGetDevice(&dev));
-    KPX_REQUIRE(dev >= 0 && dev < kLaneDevices, "lanes_get: device ordinal %d out of range", dev);
-    ThreadResources &tr = thread_resources();
-    LaneSet &set = tr.lanes[dev];
-    if (!set.fork) {                       // (what an earlier, failed attempt did create is kept and counted)
-        tr.hold();
-        for (int l = 0; l < kLaneCount; ++l) {
-            if (!set.s[l]) { KPX_HIP(hipStreamCreateWithFlags(&set.s[l], hipStreamNonBlocking)); g_held[1].fetch_add(1, std::memory_order_relaxed); }
-            if (!set.join[l]) { KPX_HIP(hipEventCreateWithFlags(&set.join[l], hipEventDisableTiming)); g_held[2].fetch_add(1, std::memory_order_relaxed); }
-        }
-        KPX_HIP(hipEventCreateWithFlags(&set.fork, hipEventDisableTiming));
-        g_held[2].fetch_add(1, std::memory_order_relaxed);
-    }
-    *out = &set;
-    return KPX_OK;
-}
-int lanes_fork(LaneSet *l, hipStream_t caller, int used)
-{
-    KPX_HIP(hipEventRecord(l->fork, caller));
-    for (int i = 0; i < used && i < kLaneCount; ++i) KPX_HIP(hipStreamWaitEvent(l->s[i], l->fork, 0));
-    return KPX_OK;
-}
-int lanes_join(LaneSet *l, hipStream_t caller, int used)
-{
-    for (int i = 0; i < used && i < kLaneCount; ++i) {
-        KPX_HIP(hipEventRecord(l->join[i], l->s[i]));
-        KPX_HIP(hipStreamWaitEvent(caller, l->join[i], 0));
-    }
-    return KPX_OK;
-}
-
 // small clouds: one block does the whole reduction (one launch instead of two; the chains these boxes sit in are bound by
 // the host's launch rate)
 __global__ __launch_bounds__(1024) void bbox_small_kernel(const float *__restrict__ pts, int64_t n, double *__restrict__ bbox)
 {
-    __shared__ float sh[6][16];
     float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
     // eight points per trip, their loads issued together: one block streams the cloud, so the loop is as fast as its loads in flight
     // (one point per trip took 14 us for 30k points, the latency of 30 dependent trips)
@@ -363,16 +219,7 @@ __global__ __launch_bounds__(1024) void bbox_small_kernel(const float *__restric
 #pragma unroll
             for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], v[u][a]); mx[a] = fmaxf(mx[a], v[u][a]); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 16; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        bbox[threadIdx.x] = (double)v;
-    }
+    box_block_fold<16>(mn, mx, bbox);
 }
 int bbox_f32(const float *pts, int64_t n, double *d_bbox6, double *ws_partials, hipStream_t st)
 {
@@ -400,9 +247,9 @@ __global__ __launch_bounds__(256) void gather3_kernel(const float *__restrict__ 
 {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_idx; k += (int64_t)gridDim.x * blockDim.x) {
         int64_t s = idx[k];
-        if (a0) { o0[3 * k] = a0[3 * s]; o0[3 * k + 1] = a0[3 * s + 1]; o0[3 * k + 2] = a0[3 * s + 2]; }
-        if (a1) { o1[3 * k] = a1[3 * s]; o1[3 * k + 1] = a1[3 * s + 1]; o1[3 * k + 2] = a1[3 * s + 2]; }
-        if (a2) { o2[3 * k] = a2[3 * s]; o2[3 * k + 1] = a2[3 * s + 1]; o2[3 * k + 2] = a2[3 * s + 2]; }
+        if (a0) copy3(o0 + 3 * k, a0 + 3 * s);
+        if (a1) copy3(o1 + 3 * k, a1 + 3 * s);
+        if (a2) copy3(o2 + 3 * k, a2 + 3 * s);
     }
 }
 // the gather of the first attribute (the points) that also leaves the partial boxes of what it wrote (rows of six doubles, one per block,
@@ -413,7 +260,6 @@ __global__ __launch_bounds__(256) void gather3_bounds_kernel(const float *__rest
                                                              int64_t n_idx, float *__restrict__ o0, float *__restrict__ o1,
                                                              float *__restrict__ o2, double *__restrict__ part)
 {
-    __shared__ float sh[6][4];
     float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_idx; k += (int64_t)gridDim.x * blockDim.x) {
         int64_t s = idx[k];
@@ -422,19 +268,10 @@ __global__ __launch_bounds__(256) void gather3_bounds_kernel(const float *__rest
             const float v = a0[3 * s + a];
             o0[3 * k + a] = v; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v);
         }
-        if (a1) { o1[3 * k] = a1[3 * s]; o1[3 * k + 1] = a1[3 * s + 1]; o1[3 * k + 2] = a1[3 * s + 2]; }
-        if (a2) { o2[3 * k] = a2[3 * s]; o2[3 * k + 1] = a2[3 * s + 1]; o2[3 * k + 2] = a2[3 * s + 2]; }
+        if (a1) copy3(o1 + 3 * k, a1 + 3 * s);
+        if (a2) copy3(o2 + 3 * k, a2 + 3 * s);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; ++a) { sh[a][wave_id()] = mn[a]; sh[3 + a][wave_id()] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = sh[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, sh[threadIdx.x][w]) : fmaxf(v, sh[threadIdx.x][w]);
-        part[(int64_t)blockIdx.x * 6 + threadIdx.x] = (double)v;
-    }
+    box_block_fold<4>(mn, mx, part + (int64_t)blockIdx.x * 6);
 }
 __global__ __launch_bounds__(256) void mark_kernel(const int32_t *__restrict__ idx, int64_t n_idx, int64_t n, uint8_t *__restrict__ flag)
 {
@@ -456,9 +293,9 @@ struct Gather3Emit {
     __device__ void operator()(int64_t i, int, int32_t dst) const
     {
         int64_t d = dst;
-        if (a0) { o0[3 * d] = a0[3 * i]; o0[3 * d + 1] = a0[3 * i + 1]; o0[3 * d + 2] = a0[3 * i + 2]; }
-        if (a1) { o1[3 * d] = a1[3 * i]; o1[3 * d + 1] = a1[3 * i + 1]; o1[3 * d + 2] = a1[3 * i + 2]; }
-        if (a2) { o2[3 * d] = a2[3 * i]; o2[3 * d + 1] = a2[3 * i + 1]; o2[3 * d + 2] = a2[3 * i + 2]; }
+        if (a0) copy3(o0 + 3 * d, a0 + 3 * i);
+        if (a1) copy3(o1 + 3 * d, a1 + 3 * i);
+        if (a2) copy3(o2 + 3 * d, a2 + 3 * i);
     }
 };
 
@@ -506,16 +343,30 @@ static int grid_for(int64_t work, int per_block, int cap = 4096)
     return (int)(b > cap ? cap : b);
 }
 
+
+// ---- scratch: every layout stated once, carved by the byte-count function and by the entry points alike -----------------
+static double *bounds_carve(Arena &a) { return a.get<double>((size_t)kBboxBlocks * 6); }      // bbox_f32's partial boxes
+// what the select_by_index, half-space and slab entry points share (kpx_select_workspace_bytes)
+struct PointSelectScratch {
+    uint8_t *flag;              // [n] the marks of the mask modes
+    int32_t *counts;            // compact()'s tile words
+    double *part, *bbox;        // bbox_f32's partial boxes and the box it leaves (slab split of a cloud without known bounds)
+    CompactPtsScratch pts;      // compact_points()
+    double *gather_part;        // [kGatherBoundsBlocks * 6] the partial boxes of gather3_bounds_kernel
+};
+static void point_select_carve(Arena &a, int64_t n, PointSelectScratch *s)
+{
+    s->flag = a.get<uint8_t>((size_t)(n > 0 ? n : 1));
+    s->counts = a.get<int32_t>((size_t)compact_ws_ints(n));
+    s->part = bounds_carve(a);
+    s->bbox = a.get<double>(8);
+    compact_pts_carve(a, n, &s->pts);
+    s->gather_part = a.get<double>((size_t)kGatherBoundsBlocks * 6);
+}
+
 }  // namespace kpx
 
 using namespace kpx;
-
-KPX_EXPORT int kpx_host_resources(uint64_t *h_out4)
-{
-    KPX_REQUIRE(h_out4, "kpx_host_resources: null pointer");
-    for (int i = 0; i < 4; ++i) h_out4[i] = g_held[i].load(std::memory_order_relaxed);
-    return KPX_OK;
-}
 
 KPX_EXPORT int kpx_transform(const float *pts, int64_t n, const double *h_T, float *out, void *stream)
 {
@@ -610,25 +461,21 @@ KPX_EXPORT int kpx_sort_pairs_u32(const uint32_t *keys_in, const int32_t *vals_i
 KPX_EXPORT size_t kpx_select_workspace_bytes(int64_t n)
 {
     Arena a(nullptr, 0);
-    a.get<uint8_t>((size_t)(n > 0 ? n : 1));
-    a.get<int32_t>((size_t)compact_ws_ints(n));
-    a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    CompactPtsScratch cs;
-    compact_pts_carve(a, n, &cs);
-    a.get<double>((size_t)kGatherBoundsBlocks * 6);              // kpx_select_by_index_bounds' partial boxes
+    PointSelectScratch s;
+    point_select_carve(a, n, &s);
     return a.off;
 }
 KPX_EXPORT size_t kpx_bounds_workspace_bytes(void)
 {
     Arena a(nullptr, 0);
-    a.get<double>((size_t)kBboxBlocks * 6);
+    bounds_carve(a);
     return a.off;
 }
 KPX_EXPORT int kpx_bounds(const float *pts, int64_t n, double *d_bbox6, void *ws, size_t ws_bytes, void *stream)
 {
     KPX_REQUIRE(n > 0 && pts && d_bbox6 && ws, "kpx_bounds: bad arguments");
     Arena a(ws, ws_bytes);
-    double *part = a.get<double>((size_t)kBboxBlocks * 6);
+    double *part = bounds_carve(a);
     KPX_ARENA_CHECK(a);
     return bbox_f32(pts, n, d_bbox6, part, (hipStream_t)stream);
 }
@@ -639,16 +486,12 @@ KPX_EXPORT int kpx_select_by_index_bounds(const float *a0, const float *a1, cons
     KPX_REQUIRE(idx && a0 && o0 && d_bbox6 && ws, "kpx_select_by_index_bounds: null pointer");
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    a.get<uint8_t>((size_t)(n > 0 ? n : 1));
-    a.get<int32_t>((size_t)compact_ws_ints(n));
-    a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    CompactPtsScratch cs;
-    compact_pts_carve(a, n, &cs);
-    double *part = a.get<double>((size_t)kGatherBoundsBlocks * 6);
+    PointSelectScratch s;
+    point_select_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
     const int nb = grid_for(n_idx, 256, kGatherBoundsBlocks);
-    hipLaunchKernelGGL(gather3_bounds_kernel, dim3(nb), dim3(256), 0, st, a0, a1, a2, idx, n_idx, o0, o1, o2, part);
-    hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(256), 0, st, part, nb, d_bbox6);
+    hipLaunchKernelGGL(gather3_bounds_kernel, dim3(nb), dim3(256), 0, st, a0, a1, a2, idx, n_idx, o0, o1, o2, s.gather_part);
+    hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(256), 0, st, s.gather_part, nb, d_bbox6);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -668,13 +511,13 @@ KPX_EXPORT int kpx_select_by_index(const float *a0, const float *a1, const float
     KPX_REQUIRE(invert == KPX_SELECT_INVERT || invert == KPX_SELECT_MASK, "kpx_select_by_index: unknown mode %d", invert);
     KPX_REQUIRE(ws && d_count, "kpx_select_by_index: the mask modes need workspace and d_count");
     Arena a(ws, ws_bytes);
-    uint8_t *flag = a.get<uint8_t>((size_t)(n > 0 ? n : 1));
-    int32_t *counts = a.get<int32_t>((size_t)compact_ws_ints(n));
+    PointSelectScratch s;
+    point_select_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
-    KPX_HIP(hipMemsetAsync(flag, 0, (size_t)(n > 0 ? n : 1), st));
-    if (n_idx) hipLaunchKernelGGL(mark_kernel, dim3(grid_for(n_idx, 256)), dim3(256), 0, st, idx, n_idx, n, flag);
-    if (invert == KPX_SELECT_MASK) return compact(MarkedPred{ flag }, Gather3Emit{ a0, a1, a2, o0, o1, o2 }, n, 1, counts, d_count, st);
-    return compact(UnmarkedPred{ flag }, Gather3Emit{ a0, a1, a2, o0, o1, o2 }, n, 1, counts, d_count, st);
+    KPX_HIP(hipMemsetAsync(s.flag, 0, (size_t)(n > 0 ? n : 1), st));
+    if (n_idx) hipLaunchKernelGGL(mark_kernel, dim3(grid_for(n_idx, 256)), dim3(256), 0, st, idx, n_idx, n, s.flag);
+    if (invert == KPX_SELECT_MASK) return compact(MarkedPred{ s.flag }, Gather3Emit{ a0, a1, a2, o0, o1, o2 }, n, 1, s.counts, d_count, st);
+    return compact(UnmarkedPred{ s.flag }, Gather3Emit{ a0, a1, a2, o0, o1, o2 }, n, 1, s.counts, d_count, st);
 }
 
 KPX_EXPORT int kpx_halfspace_select(const float *pts, int64_t n, const double *h_plane, int32_t *idx, int32_t *d_count,
@@ -682,15 +525,12 @@ KPX_EXPORT int kpx_halfspace_select(const float *pts, int64_t n, const double *h
 {
     KPX_REQUIRE(n >= 0 && h_plane && idx && d_count && ws, "kpx_halfspace_select: bad arguments");
     Arena a(ws, ws_bytes);
-    a.get<uint8_t>((size_t)(n > 0 ? n : 1));
-    int32_t *counts = a.get<int32_t>((size_t)compact_ws_ints(n));
-    a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    CompactPtsScratch cs;
-    compact_pts_carve(a, n, &cs);
+    PointSelectScratch s;
+    point_select_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
-    if (n == 0) return compact(HalfspacePred{ pts, h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, IndexEmit{ idx }, n, 1, counts, d_count,
+    if (n == 0) return compact(HalfspacePred{ pts, h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, IndexEmit{ idx }, n, 1, s.counts, d_count,
                                (hipStream_t)stream);
-    return compact_points(pts, n, HalfspaceXYZ{ h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, idx, d_count, nullptr, nullptr, cs,
+    return compact_points(pts, n, HalfspaceXYZ{ h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, idx, d_count, nullptr, nullptr, s.pts,
                           (hipStream_t)stream);
 }
 
@@ -699,18 +539,14 @@ static int slab_split_impl(const float *pts, int64_t n, double slab, const doubl
                            int32_t *upper_idx, int32_t *d_upper, void *ws, size_t ws_bytes, hipStream_t st)
 {
     Arena a(ws, ws_bytes);
-    a.get<uint8_t>((size_t)n);
-    a.get<int32_t>((size_t)compact_ws_ints(n));
-    double *part = a.get<double>((size_t)kBboxBlocks * 6 + 8);
-    CompactPtsScratch cs;
-    compact_pts_carve(a, n, &cs);
+    PointSelectScratch s;
+    point_select_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
-    double *bbox = part + (size_t)kBboxBlocks * 6;
     if (!d_bounds) {
-        int rc = bbox_f32(pts, n, bbox, part, st);
+        int rc = bbox_f32(pts, n, s.bbox, s.part, st);
         if (rc) return rc;
     }
-    return compact_points(pts, n, SlabXYZ{ d_bounds ? d_bounds : bbox, slab }, lower_idx, d_lower, upper_idx, d_upper, cs, st);      // one pass feeds both lists
+    return compact_points(pts, n, SlabXYZ{ d_bounds ? d_bounds : s.bbox, slab }, lower_idx, d_lower, upper_idx, d_upper, s.pts, st);      // one pass feeds both lists
 }
 KPX_EXPORT int kpx_slab_split(const float *pts, int64_t n, double slab, int32_t *lower_idx, int32_t *d_lower,
                               int32_t *upper_idx, int32_t *d_upper, void *ws, size_t ws_bytes, void *stream)
@@ -724,3 +560,4 @@ KPX_EXPORT int kpx_slab_split_bounded(const float *pts, int64_t n, double slab, 
     KPX_REQUIRE(n > 0 && pts && d_bbox6 && lower_idx && upper_idx && d_lower && d_upper && ws, "kpx_slab_split_bounded: bad arguments");
     return slab_split_impl(pts, n, slab, d_bbox6, lower_idx, d_lower, upper_idx, d_upper, ws, ws_bytes, (hipStream_t)stream);
 }
+

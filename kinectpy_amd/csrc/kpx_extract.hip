@@ -1,51 +1,9 @@
 // kpx_extract.hip -- extract stage: depth -> XYZ int16, exact median, mask + gate + compaction.
 // Reference: preprocessing/extractor.py:68-80 (external unprojection, `.dat` contract),
 // utils/io.py:15-43, preprocessing/data.py:165-178.  All HBM-streaming kernels.
-#include <stdarg.h>
-
-#include <mutex>
-
 #include "kpx_internal.h"
 
 namespace kpx {
-
-thread_local char g_err[512] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// ---- profiler -------------------------------------------------------------------------------------
-static struct {
-    bool on = false;
-    int stride = 1;                          // time every stride-th launch of a kernel id
-    long long total[KPX_PROF_KERNELS] = {};  // launches seen while armed, timed or not
-    int cap = 0, used = 0;
-    hipEvent_t *e0 = nullptr, *e1 = nullptr;
-    int *kid = nullptr;
-    double *work = nullptr;
-} g_prof;
-
-bool prof_armed() { return g_prof.on; }
-static std::mutex g_prof_mutex;         // launches may come from several host threads
-ProfScope::ProfScope(int kernel_id, double w, hipStream_t stream) : slot(-1), st(stream)
-{
-    if (!g_prof.on) return;
-    std::lock_guard<std::mutex> lock(g_prof_mutex);
-    if ((g_prof.total[kernel_id]++ % g_prof.stride) != 0 || g_prof.used >= g_prof.cap) return;
-    slot = g_prof.used++;
-    g_prof.kid[slot] = kernel_id;
-    g_prof.work[slot] = w;
-    (void)hipEventRecord(g_prof.e0[slot], st);
-}
-ProfScope::~ProfScope()
-{
-    if (slot >= 0) (void)hipEventRecord(g_prof.e1[slot], st);
-}
 
 // ------------------------------------------------------------------------------------------------
 // a1 unproject: 8 pixels per thread.  Reads 16 B of depth + 64 B of table, writes 48 B of int16 xyz.
@@ -616,51 +574,6 @@ struct DepthEmit {
 }  // namespace kpx
 
 using namespace kpx;
-
-KPX_EXPORT const char *kpx_last_error(void) { return g_err; }
-
-KPX_EXPORT int kpx_prof_begin(int32_t capacity)
-{
-    KPX_REQUIRE(capacity > 0 && capacity <= (1 << 20), "kpx_prof_begin: bad capacity");
-    if (g_prof.cap < capacity) {
-        for (int i = 0; i < g_prof.cap; ++i) { (void)hipEventDestroy(g_prof.e0[i]); (void)hipEventDestroy(g_prof.e1[i]); }
-        delete[] g_prof.e0; delete[] g_prof.e1; delete[] g_prof.kid; delete[] g_prof.work;
-        g_prof.e0 = new hipEvent_t[capacity]; g_prof.e1 = new hipEvent_t[capacity];
-        g_prof.kid = new int[capacity]; g_prof.work = new double[capacity];
-        for (int i = 0; i < capacity; ++i) { KPX_HIP(hipEventCreate(&g_prof.e0[i])); KPX_HIP(hipEventCreate(&g_prof.e1[i])); }
-        g_prof.cap = capacity;
-    }
-    g_prof.used = 0;
-    for (int k = 0; k < KPX_PROF_KERNELS; ++k) g_prof.total[k] = 0;
-    g_prof.on = true;
-    (void)nn_local_take_visits();
-    return KPX_OK;
-}
-KPX_EXPORT int kpx_prof_stride(int32_t stride)
-{
-    KPX_REQUIRE(stride >= 1, "kpx_prof_stride: stride must be >= 1");
-    g_prof.stride = stride;
-    return KPX_OK;
-}
-KPX_EXPORT int kpx_prof_end(double *h_ms, int64_t *h_launches, double *h_work)
-{
-    KPX_REQUIRE(h_ms && h_launches && h_work, "kpx_prof_end: null pointer");
-    g_prof.on = false;
-    for (int k = 0; k < KPX_PROF_KERNELS; ++k) { h_ms[k] = 0.0; h_launches[k] = 0; h_work[k] = 0.0; }
-    for (int i = 0; i < g_prof.used; ++i) {
-        KPX_HIP(hipEventSynchronize(g_prof.e1[i]));
-        float ms = 0.f;
-        KPX_HIP(hipEventElapsedTime(&ms, g_prof.e0[i], g_prof.e1[i]));
-        int k = g_prof.kid[i];
-        h_ms[k] += ms; h_launches[k] += 1; h_work[k] += g_prof.work[i];
-    }
-    g_prof.used = 0;
-    // flops actually issued (16 x 16 x 4 MAC per tile), scaled to the timed share of the launches
-    h_work[KPX_PROF_NN_LOCAL] = 2048.0 * nn_local_take_visits() * (g_prof.total[KPX_PROF_NN_LOCAL] > 0
-                                    ? (double)h_launches[KPX_PROF_NN_LOCAL] / (double)g_prof.total[KPX_PROF_NN_LOCAL] : 0.0);
-    return KPX_OK;
-}
-KPX_EXPORT int kpx_version(void) { return KPX_VERSION; }
 
 KPX_EXPORT int kpx_unproject_u16(const uint16_t *depth, const float *xy, int64_t n_px, int32_t frames, int16_t *xyz,
                                  void *stream)

@@ -454,13 +454,17 @@ struct NnProblem {
     NnPlan p;
     NnBuffers b;
     double *extra;
+    void carve(Arena &a, int64_t n_src, int64_t n_tgt, size_t extra_doubles)
+    {
+        p = nn_plan(n_src, n_tgt);
+        nn_carve(a, n_src, n_tgt, p, &b);
+        extra = a.get<double>(extra_doubles);
+    }
     int setup(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *h_init, void *ws, size_t ws_bytes, hipStream_t st,
               size_t extra_doubles = 0)
     {
         Arena a(ws, ws_bytes);
-        p = nn_plan(n_src, n_tgt);
-        nn_carve(a, n_src, n_tgt, p, &b);
-        extra = a.get<double>(extra_doubles);
+        carve(a, n_src, n_tgt, extra_doubles);
         KPX_ARENA_CHECK(a);
         if (h_init) hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(1), 0, st, b.state, mat16_from(h_init));
         const int rc = nn_prep(tgt, p, b, st);
@@ -602,7 +606,7 @@ KPX_EXPORT int kpx_nn_search(const float *src, int64_t n_src, const float *tgt, 
 // (block_sum), the blocks in order (regeval_finish_kernel) -- fixed by (n, grid), no floating-point atomics, so equal idx / d2
 // give equal bits whichever engine searched.
 // The gathers of t are n random 12-byte loads; the kernel is a few microseconds beside the search.
-constexpr int kEvalSums = 11, kEvalBlocks = 256, kEvalThreads = 256;
+constexpr int kEvalSums = 11, kEvalBlocks = 256, kEvalThreads = 256, kEvalPartials = kEvalBlocks * kEvalSums;      // (partials: doubles, NnProblem::extra)
 __global__ __launch_bounds__(kEvalThreads) void regeval_acc_kernel(const float *__restrict__ tgt, int64_t n, int64_t m, const int32_t *__restrict__ idx,
                                                                   const double *__restrict__ d2, double max_d2, double *__restrict__ part)
 {
@@ -660,9 +664,8 @@ __global__ __launch_bounds__(64) void regeval_finish_kernel(const double *__rest
 KPX_EXPORT size_t kpx_registration_eval_workspace_bytes(int64_t n_src, int64_t n_tgt)
 {
     Arena a(nullptr, 0);
-    NnBuffers b;
-    nn_carve(a, n_src, n_tgt, nn_plan(n_src, n_tgt), &b);
-    a.get<double>((size_t)kEvalBlocks * kEvalSums);
+    NnProblem q;
+    q.carve(a, n_src, n_tgt, kEvalPartials);
     return a.off;
 }
 KPX_EXPORT int kpx_registration_eval(const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double *d_T,
@@ -675,7 +678,7 @@ KPX_EXPORT int kpx_registration_eval(const float *src, int64_t n_src, const floa
     KPX_REQUIRE(src && tgt && d_T && d_result && ws, "kpx_registration_eval: null pointer");
     hipStream_t st = (hipStream_t)stream;
     NnProblem q;
-    int rc = q.setup(src, n_src, tgt, n_tgt, nullptr, ws, ws_bytes, st, (size_t)kEvalBlocks * kEvalSums);      // (the state is not used)
+    int rc = q.setup(src, n_src, tgt, n_tgt, nullptr, ws, ws_bytes, st, kEvalPartials);      // (the state is not used)
     if (rc) return rc;
     rc = nn_search_launch(src, tgt, nullptr, q.p, q.b, d_T, nullptr, false, false, 0.0, -1, st);      // as kpx_nn_search: the engine kpx_nn_engine selects
     if (rc) return rc;
@@ -687,10 +690,11 @@ KPX_EXPORT int kpx_registration_eval(const float *src, int64_t n_src, const floa
     return q.copy_pairs(idx, d2, st);
 }
 
+static double *kabsch_carve(Arena &a) { return a.get<double>((size_t)256 * kAcc); }      // pairs_acc_kernel's partial sums, one row per block
 KPX_EXPORT size_t kpx_kabsch_workspace_bytes(int64_t n_corr)
 {
     Arena a(nullptr, 0);
-    a.get<double>((size_t)256 * kAcc);
+    kabsch_carve(a);
     return a.off;
 }
 KPX_EXPORT int kpx_kabsch(const float *src, const float *tgt, const int32_t *corr, int64_t n_corr, double *d_T, void *ws,
@@ -700,7 +704,7 @@ KPX_EXPORT int kpx_kabsch(const float *src, const float *tgt, const int32_t *cor
     KPX_REQUIRE(n_corr == 0 || (src && tgt && corr), "kpx_kabsch: null pointer");
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    double *part = a.get<double>((size_t)256 * kAcc);
+    double *part = kabsch_carve(a);
     KPX_ARENA_CHECK(a);
     int nb = (int)(cdiv(n_corr > 0 ? n_corr : 1, 256) > 256 ? 256 : cdiv(n_corr > 0 ? n_corr : 1, 256));
     hipLaunchKernelGGL(pairs_acc_kernel, dim3(nb), dim3(256), 0, st, src, tgt, corr, n_corr, part);

@@ -49,7 +49,7 @@ int lanes_fork(LaneSet *l, hipStream_t caller, int used);
 int lanes_join(LaneSet *l, hipStream_t caller, int used);
 
 // ---- what a host thread holds -----------------------------------------------------------------------
-// Every host-side HIP resource the library keeps per calling thread lives in ONE thread_local object (kpx_misc.hip): the pinned
+// Every host-side HIP resource the library keeps per calling thread lives in ONE thread_local object (kpx_runtime.hip): the pinned
 // read-back blocks of the sites below, the lane sets, and the plain counters and caches that go with them.  Its destructor runs when
 // the thread ends (a kpx_stream worker: before kpx_stream_destroy's join returns) and gives everything back, ignoring every error
 // code -- a runtime that has already shut down must not turn a normal exit into a failure.  kpx_host_resources sums what all

@@ -952,12 +952,19 @@ KPX_EXPORT int kpx_sor_partial(const float *pts, int64_t n, int32_t nb_neighbors
     Arena a(ws, ws_bytes);
     return sor_impl(pts, n, nb_neighbors, 1.0, nullptr, nullptr, nullptr, d_avg_sorted, a, (hipStream_t)stream, false, q_begin, q_end, d_order);
 }
+// [n] the mean distances in the caller's order, [1024] sor_stats_compact's partial sums, compact()'s tile words
+struct SorFinishScratch { double *avg, *part; int32_t *counts; };
+static void sor_finish_carve(Arena &a, int64_t n, SorFinishScratch *s)
+{
+    s->avg = a.get<double>((size_t)(n > 0 ? n : 1));
+    s->part = a.get<double>(1024);
+    s->counts = a.get<int32_t>((size_t)compact_ws_ints(n));
+}
 KPX_EXPORT size_t kpx_sor_finish_workspace_bytes(int64_t n)
 {
     Arena a(nullptr, 0);
-    a.get<double>((size_t)(n > 0 ? n : 1));
-    a.get<double>(1024);
-    a.get<int32_t>((size_t)compact_ws_ints(n));
+    SorFinishScratch s;
+    sor_finish_carve(a, n, &s);
     return a.off;
 }
 KPX_EXPORT int kpx_sor_finish(const double *d_avg_sorted, const int32_t *d_order, int64_t n, double std_ratio, int32_t *keep_idx,
@@ -968,13 +975,12 @@ KPX_EXPORT int kpx_sor_finish(const double *d_avg_sorted, const int32_t *d_order
     KPX_REQUIRE(d_avg_sorted && d_order && keep_idx && d_count && d_stats && ws, "kpx_sor_finish: null pointer");
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    double *avg = a.get<double>((size_t)n);
-    double *part = a.get<double>(1024);
-    int32_t *counts = a.get<int32_t>((size_t)compact_ws_ints(n));
+    SorFinishScratch s;
+    sor_finish_carve(a, n, &s);
     KPX_ARENA_CHECK(a);
-    if (d_avg) avg = d_avg;
+    double *avg = d_avg ? d_avg : s.avg;
     hipLaunchKernelGGL(sor_unsort_kernel, dim3((unsigned)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256))), dim3(256), 0, st, d_avg_sorted, d_order, n, avg);
-    return sor_stats_compact(avg, n, std_ratio, part, counts, keep_idx, d_count, d_stats, st);
+    return sor_stats_compact(avg, n, std_ratio, s.part, s.counts, keep_idx, d_count, d_stats, st);
 }
 
 KPX_EXPORT size_t kpx_normals_workspace_bytes(int64_t n, int32_t max_nn)

@@ -1052,11 +1052,20 @@ KPX_EXPORT int kpx_mesh_select_vertices(const float *vertices, const float *colo
                    n_triangles, 1, s.counts_t, d_counts + 1, st);
 }
 
+// the widened arrays in two generations each, and the vertices a Laplacian step reads when they are not smoothed themselves
+struct SmoothScratch { double *buf[kSmoothArrays][2], *fixed_x; };
+static void smooth_carve(Arena &a, int64_t n_vertices, SmoothScratch *s)
+{
+    const size_t n3 = (size_t)(n_vertices > 0 ? 3 * n_vertices : 1);
+    for (int k = 0; k < kSmoothArrays; ++k) { s->buf[k][0] = a.get<double>(n3); s->buf[k][1] = a.get<double>(n3); }
+    s->fixed_x = a.get<double>(n3);
+}
 KPX_EXPORT size_t kpx_mesh_smooth_workspace_bytes(int64_t n_vertices)
 {
     if (n_vertices < 0 || n_vertices > kMeshMax) return 0;
     Arena a(nullptr, 0);
-    for (int i = 0; i < 2 * kSmoothArrays + 1; ++i) a.get<double>((size_t)(n_vertices > 0 ? 3 * n_vertices : 1));
+    SmoothScratch s;
+    smooth_carve(a, n_vertices, &s);
     return a.off;
 }
 
@@ -1074,33 +1083,32 @@ KPX_EXPORT int kpx_mesh_smooth(const float *vertices, const float *normals, cons
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
     const size_t n3 = (size_t)(3 * n_vertices);
-    double *buf[kSmoothArrays][2], *fixed_x = nullptr;
+    SmoothScratch sc;
+    smooth_carve(a, n_vertices, &sc);
+    KPX_ARENA_CHECK(a);
     const float *src[kSmoothArrays] = { vertices, normals, colors };
     float *dst[kSmoothArrays] = { out_vertices, out_normals, out_colors };
-    for (int k = 0; k < kSmoothArrays; ++k) { buf[k][0] = a.get<double>(n3); buf[k][1] = a.get<double>(n3); }
-    fixed_x = a.get<double>(n3);
-    KPX_ARENA_CHECK(a);
     const unsigned nb3 = mesh_blocks((int64_t)n3);
     int which[kSmoothArrays], count = 0;
     for (int k = 0; k < kSmoothArrays; ++k)
         if (dst[k]) {
             which[count++] = k;
-            hipLaunchKernelGGL(mesh_widen_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, src[k], (int64_t)n3, buf[k][0]);
+            hipLaunchKernelGGL(mesh_widen_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, src[k], (int64_t)n3, sc.buf[k][0]);
         }
     const int laplacian = method != KPX_MESH_SMOOTH_SIMPLE;
-    if (laplacian && !out_vertices) hipLaunchKernelGGL(mesh_widen_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, vertices, (int64_t)n3, fixed_x);
+    if (laplacian && !out_vertices) hipLaunchKernelGGL(mesh_widen_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, vertices, (int64_t)n3, sc.fixed_x);
     const int64_t steps = (int64_t)iterations * (method == KPX_MESH_SMOOTH_TAUBIN ? 2 : 1);
     int cur = 0;
     for (int64_t s = 0; s < steps; ++s, cur ^= 1) {
         SmoothArrays A{};
         A.count = count;
-        for (int i = 0; i < count; ++i) { A.in[i] = buf[which[i]][cur]; A.out[i] = buf[which[i]][cur ^ 1]; }
+        for (int i = 0; i < count; ++i) { A.in[i] = sc.buf[which[i]][cur]; A.out[i] = sc.buf[which[i]][cur ^ 1]; }
         const double lam = method == KPX_MESH_SMOOTH_TAUBIN && (s & 1) ? mu : lambda_filter;
         hipLaunchKernelGGL(mesh_smooth_kernel, dim3(mesh_blocks(n_vertices)), dim3(kMeshThreads), 0, st, offsets, neighbours, n_vertices, n_neighbours,
-                           (const double *)(out_vertices ? buf[0][cur] : fixed_x), A, laplacian, lam);
+                           (const double *)(out_vertices ? sc.buf[0][cur] : sc.fixed_x), A, laplacian, lam);
     }
     for (int i = 0; i < count; ++i)
-        hipLaunchKernelGGL(mesh_narrow_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, (const double *)buf[which[i]][cur], (int64_t)n3, dst[which[i]]);
+        hipLaunchKernelGGL(mesh_narrow_kernel, dim3(nb3), dim3(kMeshThreads), 0, st, (const double *)sc.buf[which[i]][cur], (int64_t)n3, dst[which[i]]);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -1224,11 +1232,12 @@ KPX_EXPORT int kpx_mesh_orientation(const int32_t *triangles, int64_t n_vertices
     return KPX_OK;
 }
 
+static double *volume_carve(Arena &a, int64_t n_triangles) { return a.get<double>((size_t)(n_triangles > 0 ? n_triangles : 1)); }      // the chain's prefix sums
 KPX_EXPORT size_t kpx_mesh_volume_workspace_bytes(int64_t n_triangles)
 {
     if (n_triangles < 0 || n_triangles > kMeshMax) return 0;
     Arena a(nullptr, 0);
-    a.get<double>((size_t)(n_triangles > 0 ? n_triangles : 1));
+    volume_carve(a, n_triangles);
     return a.off;
 }
 
@@ -1240,7 +1249,7 @@ KPX_EXPORT int kpx_mesh_volume(const float *vertices, int64_t n_vertices, const 
     KPX_REQUIRE(d_volume && ws && (n_triangles == 0 || (vertices && triangles)), "kpx_mesh_volume: null pointer");
     hipStream_t st = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    double *prefix = a.get<double>((size_t)(n_triangles > 0 ? n_triangles : 1));
+    double *prefix = volume_carve(a, n_triangles);
     KPX_ARENA_CHECK(a);
     if (n_triangles > 0)
         hipLaunchKernelGGL((mesh_chain_kernel<false, kTermTriple>), dim3(1), dim3(kAreaThreads), 0, st, vertices, n_vertices, triangles, n_triangles,

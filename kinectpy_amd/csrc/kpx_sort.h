@@ -28,7 +28,7 @@ enum SortForm {
     kSortDefault,        // default config, size_t count: the mesh's 64-bit pair keys
     kSortDefault32,      // default config, int count (n < 2^31): voxel keys, batched curve keys, sampler keys
 };
-bool sort_radix_off();          // KPX_RADIX=0, read once (kpx_misc.hip)
+bool sort_radix_off();          // KPX_RADIX=0, read once (kpx_runtime.hip)
 
 // tmp == nullptr: bytes receives the temporary size and nothing runs
 template <class Key, bool kVals, SortForm kForm>

@@ -95,11 +95,12 @@ inline bool tsdf_res_ok(int32_t res) { return res >= 1 && res <= KPX_TSDF_MAX_RE
 
 using namespace kpx;
 
+static int64_t *tsdf_carve(Arena &a, int64_t nchunks) { return a.get<int64_t>((size_t)nchunks + 1); }      // the chunks' offsets and the total
 KPX_EXPORT size_t kpx_tsdf_workspace_bytes(int32_t resolution)
 {
     if (!tsdf_res_ok(resolution)) return 0;
     Arena a(nullptr, 0);
-    a.get<int64_t>((size_t)tsdf_chunks(resolution) + 1);
+    tsdf_carve(a, tsdf_chunks(resolution));
     return a.off;
 }
 
@@ -155,7 +156,7 @@ KPX_EXPORT int kpx_tsdf_extract_count(const float *volume, int32_t resolution, i
     KPX_REQUIRE(volume && d_count && ws, "kpx_tsdf_extract_count: null pointer");
     const int64_t nchunks = tsdf_chunks(resolution);
     Arena a(ws, ws_bytes);
-    int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
+    int64_t *offsets = tsdf_carve(a, nchunks);
     KPX_ARENA_CHECK(a);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(tsdf_count_kernel<UniformView>, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
@@ -176,7 +177,7 @@ KPX_EXPORT int kpx_tsdf_extract_fill(const float *volume, const float *color, in
     KPX_REQUIRE(volume && h_origin && pts && ws, "kpx_tsdf_extract_fill: null pointer");
     const int64_t nchunks = tsdf_chunks(resolution);
     Arena a(ws, ws_bytes);
-    const int64_t *offsets = a.get<int64_t>((size_t)nchunks + 1);
+    const int64_t *offsets = tsdf_carve(a, nchunks);
     KPX_ARENA_CHECK(a);
     const TsdfFillArgs f = { pts, mode == KPX_TSDF_SURFACE ? nrm : nullptr, col, total };
     hipStream_t st = (hipStream_t)stream;

@@ -363,8 +363,7 @@ __global__ __launch_bounds__(64) void fuse_bbox_final_kernel(const double *__res
 #pragma unroll
         for (int a = 0; a < 3; ++a) { v[a] = fmin(v[a], part[(int64_t)r * 6 + a]); v[3 + a] = fmax(v[3 + a], part[(int64_t)r * 6 + 3 + a]); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { v[a] = wave_min(v[a]); v[3 + a] = wave_max(v[3 + a]); }
+    box_wave_fold(v, v + 3);
     if (lane == 0) {
         for (int a = 0; a < 6; ++a) bbox[a] = v[a];
         *err = 0;

@@ -4,7 +4,7 @@ INTEGRATION.md promises that the switches never change results.  FAMILIES lists,
 is compared with the family's default child; FLIPPED_ELSEWHERE the names an existing test already flips; EXEMPT the names that select
 no kernel form.  tests/test_switches_cpu.py holds the three lists against the names the sources read.
 
-The functions below restate the library's dispatch conditions (kpx_knn.hip kpx_sor / grid_build, kpx_misc.hip bbox_f32, kpx_icp.hip
+The functions below restate the library's dispatch conditions (kpx_knn.hip kpx_sor / grid_build, kpx_container.hip bbox_f32, kpx_icp.hip
 nn_search_launch, kpx_fps.hip fps_use_block); the GPU test asserts from them that each input sits on the side where its switch
 matters.  They must be moved with the library's.  The inputs are built here, from NumPy alone, so that the children, the parent's
 oracle runs and the CPU precondition see the same arrays."""
@@ -20,7 +20,7 @@ _define = lambda name: int(re.search(r"#define\s+%s\s+(\d+)" % name, _HEADER).gr
 FPS_BLOCK_MAX_N, FPS_BATCH_BLOCK_MAX_N, FPS_BATCH_MIN_CLOUDS = _define("KPX_FPS_BLOCK_MAX_N"), _define("KPX_FPS_BATCH_BLOCK_MAX_N"), _define("KPX_FPS_BATCH_MIN_CLOUDS")
 FPS_REG_N, FPS_LDS_N = _define("KPX_FPS_REG_N"), _define("KPX_FPS_LDS_N")
 GRID_SORT_MIN = 65536                     # kpx_knn.hip grid_build: the radix-sort build above 65536 points, the counting build up to there
-BBOX_SMALL_MAX = 65536                    # kpx_misc.hip bbox_f32: one block up to 65536 points, partial boxes (vector / scalar loads) above
+BBOX_SMALL_MAX = 65536                    # kpx_container.hip bbox_f32: one block up to 65536 points, partial boxes (vector / scalar loads) above
 VOXEL_READBACK_MIN = 128 * 1024           # kpx_voxel.hip voxel_batch_impl: the key width is read back above 131072 points
 ICP_CHAIN_BLOCKS = 512                    # the one-launch ICP chain's budget on the MI355X: (blocks per CU - 1) x CUs
 

@@ -175,6 +175,30 @@ def test_transform_rotate_bit_exact(ops, oracle, base_cloud):
     assert np.array_equal(npy(t), oracle.transform(base_cloud[:1000], T))
 
 
+def test_transform_rotate_every_form(ops, oracle):
+    """Each form of kpx_transform / kpx_rotate at the smallest sizes that reach it, bit for bit against the oracle: the scalar loop alone
+    (n < 4, or a view that starts 12 bytes in and so is not 16-byte aligned), the vector loop with every n % 4 tail, transform's LDS
+    kernel alone (65536 aligned points) and with its one-block tail launch; out of place and in place."""
+    T = synth.t_star()
+    sizes = (1, 3, 4, 5, 255, 256, 257, 65535, 65536, 65536 + 3, 65536 + 255, 65536 + 256 + 1)
+    host = (np.random.default_rng(11).standard_normal((max(sizes) + 1, 3)) * 700.0).astype(np.float32)
+    dev = torch.as_tensor(host).cuda()
+    assert dev.data_ptr() % 16 == 0
+    for name in ("transform", "rotate"):
+        op, ref = getattr(ops, name), getattr(oracle, name)
+        for first in (0, 1):
+            for n in sizes:
+                want = ref(host[first:first + n], T)
+                view = dev[first:first + n]
+                assert view.data_ptr() == dev.data_ptr() + 12 * first
+                assert np.array_equal(npy(op(view, T)), want), (name, first, n, "out of place")
+                work = dev.clone()
+                view = work[first:first + n]
+                assert work.data_ptr() % 16 == 0 and op(view, T, out=view) is view
+                assert np.array_equal(npy(view), want), (name, first, n, "in place")
+                assert np.array_equal(npy(work[first + n:]), host[first + n:]) and np.array_equal(npy(work[:first]), host[:first]), (name, first, n, "wrote outside the view")
+
+
 def test_joints_affine_reference_kat():
     from kinectpy_amd.preprocessing.extractor import transform_joint_rows
     for c in KAT["transform_joints"]:
