@@ -1154,6 +1154,42 @@ int kpx_pointnet_forward(const float *weights, int64_t weights_floats, const flo
 int kpx_joint_metrics(const float *y_true, const float *y_pred, int64_t n, const double *h_thresholds, int32_t n_thresholds, int64_t *d_counts,
                       double *d_sum_sq, void *stream);
 
+/* ---- PointNet joint regression, training (arithmetic contract AC19) ------------------------------------------------------
+ * One step of train.py's model.fit on create_pointnet: batch normalisation on the batch statistics (epsilon 1e-3, momentum 0: the moving
+ * statistics become the step's batch statistics), Dropout(0.3) behind the two main-head dense_bn blocks, loss = the mean squared error
+ * plus the two OrthogonalRegularizer terms divided by the batch size, gradients of the 74 trainable arrays, Adam.
+ * params: the parameter buffer, f32, 16-byte aligned, every array starting at a multiple of 64 floats (gaps are zero and stay zero):
+ *     the TRAINABLE part first -- for layer 0, 1, ..., 19 (numbered as above) its kernel [c_in][c_out] row-major, its bias [c_out] and,
+ *     for the 17 layers with batch normalisation (all but 5, 13, 19), gamma [c_out] and beta [c_out] -- then, for the same 17 layers in
+ *     order, moving_mean [c_out] and moving_variance [c_out].  kpx_pointnet_train_floats gives the length of the buffer (*total) and of its
+ *     trainable part (*trainable); grad, m and v have the trainable part's layout.
+ * kpx_pointnet_grad: x f32 [batch][n][3], y f32 [batch][3 joints] -> loss f32 [3] on the device (total, mean squared error,
+ *     regulariser), grad, and the moving statistics written into params.  training_dropout 0 leaves dropout out; otherwise the element
+ *     (row, channel) of dropout layer d (0: behind 512 -> 256, 1: behind 256 -> 128) is kept iff (h >> 8) < 11744051 with
+ *     h = mix(mix(mix(mix(seed) ^ step) ^ d) ^ (512 row + channel)) in 32-bit arithmetic (seed and step taken modulo 2^32),
+ *     mix(x): x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16; kept values are multiplied by fl32(1 / 0.7).
+ *     Optional stage outputs (NULL = not wanted): T3 [batch][9], T32 [batch][1024], g1 / g2 / g3 f32 [batch][512] the pooled
+ *     activations with i1 / i2 / i3 i32 [batch][512] the pooled points, out [batch][3 joints].  The pooled point of (cloud, channel) is the
+ *     one with the largest sign(gamma) z, the lowest index among equal z; where the pooled activation is 0 (no gradient) index 0.
+ * kpx_adam_step: m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, w -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps), t >= 1,
+ *     evaluated in fp64 on the f32 inputs, each stored value rounded once.  One launch.
+ * kpx_pointnet_train_step: kpx_pointnet_grad, then kpx_adam_step over the trainable part; the same bits as the two calls.
+ * Arithmetic: f32 storage, f32 products and fused multiply-adds in the point-wise layers; every sum over points or rows is per-block
+ *     partial sums in a fixed order, combined in ascending order in fp64, and the B-row sums of the heads are taken in fp64; no
+ *     floating-point atomics: two runs give the same bits, whatever the workspace held.  joints, n and batch are checked as for kpx_pointnet_forward, the buffer
+ *     length and the workspace size before the device is touched; batch = 0 clears loss and grad and does nothing else.
+ *     Asynchronous on `stream`, no host read-back. */
+int kpx_pointnet_train_floats(int32_t joints, int64_t *total, int64_t *trainable);
+size_t kpx_pointnet_train_workspace_bytes(int32_t batch, int64_t n, int32_t joints);
+int kpx_pointnet_grad(float *params, int64_t params_floats, const float *x, const float *y, int32_t batch, int64_t n, int32_t joints, uint64_t seed,
+                      uint64_t step, int32_t training_dropout, float *loss, float *grad, float *T3, float *T32, float *g1, int32_t *i1, float *g2,
+                      int32_t *i2, float *g3, int32_t *i3, float *out, void *ws, size_t ws_bytes, void *stream);
+int kpx_adam_step(float *w, const float *g, float *m, float *v, int64_t count, double lr, double beta1, double beta2, double eps, int64_t t,
+                  void *stream);
+int kpx_pointnet_train_step(float *params, int64_t params_floats, const float *x, const float *y, int32_t batch, int64_t n, int32_t joints,
+                            uint64_t seed, uint64_t step, int32_t training_dropout, float *loss, float *grad, float *m, float *v, double lr,
+                            double beta1, double beta2, double eps, int64_t t, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,12 @@ SIGNATURES = {
     "kpx_pointnet_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "kpx_pointnet_forward": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_joint_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "kpx_pointnet_train_floats": (C.c_int, [_i32, _vp, _vp]),
+    "kpx_pointnet_train_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "kpx_pointnet_grad": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _u64, _u64, _i32, _vp, _vp] + [_vp] * 9 + [_vp, _sz, _vp]),
+    "kpx_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "kpx_pointnet_train_step": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _u64, _u64, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i64,
+                                          _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2166,3 +2166,160 @@ def joint_metrics(y_true, y_pred, thresholds):
     total = torch.zeros(1, dtype=torch.float64, device=yt.device)
     L.check(lib.kpx_joint_metrics(L.ptr(yt), L.ptr(yp), int(yt.numel()), L.hptr(thr), int(thr.size), L.ptr(counts), L.ptr(total), L.stream_ptr()))
     return counts[:thr.size], total, int(yt.numel())
+
+
+# ---- PointNet joint regression, training (AC19) ------------------------------------------------------------------------------
+_PN_CONV_LAYERS = (0, 1, 2, 6, 7, 8, 9, 10, 14, 15, 16)          # Conv1D blocks: Keras kernels (1, c_in, c_out)
+_PN_KERAS = ("kernel", "bias", "gamma", "beta", "moving_mean", "moving_variance")
+DROPOUT_RATE = 0.3
+_PN_KEEP_BELOW = 11744051                # floor(0.7 2^24)
+
+
+def pointnet_train_layout(joints):
+    """-> (slots, trainable, total): slots = (offset, shape) of the 108 arrays in Keras' get_weights() order inside the training parameter
+    buffer (include/kinectpx.h: the trainable arrays of all layers first, then the moving statistics), trainable / total in floats"""
+    pad = lambda v: -(-v // _PN_PAD) * _PN_PAD
+    shapes = pointnet_layer_shapes(joints)
+    per, off = [], 0
+    for l, (ci, co, bn) in enumerate(shapes):
+        d = {"kernel": (off, (1, ci, co) if l in _PN_CONV_LAYERS else (ci, co))}
+        off += pad(ci * co)
+        for q in _PN_KERAS[1:4] if bn else _PN_KERAS[1:2]:
+            d[q] = (off, (co,))
+            off += pad(co)
+        per.append(d)
+    trainable = off
+    for d, (ci, co, bn) in zip(per, shapes):
+        for q in _PN_KERAS[4:] if bn else ():
+            d[q] = (off, (co,))
+            off += pad(co)
+    slots = [d[q] for d, (_, _, bn) in zip(per, shapes) for q in (_PN_KERAS if bn else _PN_KERAS[:2])]
+    return slots, trainable, off
+
+
+_pn_train_sizes = {}
+
+
+def _pn_train_joints_of(floats):
+    if not _pn_train_sizes:
+        for j in range(1, POINTNET_MAX_OUT // 3 + 1):
+            _pn_train_sizes[pointnet_train_layout(j)[2]] = j
+    if floats not in _pn_train_sizes:
+        raise ValueError(f"a buffer of {floats} floats is not a PointNet training parameter buffer")
+    return _pn_train_sizes[floats]
+
+
+def pointnet_train_pack_host(weights):
+    """the 108 Keras-ordered arrays -> the float32 parameter buffer as a NumPy array"""
+    weights = list(weights)
+    if len(weights) != POINTNET_WEIGHT_ARRAYS:
+        raise ValueError(f"pointnet_train_pack: expected {POINTNET_WEIGHT_ARRAYS} weight arrays, got {len(weights)}")
+    last = np.asarray(weights[-1])
+    if last.ndim != 1 or last.size % 3 or not 1 <= last.size // 3 or last.size > POINTNET_MAX_OUT:
+        raise ValueError(f"pointnet_train_pack: array {POINTNET_WEIGHT_ARRAYS - 1} (the output bias) has shape {last.shape}: expected (3 joints,) with "
+                         f"3 joints <= {POINTNET_MAX_OUT}")
+    slots, _, total = pointnet_train_layout(last.size // 3)
+    buf = np.zeros(total, np.float32)
+    for i, (a, (off, shape)) in enumerate(zip(weights, slots)):
+        a = np.asarray(a)
+        if a.shape != shape and a.shape != shape[-2:]:
+            raise ValueError(f"pointnet_train_pack: array {i} has shape {a.shape}: expected {shape}")
+        buf[off:off + a.size] = a.astype(np.float32).reshape(-1)
+    return buf
+
+
+def pointnet_train_pack(weights):
+    """the 108 Keras-ordered arrays -> the device parameter buffer of pointnet_grad / pointnet_train_step (layout: include/kinectpx.h)"""
+    return _dev(pointnet_train_pack_host(weights), torch.float32)
+
+
+def pointnet_train_unpack(buffer, joints):
+    """the parameter buffer (device tensor or NumPy) -> the 108 arrays in Keras' get_weights() order"""
+    slots, _, total = pointnet_train_layout(joints)
+    buf = buffer.detach().cpu().numpy() if isinstance(buffer, torch.Tensor) else np.asarray(buffer)
+    if buf.dtype != np.float32 or buf.shape != (total,):
+        raise ValueError(f"pointnet_train_unpack: expected a float32 buffer of {total} floats for {joints} joints, got {buf.dtype} {buf.shape}")
+    return [buf[off:off + int(np.prod(shape))].reshape(shape).copy() for off, shape in slots]
+
+
+def _pn_mix(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def pointnet_dropout_masks(seed, step, B):
+    """the keep masks of one training step on the host: (bool (B, 256), bool (B, 128)) -- the counter-based generator of AC19"""
+    with np.errstate(over="ignore"):
+        base = _pn_mix(np.uint32(int(seed) & 0xFFFFFFFF)) ^ np.uint32(int(step) & 0xFFFFFFFF)
+        out = []
+        for layer, width in enumerate((256, 128)):
+            cell = (np.arange(B, dtype=np.uint32)[:, None] * np.uint32(512) + np.arange(width, dtype=np.uint32)[None, :]).astype(np.uint32)
+            h = _pn_mix(_pn_mix(_pn_mix(base) ^ np.uint32(layer)) ^ cell)
+            out.append((h >> np.uint32(8)) < np.uint32(_PN_KEEP_BELOW))
+    return tuple(out)
+
+
+def _pn_train_args(who, params, x, y):
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous() and params.ndim == 1):
+        raise ValueError(f"{who}: params must be the float32 device buffer of pointnet_train_pack")
+    joints = _pn_train_joints_of(int(params.numel()))
+    x, y = _dev(x, torch.float32), _dev(y, torch.float32)
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError(f"{who}: x must be (B, N, 3), got {tuple(x.shape)}")
+    if tuple(y.shape) != (x.shape[0], 3 * joints):
+        raise ValueError(f"{who}: y must be ({x.shape[0]}, {3 * joints}), got {tuple(y.shape)}")
+    return joints, x, y, int(x.shape[0]), int(x.shape[1])
+
+
+def pointnet_grad(params, x, y, seed=0, step=0, training_dropout=True, want_stages=False):
+    """one train-mode forward and backward of create_pointnet (AC19) -> (loss f32 (3): total, mean squared error, regulariser; grad f32 in
+    the trainable layout), both on the device; the moving statistics inside `params` are overwritten with the batch statistics.
+    want_stages: also a dict T3, T32, g1..g3 (pooled activations), i1..i3 (pooled point indices, int32), out.  No host read-back."""
+    lib = L.load()
+    joints, x, y, B, N = _pn_train_args("pointnet_grad", params, x, y)
+    trainable = pointnet_train_layout(joints)[1]
+    loss = torch.empty(3, dtype=torch.float32, device=x.device)
+    grad = torch.empty(trainable, dtype=torch.float32, device=x.device)
+    st = None
+    if want_stages:
+        new = lambda dt, *s: torch.empty((B,) + s, dtype=dt, device=x.device)
+        st = {"T3": new(torch.float32, 3, 3), "T32": new(torch.float32, 32, 32), "out": new(torch.float32, 3 * joints)}
+        for t in "123":
+            st["g" + t], st["i" + t] = new(torch.float32, 512), new(torch.int32, 512)
+    ws, wsz = L.workspace(lib.kpx_pointnet_train_workspace_bytes(B, N, joints)) if B and N else (None, 0)
+    sp = [L.ptr(st[k]) if st else None for k in ("T3", "T32", "g1", "i1", "g2", "i2", "g3", "i3", "out")]
+    L.check(lib.kpx_pointnet_grad(L.ptr(params), int(params.numel()), L.ptr(x), L.ptr(y), B, N, joints, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                  int(bool(training_dropout)), L.ptr(loss), L.ptr(grad), *sp, ws, wsz, L.stream_ptr()))
+    return (loss, grad, st) if want_stages else (loss, grad)
+
+
+def adam_step(w, g, m, v, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, t=1):
+    """Adam's update of the float32 device vectors w, m, v in place from the gradient g (AC19): step number t >= 1.  One launch."""
+    lib = L.load()
+    for name, a in (("w", w), ("g", g), ("m", m), ("v", v)):
+        if not (isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.is_cuda and a.is_contiguous() and a.numel() == w.numel()):
+            raise ValueError(f"adam_step: {name} must be a contiguous float32 device tensor of w's length")
+    L.check(lib.kpx_adam_step(L.ptr(w), L.ptr(g), L.ptr(m), L.ptr(v), int(w.numel()), float(learning_rate), float(beta_1), float(beta_2), float(epsilon), int(t),
+                              L.stream_ptr()))
+    return w
+
+
+def pointnet_train_step(params, x, y, m, v, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, t=1, seed=0, step=0, training_dropout=True):
+    """pointnet_grad followed by adam_step over the trainable part of `params` (m, v: float32 device vectors of that length), chained on
+    the stream -> (loss (3), grad)"""
+    lib = L.load()
+    joints, x, y, B, N = _pn_train_args("pointnet_train_step", params, x, y)
+    trainable = pointnet_train_layout(joints)[1]
+    for name, a in (("m", m), ("v", v)):
+        if not (isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.is_cuda and a.is_contiguous() and a.numel() == trainable):
+            raise ValueError(f"pointnet_train_step: {name} must be a contiguous float32 device tensor of {trainable} floats")
+    loss = torch.empty(3, dtype=torch.float32, device=x.device)
+    grad = torch.empty(trainable, dtype=torch.float32, device=x.device)
+    ws, wsz = L.workspace(lib.kpx_pointnet_train_workspace_bytes(B, N, joints)) if B and N else (None, 0)
+    L.check(lib.kpx_pointnet_train_step(L.ptr(params), int(params.numel()), L.ptr(x), L.ptr(y), B, N, joints, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                        int(bool(training_dropout)), L.ptr(loss), L.ptr(grad), L.ptr(m), L.ptr(v), float(learning_rate), float(beta_1),
+                                        float(beta_2), float(epsilon), int(t), ws, wsz, L.stream_ptr()))
+    return loss, grad

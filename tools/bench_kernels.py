@@ -59,8 +59,11 @@ def main():
     ap.add_argument("--odometry", action="store_true", help="only the RGB-D odometry rows")
     ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
     ap.add_argument("--pointnet", action="store_true", help="only the PointNet forward rows (fused against eval-mode torch modules)")
+    ap.add_argument("--pointnet-train", action="store_true", help="only the PointNet training step rows (against train-mode torch modules with torch.optim.Adam)")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    if a.pointnet_train:
+        return pointnet_train_rows(dev, a.quick)
     if a.pointnet:
         return pointnet_rows(dev, a.quick)
     if a.tsdf:
@@ -850,6 +853,55 @@ def pointnet_rows(dev, quick):
             report(f"pointnet forward {name} (B, N, J) = ({B}, {N}, {J})", med[name], ms_range=[round(min(ts[name]), 4), round(max(ts[name]), 4)],
                    windows=windows, calls_per_window=calls, fp32_floor_ms=round(floor, 4), TFLOPs_fp32=round(B * N * POINTNET_FLOP_PER_POINT / med[name] / 1e9, 2),
                    torch_over_fused=round(med["torch"] / med["fused"], 3), fused_vs_torch_max_rel=dev_rel)
+
+
+def pointnet_train_rows(dev, quick):
+    """PointNet training step: ops.pointnet_train_step against the same model as train-mode torch modules with
+    torch.optim.Adam (tests/pointnet_train_ref.torch_modules), same device, same process, windows of `calls` steps between two events, the
+    two alternating window by window; median and range over the windows."""
+    from tests import pointnet_train_ref as T
+    windows, calls = (5, 10) if quick else (15, 30)
+    for B, N, J in ((16, 1024, 32), (32, 4096, 32)):
+        w = T.train_weights(J)
+        params = ops.pointnet_train_pack(w)
+        n = ops.pointnet_train_layout(J)[1]
+        m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        net, loss_fn = T.torch_modules(w, dev)
+        opt = torch.optim.Adam(net.parameters(), lr=0.005, eps=1e-7)
+        x = torch.as_tensor(T.R.make_clouds(B, N, T.R.UNIT, 1)).to(dev)
+        y = torch.as_tensor(np.random.default_rng(1).normal(0, 0.3, (B, 3 * J)).astype(np.float32)).to(dev)
+        count = {"t": 0}
+
+        def ours():
+            count["t"] += 1
+            return ops.pointnet_train_step(params, x, y, m, v, learning_rate=0.005, t=count["t"], step=count["t"])[0]
+
+        def theirs():
+            opt.zero_grad(set_to_none=True)
+            loss = loss_fn(*net(x), y)
+            loss.backward()
+            opt.step()
+            return loss
+
+        forms = {"kinectpx": ours, "torch": theirs}
+        for fn in forms.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        ts = {k: [] for k in forms}
+        for _ in range(windows):
+            for name, fn in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1) / calls)
+        med = {k: float(np.median(t)) for k, t in ts.items()}
+        for name in forms:
+            report(f"pointnet train step {name} (B, N, J) = ({B}, {N}, {J})", med[name], ms_range=[round(min(ts[name]), 4), round(max(ts[name]), 4)],
+                   windows=windows, calls_per_window=calls, torch_over_kinectpx=round(med["torch"] / med["kinectpx"], 3))
 
 
 if __name__ == "__main__":
