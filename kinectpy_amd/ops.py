@@ -2,6 +2,9 @@
 
 Inputs/outputs are torch-ROCm tensors (device memory containers).  Functions that produce a
 data-dependent number of rows read the device count (one host sync) and return trimmed views.
+Where a function hands back a padded buffer with its count instead, the rows at and beyond the
+count are unspecified ("carved scratch": the contract tests/test_scratch_gpu.py holds
+every operator to).
 """
 import ctypes as C
 
@@ -74,7 +77,7 @@ def median_i16(v, n, stride, frames=1):
 def rgbd_compact(xyz, rgb=None, frames=1, color_mask=False, depth_gate=False, gate=GATE_MM, want_idx=True, sync=True):
     """a3 (+a4).  xyz int16 [frames, n, 3]; rgb u8 [frames, n, 3] or None.
     Returns per-frame lists (points f32 (K,3), colours f32 (K,3)|None, idx i32 (K)|None) or, with sync=False, the padded buffers
-    and the device count tensor (no host round trip)."""
+    and the device count tensor (no host round trip).  The rows of a padded buffer at and beyond its frame's count are unspecified."""
     lib = L.load()
     xyz = _dev(xyz, torch.int16).reshape(frames, -1, 3)
     n = xyz.shape[1]
@@ -99,7 +102,7 @@ def rgbd_compact(xyz, rgb=None, frames=1, color_mask=False, depth_gate=False, ga
 def depth_to_cloud(depth, xy_table, rgb=None, frames=1, color_mask=False, depth_gate=False, gate=GATE_MM,
                    want_idx=False, sync=True):
     """Fused a1+a3+a4.  Returns per-frame (points, colours|None, idx|None) or, with sync=False,
-    the padded buffers and the device count tensor."""
+    the padded buffers and the device count tensor.  The rows of a padded buffer at and beyond its frame's count are unspecified."""
     lib = L.load()
     depth = _dev(depth, torch.uint16).reshape(frames, -1)
     n = depth.shape[1]
@@ -1407,7 +1410,8 @@ def mesh_adjacency(vertices, triangles):
 
 
 def _mesh_adjacency(vert, tri):
-    """-> (offsets, neighbours with room for 6 T entries, their number int32 (1,) on the device): no host read"""
+    """-> (offsets, neighbours with room for 6 T entries, their number int32 (1,) on the device): no host read.  The entries of
+    `neighbours` at and beyond that number are unspecified."""
     lib = L.load()
     nv, nt = vert.shape[0], tri.shape[0]
     off = torch.empty(nv + 1, dtype=torch.int32, device=vert.device)
