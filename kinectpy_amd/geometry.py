@@ -135,7 +135,14 @@ class OrientedBoundingBox:
 class PointCloud:
     """Covariances (`covariances`, estimate_covariances, generalized ICP) are an fp64 (N,3,3) device tensor `_cov`.  transform()
     rotates them, deepcopy / clone() and `+` carry them; every other method returns a cloud WITHOUT covariances -- unlike Open3D,
-    whose select_by_index (and the filters built on it) keeps them."""
+    whose select_by_index (and the filters built on it) keeps them.
+
+    State.  Copied on entry: whatever the constructor or a setter (points, colors, normals, covariances) is given as a
+    Vector3dVector / Matrix3dVector -- another cloud's property included -- and every host array; a bare torch.Tensor of the stored
+    dtype, device and layout is adopted without a copy and written in place from then on.  In place, returning self: transform,
+    estimate_normals, estimate_covariances, normalize_normals, the three orient_normals_*, `+=` (and utils.processing's
+    normalize_pointcloud).  Every other method that returns a cloud (`+`, copy / deepcopy / clone, select_by_index, the down-samplers
+    and outlier filters) returns a new one that shares no storage with this cloud or with the other operand."""
     _cov = None
     # _bounds: the cloud's min / max as a float64[6] DEVICE tensor once some kernel has computed them (the gather that produced the
     # cloud, or the first get_*_bound / remove_floor); dropped whenever the points change
@@ -153,7 +160,7 @@ class PointCloud:
         self._bounds = None
 
     def __init__(self, points=None):
-        self._pts = Vector3dVector(points).t
+        self._pts = _taken(points, Vector3dVector)
         self._col = None
         self._nrm = None
         self._cov = None
@@ -165,7 +172,7 @@ class PointCloud:
 
     @points.setter
     def points(self, v):
-        self._pts = Vector3dVector(v).t
+        self._pts = _taken(v, Vector3dVector)
 
     @property
     def colors(self):
@@ -173,7 +180,7 @@ class PointCloud:
 
     @colors.setter
     def colors(self, v):
-        t = Vector3dVector(v).t
+        t = _taken(v, Vector3dVector)
         self._col = t if t.shape[0] else None
 
     @property
@@ -182,7 +189,7 @@ class PointCloud:
 
     @normals.setter
     def normals(self, v):
-        t = Vector3dVector(v).t
+        t = _taken(v, Vector3dVector)
         self._nrm = t if t.shape[0] else None
 
     @property
@@ -191,7 +198,7 @@ class PointCloud:
 
     @covariances.setter
     def covariances(self, v):
-        t = Matrix3dVector(v).t
+        t = _taken(v, Matrix3dVector)
         self._cov = t if t.shape[0] else None
 
     def has_covariances(self):
@@ -416,13 +423,15 @@ class PointCloud:
         both_v = self.has_covariances() and other.has_covariances()
         if not self.has_points():
             both_c, both_n, both_v = other.has_colors(), other.has_normals(), other.has_covariances()
+        # an empty cloud takes the other's attributes over: as copies, like the concatenations (the sum shares nothing with its operands)
         pc = PointCloud._make(torch.cat([self._pts, other._pts], 0),
-                              torch.cat([self._col, other._col], 0) if both_c and self.has_points() else (other._col if both_c else None),
-                              torch.cat([self._nrm, other._nrm], 0) if both_n and self.has_points() else (other._nrm if both_n else None))
-        pc._cov = torch.cat([self._cov, other._cov], 0) if both_v and self.has_points() else (other._cov if both_v else None)
+                              torch.cat([self._col, other._col], 0) if both_c and self.has_points() else (other._col.clone() if both_c else None),
+                              torch.cat([self._nrm, other._nrm], 0) if both_n and self.has_points() else (other._nrm.clone() if both_n else None))
+        pc._cov = torch.cat([self._cov, other._cov], 0) if both_v and self.has_points() else (other._cov.clone() if both_v else None)
         return pc
 
     def __iadd__(self, other):
+        """in place -> self; `other` is left as it is and shares nothing with the result"""
         r = self + other
         self._pts, self._col, self._nrm, self._cov, self._bounds = r._pts, r._col, r._nrm, r._cov, None
         return self
@@ -436,7 +445,8 @@ class KDTreeFlann:
     set_geometry and never per query.  The three *_vector_3d searches take ONE query point and return Open3D's
     (count, indices, squared distances); search_knn / search_radius / search_hybrid take (M,3) queries -- the library's
     extension -- and return device tensors (ops.search_*).  Rows ascend in (d2, index): on equal distances the lowest index comes
-    first (Open3D leaves the order of ties open).  Coordinates are float32 storage: float64 input is rounded on entry."""
+    first (Open3D leaves the order of ties open).  Coordinates are float32 storage: float64 input is rounded on entry.  The index is
+    self-contained: it answers for the points as they were at set_geometry, whatever happens to the cloud afterwards."""
 
     def __init__(self, geometry=None):
         self._index = None
@@ -515,10 +525,10 @@ class ImageFilterType(enum.Enum):
 
 class Image:
     """o3d.geometry.Image stand-in: wraps a host ndarray -- uint8 (H, W, 3) colour, uint16 or float32 (H, W) depth / intensity.
-    np.asarray(image) gives the array back."""
+    np.asarray(image) gives the array back.  Image(other_image) copies the array; a contiguous ndarray is wrapped as it is."""
 
     def __init__(self, data=None):
-        a = np.zeros((0, 0), np.uint8) if data is None else np.ascontiguousarray(data.data if isinstance(data, Image) else data)
+        a = np.zeros((0, 0), np.uint8) if data is None else (data.data.copy() if isinstance(data, Image) else np.ascontiguousarray(data))
         if a.ndim == 3 and a.shape[2] == 1:
             a = a[:, :, 0]
         if not ((a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8) or (a.ndim == 2 and a.dtype in (np.uint8, np.uint16, np.float32))):
@@ -888,6 +898,17 @@ class Vector3iVector:
         return np.asarray(self)[i]
 
 
+def _taken(v, wrap, device=None):
+    """The tensor a constructor or setter of PointCloud / TriangleMesh stores for `v`.  A wrapper -- what another
+    geometry's property hands out -- is copied, so no two geometries share storage (once: a wrapper of host triangles that moving to
+    `device` has copied already is not copied again); a host array becomes a new device tensor anyway; a bare torch.Tensor is
+    ADOPTED: when it already has the dtype, device and layout the object keeps, the object works in it, in place, without a copy."""
+    t = wrap(v).t
+    if device is not None:
+        t = t.to(device)
+    return t.clone() if isinstance(v, (Vector3dVector, Matrix3dVector, Vector3iVector)) and t is v.t else t
+
+
 class FilterScope(enum.Enum):
     """[O3D] geometry.FilterScope: the arrays a TriangleMesh.filter_smooth_* call filters"""
     All = 0
@@ -908,14 +929,23 @@ class TriangleMesh:
     hierarchy), is_orientable / orient_triangles, get_volume and euler_poincare_characteristic; watertightness is
     ops.mesh_is_watertight(vertices, triangles) on the mesh's arrays.
     Not built: remove_duplicated_vertices, remove_duplicated_triangles, the simplification methods, is_watertight as a method (the
-    clean-up suite holds the class to not having it), sample_points_poisson_disk, crop, is_bounding_box_intersecting."""
+    clean-up suite holds the class to not having it), sample_points_poisson_disk, crop, is_bounding_box_intersecting.
+
+    State.  Copied on entry: whatever the constructor or a setter (vertices, triangles, vertex_colors, vertex_normals,
+    triangle_normals) is given as a Vector3dVector / Vector3iVector -- another mesh's property included -- and every host array; a
+    bare torch.Tensor of the stored dtype, device and layout is adopted without a copy and written in place from then on.  In place,
+    returning self: transform, compute_triangle_normals, compute_vertex_normals, compute_adjacency_list and the remove_* family;
+    orient_triangles rewrites the triangles in place and returns whether it could; sample_points_uniformly(use_triangle_normal=True)
+    fills missing triangle normals.  copy / deepcopy, select_by_index and filter_smooth_* return a new mesh, sample_points_uniformly a
+    new cloud, that share no storage with this mesh.  Cached answers (the bounds, the adjacency list) are dropped by whatever changes
+    the arrays they were computed from."""
     _bounds = None
     _adj = None               # (offsets, neighbours) device tensors: compute_adjacency_list's CSR
     _adj_sets = None          # the same as Python sets, built on first use of adjacency_list
 
     def __init__(self, vertices=None, triangles=None):
-        self._vert = Vector3dVector(vertices).t
-        self._tri = Vector3iVector(triangles).t.to(L.device())
+        self._vert = _taken(vertices, Vector3dVector)
+        self._tri = _taken(triangles, Vector3iVector, L.device())
         self._vcol = self._vnrm = self._tnrm = None
 
     @classmethod
@@ -931,7 +961,7 @@ class TriangleMesh:
 
     @vertices.setter
     def vertices(self, v):
-        self._vert, self._bounds = Vector3dVector(v).t, None
+        self._vert, self._bounds = _taken(v, Vector3dVector), None
 
     @property
     def triangles(self):
@@ -939,7 +969,7 @@ class TriangleMesh:
 
     @triangles.setter
     def triangles(self, v):
-        self._tri = Vector3iVector(v).t.to(L.device())
+        self._tri = _taken(v, Vector3iVector, L.device())
         self._adj = self._adj_sets = None
 
     def _optional(name):
@@ -948,7 +978,7 @@ class TriangleMesh:
             return Vector3dVector(t if t is not None else None)
 
         def put(self, v):
-            t = Vector3dVector(v).t
+            t = _taken(v, Vector3dVector)
             setattr(self, name, t if t.shape[0] else None)
         return property(get, put)
 
@@ -1188,7 +1218,9 @@ class RaycastingScene:
     dimension is 6 (rays: origin, direction; directions are not normalised, t_hit is in units of |d|) or 3 (points); leading
     dimensions are preserved.  Results are NumPy arrays in Open3D's dtypes -- the uint32 ids are the device's int32 viewed, so -1 reads
     as INVALID_ID -- or, with device=True, the device tensors of ops.rayscene_*.  The index is built on the first query and rebuilt
-    after a later add_triangles.  Shape and dtype errors raise before the device is touched.
+    after a later add_triangles, both from the copies add_triangles took: the scene answers for every geometry as it was when it was
+    handed over, whatever happens to the mesh or the tensors afterwards.  Nothing works in place on a scene.
+    Shape and dtype errors raise before the device is touched.
     Deviations: compute_occupancy / compute_signed_distance cast ONE ray per point (nsamples = 1 only) in the fixed direction
     (1, 0.375, 0.3125) -- marching-cubes meshes are full of axis-aligned edges, which a ray along +x would graze; a ray through an edge
     shared by two triangles counts both.  Not built: list_intersections, nsamples > 1, line sets, t.geometry tensors."""
@@ -1196,16 +1228,18 @@ class RaycastingScene:
     OCCUPANCY_DIRECTION = (1.0, 0.375, 0.3125)
 
     def __init__(self):
-        self._geoms = []              # (vertices, triangles): host arrays, or a TriangleMesh's device tensors
+        self._geoms = []              # (vertices, triangles): host arrays or device tensors, copies made by add_triangles
         self._scene = None
 
     # ---- geometries ---------------------------------------------------------------------------
     def add_triangles(self, vertex_positions, triangle_indices=None):
-        """(vertex_positions float (V, 3), triangle_indices integer (T, 3)), or one TriangleMesh -> the geometry id"""
+        """(vertex_positions float (V, 3), triangle_indices integer (T, 3)), or one TriangleMesh -> the geometry id.  The scene keeps
+        a copy made here, of host arrays, of device tensors and of a mesh's arrays alike: what the caller does to them afterwards
+        (TriangleMesh.transform works in place) does not reach the scene, whenever its index is built or rebuilt."""
         if isinstance(vertex_positions, TriangleMesh):
             if triangle_indices is not None:
                 raise RuntimeError("RaycastingScene.add_triangles: a TriangleMesh brings its own triangles")
-            pair = (vertex_positions._vert, vertex_positions._tri)
+            pair = (vertex_positions._vert.clone(), vertex_positions._tri.clone())
         else:
             v, t = vertex_positions, triangle_indices
             if t is None:
@@ -1228,6 +1262,8 @@ class RaycastingScene:
                 if not np.isfinite(v).all():
                     raise RuntimeError("RaycastingScene.add_triangles: a vertex coordinate is not finite (after rounding to float32)")
                 t = t.astype(np.int32)
+            else:
+                v, t = v.detach().clone(), t.detach().clone()
             pair = (v, t)
         self._geoms.append(pair)
         self._scene = None
