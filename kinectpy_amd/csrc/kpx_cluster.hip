@@ -19,6 +19,7 @@
 // Nothing depends on the order in which the atomics land: the partition, its roots and the ranks are functions of the input.
 #include <float.h>
 
+#include "kpx_compact.h"
 #include "kpx_fixed.h"
 #include "kpx_gridknn.h"
 #include "kpx_linalg.h"

@@ -1,6 +1,7 @@
 // kpx_container.hip -- container operations of the Open3D surface the path touches: transform / rotate / joints
 // affine, skeleton fusion, bounding box, select_by_index, half-space select, slab split, and the sort of the caller's own pairs.
 // HBM-streaming.
+#include "kpx_compact.h"
 #include "kpx_internal.h"
 #include "kpx_box.h"
 #include "kpx_sort.h"
@@ -344,6 +345,142 @@ static int grid_for(int64_t work, int per_block, int cap = 4096)
 }
 
 
+// ---- index compaction over a float32 (n,3) cloud with a predicate on the coordinates ----------------------------
+// The selections of the path (half space, slab split).  ONE pass over the points: a thread loads its 8 points as six
+// 16-byte vectors (96 contiguous bytes), evaluates the predicate -- which may feed two lists at once, bit 0 = list A,
+// bit 1 = list B -- and stores its 8 decisions per list as one byte; the scatter pass reads those bytes (n/8 bytes per
+// list instead of the 12 n of the points), stages the kept indices of a block in LDS and writes them as consecutive
+// dwords.  HBM traffic: 12 n + 4 K + n/4 per list, against 24 n + 4 K when the scatter pass re-evaluates the predicate.
+// The decisions are stored as ballots: bit i of the flag array <-> point i (so the scatter pass's thread t of a block
+// reads byte t = points 8 t .. 8 t + 7 of the tile).
+// The decisions of a wave's 512 points = 6 KiB, starting at point wbase: six lane-contiguous 16-byte loads (every load instruction
+// of the wave reads one contiguous KiB -- 96-byte strides per lane ran at 60 % of this) into `stage`, the wave's 1536 floats of LDS,
+// then lane l evaluates points 64 k + l, k = 0..7, read back with a 3-dword stride (conflict-free).  m[k]: the ballot of row k for
+// list A, m[8 + k] for list B (TWO).  `stage` is typed as LDS: through a plain pointer the compiler folds a row's staged read and its
+// global read into one flat load (3.5 % on the flag pass over 64 M points).
+#define KPX_LDS __attribute__((address_space(3)))
+template <bool TWO, class PredXYZ>
+__device__ __forceinline__ void pts_wave_ballots(const float *__restrict__ pts, int64_t n, const PredXYZ &pred, bool aligned, int64_t wbase,
+                                                 KPX_LDS float *stage, unsigned long long (&m)[TWO ? 16 : 8])
+{
+    const int lane = lane_id();
+    const bool full = aligned && wbase + 512 <= n;
+    if (full) {
+        const float4 *src = reinterpret_cast<const float4 *>(pts + 3 * wbase);
+        float4 *dst = reinterpret_cast<float4 *>((float *)stage);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) dst[64 * r + lane] = stream_load16(src + 64 * r + lane);       // the points are read once: non-temporal
+        wave_lds_fence();
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int p = 64 * k + lane;
+        unsigned r = 0;
+        if (full) r = pred(stage[3 * p], stage[3 * p + 1], stage[3 * p + 2]);
+        else if (wbase + p < n) r = pred(pts[3 * (wbase + p)], pts[3 * (wbase + p) + 1], pts[3 * (wbase + p) + 2]);
+        m[k] = __ballot((r & 1u) != 0);
+        if constexpr (TWO) m[8 + k] = __ballot((r & 2u) != 0);
+    }
+}
+// flags_*: tiles * kCompactThreads bytes; counts_*: one int per tile.  TWO = false: list A only.
+template <class PredXYZ, bool TWO>
+__global__ __launch_bounds__(kCompactThreads) void compact_pts_flag_kernel(const float *__restrict__ pts, int64_t n, PredXYZ pred, bool aligned,
+                                                                           uint8_t *__restrict__ flags_a, int32_t *__restrict__ counts_a,
+                                                                           uint8_t *__restrict__ flags_b, int32_t *__restrict__ counts_b)
+{
+    __shared__ __align__(16) float stage[kCompactThreads / 64][1536];
+    __shared__ int sh[2][kCompactThreads / 64];
+    const int wave = wave_id(), lane = lane_id();
+    unsigned long long m[TWO ? 16 : 8];
+    pts_wave_ballots<TWO>(pts, n, pred, aligned, (int64_t)blockIdx.x * kCompactTile + (int64_t)wave * 512, (KPX_LDS float *)stage[wave], m);
+    unsigned long long ma = 0, mb = 0;          // lane k < 8 keeps the ballot of row k
+    int ca = 0, cb = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        ca += __builtin_popcountll(m[k]);
+        if (lane == k) ma = m[k];
+        if constexpr (TWO) {
+            cb += __builtin_popcountll(m[8 + k]);
+            if (lane == k) mb = m[8 + k];
+        }
+    }
+    const int64_t slot = ((int64_t)blockIdx.x * (kCompactThreads / 64) + wave) * 8 + lane;       // in units of 8 bytes
+    if (lane < 8) {
+        reinterpret_cast<unsigned long long *>(flags_a)[slot] = ma;
+        if (TWO) reinterpret_cast<unsigned long long *>(flags_b)[slot] = mb;
+    }
+    if (lane == 0) { sh[0][wave] = ca; sh[1][wave] = cb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int ta = 0, tb = 0;
+        for (int w = 0; w < kCompactThreads / 64; ++w) { ta += sh[0][w]; tb += sh[1][w]; }
+        counts_a[blockIdx.x] = ta;
+        if (TWO) counts_b[blockIdx.x] = tb;
+    }
+}
+// blockIdx.y == 1: the second list of a two-list pass (*_b)
+__global__ __launch_bounds__(kCompactThreads) void compact_flags_scatter_kernel(const uint8_t *__restrict__ flag_bytes,
+                                                                                const int32_t *__restrict__ block_offsets, int32_t *__restrict__ idx,
+                                                                                const uint8_t *__restrict__ flag_bytes_b,
+                                                                                const int32_t *__restrict__ block_offsets_b, int32_t *__restrict__ idx_b)
+{
+    __shared__ int sh[kCompactThreads / 64 + 1];
+    __shared__ int32_t si[kCompactTile];
+    if (blockIdx.y) { flag_bytes = flag_bytes_b; block_offsets = block_offsets_b; idx = idx_b; }
+    const int64_t base = (int64_t)blockIdx.x * kCompactTile + (int64_t)threadIdx.x * kCompactItems;
+    const unsigned flags = flag_bytes[(int64_t)blockIdx.x * kCompactThreads + threadIdx.x];
+    int tot;
+    int pos = block_excl_scan(__builtin_popcount(flags), sh, &tot);
+#pragma unroll
+    for (int k = 0; k < kCompactItems; ++k)
+        if (flags & (1u << k)) si[pos++] = (int32_t)(base + k);
+    __syncthreads();
+    const int64_t o = block_offsets[blockIdx.x];
+    for (int e = threadIdx.x; e < tot; e += kCompactThreads) idx[o + e] = si[e];
+}
+// ONE pass for one list: the wave-staged predicate evaluation, then the tile's offset by look-back and the kept indices written
+// from LDS as consecutive dwords -- the points are read once, nothing else is read or written but the index list (12 n + 4 K bytes,
+// the algorithmic minimum) and one launch replaces three.
+template <class PredXYZ>
+__global__ __launch_bounds__(kCompactThreads) void compact_pts_onepass_kernel(const float *__restrict__ pts, int64_t n, PredXYZ pred, bool aligned,
+                                                                              unsigned long long *__restrict__ tile_state, int32_t *__restrict__ idx,
+                                                                              int32_t *__restrict__ d_count)
+{
+    __shared__ __align__(16) float stage[kCompactThreads / 64][1536];
+    __shared__ int sh[kCompactThreads / 64 + 2];
+    __shared__ int wave_base[kCompactThreads / 64 + 1];
+    const int wave = wave_id(), lane = lane_id();
+    const int64_t wbase = (int64_t)blockIdx.x * kCompactTile + (int64_t)wave * 512;
+    unsigned long long m[8];
+    pts_wave_ballots<false>(pts, n, pred, aligned, wbase, (KPX_LDS float *)stage[wave], m);
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cnt += __builtin_popcountll(m[k]);
+    if (lane == 0) sh[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int w = 0; w < kCompactThreads / 64; ++w) { wave_base[w] = run; run += sh[w]; }
+        wave_base[kCompactThreads / 64] = run;
+    }
+    __syncthreads();
+    const int tot = wave_base[kCompactThreads / 64];
+    const int before = lookback_exclusive(tile_state, blockIdx.x, tot, sh + kCompactThreads / 64 + 1);
+    // kept indices of the wave's 512 points in ascending order: row k (points 64 k + l) after the rows before it
+    int32_t *si = reinterpret_cast<int32_t *>(stage[wave]);          // the staged points are consumed: reuse the wave's LDS
+    wave_lds_fence();
+    int off = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if ((m[k] >> lane) & 1ull) si[off + __builtin_popcountll(m[k] & ((1ull << lane) - 1ull))] = (int32_t)(wbase + 64 * k + lane);
+        off += __builtin_popcountll(m[k]);
+    }
+    wave_lds_fence();
+    const int64_t o = (int64_t)before + wave_base[wave];
+    for (int e = lane; e < cnt; e += 64) idx[o + e] = si[e];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *d_count = before + tot;
+}
+
 // ---- scratch: every layout stated once, carved by the byte-count function and by the entry points alike -----------------
 static double *bounds_carve(Arena &a) { return a.get<double>((size_t)kBboxBlocks * 6); }      // bbox_f32's partial boxes
 // what the select_by_index, half-space and slab entry points share (kpx_select_workspace_bytes)
@@ -351,7 +488,8 @@ struct PointSelectScratch {
     uint8_t *flag;              // [n] the marks of the mask modes
     int32_t *counts;            // compact()'s tile words
     double *part, *bbox;        // bbox_f32's partial boxes and the box it leaves (slab split of a cloud without known bounds)
-    CompactPtsScratch pts;      // compact_points()
+    uint8_t *pts_flags[2];      // compact_points(): per list one flag byte per thread ...
+    int32_t *pts_counts[2];     // ... and one count per tile
     double *gather_part;        // [kGatherBoundsBlocks * 6] the partial boxes of gather3_bounds_kernel
 };
 static void point_select_carve(Arena &a, int64_t n, PointSelectScratch *s)
@@ -360,8 +498,39 @@ static void point_select_carve(Arena &a, int64_t n, PointSelectScratch *s)
     s->counts = a.get<int32_t>((size_t)compact_ws_ints(n));
     s->part = bounds_carve(a);
     s->bbox = a.get<double>(8);
-    compact_pts_carve(a, n, &s->pts);
+    for (int l = 0; l < 2; ++l) {
+        s->pts_flags[l] = a.get<uint8_t>((size_t)compact_tiles(n) * kCompactThreads);
+        s->pts_counts[l] = a.get<int32_t>((size_t)compact_tiles(n));
+    }
     s->gather_part = a.get<double>((size_t)kGatherBoundsBlocks * 6);
+}
+
+// The form of a points call: the flag, scan and scatter launches above the one-pass limit and always for two lists.  The grid is a row
+// of tiles: the look-back's predecessor is the block dispatched just before (compact_plan states the assumption).
+static CompactPlan points_plan(int32_t tiles, bool two_lists) { return { !two_lists && use_onepass(tiles) ? CompactForm::OnePass : CompactForm::ThreeLaunch, dim3(tiles) }; }
+// idx_b / d_count_b == nullptr: one list (the predicate's bit 0).
+template <class PredXYZ>
+static int compact_points(const float *pts, int64_t n, PredXYZ pred, int32_t *idx_a, int32_t *d_count_a, int32_t *idx_b, int32_t *d_count_b,
+                          const PointSelectScratch &s, hipStream_t st)
+{
+    const int32_t tiles = (int32_t)compact_tiles(n);
+    const bool aligned = ((uintptr_t)pts % 16) == 0;
+    const CompactPlan plan = points_plan(tiles, idx_b != nullptr);
+    const dim3 row = plan.grid, thr(kCompactThreads);
+    if (plan.form == CompactForm::OnePass) {
+        unsigned long long *state = reinterpret_cast<unsigned long long *>(s.pts_flags[0]);     // tiles * 256 bytes >= tiles * 8
+        KPX_HIP(hipMemsetAsync(state, 0, (size_t)tiles * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL((compact_pts_onepass_kernel<PredXYZ>), row, thr, 0, st, pts, n, pred, aligned, state, idx_a, d_count_a);
+    } else {                                            // two lists: both in one scan launch and one scatter launch
+        hipLaunchKernelGGL((idx_b ? compact_pts_flag_kernel<PredXYZ, true> : compact_pts_flag_kernel<PredXYZ, false>), row, thr, 0, st, pts, n, pred, aligned,
+                           s.pts_flags[0], s.pts_counts[0], s.pts_flags[1], s.pts_counts[1]);
+        if (idx_b) compact_scan2(s.pts_counts[0], s.pts_counts[1], tiles, d_count_a, d_count_b, st);
+        else compact_scan(s.pts_counts[0], tiles, 1, d_count_a, st);
+        hipLaunchKernelGGL(compact_flags_scatter_kernel, dim3(tiles, idx_b ? 2 : 1), thr, 0, st, (const uint8_t *)s.pts_flags[0], (const int32_t *)s.pts_counts[0], idx_a,
+                           (const uint8_t *)s.pts_flags[1], (const int32_t *)s.pts_counts[1], idx_b);
+    }
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
 }
 
 }  // namespace kpx
@@ -530,7 +699,7 @@ KPX_EXPORT int kpx_halfspace_select(const float *pts, int64_t n, const double *h
     KPX_ARENA_CHECK(a);
     if (n == 0) return compact(HalfspacePred{ pts, h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, IndexEmit{ idx }, n, 1, s.counts, d_count,
                                (hipStream_t)stream);
-    return compact_points(pts, n, HalfspaceXYZ{ h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, idx, d_count, nullptr, nullptr, s.pts,
+    return compact_points(pts, n, HalfspaceXYZ{ h_plane[0], h_plane[1], h_plane[2], h_plane[3] }, idx, d_count, nullptr, nullptr, s,
                           (hipStream_t)stream);
 }
 
@@ -546,7 +715,7 @@ static int slab_split_impl(const float *pts, int64_t n, double slab, const doubl
         int rc = bbox_f32(pts, n, s.bbox, s.part, st);
         if (rc) return rc;
     }
-    return compact_points(pts, n, SlabXYZ{ d_bounds ? d_bounds : s.bbox, slab }, lower_idx, d_lower, upper_idx, d_upper, s.pts, st);      // one pass feeds both lists
+    return compact_points(pts, n, SlabXYZ{ d_bounds ? d_bounds : s.bbox, slab }, lower_idx, d_lower, upper_idx, d_upper, s, st);      // one pass feeds both lists
 }
 KPX_EXPORT int kpx_slab_split(const float *pts, int64_t n, double slab, int32_t *lower_idx, int32_t *d_lower,
                               int32_t *upper_idx, int32_t *d_upper, void *ws, size_t ws_bytes, void *stream)

@@ -1,6 +1,7 @@
 // kpx_extract.hip -- extract stage: depth -> XYZ int16, exact median, mask + gate + compaction.
 // Reference: preprocessing/extractor.py:68-80 (external unprojection, `.dat` contract),
 // utils/io.py:15-43, preprocessing/data.py:165-178.  All HBM-streaming kernels.
+#include "kpx_compact.h"
 #include "kpx_internal.h"
 
 namespace kpx {
@@ -684,61 +685,27 @@ __global__ __launch_bounds__(kCompactThreads) void depth_count_vec_kernel(const 
     c = block_sum(c, sh);
     if (threadIdx.x == 0) block_counts[(int64_t)f * gridDim.x + blockIdx.x] = c;
 }
-template <bool COL, bool IDX>
-__global__ __launch_bounds__(kCompactThreads) void depth_scatter_vec_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy,
-                                                                            const uint8_t *__restrict__ rgb, const double *__restrict__ median,
-                                                                            int64_t n, int flags, double gate, const int32_t *__restrict__ block_offsets,
-                                                                            float *__restrict__ pts, float *__restrict__ col, int32_t *__restrict__ idx)
+// The look-back of the px8 family: tile-major as everywhere, or FRAME-major for batches -- blockIdx.x is the FRAME, so that a frame's
+// consecutive tiles are dispatched a whole row of frames apart and a tile's predecessor has usually published its count by the time it
+// is asked for (tile-major, every block waits for the block dispatched just before it: measured 2.2 TB/s against 3.0 for count -> scan ->
+// emit on 256 frames)
+struct Px8Lookback : LookbackOffsets { int frame_major; };
+// The tile's pixels are unprojected and tested, the kept points leave through LDS as consecutive dwords.  ScannedOffsets: the third
+// launch of count -> scan -> emit.  Px8Lookback: ONE pass over the frame -- depth / table / colour are read once instead of twice and
+// three launches become one (+ the clear of the tile words).
+template <bool COL, bool IDX, class Offsets>
+__global__ __launch_bounds__(kCompactThreads) void depth_emit_vec_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy,
+                                                                         const uint8_t *__restrict__ rgb, const double *__restrict__ median,
+                                                                         int64_t n, int flags, double gate, float *__restrict__ pts,
+                                                                         float *__restrict__ col, int32_t *__restrict__ idx, Offsets off)
 {
-    __shared__ int sh[kCompactThreads / 64 + 1];
+    __shared__ int sh[kCompactThreads / 64 + 1 + Offsets::kLdsInts];
     // staged as the integers they are (converted when written): 18 KB instead of 48 KB per block, 8 blocks per CU instead of 3
     __shared__ int16_t sp[kCompactTile * 3];
     __shared__ uint8_t sc[COL ? kCompactTile * 3 : 1];
     __shared__ int32_t si[IDX ? kCompactTile : 1];
-    const int f = blockIdx.y;
-    const int64_t base = (int64_t)blockIdx.x * kCompactTile + (int64_t)threadIdx.x * kCompactItems;
-    Px8 p;
-    p.keep = 0;
-    if (base < n) load_px8(depth, xy, rgb, median, n, f, base, flags, gate, p);
-    int tot;
-    int pos = block_excl_scan(__builtin_popcount(p.keep), sh, &tot);
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        if (p.keep & (1u << k)) {
-            sp[3 * pos] = p.x[k]; sp[3 * pos + 1] = p.y[k]; sp[3 * pos + 2] = p.z[k];
-            if (COL) { sc[3 * pos] = p.c[3 * k]; sc[3 * pos + 1] = p.c[3 * k + 1]; sc[3 * pos + 2] = p.c[3 * k + 2]; }
-            if (IDX) si[pos] = (int32_t)(base + k);
-            ++pos;
-        }
-    __syncthreads();
-    const int64_t o = (int64_t)f * n + block_offsets[(int64_t)f * gridDim.x + blockIdx.x];
-    for (int e = threadIdx.x; e < tot * 3; e += kCompactThreads) {
-        pts[o * 3 + e] = (float)sp[e];
-        if (COL) col[o * 3 + e] = (float)((double)sc[e] / 255.0);
-    }
-    if (IDX)
-        for (int e = threadIdx.x; e < tot; e += kCompactThreads) idx[o + e] = si[e];
-}
-
-// ONE pass over the frame: the tile's pixels are unprojected and tested once, its offset inside the frame's cloud comes from the
-// decoupled look-back (kpx_common.h), the kept points leave through LDS as consecutive dwords.  Against count -> scan ->
-// scatter: depth / table / colour are read once instead of twice and three launches become one (+ the clear of the tile words).
-template <bool COL, bool IDX>
-__global__ __launch_bounds__(kCompactThreads) void depth_onepass_vec_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy,
-                                                                            const uint8_t *__restrict__ rgb, const double *__restrict__ median,
-                                                                            int64_t n, int flags, double gate, unsigned long long *__restrict__ tile_state,
-                                                                            float *__restrict__ pts, float *__restrict__ col, int32_t *__restrict__ idx,
-                                                                            int32_t *__restrict__ d_count, int frame_major)
-{
-    __shared__ int sh[kCompactThreads / 64 + 2];
-    __shared__ int16_t sp[kCompactTile * 3];
-    __shared__ uint8_t sc[COL ? kCompactTile * 3 : 1];
-    __shared__ int32_t si[IDX ? kCompactTile : 1];
-    // frame_major (batches): blockIdx.x is the FRAME, so that a frame's consecutive tiles are dispatched a whole row of frames apart and
-    // a tile's predecessor has usually published its count by the time it is asked for (tile-major, every block waits for the block
-    // dispatched just before it: measured 2.2 TB/s against 3.0 for count -> scan -> scatter on 256 frames)
-    const int f = frame_major ? blockIdx.x : blockIdx.y;
-    const unsigned tile = frame_major ? blockIdx.y : blockIdx.x, tiles = frame_major ? gridDim.y : gridDim.x;
+    const int f = off.frame_major ? blockIdx.x : blockIdx.y;
+    const unsigned tile = off.frame_major ? blockIdx.y : blockIdx.x, tiles = off.frame_major ? gridDim.y : gridDim.x;
     const int64_t base = (int64_t)tile * kCompactTile + (int64_t)threadIdx.x * kCompactItems;
     Px8 p;
     p.keep = 0;
@@ -754,7 +721,7 @@ __global__ __launch_bounds__(kCompactThreads) void depth_onepass_vec_kernel(cons
             ++pos;
         }
     __syncthreads();
-    const int before = lookback_exclusive(tile_state + (int64_t)f * tiles, tile, tot, sh + kCompactThreads / 64 + 1);
+    const int before = off.before(f, tile, tiles, tot, sh + kCompactThreads / 64 + 1);
     const int64_t o = (int64_t)f * n + before;
     for (int e = threadIdx.x; e < tot * 3; e += kCompactThreads) {
         pts[o * 3 + e] = (float)sp[e];
@@ -762,7 +729,7 @@ __global__ __launch_bounds__(kCompactThreads) void depth_onepass_vec_kernel(cons
     }
     if (IDX)
         for (int e = threadIdx.x; e < tot; e += kCompactThreads) idx[o + e] = si[e];
-    if (tile == tiles - 1 && threadIdx.x == 0) d_count[f] = before + tot;
+    off.total(f, tile, tiles, before + tot);
 }
 
 // The frame count of a batch becomes gridDim.y of the compaction (and of the median's histogram passes): at most what the device
@@ -776,38 +743,41 @@ static int32_t max_compact_frames()
     }();
     return lim;
 }
+// The form of a px8 call.  Up to the one-pass limit, and for what may not go frame-major, compact_plan's answer.  Batches beyond the
+// limit: the one-pass kernel FRAME-major on the transposed grid (frames, tiles), whose y dimension -- the tiles -- must fit the
+// 65535 every device grants (KPX_ONEPASS_BATCH=0: count -> scan -> emit as before).  The look-back spins on the states of a frame's
+// earlier tiles and rests on blocks being dispatched in linear order, x fastest: here tile t - 1 of a frame sits `frames` blocks before
+// tile t, so it is running or finished whenever tile t runs.
+static CompactPlan px8_plan(int32_t tiles, int32_t frames)
+{
+    static const bool batch_onepass = [] { const char *e = getenv("KPX_ONEPASS_BATCH"); return !(e && e[0] == '0'); }();
+    const bool small = use_onepass((int64_t)tiles * frames);
+    const bool frame_major = !small && batch_onepass && frames >= 8 && frames <= 65535 && tiles <= 65535;
+    if (frame_major) return { CompactForm::OnePassFrameMajor, dim3(frames, tiles) };
+    return compact_plan(tiles, frames);
+}
 // the 8-pixel kernels (xy == NULL: int16 XYZ image input).  counts: frames * compact_ws_ints(n) ints (the 64-bit tile words)
 static int px8_compact(const uint16_t *depth, const float *xy, const uint8_t *rgb, const double *med, int64_t n, int32_t frames, int32_t flags,
                        double gate, int32_t *counts, float *pts, float *col, int32_t *idx, int32_t *d_count, hipStream_t st, bool state_is_clear = false)
 {
     const int32_t tiles = (int32_t)compact_tiles(n);
-    const dim3 grid(tiles, frames), thr(kCompactThreads);
-    const bool wc = col && rgb;
-    // batches beyond the one-pass limit: the one-pass kernel FRAME-major (KPX_ONEPASS_BATCH=0: count -> scan -> scatter as before)
-    static const bool batch_onepass = [] { const char *e = getenv("KPX_ONEPASS_BATCH"); return !(e && e[0] == '0'); }();
-    const bool small = use_onepass((int64_t)tiles * frames);
-    const bool frame_major = !small && batch_onepass && frames >= 8 && frames <= 65535;
-    const bool onepass = small || frame_major;
-    const dim3 ogrid = frame_major ? dim3(frames, tiles) : grid;
-    unsigned long long *state = reinterpret_cast<unsigned long long *>(counts);
-    if (onepass) { if (!state_is_clear) KPX_HIP(hipMemsetAsync(state, 0, (size_t)tiles * frames * sizeof(unsigned long long), st)); }
-    else {
-        hipLaunchKernelGGL(depth_count_vec_kernel, grid, thr, 0, st, depth, xy, rgb, med, n, flags, gate, counts);
-        hipLaunchKernelGGL(compact_scan_kernel, dim3(frames), dim3(compact_scan_threads(tiles)), 0, st, counts, tiles, d_count);
+    const CompactPlan plan = px8_plan(tiles, frames);
+    const dim3 thr(kCompactThreads);
+    const bool wc = col && rgb, onepass = plan.form != CompactForm::ThreeLaunch;
+    const auto emit = [&](auto off) {                  // the emit kernel of (colours, indices) with this source of offsets
+        using O = decltype(off);
+        const auto kernel = wc ? (idx ? depth_emit_vec_kernel<true, true, O> : depth_emit_vec_kernel<true, false, O>)
+                               : (idx ? depth_emit_vec_kernel<false, true, O> : depth_emit_vec_kernel<false, false, O>);
+        hipLaunchKernelGGL(kernel, plan.grid, thr, 0, st, depth, xy, rgb, med, n, flags, gate, pts, col, idx, off);
+    };
+    if (onepass) {
+        if (!state_is_clear) KPX_HIP(hipMemsetAsync(counts, 0, (size_t)tiles * frames * sizeof(unsigned long long), st));
+        emit(Px8Lookback{ { reinterpret_cast<unsigned long long *>(counts), d_count }, plan.form == CompactForm::OnePassFrameMajor ? 1 : 0 });
+    } else {
+        hipLaunchKernelGGL(depth_count_vec_kernel, plan.grid, thr, 0, st, depth, xy, rgb, med, n, flags, gate, counts);
+        compact_scan(counts, tiles, frames, d_count, st);
+        emit(ScannedOffsets{ counts });
     }
-#define KPX_D2C(COL, IDX)                                                                                                       \
-    do {                                                                                                                        \
-        if (onepass)                                                                                                            \
-            hipLaunchKernelGGL((depth_onepass_vec_kernel<COL, IDX>), ogrid, thr, 0, st, depth, xy, rgb, med, n, flags, gate, state, pts, col, idx, d_count, \
-                               frame_major ? 1 : 0);                                                                           \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((depth_scatter_vec_kernel<COL, IDX>), grid, thr, 0, st, depth, xy, rgb, med, n, flags, gate, counts, pts, col, idx);        \
-    } while (0)
-    if (wc && idx) KPX_D2C(true, true);
-    else if (wc) KPX_D2C(true, false);
-    else if (idx) KPX_D2C(false, true);
-    else KPX_D2C(false, false);
-#undef KPX_D2C
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }
@@ -846,8 +816,7 @@ KPX_EXPORT int kpx_rgbd_compact(const int16_t *xyz, const uint8_t *rgb, int64_t 
     KPX_ARENA_CHECK(a);
     XyzPred pred{ xyz, rgb, d_median, n, flags, gate };
     XyzEmit emit{ xyz, rgb, n, pts, col, idx };
-    if (n == 0) return compact(pred, emit, n, frames, counts, d_count, (hipStream_t)stream);
-    const bool vec = (n % 8 == 0) && ((uintptr_t)xyz % 16 == 0) && ((uintptr_t)rgb % 8 == 0);
+    const bool vec = n > 0 && (n % 8 == 0) && ((uintptr_t)xyz % 16 == 0) && ((uintptr_t)rgb % 8 == 0);
     if (!vec) return compact(pred, emit, n, frames, counts, d_count, (hipStream_t)stream);
     return px8_compact(reinterpret_cast<const uint16_t *>(xyz), nullptr, rgb, d_median, n, frames, flags, gate, counts, pts, col, idx, d_count,
                        (hipStream_t)stream);

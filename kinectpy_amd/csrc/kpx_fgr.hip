@@ -12,7 +12,7 @@
 // in wave order by sixteen lanes (one per sum), lane 0 solves (solve6_ldlt_ranked, euler_update) and publishes T and par in LDS.
 #include <vector>
 
-#include "kpx_common.h"
+#include "kpx_compact.h"
 #include "kpx_fixed.h"
 #include "kpx_linalg.h"
 

@@ -9,6 +9,7 @@
 // better-than / est_k logic of Open3D is replayed on the host in iteration order.
 #include <vector>
 
+#include "kpx_compact.h"
 #include "kpx_gridknn.h"
 #include "kpx_linalg.h"
 

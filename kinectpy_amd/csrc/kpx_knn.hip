@@ -10,6 +10,7 @@
 // Squared distance (contract AC3): d2 = fma(dz,dz, fma(dy,dy, dx*dx)), differences in fp64.
 #include <hipcub/hipcub.hpp>
 
+#include "kpx_compact.h"
 #include "kpx_gridknn.h"
 #include "kpx_morton.h"
 #include "kpx_linalg.h"
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(256) void grid_rank_kernel(const float *__restrict_
     }
 }
 
-// Exclusive prefix sums of the cell counts in ONE launch (decoupled look-back over tiles of 2048 counters, kpx_common.h) instead of
+// Exclusive prefix sums of the cell counts in ONE launch (decoupled look-back over tiles of 2048 counters, kpx_compact.h) instead of
 // the vendor scan's two launches and its host-side set-up: with four frames in flight the frame's stream sat idle 50-65 us in front
 // of that scan (profiles/r05/overlap_timeline_native_stream.txt).  states: one cleared 64-bit word per tile.
 constexpr int kGridScanItems = 8, kGridScanTile = 256 * kGridScanItems;

@@ -8,6 +8,7 @@
 // then a pass over the sorted keys in which every entry looks only at its predecessor.  Every fp64 sum whose order the contract fixes
 // is taken by one owner in that order (a thread over its CSR row, one block's chain over the triangles); the only atomics are the
 // union-find's hooks and integer counts, whose results do not depend on the order in which they land.
+#include "kpx_compact.h"
 #include "kpx_sort.h"
 #include "kpx_unionfind.h"
 

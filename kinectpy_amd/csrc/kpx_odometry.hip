@@ -13,7 +13,7 @@
 //                      new pose.
 // Everything a decision depends on is fp64 from plain multiplies and adds in the order written here (-ffp-contract=off), so that
 // tests/odometry_ref.py can restate it bit for bit.
-#include "kpx_common.h"
+#include "kpx_compact.h"
 #include "kpx_linalg.h"
 
 #include <math.h>

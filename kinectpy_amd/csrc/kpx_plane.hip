@@ -8,6 +8,7 @@
 //      (with its probabilistic early exit) is replayed by one thread;
 //   4. inlier compaction for the winning plane, re-fit to the inliers.
 // Distance (contract): |fma(a,x, fma(b,y, fma(c,z, d)))| < thr.
+#include "kpx_compact.h"
 #include "kpx_internal.h"
 
 namespace kpx {

@@ -14,6 +14,7 @@
 //            kernel first descends once by the nearest child to have a bound before the walk starts (it decides no result).
 //   pairs  = AC15: one lane per query triangle walks the same tree with the visit "boxes overlap" and runs tri_tri in
 //            the leaves; count, scan, emit, one sort.
+#include "kpx_compact.h"
 #include "kpx_morton.h"
 
 #include <math.h>
@@ -766,7 +767,7 @@ KPX_EXPORT int kpx_rayscene_triangle_pairs_count(const void *scene, size_t scene
         pairs_launch<kPairAny>(self != 0, brute != 0, st, v, vertices, n_vertices, triangles, m, nullptr, nullptr, 0, d_flag);
     } else {
         pairs_launch<kPairCount>(self != 0, brute != 0, st, v, vertices, n_vertices, triangles, m, out_offsets, nullptr, 0, nullptr);
-        hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, out_offsets, m);
+        scan_i64(out_offsets, m, st);
     }
     KPX_LAUNCH_CHECK();
     return KPX_OK;

@@ -9,6 +9,7 @@
 //   radius: count pass (grid_radius_scan, no cap), the library's own 64-bit scan, fill pass, then every segment sorted by
 //            (d2, index): a wave per segment in LDS up to kSegLds entries, one block per longer segment in place in global memory.
 // Squared distance (contract AC3): d2 = fma(dz,dz, fma(dy,dy, dx*dx)), d = q - p in fp64.  Rows ascend in (d2, index).
+#include "kpx_compact.h"
 #include "kpx_searchview.h"
 
 namespace kpx {
@@ -430,7 +431,7 @@ KPX_EXPORT int kpx_search_radius_count(const void *index, size_t index_bytes, co
     if (m > 0)
         hipLaunchKernelGGL(search_radius_count_kernel, dim3((unsigned)(cdiv(m, 256) > 8192 ? 8192 : cdiv(m, 256))), dim3(256), 0, st, v, queries, m, radius,
                            radius * radius, offsets);
-    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, offsets, m);
+    scan_i64(offsets, m, st);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

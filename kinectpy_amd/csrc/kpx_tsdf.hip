@@ -161,7 +161,7 @@ KPX_EXPORT int kpx_tsdf_extract_count(const float *volume, int32_t resolution, i
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(tsdf_count_kernel<UniformView>, dim3((unsigned)cdiv(nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st,
                        uniform_view(volume, nullptr, resolution, 0.0, nullptr), mode, nchunks, offsets);
-    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, offsets, nchunks);
+    scan_i64(offsets, nchunks, st);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_count, offsets + nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     return KPX_OK;

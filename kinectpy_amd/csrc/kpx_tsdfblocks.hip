@@ -611,7 +611,7 @@ KPX_EXPORT int kpx_tsdf_blocks_touch(const int64_t *index_keys, const int32_t *i
     const unsigned grid = (unsigned)cdiv(t.nchunks, kExtractWaves);
     hipLaunchKernelGGL(blk_heads_count_kernel, dim3(grid), dim3(kExtractWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, t.n, t.nchunks, index,
                        (int32_t)n_blocks, t.hoff, t.noff);
-    hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, t.hoff, t.noff, t.nchunks);
+    scan2_i64(t.hoff, t.noff, t.nchunks, st);
     hipLaunchKernelGGL(blk_heads_fill_kernel, dim3(grid), dim3(kExtractWaves * 64), 0, st, (const uint64_t *)t.sort.keys_out, (const int32_t *)t.sort.vals_out, t.n,
                        t.nchunks, index, index_slots, (int32_t)n_blocks, (const int64_t *)t.hoff, (const int64_t *)t.noff, t.ukeys, t.tslot, t.tmask, t.newkeys);
     hipLaunchKernelGGL(blk_touch_done_kernel, dim3(1), dim3(64), 0, st, (const int64_t *)t.hoff, (const int64_t *)t.noff, t.nchunks, (const int32_t *)t.err, d_counts);
@@ -730,7 +730,7 @@ KPX_EXPORT int kpx_tsdf_blocks_extract_count(const int64_t *index_keys, const in
     const BlkView v = blk_view(index_keys, index_slots, n_blocks, pool, nullptr, unit_resolution, 0.0, s.nbr);
     hipLaunchKernelGGL(blk_neighbours_kernel, dim3((unsigned)cdiv(n_blocks * 27, 256)), dim3(256), 0, st, v.keys, v.B, s.nbr);
     hipLaunchKernelGGL(tsdf_count_kernel<BlkView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, mode, s.nchunks, s.offsets);
-    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, s.offsets, s.nchunks);
+    scan_i64(s.offsets, s.nchunks, st);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_count, s.offsets + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     return KPX_OK;
@@ -777,7 +777,7 @@ KPX_EXPORT int kpx_tsdf_blocks_mesh_count(const int64_t *index_keys, const int32
     hipLaunchKernelGGL(blk_mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, v, s.codes);
     hipLaunchKernelGGL(mc_count_kernel<BlkView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, (const uint8_t *)s.codes, s.nchunks,
                        s.groups, s.voff, s.toff);
-    hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, s.voff, s.toff, s.nchunks);
+    scan2_i64(s.voff, s.toff, s.nchunks, st);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_counts, s.voff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     KPX_HIP(hipMemcpyAsync(d_counts + 1, s.toff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));

@@ -18,7 +18,7 @@
 //   tap0(c, fl, k)               floor(q / vl - 0.5) = fl as a coordinate counted from c's block
 // UniformView is below; BlkView is kpx_tsdfblocks.hip's.
 #pragma once
-#include "kpx_common.h"
+#include "kpx_compact.h"
 
 #include <math.h>
 

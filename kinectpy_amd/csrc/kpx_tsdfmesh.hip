@@ -157,7 +157,7 @@ KPX_EXPORT int kpx_tsdf_mesh_count(const float *volume, int32_t resolution, int6
     hipLaunchKernelGGL(mc_code_kernel, dim3((unsigned)cdiv(s.nvox, 256)), dim3(256), 0, st, v.vol, resolution, s.nvox, s.codes);
     hipLaunchKernelGGL(mc_count_kernel<UniformView>, dim3((unsigned)cdiv(s.nchunks, kExtractWaves)), dim3(kExtractWaves * 64), 0, st, v, (const uint8_t *)s.codes,
                        s.nchunks, s.groups, s.voff, s.toff);
-    hipLaunchKernelGGL(scan2_i64_kernel, dim3(2), dim3(1024), 0, st, s.voff, s.toff, s.nchunks);
+    scan2_i64(s.voff, s.toff, s.nchunks, st);
     KPX_LAUNCH_CHECK();
     KPX_HIP(hipMemcpyAsync(d_counts, s.voff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     KPX_HIP(hipMemcpyAsync(d_counts + 1, s.toff + s.nchunks, sizeof(int64_t), hipMemcpyDeviceToDevice, st));

@@ -2,6 +2,7 @@
 // stable sort of (key, point id), head compaction and the per-voxel sequential fp64 sums.  kpx_voxel.hip (voxel_down_sample in its
 // plain, batch and fused forms) and kpx_voxelgrid.hip (VoxelGrid.create_from_point_cloud) are host policies over them.
 #pragma once
+#include "kpx_compact.h"
 #include "kpx_cloudset.h"
 #include "kpx_internal.h"
 #include "kpx_sort.h"

@@ -1,16 +1,17 @@
 """Plain helpers (no GPU) for the stream-compaction tests: which form of the order-preserving compaction a call takes, inputs whose
 kept items are laid out in whole tiles, NumPy references where the C oracle has none, and the comparison the GPU tests use.
 
-`compact_form` restates the switch conditions of kpx_common.h (compact, compact_points, compact_scan_threads, use_onepass) and of
-kpx_extract.hip (px8_compact, the vector-path conditions of kpx_depth_to_cloud / kpx_rgbd_compact); the constants below must be moved
-with the library's."""
+`compact_form` restates the switch conditions of kpx_compact.h (compact_plan, compact_scan_threads, use_onepass), of kpx_container.hip
+(points_plan) and of kpx_extract.hip (px8_plan, the vector-path conditions of kpx_depth_to_cloud / kpx_rgbd_compact); the constants
+below must be moved with the library's."""
 import numpy as np
 
-TILE = 2048                  # kpx_common.h kCompactTile = kCompactThreads (256) x kCompactItems (8)
-ONE_PASS_TILES = 2048        # kpx_common.h kOnePassTiles: the look-back kernels serve up to this many tiles (x frames)
+TILE = 2048                  # kpx_compact.h kCompactTile = kCompactThreads (256) x kCompactItems (8)
+ONE_PASS_TILES = 2048        # kpx_compact.h kOnePassTiles: the look-back kernels serve up to this many tiles (x frames)
 SCAN_WIDE_ABOVE = 2048       # compact_scan_threads: 256 threads up to here, 1024 above
-SCAN_ITEMS = 8               # compact_scan_body: counts per thread and round
-FRAME_MAJOR_MIN, FRAME_MAJOR_MAX = 8, 65535      # px8_compact: the frame-major one-pass grid's range of frame counts
+SCAN_ITEMS = 8               # kpx_compact.hip compact_scan_body: counts per thread and round
+FRAME_MAJOR_MIN, FRAME_MAJOR_MAX = 8, 65535      # px8_plan: the frame-major one-pass grid's range of frame counts
+FRAME_MAJOR_MAX_TILES = 65535                    # px8_plan: ... and the most tiles per frame (they are the grid's y dimension)
 GATE_MM = 750.0
 
 GENERIC_ONEPASS, GENERIC_THREE = "generic one-pass", "generic three-launch"
@@ -54,7 +55,7 @@ def compact_form(n, frames, vec, lists=1, kind="extract", onepass=None, onepass_
         return (GENERIC_ONEPASS, None) if small else (GENERIC_THREE, scan_shape(tiles))
     if small:
         return PX8_TILE_MAJOR, None
-    if onepass_batch and FRAME_MAJOR_MIN <= frames <= FRAME_MAJOR_MAX:
+    if onepass_batch and FRAME_MAJOR_MIN <= frames <= FRAME_MAJOR_MAX and tiles <= FRAME_MAJOR_MAX_TILES:
         return PX8_FRAME_MAJOR, None
     return PX8_THREE, scan_shape(tiles)
 

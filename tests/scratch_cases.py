@@ -9,7 +9,7 @@ One entry per function of kinectpy_amd/ops.py whose body calls L.workspace(.  An
                    restated from the test named beside it -- no new tolerance is made up here)
 
 Sizes are the smallest at which scratch can go wrong: "small" lies below one block or tile of the operator's first kernel, "large"
-is three tiles and a ragged tail (TILE: kCompactTile = kRxTile = kGridScanTile = 2048 items, restated from kpx_common.h / kpx_radix.h /
+is three tiles and a ragged tail (TILE: kCompactTile = kRxTile = kGridScanTile = 2048 items, restated from kpx_compact.h / kpx_radix.h /
 kpx_knn.hip as tests/test_boundaries_gpu.py restates them) or one past a form switch (the limits of include/kinectpx.h are read from
 it).  "one" (n = 1) goes to the twenty operators whose own suites run a single point, pixel or pair and whose references are defined
 there; the registrations and solves need three pairs, the features and covariances a neighbourhood, the meshes and scenes a triangle,

@@ -15,15 +15,15 @@ def test_constants_restate_the_library():
     import os
     import re
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "kinectpy_amd", "csrc")
-    common, extract = open(os.path.join(src, "kpx_common.h")).read(), open(os.path.join(src, "kpx_extract.hip")).read()
+    common, scans, extract = (open(os.path.join(src, f)).read() for f in ("kpx_compact.h", "kpx_compact.hip", "kpx_extract.hip"))
     num = lambda pat, text: int(re.search(pat, text).group(1))
     assert num(r"kCompactThreads = (\d+);", common) * num(r"kCompactItems = (\d+);", common) == CR.TILE
     assert num(r"kOnePassTiles = (\d+);", common) == CR.ONE_PASS_TILES
     m = re.search(r"compact_scan_threads\(int64_t tiles\) \{ return tiles > (\d+) \? (\d+) : (\d+); \}", common)
     assert [int(g) for g in m.groups()] == [CR.SCAN_WIDE_ABOVE, 1024, 256]
-    assert re.search(r"b0 \+= (\d+) \* \(int32_t\)blockDim\.x", common).group(1) == str(CR.SCAN_ITEMS)
-    m = re.search(r"frame_major = !small && batch_onepass && frames >= (\d+) && frames <= (\d+);", extract)
-    assert [int(g) for g in m.groups()] == [CR.FRAME_MAJOR_MIN, CR.FRAME_MAJOR_MAX]
+    assert re.search(r"b0 \+= (\d+) \* \(int32_t\)blockDim\.x", scans).group(1) == str(CR.SCAN_ITEMS)
+    m = re.search(r"frame_major = !small && batch_onepass && frames >= (\d+) && frames <= (\d+) && tiles <= (\d+);", extract)
+    assert [int(g) for g in m.groups()] == [CR.FRAME_MAJOR_MIN, CR.FRAME_MAJOR_MAX, CR.FRAME_MAJOR_MAX_TILES]
 
 
 def test_scan_shapes():
@@ -60,6 +60,8 @@ def test_form_px8_boundaries():
     assert f(2049 * T - 2040, 1) == (CR.PX8_THREE, (1024, False))
     assert f(8193 * T - 2040, 1) == (CR.PX8_THREE, (1024, True))
     assert f(8, 65535) == (CR.PX8_FRAME_MAJOR, None) and f(8, 65536) == (CR.PX8_THREE, (256, False))
+    # the tiles are the frame-major grid's y dimension
+    assert f(65535 * T, 8) == (CR.PX8_FRAME_MAJOR, None) and f(65536 * T, 8) == (CR.PX8_THREE, (1024, True))
     # the switches: KPX_ONEPASS forces either side at any size, KPX_ONEPASS_BATCH=0 sends a batch above the limit to three launches
     assert f(n, 9, onepass=0) == (CR.PX8_FRAME_MAJOR, None) and f(n, 3, onepass=0) == (CR.PX8_THREE, (256, False))
     assert f(n, 9, onepass=1) == (CR.PX8_TILE_MAJOR, None)

@@ -34,7 +34,7 @@ def short(n):
     return n.split("(")[0][:44]
 
 
-starts = [i for i, e in enumerate(ev) if "depth_onepass_vec_kernel<false" in e[2] or "depth_onepass_vec_kernel<0" in e[2]]
+starts = [i for i, e in enumerate(ev) if "depth_emit_vec_kernel<false" in e[2] or "depth_emit_vec_kernel<0" in e[2]]
 frames = [ev[a:b] for a, b in zip(starts[:-1], starts[1:])]
 frames = [f for f in frames if len(f) > 20]
 if not frames:

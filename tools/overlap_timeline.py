@@ -44,7 +44,7 @@ for name, (c, t) in sorted(byk.items(), key=lambda x: -x[1][1])[:14]:
 # ---- one frame of one stream under load: every dispatch with the idle gap in front of it (argument 3 = "list") -------------------
 if len(sys.argv) > 3 and sys.argv[3] == "list":
     q = sorted(byq.items(), key=lambda x: -len(x[1]))[0][1]
-    starts = [i for i, e in enumerate(q) if "depth_onepass_vec_kernel<false" in e[2] or "depth_onepass_vec_kernel<0" in e[2]]
+    starts = [i for i, e in enumerate(q) if "depth_emit_vec_kernel<false" in e[2] or "depth_emit_vec_kernel<0" in e[2]]
     frames = [q[a:b] for a, b in zip(starts[:-1], starts[1:]) if b - a > 20]
     frames.sort(key=lambda f: f[-1][1] - f[0][0])
     fr = frames[len(frames) // 2]
