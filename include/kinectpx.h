@@ -1190,6 +1190,52 @@ int kpx_pointnet_train_step(float *params, int64_t params_floats, const float *x
                             uint64_t seed, uint64_t step, int32_t training_dropout, float *loss, float *grad, float *m, float *v, double lr,
                             double beta1, double beta2, double eps, int64_t t, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- sensor calibration: lens-model ray tables, colour aligned to depth (arithmetic contract AC20) ---------------------
+ * A camera is KPX_CAMERA_DOUBLES doubles on the host: fx, fy, cx, cy, k1, k2, k3, k4, k5, k6, p1, p2, metric_radius (pixel units,
+ * integer pixel coordinates are pixel centres, OpenCV's rational model).  Everything below is fp64, every multiply, add and divide
+ * rounded separately, in exactly the order written here (no fused multiply-add anywhere):
+ *   distort(x, y):  xx = x x, yy = y y, r2 = xx + yy, r4 = r2 r2, r6 = r4 r2,
+ *                   num = ((1 + k1 r2) + k2 r4) + k3 r6, den = ((1 + k4 r2) + k5 r4) + k6 r6, radial = num / den, xy2 = 2 (x y),
+ *                   xd = (x radial + p1 xy2) + p2 (r2 + 2 xx), yd = (y radial + p1 (r2 + 2 yy)) + p2 xy2.
+ *   forward(X, Y, Z), Z > 0:  x = X / Z, y = Y / Z; invalid when r2 > metric_radius metric_radius; u = fx xd + cx, v = fy yd + cy.
+ *   jacobian(x, y): nd = (k1 + (2 k2) r2) + (3 k3) r4, dd = (k4 + (2 k5) r2) + (3 k6) r4, dr = (nd den - num dd) / (den den),
+ *                   gx = (2 x) dr, gy = (2 y) dr,
+ *                   a = ((radial + x gx) + (2 p1) y) + (6 p2) x,   b = (x gy + (2 p1) x) + (2 p2) y,
+ *                   c = (y gx + (2 p1) x) + (2 p2) y,              d = ((radial + y gy) + (6 p1) y) + (2 p2) x.
+ *   inverse(u, v):  xn = (u - cx) / fx, yn = (v - cy) / fy, (x, y) = (xn, yn); then up to 21 rounds: (xd, yd) = distort(x, y),
+ *                   ex = xd - xn, ey = yd - yn; converged when ex ex + ey ey <= 1e-22 (a NaN never is); the 21st round only tests;
+ *                   otherwise det = a d - b c, stop unless det is finite and non-zero,
+ *                   x = x - (d ex - b ey) / det, y = y - (a ey - c ex) / det   (at most 20 Newton steps).
+ *                   The result is (NaN, NaN) unless converged with x, y finite and x x + y y <= metric_radius metric_radius.
+ * kpx_xy_table: xy f32 [height][width][2] on the device = inverse(column, row) rounded once to float32 (NaN pairs where invalid):
+ *     the table kpx_unproject_u16 / kpx_depth_to_cloud take.  One thread per pixel, one launch, asynchronous.
+ * kpx_color_to_depth: the colour image (or a mask / label image on the colour camera) resampled into the depth camera's pixel grid.
+ *     depth u16 [frames][n_px] millimetres; xy f32 [calibrations][n_px][2]; color u8 [frames][color_height][color_width][channels],
+ *     channels 1 or 3; out u8 [frames][n_px][channels]; all on the device, no alignment required.  h_calibrations: `calibrations`
+ *     (1 .. KPX_SENSOR_MAX_CALIBRATIONS) blocks of KPX_CALIBRATION_DOUBLES doubles on the host: the colour camera, then the row-major
+ *     4x4 depth -> colour transform in millimetres (its last row is not read).  Frame f uses calibration f mod calibrations, which
+ *     must divide frames.  Per depth pixel with depth d and table entry (xt, yt):
+ *         px = xt d, py = yt d, pz = d;   q_i = ((R_i0 px + R_i1 py) + R_i2 pz) + t_i;   (uc, vc) = forward(q) of the colour camera;
+ *         KPX_SAMPLE_NEAREST:  the pixel (floor(uc + 0.5), floor(vc + 0.5));
+ *         KPX_SAMPLE_BILINEAR: x0 = floor(uc), y0 = floor(vc), ax = uc - x0, ay = vc - y0, per channel
+ *             val = (((1 - ax)(1 - ay) c00 + ax (1 - ay) c10) + (1 - ax) ay c01) + ax ay c11 (c10 right of c00, c01 below it),
+ *             stored as floor(val + 0.5).
+ *     The pixel is all zeros when d == 0, the table entry has a NaN, q_z <= 0, the projection is invalid, the nearest pixel lies
+ *     outside the image, or (bilinear) any of the four neighbours does, whatever its weight.  Every output byte is written.  Like the
+ *     sensor SDK's own transformation this does not test occlusion between the two cameras.  One launch for the whole batch
+ *     (frames <= 65535), asynchronous.
+ * Neither entry takes device scratch.  Sizes, null pointers, channels, the sampling code and calibrations not dividing frames are
+ * rejected before the device is touched; width height = 0, frames = 0 and n_px = 0 return KPX_OK without a launch. */
+#define KPX_CAMERA_DOUBLES 13
+#define KPX_CALIBRATION_DOUBLES 29
+#define KPX_SENSOR_MAX_CALIBRATIONS 16
+#define KPX_SAMPLE_NEAREST 0
+#define KPX_SAMPLE_BILINEAR 1
+int kpx_xy_table(const double *h_camera, int32_t width, int32_t height, float *xy, void *stream);
+int kpx_color_to_depth(const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
+                       int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
+                       uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

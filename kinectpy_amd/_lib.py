@@ -237,6 +237,8 @@ SIGNATURES = {
     "kpx_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _vp]),
     "kpx_pointnet_train_step": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _u64, _u64, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i64,
                                           _vp, _sz, _vp]),
+    "kpx_xy_table": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "kpx_color_to_depth": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

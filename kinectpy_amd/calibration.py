@@ -1,0 +1,236 @@
+"""Sensor calibration (arithmetic contract AC20): the lens model of a camera, the depth -> colour transform of one
+sensor, and a rig of sensors.
+
+The reference pairs `<ts>_rgb.png` with `<ts>_depth.dat` row for row (preprocessing/data.py:165-178) because the sensor SDK's
+offline processor has already un-projected the depth image through the lens model and warped the colour image into the depth
+camera.  Both steps are open geometry (OpenCV's rational model); here they are `SensorCalibration.xy_table()` -- the table every
+entry point at the front of the hot path takes -- and `register_color` / `register_mask`, on the device.
+
+`CameraIntrinsics.project` / `unproject` are host NumPy float64 that follow AC20 operation for operation: they are meant for a
+handful of skeleton joints, not for images.
+"""
+import json
+
+import numpy as np
+
+from . import ops
+
+_FIELDS = ("width", "height", "fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4", "k5", "k6", "p1", "p2", "metric_radius")
+MAX_ROUNDS = 21             # 20 Newton steps and one last test
+RESIDUAL2 = 1e-22
+
+
+class CameraIntrinsics:
+    """Pixel units; integer pixel coordinates are pixel centres; k1..k6, p1, p2 have OpenCV's meaning (pyk4a's
+    get_camera_matrix / get_distortion_coefficients: `from_opencv`)."""
+
+    def __init__(self, width, height, fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0, k5=0.0, k6=0.0, p1=0.0, p2=0.0, metric_radius=1.7):
+        self.width, self.height = int(width), int(height)
+        for name, v in zip(_FIELDS[2:], (fx, fy, cx, cy, k1, k2, k3, k4, k5, k6, p1, p2, metric_radius)):
+            setattr(self, name, float(v))
+        if self.width < 0 or self.height < 0:
+            raise ValueError(f"CameraIntrinsics: image size {self.width} x {self.height}")
+        if not np.all(np.isfinite(self.packed())) or self.fx == 0.0 or self.fy == 0.0 or not self.metric_radius > 0.0:
+            raise ValueError("CameraIntrinsics: finite numbers, non-zero focal lengths and a positive metric radius")
+
+    @classmethod
+    def from_opencv(cls, width, height, camera_matrix, dist_coeffs, metric_radius=1.7):
+        """camera_matrix 3x3, dist_coeffs in OpenCV's storage order (k1, k2, p1, p2, k3, k4, k5, k6), shorter vectors padded with 0"""
+        K = np.asarray(camera_matrix, dtype=np.float64).reshape(3, 3)
+        d = np.zeros(8)
+        dc = np.asarray(dist_coeffs, dtype=np.float64).reshape(-1)[:8]
+        d[:dc.size] = dc
+        return cls(width, height, K[0, 0], K[1, 1], K[0, 2], K[1, 2], d[0], d[1], d[4], d[5], d[6], d[7], d[2], d[3], metric_radius)
+
+    def packed(self):
+        """float64[13]: fx fy cx cy k1..k6 p1 p2 metric_radius (KPX_CAMERA_DOUBLES of include/kinectpx.h)"""
+        return np.array([getattr(self, n) for n in _FIELDS[2:]], dtype=np.float64)
+
+    def to_dict(self):
+        return {n: getattr(self, n) for n in _FIELDS}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**{n: d[n] for n in _FIELDS})
+
+    def __eq__(self, other):
+        return isinstance(other, CameraIntrinsics) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return "CameraIntrinsics(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in _FIELDS) + ")"
+
+    def has_distortion(self):
+        return any(getattr(self, n) != 0.0 for n in _FIELDS[6:14])
+
+    def to_pinhole(self):
+        """o3d.camera.PinholeCameraIntrinsic for the pinhole-only consumers (TSDF, odometry, VoxelGrid carving); refuses a distorted
+        camera: those consumers would silently use the wrong rays."""
+        if self.has_distortion():
+            raise ValueError("to_pinhole: this camera has lens distortion; undistort the images first (DESIGN.md 9)")
+        from . import o3d
+        return o3d.camera.PinholeCameraIntrinsic(self.width, self.height, self.fx, self.fy, self.cx, self.cy)
+
+    # ---- AC20 on the host ------------------------------------------------------------------------------------------------------
+    def _distort(self, x, y):
+        xx = x * x
+        yy = y * y
+        r2 = xx + yy
+        r4 = r2 * r2
+        r6 = r4 * r2
+        num = ((1.0 + self.k1 * r2) + self.k2 * r4) + self.k3 * r6
+        den = ((1.0 + self.k4 * r2) + self.k5 * r4) + self.k6 * r6
+        radial = num / den
+        xy2 = 2.0 * (x * y)
+        xd = (x * radial + self.p1 * xy2) + self.p2 * (r2 + 2.0 * xx)
+        yd = (y * radial + self.p1 * (r2 + 2.0 * yy)) + self.p2 * xy2
+        return xd, yd, r2, r4, num, den, radial
+
+    def project(self, points):
+        """(..., 3) points in the camera frame -> (..., 2) pixel coordinates, NaN pairs where Z <= 0 or beyond the metric radius"""
+        p = np.asarray(points, dtype=np.float64)
+        X, Y, Z = p[..., 0], p[..., 1], p[..., 2]
+        with np.errstate(all="ignore"):
+            x = X / Z
+            y = Y / Z
+            xd, yd, r2 = self._distort(x, y)[:3]
+            u = self.fx * xd + self.cx
+            v = self.fy * yd + self.cy
+            ok = (Z > 0.0) & (r2 <= self.metric_radius * self.metric_radius)
+        return np.where(ok[..., None], np.stack([u, v], -1), np.nan)
+
+    def unproject(self, pixels):
+        """(..., 2) pixel coordinates -> (..., 2) normalised (x, y) = (X / Z, Y / Z) of the ray, NaN pairs where there is none"""
+        uv = np.asarray(pixels, dtype=np.float64)
+        shape = uv.shape[:-1]
+        u, v = uv[..., 0].reshape(-1), uv[..., 1].reshape(-1)
+        xn = (u - self.cx) / self.fx
+        yn = (v - self.cy) / self.fy
+        x, y = xn.copy(), yn.copy()
+        live = np.ones(x.shape, dtype=bool)             # still iterating
+        done = np.zeros(x.shape, dtype=bool)            # converged
+        p1x2, p2x2, p1x6, p2x6 = 2.0 * self.p1, 2.0 * self.p2, 6.0 * self.p1, 6.0 * self.p2
+        with np.errstate(all="ignore"):
+            for rnd in range(MAX_ROUNDS):
+                i = np.nonzero(live)[0]
+                if i.size == 0:
+                    break
+                xi, yi = x[i], y[i]
+                xd, yd, r2, r4, num, den, radial = self._distort(xi, yi)
+                ex = xd - xn[i]
+                ey = yd - yn[i]
+                conv = ex * ex + ey * ey <= RESIDUAL2
+                done[i[conv]] = True
+                if rnd == MAX_ROUNDS - 1:
+                    break
+                nd = (self.k1 + (2.0 * self.k2) * r2) + (3.0 * self.k3) * r4
+                dd = (self.k4 + (2.0 * self.k5) * r2) + (3.0 * self.k6) * r4
+                dr = (nd * den - num * dd) / (den * den)
+                gx = (2.0 * xi) * dr
+                gy = (2.0 * yi) * dr
+                a = ((radial + xi * gx) + p1x2 * yi) + p2x6 * xi
+                b = (xi * gy + p1x2 * xi) + p2x2 * yi
+                c = (yi * gx + p1x2 * xi) + p2x2 * yi
+                d = ((radial + yi * gy) + p1x6 * yi) + p2x2 * xi
+                det = a * d - b * c
+                step = ~conv & np.isfinite(det) & (det != 0.0)
+                live[i[~step]] = False
+                j = i[step]
+                x[j] = xi[step] - ((d * ex - b * ey) / det)[step]
+                y[j] = yi[step] - ((a * ey - c * ex) / det)[step]
+            ok = done & np.isfinite(x) & np.isfinite(y) & (x * x + y * y <= self.metric_radius * self.metric_radius)
+        out = np.where(ok[:, None], np.stack([x, y], -1), np.nan)
+        return out.reshape(shape + (2,))
+
+
+class SensorCalibration:
+    """One sensor: its depth camera, its colour camera and the 4x4 depth -> colour transform in millimetres."""
+
+    def __init__(self, depth, color, depth_to_color):
+        if not isinstance(depth, CameraIntrinsics) or not isinstance(color, CameraIntrinsics):
+            raise TypeError("SensorCalibration: depth and color are CameraIntrinsics")
+        T = np.array(depth_to_color, dtype=np.float64)
+        if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+            raise ValueError("SensorCalibration: depth_to_color is a finite 4x4 matrix")
+        self.depth, self.color, self.depth_to_color = depth, color, T
+        self._table = None
+
+    def xy_table(self):
+        """the depth camera's ray table, float32 (H * W, 2) on the device (ops.xy_table), computed once"""
+        if self._table is None:
+            self._table = ops.xy_table(self.depth)
+        return self._table
+
+    def register_color(self, depth, color):
+        """depth uint16 (n_px,), color uint8 (Hc, Wc, 3) -> uint8 (n_px, 3) in the depth camera's pixel grid, bilinear (no occlusion
+        test: ops.color_to_depth)"""
+        return _register([self], depth, color, "bilinear", 1)[0]
+
+    def register_mask(self, depth, mask):
+        """depth uint16 (n_px,), mask uint8 (Hc, Wc) taken on the colour image -> uint8 (n_px,), nearest pixel"""
+        return _register([self], depth, mask, "nearest", 1)[0]
+
+    def to_dict(self):
+        return {"depth": self.depth.to_dict(), "color": self.color.to_dict(), "depth_to_color": self.depth_to_color.tolist()}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(CameraIntrinsics.from_dict(d["depth"]), CameraIntrinsics.from_dict(d["color"]), d["depth_to_color"])
+
+    def save(self, path):
+        """plain JSON of the fields (Python writes the shortest decimal that reads back as the same double: the round trip is exact)"""
+        with open(path, "w") as f:
+            json.dump(self.to_dict(), f, indent=1)
+
+    @classmethod
+    def load(cls, path):
+        with open(path) as f:
+            return cls.from_dict(json.load(f))
+
+    def __eq__(self, other):
+        return isinstance(other, SensorCalibration) and self.to_dict() == other.to_dict()
+
+
+class SensorRig:
+    """The sensors of a rig, in the order of the frames' sensor axis."""
+
+    def __init__(self, calibrations):
+        self.calibrations = list(calibrations)
+        if not self.calibrations or not all(isinstance(c, SensorCalibration) for c in self.calibrations):
+            raise TypeError("SensorRig: a non-empty list of SensorCalibration")
+        n = {(c.depth.width, c.depth.height) for c in self.calibrations}
+        if len(n) != 1:
+            raise ValueError(f"SensorRig: the depth cameras differ in size: {sorted(n)}")
+        self._tables = None
+
+    def __len__(self):
+        return len(self.calibrations)
+
+    def xy_tables(self):
+        """float32 (S, n_px, 2) on the device: one table per sensor (the batched kpx_depth_to_cloud / frame step take ONE table: a
+        rig of distinct lenses calls them once per sensor)"""
+        if self._tables is None:
+            import torch
+            self._tables = torch.stack([c.xy_table() for c in self.calibrations])
+        return self._tables
+
+    def register_colors(self, depth, colors):
+        """depth uint16 (S, n_px) -- or (F, n_px) with S dividing F, frame f of sensor f % S --, colors uint8 (F, Hc, Wc, 3) ->
+        uint8 (F, n_px, 3): every sensor's colour image in its depth camera's grid, one launch"""
+        return _register(self.calibrations, depth, colors, "bilinear", None, self.xy_tables())
+
+    def register_masks(self, depth, masks):
+        """as register_colors for uint8 (F, Hc, Wc) masks / label images, nearest pixel -> uint8 (F, n_px)"""
+        return _register(self.calibrations, depth, masks, "nearest", None, self.xy_tables())
+
+
+def _register(cals, depth, image, interpolation, frames, tables=None):
+    import torch
+    if tables is None:
+        tables = torch.stack([c.xy_table() for c in cals]) if len(cals) > 1 else cals[0].xy_table()
+    img = image if isinstance(image, torch.Tensor) else np.asarray(image)
+    want = 3 if interpolation == "nearest" else 4         # dimensions of a batch
+    if frames == 1 and img.ndim == want - 1:
+        img = img[None]
+    if img.ndim != want:
+        raise ValueError(f"register: the image batch has {img.ndim} dimensions, expected {want}")
+    return ops.color_to_depth(depth, tables, img, cals, interpolation)

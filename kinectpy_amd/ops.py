@@ -2327,3 +2327,72 @@ def pointnet_train_step(params, x, y, m, v, learning_rate=0.001, beta_1=0.9, bet
                                         int(bool(training_dropout)), L.ptr(loss), L.ptr(grad), L.ptr(m), L.ptr(v), float(learning_rate), float(beta_1),
                                         float(beta_2), float(epsilon), int(t), ws, wsz, L.stream_ptr()))
     return loss, grad
+
+
+# ---- sensor calibration (AC20) ------------------------------------------------------------------------
+SAMPLE_MODES = {"nearest": 0, "bilinear": 1}          # KPX_SAMPLE_* (include/kinectpx.h)
+CAMERA_DOUBLES, CALIBRATION_DOUBLES, SENSOR_MAX_CALIBRATIONS = 13, 29, 16
+
+
+def _camera13(intrinsics):
+    """a calibration.CameraIntrinsics (anything with .packed()) or 13 numbers -> float64[13]: fx fy cx cy k1..k6 p1 p2 metric_radius"""
+    a = intrinsics.packed() if hasattr(intrinsics, "packed") else intrinsics
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+    if a.size != CAMERA_DOUBLES:
+        raise L.KinectPxError(f"a camera is {CAMERA_DOUBLES} numbers (fx fy cx cy k1..k6 p1 p2 metric_radius), got {a.size}")
+    return a
+
+
+def xy_table(intrinsics):
+    """AC20's ray table of a lens (a calibration.CameraIntrinsics): float32 (height * width, 2) device tensor of the fp64 inverse of
+    the camera model at every pixel centre, NaN pairs where there is none -- what unproject_u16 / depth_to_cloud / frame_step take as
+    `xy_table`."""
+    lib = L.load()
+    cam = _camera13(intrinsics)
+    w, h = int(intrinsics.width), int(intrinsics.height)
+    out = torch.empty((h * w, 2), dtype=torch.float32, device=L.device())
+    L.check(lib.kpx_xy_table(L.hptr(cam), w, h, L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def color_to_depth(depth, xy, color, calibrations, interpolation="bilinear", out=None):
+    """AC20: colour images (or masks / label images taken on the colour camera) resampled into the depth camera's pixel grid.
+    depth uint16 (F, n_px) mm; xy float32 (S, n_px, 2) -- the depth cameras' tables, (n_px, 2) for one; color uint8 (F, Hc, Wc, C) or
+    (F, Hc, Wc), C in {1, 3}; calibrations: S objects with `.color` (CameraIntrinsics of size Wc x Hc) and `.depth_to_color` (4x4, mm)
+    -- calibration.SensorCalibration -- or S (camera, 4x4) pairs; frame f uses calibration f % S and S divides F.
+    interpolation: "bilinear" (colour) or "nearest" (masks, labels).  -> uint8 (F, n_px, C) (or (F, n_px) for a (F, Hc, Wc) input):
+    zeros where there is no depth, no ray, the point lies behind the colour camera or outside its image.  Like the sensor SDK's own
+    transformation this does NOT test occlusion: a depth pixel the colour camera cannot see takes the colour of what hides it.
+    out: a contiguous uint8 device tensor of F * n_px * C elements to write into."""
+    lib = L.load()
+    if interpolation not in SAMPLE_MODES:
+        raise ValueError(f"color_to_depth: unknown interpolation {interpolation!r}: expected one of {sorted(SAMPLE_MODES)}")
+    cals = list(calibrations)
+    S = len(cals)
+    if not 1 <= S <= SENSOR_MAX_CALIBRATIONS:
+        raise L.KinectPxError(f"color_to_depth: 1 to {SENSOR_MAX_CALIBRATIONS} calibrations, got {S}")
+    col = _dev(color, torch.uint8)
+    if col.dim() not in (3, 4):
+        raise L.KinectPxError("color_to_depth: color must be uint8 (F, Hc, Wc, C) or (F, Hc, Wc)")
+    flat = col.dim() == 3
+    F, hc, wc = int(col.shape[0]), int(col.shape[1]), int(col.shape[2])
+    ch = 1 if flat else int(col.shape[3])
+    dep = _dev(depth, torch.uint16).reshape(F, -1)
+    n_px = int(dep.shape[1])
+    table = _dev(xy, torch.float32).reshape(-1, n_px, 2) if n_px else _dev(xy, torch.float32).reshape(S, 0, 2)
+    if table.shape[0] != S:
+        raise L.KinectPxError(f"color_to_depth: {table.shape[0]} tables for {S} calibrations")
+    pack = np.empty((S, CALIBRATION_DOUBLES), dtype=np.float64)
+    for s, c in enumerate(cals):
+        cam, T = (c.color, c.depth_to_color) if hasattr(c, "depth_to_color") else c
+        if hasattr(cam, "width") and (int(cam.width), int(cam.height)) != (wc, hc):
+            raise L.KinectPxError(f"color_to_depth: calibration {s} is for a {cam.width} x {cam.height} colour image, got {wc} x {hc}")
+        pack[s, :CAMERA_DOUBLES] = _camera13(cam)
+        pack[s, CAMERA_DOUBLES:] = _T(T).reshape(16)
+    if out is None:
+        out = torch.empty((F, n_px) if flat else (F, n_px, ch), dtype=torch.uint8, device=dep.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() == F * n_px * ch):
+        raise ValueError(f"color_to_depth: out must be a contiguous uint8 device tensor of {F * n_px * ch} elements")
+    L.check(lib.kpx_color_to_depth(L.ptr(dep), L.ptr(table), L.ptr(col), n_px, F, wc, hc, ch, L.hptr(pack), S, SAMPLE_MODES[interpolation], L.ptr(out),
+                                   L.stream_ptr()))
+    return out

@@ -22,7 +22,8 @@ class MKVFilesProcessing(object):
                  number_of_joints: int = 32, frame_source: Optional[FrameSource] = None) -> None:
         """Same arguments as the reference (extractor.py:18-24) plus `frame_source`: a callable
         mkv_fp -> (xy_table f32 (H*W,2), iterable of (timestamp, depth u16 (H*W,))) replacing the MKV
-        demux of the external binary."""
+        demux of the external binary.  In place of the table it may return the sensor's
+        calibration.SensorCalibration: the table is then computed from the depth camera's lens model."""
         self.mkv_fps, self.output_dirs = mkv_fps, output_dirs
         self.offline_processor_fp, self.number_of_joints = offline_processor_fp, number_of_joints
         self.frame_source = frame_source
@@ -44,6 +45,8 @@ class MKVFilesProcessing(object):
         for mkv_fp, output_dir in zip(self.mkv_fps, self.output_dirs):
             logging.info(f'Starting to process MKV File {mkv_fp}\nIt will be saved under directory: {output_dir}\n')
             xy, frames = self.frame_source(mkv_fp)
+            if hasattr(xy, 'xy_table'):                    # a calibration.SensorCalibration: the table of its depth camera's lens
+                xy = xy.xy_table()
             stamps, buf = [], []
 
             def flush():

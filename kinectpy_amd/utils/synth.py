@@ -262,6 +262,27 @@ def sensor_ring(n_sensors, n_frames=1, xy=None, sensors=None, first_frame=0):
     return xy, depth, rgb, inits, truth
 
 
+def sensor_calibration(i=0):
+    """calibration.SensorCalibration of synthetic sensor i: plausible NFOV-unbinned numbers that are NO real device's -- depth 640 x 576
+    at f ~ 504, colour 1280 x 720 at f ~ 605, all six radial terms of the rational lens model non-zero, the colour camera ~32 mm beside
+    the depth camera and tilted ~6 degrees about x.  The numbers vary slightly with i (every sensor of a rig has its own lens)."""
+    from ..calibration import CameraIntrinsics, SensorCalibration
+    s = float(i)
+    depth = CameraIntrinsics(W, H, 504.0 + 0.37 * s, 504.2 + 0.41 * s, 321.3 - 0.9 * s, 329.6 + 1.3 * s,
+                             k1=4.9 + 0.11 * s, k2=3.1 - 0.07 * s, k3=0.17 + 0.004 * s, k4=5.23 + 0.11 * s, k5=4.7 - 0.09 * s, k6=0.88 + 0.01 * s,
+                             p1=7.0e-5 - 1.0e-5 * s, p2=-4.0e-5 + 2.0e-5 * s)
+    color = CameraIntrinsics(1280, 720, 605.3 + 0.5 * s, 605.1 + 0.45 * s, 639.2 + 1.1 * s, 366.4 - 0.8 * s,
+                             k1=0.61 + 0.02 * s, k2=-2.7 - 0.05 * s, k3=1.5 + 0.03 * s, k4=0.49 + 0.02 * s, k5=-2.5 - 0.05 * s, k6=1.44 + 0.03 * s,
+                             p1=5.0e-4 + 1.0e-5 * s, p2=-2.0e-4 - 1.0e-5 * s)
+    a, b = np.deg2rad(6.0 + 0.1 * s), np.deg2rad(0.2 - 0.05 * s)
+    Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+    Rz = np.array([[np.cos(b), -np.sin(b), 0], [np.sin(b), np.cos(b), 0], [0, 0, 1]])
+    T = np.eye(4)
+    T[:3, :3] = Rz @ Rx
+    T[:3, 3] = [-32.0 - 0.2 * s, -2.1 + 0.1 * s, 3.9 - 0.1 * s]
+    return SensorCalibration(depth, color, T)
+
+
 def small_xy(scale=4):
     """a 1/scale-resolution camera (144 x 160 for scale 4) with the same field of view: CPU-sized frames for rehearsals"""
     return xy_table(h=H // scale, w=W // scale, fx=FX / scale, fy=FY / scale, cx=CX / scale, cy=CY / scale)

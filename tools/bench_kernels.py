@@ -60,8 +60,11 @@ def main():
     ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
     ap.add_argument("--pointnet", action="store_true", help="only the PointNet forward rows (fused against eval-mode torch modules)")
     ap.add_argument("--pointnet-train", action="store_true", help="only the PointNet training step rows (against train-mode torch modules with torch.optim.Adam)")
+    ap.add_argument("--sensor", action="store_true", help="only the sensor calibration rows (xy_table, color_to_depth)")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    if a.sensor:
+        return sensor_rows(dev, a.quick)
     if a.pointnet_train:
         return pointnet_train_rows(dev, a.quick)
     if a.pointnet:
@@ -681,6 +684,27 @@ def orient_rows(dev, quick):
         for mode in ("normalize", "direction", "camera"):
             ms, _ = timed(lambda: ops.orient_normals(nrm, mode, (0.0, 0.0, 1.0), pts), reps=20, warm=2)
             report(f"orient_normals {mode} on {what}", ms, n * (36 if mode == "camera" else 24), n=n)
+
+
+def sensor_rows(dev, quick):
+    """DESIGN.md 5.21 at the rig's real size: the ray table of one 640 x 576 depth lens, and 4 x 640 x 576 depth with 4 x 1280 x 720 x 3
+    colour registered in one launch (masks: 1 channel, nearest).  Algorithmic bytes of color_to_depth: depth 2 + table 8 + output C
+    per depth pixel, plus every colour image read once."""
+    from kinectpy_amd.calibration import SensorRig
+    S = 4
+    rig = SensorRig([synth.sensor_calibration(i) for i in range(S)])
+    reps = 5 if quick else 20
+    ms, _ = timed(lambda: ops.xy_table(rig.calibrations[0].depth), reps=reps, warm=2)
+    report("xy_table 640x576 (AC20 Newton inverse, fp64)", ms, N_PX * 8, pixels=N_PX)
+    tables = rig.xy_tables()
+    depth = torch.as_tensor(np.stack([synth.render_depth(synth.camera_pose(i, S), seed=100 + i) for i in range(S)])).to(dev)
+    color = torch.randint(1, 256, (S, 720, 1280, 3), dtype=torch.uint8, device=dev)
+    for ch, interp, img in ((3, "bilinear", color), (1, "nearest", color[..., 0].contiguous())):
+        out = torch.empty(S * N_PX * ch, dtype=torch.uint8, device=dev)
+        ms, res = timed(lambda: ops.color_to_depth(depth, tables, img, rig.calibrations, interp, out=out), reps=reps, warm=2)
+        filled = int((res.reshape(S * N_PX, ch) != 0).any(1).sum().item())
+        report(f"color_to_depth {S} x 640x576 <- {S} x 1280x720x{ch} {interp}", ms, S * N_PX * (2 + 8 + ch) + S * 720 * 1280 * ch, frames=S,
+               filled=filled)
 
 
 def odometry_launches(iterations):
