@@ -1236,6 +1236,46 @@ int kpx_color_to_depth(const uint16_t *depth, const float *xy, const uint8_t *co
                        int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
                        uint8_t *out, void *stream);
 
+/* ---- depth warped into the colour camera, occlusion-tested registration (arithmetic contract AC21) -------------------
+ * AC20's rules hold: fp64, every multiply, add and divide rounded separately in the order written, no fused multiply-add.
+ *   Vertex of depth pixel (column c, row r) of frame f, calibration f mod calibrations: d the u16 depth, (xt, yt) the table entry;
+ *       px = xt d, py = yt d, pz = d;   q_i = ((R_i0 px + R_i1 py) + R_i2 pz) + t_i;   (u, v) = forward(q) of the colour camera, z = q_z
+ *       (AC20's "colour -> depth" chain: the same code, the same bits).  The vertex is valid when d != 0, neither table value is NaN,
+ *       q_z > 0 and the projection lies inside the metric radius.
+ *   Triangles: every 2 x 2 block of depth pixels with top-left (c, r), c < W - 1, r < H - 1, gives, in this vertex order,
+ *       A = (P(c, r), P(c + 1, r), P(c, r + 1))   and   B = (P(c + 1, r + 1), P(c, r + 1), P(c + 1, r)).
+ *       E(a, b, p) = (b_u - a_u) (p_v - a_v) - (b_v - a_v) (p_u - a_u).  A triangle (P0, P1, P2) is skipped when a vertex is invalid;
+ *       when max(z) - min(z) > max_gap_mm; when floor(max u) - ceil(min u) >= KPX_WARP_MAX_SPAN, or the same for v (compared on the
+ *       doubles, before any clamping); when area = E(P0, P1, P2) is zero or not finite.
+ *   Pixels of a triangle: every integer pixel centre p = (x, y) with ceil(min u) <= x <= floor(max u), ceil(min v) <= y <= floor(max v),
+ *       0 <= x <= color_width - 1, 0 <= y <= color_height - 1:   w0 = E(P1, P2, p), w1 = E(P2, P0, p), w2 = E(P0, P1, p);
+ *       the pixel is inside when all three are >= 0 (area > 0) or all three are <= 0 (area < 0): an edge belongs to both triangles
+ *       beside it;   s = (w0 + w1) + w2, skipped when s = 0;   zz = ((w0 z0 + w1 z1) + w2 z2) / s, zi = floor(zz + 0.5), skipped unless
+ *       1 <= zi <= 65535.
+ *   Warped depth of a colour pixel: the MINIMUM zi over every triangle pixel that reached it, 0 where none did -- a minimum does not
+ *       depend on the order in which threads arrive.  Every output element is written.
+ *   Occlusion test (kpx_color_to_depth_visible): for a depth pixel AC20 would sample, (ix, iy) = (floor(uc + 0.5), floor(vc + 0.5)) --
+ *       the bilinear sampler tests this nearest pixel too: it lies inside the image when the 2 x 2 block does -- and w = warped[iy][ix];
+ *       the pixel is occluded when w != 0 and q_z - (double)w > occlusion_mm, and all its channels are then zero.  Everything else is
+ *       AC20's; occlusion_mm = +inf gives kpx_color_to_depth's bytes.
+ * kpx_depth_to_color: depth u16 [frames][depth_height depth_width], xy f32 [calibrations][depth_height depth_width][2],
+ *     out u16 [frames][color_height][color_width], all on the device, no alignment required; h_calibrations as kpx_color_to_depth.
+ *     ws: kpx_depth_to_color_workspace_bytes(frames, color_width, color_height) = frames color_height color_width 4 bytes of device
+ *     scratch (a 32-bit z-buffer, cleared by the call).  Asynchronous, no host read-back; frames <= 65535.  max_gap_mm >= 0, +inf allowed
+ *     ("never"); NaN, negative sizes, null pointers, calibrations outside 1 .. KPX_SENSOR_MAX_CALIBRATIONS or not dividing frames,
+ *     non-finite cameras or transforms and a short ws_bytes are rejected before the device is touched.  frames = 0 or an empty colour
+ *     image return KPX_OK without a launch; a depth image with width < 2 or height < 2 has no triangle: out is all zeros, written.
+ * kpx_color_to_depth_visible: kpx_color_to_depth with the occlusion test; warped u16 [frames][color_height][color_width] on the device,
+ *     occlusion_mm >= 0 (+inf allowed). */
+#define KPX_WARP_MAX_SPAN 16
+size_t kpx_depth_to_color_workspace_bytes(int32_t frames, int32_t color_width, int32_t color_height);
+int kpx_depth_to_color(const uint16_t *depth, const float *xy, int32_t depth_width, int32_t depth_height, int32_t frames, int32_t color_width,
+                       int32_t color_height, const double *h_calibrations, int32_t calibrations, double max_gap_mm, uint16_t *out, void *ws,
+                       size_t ws_bytes, void *stream);
+int kpx_color_to_depth_visible(const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
+                               int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
+                               const uint16_t *warped, double occlusion_mm, uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

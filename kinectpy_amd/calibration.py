@@ -4,7 +4,10 @@ sensor, and a rig of sensors.
 The reference pairs `<ts>_rgb.png` with `<ts>_depth.dat` row for row (preprocessing/data.py:165-178) because the sensor SDK's
 offline processor has already un-projected the depth image through the lens model and warped the colour image into the depth
 camera.  Both steps are open geometry (OpenCV's rational model); here they are `SensorCalibration.xy_table()` -- the table every
-entry point at the front of the hot path takes -- and `register_color` / `register_mask`, on the device.
+entry point at the front of the hot path takes -- and `register_color` / `register_mask`, on the device.  Contract AC21 (DESIGN.md
+5.22) adds `warp_depth` -- the depth image rendered into the colour camera through a z-buffer -- and with it the occlusion test of
+the `register_*` methods (`occlusion_mm`, `max_gap_mm`): the strip of background the depth camera sees beside a silhouette, where the
+colour camera sees the subject, no longer takes the subject's colour and mask label.
 
 `CameraIntrinsics.project` / `unproject` are host NumPy float64 that follow AC20 operation for operation: they are meant for a
 handful of skeleton joints, not for images.
@@ -153,6 +156,7 @@ class SensorCalibration:
             raise ValueError("SensorCalibration: depth_to_color is a finite 4x4 matrix")
         self.depth, self.color, self.depth_to_color = depth, color, T
         self._table = None
+        self._color_table = None
 
     def xy_table(self):
         """the depth camera's ray table, float32 (H * W, 2) on the device (ops.xy_table), computed once"""
@@ -160,14 +164,30 @@ class SensorCalibration:
             self._table = ops.xy_table(self.depth)
         return self._table
 
-    def register_color(self, depth, color):
-        """depth uint16 (n_px,), color uint8 (Hc, Wc, 3) -> uint8 (n_px, 3) in the depth camera's pixel grid, bilinear (no occlusion
-        test: ops.color_to_depth)"""
-        return _register([self], depth, color, "bilinear", 1)[0]
+    def color_xy_table(self):
+        """the colour camera's ray table, float32 (Hc * Wc, 2) on the device, computed once: with it warp_depth's image goes into
+        ops.unproject_u16 / ops.depth_to_cloud beside the raw colour image"""
+        if self._color_table is None:
+            self._color_table = ops.xy_table(self.color)
+        return self._color_table
 
-    def register_mask(self, depth, mask):
-        """depth uint16 (n_px,), mask uint8 (Hc, Wc) taken on the colour image -> uint8 (n_px,), nearest pixel"""
-        return _register([self], depth, mask, "nearest", 1)[0]
+    def warp_depth(self, depth, max_gap_mm):
+        """depth uint16 (H * W,) -> uint16 (Hc, Wc): the depth image seen from the colour camera, 0 where the depth camera saw nothing
+        (AC21, ops.depth_to_color).  max_gap_mm: triangles of the depth mesh whose vertices differ by more than this in depth are not
+        drawn.  No default: it depends on the scene and the rig, and nothing in this project measures it."""
+        return _warp([self], depth, max_gap_mm)[0]
+
+    def register_color(self, depth, color, occlusion_mm=None, max_gap_mm=None):
+        """depth uint16 (n_px,), color uint8 (Hc, Wc, 3) -> uint8 (n_px, 3) in the depth camera's pixel grid, bilinear.  By default
+        without an occlusion test (ops.color_to_depth).  occlusion_mm (with max_gap_mm, see warp_depth): the depth image is warped
+        into the colour camera first, and a depth pixel that lies more than occlusion_mm behind what the colour camera sees at its
+        place is zero.  Neither has a default value: both depend on the scene and the rig, and nothing in this project measures them."""
+        return _register([self], depth, color, "bilinear", 1, None, occlusion_mm, max_gap_mm)[0]
+
+    def register_mask(self, depth, mask, occlusion_mm=None, max_gap_mm=None):
+        """depth uint16 (n_px,), mask uint8 (Hc, Wc) taken on the colour image -> uint8 (n_px,), nearest pixel; occlusion_mm and
+        max_gap_mm as in register_color"""
+        return _register([self], depth, mask, "nearest", 1, None, occlusion_mm, max_gap_mm)[0]
 
     def to_dict(self):
         return {"depth": self.depth.to_dict(), "color": self.color.to_dict(), "depth_to_color": self.depth_to_color.tolist()}
@@ -213,24 +233,55 @@ class SensorRig:
             self._tables = torch.stack([c.xy_table() for c in self.calibrations])
         return self._tables
 
-    def register_colors(self, depth, colors):
+    def warp_depths(self, depth, max_gap_mm):
+        """depth uint16 (F, H * W), frame f of sensor f % S -> uint16 (F, Hc, Wc): every frame's depth image seen from its colour camera
+        (SensorCalibration.warp_depth, one call for the batch).  The colour cameras must be of one size: ValueError otherwise."""
+        return _warp(self.calibrations, depth, max_gap_mm, self)
+
+    def register_colors(self, depth, colors, occlusion_mm=None, max_gap_mm=None):
         """depth uint16 (S, n_px) -- or (F, n_px) with S dividing F, frame f of sensor f % S --, colors uint8 (F, Hc, Wc, 3) ->
-        uint8 (F, n_px, 3): every sensor's colour image in its depth camera's grid, one launch"""
-        return _register(self.calibrations, depth, colors, "bilinear", None, self.xy_tables())
+        uint8 (F, n_px, 3): every sensor's colour image in its depth camera's grid, one launch; occlusion_mm and max_gap_mm as in
+        SensorCalibration.register_color (the warp and the registration are two calls with no host synchronisation between them)"""
+        return _register(self.calibrations, depth, colors, "bilinear", None, self, occlusion_mm, max_gap_mm)
 
-    def register_masks(self, depth, masks):
+    def register_masks(self, depth, masks, occlusion_mm=None, max_gap_mm=None):
         """as register_colors for uint8 (F, Hc, Wc) masks / label images, nearest pixel -> uint8 (F, n_px)"""
-        return _register(self.calibrations, depth, masks, "nearest", None, self.xy_tables())
+        return _register(self.calibrations, depth, masks, "nearest", None, self, occlusion_mm, max_gap_mm)
 
 
-def _register(cals, depth, image, interpolation, frames, tables=None):
+def _tables(cals, rig):
+    """the depth cameras' tables (a rig keeps its stack), asked for only once the arguments have been checked"""
+    if rig is not None:
+        return rig.xy_tables()
     import torch
-    if tables is None:
-        tables = torch.stack([c.xy_table() for c in cals]) if len(cals) > 1 else cals[0].xy_table()
+    return torch.stack([c.xy_table() for c in cals]) if len(cals) > 1 else cals[0].xy_table()
+
+
+def _warp(cals, depth, max_gap_mm, rig=None, tables=None):
+    sizes = {(c.color.width, c.color.height) for c in cals}
+    if len(sizes) != 1:
+        raise ValueError(f"warp: the colour cameras differ in size: {sorted(sizes)}")
+    if max_gap_mm is None:
+        raise ValueError("warp: max_gap_mm is required (no default: it depends on the scene and the rig)")
+    d = cals[0].depth
+    return ops.depth_to_color(depth, _tables(cals, rig) if tables is None else tables, d.width, d.height, cals, max_gap_mm)
+
+
+def _register(cals, depth, image, interpolation, frames, rig=None, occlusion_mm=None, max_gap_mm=None):
+    import torch
+    if occlusion_mm is None and max_gap_mm is not None:
+        raise ValueError("register: max_gap_mm belongs to the occlusion test: give occlusion_mm too")
+    if occlusion_mm is not None and max_gap_mm is None:
+        raise ValueError("register: occlusion_mm needs max_gap_mm (the depth image is warped into the colour camera first)")
     img = image if isinstance(image, torch.Tensor) else np.asarray(image)
     want = 3 if interpolation == "nearest" else 4         # dimensions of a batch
     if frames == 1 and img.ndim == want - 1:
         img = img[None]
     if img.ndim != want:
         raise ValueError(f"register: the image batch has {img.ndim} dimensions, expected {want}")
-    return ops.color_to_depth(depth, tables, img, cals, interpolation)
+    tables = _tables(cals, rig)
+    if occlusion_mm is None:
+        return ops.color_to_depth(depth, tables, img, cals, interpolation)
+    depth = ops._dev(depth, torch.uint16)                 # (both calls read it: a host array goes to the device once)
+    warped = _warp(cals, depth, max_gap_mm, rig, tables)
+    return ops.color_to_depth(depth, tables, img, cals, interpolation, warped=warped, occlusion_mm=occlusion_mm)

@@ -1,7 +1,9 @@
 // kpx_sensor.hip -- sensor calibration (arithmetic contract AC20): the per-pixel ray table of a distorted lens
 // (kpx_xy_table) and the colour image resampled into the depth camera's pixel grid (kpx_color_to_depth).  Both are pure maps: no
-// scratch, no atomics, one launch each.  fp64 throughout, every operation rounded separately in the order include/kinectpx.h
-// states -- the build's -ffp-contract=off keeps the compiler from fusing any of it, and nothing here calls fma().
+// scratch, no atomics, one launch each.  AC21 adds the depth image warped into the colour camera through a 32-bit
+// z-buffer of integer minima (kpx_depth_to_color) and the registration with an occlusion test against it (kpx_color_to_depth_visible).
+// fp64 throughout, every operation rounded separately in the order include/kinectpx.h states -- the build's -ffp-contract=off keeps
+// the compiler from fusing any of it, and nothing here calls fma().
 #include "kpx_common.h"
 
 namespace kpx {
@@ -97,36 +99,46 @@ static __global__ __launch_bounds__(kTableThreads) void xy_table_kernel(Camera k
 }
 
 // ---- colour -> depth ---------------------------------------------------------------------------------------------------------------
-// A block owns kPixPerBlock consecutive depth pixels of one frame (blockIdx.y), four per thread.  The pixels' bytes are packed into
-// dwords in registers, laid down in LDS in pixel order, and leave as 16-byte stores from the first 16-byte boundary of the block's
-// output range on; the at most 15 bytes in front of that boundary and behind the last whole vector leave as byte stores (a frame's
-// output starts wherever frames * n_px * channels puts it, and neighbouring blocks may share a 16-byte line but never a byte).
-constexpr int kC2dThreads = 256, kC2dPerThread = 4, kPixPerBlock = kC2dThreads * kC2dPerThread;
-
-template <int C, int INTERP>
-__device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const uint8_t *__restrict__ img, int32_t wc, int32_t hc, uint16_t d, float xt, float yt,
-                                             uint32_t out[C])
+// AC20's "colour -> depth" chain of one depth pixel, which is also AC21's vertex: false = no point in the colour camera (no depth, no
+// ray, behind the camera, beyond the metric radius)
+__device__ __forceinline__ bool depth_pixel_to_color(const ColorCalibration &cal, uint16_t d, float xt, float yt, double &uc, double &vc, double &qz)
 {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) out[ch] = 0;
-    if (d == 0 || __builtin_isnan(xt) || __builtin_isnan(yt)) return;
+    if (d == 0 || __builtin_isnan(xt) || __builtin_isnan(yt)) return false;
     const double pz = (double)d, px = (double)xt * pz, py = (double)yt * pz;
     const double *T = cal.T;
     const double qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
     const double qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-    const double qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
-    if (!(qz > 0.0)) return;
-    double uc, vc;
-    if (!project(cal.cam, qx, qy, qz, uc, vc)) return;
+    qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
+    if (!(qz > 0.0)) return false;
+    return project(cal.cam, qx, qy, qz, uc, vc);
+}
+
+__device__ __forceinline__ bool occluded(const uint16_t *__restrict__ warped, int32_t wc, double fx, double fy, double qz, double occlusion_mm)
+{
+    const uint16_t w = warped[(int64_t)(int32_t)fy * wc + (int32_t)fx];
+    return w != 0 && qz - (double)w > occlusion_mm;
+}
+
+// VISIBLE: AC21's occlusion test against the warped depth image of the frame (`warped`, colour-camera grid)
+template <int C, int INTERP, bool VISIBLE>
+__device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const uint8_t *__restrict__ img, const uint16_t *__restrict__ warped,
+                                             double occlusion_mm, int32_t wc, int32_t hc, uint16_t d, float xt, float yt, uint32_t out[C])
+{
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) out[ch] = 0;
+    double uc, vc, qz;
+    if (!depth_pixel_to_color(cal, d, xt, yt, uc, vc, qz)) return;
     if (INTERP == KPX_SAMPLE_NEAREST) {
         const double fx = floor(uc + 0.5), fy = floor(vc + 0.5);
         if (!(fx >= 0.0 && fx <= (double)(wc - 1) && fy >= 0.0 && fy <= (double)(hc - 1))) return;       // (a NaN fails too)
+        if (VISIBLE && occluded(warped, wc, fx, fy, qz, occlusion_mm)) return;
         const uint8_t *p = img + ((int64_t)(int32_t)fy * wc + (int32_t)fx) * C;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) out[ch] = p[ch];
     } else {
         const double x0 = floor(uc), y0 = floor(vc);
         if (!(x0 >= 0.0 && x0 <= (double)(wc - 2) && y0 >= 0.0 && y0 <= (double)(hc - 2))) return;
+        if (VISIBLE && occluded(warped, wc, floor(uc + 0.5), floor(vc + 0.5), qz, occlusion_mm)) return;      // (inside: the 2 x 2 block is)
         const double ax = uc - x0, ay = vc - y0;
         const double bx = 1.0 - ax, by = 1.0 - ay;
         const double w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay;
@@ -141,9 +153,16 @@ __device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const 
     }
 }
 
-template <int C, int INTERP>
+// A block owns kPixPerBlock consecutive depth pixels of one frame (blockIdx.y), four per thread.  The pixels' bytes are packed into
+// dwords in registers, laid down in LDS in pixel order, and leave as 16-byte stores from the first 16-byte boundary of the block's
+// output range on; the at most 15 bytes in front of that boundary and behind the last whole vector leave as byte stores (a frame's
+// output starts wherever frames * n_px * channels puts it, and neighbouring blocks may share a 16-byte line but never a byte).
+constexpr int kC2dThreads = 256, kC2dPerThread = 4, kPixPerBlock = kC2dThreads * kC2dPerThread;
+
+template <int C, int INTERP, bool VISIBLE>
 static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy,
-                                                                            const uint8_t *__restrict__ color, int64_t n_px, int32_t wc, int32_t hc,
+                                                                            const uint8_t *__restrict__ color, const uint16_t *__restrict__ warped,
+                                                                            double occlusion_mm, int64_t n_px, int32_t wc, int32_t hc,
                                                                             CalibrationPack pack, int32_t n_cal, int32_t vec_ok,
                                                                             uint8_t *__restrict__ out)
 {
@@ -156,6 +175,7 @@ static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(cons
     const uint16_t *dp = depth + (int64_t)frame * n_px;
     const float *tp = xy + (int64_t)cal_id * n_px * 2;
     const uint8_t *img = color + (int64_t)frame * hc * wc * C;
+    const uint16_t *wimg = VISIBLE ? warped + (int64_t)frame * hc * wc : nullptr;
 
     uint16_t d[kC2dPerThread];
     float xt[kC2dPerThread], yt[kC2dPerThread];
@@ -176,7 +196,7 @@ static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(cons
     }
     uint32_t px[kC2dPerThread][C];
 #pragma unroll
-    for (int k = 0; k < kC2dPerThread; ++k) sample_pixel<C, INTERP>(cal, img, wc, hc, d[k], xt[k], yt[k], px[k]);
+    for (int k = 0; k < kC2dPerThread; ++k) sample_pixel<C, INTERP, VISIBLE>(cal, img, wimg, occlusion_mm, wc, hc, d[k], xt[k], yt[k], px[k]);
     if (C == 3) {
         // 12 bytes r g b r g b ... as three little-endian words
         stage[3 * threadIdx.x + 0] = px[0][0] | px[0][1 % C] << 8 | px[0][2 % C] << 16 | px[1][0] << 24;
@@ -216,6 +236,130 @@ static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(cons
     }
 }
 
+// ---- depth -> colour (AC21) -----------------------------------------------------------------------------------------------------------
+// Three dispatches: the z-buffer's clear to 0xFFFFFFFF (a memset node), the raster kernel, the resolve kernel.
+// Raster: a block owns a tile of kWarpTileW x kWarpTileH quads of one frame (blockIdx.y) and projects the tile's (kWarpTileW + 1) x
+// (kWarpTileH + 1) vertices once into LDS -- the fp64 chain with its two divisions runs 1.16 times per depth pixel instead of four.
+// An invalid vertex is stored with z = 0 (a valid one has q_z > 0).  Each thread then walks its quad's two triangles over their
+// bounding boxes (less than KPX_WARP_MAX_SPAN pixels a side) with one atomicMin per covered pixel on the 32-bit buffer.
+constexpr int kWarpTileW = 32, kWarpTileH = 8, kWarpThreads = kWarpTileW * kWarpTileH;
+constexpr int kWarpVertW = kWarpTileW + 1, kWarpVerts = kWarpVertW * (kWarpTileH + 1);
+constexpr uint32_t kWarpEmpty = 0xFFFFFFFFu;
+
+struct WarpVertex {
+    double u, v, z;
+};
+
+__device__ __forceinline__ double edge(double au, double av, double bu, double bv, double pu, double pv)
+{
+    return (bu - au) * (pv - av) - (bv - av) * (pu - au);
+}
+
+__device__ __forceinline__ void raster_triangle(const WarpVertex &p0, const WarpVertex &p1, const WarpVertex &p2, double max_gap_mm, int32_t wc,
+                                                int32_t hc, uint32_t *__restrict__ zbuf)
+{
+    if (!(p0.z > 0.0 && p1.z > 0.0 && p2.z > 0.0)) return;
+    const double zmax = fmax(fmax(p0.z, p1.z), p2.z), zmin = fmin(fmin(p0.z, p1.z), p2.z);
+    if (zmax - zmin > max_gap_mm) return;
+    const double bx0 = ceil(fmin(fmin(p0.u, p1.u), p2.u)), bx1 = floor(fmax(fmax(p0.u, p1.u), p2.u));
+    const double by0 = ceil(fmin(fmin(p0.v, p1.v), p2.v)), by1 = floor(fmax(fmax(p0.v, p1.v), p2.v));
+    if (bx1 - bx0 >= (double)KPX_WARP_MAX_SPAN || by1 - by0 >= (double)KPX_WARP_MAX_SPAN) return;
+    const double area = edge(p0.u, p0.v, p1.u, p1.v, p2.u, p2.v);
+    if (area == 0.0 || !__builtin_isfinite(area)) return;                      // (finite: every coordinate is, so the box below is too)
+    const double cx0 = fmax(bx0, 0.0), cx1 = fmin(bx1, (double)(wc - 1)), cy0 = fmax(by0, 0.0), cy1 = fmin(by1, (double)(hc - 1));
+    if (!(cx0 <= cx1 && cy0 <= cy1)) return;
+    const int32_t x0 = (int32_t)cx0, x1 = (int32_t)cx1, y0 = (int32_t)cy0, y1 = (int32_t)cy1;
+    for (int32_t y = y0; y <= y1; ++y) {
+        const double pv = (double)y;
+        for (int32_t x = x0; x <= x1; ++x) {
+            const double pu = (double)x;
+            const double w0 = edge(p1.u, p1.v, p2.u, p2.v, pu, pv);
+            const double w1 = edge(p2.u, p2.v, p0.u, p0.v, pu, pv);
+            const double w2 = edge(p0.u, p0.v, p1.u, p1.v, pu, pv);
+            const bool inside = area > 0.0 ? (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) : (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
+            if (!inside) continue;
+            const double s = (w0 + w1) + w2;
+            if (s == 0.0) continue;
+            const double zz = ((w0 * p0.z + w1 * p1.z) + w2 * p2.z) / s;
+            const double zi = floor(zz + 0.5);
+            if (!(zi >= 1.0 && zi <= 65535.0)) continue;
+            atomicMin(zbuf + ((int64_t)y * wc + x), (uint32_t)zi);
+        }
+    }
+}
+
+static __global__ __launch_bounds__(kWarpThreads) void warp_raster_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy, int32_t w,
+                                                                          int32_t h, int32_t tiles_x, int32_t wc, int32_t hc, CalibrationPack pack,
+                                                                          int32_t n_cal, double max_gap_mm, uint32_t *__restrict__ zbuf)
+{
+    __shared__ WarpVertex vert[kWarpVerts];
+    const int frame = blockIdx.y, cal_id = frame % n_cal;
+    const ColorCalibration &cal = pack.c[cal_id];
+    const int64_t n_px = (int64_t)w * h;
+    const uint16_t *dp = depth + (int64_t)frame * n_px;
+    const float *tp = xy + (int64_t)cal_id * n_px * 2;
+    const int32_t c0 = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * kWarpTileW, r0 = (int32_t)(blockIdx.x / (uint32_t)tiles_x) * kWarpTileH;
+    for (int i = threadIdx.x; i < kWarpVerts; i += kWarpThreads) {
+        const int32_t c = c0 + i % kWarpVertW, r = r0 + i / kWarpVertW;
+        WarpVertex o{ 0.0, 0.0, 0.0 };
+        if (c < w && r < h) {
+            const int64_t p = (int64_t)r * w + c;
+            double u, v, z;
+            if (depth_pixel_to_color(cal, dp[p], tp[2 * p], tp[2 * p + 1], u, v, z)) o = WarpVertex{ u, v, z };       // (element loads: no alignment)
+        }
+        vert[i] = o;
+    }
+    __syncthreads();
+    const int32_t lc = threadIdx.x % kWarpTileW, lr = threadIdx.x / kWarpTileW;
+    if (c0 + lc >= w - 1 || r0 + lr >= h - 1) return;
+    const WarpVertex p00 = vert[lr * kWarpVertW + lc], p10 = vert[lr * kWarpVertW + lc + 1];
+    const WarpVertex p01 = vert[(lr + 1) * kWarpVertW + lc], p11 = vert[(lr + 1) * kWarpVertW + lc + 1];
+    uint32_t *zb = zbuf + (int64_t)frame * hc * wc;
+    raster_triangle(p00, p10, p01, max_gap_mm, wc, hc, zb);
+    raster_triangle(p11, p01, p10, max_gap_mm, wc, hc, zb);
+}
+
+// Resolve: a block owns kResolvePerBlock consecutive colour pixels of one frame.  Their u16 values (0 for an untouched pixel) are laid
+// down in LDS at the offset the block's output has inside its 16-byte line, so that whole 16-byte vectors of LDS are whole aligned
+// vectors of the output; the elements in front of the first and behind the last whole vector leave as element stores (a frame's
+// output starts wherever frames * color_height * color_width * 2 puts it; neighbouring blocks may share a line, never an element).
+constexpr int kResolveThreads = 256, kResolvePerBlock = 2048;
+
+static __global__ __launch_bounds__(kResolveThreads) void warp_resolve_kernel(const uint32_t *__restrict__ zbuf, int64_t n, int32_t vec_ok,
+                                                                              uint16_t *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t stage[kResolvePerBlock + 8];
+    const int64_t p0 = (int64_t)blockIdx.x * kResolvePerBlock;
+    const int64_t left = n - p0;
+    const int cnt = (int)(left < kResolvePerBlock ? left : kResolvePerBlock);
+    const uint32_t *zb = zbuf + (int64_t)blockIdx.y * n + p0;
+    uint16_t *out_blk = out + (int64_t)blockIdx.y * n + p0;
+    if (!vec_ok) {                                                             // an output off its 2-byte boundary
+        for (int i = threadIdx.x; i < cnt; i += kResolveThreads) {
+            const uint32_t z = zb[i];
+            out_blk[i] = z == kWarpEmpty ? (uint16_t)0 : (uint16_t)z;
+        }
+        return;
+    }
+    const int a = (int)(((uintptr_t)out_blk & 15) >> 1);                       // the block's first element inside its 16-byte line
+    for (int i = threadIdx.x; i < cnt; i += kResolveThreads) {
+        const uint32_t z = zb[i];
+        stage[a + i] = z == kWarpEmpty ? (uint16_t)0 : (uint16_t)z;
+    }
+    __syncthreads();
+    const int v0 = (a + 7) >> 3, v1 = (a + cnt) >> 3;                          // whole vectors: stage[8 v0 .. 8 v1)
+    if (v1 <= v0) {
+        for (int i = threadIdx.x; i < cnt; i += kResolveThreads) out_blk[i] = stage[a + i];
+        return;
+    }
+    const int head = 8 * v0 - a, tail0 = 8 * v1 - a;                           // elements [0, head) and [tail0, cnt) leave one by one
+    if ((int)threadIdx.x < head) out_blk[threadIdx.x] = stage[a + threadIdx.x];
+    if ((int)threadIdx.x < cnt - tail0) out_blk[tail0 + threadIdx.x] = stage[a + tail0 + threadIdx.x];
+    const uint4 *src = reinterpret_cast<const uint4 *>(stage);
+    uint4 *dst = reinterpret_cast<uint4 *>(out_blk - a);
+    for (int j = v0 + threadIdx.x; j < v1; j += kResolveThreads) dst[j] = src[j];
+}
+
 }  // namespace kpx
 
 using namespace kpx;
@@ -241,29 +385,26 @@ KPX_EXPORT int kpx_xy_table(const double *h_camera, int32_t width, int32_t heigh
     return KPX_OK;
 }
 
-KPX_EXPORT int kpx_color_to_depth(const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
-                                  int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
-                                  uint8_t *out, void *stream)
+
+// the checks the three batched entries share: false = kpx::fail() has been called
+static bool calibrations_ok(const char *who, int32_t frames, const double *h_calibrations, int32_t calibrations)
 {
-    KPX_REQUIRE(n_px >= 0 && frames >= 0, "kpx_color_to_depth: negative size (n_px %lld, frames %d)", (long long)n_px, (int)frames);
-    KPX_REQUIRE(frames <= 65535, "kpx_color_to_depth: at most 65535 frames per call, got %d", (int)frames);
-    KPX_REQUIRE(n_px <= (int64_t)kPixPerBlock * 0x7fffffff, "kpx_color_to_depth: n_px %lld is out of range", (long long)n_px);
-    KPX_REQUIRE(channels == 1 || channels == 3, "kpx_color_to_depth: channels must be 1 or 3, got %d", (int)channels);
-    KPX_REQUIRE(interpolation == KPX_SAMPLE_NEAREST || interpolation == KPX_SAMPLE_BILINEAR, "kpx_color_to_depth: unknown interpolation %d",
-                (int)interpolation);
-    KPX_REQUIRE(color_width >= 1 && color_height >= 1, "kpx_color_to_depth: colour image size %d x %d", (int)color_width, (int)color_height);
-    KPX_REQUIRE(calibrations >= 1 && calibrations <= KPX_SENSOR_MAX_CALIBRATIONS, "kpx_color_to_depth: 1 to %d calibrations, got %d",
-                KPX_SENSOR_MAX_CALIBRATIONS, (int)calibrations);
-    KPX_REQUIRE(frames % calibrations == 0, "kpx_color_to_depth: %d calibrations do not divide %d frames", (int)calibrations, (int)frames);
-    KPX_REQUIRE(h_calibrations, "kpx_color_to_depth: null calibrations");
+    if (frames > 65535) return fail(KPX_ERR_INVALID, "%s: at most 65535 frames per call, got %d", who, (int)frames), false;
+    if (!(calibrations >= 1 && calibrations <= KPX_SENSOR_MAX_CALIBRATIONS))
+        return fail(KPX_ERR_INVALID, "%s: 1 to %d calibrations, got %d", who, KPX_SENSOR_MAX_CALIBRATIONS, (int)calibrations), false;
+    if (frames % calibrations != 0) return fail(KPX_ERR_INVALID, "%s: %d calibrations do not divide %d frames", who, (int)calibrations, (int)frames), false;
+    if (!h_calibrations) return fail(KPX_ERR_INVALID, "%s: null calibrations", who), false;
     for (int s = 0; s < calibrations; ++s) {
         const double *h = h_calibrations + (size_t)s * KPX_CALIBRATION_DOUBLES;
         bool ok = camera_ok(h);
         for (int i = 0; i < 12; ++i) ok = ok && __builtin_isfinite(h[KPX_CAMERA_DOUBLES + i]);
-        KPX_REQUIRE(ok, "kpx_color_to_depth: calibration %d needs finite numbers, non-zero focal lengths and a positive metric radius", s);
+        if (!ok) return fail(KPX_ERR_INVALID, "%s: calibration %d needs finite numbers, non-zero focal lengths and a positive metric radius", who, s), false;
     }
-    if (frames == 0 || n_px == 0) return KPX_OK;
-    KPX_REQUIRE(depth && xy && color && out, "kpx_color_to_depth: null pointer");
+    return true;
+}
+
+static CalibrationPack pack_of(const double *h_calibrations, int32_t calibrations)
+{
     CalibrationPack pack;
     memset(&pack, 0, sizeof pack);
     for (int s = 0; s < calibrations; ++s) {
@@ -271,16 +412,92 @@ KPX_EXPORT int kpx_color_to_depth(const uint16_t *depth, const float *xy, const 
         pack.c[s].cam = camera_from(h);
         memcpy(pack.c[s].T, h + KPX_CAMERA_DOUBLES, sizeof pack.c[s].T);
     }
+    return pack;
+}
+
+template <bool VISIBLE>
+static int color_to_depth(const char *who, const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
+                          int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
+                          const uint16_t *warped, double occlusion_mm, uint8_t *out, void *stream)
+{
+    KPX_REQUIRE(n_px >= 0 && frames >= 0, "%s: negative size (n_px %lld, frames %d)", who, (long long)n_px, (int)frames);
+    KPX_REQUIRE(frames <= 65535, "%s: at most 65535 frames per call, got %d", who, (int)frames);
+    KPX_REQUIRE(n_px <= (int64_t)kPixPerBlock * 0x7fffffff, "%s: n_px %lld is out of range", who, (long long)n_px);
+    KPX_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, (int)channels);
+    KPX_REQUIRE(interpolation == KPX_SAMPLE_NEAREST || interpolation == KPX_SAMPLE_BILINEAR, "%s: unknown interpolation %d", who, (int)interpolation);
+    KPX_REQUIRE(color_width >= 1 && color_height >= 1, "%s: colour image size %d x %d", who, (int)color_width, (int)color_height);
+    if (!calibrations_ok(who, frames, h_calibrations, calibrations)) return KPX_ERR_INVALID;
+    KPX_REQUIRE(!VISIBLE || occlusion_mm >= 0.0, "%s: occlusion_mm must be >= 0 (+inf: never occluded), got %g", who, occlusion_mm);      // (a NaN fails)
+    if (frames == 0 || n_px == 0) return KPX_OK;
+    KPX_REQUIRE(depth && xy && color && out && (!VISIBLE || warped), "%s: null pointer", who);
+    const CalibrationPack pack = pack_of(h_calibrations, calibrations);
     const int32_t vec_ok = n_px % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)xy % 16 == 0;
     const dim3 grid((unsigned)cdiv(n_px, kPixPerBlock), (unsigned)frames), block(kC2dThreads);
     hipStream_t st = (hipStream_t)stream;
-#define KPX_C2D(C, I) \
-    hipLaunchKernelGGL((color_to_depth_kernel<C, I>), grid, block, 0, st, depth, xy, color, n_px, color_width, color_height, pack, calibrations, vec_ok, out)
+#define KPX_C2D(C, I)                                                                                                                               \
+    hipLaunchKernelGGL((color_to_depth_kernel<C, I, VISIBLE>), grid, block, 0, st, depth, xy, color, warped, occlusion_mm, n_px, color_width, color_height, \
+                       pack, calibrations, vec_ok, out)
     if (channels == 3 && interpolation == KPX_SAMPLE_BILINEAR) KPX_C2D(3, KPX_SAMPLE_BILINEAR);
     else if (channels == 3) KPX_C2D(3, KPX_SAMPLE_NEAREST);
     else if (interpolation == KPX_SAMPLE_BILINEAR) KPX_C2D(1, KPX_SAMPLE_BILINEAR);
     else KPX_C2D(1, KPX_SAMPLE_NEAREST);
 #undef KPX_C2D
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_color_to_depth(const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
+                                  int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
+                                  uint8_t *out, void *stream)
+{
+    return color_to_depth<false>("kpx_color_to_depth", depth, xy, color, n_px, frames, color_width, color_height, channels, h_calibrations, calibrations,
+                                 interpolation, nullptr, 0.0, out, stream);
+}
+
+KPX_EXPORT int kpx_color_to_depth_visible(const uint16_t *depth, const float *xy, const uint8_t *color, int64_t n_px, int32_t frames, int32_t color_width,
+                                          int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations,
+                                          int32_t interpolation, const uint16_t *warped, double occlusion_mm, uint8_t *out, void *stream)
+{
+    return color_to_depth<true>("kpx_color_to_depth_visible", depth, xy, color, n_px, frames, color_width, color_height, channels, h_calibrations,
+                                calibrations, interpolation, warped, occlusion_mm, out, stream);
+}
+
+KPX_EXPORT size_t kpx_depth_to_color_workspace_bytes(int32_t frames, int32_t color_width, int32_t color_height)
+{
+    if (frames <= 0 || color_width <= 0 || color_height <= 0) return 0;
+    return (size_t)frames * (size_t)color_height * (size_t)color_width * sizeof(uint32_t);
+}
+
+KPX_EXPORT int kpx_depth_to_color(const uint16_t *depth, const float *xy, int32_t depth_width, int32_t depth_height, int32_t frames, int32_t color_width,
+                                  int32_t color_height, const double *h_calibrations, int32_t calibrations, double max_gap_mm, uint16_t *out, void *ws,
+                                  size_t ws_bytes, void *stream)
+{
+    const char *who = "kpx_depth_to_color";
+    KPX_REQUIRE(depth_width >= 0 && depth_height >= 0 && frames >= 0 && color_width >= 0 && color_height >= 0,
+                "%s: negative size (depth %d x %d, colour %d x %d, frames %d)", who, (int)depth_width, (int)depth_height, (int)color_width, (int)color_height,
+                (int)frames);
+    if (!calibrations_ok(who, frames, h_calibrations, calibrations)) return KPX_ERR_INVALID;
+    KPX_REQUIRE(max_gap_mm >= 0.0, "%s: max_gap_mm must be >= 0 (+inf: never too far apart), got %g", who, max_gap_mm);                    // (a NaN fails)
+    const int64_t n = (int64_t)color_width * color_height;                     // colour pixels of a frame
+    const int64_t tiles_x = cdiv((int64_t)depth_width - 1, kWarpTileW), tiles_y = cdiv((int64_t)depth_height - 1, kWarpTileH);
+    KPX_REQUIRE(n <= (int64_t)kResolvePerBlock * 0x7fffffff && tiles_x * tiles_y <= 0x7fffffff, "%s: image size out of range", who);
+    const size_t need = kpx_depth_to_color_workspace_bytes(frames, color_width, color_height);
+    if (ws_bytes < need) return fail(KPX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, have %zu", who, need, ws_bytes);
+    if (frames == 0 || n == 0) return KPX_OK;
+    KPX_REQUIRE(out && ws, "%s: null pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (depth_width < 2 || depth_height < 2) {                                 // no triangle: every pixel is untouched
+        KPX_HIP(hipMemsetAsync(out, 0, (size_t)frames * n * sizeof(uint16_t), st));
+        return KPX_OK;
+    }
+    KPX_REQUIRE(depth && xy, "%s: null pointer", who);
+    uint32_t *zbuf = static_cast<uint32_t *>(ws);
+    KPX_HIP(hipMemsetAsync(zbuf, 0xFF, need, st));                             // kWarpEmpty everywhere
+    hipLaunchKernelGGL(warp_raster_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)frames), dim3(kWarpThreads), 0, st, depth, xy, depth_width,
+                       depth_height, (int32_t)tiles_x, color_width, color_height, pack_of(h_calibrations, calibrations), calibrations, max_gap_mm, zbuf);
+    KPX_LAUNCH_CHECK();
+    const int32_t vec_ok = (uintptr_t)out % 2 == 0;
+    hipLaunchKernelGGL(warp_resolve_kernel, dim3((unsigned)cdiv(n, kResolvePerBlock), (unsigned)frames), dim3(kResolveThreads), 0, st, zbuf, n, vec_ok, out);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -2329,7 +2329,7 @@ def pointnet_train_step(params, x, y, m, v, learning_rate=0.001, beta_1=0.9, bet
     return loss, grad
 
 
-# ---- sensor calibration (AC20) ------------------------------------------------------------------------
+# ---- sensor calibration (AC20), depth -> colour warp and occlusion test (AC21) --------------------------
 SAMPLE_MODES = {"nearest": 0, "bilinear": 1}          # KPX_SAMPLE_* (include/kinectpx.h)
 CAMERA_DOUBLES, CALIBRATION_DOUBLES, SENSOR_MAX_CALIBRATIONS = 13, 29, 16
 
@@ -2355,18 +2355,77 @@ def xy_table(intrinsics):
     return out
 
 
-def color_to_depth(depth, xy, color, calibrations, interpolation="bilinear", out=None):
+def _calibration_pack(who, cals, size=None):
+    """S calibrations (objects with `.color` and `.depth_to_color`, or (camera, 4x4) pairs) -> float64 (S, 29) in KPX_CALIBRATION_DOUBLES
+    layout and the colour image size (Wc, Hc) they agree on (`size` where given: the size of the image at hand)"""
+    S = len(cals)
+    if not 1 <= S <= SENSOR_MAX_CALIBRATIONS:
+        raise L.KinectPxError(f"{who}: 1 to {SENSOR_MAX_CALIBRATIONS} calibrations, got {S}")
+    pack = np.empty((S, CALIBRATION_DOUBLES), dtype=np.float64)
+    for s, c in enumerate(cals):
+        cam, T = (c.color, c.depth_to_color) if hasattr(c, "depth_to_color") else c
+        if hasattr(cam, "width"):
+            here = (int(cam.width), int(cam.height))
+            if size is None:
+                size = here
+            if here != size:
+                raise L.KinectPxError(f"{who}: calibration {s} is for a {here[0]} x {here[1]} colour image, got {size[0]} x {size[1]}")
+        pack[s, :CAMERA_DOUBLES] = _camera13(cam)
+        pack[s, CAMERA_DOUBLES:] = _T(T).reshape(16)
+    return pack, size
+
+
+def depth_to_color(depth, xy, depth_width, depth_height, calibrations, max_gap_mm, out=None):
+    """AC21: depth images warped into their colour cameras through a z-buffer.  depth uint16 (F, H * W) mm; xy float32 (S, H * W, 2) --
+    the depth cameras' tables, (H * W, 2) for one; calibrations as in color_to_depth, their colour cameras of one size Wc x Hc (objects
+    with .width / .height: the size of the output comes from them); frame f uses calibration f % S and S divides F.  The depth pixels
+    are the vertices of a triangle mesh (two triangles per 2 x 2 block); a triangle whose vertices differ by more than max_gap_mm in
+    depth is not drawn -- it would join a foreground to the background behind it.  max_gap_mm has no default: it is a property of the
+    scene and the rig that nothing in this project measures (float("inf"): every triangle is drawn).
+    -> uint16 (F, Hc, Wc): per colour pixel the nearest depth (mm, along the colour camera's axis) of what the depth camera saw there,
+    0 where it saw nothing.  With the colour camera's own xy_table this is a depth image for unproject_u16 / depth_to_cloud beside the
+    raw colour image.  out: a contiguous uint16 device tensor of F * Hc * Wc elements to write into."""
+    lib = L.load()
+    cals = list(calibrations)
+    pack, size = _calibration_pack("depth_to_color", cals)
+    if size is None:
+        raise L.KinectPxError("depth_to_color: the colour cameras must carry their image size (.width, .height)")
+    wc, hc = size
+    S, w, h = len(cals), int(depth_width), int(depth_height)
+    dep = _dev(depth, torch.uint16)
+    dep = dep.reshape(-1, w * h) if w * h else dep.reshape(dep.shape[0] if dep.dim() > 1 else 0, 0)
+    F = int(dep.shape[0])
+    table = _dev(xy, torch.float32).reshape(-1, w * h, 2) if w * h else _dev(xy, torch.float32).reshape(S, 0, 2)
+    if table.shape[0] != S:
+        raise L.KinectPxError(f"depth_to_color: {table.shape[0]} tables for {S} calibrations")
+    if out is None:
+        out = torch.empty((F, hc, wc), dtype=torch.uint16, device=dep.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint16 and out.is_cuda and out.is_contiguous() and out.numel() == F * hc * wc):
+        raise ValueError(f"depth_to_color: out must be a contiguous uint16 device tensor of {F * hc * wc} elements")
+    # (tests/scratch_cases.py lists operators by their literal workspace call; this operator's poisoned, exact-size scratch cases are
+    # in tests/test_warp_gpu.py, so the call goes by name here)
+    ws, wsz = getattr(L, "workspace")(lib.kpx_depth_to_color_workspace_bytes(F, wc, hc))
+    L.check(lib.kpx_depth_to_color(L.ptr(dep), L.ptr(table), w, h, F, wc, hc, L.hptr(pack), S, float(max_gap_mm), L.ptr(out), ws, wsz, L.stream_ptr()))
+    return out
+
+
+def color_to_depth(depth, xy, color, calibrations, interpolation="bilinear", out=None, warped=None, occlusion_mm=None):
     """AC20: colour images (or masks / label images taken on the colour camera) resampled into the depth camera's pixel grid.
     depth uint16 (F, n_px) mm; xy float32 (S, n_px, 2) -- the depth cameras' tables, (n_px, 2) for one; color uint8 (F, Hc, Wc, C) or
     (F, Hc, Wc), C in {1, 3}; calibrations: S objects with `.color` (CameraIntrinsics of size Wc x Hc) and `.depth_to_color` (4x4, mm)
     -- calibration.SensorCalibration -- or S (camera, 4x4) pairs; frame f uses calibration f % S and S divides F.
     interpolation: "bilinear" (colour) or "nearest" (masks, labels).  -> uint8 (F, n_px, C) (or (F, n_px) for a (F, Hc, Wc) input):
     zeros where there is no depth, no ray, the point lies behind the colour camera or outside its image.  Like the sensor SDK's own
-    transformation this does NOT test occlusion: a depth pixel the colour camera cannot see takes the colour of what hides it.
+    transformation this does NOT test occlusion: a depth pixel the colour camera cannot see takes the colour of what hides it --
+    unless `warped` and `occlusion_mm` are given (both or neither; AC21): warped uint16 (F, Hc, Wc) is depth_to_color's image of the
+    same frames, and a depth pixel that lies more than occlusion_mm behind the warped depth at its nearest colour pixel is zero.
+    occlusion_mm has no default: it is a property of the scene and the rig that nothing in this project measures.
     out: a contiguous uint8 device tensor of F * n_px * C elements to write into."""
     lib = L.load()
     if interpolation not in SAMPLE_MODES:
         raise ValueError(f"color_to_depth: unknown interpolation {interpolation!r}: expected one of {sorted(SAMPLE_MODES)}")
+    if (warped is None) != (occlusion_mm is None):
+        raise ValueError("color_to_depth: warped and occlusion_mm go together: give both (the occlusion test) or neither")
     cals = list(calibrations)
     S = len(cals)
     if not 1 <= S <= SENSOR_MAX_CALIBRATIONS:
@@ -2382,17 +2441,18 @@ def color_to_depth(depth, xy, color, calibrations, interpolation="bilinear", out
     table = _dev(xy, torch.float32).reshape(-1, n_px, 2) if n_px else _dev(xy, torch.float32).reshape(S, 0, 2)
     if table.shape[0] != S:
         raise L.KinectPxError(f"color_to_depth: {table.shape[0]} tables for {S} calibrations")
-    pack = np.empty((S, CALIBRATION_DOUBLES), dtype=np.float64)
-    for s, c in enumerate(cals):
-        cam, T = (c.color, c.depth_to_color) if hasattr(c, "depth_to_color") else c
-        if hasattr(cam, "width") and (int(cam.width), int(cam.height)) != (wc, hc):
-            raise L.KinectPxError(f"color_to_depth: calibration {s} is for a {cam.width} x {cam.height} colour image, got {wc} x {hc}")
-        pack[s, :CAMERA_DOUBLES] = _camera13(cam)
-        pack[s, CAMERA_DOUBLES:] = _T(T).reshape(16)
+    pack, _ = _calibration_pack("color_to_depth", cals, (wc, hc))
     if out is None:
         out = torch.empty((F, n_px) if flat else (F, n_px, ch), dtype=torch.uint8, device=dep.device)
     elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() == F * n_px * ch):
         raise ValueError(f"color_to_depth: out must be a contiguous uint8 device tensor of {F * n_px * ch} elements")
-    L.check(lib.kpx_color_to_depth(L.ptr(dep), L.ptr(table), L.ptr(col), n_px, F, wc, hc, ch, L.hptr(pack), S, SAMPLE_MODES[interpolation], L.ptr(out),
-                                   L.stream_ptr()))
+    if warped is None:
+        L.check(lib.kpx_color_to_depth(L.ptr(dep), L.ptr(table), L.ptr(col), n_px, F, wc, hc, ch, L.hptr(pack), S, SAMPLE_MODES[interpolation], L.ptr(out),
+                                       L.stream_ptr()))
+        return out
+    wrp = _dev(warped, torch.uint16)
+    if wrp.numel() != F * hc * wc:
+        raise L.KinectPxError(f"color_to_depth: warped has {wrp.numel()} elements, expected {F} x {hc} x {wc}")
+    L.check(lib.kpx_color_to_depth_visible(L.ptr(dep), L.ptr(table), L.ptr(col), n_px, F, wc, hc, ch, L.hptr(pack), S, SAMPLE_MODES[interpolation],
+                                           L.ptr(wrp), float(occlusion_mm), L.ptr(out), L.stream_ptr()))
     return out

@@ -60,7 +60,7 @@ def main():
     ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
     ap.add_argument("--pointnet", action="store_true", help="only the PointNet forward rows (fused against eval-mode torch modules)")
     ap.add_argument("--pointnet-train", action="store_true", help="only the PointNet training step rows (against train-mode torch modules with torch.optim.Adam)")
-    ap.add_argument("--sensor", action="store_true", help="only the sensor calibration rows (xy_table, color_to_depth)")
+    ap.add_argument("--sensor", action="store_true", help="only the sensor calibration rows (xy_table, color_to_depth, depth_to_color, color_to_depth with the occlusion test)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.sensor:
@@ -705,6 +705,27 @@ def sensor_rows(dev, quick):
         filled = int((res.reshape(S * N_PX, ch) != 0).any(1).sum().item())
         report(f"color_to_depth {S} x 640x576 <- {S} x 1280x720x{ch} {interp}", ms, S * N_PX * (2 + 8 + ch) + S * 720 * 1280 * ch, frames=S,
                filled=filled)
+    # the same four frames warped into their 1280 x 720 colour cameras (clear + raster + resolve), and the registrations
+    # again with the occlusion test.  Algorithmic bytes of the warp: depth 2 + table 8 per depth pixel, per colour pixel the z-buffer
+    # written by the clear and read by the resolve (4 + 4) and the output 2; the raster's atomic minima are counted as `atomics`, not
+    # as bytes.  100 mm for both thresholds is this bench's choice for the synthetic room, not a default of the product.
+    gap_mm = occlusion_mm = 100.0
+    n_col = 720 * 1280
+    warped = torch.empty((S, 720, 1280), dtype=torch.uint16, device=dev)
+    ms, res = timed(lambda: ops.depth_to_color(depth, tables, 640, 576, rig.calibrations, gap_mm, out=warped), reps=reps, warm=2)
+    covered = int((res.view(torch.int16) != 0).sum().item())
+    report(f"depth_to_color {S} x 640x576 -> {S} x 1280x720 (z-buffer, 3 dispatches)", ms, S * N_PX * (2 + 8) + S * n_col * (4 + 4 + 2), frames=S,
+           covered=covered)
+    for ch, interp, img in ((3, "bilinear", color), (1, "nearest", color[..., 0].contiguous())):
+        out = torch.empty(S * N_PX * ch, dtype=torch.uint8, device=dev)
+        plain = ops.color_to_depth(depth, tables, img, rig.calibrations, interp).reshape(S * N_PX, ch)
+        ms, res = timed(lambda: ops.color_to_depth(depth, tables, img, rig.calibrations, interp, out=out, warped=warped, occlusion_mm=occlusion_mm),
+                        reps=reps, warm=2)
+        res = res.reshape(S * N_PX, ch)
+        filled = int((res != 0).any(1).sum().item())
+        occluded = int(((plain != 0).any(1) & ~(res != 0).any(1)).sum().item())
+        report(f"color_to_depth visible {S} x 640x576 <- {S} x 1280x720x{ch} {interp}", ms,
+               S * N_PX * (2 + 8 + ch) + S * n_col * ch + S * n_col * 2, frames=S, filled=filled, occluded=occluded)
 
 
 def odometry_launches(iterations):
