@@ -36,7 +36,17 @@ constexpr int kFRowsPerBlock = kWaves * kFRT * 16; // 256
 constexpr int kFCT = 64;                     // f32 tiles per LDS stage (16 KiB)
 constexpr int kFStageFloats = kFCT * 64;
 constexpr int kCand = 64;                    // candidate slots per source row
-constexpr int kAcc = 44;                     // accumulator slots: count, sum d2, sum s, sum t, sum t s^T, J^T J (21), J^T r (6)
+constexpr int kAcc = 44;                     // accumulator slots: 0 count, 1 sum d2, 2..4 sum s, 5..7 sum t, 8..16 sum t s^T, 17..37 J^T J (21), 38..43 J^T r (6)
+// Which slots a mode's update reads -- and the culled engine's iteration kernels therefore produce, stage, sum, add and read back:
+// point-to-point (icp_finish / update_p2p) slots 0..16; point-to-plane (update_p2plane) count, sum d2 and the 27 plane slots, 29 of
+// the 44: fitness, rmse, the convergence test, the 6x6 system and LightSkip's bookkeeping use none of slots 2..16.  The slot NUMBERS
+// and the accumulators' layout are the same in both modes (the merge kernels and icp_solve_kernel share the numbering; GICP, the
+// coloured and the robust modes fill slots 0..16 AND 17..43 there); a slot that is not live stays at the zero the accumulators are
+// cleared to, and its total is 0.0 without a load.
+// In either mode the live slots are 0, 1 and ONE range [acc_lo, acc_hi): loops over them need no test per slot.
+__host__ __device__ constexpr int acc_lo(bool plane) { return plane ? 17 : 2; }
+__host__ __device__ constexpr int acc_hi(bool plane) { return plane ? kAcc : 17; }
+__host__ __device__ constexpr bool acc_live(bool plane, int slot) { return (slot >= 0 && slot < 2) || (slot >= acc_lo(plane) && slot < acc_hi(plane)); }
 
 struct IcpState {
     double T[16];
@@ -95,19 +105,23 @@ __device__ __forceinline__ double plane_row(const double s[3], const double t[3]
     J[3] = nx; J[4] = ny; J[5] = nz;
     return (s[0] - t[0]) * nx + (s[1] - t[1]) * ny + (s[2] - t[2]) * nz;
 }
-// What a pair within the correspondence distance adds to the update sums, handed to put(slot, value): the 17 point-to-point terms
-// (count, d2, s, t, t s^T) and, with `plane`, the 27 point-to-plane terms (J^T J upper triangle, J^T r).  Every form of the iteration
-// gets its terms here, which is what keeps them equal to the last bit.
+// What a pair within the correspondence distance adds to the update sums, handed to put(slot, value): count and d2, with `point`
+// the 15 point-to-point terms (s, t, t s^T: slots 2..16), with `plane` the 27 point-to-plane terms (J^T J upper triangle, J^T r:
+// slots 17..43).  Every form of the iteration gets its terms here, which is what keeps them equal to the last bit.  The culled
+// engine's kernels ask for the slots that are live in their mode (acc_live: point = !plane); the dense engine's merge kernel, whose
+// sums are a partial row per block and not atomics, keeps filling all of them (point = true).
 template <class Put>
-__device__ __forceinline__ void pair_terms(const double s[3], const double t[3], double d2, bool plane, const float *nrm, Put put)
+__device__ __forceinline__ void pair_terms(const double s[3], const double t[3], double d2, bool point, bool plane, const float *nrm, Put put)
 {
     put(0, 1.0); put(1, d2);
+    if (point) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { put(2 + c, s[c]); put(5 + c, t[c]); }
+        for (int c = 0; c < 3; ++c) { put(2 + c, s[c]); put(5 + c, t[c]); }
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
+        for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) put(8 + 3 * a + c, t[a] * s[c]);
+            for (int c = 0; c < 3; ++c) put(8 + 3 * a + c, t[a] * s[c]);
+    }
     if (plane) {
         double J[6];
         const double res = plane_row(s, t, nrm, J);

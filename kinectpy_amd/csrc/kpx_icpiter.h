@@ -171,12 +171,12 @@ __device__ __forceinline__ IcpFuse ticket_fuse(const IcpProblem &P, int max_iter
                     (light & 2) ? P.thist : (double *)nullptr, (light & 4) ? 1 : 0, pol, chain_rec, stamp };
 }
 // The winner's step (the block that drew its registration's last ticket, THREADS threads, tix_w the caller's thread number behind an
-// opaque move), first part: the coherent totals into s_sums, the searched-row count (SEARCHED; returned), then -- the block's
+// opaque move), first part: the coherent totals of the mode's live slots into s_sums (0.0 for the others, without a load), the searched-row count (SEARCHED; returned), then -- the block's
 // s_sums complete -- the accumulators cleared and the ticket reset for the next launch.
 template <int THREADS, bool SEARCHED>
-__device__ __forceinline__ unsigned long long winner_take(unsigned long long *acc, unsigned long long *ticket, int nacc, double *s_sums, int tix_w)
+__device__ __forceinline__ unsigned long long winner_take(unsigned long long *acc, unsigned long long *ticket, bool plane, double *s_sums, int tix_w)
 {
-    if (tix_w < kAcc) s_sums[tix_w] = tix_w < nacc ? fixed_total_coherent(acc, tix_w) : 0.0;
+    if (tix_w < kAcc) s_sums[tix_w] = acc_live(plane, tix_w) ? fixed_total_coherent(acc, tix_w) : 0.0;
     const unsigned long long n_searched = SEARCHED ? searched_take(ticket, tix_w) : 0ull;
     if (THREADS > 64) __syncthreads(); else wave_lds_fence();
     for (int e = tix_w; e < kAccSet; e += THREADS) __hip_atomic_store(acc + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -289,7 +289,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
         IcpState *out = fuse.pair + (k & 1);
         // state and accumulators are read in ONE round trip (the sums of a converged chain are simply not used)
         const unsigned long long *prev = fuse.ring + (int64_t)((k + 2) % 3) * kAccSet;
-        if (k > 0 && tix < kAcc) s_sums[tix] = (int)tix < (mode == 1 ? kAcc : 17) ? fixed_total(prev, tix) : 0.0;
+        if (k > 0 && tix < kAcc) s_sums[tix] = acc_live(mode == 1, (int)tix) ? fixed_total(prev, tix) : 0.0;
         if (tix == 0) s_state = *in;
         __syncthreads();
         if (s_state.done) {                               // converged earlier: hand the state on, nothing else to do
@@ -471,7 +471,8 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     const int lane_e = lane_p, wave_e = wave_p;
     if (lane_e < 16) {
         const int col = wave_e * 16 + lane_e;
-        for (int a = 0; a < nacc; ++a) sh[a][col] = 0.0;
+        sh[0][col] = 0.0; sh[1][col] = 0.0;                  // the live slots: 0, 1 and [acc_lo, acc_hi)
+        for (int a = acc_lo(mode == 1); a < nacc; ++a) sh[a][col] = 0.0;
         if (row_base_p + lane_e <= last) {
             const int32_t bj = rowi[wave_e][lane_e][0];
             const int64_t i = rowi[wave_e][lane_e][1];
@@ -512,7 +513,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
                 const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
                 const double d2 = pair_d2(s, t);
                 if (d2_cur) d2_cur[i] = d2;
-                if (d2 < max_d2) pair_terms(s, t, d2, mode == 1, nf, [&](int slot, double v) { sh[slot][col] = v; });
+                if (d2 < max_d2) pair_terms(s, t, d2, mode != 1, mode == 1, nf, [&](int slot, double v) { sh[slot][col] = v; });
             }
         }
     }
@@ -522,8 +523,9 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     // value per lane known from the kernel's first instruction, was otherwise computed there and carried -- spilled -- across the sweep;
     // every spilled dword is 256 B of scratch per wave written back to HBM at the end of the launch: 0.5 MB per launch at 31k rows)
     const int tix_e = wave_e * 64 + lane_e;
-    if (tix_e < nacc) {
-        // The sums' contract (round 5): per 16-row TILE a balanced tree over adjacent rows (tile_tree16: what four DPP steps give a
+    if (tix_e < nacc && acc_live(mode == 1, tix_e)) {
+        // The sums' contract (round 5), for the slots that are live in the mode (acc_live: 0..16 point-to-point; 0, 1 and 17..43 point-to-plane;
+        // a slot that is not live is neither staged in sh nor summed nor added, and the winner takes its total as 0.0): per 16-row TILE a balanced tree over adjacent rows (tile_tree16: what four DPP steps give a
         // wave that holds one row per lane, icp_rows_kernel), the tiles' partials then added EXACTLY in 128-bit fixed point -- so the
         // totals do not depend on how tiles are dealt out to waves, blocks or launches, and every form of the iteration agrees bit for bit.
         unsigned long long lo = 0ull, hi = 0ull;
@@ -562,7 +564,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     if (!fuse.ticket) return;
     // "The last block finishes the job": every add above has RETURNED (it has been performed at the device's point of coherence),
     // the barrier orders the block's ticket behind them, and the block that draws the last ticket of its registration reads the
-    // totals -- 8 x 44 pairs of words -- with device-coherent loads, clears them for the next launch and performs the update.
+    // totals -- 8 pairs of words for each of the mode's 17 / 29 live slots -- with device-coherent loads, clears the whole set for the next launch and performs the update.
     // Only relaxed atomics on the producers' side: no release fence, which on this part writes back the XCD's L2 (measured 10x slower,
     // once per block).  The CONSUMER side is by the book: the winner -- one block per registration and launch -- acquires at agent
     // scope behind its ticket (a single buffer_inv; same-box A/B against none: equal within noise, profiles/r03/exp_icp_acquire_fence.txt).
@@ -586,7 +588,7 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the winner only: one per registration and launch
     // (the winner's thread number behind an opaque move as well: addresses derived from it are then formed here, not in front of the sweep)
     const int tix_w = opaque_i((int)threadIdx.x);
-    const unsigned long long n_searched = winner_take<kIThreads, !PERSIST>(acc, fuse.ticket, nacc, s_sums, tix_w);
+    const unsigned long long n_searched = winner_take<kIThreads, !PERSIST>(acc, fuse.ticket, mode == 1, s_sums, tix_w);
     if (PERSIST) chain_tick(fuse.stamp, 7, tix == 0);         // (the clearing stores are issued, not waited for)
     // PERSIST: the blocks that see the next record add to these accumulators at once, so every clearing store (and the ticket's) must
     // have been performed before the record is published: each wave drains its stores, the block meets at a barrier (wave 0 after the

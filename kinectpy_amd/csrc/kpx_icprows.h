@@ -3,15 +3,15 @@
 // icp_iter_body gives every 16-row tile a wave and every 64 rows a block of four: right for the first iterations, where every tile
 // is searched, and wasteful afterwards -- from iteration ~10 on 95-99.9 % of the rows carry a certificate ("Certificates", kpx_icpiter.h),
 // a block then lives ~8.6 us of which the search is 0.3, and only 16 of a wave's 64 lanes do the per-row work (transform, bound,
-// certificate test, the 44 products of the update sums).  With four frames in flight the chip's wave slots x a block's life time IS the
+// certificate test, the 17 / 29 terms of the update sums).  With four frames in flight the chip's wave slots x a block's life time IS the
 // frame rate, so here
 //   * a block is ONE wave and owns 64 consecutive sorted rows, one row per lane in the prologue (rows, previous partners and their
 //     coordinates / normals, certificates: coalesced loads; AC1, the partner's AC2 value, the certificate test) and in the pair epilogue
-//     (AC3, the 17 / 44 contributions);
+//     (AC3, the 17 / 29 contributions: the slots that are live in the mode, acc_live in kpx_icpdefs.h);
 //   * the wave sweeps only those of its four 16-row tiles that hold an uncertified row, one after the other, through the same
 //     sweep_wave (kpx_nnlocal.h) on the tile's row records in LDS -- partners are those of icp_iter_body bit for bit;
 //   * the sums follow the contract stated in icp_iter_body: per tile the balanced tree of four DPP butterfly steps
-//     (row16_tree_sum == tile_tree16), the four tile partials added exactly in fixed point, one pair of returning atomics per sum;
+//     (row16_tree_sum == tile_tree16), the four tile partials added exactly in fixed point, one pair of returning atomics per live sum;
 //   * the block that draws the registration's last ticket performs the update (icp_finish_wave), as in icp_iter_body's ticket mode;
 //   * the launch takes the argument block of icp_iter_batch_kernel (IcpBatchArgs: one frame's registrations onto their shared target,
 //     all at iteration p[..].k), and the row prologue, the pair terms and the winner's step are the functions icp_iter_body calls.
@@ -41,7 +41,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
 {
     constexpr int NACC = MODE == 1 ? kAcc : 17;
     // (the descriptor by VALUE: read through a reference into the argument block, field by field where it is used, the kernel came out
-    // with 22 / 4 spilled vector registers (MODE 1 / 0) instead of 18 / 2 -- one more double carried through the sweep in scratch memory)
+    // with 22 / 4 spilled vector registers (MODE 1 / 0) instead of 18 / 2 -- one more double carried through the sweep in scratch memory;
+    // measured while MODE 1 still carried the 15 sums point-to-plane does not read: without them it spills 2, like MODE 0)
     const IcpProblem P = args.p[batch_problem(args)];
     const unsigned bid = blockIdx.x - P.block0;
     const int k = P.k;
@@ -211,7 +212,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
         if (certs && cert_check && lane_e == 0) cert_check_count(bid == 0, k, st, c_skin, __builtin_popcountll(certd64), __builtin_popcountll(act64 & ~certd64));
         if (tile_visits && lane_e == 0 && visited_total) atomicAdd(tile_visits + (blockIdx.x & (kVisitSlots - 1)), (unsigned long long)visited_total);
 
-        // the chosen pairs: direct distance (AC3), contribution to the sums -- one row per lane
+        // the chosen pairs: direct distance (AC3), contribution to the sums -- one row per lane.  Only the slots that are live in the mode
+        // (acc_live, kpx_icpdefs.h) exist from here on: the others are never formed, summed, parked in s_part or added
+        constexpr bool PLANE = MODE == 1;
         double c[NACC];
 #pragma unroll
         for (int a = 0; a < NACC; ++a) c[a] = 0.0;
@@ -247,19 +250,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
                 }
                 const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
                 const double d2 = pair_d2(s, t);
-                if (d2 < max_d2) pair_terms(s, t, d2, MODE == 1, nf, [&](int slot, double v) { c[slot] = v; });
+                if (d2 < max_d2) pair_terms(s, t, d2, !PLANE, PLANE, nf, [&](int slot, double v) { c[slot] = v; });
             }
         }
         // per tile the balanced tree (every lane of the tile's DPP row ends with the tile's partial), then the four partials exactly
 #pragma unroll
-        for (int a = 0; a < NACC; ++a) c[a] = row16_tree_sum(c[a]);
+        for (int a = 0; a < NACC; ++a)
+            if (acc_live(PLANE, a)) c[a] = row16_tree_sum(c[a]);
         wave_lds_fence();                                     // (the partials take the place of the sweep's scratch)
         if ((lane_e & 15) == 0) {
 #pragma unroll
-            for (int a = 0; a < NACC; ++a) s_part[lane_e >> 4][a] = c[a];
+            for (int a = 0; a < NACC; ++a)
+                if (acc_live(PLANE, a)) s_part[lane_e >> 4][a] = c[a];
         }
         wave_lds_fence();
-        if (lane_e < NACC) {
+        if (lane_e < NACC && acc_live(PLANE, lane_e)) {
             unsigned long long lo = 0ull, hi = 0ull;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -287,7 +292,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPX_ICP_WPE,
     if (tk != P.blocks - 1u) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int lane_w = opaque_i((int)threadIdx.x);
-    const unsigned long long n_searched = winner_take<kRowsBlock, true>(P.ring, ticket, NACC, s_sums, lane_w);
+    const unsigned long long n_searched = winner_take<kRowsBlock, true>(P.ring, ticket, MODE == 1, s_sums, lane_w);
     const double *tbbox_w = P.tbbox;
     asm volatile("" : "+s"(tbbox_w));
     const double t2max_w = target_t2max(tbbox_w);

@@ -331,9 +331,10 @@ __global__ __launch_bounds__(64) void pairs_solve_kernel(const double *__restric
 
 
 // ---- exact accumulation of the update sums (culled engine) --------------------------------------------------------
-// Every block adds its 44 fp64 partial sums to 128-bit fixed-point accumulators (kpx_fixed.h): the totals do not
-// depend on the order of the blocks, so the registration stays bitwise reproducible with ONE pair of words per sum
-// instead of one partial row per block -- the solve kernel reads 8 x 44 pairs instead of N/64 x 44 doubles.
+// Every block adds its fp64 partial sums -- the 17 / 29 of the 44 slots that are live in the mode (acc_live, kpx_icpdefs.h) -- to
+// 128-bit fixed-point accumulators (kpx_fixed.h): the totals do not depend on the order of the blocks, so the registration stays
+// bitwise reproducible with ONE pair of words per sum instead of one partial row per block -- the solve kernel reads 8 pairs per
+// live slot instead of N/64 x 44 doubles.
 // kAccCopies copies (block & 7) keep the same-address atomic traffic low.
 constexpr int kAccCopies = 8;
 __device__ __forceinline__ double fixed_total(const unsigned long long *acc, int slot)
@@ -373,8 +374,7 @@ __global__ __launch_bounds__(256) void icp_solve_fixed_kernel(unsigned long long
 {
     if (st->done) return;
     __shared__ double sums[kAcc];
-    const int nacc = mode == 1 ? kAcc : 17;
-    if (threadIdx.x < kAcc) sums[threadIdx.x] = (int)threadIdx.x < nacc ? fixed_total(acc, threadIdx.x) : 0.0;
+    if (threadIdx.x < kAcc) sums[threadIdx.x] = acc_live(mode == 1, (int)threadIdx.x) ? fixed_total(acc, threadIdx.x) : 0.0;     // (only live slots were added to)
     __syncthreads();
     for (int e = threadIdx.x; e < kAccCopies * kAcc * kFixedWords; e += 256) acc[e] = 0ull;
     __shared__ FinishScratch fs;

@@ -595,7 +595,7 @@ __global__ __launch_bounds__(kMergeThreads) void nn_merge_kernel(const float *__
             if (mode >= 0 && d2 < max_d2) {
                 // (the plain point-to-plane terms come with the point-to-point ones; GICP, the robust losses and the coloured mode form theirs below)
                 const bool plane = !Terms::kGicp && !Terms::kRobust && mode == 1;
-                pair_terms(s, t, d2, plane, plane ? tn + 3 * (int64_t)bj : (const float *)nullptr, [&](int q, double v) { acc[q] = v; });
+                pair_terms(s, t, d2, true, plane, plane ? tn + 3 * (int64_t)bj : (const float *)nullptr, [&](int q, double v) { acc[q] = v; });
                 if constexpr (Terms::kGicp) {
                     gicp_pair_rows(ct, T, ct.src_cov + 9 * i, ct.tgt_cov + 9 * (int64_t)bj, s, t, acc);
                 } else if (mode == 1) {
