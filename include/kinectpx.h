@@ -1276,6 +1276,40 @@ int kpx_color_to_depth_visible(const uint16_t *depth, const float *xy, const uin
                                int32_t color_height, int32_t channels, const double *h_calibrations, int32_t calibrations, int32_t interpolation,
                                const uint16_t *warped, double occlusion_mm, uint8_t *out, void *stream);
 
+/* ---- lens undistortion: pinhole maps, image and depth remap (arithmetic contract AC22) ---------------------------------
+ * AC20's rules hold: fp64, every multiply, add and divide rounded separately in the order written, no fused multiply-add.  The
+ * undistorted camera is a distortion-free camera (fx', fy', cx', cy') with the centre and the axis of the real one: a depth value (Z
+ * along the axis) does not change, there is no parallax and no occlusion, and the lens model is closed form in the direction needed
+ * (target pixel -> source pixel), so an inverse remap through a stored map is exact and needs neither Newton iteration nor z-buffer.
+ * kpx_undistort_map: h_camera KPX_CAMERA_DOUBLES doubles (the real lens), h_pinhole 4 doubles fx', fy', cx', cy' on the host;
+ *     map f32 [out_height][out_width][2] on the device.  Per output pixel (column c, row r):
+ *         x = (c - cx') / fx', y = (r - cy') / fy';   (xd, yd) = distort(x, y) of AC20;   u = fx xd + cx, v = fy yd + cy;
+ *     the entry is ((float)u, (float)v), each rounded once -- or (NaN, NaN) when r2 > metric_radius metric_radius or when u or v is not
+ *     finite.  One thread per pixel, one launch, no scratch, asynchronous.
+ * kpx_remap_u8: src u8 [frames][src_height][src_width][channels], channels 1 or 3; map f32 [maps][out_height][out_width][2];
+ *     out u8 [frames][out_height][out_width][channels]; all on the device, no alignment required.  Frame f uses map f mod maps;
+ *     1 <= maps <= KPX_SENSOR_MAX_CALIBRATIONS and maps divides frames.  Output pixel (c, r) samples the frame's source image at
+ *     (uc, vc) = ((double)u, (double)v) of its map entry with exactly AC20's KPX_SAMPLE_NEAREST / KPX_SAMPLE_BILINEAR rules (the same
+ *     formula, the same rounding: one device function serves both).  The pixel is all zeros when the map entry has a NaN, when the
+ *     nearest pixel lies outside the image, or (bilinear) when any of the four neighbours does, whatever its weight.  Every output
+ *     byte is written.  One launch for the whole batch (frames <= 65535), no scratch, asynchronous.
+ * kpx_remap_depth: src u16 [frames][src_height][src_width], out u16 [frames][out_height][out_width], map and frames as kpx_remap_u8.
+ *         KPX_SAMPLE_NEAREST:  the source pixel (floor(uc + 0.5), floor(vc + 0.5)), copied (0 stays 0); 0 when it lies outside.
+ *         KPX_SAMPLE_BILINEAR, depth aware: x0, y0, ax, ay and the four neighbours d00, d10, d01, d11 as in AC20; 0 when any neighbour
+ *             lies outside the image; 0 when any of the four is 0; 0 when max - min of the four exceeds max_gap_mm (they straddle a
+ *             depth edge: a blend would invent a surface between foreground and background); otherwise AC20's val, stored as
+ *             floor(val + 0.5).
+ *     max_gap_mm >= 0, +inf allowed ("never"); it is not read for KPX_SAMPLE_NEAREST but checked all the same.  It has no default
+ *     anywhere: like AC21's it is a property of the scene and the rig.  Every output element is written.
+ * Rejected before the device is touched: negative sizes, null pointers, channels, the sampling code, maps outside its range or not
+ * dividing frames, a non-finite camera or pinhole target, zero focal lengths, a non-positive metric radius, a NaN or negative
+ * max_gap_mm.  An empty output image or frames = 0 return KPX_OK without a launch; an empty source image gives all zeros, written. */
+int kpx_undistort_map(const double *h_camera, const double *h_pinhole, int32_t out_width, int32_t out_height, float *map, void *stream);
+int kpx_remap_u8(const uint8_t *src, const float *map, int32_t src_width, int32_t src_height, int32_t channels, int32_t out_width,
+                 int32_t out_height, int32_t frames, int32_t maps, int32_t interpolation, uint8_t *out, void *stream);
+int kpx_remap_depth(const uint16_t *src, const float *map, int32_t src_width, int32_t src_height, int32_t out_width, int32_t out_height,
+                    int32_t frames, int32_t maps, int32_t interpolation, double max_gap_mm, uint16_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

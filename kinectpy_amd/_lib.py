@@ -242,6 +242,9 @@ SIGNATURES = {
     "kpx_depth_to_color_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "kpx_depth_to_color": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _vp, _vp, _sz, _vp]),
     "kpx_color_to_depth_visible": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _f64, _vp, _vp]),
+    "kpx_undistort_map": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "kpx_remap_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "kpx_remap_depth": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp]),
 }
 
 _lib = None

@@ -7,7 +7,10 @@ camera.  Both steps are open geometry (OpenCV's rational model); here they are `
 entry point at the front of the hot path takes -- and `register_color` / `register_mask`, on the device.  Contract AC21 (DESIGN.md
 5.22) adds `warp_depth` -- the depth image rendered into the colour camera through a z-buffer -- and with it the occlusion test of
 the `register_*` methods (`occlusion_mm`, `max_gap_mm`): the strip of background the depth camera sees beside a silhouette, where the
-colour camera sees the subject, no longer takes the subject's colour and mask label.
+colour camera sees the subject, no longer takes the subject's colour and mask label.  Contract AC22 adds lens
+undistortion for the pinhole-only consumers (TSDF volumes, odometry, VoxelGrid carving): `undistorted()` gives the distortion-free
+camera with the same centre and axis, `undistort_map()` the device map from its pixels to the lens's, and `undistort_depth` /
+`undistort_color` / `undistort_mask` (`SensorRig.undistort_*s` for a batch) the images resampled through it.
 
 `CameraIntrinsics.project` / `unproject` are host NumPy float64 that follow AC20 operation for operation: they are meant for a
 handful of skeleton joints, not for images.
@@ -69,9 +72,74 @@ class CameraIntrinsics:
         """o3d.camera.PinholeCameraIntrinsic for the pinhole-only consumers (TSDF, odometry, VoxelGrid carving); refuses a distorted
         camera: those consumers would silently use the wrong rays."""
         if self.has_distortion():
-            raise ValueError("to_pinhole: this camera has lens distortion; undistort the images first (DESIGN.md 9)")
+            raise ValueError("to_pinhole: this camera has lens distortion; undistort the images first (undistorted() is the camera "
+                             "they are then taken with, SensorCalibration.undistort_depth / undistort_color resample them)")
         from . import o3d
         return o3d.camera.PinholeCameraIntrinsic(self.width, self.height, self.fx, self.fy, self.cx, self.cy)
+
+    # ---- AC22: the distortion-free camera with this one's centre and axis -----------------------------------------------------
+    def _border_rays(self):
+        """the rays of the border pixel centres of the image as four (n, 2) arrays of normalised (x, y): left, right, top, bottom edge
+        (NaN pairs where a pixel has no ray)"""
+        if self.width < 1 or self.height < 1:
+            raise ValueError("undistorted: the camera has no image size to fit a rectangle to")
+        r = np.arange(self.height, dtype=np.float64)
+        c = np.arange(self.width, dtype=np.float64)
+        edges = (np.stack([np.zeros_like(r), r], -1), np.stack([np.full_like(r, self.width - 1.0), r], -1),
+                 np.stack([c, np.zeros_like(c)], -1), np.stack([c, np.full_like(c, self.height - 1.0)], -1))
+        return tuple(self.unproject(e) for e in edges)
+
+    def view_rectangle(self, fit):
+        """(x_left, x_right, y_top, y_bottom) in normalised coordinates.  fit="inside": the rectangle inside the image's outline --
+        the largest x on the left edge, the smallest on the right, the same for y -- shrunk by one source pixel (1 / fx, 1 / fy) on
+        each side, so that every pixel of a target fitted to it has all four bilinear neighbours; a border pixel without a ray
+        raises ValueError.  fit="all": the rectangle around every border pixel that has a ray."""
+        left, right, top, bottom = self._border_rays()
+        if fit == "inside":
+            if any(np.isnan(e).any() for e in (left, right, top, bottom)):
+                raise ValueError('undistorted: fit="inside" needs a ray at every border pixel, and some lie beyond the metric radius (fit="all" ignores them)')
+            px, py = abs(1.0 / self.fx), abs(1.0 / self.fy)
+            rect = (left[:, 0].max() + px, right[:, 0].min() - px, top[:, 1].max() + py, bottom[:, 1].min() - py)
+        elif fit == "all":
+            rays = np.concatenate([left, right, top, bottom])
+            rays = rays[~np.isnan(rays[:, 0])]
+            if rays.size == 0:
+                raise ValueError("undistorted: no border pixel has a ray")
+            rect = (rays[:, 0].min(), rays[:, 0].max(), rays[:, 1].min(), rays[:, 1].max())
+        else:
+            raise ValueError(f'undistorted: fit must be "same", "inside" or "all", got {fit!r}')
+        return tuple(float(v) for v in rect)
+
+    @classmethod
+    def from_view_rectangle(cls, rect, width, height, metric_radius=1.7):
+        """the distortion-free camera whose pixel columns 0 .. width - 1 span x_left .. x_right and rows 0 .. height - 1 span
+        y_top .. y_bottom: fx' = (width - 1) / (x_right - x_left), cx' = -fx' x_left, the same for y"""
+        xl, xr, yt, yb = rect
+        if not (xr > xl and yb > yt) or width < 2 or height < 2:
+            raise ValueError(f"undistorted: empty view rectangle x {xl} .. {xr}, y {yt} .. {yb} for a {width} x {height} image")
+        fx = (width - 1) / (xr - xl)
+        fy = (height - 1) / (yb - yt)
+        return cls(width, height, fx, fy, -fx * xl, -fy * yt, metric_radius=metric_radius)
+
+    def undistorted(self, fit="same", width=None, height=None):
+        """the distortion-free CameraIntrinsics (to_pinhole() works on it) of width x height pixels (default: this camera's) that the
+        undistorted images are taken with.  fit="same" keeps fx, fy, cx, cy; "inside" / "all" fit the view to view_rectangle(fit):
+        "inside" sees only what the lens saw (no empty border), "all" everything it saw."""
+        w = self.width if width is None else int(width)
+        h = self.height if height is None else int(height)
+        if fit == "same":
+            return CameraIntrinsics(w, h, self.fx, self.fy, self.cx, self.cy, metric_radius=self.metric_radius)
+        return CameraIntrinsics.from_view_rectangle(self.view_rectangle(fit), w, h, self.metric_radius)
+
+    def undistort_map(self, pinhole=None):
+        """AC22's map for the target camera `pinhole` (default: undistorted()): float32 (H', W', 2) on the device (ops.undistort_map),
+        computed once per target"""
+        target = self.undistorted() if pinhole is None else pinhole
+        key = (tuple(self.packed()), _target_key(target))
+        cache = self.__dict__.setdefault("_maps", {})
+        if key not in cache:
+            cache[key] = ops.undistort_map(self, target)
+        return cache[key]
 
     # ---- AC20 on the host ------------------------------------------------------------------------------------------------------
     def _distort(self, x, y):
@@ -189,6 +257,25 @@ class SensorCalibration:
         max_gap_mm as in register_color"""
         return _register([self], depth, mask, "nearest", 1, None, occlusion_mm, max_gap_mm)[0]
 
+    def undistorted(self, fit="same"):
+        """the SensorCalibration of the undistorted images: both cameras distortion-free (CameraIntrinsics.undistorted(fit)), the same
+        depth_to_color -- undistortion moves neither camera"""
+        return SensorCalibration(self.depth.undistorted(fit), self.color.undistorted(fit), self.depth_to_color)
+
+    def undistort_depth(self, depth, interpolation="nearest", max_gap_mm=None, pinhole=None):
+        """depth uint16 (H * W,) or (H, W) -> uint16 (H', W') as the camera `pinhole` (default: depth.undistorted()) sees it (AC22,
+        ops.remap_depth).  "nearest" copies depth values; "bilinear" blends the four neighbours unless one is 0 or they differ by more
+        than max_gap_mm, which it then needs (no default, as in warp_depth)."""
+        return _undistort([self], "depth", depth, interpolation, pinhole, True, depth=True, max_gap_mm=max_gap_mm)[0]
+
+    def undistort_color(self, color, pinhole=None):
+        """color uint8 (Hc, Wc, 3) -> uint8 (H', W', 3) as the camera `pinhole` (default: color.undistorted()) sees it, bilinear"""
+        return _undistort([self], "color", color, "bilinear", pinhole, True, channels=3)[0]
+
+    def undistort_mask(self, mask, camera="color", pinhole=None):
+        """mask uint8 (H, W) taken on the image of `camera` ("color" or "depth") -> uint8 (H', W'), nearest pixel"""
+        return _undistort([self], camera, mask, "nearest", pinhole, True)[0]
+
     def to_dict(self):
         return {"depth": self.depth.to_dict(), "color": self.color.to_dict(), "depth_to_color": self.depth_to_color.tolist()}
 
@@ -221,6 +308,7 @@ class SensorRig:
         if len(n) != 1:
             raise ValueError(f"SensorRig: the depth cameras differ in size: {sorted(n)}")
         self._tables = None
+        self._maps = {}
 
     def __len__(self):
         return len(self.calibrations)
@@ -247,6 +335,83 @@ class SensorRig:
     def register_masks(self, depth, masks, occlusion_mm=None, max_gap_mm=None):
         """as register_colors for uint8 (F, Hc, Wc) masks / label images, nearest pixel -> uint8 (F, n_px)"""
         return _register(self.calibrations, depth, masks, "nearest", None, self, occlusion_mm, max_gap_mm)
+
+    def common_pinhole(self, camera="depth", fit="inside"):
+        """one distortion-free CameraIntrinsics for `camera` ("depth" or "color") of every sensor, of the cameras' size: fitted to the
+        intersection (fit="inside") or the union ("all") of the sensors' view rectangles (CameraIntrinsics.view_rectangle) -- the one
+        PinholeCameraIntrinsic the batched consumers (integrate_frames, carve_depth_maps) take"""
+        cams = _cameras(self.calibrations, camera)
+        rects = np.array([c.view_rectangle(fit) for c in cams])
+        lo, hi = (rects.max(0), rects.min(0)) if fit == "inside" else (rects.min(0), rects.max(0))
+        return CameraIntrinsics.from_view_rectangle((lo[0], hi[1], lo[2], hi[3]), cams[0].width, cams[0].height, min(c.metric_radius for c in cams))
+
+    def undistort_maps(self, camera="depth", pinhole=None):
+        """float32 (S, H', W', 2) on the device: every sensor's map to the one target `pinhole` (default: common_pinhole(camera)),
+        stacked once per target"""
+        target = self.common_pinhole(camera) if pinhole is None else pinhole
+        key = (camera, tuple(tuple(c.packed()) for c in _cameras(self.calibrations, camera)), _target_key(target))
+        if key not in self._maps:
+            import torch
+            self._maps[key] = torch.stack([c.undistort_map(target) for c in _cameras(self.calibrations, camera)])
+        return self._maps[key]
+
+    def undistort_depths(self, depth, interpolation="nearest", max_gap_mm=None, pinhole=None):
+        """depth uint16 (F, H * W) or (F, H, W), frame f of sensor f % S -> uint16 (F, H', W') as the one camera `pinhole` (default:
+        common_pinhole("depth")) sees them; one launch for the batch (SensorCalibration.undistort_depth)"""
+        return _undistort(self.calibrations, "depth", depth, interpolation, pinhole, False, self, depth=True, max_gap_mm=max_gap_mm)
+
+    def undistort_colors(self, colors, pinhole=None, camera="color", interpolation="bilinear"):
+        """colors uint8 (F, H, W, 3) taken on `camera`'s image -> uint8 (F, H', W', 3) as `pinhole` (default: common_pinhole(camera))
+        sees them.  Colours already registered into the depth grid (register_colors) are (F, H * W, 3) with camera="depth"; their
+        zero holes want interpolation="nearest" (bilinear would blend them in)."""
+        return _undistort(self.calibrations, camera, colors, interpolation, pinhole, False, self, channels=3)
+
+    def undistort_masks(self, masks, camera="color", pinhole=None):
+        """masks uint8 (F, H, W) taken on `camera`'s image -> uint8 (F, H', W'), nearest pixel"""
+        return _undistort(self.calibrations, camera, masks, "nearest", pinhole, False, self)
+
+
+def _target_key(target):
+    if hasattr(target, "packed"):
+        return (int(target.width), int(target.height)) + tuple(target.packed())
+    return (int(target.width), int(target.height)) + tuple(np.asarray(target.intrinsic_matrix, dtype=np.float64).reshape(-1))
+
+
+def _cameras(cals, camera):
+    if camera not in ("depth", "color"):
+        raise ValueError(f'camera must be "depth" or "color", got {camera!r}')
+    cams = [getattr(c, camera) for c in cals]
+    sizes = {(c.width, c.height) for c in cams}
+    if len(sizes) != 1:
+        raise ValueError(f"undistort: the {camera} cameras differ in size: {sorted(sizes)}")
+    return cams
+
+
+def _undistort(cals, camera, image, interpolation, pinhole, single, rig=None, channels=None, depth=False, max_gap_mm=None):
+    """the images of `camera` resampled to `pinhole`: uint16 depth images (depth=True) or uint8 images of `channels` channels (None: no
+    channel axis).  Everything is checked before the maps are asked for (the first device call)."""
+    import torch
+    cams = _cameras(cals, camera)
+    w, h = cams[0].width, cams[0].height
+    img = image if isinstance(image, torch.Tensor) else np.asarray(image)
+    if depth and interpolation == "bilinear" and max_gap_mm is None:
+        raise ValueError("undistort: the bilinear depth mode needs max_gap_mm (no default: it depends on the scene and the rig)")
+    tail = () if channels is None else (channels,)
+    shape = tuple(int(n) for n in img.shape)
+    lead = shape[:1] if not single else ()
+    if shape not in (lead + (h, w) + tail, lead + (h * w,) + tail):
+        raise ValueError(f"undistort: the image is {shape}, expected {lead + (h, w) + tail} for the {w} x {h} {camera} camera"
+                         + ("" if single else f" (F frames first, frame f of sensor f % {len(cals)})"))
+    if not single and shape[0] % len(cals) != 0:
+        raise ValueError(f"undistort: {len(cals)} sensors do not divide {shape[0]} frames")
+    img = img.reshape(((1,) if single else lead) + (h, w) + tail)
+    if rig is not None:
+        maps = rig.undistort_maps(camera, pinhole)
+    else:
+        maps = cams[0].undistort_map(pinhole)
+    if depth:
+        return ops.remap_depth(img, maps, interpolation, max_gap_mm)
+    return ops.remap(img, maps, interpolation)
 
 
 def _tables(cals, rig):

@@ -2,6 +2,8 @@
 // (kpx_xy_table) and the colour image resampled into the depth camera's pixel grid (kpx_color_to_depth).  Both are pure maps: no
 // scratch, no atomics, one launch each.  AC21 adds the depth image warped into the colour camera through a 32-bit
 // z-buffer of integer minima (kpx_depth_to_color) and the registration with an occlusion test against it (kpx_color_to_depth_visible).
+// AC22 adds lens undistortion: the map from the pixels of a distortion-free target camera to source pixel coordinates
+// (kpx_undistort_map) and the images resampled through stored maps (kpx_remap_u8, kpx_remap_depth) -- pure maps again.
 // fp64 throughout, every operation rounded separately in the order include/kinectpx.h states -- the build's -ffp-contract=off keeps
 // the compiler from fusing any of it, and nothing here calls fma().
 #include "kpx_common.h"
@@ -119,15 +121,12 @@ __device__ __forceinline__ bool occluded(const uint16_t *__restrict__ warped, in
     return w != 0 && qz - (double)w > occlusion_mm;
 }
 
-// VISIBLE: AC21's occlusion test against the warped depth image of the frame (`warped`, colour-camera grid)
+// AC20's samplers at (uc, vc) of a wc x hc image of C channels: out stays as it is where the rules give no sample (a NaN coordinate
+// fails the range tests).  VISIBLE: AC21's occlusion test against the warped depth image of the frame (`warped`, colour-camera grid)
 template <int C, int INTERP, bool VISIBLE>
-__device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const uint8_t *__restrict__ img, const uint16_t *__restrict__ warped,
-                                             double occlusion_mm, int32_t wc, int32_t hc, uint16_t d, float xt, float yt, uint32_t out[C])
+__device__ __forceinline__ void sample_at(const uint8_t *__restrict__ img, const uint16_t *__restrict__ warped, double occlusion_mm, int32_t wc, int32_t hc,
+                                          double uc, double vc, double qz, uint32_t out[C])
 {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) out[ch] = 0;
-    double uc, vc, qz;
-    if (!depth_pixel_to_color(cal, d, xt, yt, uc, vc, qz)) return;
     if (INTERP == KPX_SAMPLE_NEAREST) {
         const double fx = floor(uc + 0.5), fy = floor(vc + 0.5);
         if (!(fx >= 0.0 && fx <= (double)(wc - 1) && fy >= 0.0 && fy <= (double)(hc - 1))) return;       // (a NaN fails too)
@@ -153,12 +152,64 @@ __device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const 
     }
 }
 
-// A block owns kPixPerBlock consecutive depth pixels of one frame (blockIdx.y), four per thread.  The pixels' bytes are packed into
-// dwords in registers, laid down in LDS in pixel order, and leave as 16-byte stores from the first 16-byte boundary of the block's
-// output range on; the at most 15 bytes in front of that boundary and behind the last whole vector leave as byte stores (a frame's
-// output starts wherever frames * n_px * channels puts it, and neighbouring blocks may share a 16-byte line but never a byte).
+template <int C, int INTERP, bool VISIBLE>
+__device__ __forceinline__ void sample_pixel(const ColorCalibration &cal, const uint8_t *__restrict__ img, const uint16_t *__restrict__ warped,
+                                             double occlusion_mm, int32_t wc, int32_t hc, uint16_t d, float xt, float yt, uint32_t out[C])
+{
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) out[ch] = 0;
+    double uc, vc, qz;
+    if (!depth_pixel_to_color(cal, d, xt, yt, uc, vc, qz)) return;
+    sample_at<C, INTERP, VISIBLE>(img, warped, occlusion_mm, wc, hc, uc, vc, qz, out);
+}
+
 constexpr int kC2dThreads = 256, kC2dPerThread = 4, kPixPerBlock = kC2dThreads * kC2dPerThread;
 
+// The packed store of a block of byte pixels, four per thread: the pixels' bytes are packed into dwords in registers, laid down in LDS
+// in pixel order, and leave as 16-byte stores from the first 16-byte boundary of the block's output range out_blk[0 .. nbytes) on; the
+// at most 15 bytes in front of that boundary and behind the last whole vector leave as byte stores (neighbouring blocks may share a
+// 16-byte line but never a byte).  stage: kPixPerBlock * C / 4 + 8 words of LDS.
+template <int C>
+__device__ __forceinline__ void store_packed(const uint32_t px[kC2dPerThread][C], uint32_t *stage, uint8_t *__restrict__ out_blk, int nbytes)
+{
+    if (C == 3) {
+        // 12 bytes r g b r g b ... as three little-endian words
+        stage[3 * threadIdx.x + 0] = px[0][0] | px[0][1 % C] << 8 | px[0][2 % C] << 16 | px[1][0] << 24;
+        stage[3 * threadIdx.x + 1] = px[1][1 % C] | px[1][2 % C] << 8 | px[2][0] << 16 | px[2][1 % C] << 24;
+        stage[3 * threadIdx.x + 2] = px[2][2 % C] | px[3][0] << 8 | px[3][1 % C] << 16 | px[3][2 % C] << 24;
+    } else {
+        stage[threadIdx.x] = px[0][0] | px[1][0] << 8 | px[2][0] << 16 | px[3][0] << 24;
+    }
+    __syncthreads();
+
+    const uint8_t *stage_bytes = reinterpret_cast<const uint8_t *>(stage);
+    int head = (int)((16 - ((uintptr_t)out_blk & 15)) & 15);                   // bytes in front of the first 16-byte boundary
+    if (head > nbytes) head = nbytes;
+    const int vecs = (nbytes - head) >> 4;
+    const int tail0 = head + 16 * vecs;                                        // first byte behind the last whole vector
+    if ((int)threadIdx.x < head) out_blk[threadIdx.x] = stage_bytes[threadIdx.x];
+    if ((int)threadIdx.x < nbytes - tail0) out_blk[tail0 + threadIdx.x] = stage_bytes[tail0 + threadIdx.x];
+    const int w0 = head >> 2, sh = 8 * (head & 3);
+    uint4 *dst = reinterpret_cast<uint4 *>(out_blk + head);
+    for (int j = threadIdx.x; j < vecs; j += kC2dThreads) {
+        uint32_t w[5];
+#pragma unroll
+        for (int e = 0; e < 5; ++e) w[e] = stage[w0 + 4 * j + e];
+        uint4 v;
+        if (sh) {
+            v.x = w[0] >> sh | w[1] << (32 - sh);
+            v.y = w[1] >> sh | w[2] << (32 - sh);
+            v.z = w[2] >> sh | w[3] << (32 - sh);
+            v.w = w[3] >> sh | w[4] << (32 - sh);
+        } else {
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        dst[j] = v;
+    }
+}
+
+// A block owns kPixPerBlock consecutive depth pixels of one frame (blockIdx.y), four per thread, and stores them with store_packed (a
+// frame's output starts wherever frames * n_px * channels puts it).
 template <int C, int INTERP, bool VISIBLE>
 static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ xy,
                                                                             const uint8_t *__restrict__ color, const uint16_t *__restrict__ warped,
@@ -197,43 +248,9 @@ static __global__ __launch_bounds__(kC2dThreads) void color_to_depth_kernel(cons
     uint32_t px[kC2dPerThread][C];
 #pragma unroll
     for (int k = 0; k < kC2dPerThread; ++k) sample_pixel<C, INTERP, VISIBLE>(cal, img, wimg, occlusion_mm, wc, hc, d[k], xt[k], yt[k], px[k]);
-    if (C == 3) {
-        // 12 bytes r g b r g b ... as three little-endian words
-        stage[3 * threadIdx.x + 0] = px[0][0] | px[0][1 % C] << 8 | px[0][2 % C] << 16 | px[1][0] << 24;
-        stage[3 * threadIdx.x + 1] = px[1][1 % C] | px[1][2 % C] << 8 | px[2][0] << 16 | px[2][1 % C] << 24;
-        stage[3 * threadIdx.x + 2] = px[2][2 % C] | px[3][0] << 8 | px[3][1 % C] << 16 | px[3][2 % C] << 24;
-    } else {
-        stage[threadIdx.x] = px[0][0] | px[1][0] << 8 | px[2][0] << 16 | px[3][0] << 24;
-    }
-    __syncthreads();
-
     const int64_t left = n_px - p0;
-    const int nbytes = (int)(left < kPixPerBlock ? left : kPixPerBlock) * C;   // what this block owns: out_blk[0 .. nbytes)
-    uint8_t *out_blk = out + ((int64_t)frame * n_px + p0) * C;
-    const uint8_t *stage_bytes = reinterpret_cast<const uint8_t *>(stage);
-    int head = (int)((16 - ((uintptr_t)out_blk & 15)) & 15);                   // bytes in front of the first 16-byte boundary
-    if (head > nbytes) head = nbytes;
-    const int vecs = (nbytes - head) >> 4;
-    const int tail0 = head + 16 * vecs;                                        // first byte behind the last whole vector
-    if ((int)threadIdx.x < head) out_blk[threadIdx.x] = stage_bytes[threadIdx.x];
-    if ((int)threadIdx.x < nbytes - tail0) out_blk[tail0 + threadIdx.x] = stage_bytes[tail0 + threadIdx.x];
-    const int w0 = head >> 2, sh = 8 * (head & 3);
-    uint4 *dst = reinterpret_cast<uint4 *>(out_blk + head);
-    for (int j = threadIdx.x; j < vecs; j += kC2dThreads) {
-        uint32_t w[5];
-#pragma unroll
-        for (int e = 0; e < 5; ++e) w[e] = stage[w0 + 4 * j + e];
-        uint4 v;
-        if (sh) {
-            v.x = w[0] >> sh | w[1] << (32 - sh);
-            v.y = w[1] >> sh | w[2] << (32 - sh);
-            v.z = w[2] >> sh | w[3] << (32 - sh);
-            v.w = w[3] >> sh | w[4] << (32 - sh);
-        } else {
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        dst[j] = v;
-    }
+    const int nbytes = (int)(left < kPixPerBlock ? left : kPixPerBlock) * C;   // what this block owns
+    store_packed<C>(px, stage, out + ((int64_t)frame * n_px + p0) * C, nbytes);
 }
 
 // ---- depth -> colour (AC21) -----------------------------------------------------------------------------------------------------------
@@ -358,6 +375,120 @@ static __global__ __launch_bounds__(kResolveThreads) void warp_resolve_kernel(co
     const uint4 *src = reinterpret_cast<const uint4 *>(stage);
     uint4 *dst = reinterpret_cast<uint4 *>(out_blk - a);
     for (int j = v0 + threadIdx.x; j < v1; j += kResolveThreads) dst[j] = src[j];
+}
+
+// ---- lens undistortion (AC22) ---------------------------------------------------------------------------------------------------------
+struct Pinhole {
+    double fx, fy, cx, cy;
+};
+
+// One thread per pixel of the target camera, closed form (the lens model runs in its forward direction): a thread's (u, v) is one
+// 8-byte store, a wave's 512 contiguous bytes.
+static __global__ __launch_bounds__(kTableThreads) void undistort_map_kernel(Camera k, Pinhole t, int32_t width, int64_t n_px, float2 *__restrict__ map)
+{
+    const int64_t i = (int64_t)blockIdx.x * kTableThreads + threadIdx.x;
+    if (i >= n_px) return;
+    const int64_t row = i / width;
+    const double x = ((double)(i - row * width) - t.cx) / t.fx, y = ((double)row - t.cy) / t.fy;
+    const Distorted o = distort(k, x, y);
+    const double u = k.fx * o.xd + k.cx, v = k.fy * o.yd + k.cy;
+    const float nan = __builtin_nanf("");
+    float2 e = make_float2(nan, nan);
+    if (!(o.r2 > k.mr * k.mr) && __builtin_isfinite(u) && __builtin_isfinite(v)) e = make_float2((float)u, (float)v);
+    map[i] = e;
+}
+
+// the map entries of a thread's four consecutive output pixels from i0 on (0, 0 behind the last pixel: never stored).  vec_ok: n_px is
+// a multiple of 4 and the map's base is 16-byte aligned, so every map's group of 4 entries is two aligned 16-byte loads
+__device__ __forceinline__ void load_map4(const float *__restrict__ mp, int64_t i0, int64_t n_px, int32_t vec_ok, float u[kC2dPerThread], float v[kC2dPerThread])
+{
+    if (vec_ok && i0 + kC2dPerThread <= n_px) {
+        const float4 t0 = *reinterpret_cast<const float4 *>(mp + 2 * i0), t1 = *reinterpret_cast<const float4 *>(mp + 2 * i0 + 4);
+        u[0] = t0.x; v[0] = t0.y; u[1] = t0.z; v[1] = t0.w; u[2] = t1.x; v[2] = t1.y; u[3] = t1.z; v[3] = t1.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < kC2dPerThread; ++k) {
+            const bool in = i0 + k < n_px;
+            u[k] = in ? mp[2 * (i0 + k)] : 0.0f;
+            v[k] = in ? mp[2 * (i0 + k) + 1] : 0.0f;
+        }
+    }
+}
+
+// color_to_depth_kernel's shape: a block owns kPixPerBlock consecutive output pixels of one frame (blockIdx.y), four per thread, and
+// stores them with store_packed.  A NaN map entry fails the samplers' range tests and leaves the pixel zero.
+template <int C, int INTERP>
+static __global__ __launch_bounds__(kC2dThreads) void remap_u8_kernel(const uint8_t *__restrict__ src, const float *__restrict__ map, int32_t ws, int32_t hs,
+                                                                      int64_t n_px, int32_t n_maps, int32_t vec_ok, uint8_t *__restrict__ out)
+{
+    constexpr int kStageWords = kPixPerBlock * C / 4;
+    __shared__ uint32_t stage[kStageWords + 8];
+    const int frame = blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * kPixPerBlock;
+    const int64_t i0 = p0 + (int64_t)threadIdx.x * kC2dPerThread;
+    const uint8_t *img = src + (int64_t)frame * hs * ws * C;
+    float u[kC2dPerThread], v[kC2dPerThread];
+    load_map4(map + (int64_t)(frame % n_maps) * n_px * 2, i0, n_px, vec_ok, u, v);
+    uint32_t px[kC2dPerThread][C];
+#pragma unroll
+    for (int k = 0; k < kC2dPerThread; ++k) {
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) px[k][ch] = 0;
+        if (i0 + k < n_px) sample_at<C, INTERP, false>(img, nullptr, 0.0, ws, hs, (double)u[k], (double)v[k], 0.0, px[k]);
+    }
+    const int64_t left = n_px - p0;
+    const int nbytes = (int)(left < kPixPerBlock ? left : kPixPerBlock) * C;
+    store_packed<C>(px, stage, out + ((int64_t)frame * n_px + p0) * C, nbytes);
+}
+
+template <int INTERP>
+__device__ __forceinline__ uint32_t sample_depth_at(const uint16_t *__restrict__ img, int32_t ws, int32_t hs, double uc, double vc, double max_gap_mm)
+{
+    if (INTERP == KPX_SAMPLE_NEAREST) {
+        const double fx = floor(uc + 0.5), fy = floor(vc + 0.5);
+        if (!(fx >= 0.0 && fx <= (double)(ws - 1) && fy >= 0.0 && fy <= (double)(hs - 1))) return 0;
+        return img[(int64_t)(int32_t)fy * ws + (int32_t)fx];
+    }
+    const double x0 = floor(uc), y0 = floor(vc);
+    if (!(x0 >= 0.0 && x0 <= (double)(ws - 2) && y0 >= 0.0 && y0 <= (double)(hs - 2))) return 0;
+    const uint16_t *p0 = img + ((int64_t)(int32_t)y0 * ws + (int32_t)x0);
+    const uint16_t *p1 = p0 + ws;
+    const uint32_t d00 = p0[0], d10 = p0[1], d01 = p1[0], d11 = p1[1];
+    if (d00 == 0 || d10 == 0 || d01 == 0 || d11 == 0) return 0;
+    const uint32_t lo = min(min(d00, d10), min(d01, d11)), hi = max(max(d00, d10), max(d01, d11));
+    if ((double)(hi - lo) > max_gap_mm) return 0;
+    const double ax = uc - x0, ay = vc - y0;
+    const double bx = 1.0 - ax, by = 1.0 - ay;
+    const double w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay;
+    const double val = ((w00 * (double)d00 + w10 * (double)d10) + w01 * (double)d01) + w11 * (double)d11;
+    return (uint32_t)(int32_t)floor(val + 0.5);
+}
+
+// Four consecutive output pixels per thread, one frame per blockIdx.y.  vec_out: n_px is a multiple of 4 and out's base is 8-byte
+// aligned, so a thread's four u16 values are one aligned 8-byte store (a wave's 512 contiguous bytes); element stores otherwise.
+template <int INTERP>
+static __global__ __launch_bounds__(kC2dThreads) void remap_depth_kernel(const uint16_t *__restrict__ src, const float *__restrict__ map, int32_t ws,
+                                                                         int32_t hs, int64_t n_px, int32_t n_maps, int32_t vec_ok, int32_t vec_out,
+                                                                         double max_gap_mm, uint16_t *__restrict__ out)
+{
+    const int frame = blockIdx.y;
+    const int64_t i0 = ((int64_t)blockIdx.x * kC2dThreads + threadIdx.x) * kC2dPerThread;
+    if (i0 >= n_px) return;
+    const uint16_t *img = src + (int64_t)frame * hs * ws;
+    float u[kC2dPerThread], v[kC2dPerThread];
+    load_map4(map + (int64_t)(frame % n_maps) * n_px * 2, i0, n_px, vec_ok, u, v);
+    uint32_t d[kC2dPerThread];
+#pragma unroll
+    for (int k = 0; k < kC2dPerThread; ++k)
+        d[k] = i0 + k < n_px ? sample_depth_at<INTERP>(img, ws, hs, (double)u[k], (double)v[k], max_gap_mm) : 0u;
+    uint16_t *o = out + (int64_t)frame * n_px + i0;
+    if (vec_out) {                                                             // (then i0 + 4 <= n_px)
+        *reinterpret_cast<uint2 *>(o) = make_uint2(d[0] | d[1] << 16, d[2] | d[3] << 16);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kC2dPerThread; ++k)
+            if (i0 + k < n_px) o[k] = (uint16_t)d[k];
+    }
 }
 
 }  // namespace kpx
@@ -498,6 +629,94 @@ KPX_EXPORT int kpx_depth_to_color(const uint16_t *depth, const float *xy, int32_
     KPX_LAUNCH_CHECK();
     const int32_t vec_ok = (uintptr_t)out % 2 == 0;
     hipLaunchKernelGGL(warp_resolve_kernel, dim3((unsigned)cdiv(n, kResolvePerBlock), (unsigned)frames), dim3(kResolveThreads), 0, st, zbuf, n, vec_ok, out);
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+// ---- lens undistortion (AC22) ---------------------------------------------------------------------------------------------------------
+KPX_EXPORT int kpx_undistort_map(const double *h_camera, const double *h_pinhole, int32_t out_width, int32_t out_height, float *map, void *stream)
+{
+    const char *who = "kpx_undistort_map";
+    KPX_REQUIRE(out_width >= 0 && out_height >= 0, "%s: negative image size %d x %d", who, (int)out_width, (int)out_height);
+    KPX_REQUIRE(h_camera, "%s: null camera", who);
+    KPX_REQUIRE(h_pinhole, "%s: null pinhole", who);
+    KPX_REQUIRE(camera_ok(h_camera), "%s: the camera needs finite numbers, non-zero focal lengths and a positive metric radius", who);
+    bool ok = h_pinhole[0] != 0.0 && h_pinhole[1] != 0.0;
+    for (int i = 0; i < 4; ++i) ok = ok && __builtin_isfinite(h_pinhole[i]);
+    KPX_REQUIRE(ok, "%s: the pinhole target needs finite numbers and non-zero focal lengths", who);
+    const int64_t n_px = (int64_t)out_width * out_height;
+    if (n_px == 0) return KPX_OK;
+    KPX_REQUIRE(map, "%s: null pointer", who);
+    hipLaunchKernelGGL(undistort_map_kernel, dim3((unsigned)cdiv(n_px, kTableThreads)), dim3(kTableThreads), 0, (hipStream_t)stream, camera_from(h_camera),
+                       Pinhole{ h_pinhole[0], h_pinhole[1], h_pinhole[2], h_pinhole[3] }, out_width, n_px, reinterpret_cast<float2 *>(map));
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+// the checks the two remap entries share: false = kpx::fail() has been called
+static bool remap_ok(const char *who, int32_t src_width, int32_t src_height, int32_t out_width, int32_t out_height, int32_t frames, int32_t maps,
+                     int32_t interpolation)
+{
+    if (src_width < 0 || src_height < 0 || out_width < 0 || out_height < 0 || frames < 0)
+        return fail(KPX_ERR_INVALID, "%s: negative size (source %d x %d, output %d x %d, frames %d)", who, (int)src_width, (int)src_height, (int)out_width,
+                    (int)out_height, (int)frames), false;
+    if (frames > 65535) return fail(KPX_ERR_INVALID, "%s: at most 65535 frames per call, got %d", who, (int)frames), false;
+    if ((int64_t)out_width * out_height > (int64_t)kPixPerBlock * 0x7fffffff) return fail(KPX_ERR_INVALID, "%s: output size out of range", who), false;
+    if (interpolation != KPX_SAMPLE_NEAREST && interpolation != KPX_SAMPLE_BILINEAR)
+        return fail(KPX_ERR_INVALID, "%s: unknown interpolation %d", who, (int)interpolation), false;
+    if (!(maps >= 1 && maps <= KPX_SENSOR_MAX_CALIBRATIONS)) return fail(KPX_ERR_INVALID, "%s: 1 to %d maps, got %d", who, KPX_SENSOR_MAX_CALIBRATIONS, (int)maps), false;
+    if (frames % maps != 0) return fail(KPX_ERR_INVALID, "%s: %d maps do not divide %d frames", who, (int)maps, (int)frames), false;
+    return true;
+}
+
+KPX_EXPORT int kpx_remap_u8(const uint8_t *src, const float *map, int32_t src_width, int32_t src_height, int32_t channels, int32_t out_width,
+                            int32_t out_height, int32_t frames, int32_t maps, int32_t interpolation, uint8_t *out, void *stream)
+{
+    const char *who = "kpx_remap_u8";
+    if (!remap_ok(who, src_width, src_height, out_width, out_height, frames, maps, interpolation)) return KPX_ERR_INVALID;
+    KPX_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, (int)channels);
+    const int64_t n_px = (int64_t)out_width * out_height;
+    if (frames == 0 || n_px == 0) return KPX_OK;
+    KPX_REQUIRE(out, "%s: null pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_width == 0 || src_height == 0) {                                   // no source pixel: every sample lies outside
+        KPX_HIP(hipMemsetAsync(out, 0, (size_t)frames * n_px * channels, st));
+        return KPX_OK;
+    }
+    KPX_REQUIRE(src && map, "%s: null pointer", who);
+    const int32_t vec_ok = n_px % 4 == 0 && (uintptr_t)map % 16 == 0;
+    const dim3 grid((unsigned)cdiv(n_px, kPixPerBlock), (unsigned)frames), block(kC2dThreads);
+#define KPX_REMAP(C, I) hipLaunchKernelGGL((remap_u8_kernel<C, I>), grid, block, 0, st, src, map, src_width, src_height, n_px, maps, vec_ok, out)
+    if (channels == 3 && interpolation == KPX_SAMPLE_BILINEAR) KPX_REMAP(3, KPX_SAMPLE_BILINEAR);
+    else if (channels == 3) KPX_REMAP(3, KPX_SAMPLE_NEAREST);
+    else if (interpolation == KPX_SAMPLE_BILINEAR) KPX_REMAP(1, KPX_SAMPLE_BILINEAR);
+    else KPX_REMAP(1, KPX_SAMPLE_NEAREST);
+#undef KPX_REMAP
+    KPX_LAUNCH_CHECK();
+    return KPX_OK;
+}
+
+KPX_EXPORT int kpx_remap_depth(const uint16_t *src, const float *map, int32_t src_width, int32_t src_height, int32_t out_width, int32_t out_height,
+                               int32_t frames, int32_t maps, int32_t interpolation, double max_gap_mm, uint16_t *out, void *stream)
+{
+    const char *who = "kpx_remap_depth";
+    if (!remap_ok(who, src_width, src_height, out_width, out_height, frames, maps, interpolation)) return KPX_ERR_INVALID;
+    KPX_REQUIRE(max_gap_mm >= 0.0, "%s: max_gap_mm must be >= 0 (+inf: never too far apart), got %g", who, max_gap_mm);                   // (a NaN fails)
+    const int64_t n_px = (int64_t)out_width * out_height;
+    if (frames == 0 || n_px == 0) return KPX_OK;
+    KPX_REQUIRE(out, "%s: null pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_width == 0 || src_height == 0) {
+        KPX_HIP(hipMemsetAsync(out, 0, (size_t)frames * n_px * sizeof(uint16_t), st));
+        return KPX_OK;
+    }
+    KPX_REQUIRE(src && map, "%s: null pointer", who);
+    const int32_t vec_ok = n_px % 4 == 0 && (uintptr_t)map % 16 == 0, vec_out = n_px % 4 == 0 && (uintptr_t)out % 8 == 0;
+    const dim3 grid((unsigned)cdiv(n_px, kPixPerBlock), (unsigned)frames), block(kC2dThreads);
+    if (interpolation == KPX_SAMPLE_BILINEAR)
+        hipLaunchKernelGGL(remap_depth_kernel<KPX_SAMPLE_BILINEAR>, grid, block, 0, st, src, map, src_width, src_height, n_px, maps, vec_ok, vec_out, max_gap_mm, out);
+    else
+        hipLaunchKernelGGL(remap_depth_kernel<KPX_SAMPLE_NEAREST>, grid, block, 0, st, src, map, src_width, src_height, n_px, maps, vec_ok, vec_out, max_gap_mm, out);
     KPX_LAUNCH_CHECK();
     return KPX_OK;
 }

@@ -2456,3 +2456,89 @@ def color_to_depth(depth, xy, color, calibrations, interpolation="bilinear", out
     L.check(lib.kpx_color_to_depth_visible(L.ptr(dep), L.ptr(table), L.ptr(col), n_px, F, wc, hc, ch, L.hptr(pack), S, SAMPLE_MODES[interpolation],
                                            L.ptr(wrp), float(occlusion_mm), L.ptr(out), L.stream_ptr()))
     return out
+
+
+# ---- lens undistortion (AC22) -------------------------------------------------------------------------------
+def _pinhole4(who, pinhole):
+    """the target of an undistortion -- a distortion-free calibration.CameraIntrinsics, or anything with width, height and
+    intrinsic_matrix (o3d.camera.PinholeCameraIntrinsic) -> float64[4] fx' fy' cx' cy', width, height"""
+    if hasattr(pinhole, "has_distortion"):
+        if pinhole.has_distortion():
+            raise ValueError(f"{who}: the target camera has lens distortion (CameraIntrinsics.undistorted() gives one without)")
+        a = [pinhole.fx, pinhole.fy, pinhole.cx, pinhole.cy]
+    else:
+        K = np.asarray(pinhole.intrinsic_matrix, dtype=np.float64).reshape(3, 3)
+        a = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
+    return np.ascontiguousarray(a, dtype=np.float64), int(pinhole.width), int(pinhole.height)
+
+
+def undistort_map(camera, pinhole):
+    """AC22's map of a lens (camera: a calibration.CameraIntrinsics or 13 numbers) for a distortion-free target camera `pinhole`
+    (its width and height are the map's): float32 (H', W', 2) device tensor, per target pixel the source pixel coordinates (u, v) it
+    sees -- the lens model in its closed-form direction, rounded once --, NaN pairs beyond the metric radius.  What remap /
+    remap_depth take as `maps`."""
+    lib = L.load()
+    cam = _camera13(camera)
+    pin, w, h = _pinhole4("undistort_map", pinhole)
+    if w < 0 or h < 0:
+        raise L.KinectPxError(f"undistort_map: negative image size {w} x {h}")
+    out = torch.empty((h, w, 2), dtype=torch.float32, device=L.device())
+    L.check(lib.kpx_undistort_map(L.hptr(cam), L.hptr(pin), w, h, L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def _remap_args(who, src, maps, dtype, dims, interpolation):
+    if interpolation not in SAMPLE_MODES:
+        raise ValueError(f"{who}: unknown interpolation {interpolation!r}: expected one of {sorted(SAMPLE_MODES)}")
+    src = src if isinstance(src, torch.Tensor) else np.asarray(src)
+    maps = maps if isinstance(maps, torch.Tensor) else np.asarray(maps)
+    if len(src.shape) not in dims:
+        raise L.KinectPxError(f"{who}: src has {len(src.shape)} dimensions, expected (F, H, W" + (", C) or (F, H, W)" if len(dims) > 1 else ")"))
+    if len(maps.shape) not in (3, 4) or int(maps.shape[-1]) != 2:
+        raise L.KinectPxError(f"{who}: maps must be float32 (M, H', W', 2) or (H', W', 2)")
+    M = int(maps.shape[0]) if len(maps.shape) == 4 else 1
+    F = int(src.shape[0])
+    if not 1 <= M <= SENSOR_MAX_CALIBRATIONS:
+        raise L.KinectPxError(f"{who}: 1 to {SENSOR_MAX_CALIBRATIONS} maps, got {M}")
+    if F % M != 0:
+        raise L.KinectPxError(f"{who}: {M} maps do not divide {F} frames")
+    return _dev(src, dtype), _dev(maps, torch.float32), F, M, int(maps.shape[-3]), int(maps.shape[-2])
+
+
+def remap(src, maps, interpolation, out=None):
+    """AC22: images resampled through stored maps.  src uint8 (F, H, W, C) or (F, H, W), C in {1, 3}; maps float32 (M, H', W', 2) --
+    undistort_map's, (H', W', 2) for one; frame f uses map f % M and M divides F.  interpolation: "bilinear" (colour) or "nearest"
+    (masks, labels, colour images with holes).  -> uint8 (F, H', W', C) (or (F, H', W')): color_to_depth's two samplers at the map's
+    coordinates, zeros where the map entry is NaN or the sample lies outside the source image.
+    out: a contiguous uint8 device tensor of F * H' * W' * C elements to write into."""
+    lib = L.load()
+    col, table, F, M, ho, wo = _remap_args("remap", src, maps, torch.uint8, (3, 4), interpolation)
+    flat = col.dim() == 3
+    hs, ws = int(col.shape[1]), int(col.shape[2])
+    ch = 1 if flat else int(col.shape[3])
+    if out is None:
+        out = torch.empty((F, ho, wo) if flat else (F, ho, wo, ch), dtype=torch.uint8, device=col.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() == F * ho * wo * ch):
+        raise ValueError(f"remap: out must be a contiguous uint8 device tensor of {F * ho * wo * ch} elements")
+    L.check(lib.kpx_remap_u8(L.ptr(col), L.ptr(table), ws, hs, ch, wo, ho, F, M, SAMPLE_MODES[interpolation], L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def remap_depth(src, maps, interpolation="nearest", max_gap_mm=None, out=None):
+    """AC22: depth images resampled through stored maps.  src uint16 (F, H, W) mm; maps as in remap.  "nearest" copies the nearest
+    source pixel (0 stays 0); "bilinear" is depth aware: 0 when one of the four neighbours is 0 or when they differ by more than
+    max_gap_mm (a blend across a depth edge would invent a surface), AC20's bilinear value otherwise.  max_gap_mm is required for
+    "bilinear" and has no default: it is a property of the scene and the rig that nothing in this project measures
+    (float("inf"): never).  -> uint16 (F, H', W').  out: a contiguous uint16 device tensor of F * H' * W' elements to write into."""
+    lib = L.load()
+    if interpolation == "bilinear" and max_gap_mm is None:
+        raise ValueError("remap_depth: the bilinear mode needs max_gap_mm (no default: it depends on the scene and the rig)")
+    dep, table, F, M, ho, wo = _remap_args("remap_depth", src, maps, torch.uint16, (3,), interpolation)
+    hs, ws = int(dep.shape[1]), int(dep.shape[2])
+    if out is None:
+        out = torch.empty((F, ho, wo), dtype=torch.uint16, device=dep.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint16 and out.is_cuda and out.is_contiguous() and out.numel() == F * ho * wo):
+        raise ValueError(f"remap_depth: out must be a contiguous uint16 device tensor of {F * ho * wo} elements")
+    L.check(lib.kpx_remap_depth(L.ptr(dep), L.ptr(table), ws, hs, wo, ho, F, M, SAMPLE_MODES[interpolation], float(0.0 if max_gap_mm is None else max_gap_mm),
+                                L.ptr(out), L.stream_ptr()))
+    return out

@@ -17,8 +17,21 @@ class _Intrinsic:
         self.intrinsic_matrix = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
 
 
+def _undistorted_frames(who, rig, depth, rgb, intrinsic):
+    """the frames of a rig of distorted lenses as its common pinhole camera sees them -> depth (S, H' W'), rgb (S, H' W', 3) or None,
+    the PinholeCameraIntrinsic"""
+    if intrinsic is not None:
+        raise ValueError(f"{who}: give either intrinsic (pinhole frames) or rig (frames as the lenses took them), not both")
+    target = rig.common_pinhole()
+    n = int(depth.shape[0])
+    depth = rig.undistort_depths(depth, pinhole=target).reshape(n, -1)
+    if rgb is not None:
+        rgb = rig.undistort_colors(rgb, pinhole=target, camera="depth", interpolation="nearest").reshape(n, -1, 3)
+    return depth, rgb, target.to_pinhole()
+
+
 def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution, origin, sdf_trunc=None, depth_scale=1.0, depth_trunc=6000.0, mesh=False,
-                    min_cluster_triangles=0, taubin_iterations=0, scalable=False, volume_unit_resolution=16, depth_sampling_stride=4):
+                    min_cluster_triangles=0, taubin_iterations=0, scalable=False, volume_unit_resolution=16, depth_sampling_stride=4, rig=None):
     """depth: uint16 (S, H W) raw frames (synth.sensor_ring's layout; host or device); rgb: uint8 (S, H W, 3) or None (no colours);
     intrinsic: a PinholeCameraIntrinsic, or None for the Kinect's (synth.FX, FY, CX, CY at synth.W x synth.H); sensor_to_master:
     the S - 1 transforms of the sub sensors (sensor 0 is the master, identity).  The world frame is the master's: sensor s is
@@ -28,7 +41,12 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     drops every connected component of fewer triangles (the specks flying pixels leave) and then the vertices nothing names;
     taubin_iterations > 0 smooths with filter_smooth_taubin's defaults before the normals are computed.  scalable=True: a
     ScalableTSDFVolume of voxel length `length / resolution` with volume_unit_resolution and depth_sampling_stride instead of the
-    uniform volume; `origin` is not used (the blocks sit on the world lattice); everything after the volume is the same."""
+    uniform volume; `origin` is not used (the blocks sit on the world lattice); everything after the volume is the same.
+    rig: a calibration.SensorRig of the S sensors for frames as the lenses took them (`intrinsic` must then be None): depth, and rgb
+    already registered into the depth grid (SensorRig.register_colors), are undistorted to rig.common_pinhole() first, both with
+    nearest sampling -- depth values are copied, and bilinear would blend the registered colours' zero holes."""
+    if rig is not None:
+        depth, rgb, intrinsic = _undistorted_frames("fuse_depth_tsdf", rig, depth, rgb, intrinsic)
     if intrinsic is None:
         intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
     n = int(depth.shape[0])
@@ -54,12 +72,15 @@ def fuse_depth_tsdf(depth, rgb, intrinsic, sensor_to_master, length, resolution,
     return vol.extract_point_cloud()
 
 
-def remove_free_space_points(pcd, depth, intrinsic, sensor_to_master, voxel_size, keep_unmeasured=True, depth_scale=1.0, depth_trunc=6000.0):
+def remove_free_space_points(pcd, depth, intrinsic, sensor_to_master, voxel_size, keep_unmeasured=True, depth_scale=1.0, depth_trunc=6000.0, rig=None):
     """pcd: the fused cloud in the master's frame; depth, intrinsic, sensor_to_master, depth_scale, depth_trunc as in fuse_depth_tsdf.
     The cloud's VoxelGrid (voxel_size) is carved by every sensor's depth map in one pass (carve_depth_maps with
     keep_voxels_outside_image=True: a sensor that does not see a voxel says nothing about it); a point is kept when its voxel
     survived.  keep_unmeasured=True: a pixel without depth is no evidence of free space (Open3D's rule, False, carves its whole
-    ray).  -> (PointCloud of the kept points, their indices in pcd: ascending int32 device tensor)"""
+    ray).  rig: as in fuse_depth_tsdf (the depth frames as the lenses took them, `intrinsic` None).
+    -> (PointCloud of the kept points, their indices in pcd: ascending int32 device tensor)"""
+    if rig is not None:
+        depth, _, intrinsic = _undistorted_frames("remove_free_space_points", rig, depth, None, intrinsic)
     if intrinsic is None:
         intrinsic = _Intrinsic(synth.W, synth.H, synth.FX, synth.FY, synth.CX, synth.CY)
     n = int(depth.shape[0])

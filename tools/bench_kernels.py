@@ -60,7 +60,7 @@ def main():
     ap.add_argument("--orient", action="store_true", help="only the normal orientation / EMST rows")
     ap.add_argument("--pointnet", action="store_true", help="only the PointNet forward rows (fused against eval-mode torch modules)")
     ap.add_argument("--pointnet-train", action="store_true", help="only the PointNet training step rows (against train-mode torch modules with torch.optim.Adam)")
-    ap.add_argument("--sensor", action="store_true", help="only the sensor calibration rows (xy_table, color_to_depth, depth_to_color, color_to_depth with the occlusion test)")
+    ap.add_argument("--sensor", action="store_true", help="only the sensor calibration rows (xy_table, color_to_depth, depth_to_color, color_to_depth with the occlusion test, undistort_map, remap, remap_depth)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.sensor:
@@ -726,6 +726,25 @@ def sensor_rows(dev, quick):
         occluded = int(((plain != 0).any(1) & ~(res != 0).any(1)).sum().item())
         report(f"color_to_depth visible {S} x 640x576 <- {S} x 1280x720x{ch} {interp}", ms,
                S * N_PX * (2 + 8 + ch) + S * n_col * ch + S * n_col * 2, frames=S, filled=filled, occluded=occluded)
+    # the undistortion map of one depth lens, then the rig's frames resampled to its common pinhole cameras, one launch
+    # per batch.  Algorithmic bytes of a remap per output pixel: map 8 + source C + output C (2 + 2 for depth), the source counted as
+    # read once.  The rows of F = 4 frames stay inside the 256 MB cache in front of HBM from one repetition to the next; the rows of
+    # the larger batches (frame f uses map f % 4, so the four maps are the only bytes that stay) do not.  100 mm is this bench's choice.
+    target_d, target_c = rig.common_pinhole("depth"), rig.common_pinhole("color")
+    ms, _ = timed(lambda: ops.undistort_map(rig.calibrations[0].depth, target_d), reps=reps, warm=2)
+    report("undistort_map 640x576 (AC22 closed form, fp64)", ms, N_PX * 8, pixels=N_PX)
+    maps_d, maps_c = rig.undistort_maps("depth"), rig.undistort_maps("color")
+    for F in (S, 16 * S):
+        col = color.repeat(F // S, 1, 1, 1)
+        out = torch.empty((F, 720, 1280, 3), dtype=torch.uint8, device=dev)
+        ms, res = timed(lambda: ops.remap(col, maps_c, "bilinear", out=out), reps=reps, warm=2)
+        report(f"remap {F} x 1280x720x3 bilinear", ms, F * n_col * (8 + 3 + 3), frames=F, filled=int((res[:S] != 0).any(-1).sum().item()))
+    for F in (S, 64 * S):
+        dep = depth.view(torch.int16).reshape(S, 576, 640).repeat(F // S, 1, 1).view(torch.uint16)        # (repeat has no uint16 form)
+        out = torch.empty((F, 576, 640), dtype=torch.uint16, device=dev)
+        for interp in ("nearest", "bilinear"):
+            ms, res = timed(lambda: ops.remap_depth(dep, maps_d, interp, gap_mm, out=out), reps=reps, warm=2)
+            report(f"remap_depth {F} x 640x576 {interp}", ms, F * N_PX * (8 + 2 + 2), frames=F, filled=int((res[:S].view(torch.int16) != 0).sum().item()))
 
 
 def odometry_launches(iterations):
