@@ -292,6 +292,22 @@ size_t kpx_covariances_workspace_bytes(int64_t n, int32_t max_nn);
 int kpx_estimate_covariances(const float *pts, int64_t n, double radius, int32_t max_nn, double *cov,
                              void *ws, size_t ws_bytes, void *stream);
 
+/* Self-test of the whole-wave primitives the neighbour searches reduce, scan and broadcast with (csrc/kpx_wave.h): one block of four
+ * waves, every wave applies primitive `kind` to rows of 64 values.  in / out: u64 [rows][64] in device memory, the 32-bit kinds use
+ * the low word; out[r][l] is what lane l holds afterwards (the SUM_DOWN kinds define lane 0 only; F64X9 reduces groups of nine rows
+ * together and stores lane 0, rows % 9 == 0; BCAST broadcasts lane r % 64 of row r).  rows <= 65536. */
+#define KPX_WAVE_SUM_I32 0
+#define KPX_WAVE_MIN_U32 1
+#define KPX_WAVE_MAX_U32 2
+#define KPX_WAVE_MAX_U64 3
+#define KPX_WAVE_MAX_F64 4
+#define KPX_WAVE_INCL_SCAN_I32 5
+#define KPX_WAVE_BCAST 6
+#define KPX_WAVE_SUM_DOWN_F64 7
+#define KPX_WAVE_SUM_DOWN_F32 8
+#define KPX_WAVE_SUM_DOWN_F64X9 9
+int kpx_wave_selftest(int32_t kind, const uint64_t *in, int64_t rows, uint64_t *out, void *stream);
+
 /* Neighbour search between a cloud and ARBITRARY query points ([O3D] KDTreeFlann SearchKNN / SearchRadius / SearchHybrid).
  * The index is a caller-owned device buffer of kpx_search_index_bytes(n) bytes that kpx_search_index_build fills from a float32 (n,3)
  * cloud: grid parameters, cell starts, cell-sorted coordinates, original indices.  It does not point back into pts and the library keeps

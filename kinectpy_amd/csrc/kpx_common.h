@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "../../include/kinectpx.h"
+#include "kpx_wave.h"
 
 #define KPX_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -106,6 +107,7 @@ constexpr int kWave = 64;
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// (the shuffle tree; kpx_wave.h has the same sums on the vector ALU for call sites known to run with all 64 lanes active)
 template <class T> __device__ __forceinline__ T wave_sum(T v)
 {
 #pragma unroll

@@ -186,13 +186,9 @@ __device__ __forceinline__ void grid_radius_scan(const GridParams &g, const uint
 // when that value lies inside the distance the block covers -- the termination rule of the ring walk above
 // (grid_knn_scan).  Otherwise the k-th candidate found so far bounds the true k-th distance: the candidates are
 // gathered again, only those within it, from the block that covers it.  When the buffer fills, gathering stops; the
-// cap candidates held are still real points, so their k-th smallest is a valid bound too.
-__device__ __forceinline__ unsigned long long wave_all_max_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    return v;
-}
+// cap candidates held are still real points, so their k-th smallest is a valid bound too.  The wave's reductions, scans and
+// broadcasts are those of kpx_wave.h (vector ALU only, no ds_bpermute); every call site below is wave-uniform.
+
 // squared distance the block [c-r, c+r] covers around q (infinity once it holds the whole grid)
 __device__ __forceinline__ double block_cover2(const GridParams &g, const double q[3], const int c[3], int r)
 {
@@ -245,10 +241,7 @@ __device__ __forceinline__ unsigned wave_count_select(KeyF key, int m, unsigned 
         const uint4 t4 = hz[0];
         const int hv[4] = { (int)t4.x, (int)t4.y, (int)t4.z, (int)t4.w };
         const int lsum = hv[0] + hv[1] + hv[2] + hv[3];
-        int incl = lsum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t2 = __shfl_up(incl, o, 64); if (lane >= o) incl += t2; }
-        const int excl = incl - lsum;
+        const int incl = wave_incl_scan_i32(lsum), excl = incl - lsum;
         const bool mine = rank > excl && rank <= incl;
         int B = -1, cb = 0, hb = 0;
         if (mine) {
@@ -262,7 +255,7 @@ __device__ __forceinline__ unsigned wave_count_select(KeyF key, int m, unsigned 
         const unsigned long long bm = __builtin_amdgcn_ballot_w64(mine);
         if (bm == 0ull) return a;                                   // fewer than `rank` keys in the window: the caller's count is off
         const int owner = __builtin_ctzll(bm);
-        B = __shfl(B, owner, 64); cb = __shfl(cb, owner, 64); hb = __shfl(hb, owner, 64);
+        B = wave_bcast(B, owner); cb = wave_bcast(cb, owner); hb = wave_bcast(hb, owner);
         const unsigned wend = a + range, bstart = a + ((unsigned)B << shift), bspan = (1u << shift) - 1u;
         const unsigned bend = wend - bstart < bspan ? wend : bstart + bspan;      // the window's end may cut its last bucket
         if (rank - cb == hb) { exact = true; return bend; }        // the rank-th is the last of its bucket
@@ -271,40 +264,29 @@ __device__ __forceinline__ unsigned wave_count_select(KeyF key, int m, unsigned 
     }
     return a;
 }
-__device__ __forceinline__ unsigned wave_all_min_u32(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_all_max_u32(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_all_sum_i32(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // A threshold thr with { pattern <= thr } = the kk smallest of the m non-negative doubles vals[0 .. m) in LDS plus whatever ties with the
 // kk-th (1 <= kk < m): high words first (zero distances -- the query itself, its duplicates -- are counted, not bucketed: with zero in the
 // window the first level's buckets are eight binades wide), low words only among the candidates that share the kk-th high word.
-__device__ __forceinline__ unsigned long long wave_kth_pattern(const double *__restrict__ vals, int m, int kk, uint32_t *__restrict__ hist)
-{
-    const int lane = threadIdx.x & 63;
-    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(vals);           // little endian: word 2 t + 1 is the high word
-    unsigned vmin = 0xFFFFFFFFu, vmax = 0u;
-    int zeros = 0;
-    for (int t = lane; t < m; t += 64) {
-        const unsigned h = w32[2 * t + 1];
+// The statistics of the high words -- smallest non-zero, largest, number of zeros -- come from the gather, which tracks them per lane
+// for the candidates it stores (WaveHighStats).
+struct WaveHighStats {
+    unsigned vmin, vmax;
+    int zeros;
+    __device__ void reset() { vmin = 0xFFFFFFFFu; vmax = 0u; zeros = 0; }
+    __device__ void add(double d)
+    {
+        const unsigned h = (unsigned)((unsigned long long)__double_as_longlong(d) >> 32);
         zeros += h == 0u ? 1 : 0;
         const unsigned nz = h == 0u ? 0xFFFFFFFFu : h;
         vmin = nz < vmin ? nz : vmin; vmax = h > vmax ? h : vmax;
     }
-    vmin = wave_all_min_u32(vmin); vmax = wave_all_max_u32(vmax); zeros = wave_all_sum_i32(zeros);
+};
+__device__ __forceinline__ unsigned long long wave_kth_pattern(const double *__restrict__ vals, int m, int kk, uint32_t *__restrict__ hist, const WaveHighStats &hs)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(vals);           // little endian: word 2 t + 1 is the high word
+    const unsigned vmin = wave_min_u32(hs.vmin), vmax = wave_max_u32(hs.vmax);
+    const int zeros = wave_sum_i32(hs.zeros);
     unsigned P = 0u;
     bool exact = false;
     if (kk > zeros) {
@@ -320,10 +302,10 @@ __device__ __forceinline__ unsigned long long wave_kth_pattern(const double *__r
         c_less += h < P ? 1 : 0;
         if (h == P) { const unsigned l = w32[2 * t]; ++c_eq; lmin = l < lmin ? l : lmin; lmax = l > lmax ? l : lmax; }
     }
-    c_less = wave_all_sum_i32(c_less); c_eq = wave_all_sum_i32(c_eq);
+    c_less = wave_sum_i32(c_less); c_eq = wave_sum_i32(c_eq);
     const int r2 = kk - c_less;                                                // rank of the kk-th among the candidates with high word P
     if (r2 >= c_eq) return ((unsigned long long)P << 32) | 0xFFFFFFFFull;      // all of them are selected
-    lmin = wave_all_min_u32(lmin); lmax = wave_all_max_u32(lmax);
+    lmin = wave_min_u32(lmin); lmax = wave_max_u32(lmax);
     unsigned Q = lmin;
     if (lmin < lmax)
         Q = wave_count_select([&](int t, unsigned &kv) { kv = w32[2 * t]; return w32[2 * t + 1] == P; }, m, lmin, lmax - lmin, r2, hist, exact);
@@ -348,6 +330,8 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
     int maxr = g.dim[0] > g.dim[1] ? g.dim[0] : g.dim[1];
     if (g.dim[2] > maxr) maxr = g.dim[2];
     bool truncated = false;
+    WaveHighStats hs;                                             // per lane, of the candidates this lane stored in the last gather
+    hs.reset();
     auto gather_block = [&](int r, double tau) -> int {
         const int xa = c[0] - r < 0 ? 0 : c[0] - r, xb = c[0] + r >= g.dim[0] ? g.dim[0] - 1 : c[0] + r;
         const int ya = c[1] - r < 0 ? 0 : c[1] - r, yb = c[1] + r >= g.dim[1] ? g.dim[1] - 1 : c[1] + r;
@@ -355,6 +339,7 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
         const int ny = yb - ya + 1, ncols = (xb - xa + 1) * ny;
         int m = 0;
         truncated = false;
+        hs.reset();                                               // every gather starts over: a round that gathers again, or a truncated one
         for (int c0 = 0; c0 < ncols && !truncated; c0 += 64) {
             const int nruns = ncols - c0 < 64 ? ncols - c0 : 64;
             uint32_t s0 = 0;
@@ -365,8 +350,8 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
                 s0 = cell_start[col + za];
                 len = (int)(cell_start[col + zb + 1] - s0);
             }
-            const int incl = wave_incl_scan(len);
-            const int mc = __shfl(incl, 63, 64);
+            const int incl = wave_incl_scan_i32(len);
+            const int mc = wave_bcast(incl, 63);
             if (mc == 0) continue;
             sc.run_s0[lane] = s0;
             sc.run_off[lane] = incl - len;
@@ -390,6 +375,7 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
                 const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
                 const int pos = m + __builtin_popcountll(km & ((1ull << lane) - 1ull));
                 if (keep && pos < sc.cap) {
+                    hs.add(d);
                     sc.vals[pos] = d;
                     if (POS) sc.pos[pos] = sp;
                 }
@@ -418,13 +404,13 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
         const int kk = m < k ? m : k;
         // the threshold of the kk smallest patterns
         unsigned long long lo = 0ull;
-        if (m > k) lo = wave_kth_pattern(sc.vals, m, kk, sc.hist);             // by counting (above)
+        if (m > k) lo = wave_kth_pattern(sc.vals, m, kk, sc.hist, hs);            // by counting (above)
         else if (m > 0) {                                       // everything gathered is selected: the largest pattern
             for (int t = lane; t < m; t += 64) {
                 const unsigned long long p = (unsigned long long)__double_as_longlong(sc.vals[t]);
                 lo = p > lo ? p : lo;
             }
-            lo = wave_all_max_u64(lo);
+            lo = wave_max_u64(lo);
         }
         double top = 0.0;
         int cnt = 0;
@@ -434,8 +420,7 @@ __device__ __forceinline__ bool wave_knn_select(const GridParams &g, const uint3
             if (le) top = fmax(top, sc.vals[t]);
             cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) top = fmax(top, __shfl_xor(top, o, 64));
+        top = wave_max_f64(top);
         if (!truncated && (whole || top < cov2)) {
             out.m = m; out.kk = kk; out.cnt = cnt; out.thr = lo; out.top = top;
             return true;
@@ -475,9 +460,7 @@ __device__ __forceinline__ int32_t wave_knn_tie_threshold(const WaveKnnScratch &
                 const int32_t oi = sidx[sc.pos[t]];
                 if (oi > last && oi < cand) cand = oi;
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int32_t t2 = __shfl_xor(cand, o, 64); cand = t2 < cand ? t2 : cand; }
-        last = cand;
+        last = (int32_t)wave_min_u32((unsigned)cand);              // original indices: >= 0, the unsigned order is theirs
     }
     return last;
 }
@@ -499,7 +482,10 @@ __device__ __forceinline__ bool wave_knn_is_selected(const WaveKnnScratch &sc, c
 //     Op::Heap                    HeapD or HeapDI; with kPos the ring walk is handed op.sidx and the heap holds original indices
 //     op.r2max(heap_walk)         the hybrid search's squared radius in the convention of wave_knn_select / grid_knn_scan
 //     op.defer(s)                 lane 0, when the wave form hands query s to the next pass
-//     op.wave(sc, res, s, spts)   the whole wave, with the selected set of query s in LDS
+//     op.wave(sc, res, s, spts)   the whole wave, with the selected set of query s in LDS.  The operator OWNS the wave's scratch from
+//                                 here on: it may overwrite sc.vals, sc.run_s0 and sc.run_off (SorOp stores negated roots over the
+//                                 distances and lists positions in run_off), so nothing after op.wave -- the kernel's epilogue, a second
+//                                 consumer -- may read them; the next query's gather fills them again
 //     op.heap(s, heap)            one thread, with the filled heap of query s (heap_alt: a second consumer, chosen by the host)
 // Queries are cell-sorted positions: [q0, q1), or -- in_list != NULL -- in_list[0 .. *in_count), the ones an earlier pass listed.
 template <class Op, int WAVES>

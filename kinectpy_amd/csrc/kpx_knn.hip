@@ -247,13 +247,34 @@ struct SorOp {
     __device__ void wave(const WaveKnnScratch &sc, const WaveKnnResult &res, int64_t s, const float *) const
     {
         const int lane = threadIdx.x & 63;
+        // The roots, ONE fp64 sqrt sequence per 64 selected candidates instead of one per 64 gathered (a chunk of the buffer holds a
+        // handful of selected values, and the sequence ran for each chunk under a divergent test): a ballot per chunk lists the selected
+        // positions, lanes 0 .. n-1 take the roots of up to 64 listed positions and store them back NEGATED -- the sign marks a
+        // candidate as selected for the sum below (d^2 = 0 gives -0).  Nothing reads the distances after this operator.
+        int32_t *list = sc.run_off;                                  // free once the gather is over
+        int listed = 0;                                              // wave-uniform
+        auto roots = [&](int n) {
+            wave_lds_fence();
+            if (lane < n) { const int t = list[lane]; sc.vals[t] = -sqrt(sc.vals[t]); }
+            wave_lds_fence();
+        };
+        for (int t0 = 0; t0 < res.m; t0 += 64) {
+            const int t = t0 + lane;
+            const bool sel = t < res.m && (unsigned long long)__double_as_longlong(sc.vals[t]) <= res.thr;
+            const unsigned long long bm = __builtin_amdgcn_ballot_w64(sel);
+            const int n = __builtin_popcountll(bm);
+            if (listed + n > 64) { roots(listed); listed = 0; }
+            if (sel) list[listed + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u))] = t;
+            listed += n;
+        }
+        roots(listed);
+        // the sum in the order it always had: lane l adds its candidates l, l + 64, ... in turn, then the wave's tree
         double sum = 0.0;
         for (int t = lane; t < res.m; t += 64) {
-            const double d = sc.vals[t];
-            if ((unsigned long long)__double_as_longlong(d) <= res.thr) sum += sqrt(d);
+            const double v = sc.vals[t];
+            if (__double_as_longlong(v) < 0) sum += -v;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        sum = wave_sum_down_f64(sum);                                // lane 0
         const double total = sum - (double)(res.cnt - res.kk) * sqrt(res.top);      // ties beyond the k-th slot
         if (lane == 0) avg[sidx ? (int64_t)sidx[s] : s - q0] = res.kk > 0 ? total / (double)res.kk : -1.0;
     }
@@ -287,42 +308,10 @@ struct SorOp {
 // fp64 flops for the distances and a few 32-bit operations per candidate and counting level -- vector ALU work on LDS-resident operands
 // (12 B per candidate, staged once per cell); DESIGN.md section 5.3 has the numbers, also against the wave-per-16-queries form this
 // kernel replaced.
-__device__ __forceinline__ int dppi(int v, int ctrl_sel)
-{
-    switch (ctrl_sel) {
-    case 1: return __builtin_amdgcn_update_dpp(v, v, 0x121, 0xF, 0xF, false);
-    case 2: return __builtin_amdgcn_update_dpp(v, v, 0x122, 0xF, 0xF, false);
-    case 4: return __builtin_amdgcn_update_dpp(v, v, 0x124, 0xF, 0xF, false);
-    default: return __builtin_amdgcn_update_dpp(v, v, 0x128, 0xF, 0xF, false);
-    }
-}
-// whole-wave reductions of 32-bit integers (four DPP row steps, the four rows folded through the LDS crossbar); the result is the same in
-// every lane
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    v += dppi(v, 1); v += dppi(v, 2); v += dppi(v, 4); v += dppi(v, 8);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_min_u(unsigned v)
-{
-    unsigned o;
-    o = (unsigned)dppi((int)v, 1); v = o < v ? o : v; o = (unsigned)dppi((int)v, 2); v = o < v ? o : v;
-    o = (unsigned)dppi((int)v, 4); v = o < v ? o : v; o = (unsigned)dppi((int)v, 8); v = o < v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 16, 64); v = o < v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 32, 64); v = o < v ? o : v;
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u(unsigned v)
-{
-    unsigned o;
-    o = (unsigned)dppi((int)v, 1); v = o > v ? o : v; o = (unsigned)dppi((int)v, 2); v = o > v ? o : v;
-    o = (unsigned)dppi((int)v, 4); v = o > v ? o : v; o = (unsigned)dppi((int)v, 8); v = o > v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 16, 64); v = o > v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 32, 64); v = o > v ? o : v;
-    return v;
-}
+// The whole-wave reductions, the scan and the broadcasts are those of kpx_wave.h (result the same in every lane).
+__device__ __forceinline__ int wave_sum_i(int v) { return wave_sum_i32(v); }
+__device__ __forceinline__ unsigned wave_min_u(unsigned v) { return wave_min_u32(v); }
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) { return wave_max_u32(v); }
 constexpr int kSorBuckets = 256;              // buckets of the counting selection
 constexpr int kSorTieRoom = 32;               // candidates tied with the k-th beyond k the selection buffer still holds
 constexpr int kBlkQueries = 64, kBlkWaves = 4;
@@ -386,7 +375,7 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
                             ln = (int)(cell_start[col + zb + 1] - s0);
                         }
                     }
-                    const int incl = wave_incl_scan(ln);
+                    const int incl = wave_incl_scan_i32(ln);
                     if (lane < 32) { run_s0[lane] = s0; run_off[lane] = lane < nruns ? incl - ln : INT_MAX; }
                     if (lane == 63) s_m = incl;
                 }
@@ -469,7 +458,7 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
                                 const uint4 t4 = hz[0];
                                 const int hv[BPL] = { (int)t4.x, (int)t4.y, (int)t4.z, (int)t4.w };
                                 const int lsum = hv[0] + hv[1] + hv[2] + hv[3];
-                                const int incl = wave_incl_scan(lsum), excl = incl - lsum;
+                                const int incl = wave_incl_scan_i32(lsum), excl = incl - lsum;
                                 const bool mine = need_k > excl && need_k <= incl;
                                 int B = -1, cb = 0, hb = 0;
                                 if (mine) {
@@ -482,7 +471,7 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
                                 }
                                 const unsigned long long bm = __builtin_amdgcn_ballot_w64(mine);
                                 const int owner = bm ? __builtin_ctzll(bm) : 0;
-                                B = __shfl(B, owner, 64); cb = __shfl(cb, owner, 64); hb = __shfl(hb, owner, 64);
+                                B = wave_bcast(B, owner); cb = wave_bcast(cb, owner); hb = wave_bcast(hb, owner);
                                 // (the window's end may cut the last bucket -- the cover's high word at the first level: nothing beyond it was counted)
                                 const unsigned wend = a + range, bstart = a + ((unsigned)(B < 0 ? 0 : B) << shift), bspan = (1u << shift) - 1u;
                                 const unsigned bend = wend - bstart < bspan ? wend : bstart + bspan;
@@ -542,8 +531,7 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
                             wave_lds_fence();
                             double acc = 0.0;
                             for (int t = lane; t < n_le; t += 64) acc += sqrt(selbuf[t]);
-#pragma unroll
-                            for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+                            acc = wave_sum_down_f64(acc);
                             if (lane == 0) {
                                 const double top = __longlong_as_double((long long)(((unsigned long long)P << 32) | Q));
                                 const double total = n_le > kk ? acc - (double)(n_le - kk) * sqrt(top) : acc;
@@ -564,7 +552,7 @@ __global__ __launch_bounds__(64 * kBlkWaves, KPX_SOR_BLOCK_MINB) void sor_block_
             if (fm != 0ull) {
                 int fb_base = 0;
                 if (lane == 0) fb_base = atomicAdd(fb_count, __builtin_popcountll(fm));
-                fb_base = __shfl(fb_base, 0, 64);
+                fb_base = wave_bcast(fb_base, 0);
                 if (fb) fb_list[fb_base + __builtin_popcountll(fm & ((1ull << lane) - 1ull))] = (int32_t)(base + lane);
             }
         }
@@ -836,10 +824,7 @@ struct MomentsOp {
                 c[3] += x * x; c[4] += x * y; c[5] += x * z; c[6] += y * y; c[7] += y * z; c[8] += z * z;
             }
         }
-#pragma unroll
-        for (int a9 = 0; a9 < 9; ++a9)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c[a9] += __shfl_xor(c[a9], o, 64);
+        wave_sum_down_f64x9(c);                                      // lane 0: the tree the xor butterfly left there
         if (lane == 0) {
             double *o = covbuf + 10 * s;
 #pragma unroll

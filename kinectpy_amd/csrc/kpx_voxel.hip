@@ -113,28 +113,30 @@ __device__ __forceinline__ void voxel_batch_axis_bits(const double d[3], int bit
 // are not: 16 consecutive points of a surface cloud -- a wave's rows, a target tile of the culled ICP sweep (kpx_nnlocal.h) -- span
 // 177 instead of 246 mm (median; p99 677 instead of 1255) on the bench's 35 mm clouds, a wave multiplies 2.0 instead of 3.0 tiles
 // on average (p99 9 instead of 13; profiles/r03/exp_curve_hilbert.txt).  `bits` >= 1.
-__device__ __forceinline__ unsigned long long voxel_hcode(unsigned long long x, unsigned long long y, unsigned long long z, int bits)
+// Word: the integer the bit loops run in -- uint64_t, or uint32_t when 3 `bits` <= 32 (a 64-bit shift, and, xor is two or more vector
+// instructions per step; the values are the same numbers).
+template <class Word> __device__ __forceinline__ Word voxel_hcode(Word x, Word y, Word z, int bits)
 {
-    unsigned long long X[3] = { x, y, z };
-    const unsigned long long M = 1ull << (bits - 1);
-    for (unsigned long long Q = M; Q > 1ull; Q >>= 1) {
-        const unsigned long long P = Q - 1ull;
+    Word X[3] = { x, y, z };
+    const Word M = (Word)1 << (bits - 1);
+    for (Word Q = M; Q > (Word)1; Q >>= 1) {
+        const Word P = Q - (Word)1;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             if (X[i] & Q) X[0] ^= P;
-            else { const unsigned long long t = (X[0] ^ X[i]) & P; X[0] ^= t; X[i] ^= t; }
+            else { const Word t = (X[0] ^ X[i]) & P; X[0] ^= t; X[i] ^= t; }
         }
     }
     X[1] ^= X[0];
     X[2] ^= X[1];
-    unsigned long long t = 0ull;
-    for (unsigned long long Q = M; Q > 1ull; Q >>= 1)
-        if (X[2] & Q) t ^= Q - 1ull;
+    Word t = 0;
+    for (Word Q = M; Q > (Word)1; Q >>= 1)
+        if (X[2] & Q) t ^= Q - (Word)1;
     X[0] ^= t; X[1] ^= t; X[2] ^= t;
-    unsigned long long k = 0ull;
+    Word k = 0;
     for (int b = bits - 1; b >= 0; --b) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) k = (k << 1) | ((X[i] >> b) & 1ull);
+        for (int i = 0; i < 3; ++i) k = (k << 1) | ((X[i] >> b) & (Word)1);
     }
     return k;
 }
@@ -162,13 +164,14 @@ __device__ __forceinline__ int voxel_hilbert_key_bits(const int ab[3], int m)
     for (int a = 0; a < 3; ++a) n += ab[a] > m ? ab[a] - m : 0;
     return n;
 }
-// key of one voxel: [x >> m | y >> m | z >> m] (row-major over the cubes) above the cube's Hilbert code of the low m bits
-__device__ __forceinline__ unsigned long long voxel_hilbert_key(unsigned long long x, unsigned long long y, unsigned long long z, const int ab[3], int m)
+// key of one voxel: [x >> m | y >> m | z >> m] (row-major over the cubes) above the cube's Hilbert code of the low m bits.
+// Word = uint32_t: voxel_hilbert_key_bits(ab, m) <= 31 and every axis value below 2^ab[a] (the key and every shift fit the word).
+template <class Word> __device__ __forceinline__ Word voxel_hilbert_key(Word x, Word y, Word z, const int ab[3], int m)
 {
-    const unsigned long long mask = (1ull << m) - 1ull;
+    const Word mask = ((Word)1 << m) - (Word)1;
     const int ey = ab[1] > m ? ab[1] - m : 0, ez = ab[2] > m ? ab[2] - m : 0;
-    const unsigned long long hi = (((x >> m) << ey | (y >> m)) << ez) | (z >> m);
-    return (hi << (3 * m)) | voxel_hcode(x & mask, y & mask, z & mask, m);
+    const Word hi = (((x >> m) << ey | (y >> m)) << ez) | (z >> m);
+    return (hi << (3 * m)) | voxel_hcode<Word>(x & mask, y & mask, z & mask, m);
 }
 // largest grid extents of the batch (index < floor((max - origin) / v) + 1) and whether count x DX x DY x DZ fits 64 bits
 __device__ __forceinline__ void voxel_batch_dims(const VoxelBatch &b, const double *__restrict__ bbox, double voxel, double d[3], int *overflow)
@@ -216,13 +219,15 @@ template <class Key> struct BatchKeys {
     struct Grid {
         uint64_t DX, DY, DZ;
         int overflow, morton, ab[3], m;
+        int kb;                             // width of the curve key below the cloud number
+        int narrow;                         // the whole key fits 32 bits: cloud | curve key, or count x DX x DY x DZ < 2^32
     };
     Key *keys;
     int32_t *err, *bits_out;
     __device__ __forceinline__ Grid grid(const VoxelBatch &b, const double *__restrict__ bbox, double voxel) const
     {
         __shared__ double dims[3];
-        __shared__ int overflow, axis_bits[3], cube_bits;
+        __shared__ int overflow, axis_bits[3], cube_bits, key_bits, narrow;
         if (threadIdx.x == 0) {
             double d[3];
             int ov;
@@ -234,18 +239,30 @@ template <class Key> struct BatchKeys {
             axis_bits[0] = ab[0]; axis_bits[1] = ab[1]; axis_bits[2] = ab[2];
             while ((1 << cb) < b.count) ++cb;
             cube_bits = voxel_hilbert_cube_bits(ab, cb);
-            overflow = (ov || (b.morton && voxel_hilbert_key_bits(ab, cube_bits) + cb > 64)) ? 1 : 0;
+            key_bits = voxel_hilbert_key_bits(ab, cube_bits);
+            overflow = (ov || (b.morton && key_bits + cb > 64)) ? 1 : 0;
+            // 32-bit words throughout: every value and every shift of the key then fits one (a valid point's index on axis a is below
+            // d[a] <= 2^ab[a]; a bad one's is 0).  key_bits <= 31 keeps the cloud number's shift defined when cb = 0.
+            if (b.morton) narrow = (!overflow && key_bits + cb <= 32 && key_bits <= 31) ? 1 : 0;
+            else narrow = (!ov && ((double)b.count * d[0]) * (d[1] * d[2]) < 4294967296.0) ? 1 : 0;
         }
         __syncthreads();
-        return Grid{ (uint64_t)dims[0], (uint64_t)dims[1], (uint64_t)dims[2], overflow, b.morton, { axis_bits[0], axis_bits[1], axis_bits[2] }, cube_bits };
+        return Grid{ (uint64_t)dims[0], (uint64_t)dims[1], (uint64_t)dims[2], overflow, b.morton, { axis_bits[0], axis_bits[1], axis_bits[2] }, cube_bits,
+                     key_bits, narrow };
     }
     __device__ __forceinline__ void put(const Grid &g, const double *__restrict__ bbox, double voxel, int64_t i, int c, const double q[3]) const
     {
         double f[3];
         const bool bad = voxel_cell(q, bbox + 8 * c, voxel, f) || g.overflow;
         if (bad) { err[c] = 1; f[0] = f[1] = f[2] = 0.0; }
-        if (g.morton)
-            keys[i] = (Key)(((uint64_t)c << voxel_hilbert_key_bits(g.ab, g.m)) | voxel_hilbert_key((uint64_t)f[0], (uint64_t)f[1], (uint64_t)f[2], g.ab, g.m));
+        if constexpr (sizeof(Key) == 4) {
+            if (g.narrow) {                  // block-uniform; the same numbers as the 64-bit form below, which truncates its result to Key
+                if (g.morton) keys[i] = ((uint32_t)c << g.kb) | voxel_hilbert_key<uint32_t>((uint32_t)f[0], (uint32_t)f[1], (uint32_t)f[2], g.ab, g.m);
+                else keys[i] = (((uint32_t)c * (uint32_t)g.DX + (uint32_t)f[0]) * (uint32_t)g.DY + (uint32_t)f[1]) * (uint32_t)g.DZ + (uint32_t)f[2];
+                return;
+            }
+        }
+        if (g.morton) keys[i] = (Key)(((uint64_t)c << g.kb) | voxel_hilbert_key<uint64_t>((uint64_t)f[0], (uint64_t)f[1], (uint64_t)f[2], g.ab, g.m));
         else keys[i] = (Key)((((uint64_t)c * g.DX + (uint64_t)f[0]) * g.DY + (uint64_t)f[1]) * g.DZ + (uint64_t)f[2]);
     }
 };
