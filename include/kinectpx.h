@@ -308,6 +308,13 @@ int kpx_estimate_covariances(const float *pts, int64_t n, double radius, int32_t
 #define KPX_WAVE_SUM_DOWN_F64X9 9
 int kpx_wave_selftest(int32_t kind, const uint64_t *in, int64_t rows, uint64_t *out, void *stream);
 
+/* The group pass of the neighbour search (four queries per wave, in front of the wave-per-query passes of kpx_sor* with nb_neighbors
+ * <= 32 and of kpx_estimate_normals / kpx_estimate_covariances with max_nn <= 48): out[0] = the queries the calling thread's last such
+ * pass was given, out[1] = the ones it handed on to the passes behind it; {0, 0} before any.  Read back from the pass's counter word in
+ * that call's workspace -- valid until the workspace is used again -- after a synchronisation of that call's stream.  For tests and
+ * measurements: no result depends on which pass settled a query. */
+int kpx_knn_group_last(int64_t *out /* [2] */);
+
 /* Neighbour search between a cloud and ARBITRARY query points ([O3D] KDTreeFlann SearchKNN / SearchRadius / SearchHybrid).
  * The index is a caller-owned device buffer of kpx_search_index_bytes(n) bytes that kpx_search_index_build fills from a float32 (n,3)
  * cloud: grid parameters, cell starts, cell-sorted coordinates, original indices.  It does not point back into pts and the library keeps

@@ -15,8 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # KPX_LIBRARY: another build of the same library (A/B runs of compile-time variants, e.g. -DKPX_ICP_WAVES=2)
 _DEFAULT_SO = os.path.join(_HERE, "libkinectpx.so")
 SO_PATH = os.environ.get("KPX_LIBRARY") or _DEFAULT_SO
-# entries that only test the library itself: a build without them still serves as the other side of an A/B run
-SELFTEST_ONLY = ("kpx_wave_selftest",)
+# entries that only test or report on the library itself: a build without them still serves as the other side of an A/B run
+SELFTEST_ONLY = ("kpx_wave_selftest", "kpx_knn_group_last")
 
 _i64, _i32, _f64, _u64, _vp, _sz = C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_void_p, C.c_size_t
 
@@ -49,6 +49,7 @@ SIGNATURES = {
     "kpx_fuse_voxel_workspace_bytes": (_sz, [_i64]),
     "kpx_fuse_voxel_downsample": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_wave_selftest": (C.c_int, [_i32, _vp, _i64, _vp, _vp]),
+    "kpx_knn_group_last": (C.c_int, [_vp]),
     "kpx_sor_workspace_bytes": (_sz, [_i64, _i32]),
     "kpx_sor": (C.c_int, [_vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kpx_sor_partial": (C.c_int, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),

@@ -516,6 +516,199 @@ __global__ __launch_bounds__(WAVES * 64) void knn_wave_kernel(const GridParams *
         wave_lds_fence();
     }
 }
+// ---- four queries per wave: a query per row of 16 lanes (SOR, normals / covariances) -------------------------------------------------------
+// knn_wave_kernel pays its fixed work -- cell coordinates and cover in fp64, the run look-up, the scans, every level of the counting
+// selection, the reductions -- once per wave and so once per query; only the gather and the sums scale with a query's 150-250
+// candidates.  Here row g of a wave takes query 4 e + g and every wave-wide step serves four queries; the reductions and scans are the
+// row forms of kpx_wave.h.  The kernel knows the COMMON PATH only, round 0 of wave_knn_select at r = 1: the clipped 3 x 3 x 3 block (at
+// most nine runs), candidates appended in the same ascending order (the row's 16 bits of the ballot), the kk smallest by counting the
+// high words.  It SETTLES a query only when that is the wave kernel's answer too -- not truncated; m >= k with the k-th inside the cover
+// (at least kk candidates strictly nearer than cov2, the rule of sor_block_kernel), or m < k with the block whole; and a high-word pivot
+// with exactly kk candidates at or below it, so cnt == kk and neither the low words nor the index tie rule are ever asked -- and lists
+// everything else for the unchanged cascade behind it (knn_wave_kernel at its present buffer, then the later passes): a listed query
+// gets bit for bit what it always got.  `cap` (the buffer per query, below the wave pass's) is free to tune: overflow only defers.
+// Control flow is wave-uniform with all 64 lanes active: rows that are finished, deferred or past the end are predicated, a tail row
+// replays the last query with its stores suppressed.
+// An operator of this kernel has, besides the members listed above,
+//     op.row(res, s, spts)        all four rows at once, each with ITS query s and selected set (RowKnnResult).  The sums keep the wave
+//                                 form's association: there lane l adds candidates l, l + 64, ... in turn and wave_sum_down_* folds
+//                                 halves, then row pairs, then the row; here lane j of the row keeps the four accumulators a_q of
+//                                 t = j + 16 q (mod 64) and forms (a0 + a2) + (a1 + a3) before the row's four steps.
+constexpr int kKnnRowBuckets = 256;        // per row: 16 per lane
+struct RowKnnResult {
+    double *vals;              // the row's m candidate distances (the operator may overwrite them)
+    const uint32_t *pos;       // their sorted positions (kPos only)
+    uint32_t *list;            // kKnnRowBuckets / 4 (= 64) free words of the row
+    int m, kk, k;              // selected: the kk <= k candidates t < m whose d^2 high word is <= hi_thr (m = 0: nothing to store)
+    unsigned hi_thr;
+    int trips16;               // wave-uniform: 16 * trips16 covers every row's m
+    bool store;                // false: a tail row, or a query that was handed on -- compute, store nothing
+};
+template <class Op, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, Op::kGroupWavesPerSimd) void knn_group_kernel(const GridParams *__restrict__ gp, const uint32_t *__restrict__ cell_start,
+                                                               const float *__restrict__ spts, int64_t q0, int64_t q1, int k, int cap, Op op,
+                                                               int32_t *__restrict__ fb_list, int32_t *__restrict__ fb_count)
+{
+    extern __shared__ __align__(16) double lds[];                // WAVES x 4 x cap distances, then (kPos) WAVES x 4 x cap positions
+    __shared__ uint32_t run_s0[WAVES][4][16];
+    __shared__ int32_t run_off[WAVES][4][16];
+    __shared__ __align__(16) uint32_t row_hist[WAVES][4][kKnnRowBuckets / 4];      // byte counters: cap <= 256
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, row = lane >> 4, j = lane & 15;
+    double *vals = lds + ((size_t)wave * 4 + row) * cap;
+    uint32_t *pos = nullptr;
+    if constexpr (Op::kPos) pos = reinterpret_cast<uint32_t *>(lds + (size_t)WAVES * 4 * cap) + ((size_t)wave * 4 + row) * cap;
+    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(vals);            // little endian: word 2 t + 1 is the high word
+    uint32_t *rs0 = run_s0[wave][row], *hist = row_hist[wave][row];
+    int32_t *roff = run_off[wave][row];
+    const GridParams g = *gp;
+    const int64_t nq = q1 - q0;
+    const double r2max = op.r2max(false);
+    for (int64_t e = (int64_t)blockIdx.x * WAVES + wave; 4 * e < nq; e += (int64_t)gridDim.x * WAVES) {
+        const bool valid = 4 * e + row < nq;
+        const int64_t s = q0 + (valid ? 4 * e + row : nq - 1);
+        const double q[3] = { (double)spts[3 * s], (double)spts[3 * s + 1], (double)spts[3 * s + 2] };
+        int c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = cell_coord(q[a], g.org[a], g.h, g.dim[a]);
+        const double cov2 = block_cover2(g, q, c, 1);
+        const bool whole = cov2 == INFINITY || cov2 >= r2max;   // the block holds everything that may be selected
+        // the row's runs, one per (x, y) column of the clipped block, in the wave kernel's order
+        const int xa = c[0] - 1 < 0 ? 0 : c[0] - 1, xb = c[0] + 1 >= g.dim[0] ? g.dim[0] - 1 : c[0] + 1;
+        const int ya = c[1] - 1 < 0 ? 0 : c[1] - 1, yb = c[1] + 1 >= g.dim[1] ? g.dim[1] - 1 : c[1] + 1;
+        const int za = c[2] - 1 < 0 ? 0 : c[2] - 1, zb = c[2] + 1 >= g.dim[2] ? g.dim[2] - 1 : c[2] + 1;
+        const int ny = yb - ya + 1, ncols = (xb - xa + 1) * ny;
+        uint32_t s0 = 0;
+        int len = 0;
+        if (j < ncols) {
+            const int x = xa + j / ny, y = ya + j % ny;
+            const int64_t col = ((int64_t)x * g.dim[1] + y) * g.dim[2];
+            s0 = cell_start[col + za];
+            len = (int)(cell_start[col + zb + 1] - s0);
+        }
+        const int incl = row_incl_scan_i32(len);
+        const int mc = row_sum_i32(len);
+        rs0[j] = s0;
+        roff[j] = j < ncols ? incl - len : INT_MAX;
+        wave_lds_fence();
+        const int mcmax = (int)wave_max_u32((unsigned)mc);
+        // The nine runs of the row in registers (offset; start minus offset): the run of candidate t is the last one whose offset is
+        // <= t (the offsets ascend; INT_MAX past the last run) -- a chain of compares, no LDS look-up inside the loop.  Op::kGroupTrips trips of 16
+        // candidates are fetched together (a lane past its row's end fetches the query itself), then appended in order.
+        int roffs[9];
+        uint32_t rbase[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { roffs[i] = roff[i]; rbase[i] = rs0[i] - (uint32_t)roffs[i]; }
+        int m = 0, nin = 0;                                       // m: the same in all lanes of the row; nin: this lane's candidates inside the cover
+        WaveHighStats hs;
+        hs.reset();
+        constexpr int U = Op::kGroupTrips;
+        for (int t0 = 0; t0 < mcmax; t0 += 16 * U) {
+            uint32_t sp[U];
+            float px[U], py[U], pz[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int t = t0 + 16 * u + j;
+                uint32_t b = rbase[0];
+#pragma unroll
+                for (int i = 1; i < 9; ++i) b = roffs[i] <= t ? rbase[i] : b;
+                sp[u] = t < mc ? b + (uint32_t)t : (uint32_t)s;
+                const float *pp = spts + 3 * (int64_t)sp[u];
+                px[u] = pp[0]; py[u] = pp[1]; pz[u] = pp[2];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int t = t0 + 16 * u + j;
+                const double dx = q[0] - (double)px[u], dy = q[1] - (double)py[u], dz = q[2] - (double)pz[u];
+                const double d = fma(dz, dz, fma(dy, dy, dx * dx));
+                const bool keep = t < mc && d < r2max;
+                const unsigned bits = (unsigned)(__builtin_amdgcn_ballot_w64(keep) >> (16 * row)) & 0xFFFFu;
+                const int p = m + __builtin_popcount(bits & ((1u << j) - 1u));
+                if (keep && p < cap) {
+                    hs.add(d);
+                    nin += d < cov2 ? 1 : 0;
+                    vals[p] = d;
+                    if constexpr (Op::kPos) pos[p] = sp[u];
+                }
+                m += __builtin_popcount(bits);
+            }
+        }
+        wave_lds_fence();
+        const int kk = m < k ? m : k;
+        nin = row_sum_i32(nin);
+        // handed on: truncated (the wave kernel's `m >= cap`), too few candidates in a block that is not whole, the kk-th not inside the cover
+        bool defer = m >= cap || (!whole && (m < k || nin < kk));
+        unsigned hi_thr = 0xFFFFFFFFu;                            // m <= k: everything gathered is selected
+        bool run = !defer && m > k;
+        const int mmax = (int)wave_max_u32((unsigned)(defer ? 0 : m));
+        if (__builtin_amdgcn_ballot_w64(run) != 0ull) {
+            // the k-th smallest high word by counting (wave_count_select, per row): zero distances are counted, not bucketed, and the
+            // window runs from the smallest non-zero high word to the largest
+            const unsigned vmin = row_min_u32(hs.vmin), vmax = row_max_u32(hs.vmax);
+            int rank = kk - row_sum_i32(hs.zeros);
+            unsigned a = vmin, range = vmax - vmin;
+            if (run && rank <= 0) {                               // the kk-th is a zero distance: exactly kk of them, or duplicates beyond k
+                if (rank == 0) hi_thr = 0u; else defer = true;
+                run = false;
+            }
+            while (__builtin_amdgcn_ballot_w64(run) != 0ull) {
+                const int shift = range >= 256u ? 24 - __builtin_clz(range) : 0;      // range >> shift <= 255
+                uint4 *hz = reinterpret_cast<uint4 *>(hist + 4 * j);      // this lane's 16 buckets, a byte each (a row holds fewer than 256 keys)
+                hz[0] = make_uint4(0u, 0u, 0u, 0u);
+                wave_lds_fence();
+#pragma unroll 4
+                for (int t = j; t < mmax; t += 16) {
+                    if (run && t < m) {
+                        const unsigned kv = w32[2 * t + 1], b = (kv - a) >> shift;
+                        if (kv != 0u && kv - a <= range) __hip_atomic_fetch_add(hist + (b >> 2), 1u << (8 * (b & 3u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+                wave_lds_fence();
+                const uint4 t4 = hz[0];
+                const unsigned hw[4] = { t4.x, t4.y, t4.z, t4.w };
+                int hv[16];
+#pragma unroll
+                for (int w = 0; w < 16; ++w) hv[w] = (int)((hw[w >> 2] >> (8 * (w & 3))) & 255u);
+                int lsum = 0;
+#pragma unroll
+                for (int w = 0; w < 16; ++w) lsum += hv[w];
+                const int incl2 = row_incl_scan_i32(lsum), excl = incl2 - lsum;
+                const bool mine = run && rank > excl && rank <= incl2;
+                unsigned found = 0u;                              // bit 31, bucket (8 bits), keys below it (11), keys in it (11): m < 2048
+                if (mine) {
+                    int cum = excl;
+#pragma unroll
+                    for (int w = 0; w < 16; ++w) {
+                        if (found == 0u && rank <= cum + hv[w]) found = 0x80000000u | (unsigned)(16 * j + w) | ((unsigned)cum << 8) | ((unsigned)hv[w] << 19);
+                        cum += hv[w];
+                    }
+                }
+                found = row_reduce_u32(found, [](unsigned x, unsigned y) { return x | y; });      // one owner per row at most
+                const int B = (int)(found & 255u), cb = (int)((found >> 8) & 2047u), hb = (int)((found >> 19) & 2047u);
+                const unsigned wend = a + range, bstart = a + ((unsigned)B << shift), bspan = (1u << shift) - 1u;
+                const unsigned bend = wend - bstart < bspan ? wend : bstart + bspan;      // the window's end may cut its last bucket
+                if (run) {
+                    if ((found >> 31) == 0u) { defer = true; run = false; }               // fewer than `rank` keys in the window: cannot happen
+                    else if (rank - cb == hb) { hi_thr = bend; run = false; }             // the rank-th is the last of its bucket: exactly kk at or below
+                    else if (shift == 0) { defer = true; run = false; }                   // candidates share the k-th high word: the low words decide
+                    else { rank -= cb; a = bstart; range = bend - bstart; }
+                }
+            }
+        }
+        const RowKnnResult res{ vals, pos, hist, defer ? 0 : m, kk, k, hi_thr, (mmax + 15) >> 4, valid && !defer };
+        op.row(res, s, spts);
+        // what was not settled: ONE counter update per wave
+        const bool hand = valid && defer && j == 0;
+        const unsigned long long fm = __builtin_amdgcn_ballot_w64(hand);
+        if (fm != 0ull) {
+            int fb_base = 0;
+            if (lane == 0) fb_base = atomicAdd(fb_count, __builtin_popcountll(fm));
+            fb_base = wave_bcast(fb_base, 0);
+            if (hand) fb_list[fb_base + __builtin_popcountll(fm & ((1ull << lane) - 1ull))] = (int32_t)s;
+        }
+        wave_lds_fence();
+    }
+}
+
 // Exact ring walk, one thread per query (queries in cell order: neighbouring threads walk neighbouring cells) with a k-heap: in LDS
 // (layout [slot][thread]), or -- gheap != NULL, k beyond what LDS holds -- in the workspace, strided by the grid's thread count.
 template <class Op, bool ALT>
@@ -602,6 +795,33 @@ int knn_cascade(const Grid &g, int k, const Op &op, int64_t q0, int64_t q1, cons
     if (heap.rc) return heap.rc;
     hipLaunchKernelGGL(heap.kernel, dim3(hp.blocks), dim3(hp.threads), hp.lds, st, g.params, g.cell_start, g.sorted_pts, q0, q1, k, op, list, count,
                        hp.gheap, hp.gix);
+    return KPX_OK;
+}
+
+// The group pass in front of a cascade: all of [q0, q1) through knn_group_kernel; what it does not settle is listed in fb_list, counted in
+// *fb_count (a cleared word), and is the cascade's `list` / `count`.  CAP: the buffer per query, a multiple of 16 and at most 256 (the
+// counting selection's buckets are bytes) -- overflow only defers, so it is the caller's to tune (KPX_KNN_GROUP_CAP_SOR / _NORMALS).
+// -DKPX_KNN_GROUP=0 builds a library without the pass (A/B runs through KPX_LIBRARY).
+#ifndef KPX_KNN_GROUP
+#define KPX_KNN_GROUP 1
+#endif
+#ifndef KPX_KNN_GROUP_WAVES
+#define KPX_KNN_GROUP_WAVES 2
+#endif
+template <class Op, int CAP>
+int knn_group_pass(const Grid &g, int k, const Op &op, int64_t q0, int64_t q1, int32_t *fb_list, int32_t *fb_count, hipStream_t st)
+{
+    static_assert(CAP % 16 == 0 && CAP >= 64 && CAP <= 256, "the group buffer: a multiple of 16; the buckets of a row count its keys in bytes");
+    constexpr int W = KPX_KNN_GROUP_WAVES;
+    static const int rc = knn_lds_limit<knn_group_kernel<Op, W>, 96 * 1024>();
+    if (rc) return rc;
+    const int64_t nq = q1 - q0, blocks = cdiv(cdiv(nq, 4), W);
+    ThreadResources &tr = thread_resources();                     // kpx_knn_group_last reads the counter word back
+    tr.knn_group_word = nq > 0 ? fb_count : nullptr; tr.knn_group_given = nq > 0 ? nq : 0; tr.knn_group_stream = st;
+    if (nq <= 0) return KPX_OK;
+    hipLaunchKernelGGL((knn_group_kernel<Op, W>), dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(64 * W),
+                       (size_t)W * 4 * CAP * (sizeof(double) + (Op::kPos ? sizeof(uint32_t) : 0)), st, g.params, g.cell_start, g.sorted_pts, q0, q1, k, CAP,
+                       op, fb_list, fb_count);
     return KPX_OK;
 }
 

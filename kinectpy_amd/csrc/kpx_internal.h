@@ -76,7 +76,10 @@ struct ThreadResources {
     unsigned long long frame_seq = 0;      // kPinFrame's completion word: the value the next wait stores
     unsigned long long icp_generation = 0; // kPinIcpProgress: the last call's tag
     FrameState frame = {};
-    bool counted = false;                  // this thread is in the "threads holding any" count
+    int32_t *knn_group_word = nullptr;     // the last group pass of this thread (kpx_gridknn.h): its counter word in the caller's workspace,
+    int64_t knn_group_given = 0;           // the queries it was given and the stream it ran on -- kpx_knn_group_last
+    hipStream_t knn_group_stream = nullptr;
+    bool counted = false;                 // this thread is in the "threads holding any" count
 
     // the site's block, allocated (and zeroed) at first use; nullptr = the allocation failed (the thread's error is set)
     void *pinned(PinnedSite site, size_t bytes) { return pin[site] ? pin[site] : pinned_alloc(site, bytes); }

@@ -15,6 +15,14 @@
 #include "kpx_morton.h"
 #include "kpx_linalg.h"
 
+// candidates per query the group pass holds (kpx_gridknn.h, knn_group_pass; measured: profiles/r06/exp_knn_group.txt)
+#ifndef KPX_KNN_GROUP_CAP_SOR
+#define KPX_KNN_GROUP_CAP_SOR 256
+#endif
+#ifndef KPX_KNN_GROUP_CAP_NORMALS
+#define KPX_KNN_GROUP_CAP_NORMALS 192
+#endif
+
 namespace kpx {
 
 // ---- grid construction ------------------------------------------------------------------------------
@@ -238,6 +246,7 @@ int grid_build(const float *pts, int64_t n, double target_per_cell, Arena &a, Gr
 // sidx != NULL: avg is indexed by the caller's point index; sidx == NULL: by sorted position relative to q0.
 struct SorOp {
     static constexpr bool kPos = false;
+    static constexpr int kGroupWavesPerSimd = 5, kGroupTrips = 2; // knn_group_kernel: a register budget of 96, trips of 16 candidates fetched together
     using Heap = HeapD;
     const int32_t *sidx;
     int64_t q0;
@@ -277,6 +286,40 @@ struct SorOp {
         sum = wave_sum_down_f64(sum);                                // lane 0
         const double total = sum - (double)(res.cnt - res.kk) * sqrt(res.top);      // ties beyond the k-th slot
         if (lane == 0) avg[sidx ? (int64_t)sidx[s] : s - q0] = res.kk > 0 ? total / (double)res.kk : -1.0;
+    }
+    // the group form (knn_group_kernel): a query per row of 16 lanes, exactly kk selected (no ties beyond the k-th slot)
+    __device__ void row(const RowKnnResult &res, int64_t s, const float *) const
+    {
+        const int j = threadIdx.x & 15, row = (threadIdx.x & 63) >> 4;
+        const uint32_t *w32 = reinterpret_cast<const uint32_t *>(res.vals);
+        // the roots as in wave(): the selected positions are listed by ballot (kk <= k of them), lanes take the roots of 16 listed
+        // positions at a time and store them back negated
+        int listed = 0;                                              // the same in all lanes of the row
+        for (int u = 0; u < res.trips16; ++u) {
+            const int t = 16 * u + j;
+            const bool sel = t < res.m && w32[2 * t + 1] <= res.hi_thr;
+            const unsigned bits = (unsigned)(__builtin_amdgcn_ballot_w64(sel) >> (16 * row)) & 0xFFFFu;
+            const int at = listed + __builtin_popcount(bits & ((1u << j) - 1u));
+            if (sel && at < kKnnRowBuckets / 4) res.list[at] = (uint32_t)t;
+            listed += __builtin_popcount(bits);
+        }
+        wave_lds_fence();
+        for (int i0 = 0; i0 < res.k; i0 += 16) {
+            const int i = i0 + j;
+            if (i < listed) { const int t = (int)res.list[i]; res.vals[t] = -sqrt(res.vals[t]); }
+        }
+        wave_lds_fence();
+        // wave() has lane l add its candidates l, l + 64, ... in turn: accumulator a[q] of lane j is lane j + 16 q of that wave
+        double a[4] = { 0.0, 0.0, 0.0, 0.0 };
+        for (int u0 = 0; u0 < res.trips16; u0 += 4) {
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const int t = 16 * (u0 + qd) + j;
+                if (t < res.m) { const double v = res.vals[t]; if (__double_as_longlong(v) < 0) a[qd] += -v; }
+            }
+        }
+        const double sum = row_sum_down_f64((a[0] + a[2]) + (a[1] + a[3]));      // steps 32 and 16 of wave_sum_down_f64, then the row's
+        if (res.store && j == 0) avg[sidx ? (int64_t)sidx[s] : s - q0] = res.kk > 0 ? sum / (double)res.kk : -1.0;
     }
     __device__ void heap(int64_t s, const HeapD &heap) const
     {
@@ -715,6 +758,7 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
     int32_t *fb_list = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     int32_t *fb_list2 = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     int32_t *fb_list0 = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
+    int32_t *fb_listg = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);      // what the group pass hands on
     // k beyond the LDS heaps (KPX_SOR_LDS_K): the last pass's per-thread heaps live in the workspace
     const KnnHeaps hp = knn_heaps_carve(a, kk, KPX_SOR_LDS_K, false, sor_block_threads(kk));
     if (a.dry) return KPX_OK;
@@ -722,7 +766,7 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
     if (d_avg) avg = d_avg;
     const int32_t *out_idx = full ? g.sorted_idx : nullptr;
     const int64_t nq = q1 - q0;
-    int32_t *fb_count0 = g.spare + 2;                             // cleared by the grid build; words 0 and 1: the cascade's passes
+    int32_t *fb_count0 = g.spare + 2;                             // cleared by the grid build; words 0 and 1: the cascade's passes, word 3: the group pass
     {
         ProfScope prof(KPX_PROF_SOR_KNN, 12.0 * (double)n + 8.0 * (double)n, st);     // read points, write mean distances
         // pass 0: the queries of a cell together (sor_block_kernel<S>: a block per 64 queries, 64 x S candidates at most); what it cannot
@@ -745,6 +789,13 @@ static int sor_impl(const float *pts, int64_t n, int k, double std_ratio, int32_
                                ((size_t)(64 * S * 3) / 2 + (size_t)kBlkWaves * kSorBuckets / 2 + (size_t)kBlkWaves * kbuf) * 8, st, g.params, g.cell_start,
                                g.sorted_pts, out_idx, q0, q1, kk, kbuf, avg, fb_list0, fb_count0);
             list0 = fb_list0; count0 = fb_count0;
+        }
+        // the group pass (knn_group_kernel: four queries per wave) where every query would start at pass 1: it settles the common path and
+        // lists the rest for the passes below (profiles/r06/exp_knn_group.txt)
+        if (KPX_KNN_GROUP && !cell_on && kk <= 32) {
+            rc = knn_group_pass<SorOp, KPX_KNN_GROUP_CAP_SOR>(g, kk, SorOp{ out_idx, q0, avg }, q0, q1, fb_listg, g.spare + 3, st);
+            if (rc) return rc;
+            if (nq > 0) { list0 = fb_listg; count0 = g.spare + 3; }
         }
         // pass 1: one wave per query, 512- or 1024-candidate buffer (small k: smaller buffers, more waves per CU); k beyond half a
         // buffer skips the pass whose buffer cannot hold k candidates plus their surroundings -- the queries go on through the same lists
@@ -802,6 +853,7 @@ __device__ __forceinline__ void moments_finish(const double sums[9], double m, i
 // (heap: normals, heap_alt: covariances).
 struct MomentsOp {
     static constexpr bool kPos = true;
+    static constexpr int kGroupWavesPerSimd = 3, kGroupTrips = 4; // knn_group_kernel: a register budget of 168, trips of 16 candidates fetched together
     using Heap = HeapDI;
     const int32_t *sidx;
     const float *pts;
@@ -826,6 +878,40 @@ struct MomentsOp {
         }
         wave_sum_down_f64x9(c);                                      // lane 0: the tree the xor butterfly left there
         if (lane == 0) {
+            double *o = covbuf + 10 * s;
+#pragma unroll
+            for (int a9 = 0; a9 < 9; ++a9) o[a9] = c[a9];
+            o[9] = (double)res.kk;
+        }
+    }
+    // the group form (knn_group_kernel): exactly kk selected, so the index tie rule is never asked.  An accumulator starts at +0 and
+    // never becomes -0, so a candidate that is not selected adds zeros -- no branch around the loads
+    __device__ void row(const RowKnnResult &res, int64_t s, const float *__restrict__ spts) const
+    {
+        const int j = threadIdx.x & 15;
+        const uint32_t *w32 = reinterpret_cast<const uint32_t *>(res.vals);
+        auto acc = [&](int qd, double a[9]) {                       // lane j + 16 qd of wave(): candidates j + 16 qd, + 64, ... in turn
+#pragma unroll
+            for (int e = 0; e < 9; ++e) a[e] = 0.0;
+#pragma unroll 4
+            for (int t = 16 * qd + j; t < 16 * res.trips16; t += 64) {
+                const bool sel = t < res.m && w32[2 * t + 1] <= res.hi_thr;
+                const float *pp = spts + 3 * (sel ? (int64_t)res.pos[t] : s);
+                const double x = sel ? (double)pp[0] : 0.0, y = sel ? (double)pp[1] : 0.0, z = sel ? (double)pp[2] : 0.0;
+                a[0] += x; a[1] += y; a[2] += z;
+                a[3] += x * x; a[4] += x * y; a[5] += x * z; a[6] += y * y; a[7] += y * z; a[8] += z * z;
+            }
+        };
+        // (a0 + a2) + (a1 + a3): steps 32 and 16 of wave_sum_down_f64x9; at most three sets of nine are live
+        double c[9], b[9], a[9];
+        acc(0, c); acc(2, a);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) c[e] += a[e];
+        acc(1, b); acc(3, a);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) c[e] += b[e] + a[e];
+        row_sum_down_f64x9(c);
+        if (res.store && j == 0) {
             double *o = covbuf + 10 * s;
 #pragma unroll
             for (int a9 = 0; a9 < 9; ++a9) o[a9] = c[a9];
@@ -870,14 +956,24 @@ static int normals_impl(const float *pts, int64_t n, double radius, int max_nn, 
     if (rc) return rc;
     int32_t *fb_list = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);
     double *covbuf = a.get<double>((size_t)(n > 0 ? n : 1) * 10);
+    int32_t *fb_listg = a.get<int32_t>((size_t)(n > 0 ? n : 1) + 1);      // what the group pass hands on
     const KnnHeaps hp = knn_heaps_carve(a, kk, KPX_NORMALS_LDS_NN, true, kk <= 48 ? 128 : 64);
     if (a.dry) return KPX_OK;
     KPX_ARENA_CHECK(a);
     // pass 1: one wave per query, 512- or 1024-candidate buffer; pass 2: the few queries that did not fit, thread-per-query heap walk
     // (max_nn > 512: the wave kernel's 1024-candidate buffer cannot hold a neighbourhood and its surroundings -- every query takes the heap walk)
     const bool wave_pass = kk <= 512;
-    rc = knn_cascade<MomentsOp>(g, kk, MomentsOp{ g.sorted_idx, pts, radius * radius, covbuf, normals, out_cov }, 0, n, nullptr, nullptr,
-                                { knn_wave_pass<MomentsOp, 4>(kk <= 48 ? 512 : 1024, 8192, fb_list, wave_pass) }, g.spare,
+    const MomentsOp op{ g.sorted_idx, pts, radius * radius, covbuf, normals, out_cov };
+    // in front of it the group pass (knn_group_kernel: four queries per wave; counter word 3 of Grid::spare): the wave pass then searches
+    // only what that one listed
+    const int32_t *list0 = nullptr, *count0 = nullptr;
+    if (KPX_KNN_GROUP && kk <= 48 && n > 0) {
+        rc = knn_group_pass<MomentsOp, KPX_KNN_GROUP_CAP_NORMALS>(g, kk, op, 0, n, fb_listg, g.spare + 3, st);
+        if (rc) return rc;
+        list0 = fb_listg; count0 = g.spare + 3;
+    }
+    rc = knn_cascade<MomentsOp>(g, kk, op, 0, n, list0, count0,
+                                { knn_wave_pass<MomentsOp, 4>(kk <= 48 ? 512 : 1024, list0 ? 2048 : 8192, fb_list, wave_pass) }, g.spare,
                                 out_cov ? knn_heap_pass<MomentsOp, true>() : knn_heap_pass<MomentsOp, false>(), hp, st);
     if (rc) return rc;
     const auto eigen_kernel = out_cov ? normals_eigen_kernel<true> : normals_eigen_kernel<false>;
@@ -967,6 +1063,22 @@ KPX_EXPORT int kpx_sor_finish(const double *d_avg_sorted, const int32_t *d_order
     double *avg = d_avg ? d_avg : s.avg;
     hipLaunchKernelGGL(sor_unsort_kernel, dim3((unsigned)(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256))), dim3(256), 0, st, d_avg_sorted, d_order, n, avg);
     return sor_stats_compact(avg, n, std_ratio, s.part, s.counts, keep_idx, d_count, d_stats, st);
+}
+
+// out[0]: the queries the calling thread's last group pass (knn_group_kernel: SOR with k <= 32, normals / covariances with max_nn <= 48) was
+// given, out[1]: the ones it handed on to the wave passes -- read back from the pass's counter word, so valid until the workspace of
+// that call is used again; waits for the call's stream.  {0, 0}: no such pass yet.
+KPX_EXPORT int kpx_knn_group_last(int64_t *out)
+{
+    KPX_REQUIRE(out, "kpx_knn_group_last: null pointer");
+    out[0] = out[1] = 0;
+    const ThreadResources &tr = thread_resources();
+    if (!tr.knn_group_word) return KPX_OK;
+    int32_t handed = 0;
+    KPX_HIP(hipStreamSynchronize(tr.knn_group_stream));
+    KPX_HIP(hipMemcpy(&handed, tr.knn_group_word, sizeof(int32_t), hipMemcpyDeviceToHost));
+    out[0] = tr.knn_group_given; out[1] = handed;
+    return KPX_OK;
 }
 
 KPX_EXPORT size_t kpx_normals_workspace_bytes(int64_t n, int32_t max_nn)

@@ -235,4 +235,87 @@ __device__ __forceinline__ void wave_sum_down_f64x9(double c[9])
 #endif
 }
 
+// ---- the same per ROW of 16 lanes: four independent results per wave ------------------------------------------------------------------
+// Row r = lanes 16 r .. 16 r + 15.  DPP row controls only: a reduction or a scan ends after the four row steps, no swap16 / swap32 and
+// no ds_bpermute.  Same precondition (all 64 lanes active, wave-uniform control flow); other targets take __shfl* of width 16.
+template <class Op> __device__ __forceinline__ unsigned row_reduce_u32(unsigned v, Op op)      // the row's result in every lane of the row
+{
+#if KPX_WAVE_VALU
+    v = op(v, wave_dpp_u32<kDppRowRor + 1>(v, v)); v = op(v, wave_dpp_u32<kDppRowRor + 2>(v, v));
+    v = op(v, wave_dpp_u32<kDppRowRor + 4>(v, v)); v = op(v, wave_dpp_u32<kDppRowRor + 8>(v, v));
+    return v;
+#else
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = op(v, (unsigned)__shfl_xor((int)v, o, 16));
+    return v;
+#endif
+}
+__device__ __forceinline__ int row_sum_i32(int v)
+{
+    return (int)row_reduce_u32((unsigned)v, [](unsigned a, unsigned b) { return a + b; });
+}
+__device__ __forceinline__ unsigned row_min_u32(unsigned v)
+{
+    return row_reduce_u32(v, [](unsigned a, unsigned b) { return a < b ? a : b; });
+}
+__device__ __forceinline__ unsigned row_max_u32(unsigned v)
+{
+    return row_reduce_u32(v, [](unsigned a, unsigned b) { return a > b ? a : b; });
+}
+__device__ __forceinline__ double row_max_f64(double v)                                     // NaN and signed zeros: as wave_max_f64
+{
+#if KPX_WAVE_VALU
+    v = fmax(v, wave_dpp_f64<kDppRowRor + 1>(v)); v = fmax(v, wave_dpp_f64<kDppRowRor + 2>(v));
+    v = fmax(v, wave_dpp_f64<kDppRowRor + 4>(v)); v = fmax(v, wave_dpp_f64<kDppRowRor + 8>(v));
+    return v;
+#else
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 16));
+    return v;
+#endif
+}
+__device__ __forceinline__ int row_incl_scan_i32(int v)
+{
+#if KPX_WAVE_VALU
+    unsigned t = (unsigned)v;
+    t += wave_dpp_u32<kDppRowShr + 1>(0u, (unsigned)v) + wave_dpp_u32<kDppRowShr + 2>(0u, (unsigned)v) + wave_dpp_u32<kDppRowShr + 3>(0u, (unsigned)v);
+    t += wave_dpp_u32<kDppRowShr + 4, 0xF, 0xE>(0u, t);
+    t += wave_dpp_u32<kDppRowShr + 8, 0xF, 0xC>(0u, t);
+    return (int)t;
+#else
+    const int l = threadIdx.x & 15;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) { const int t = __shfl_up(v, o, 16); if (l >= o) v += t; }
+    return v;
+#endif
+}
+// the value of lane `lane_in_row` (0 .. 15, the same in all lanes of a row; the rows may name different lanes) in every lane of the row
+__device__ __forceinline__ unsigned row_bcast(unsigned v, int lane_in_row)
+{
+#if KPX_WAVE_VALU
+    return row_reduce_u32(((int)(threadIdx.x & 15) == lane_in_row) ? v : 0u, [](unsigned a, unsigned b) { return a | b; });
+#else
+    return (unsigned)__shfl((int)v, lane_in_row, 16);
+#endif
+}
+__device__ __forceinline__ int row_bcast(int v, int lane_in_row) { return (int)row_bcast((unsigned)v, lane_in_row); }
+// The last four steps of wave_sum_down_f64, valid in lane 0 of every row: at step o lane i < o of the row adds the value of lane i + o.
+__device__ __forceinline__ double row_sum_down_f64(double v)
+{
+#if KPX_WAVE_VALU
+    v += wave_dpp_f64<kDppRowShl + 8>(v); v += wave_dpp_f64<kDppRowShl + 4>(v);
+    v += wave_dpp_f64<kDppRowShl + 2>(v); v += wave_dpp_f64<kDppRowShl + 1>(v);
+    return v;
+#else
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_down(v, o, 16);
+    return v;
+#endif
+}
+__device__ __forceinline__ void row_sum_down_f64x9(double c[9])
+{
+#pragma unroll
+    for (int q = 0; q < 9; ++q) c[q] = row_sum_down_f64(c[q]);
+}
+
 }  // namespace kpx

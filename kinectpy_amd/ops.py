@@ -323,6 +323,14 @@ def sor(pts, nb_neighbors, std_ratio, want_avg=False):
     return idx[:k], stats, (avg[:n] if avg is not None else None)
 
 
+def knn_group_last():
+    """-> (queries given to, queries handed on by) the calling thread's last group pass of the neighbour search (sor* with nb_neighbors
+    <= 32, estimate_normals / estimate_covariances with max_nn <= 48); valid until that call's workspace is used again."""
+    out = np.zeros(2, dtype=np.int64)
+    L.check(L.load().kpx_knn_group_last(out.ctypes.data_as(C.c_void_p)))
+    return int(out[0]), int(out[1])
+
+
 def sor_select(pts, attr, nb_neighbors, std_ratio):
     """a8 with both results of `cl, ind = remove_statistical_outlier(...)`: -> kept points f32 (K,3), kept rows of `attr` (K,3) | None,
     keep_idx i32 (K), stats f64 (3) -- one pass, no count read-back between filter and selection (kpx_sor_select)."""
