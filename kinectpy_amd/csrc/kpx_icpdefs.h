@@ -16,7 +16,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #ifndef KPX_ICP_WAVES
 #define KPX_ICP_WAVES 4
 #endif
-constexpr int kIWaves = KPX_ICP_WAVES;       // waves (16-row tiles) per block: a block lives as long as its slowest wave
+constexpr int kIWaves = KPX_ICP_WAVES;       // waves (16-row tiles) per block: a block lives as long as its slowest wave, but a wave of
+                                             // the block form ends with its own rows (icp_iter_body: the last to arrive closes the block)
 constexpr int kIThreads = kIWaves * 64;
 constexpr int kRT = 2;                       // 16-row tiles per wave (the sweep below is written for 2)
 constexpr int kWaves = 4;

@@ -14,7 +14,8 @@ namespace kpx {
 // Block = 4 waves x 16 sorted rows.  Prologue: lanes 0..15 of a wave transform their row, seed it and bound it
 // with last iteration's partner (clamped to the correspondence distance); the wave sweeps (sweep_wave); lanes 0..15
 // then form the chosen pair's direct distance (AC3) and the row's contribution to the update sums, which are added
-// in a fixed order per block and added to the exact fixed-point accumulators; icp_solve_fixed_kernel performs the
+// in a fixed order per block and added to the exact fixed-point accumulators (a wave ends once its rows' terms are staged; the
+// block's last wave to arrive adds them, see s_arrive in icp_iter_body); icp_solve_fixed_kernel performs the
 // update step (kpx_icp).  Running the update redundantly in the prologue of the next launch (IcpFuse below) puts the serial
 // 6x6 / eigen algebra (~5-8 us) in front of every block's sweep against 5.7 us + 1.9 us for the solve kernel and its
 // boundary: for one large registration (100k x 100k: five rounds of blocks per launch) it was 20 % slower, so kpx_icp
@@ -45,7 +46,8 @@ constexpr unsigned long long kChainEmpty = 0xFFF8C0DEC0DEC0DEull;
 constexpr int kAccSet = kAccCopies * kAcc * kFixedWords;
 // Phase clock of the iteration kernel (while the profiler is armed): thread 0 of every block stores 100 MHz wall-clock stamps in
 // its own row of g_icp_stamp -- [0] block start, [1] after the update prologue, [2] after row preparation, [3] after the culled
-// sweep, [4] after the pair epilogue, [5] block end.  Plain stores to private slots: the clock does not disturb what it times.
+// sweep, [4] after the pair epilogue, [5] block end ([4] and [5] of the block form: lane 0 of the wave that closes the block, so [4] is
+// the arrival of the block's last wave).  Plain stores to private slots: the clock does not disturb what it times.
 // The rows of the LAST launch are read by kpx_prof_icp_phases.
 constexpr int kStampBlocks = 4096;
 __device__ unsigned long long g_icp_stamp[kStampBlocks][8];
@@ -69,6 +71,21 @@ __device__ __forceinline__ void phase_tick(unsigned long long *__restrict__ arme
     if (!armed || threadIdx.x || bid >= kStampBlocks) return;
     __builtin_nontemporal_store(wall_clock64(), &g_icp_stamp[bid][slot]);
 }
+// ... by lane 0 of whichever wave is at that point (the block-end stamps of the block form: the wave that closes the block)
+__device__ __forceinline__ void phase_tick_wave(unsigned long long *__restrict__ armed, int slot, unsigned bid, int lane)
+{
+    if (!armed || lane || bid >= kStampBlocks) return;
+    __builtin_nontemporal_store(wall_clock64(), &g_icp_stamp[bid][slot]);
+}
+// Rows of the sums' staging array `sh` in the block form: only the slots that are live in SOME mode of the culled engine have one,
+// by a dense index -- slots 0..16 as they are, the plane slots 17..43 moved down onto the point slots 2..16 they never share a launch
+// with.  In either mode the live slots then are the dense rows 0 .. acc_dense_live - 1, in slot order.
+constexpr int kAccDense = 2 + (kAcc - 17);    // 29 rows instead of 44
+static_assert(kAccDense >= 17, "the point-to-point slots 0..16 fit");
+__host__ __device__ constexpr int acc_dense(int slot) { return slot < 17 ? slot : slot - 15; }
+__host__ __device__ constexpr int acc_dense_live(bool plane) { return plane ? kAccDense : 17; }
+__host__ __device__ constexpr int acc_dense_slot(bool plane, int row) { return row < 2 ? row : row - 2 + acc_lo(plane); }
+static_assert(acc_dense(acc_dense_slot(true, 28)) == 28 && acc_dense(acc_dense_slot(false, 16)) == 16 && acc_dense_slot(true, 2) == 17, "dense rows <-> slots");
 // Certificates: rows whose partner provably cannot change are not searched again.
 // A sweep knows more than the winner: every column it multiplied gives D, every box it culled was farther than the row's culling
 // bound.  L = sqrt(min(final culling bound, smallest D - 1 among the multiplied columns OTHER than the winner)) is therefore a lower
@@ -324,12 +341,27 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     __shared__ double s_light[kIWaves];
     const int nacc = mode == 1 ? kAcc : 17;
     if (tile_visits && tix == 0 && bid < kStampBlocks) { g_icp_stamp[bid][7] = skip ? 1ull : 0ull; g_icp_stamp[bid][6] = (unsigned long long)nblocks; }
+    // The block form (!PERSIST; icp_iter_kernel, icp_iter_batch_kernel): a wave ENDS with its 16 rows.  It stages their contributions
+    // (sh, s_cnt, s_light) and adds 1 to s_arrive with a returning LDS add; the wave whose add returns kIWaves - 1 -- the last to
+    // arrive -- closes the block alone, on its lane number: the tile trees and the exact adds, the LightSkip key, the ticket and, as
+    // winner, the update.  The others return there and give their registers and wave slot back while the block's slowest wave still
+    // sweeps; nobody waits at a barrier.  The LDS operations of a CU are performed in issue order: behind its own returning add the
+    // closing wave sees everything the others staged in front of theirs (wave 0's copy of the state in s_state as well, which is in
+    // front of the barrier below).  No barrier may follow the arrival point: the closing wave runs straight-line code.  The uniform
+    // early ways out follow the same rule: every wave but one returns, one draws the ticket.
+    // The one-launch chain (PERSIST) keeps its four waves and its barriers: its blocks iterate, nothing may leave.
+    __shared__ unsigned s_arrive;
     do {
-    if (skip) break;
+    if (skip) {
+        if (!PERSIST && wave != 0) return;
+        break;
+    }
     __shared__ int32_t lists[kIWaves][kLScratch];
     __shared__ double rowd[kIWaves][16][kRowStride]; // s_x, s_y, s_z, (the sweep's row bound), K, bound / result value
     __shared__ float rowf[kIWaves][16][kRowFStride]; // float32 mirror of the rows for the sweep's culling tests
-    __shared__ double sh[kAcc][kIRows + 1];
+    constexpr int kShRows = PERSIST ? kAcc : kAccDense;
+    __shared__ double sh[kShRows][kIRows + 1];               // (block form: a row per dense index, acc_dense)
+    auto sh_row = [](int slot) { return PERSIST ? slot : acc_dense(slot); };
     if (tile_visits && tix == 0 && bid < kStampBlocks) {     // only launches that sweep stamp (not the converged / closing ones)
         g_icp_stamp[bid][0] = t_block_start;
         g_icp_stamp[bid][6] = (unsigned long long)nblocks;
@@ -337,7 +369,9 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     phase_tick(tile_visits, 1, bid);
     // s_thist was staged by all threads of the block and is read by the rows of every wave (until this barrier was added the
     // per-launch form relied on the waves of a block running in step: a row could read an entry before another wave had written it)
-    if (certs && (k > 0 || PERSIST)) __syncthreads();
+    // (block form: the arrival counter is cleared behind the same barrier, which all waves pass before any of them can arrive)
+    if (!PERSIST && kIWaves > 1 && tix == 0) s_arrive = 0u;
+    if ((!PERSIST && kIWaves > 1) || (certs && (k > 0 || PERSIST))) __syncthreads();
     if (PERSIST && fuse.stamp && tix == 0) {
         const unsigned long long t = wall_clock64();
         if (bid == 0) fuse.stamp[0] = t;
@@ -471,8 +505,11 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     const int lane_e = lane_p, wave_e = wave_p;
     if (lane_e < 16) {
         const int col = wave_e * 16 + lane_e;
-        sh[0][col] = 0.0; sh[1][col] = 0.0;                  // the live slots: 0, 1 and [acc_lo, acc_hi)
-        for (int a = acc_lo(mode == 1); a < nacc; ++a) sh[a][col] = 0.0;
+        if (PERSIST) {
+            sh[0][col] = 0.0; sh[1][col] = 0.0;              // the live slots: 0, 1 and [acc_lo, acc_hi)
+            for (int a = acc_lo(mode == 1); a < nacc; ++a) sh[a][col] = 0.0;
+        } else
+            for (int a = 0; a < acc_dense_live(mode == 1); ++a) sh[a][col] = 0.0;
         if (row_base_p + lane_e <= last) {
             const int32_t bj = rowi[wave_e][lane_e][0];
             const int64_t i = rowi[wave_e][lane_e][1];
@@ -513,10 +550,50 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
                 const double t[3] = { (double)tf[0], (double)tf[1], (double)tf[2] };
                 const double d2 = pair_d2(s, t);
                 if (d2_cur) d2_cur[i] = d2;
-                if (d2 < max_d2) pair_terms(s, t, d2, mode != 1, mode == 1, nf, [&](int slot, double v) { sh[slot][col] = v; });
+                if (d2 < max_d2) pair_terms(s, t, d2, mode != 1, mode == 1, nf, [&](int slot, double v) { sh[sh_row(slot)][col] = v; });
             }
         }
     }
+    if constexpr (!PERSIST) {
+        if (kIWaves > 1) {
+            wave_lds_fence();
+            unsigned arrived = 0u;
+            if (lane_e == 0) arrived = __hip_atomic_fetch_add(&s_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (__builtin_amdgcn_readfirstlane((int)arrived) != kIWaves - 1) return;
+            wave_lds_fence();
+        }
+        phase_tick_wave(tile_visits, 4, bid, lane_e);
+        // The sums' contract (round 5) as stated below for the chain form; lane = dense row: the mode's live slots in slot order
+        const bool plane = mode == 1;
+        if (lane_e < acc_dense_live(plane)) {
+            const int slot_e = acc_dense_slot(plane, lane_e);
+            unsigned long long lo = 0ull, hi = 0ull;
+#pragma unroll
+            for (int t = 0; t < kIWaves; ++t) {
+                unsigned long long l, h;
+                fixed_split(tile_tree16(&sh[lane_e][16 * t]), l, h);
+                fixed_accumulate(lo, hi, l, h);
+            }
+            unsigned long long *slot = acc + (((int64_t)(bid & (kAccCopies - 1)) * kAcc + slot_e) * kFixedWords);
+            if (fuse.ticket) fixed_add_words_performed(slot, lo, hi); else fixed_add_words(slot, lo, hi);
+        } else if (fuse.ticket && lane_e == nacc) {
+            int cnt = 0;
+#pragma unroll
+            for (int wv = 0; wv < kIWaves; ++wv) cnt += s_cnt[wv];
+            if (cnt) {
+                const unsigned long long back = __hip_atomic_fetch_add(fuse.ticket + kSearchedWord + (bid & 7u), (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("" ::"v"(back));
+            }
+        }
+        if (fuse.light_key && lane_e == 63) {
+            double g2 = INFINITY;
+            bool light = true;
+#pragma unroll
+            for (int wv = 0; wv < kIWaves; ++wv) { light = light && s_light[wv] >= 0.0; g2 = fmin(g2, s_light[wv]); }
+            fuse.light_key[bid] = light ? st->motion + sqrt(g2) * (1.0 - 1e-9) : 0.0;
+        }
+        phase_tick_wave(tile_visits, 5, bid, lane_e);
+    } else {
     __syncthreads();
     phase_tick(tile_visits, 4, bid);
     // (the thread number re-derived behind the sweep, like the lane state of the pair epilogue: the accumulator slot's address, a 64-bit
@@ -537,14 +614,6 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
         }
         unsigned long long *slot = acc + (((int64_t)(bid & (kAccCopies - 1)) * kAcc + tix_e) * kFixedWords);
         if (fuse.ticket) fixed_add_words_performed(slot, lo, hi); else fixed_add_words(slot, lo, hi);
-    } else if (!PERSIST && fuse.ticket && tix_e == nacc) {
-        int cnt = 0;
-#pragma unroll
-        for (int wv = 0; wv < kIWaves; ++wv) cnt += s_cnt[wv];
-        if (cnt) {
-            const unsigned long long back = __hip_atomic_fetch_add(fuse.ticket + kSearchedWord + (bid & 7u), (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("" ::"v"(back));
-        }
     }
     if (fuse.light_key && tix == kIThreads - 1) {      // (after the barrier above: s_light is complete)
         double g2 = INFINITY;
@@ -552,10 +621,36 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
 #pragma unroll
         for (int wv = 0; wv < kIWaves; ++wv) { light = light && s_light[wv] >= 0.0; g2 = fmin(g2, s_light[wv]); }
         const double nk = light ? st->motion + sqrt(g2) * (1.0 - 1e-9) : 0.0;
-        if (PERSIST) s_key = nk; else fuse.light_key[bid] = nk;
+        s_key = nk;
     }
     phase_tick(tile_visits, 5, bid);
+    }
     } while (false);
+    if constexpr (!PERSIST) {
+        // One wave is left: the one that closed the block, or wave 0 of a block LightSkip left out.  "The last block finishes the job" as
+        // described below, a wave in place of the block: the wave waits for its adds, draws the ticket, and as winner takes the totals
+        // and performs the update -- the instantiation and the sequence of icp_rows_kernel (kpx_icprows.h).
+        if (!fuse.ticket) return;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_lds_fence();
+        const int lane_w = opaque_i((int)(threadIdx.x & 63));
+        unsigned tk = 0u;
+        if (lane_w == 0) tk = (unsigned)__hip_atomic_fetch_add(fuse.ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tk = (unsigned)__builtin_amdgcn_readfirstlane((int)tk);
+        wave_lds_fence();
+        if (tk != nblocks - 1u) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the winner only: one per registration and launch
+        const unsigned long long n_searched = winner_take<64, true>(acc, fuse.ticket, mode == 1, s_sums, lane_w);
+        __shared__ FinishScratch s_tail;
+        // (t2max again from the target's box, behind an opaque move of its address: a double every lane would otherwise carry across the sweep)
+        const double *tbbox_w = tbbox;
+        asm volatile("" : "+s"(tbbox_w));
+        const double t2max_w = target_t2max(tbbox_w);
+        icp_finish_wave(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, &s_state, fuse.result, s_tail, lane_w,
+                        LightSkip{ fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w });
+        wave_lds_fence();
+        winner_publish(const_cast<IcpState *>(st), &s_state, fuse.cert ? fuse.thist : (double *)nullptr, k, fuse.progress, fuse.tag, n_searched, n, lane_w);
+    } else {
     if (PERSIST && fuse.stamp && tix == 0) {
         const unsigned long long t = wall_clock64();
         if (bid == 0) fuse.stamp[3] = t;
@@ -588,14 +683,14 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the winner only: one per registration and launch
     // (the winner's thread number behind an opaque move as well: addresses derived from it are then formed here, not in front of the sweep)
     const int tix_w = opaque_i((int)threadIdx.x);
-    const unsigned long long n_searched = winner_take<kIThreads, !PERSIST>(acc, fuse.ticket, mode == 1, s_sums, tix_w);
-    if (PERSIST) chain_tick(fuse.stamp, 7, tix == 0);         // (the clearing stores are issued, not waited for)
+    winner_take<kIThreads, false>(acc, fuse.ticket, mode == 1, s_sums, tix_w);
+    chain_tick(fuse.stamp, 7, tix == 0);         // (the clearing stores are issued, not waited for)
     // PERSIST: the blocks that see the next record add to these accumulators at once, so every clearing store (and the ticket's) must
     // have been performed before the record is published: each wave drains its stores, the block meets at a barrier (wave 0 after the
     // update algebra, which hides the drain), then wave 0 publishes
-    if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (wave != 0) {
-        if (PERSIST) __syncthreads();
+        __syncthreads();
         return;
     }
     __shared__ FinishScratch s_tail;
@@ -603,17 +698,12 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
     const double *tbbox_w = tbbox;
     asm volatile("" : "+s"(tbbox_w));
     const double t2max_w = target_t2max(tbbox_w);
-    IcpState *stw = const_cast<IcpState *>(st);
     IcpState *work = &s_state;
-    if (PERSIST)
-        icp_finish_wave_call(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, work, (double *)nullptr, &s_tail, lane,
-                             fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w, fuse.stamp ? fuse.stamp + 32 : (unsigned long long *)nullptr);
-    else
-        icp_finish_wave(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, work, fuse.result, s_tail, lane,
-                        LightSkip{ fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w });
+    icp_finish_wave_call(s_sums, n, mode, k, fuse.max_iter, fuse.rel_fit, fuse.rel_rmse, work, (double *)nullptr, &s_tail, lane,
+                         fuse.light_key ? fuse.sbbox : (const double *)nullptr, max_d2, t2max_w, fuse.stamp ? fuse.stamp + 32 : (unsigned long long *)nullptr);
     wave_lds_fence();
-    if (PERSIST) chain_tick(fuse.stamp, 8, lane == 0);
-    if (PERSIST) {
+    chain_tick(fuse.stamp, 8, lane == 0);
+    {
         static_assert(sizeof(IcpState) == kChainWords * sizeof(double), "record layout");
         __syncthreads();
         if (lane < kChainWords)
@@ -629,9 +719,8 @@ __device__ __forceinline__ void icp_iter_body(const unsigned bid, const unsigned
             __hip_atomic_store(fuse.progress, fuse.tag | (1ull << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         chain_tick(fuse.stamp, 9, lane == 0);
         if (fuse.stamp && lane == 0) fuse.stamp[12] = __builtin_amdgcn_s_memtime();      // shader clock (against [9]: the clock the chip runs the chain at)
-        return;
     }
-    winner_publish(stw, work, fuse.cert ? fuse.thist : (double *)nullptr, k, fuse.progress, fuse.tag, n_searched, n, lane);
+    }
 }
 
 
